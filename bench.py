@@ -54,6 +54,27 @@ def cpu_baseline(scene, cams, P, W, H):
                       f"(OpenMP, fp32), {dt:.2f} s"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, P, seed=0):
+    """write `arrays` (name -> host float32 array) as out_dir/<name>.npy, at most DUMP_BUDGET_BYTES in all: past the budget, every
+    per-Gaussian array (first dimension P) keeps the same fixed, seeded, sorted sample of its rows; the others are written whole"""
+    os.makedirs(out_dir, exist_ok=True)
+    per_row = sum(a[0].nbytes for a in arrays.values() if a.ndim and a.shape[0] == P)
+    rest = sum(a.nbytes for a in arrays.values() if not (a.ndim and a.shape[0] == P))
+    budget = DUMP_BUDGET_BYTES - 4096 * len(arrays)         # (room for every file's .npy header)
+    rows = None
+    if per_row and rest + per_row * P > budget:
+        n = max(1, (budget - rest) // per_row)
+        rows = np.sort(np.random.default_rng(seed).choice(P, n, replace=False))
+    for name, a in arrays.items():
+        if rows is not None and a.ndim and a.shape[0] == P:
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": out_dir, "arrays": sorted(arrays), "rows_sampled": None if rows is None else int(rows.size)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -80,7 +101,13 @@ def main():
     ap.add_argument("--slices", type=int, default=4)
     ap.add_argument("--mode", choices=("views", "scenes"), default="views",
                     help="views: view-parallel weak scaling (default, the BASELINE metric); scenes: 6 scene variants dealt over the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: the loss and the gradients of the five "
+                         "parameters and of every view's screen-space points) as DIR/<name>.npy, float32, at most 64 MB in all "
+                         "(past that, a fixed seeded sample of the Gaussians' rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as FRESH children (this process has not touched the GPU: importing
@@ -280,6 +307,9 @@ def main():
         out_ = None
         for w_ in loads:
             out_ = w_.step()
+            # (--dump-outputs: the step's loss kept WITHOUT its autograd graph -- a live graph would keep the step's AccumulateGrad
+            #  nodes, and their stream, into the next step and into the hipGraph recording)
+            w_.loss = out_.detach()
         return out_
 
     def sync():
@@ -397,6 +427,21 @@ def main():
         graphed.step() if graphed is not None else step()
     sync()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the LAST timed step returned, copied to the host before anything else runs on the workload: the replay's static outputs
+        # (graph mode) or the eager step's loss and .grad tensors, one set per scene this rank holds
+        if graphed is not None:
+            results = {"": graphed.rs.outs[graphed.rs.last()][:2]}
+        else:
+            results = {(f"scene{rank + world * j}_" if scene_mode else ""): (w_.loss, w_.grads()) for j, w_ in enumerate(loads)}
+        arrays = {}
+        for prefix, (loss_, grads_) in results.items():
+            arrays[prefix + "loss"] = loss_.detach().float().cpu().numpy().reshape(1)
+            for k, g_ in grads_.items():
+                if g_ is not None:
+                    arrays[prefix + "grad_" + k.replace("[", "_").replace("]", "")] = g_.detach().float().cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, arrays, P)
     replay_check = None
     eager_ms_per_step = None
     if graphed is not None:
@@ -715,6 +760,8 @@ def main():
         "speculation": speculation,
         "collective": collective,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     # the first half of BASELINE.json's metric ("train-step ms"): BASELINE configs[2], measured by bench_train.py (untimed
     # here, its own timed region; 1 GPU only).  Auxiliary field -- `value` stays the rasterizer fwd+bwd throughput.
     if rank == 0 and world == 1 and not scene_mode and not args.no_train_step and (P, W, V) == (100_000, 800, 4):

@@ -28,6 +28,8 @@ What it pins; every fixture holds inputs + the referenc
   losses.npz      utils.loss_utils.l1_loss / ssim, train_utils.image_losses / regularization, masked and unmasked
   gnn128.npz      EncodeProcessDecode at latent 128 on a tall graph, closed-form weights: forward + gradients (gen_gnn128)
   render_wiring.npz  gaussian_renderer.render itself with a RECORDING stand-in for the rasterizer extension (gen_render_wiring)
+  render_wiring_objects.npz  what the reference's MultiGaussianMesh / Camera of render_wiring.npz return to render()
+                  (gen_render_wiring_objects)
 """
 import inspect
 import os
@@ -1049,6 +1051,29 @@ def gen_render_wiring():
     np.savez_compressed(os.path.join(OUT, "render_wiring.npz"), **out)
 
 
+def gen_render_wiring_objects():
+    """the reference's OWN MultiGaussianMesh / Camera objects of render_wiring.npz, as render() sees them: every attribute it reads
+    and every getter it calls, with the getters' results for the arguments the wiring cases pass (the rest pose, the simulator's
+    deformed pose at the camera's time, scaling modifiers 1.0 / 1.7).  tests/test_render_wiring_cpu.py replays them to the BUILD's
+    render(), so that the drop-in check runs without the reference."""
+    install_mesh_shims()
+    install_roma_scipy()
+    with cuda_calls_as_cpu():
+        from scene_reconstruction.cameras import Camera
+        from scene_reconstruction.gaussian_mesh import MultiGaussianMesh
+        d = render_wiring_scene()
+        pc, cam, sim = render_wiring_objects(d, MultiGaussianMesh, Camera)
+        out = {f"cam.{a}": npy(getattr(cam, a)) if torch.is_tensor(getattr(cam, a)) else np.asarray(getattr(cam, a)) for a in
+               ("image_height", "image_width", "FoVx", "FoVy", "time", "world_view_transform", "full_proj_transform", "camera_center")}
+        vd = sim(time_vector=torch.tensor(cam.time).repeat(pc.mesh.pos.shape[0], 1))
+        out.update({"pc.active_sh_degree": np.asarray(pc.active_sh_degree), "pc.mesh.pos": npy(pc.mesh.pos),
+                    "pc.get_opacity": npy(pc.get_opacity), "pc.get_scaling": npy(pc.get_scaling), "pc.get_features": npy(pc.get_features),
+                    "pc.get_covariance.1.0": npy(pc.get_covariance(1.0)), "pc.get_covariance.1.7": npy(pc.get_covariance(1.7)),
+                    "pc.get_xyz.rest": npy(pc.get_xyz()), "pc.get_rotation.rest": npy(pc.get_rotation()), "deformed": npy(vd),
+                    "pc.get_xyz.deformed": npy(pc.get_xyz(vd)), "pc.get_rotation.deformed": npy(pc.get_rotation(vd))})
+    np.savez_compressed(os.path.join(OUT, "render_wiring_objects.npz"), **out)
+
+
 def gen_losses():
     """utils.loss_utils.l1_loss / ssim (:20-70; `lpips` -- imported at module level, never called here -- is an empty module)
     and scene_reconstruction.train_utils.image_losses / regularization (:50-102), whose two function bodies are exec'd from
@@ -1143,7 +1168,7 @@ if __name__ == "__main__":
     assert os.path.isdir(REF), "golden vectors can only be generated where /root/reference exists"
     only = sys.argv[1:]          # e.g. `python make_golden.py simulator`: regenerate the named fixtures only
     for name in ("camera", "sh", "misc", "normalizer", "gnn", "simulator", "densify", "scene_io", "meshsim", "mesh_transform", "losses",
-                 "render_wiring", "gnn128", "vertice_rotation", "sim128", "refine"):
+                 "render_wiring", "render_wiring_objects", "gnn128", "vertice_rotation", "sim128", "refine"):
         if not only or name in only:
             globals()["gen_" + name]()
     for f in sorted(os.listdir(OUT)):
