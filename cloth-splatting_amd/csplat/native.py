@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CSPLAT_LIB=<path>: load another build of the library (same-box A/B of kernel variants: tools/ab_libs.sh) -- the shipped file is never
 # overwritten by an experiment
 LIB_PATH = os.environ.get("CSPLAT_LIB") or os.path.join(_HERE, "libcsplat.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -32,6 +32,7 @@ EXPORTS = {
     "csplat_binning_bytes": (_sz, [_i64, _i, _i]),
     "csplat_temp_bytes": (_sz, [_i, _i64, _i, _i]),
     "csplat_backward_scratch_bytes": (_sz, [_i, _i64]),
+    "csplat_backward_depth_scratch_bytes": (_sz, [_i, _i64, _i, _i]),
     "csplat_geom_layout": (_i, [_i, C.POINTER(_sz)]),
     "csplat_binning_layout": (_i, [_i64, _i, _i, C.POINTER(_sz)]),
     "csplat_binning_fields": (_i, [_i64, _i, _i, C.POINTER(_sz)]),
@@ -52,6 +53,8 @@ EXPORTS = {
     "csplat_backward_slice_rows": (_i, [_i, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
     "csplat_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_backward_depth": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csplat_dist2": (_i, [_vp, _i, _vp, _vp]),
     "csplat_dist2_temp_bytes": (_sz, [_i]),
     "csplat_dist2_ws": (_i, [_vp, _i, _vp, _vp, _vp]),
@@ -335,7 +338,7 @@ class CsplatView(C.Structure):
                 [("num_rendered", _i), ("layout_rendered", _i)] + [(n, _vp) for n in ("geom", "binning", "image", "dL_dpix", "scratch")] +
                 [("accmask", C.c_uint)] +
                 [(n, _vp) for n in ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D",
-                                    "dL_dsh", "dL_dscale", "dL_drot")] + [("busy_tiles", _i), ("valid", _vp)])
+                                    "dL_dsh", "dL_dscale", "dL_drot")] + [("busy_tiles", _i), ("valid", _vp), ("dL_ddepth", _vp)])
 
 
 ACC_OPACITY, ACC_COLOR, ACC_MEAN3D, ACC_COV3D, ACC_SH, ACC_SCALE, ACC_ROT = 1, 2, 4, 8, 16, 32, 64
@@ -374,7 +377,7 @@ def group_by_key(keys, n_keys):
 
 
 PROF_CLASSES = ["K1_preprocess", "K2_scan", "K3_emit_keys", "K4_radix_sort", "K5_tile_ranges", "K6_render_fwd",
-                "K7_render_bwd", "K8_preprocess_bwd", "K9_dist2", "GNN"]
+                "K7_render_bwd", "K8_preprocess_bwd", "K9_dist2", "GNN", "K7_depth_partials", "K7_depth_bwd", "K8_depth_bwd"]
 
 
 def prof_enable(classes=()):

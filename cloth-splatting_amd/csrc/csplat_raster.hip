@@ -19,6 +19,7 @@
 #include "csplat_common.h"
 
 #include <atomic>
+#include <cstring>
 #include <chrono>
 #include <mutex>
 
@@ -1756,7 +1757,11 @@ __device__ __forceinline__ void rows_scan_add(float g, float Sin, float &Sr, flo
 #define CSPLAT_K7X 0
 #endif
 constexpr int RING7 = SEG;     // a segment's survivors of one block, padded to a multiple of four: at most SEG
-template <bool DET>
+// DEPTH (the depth-gradient path, k_depth_composite_bwd_views; never the default launches): the pixel's depth gradient g = dL_ddepth[pix]
+// adds g (T_i z_i - D_behind_i / (1 - alpha_i)) to dL/dalpha, with D_behind_i = (sum of the partials dpart of this and the later segments
+// of the tile, k_depth_bwd_partials) - (the in-segment prefix of T alpha z through entry i), and the block's sum of g T_i alpha_i goes to
+// record slot 9 (dL/dz of the Gaussian, K8).  With DEPTH = false every added line below is compiled out.
+template <bool DET, bool DEPTH = false>
 __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int gx, const int2 *__restrict__ ranges,
                                                    const uint32_t *__restrict__ ids_sorted,
                                                    const unsigned long long *__restrict__ bbits, const float4 *__restrict__ recA,
@@ -1766,11 +1771,14 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
                                                    const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib,
                                                    const float *__restrict__ out_color, const float *__restrict__ dL_dpix,
                                                    float *__restrict__ acc, float *__restrict__ det,
-                                                   unsigned long long *stamp = nullptr, int wg = (int)blockIdx.x) {
+                                                   unsigned long long *stamp = nullptr, int wg = (int)blockIdx.x,
+                                                   const float *__restrict__ dL_ddepth = nullptr, const float *__restrict__ dpart = nullptr) {
+    constexpr int DS = DEPTH ? 10 : 9;                              // floats per stored (entry, block) record in the DET mode
     __shared__ int s_ring[4][RING7];
     __shared__ float4 s_ra[4][64], s_rb[4][64];                     // one batch of 64 survivors' records per wave (see `stage`)
     __shared__ float s_rc[4][64];
     __shared__ uint32_t s_rid[DET ? 1 : 4][DET ? 1 : 64];
+    __shared__ float s_rz[DEPTH ? 4 : 1][DEPTH ? 64 : 1];          // (DEPTH) the survivors' view-space depths
     // in-kernel stamps (csplat_debug_stamps; tools/k7_stamps.py): wave 0 of every workgroup leaves s_memtime at the phase boundaries
     unsigned long long *my_stamp = stamp ? stamp + ((size_t)blockIdx.y * gridDim.x + (size_t)wg) * 12 : nullptr;
     auto mark = [&](int k) {
@@ -1833,6 +1841,14 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
         }
         ck = ckpt[(size_t)slot * 256 + blk * 16 + l16];
     }
+    float gz = 0.f, Dsuf = 0.f;         // (DEPTH) the pixel's dL/ddepth; T alpha z summed over this and the tile's later segments
+    if constexpr (DEPTH) {
+        if (live && dL_ddepth) {
+            if (inside) gz = dL_ddepth[pix];
+            const int s_end = seg_offset[tile + 1];
+            for (int s2 = slot; s2 < s_end; s2++) Dsuf += dpart[(size_t)s2 * 256 + blk * 16 + l16];
+        }
+    }
     // the wave's survivor list: list positions of the set bits, in order, padded with -1 to a multiple of four (wave-private LDS)
     int *ring = s_ring[w];
     int total = 0;
@@ -1873,10 +1889,12 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
             if (!DET) id = ids_sorted[pos >= 0 ? rx + (uint32_t)pos : rx];
             ra[lane] = A; rb[lane] = B; rc[lane] = C;
             if (!DET) rid[lane] = id;
+            if constexpr (DEPTH) s_rz[w][lane] = reinterpret_cast<const float *>(recC)[2 * (size_t)ri + 1];
         };
         stage(0);
         const float OD = oc0 * dp0 + oc1 * dp1 + oc2 * dp2;
         float T = 1.f, S = 0.f;
+        float SD = 0.f;                 // (DEPTH) in-segment running sum of T alpha z
         if (ncontrib > seg_lo) {
             T = ck.x;
             S = ck.y * dp0 + ck.z * dp1 + ck.w * dp2;
@@ -1890,6 +1908,7 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
         int red_t_ = -1;
 #pragma unroll
         for (int q = 0; q < 16; q++) red_t_ = l16 == q ? RED_T[q] : red_t_;
+        if constexpr (DEPTH) red_t_ = l16 == 5 ? 9 : red_t_;          // (lane 5 of a row carries the depth sum: slot 9, same 64-byte record)
         const bool red_active = red_t_ >= 0;
         const int red_t = red_active ? red_t_ : 0;
         int base = 0;                   // first survivor of the batch in the strip
@@ -1900,6 +1919,7 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
             t.pos = ring[base + sl];
             t.a = ra[sl]; t.b = rb[sl]; t.c.x = rc[sl];
             if (!DET) t.id = rid[sl];
+            if constexpr (DEPTH) t.c.y = s_rz[w][sl];
         };
         // N groups at once, statement by statement: a group is one dependent chain of ~110 vector instructions (~10 cycles from one to the
         // next: ~1,200 cycles a group for a wave on its own, tools/k7_stamps.py -- the same with the atomics removed); groups k and k + 1
@@ -1925,9 +1945,21 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
             for (int u = 0; u < N; u++) dcc[u] = al[u] * Tr[u];
 #pragma unroll
             for (int u = 0; u < N; u++) rows_scan_add(gdot[u] * dcc[u], S, Sr[u], S);
+            float SDr[N], zs[N];
+            if constexpr (DEPTH) {
+#pragma unroll
+                for (int u = 0; u < N; u++) rows_scan_add(act[u] ? dcc[u] * t[u]->c.y : 0.f, SD, SDr[u], SD);
+#pragma unroll
+                for (int u = 0; u < N; u++) {   // the block's sum of g T alpha over the row's 16 pixels (dL/dz of the survivor)
+                    float v = gz * dcc[u];
+                    v += __shfl_xor(v, 1, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 8, 16);
+                    zs[u] = v;
+                }
+            }
 #pragma unroll
             for (int u = 0; u < N; u++) {
-                const float dL_dalpha = act[u] ? Tr[u] * gdot[u] - (OD - Sr[u]) * __builtin_amdgcn_rcpf(F[u]) : 0.f;
+                float dL_dalpha = act[u] ? Tr[u] * gdot[u] - (OD - Sr[u]) * __builtin_amdgcn_rcpf(F[u]) : 0.f;
+                if constexpr (DEPTH) dL_dalpha += act[u] ? gz * (Tr[u] * t[u]->c.y - (Dsuf - SDr[u]) * __builtin_amdgcn_rcpf(F[u])) : 0.f;
                 // Round 6: the row's lanes no longer form the nine GRADIENT values and reduce each over the 16 pixels (14 multiplications + a
                 // 4-level butterfly of ~24 DPP operations); they reduce the MOMENTS of m = G dL/dalpha about the Gaussian's centre,
                 //   M0 = sum m, Mx = sum m dx, My = sum m dy, Mxx = sum m dx^2, Mxy = sum m dx dy, Myy = sum m dy^2,
@@ -1964,12 +1996,13 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
                     : "v"(gda), "v"(dx[u]), "v"(dy[u]), "v"(c0v), "v"(c1v), "v"(c2v));
                 // column t of the block's lane grid keeps: t = 0 the plain sums, t = 1 the dx-weighted, t = 2 the dx^2-weighted, t = 3 colours 1 / 2
                 tot[u] = lq0 ? R : (lq1 ? b1 : (lq2 ? b2 : X));
+                if constexpr (DEPTH) tot[u] = l16 == 5 ? zs[u] : tot[u];
             }
             // (every survivor of the list was blended at one of the block's pixels: the row always has something to add, padding aside)
 #pragma unroll
             for (int u = 0; u < N; u++)
                 if (red_active && t[u]->pos >= 0) {
-                    if (DET) det[((size_t)(rx + (uint32_t)t[u]->pos) * 16 + (size_t)blk) * 9 + red_t] = tot[u];   // one (entry, block) pair is visited exactly once
+                    if (DET) det[((size_t)(rx + (uint32_t)t[u]->pos) * 16 + (size_t)blk) * DS + red_t] = tot[u];   // one (entry, block) pair is visited exactly once
                     else if (CSPLAT_K7X != 1) atomicAdd(acc + (size_t)t[u]->id * ACC_STRIDE + red_t, tot[u]);                      // nine lanes, one 64-byte record
                     else asm volatile("" :: "v"(tot[u]));        // (elimination build CSPLAT_K7X=1: the sums are formed, nothing is sent)
                 }
@@ -2105,14 +2138,16 @@ __global__ __launch_bounds__(256) void k_det_reduce(int P, Cam cam, const float2
 struct DetView { Cam cam; const float2 *xy; const float *depth; const int32_t *radii; const int2 *ranges; const uint64_t *keys_sorted;
                  const uint32_t *ids_sorted; const float *det; float *acc; };
 struct DetTable { DetView v[B2_MAX_VIEWS]; const uint32_t *valid; };
-__global__ __launch_bounds__(256) void k_det_reduce_views(int P, DetTable tab) {
+// NF floats per stored record: 9, or 10 on the depth path (slot 9 = dL/dz)
+template <int NF>
+__device__ __forceinline__ void det_reduce_views_body(int P, const DetTable &tab) {
     if (tab.valid && *tab.valid == 0u) return;
     const DetView &w = tab.v[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
-    float s[9];
+    float s[NF];
 #pragma unroll
-    for (int t = 0; t < 9; t++) s[t] = 0.f;
+    for (int t = 0; t < NF; t++) s[t] = 0.f;
     const int rad = w.radii[i];
     if (rad > 0) {
         const float2 p = w.xy[i];
@@ -2130,12 +2165,78 @@ __global__ __launch_bounds__(256) void k_det_reduce_views(int P, DetTable tab) {
                 }
                 for (int q = 0; q < 16; q++)
 #pragma unroll
-                    for (int t = 0; t < 9; t++) s[t] += w.det[((size_t)lo * 16 + q) * 9 + t];
+                    for (int t = 0; t < NF; t++) s[t] += w.det[((size_t)lo * 16 + q) * NF + t];
             }
     }
 #pragma unroll
-    for (int t = 0; t < 9; t++) w.acc[(size_t)i * ACC_STRIDE + t] = s[t];
+    for (int t = 0; t < NF; t++) w.acc[(size_t)i * ACC_STRIDE + t] = s[t];
 }
+__global__ __launch_bounds__(256) void k_det_reduce_views(int P, DetTable tab) { det_reduce_views_body<9>(P, tab); }
+
+// ------------------------------------------------------------------------------------------- K7, depth-gradient path
+// Launched only when a depth gradient is given (csplat_view.dL_ddepth); the default K7 / K8 launches above and below are untouched.
+// The forward's checkpoints hold (T, colour so far) at every segment start but no depth, so a prepass computes, per (segment, pixel),
+// the segment's partial depth  dpart = sum over its blended entries of T alpha z  (T from the checkpoint, entries from K6's bbits words,
+// the same alpha / threshold / n_contrib tests as K7); the depth K7 then needs only sums of partials for D_behind (composite_bwd_body).
+struct DepthView {
+    B2View b;
+    const float *dL_ddepth;   // [H][W], NULL: this view has no depth gradient (its depth terms are zero)
+    float *dpart;             // [slots][256] (segment, pixel of the tile in block-major order, as the checkpoints)
+    int W, H, gx, tiles;      // tiles = 0: the view has no list entries -- nothing to do
+};
+struct DepthTable { DepthView v[B2_MAX_VIEWS]; };
+__global__ __launch_bounds__(256) void k_depth_bwd_partials(DepthTable tab) {
+    const DepthView &w = tab.v[blockIdx.y];
+    if (!w.dL_ddepth || w.tiles == 0) return;
+    const int slot = blockIdx.x;
+    const int *seg_offset = w.b.seg_offset;
+    if (slot >= seg_offset[w.tiles]) return;
+    const int tile = w.b.slot_tile[slot];
+    const int seg_lo = (slot - seg_offset[tile]) * SEG;
+    const int blk = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+    const uint32_t *blk_hi = reinterpret_cast<const uint32_t *>(seg_offset) + w.tiles + 1 + tile * 16;
+    const int px = (tile % w.gx) * CSPLAT_TILE + (blk & 3) * 4 + (l16 & 3);
+    const int py = (tile / w.gx) * CSPLAT_TILE + (blk >> 2) * 4 + (l16 >> 2);
+    float D = 0.f;
+    if ((int)blk_hi[blk] > seg_lo && px < w.W && py < w.H) {
+        const int nc = (int)w.b.n_contrib[py * w.W + px];
+        if (nc > seg_lo) {
+            float T = w.b.ckpt[(size_t)slot * 256 + threadIdx.x].x;
+            const uint32_t rx = (uint32_t)w.b.ranges[tile].x;
+            const float fx = (float)px, fy = (float)py;
+            constexpr int NW = SEG / 64;
+            const unsigned long long *bw = w.b.bbits + ((size_t)slot * 16 + (size_t)blk) * NW;
+            for (int c = 0; c < NW; c++) {
+                unsigned long long m = bw[c];
+                while (m) {
+                    const int pos = seg_lo + 64 * c + __builtin_ctzll(m);
+                    m &= m - 1ull;
+                    if (pos >= nc) { c = NW; break; }
+                    const uint32_t ri = rx + (uint32_t)pos;
+                    const float4 A = w.b.recA[ri], B = w.b.recB[ri];
+                    const float z = reinterpret_cast<const float *>(w.b.recC)[2 * (size_t)ri + 1];
+                    const float dx = A.x - fx, dy = A.y - fy;
+                    const float power = -0.5f * (A.z * dx * dx + B.x * dy * dy) - A.w * dx * dy;
+                    const float a = fminf(0.99f, B.y * __expf(power));
+                    if (power > 0.f || a < ALPHA_MIN) continue;
+                    D += a * T * z;
+                    T *= 1.f - a;
+                }
+            }
+        }
+    }
+    w.dpart[(size_t)slot * 256 + threadIdx.x] = D;
+}
+template <bool DET>
+__global__ __launch_bounds__(256) void k_depth_composite_bwd_views(DepthTable tab) {
+    const DepthView &w = tab.v[blockIdx.y];
+    if (w.tiles == 0) return;
+    const B2View &b = w.b;
+    composite_bwd_body<DET, true>(w.tiles, w.W, w.H, w.gx, b.ranges, b.ids_sorted, b.bbits, b.recA, b.recB, b.recC, b.R, b.seg_offset,
+                                  b.slot_tile, b.ckpt, b.final_T, b.n_contrib, b.out_color, b.dL_dpix, b.acc, b.det, nullptr,
+                                  (int)blockIdx.x, w.dL_ddepth, w.dpart);
+}
+__global__ __launch_bounds__(256) void k_depth_det_reduce_views(int P, DetTable tab) { det_reduce_views_body<10>(P, tab); }
 
 // ------------------------------------------------------------------------------------------- K8
 // K7's per-Gaussian record (round 6) holds the MOMENTS of m = G dL/dalpha over the pixels the Gaussian was blended at, about its centre:
@@ -2155,8 +2256,10 @@ __device__ __forceinline__ void clear_record(const float *acc, int i) {
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     p[0] = z; p[1] = z; p[2] = z;
 }
-template <bool STAGE, int NT>
-__global__ __launch_bounds__(NT) void k_preprocess_bwd(int P, int D, int M, const float *__restrict__ means3D,
+// DEPTH (k_preprocess_bwd_depth, the depth-gradient path only): record slot 9 holds dL/dz of the view-space depth z = view[2] x + view[6] y +
+// view[10] z + view[14] (summed g T alpha, K7), which adds dL/dz (view[2], view[6], view[10]) to dL/dmean3D
+template <bool STAGE, int NT, bool DEPTH>
+__device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const float *__restrict__ means3D,
                                                          const float *__restrict__ shs, const float *__restrict__ scales,
                                                          float scale_mod, const float *__restrict__ rotations,
                                                          int use_precomp_cov, Cam cam, Geom g,
@@ -2186,6 +2289,8 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd(int P, int D, int M, cons
     float a9[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) a9[k] = vis ? acc[(size_t)i * ACC_STRIDE + k] : 0.f;
+    float dz = 0.f;
+    if constexpr (DEPTH) dz = vis ? acc[(size_t)i * ACC_STRIDE + 9] : 0.f;
     if (vis && (accmask & CSPLAT_SCRATCH_ZEROED)) clear_record(acc, i);      // (consumed: the caller's buffer is all zero again for its next step)
     moments_to_gradients(a9, vis ? g.conic_opacity[i] : make_float4(0.f, 0.f, 0.f, 0.f));
     a9[0] *= (float)cam.W; a9[1] *= (float)cam.H;      // (K7 leaves dL/dmean2D without the pixel <- NDC factors 2 * 0.5 W, 2 * 0.5 H)
@@ -2332,6 +2437,7 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd(int P, int D, int M, cons
         dmean[1] += (-vx * vy * ddx + (sum2 - vy * vy) * ddy - vz * vy * ddz) * invsum32;
         dmean[2] += (-vx * vz * ddx - vy * vz * ddy + (sum2 - vz * vz) * ddz) * invsum32;
     }
+    if constexpr (DEPTH) { dmean[0] += dz * view[2]; dmean[1] += dz * view[6]; dmean[2] += dz * view[10]; }
 #pragma unroll
     for (int k = 0; k < 3; k++) PUT(dL_dmean3D, 3 * i + k, dmean[k], CSPLAT_ACC_MEAN3D);
 #pragma unroll
@@ -2385,6 +2491,20 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd(int P, int D, int M, cons
     }
 #undef PUT
 }
+#define CSPLAT_K8_ARGS                                                                                                                 \
+    int P, int D, int M, const float *__restrict__ means3D, const float *__restrict__ shs, const float *__restrict__ scales,            \
+        float scale_mod, const float *__restrict__ rotations, int use_precomp_cov, Cam cam, Geom g, const int32_t *__restrict__ radii,  \
+        const float *__restrict__ acc, float *__restrict__ dL_dmean2D, float *__restrict__ dL_dconic, float *__restrict__ dL_dopacity,  \
+        float *__restrict__ dL_dcolor, float *__restrict__ dL_dmean3D, float *__restrict__ dL_dcov3D, float *__restrict__ dL_dsh,      \
+        float *__restrict__ dL_dscale, float *__restrict__ dL_drot, unsigned accmask
+#define CSPLAT_K8_PASS P, D, M, means3D, shs, scales, scale_mod, rotations, use_precomp_cov, cam, g, radii, acc, dL_dmean2D, dL_dconic, \
+                       dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accmask
+template <bool STAGE, int NT>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd(CSPLAT_K8_ARGS) { preprocess_bwd_body<STAGE, NT, false>(CSPLAT_K8_PASS); }
+template <bool STAGE, int NT>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd_depth(CSPLAT_K8_ARGS) { preprocess_bwd_body<STAGE, NT, true>(CSPLAT_K8_PASS); }
+#undef CSPLAT_K8_ARGS
+#undef CSPLAT_K8_PASS
 
 // K8 for ALL views of a step in one launch (csplat_backward_views).  The per-view kernels above add into shared gradient
 // buffers and therefore run one after the other behind the concurrent K7s (a tail of ~27 us per view).  Here a thread
@@ -2410,309 +2530,22 @@ struct K8Table {
 // VL lanes per Gaussian, lane vl takes the views vl, vl + VL, ...: with one lane per Gaussian the launch has P / 64 = 1564 waves (1.5 per
 // SIMD) that each walk V dependent load -> compute rounds; with VL = 4 it has four times the waves and (V <= 4) one round each.  The
 // sums over the views of the shared-parameter gradients cross the VL lanes with quad DPP adds (fixed association), the SH rows in LDS.
+// The batched K8's body lives in csplat_k8_views_body.h and is included into both kernels below, so that the default kernel is compiled
+// exactly as before (a shared __device__ body changed its register allocation).  DEPTH: k_preprocess_bwd_views_depth, the depth-gradient
+// path -- every view's record slot 9 (dL/dz, zero for a view without a depth gradient) adds dL/dz (view[2], view[6], view[10]) to dL/dmean3D.
 template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
                                                                const float *__restrict__ scales, float scale_mod,
                                                                int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool STAGE = true;
-    if (tab.valid && *tab.valid == 0u) return;
-    // (block0: first workgroup of a Gaussian-range SLICE of the launch -- csplat_backward_views_parts: the gradient rows of a finished slice
-    //  can leave for the other ranks while the next slice computes)
-    const int bx = (int)blockIdx.x + block0;
-    const unsigned smask = tab.sharedmask;
-    // shared output: add to the thread's running sum; per-view output: write (or add, by that view's accmask)
-#define PUTL(local, ptr, idx, val, bit)                                                    \
-    do {                                                                                   \
-        if (smask & (bit)) (local) += (val);                                               \
-        else { float *p_ = (ptr) + (idx); *p_ = (accmask & (bit)) ? *p_ + (val) : (val); } \
-    } while (0)
-    static_assert(VL == 1 || VL == 4, "one lane or one quad per Gaussian");
-    constexpr int NG = NT / VL;                   // Gaussians per workgroup
-    __shared__ float s_in[STAGE ? NG * SH_ROW : 1];
-    __shared__ float s_out[STAGE ? NT * SH_ROW : 1];
-    const int gi = threadIdx.x / VL, vl = threadIdx.x % VL;
-    const int i = bx * NG + gi;
-    const int rows = min(NG, P - bx * NG);
-    if (STAGE) {
-        stage_sh_rows<NT>(shs + (size_t)bx * NG * 48, rows, s_in);
-        for (int k = 0; k < 48; k++) s_out[threadIdx.x * SH_ROW + k] = 0.f;
-        __syncthreads();
-    }
-    if (i < P) {
-    float L_op = 0.f, L_col[3] = {0.f, 0.f, 0.f}, L_m3[3] = {0.f, 0.f, 0.f}, L_c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float L_sc[3] = {0.f, 0.f, 0.f}, L_rt[4] = {0.f, 0.f, 0.f, 0.f};
-    // the per-view record (radius, the nine accumulated pixel-level gradients) of view vi+1 is requested while view vi is
-    // processed: otherwise the thread walks V dependent load -> compute rounds
-    bool vis_n = false;
-    float a9_n[9];
-    float4 co_n = make_float4(0.f, 0.f, 0.f, 0.f);       // (the view's conic + opacity travel with its record: moments_to_gradients)
-    if (vl < tab.n) {
-        vis_n = tab.v[vl].radii[i] > 0;
-        co_n = tab.v[vl].g.conic_opacity[i];
-#pragma unroll
-        for (int k = 0; k < 9; k++) a9_n[k] = tab.v[vl].acc[(size_t)i * ACC_STRIDE + k];
-        if (vis_n && (tab.v[vl].accmask & CSPLAT_SCRATCH_ZEROED)) clear_record(tab.v[vl].acc, i);
-    }
-    for (int vi = vl; vi < tab.n; vi += VL) {
-    const K8View &w = tab.v[vi];
-    const Cam cam = w.cam;
-    const Geom g = w.g;
-    const int32_t *radii = w.radii;
-    const float *acc = w.acc, *means3D = w.means3D, *rotations = w.rotations;
-    float *dL_dmean2D = w.dL_dmean2D, *dL_dconic = w.dL_dconic, *dL_dopacity = w.dL_dopacity, *dL_dcolor = w.dL_dcolor;
-    float *dL_dmean3D = w.dL_dmean3D, *dL_dcov3D = w.dL_dcov3D, *dL_dscale = w.dL_dscale, *dL_drot = w.dL_drot;
-    const unsigned accmask = w.accmask;
-    (void)radii; (void)acc;
-    const bool vis = vis_n;
-    float a9[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) a9[k] = vis ? a9_n[k] : 0.f;
-    moments_to_gradients(a9, vis ? co_n : make_float4(0.f, 0.f, 0.f, 0.f));
-    a9[0] *= (float)cam.W; a9[1] *= (float)cam.H;      // (see k_preprocess_bwd)
-    if (vi + VL < tab.n) {
-        const K8View &wn = tab.v[vi + VL];
-        vis_n = wn.radii[i] > 0;
-#pragma unroll
-        for (int k = 0; k < 9; k++) a9_n[k] = wn.acc[(size_t)i * ACC_STRIDE + k];
-        co_n = wn.g.conic_opacity[i];
-        if (vis_n && (wn.accmask & CSPLAT_SCRATCH_ZEROED)) clear_record(wn.acc, i);
-    }
-    dL_dmean2D[3 * i] = a9[0]; dL_dmean2D[3 * i + 1] = a9[1]; dL_dmean2D[3 * i + 2] = 0.f;
-    dL_dconic[4 * i] = a9[2]; dL_dconic[4 * i + 1] = a9[3]; dL_dconic[4 * i + 2] = 0.f; dL_dconic[4 * i + 3] = a9[4];
-    PUTL(L_op, dL_dopacity, i, a9[5], CSPLAT_ACC_OPACITY);
-    PUTL(L_col[0], dL_dcolor, 3 * i, a9[6], CSPLAT_ACC_COLOR); PUTL(L_col[1], dL_dcolor, 3 * i + 1, a9[7], CSPLAT_ACC_COLOR);
-    PUTL(L_col[2], dL_dcolor, 3 * i + 2, a9[8], CSPLAT_ACC_COLOR);
-
-    float dmean[3] = {0.f, 0.f, 0.f};
-    float g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (!vis) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) PUTL(L_m3[k], dL_dmean3D, 3 * i + k, 0.f, CSPLAT_ACC_MEAN3D);
-#pragma unroll
-        for (int k = 0; k < 6; k++) PUTL(L_c6[k], dL_dcov3D, 6 * i + k, 0.f, CSPLAT_ACC_COV3D);
-        if (dL_dscale)
-#pragma unroll
-            for (int k = 0; k < 3; k++) PUTL(L_sc[k], dL_dscale, 3 * i + k, 0.f, CSPLAT_ACC_SCALE);
-        if (dL_drot)
-#pragma unroll
-            for (int k = 0; k < 4; k++) PUTL(L_rt[k], dL_drot, 4 * i + k, 0.f, CSPLAT_ACC_ROT);
-    } else {
-    const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
-    const float *view = cam.view, *proj = cam.proj;
-
-    // ---- conic -> cov2D -> cov3D and view-space mean
-    {
-        float pv[3];
-        view_point(p, view, pv);
-        ProjJac pj;
-        proj_jacobian(pv, cam, pj);
-        float c6[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) c6[k] = g.cov3D[6 * i + k];
-        float a, b, c;
-        cov2d_from_cov3d(c6, pj, a, b, c);
-        const float denom = a * c - b * b;
-        const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-        const float gcx = a9[2], gcy = a9[3], gcz = a9[4];
-        float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-        const float *t0 = pj.t0, *t1 = pj.t1;
-        if (denom2inv != 0.f) {
-            dL_da = denom2inv * (-c * c * gcx + 2.f * b * c * gcy + (denom - a * c) * gcz);
-            dL_dc = denom2inv * (-a * a * gcz + 2.f * a * b * gcy + (denom - a * c) * gcx);
-            dL_db = denom2inv * 2.f * (b * c * gcx - (denom + 2.f * b * b) * gcy + a * b * gcz);
-            g6[0] = t0[0] * t0[0] * dL_da + t0[0] * t1[0] * dL_db + t1[0] * t1[0] * dL_dc;
-            g6[3] = t0[1] * t0[1] * dL_da + t0[1] * t1[1] * dL_db + t1[1] * t1[1] * dL_dc;
-            g6[5] = t0[2] * t0[2] * dL_da + t0[2] * t1[2] * dL_db + t1[2] * t1[2] * dL_dc;
-            g6[1] = 2.f * t0[0] * t0[1] * dL_da + (t0[0] * t1[1] + t0[1] * t1[0]) * dL_db + 2.f * t1[0] * t1[1] * dL_dc;
-            g6[2] = 2.f * t0[0] * t0[2] * dL_da + (t0[0] * t1[2] + t0[2] * t1[0]) * dL_db + 2.f * t1[0] * t1[2] * dL_dc;
-            g6[4] = 2.f * t0[2] * t0[1] * dL_da + (t0[1] * t1[2] + t0[2] * t1[1]) * dL_db + 2.f * t1[1] * t1[2] * dL_dc;
-        }
-        const float Vm[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
-        float dT0[3], dT1[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const float Vt0 = Vm[r][0] * t0[0] + Vm[r][1] * t0[1] + Vm[r][2] * t0[2];
-            const float Vt1 = Vm[r][0] * t1[0] + Vm[r][1] * t1[1] + Vm[r][2] * t1[2];
-            dT0[r] = 2.f * Vt0 * dL_da + Vt1 * dL_db;
-            dT1[r] = 2.f * Vt1 * dL_dc + Vt0 * dL_db;
-        }
-        const float dJ00 = view[0] * dT0[0] + view[4] * dT0[1] + view[8] * dT0[2];
-        const float dJ02 = view[2] * dT0[0] + view[6] * dT0[1] + view[10] * dT0[2];
-        const float dJ11 = view[1] * dT1[0] + view[5] * dT1[1] + view[9] * dT1[2];
-        const float dJ12 = view[2] * dT1[0] + view[6] * dT1[1] + view[10] * dT1[2];
-        const float tz = 1.f / pj.tz, tz2 = tz * tz, tz3 = tz2 * tz;
-        const float xg = pj.x_in ? 1.f : 0.f, yg = pj.y_in ? 1.f : 0.f;
-        const float dtx = xg * -cam.fx * tz2 * dJ02;
-        const float dty = yg * -cam.fy * tz2 * dJ12;
-        const float dtz = -cam.fx * tz2 * dJ00 - cam.fy * tz2 * dJ11 + (2.f * cam.fx * pj.tx) * tz3 * dJ02 +
-                          (2.f * cam.fy * pj.ty) * tz3 * dJ12;
-        dmean[0] += view[0] * dtx + view[1] * dty + view[2] * dtz;
-        dmean[1] += view[4] * dtx + view[5] * dty + view[6] * dtz;
-        dmean[2] += view[8] * dtx + view[9] * dty + view[10] * dtz;
-    }
-    // ---- mean2D (NDC) -> mean3D
-    {
-        const float hw = proj[3] * p[0] + proj[7] * p[1] + proj[11] * p[2] + proj[15];
-        const float m_w = 1.0f / (hw + 0.0000001f);
-        const float mul1 = (proj[0] * p[0] + proj[4] * p[1] + proj[8] * p[2] + proj[12]) * m_w * m_w;
-        const float mul2 = (proj[1] * p[0] + proj[5] * p[1] + proj[9] * p[2] + proj[13]) * m_w * m_w;
-        const float gx2 = a9[0], gy2 = a9[1];
-        dmean[0] += (proj[0] * m_w - proj[3] * mul1) * gx2 + (proj[1] * m_w - proj[3] * mul2) * gy2;
-        dmean[1] += (proj[4] * m_w - proj[7] * mul1) * gx2 + (proj[5] * m_w - proj[7] * mul2) * gy2;
-        dmean[2] += (proj[8] * m_w - proj[11] * mul1) * gx2 + (proj[9] * m_w - proj[11] * mul2) * gy2;
-    }
-    // ---- colour -> SH (+ view direction -> mean3D)
-    if (shs && dL_dsh) {
-        const float *sh = (const float *)(s_in + gi * SH_ROW);
-        float *gsh = s_out + threadIdx.x * SH_ROW;
-        const uint32_t cl = g.clamped[i];
-        const float vx = p[0] - cam.campos[0], vy = p[1] - cam.campos[1], vz = p[2] - cam.campos[2];
-        const float sum2 = vx * vx + vy * vy + vz * vz;
-        const float len = sqrtf(sum2);
-        const float x = vx / len, y = vy / len, z = vz / len;
-        float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            const float dRGB = ((cl >> ch) & 1u) ? 0.f : a9[6 + ch];
-            float dx_ = 0.f, dy_ = 0.f, dz_ = 0.f;
-#define S(k) sh[(k) * 3 + ch]
-#define GS(k) gsh[(k) * 3 + ch]
-            GS(0) += SH_C0 * dRGB;
-            if (D > 0) {
-                GS(1) += -SH_C1 * y * dRGB;
-                GS(2) += SH_C1 * z * dRGB;
-                GS(3) += -SH_C1 * x * dRGB;
-                dx_ = -SH_C1 * S(3); dy_ = -SH_C1 * S(1); dz_ = SH_C1 * S(2);
-                if (D > 1) {
-                    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    GS(4) += SH_C2[0] * xy * dRGB;
-                    GS(5) += SH_C2[1] * yz * dRGB;
-                    GS(6) += SH_C2[2] * (2.f * zz - xx - yy) * dRGB;
-                    GS(7) += SH_C2[3] * xz * dRGB;
-                    GS(8) += SH_C2[4] * (xx - yy) * dRGB;
-                    dx_ += SH_C2[0] * y * S(4) + SH_C2[2] * 2.f * -x * S(6) + SH_C2[3] * z * S(7) + SH_C2[4] * 2.f * x * S(8);
-                    dy_ += SH_C2[0] * x * S(4) + SH_C2[1] * z * S(5) + SH_C2[2] * 2.f * -y * S(6) + SH_C2[4] * 2.f * -y * S(8);
-                    dz_ += SH_C2[1] * y * S(5) + SH_C2[2] * 4.f * z * S(6) + SH_C2[3] * x * S(7);
-                    if (D > 2) {
-                        GS(9) += SH_C3[0] * y * (3.f * xx - yy) * dRGB;
-                        GS(10) += SH_C3[1] * xy * z * dRGB;
-                        GS(11) += SH_C3[2] * y * (4.f * zz - xx - yy) * dRGB;
-                        GS(12) += SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * dRGB;
-                        GS(13) += SH_C3[4] * x * (4.f * zz - xx - yy) * dRGB;
-                        GS(14) += SH_C3[5] * z * (xx - yy) * dRGB;
-                        GS(15) += SH_C3[6] * x * (xx - 3.f * yy) * dRGB;
-                        dx_ += SH_C3[0] * S(9) * 6.f * xy + SH_C3[1] * S(10) * yz + SH_C3[2] * S(11) * -2.f * xy +
-                               SH_C3[3] * S(12) * -6.f * xz + SH_C3[4] * S(13) * (-3.f * xx + 4.f * zz - yy) +
-                               SH_C3[5] * S(14) * 2.f * xz + SH_C3[6] * S(15) * 3.f * (xx - yy);
-                        dy_ += SH_C3[0] * S(9) * 3.f * (xx - yy) + SH_C3[1] * S(10) * xz +
-                               SH_C3[2] * S(11) * (-3.f * yy + 4.f * zz - xx) + SH_C3[3] * S(12) * -6.f * yz +
-                               SH_C3[4] * S(13) * -2.f * xy + SH_C3[5] * S(14) * -2.f * yz + SH_C3[6] * S(15) * -6.f * xy;
-                        dz_ += SH_C3[1] * S(10) * xy + SH_C3[2] * S(11) * 8.f * yz +
-                               SH_C3[3] * S(12) * 3.f * (2.f * zz - xx - yy) + SH_C3[4] * S(13) * 8.f * xz +
-                               SH_C3[5] * S(14) * (xx - yy);
-                    }
-                }
-            }
-#undef S
-#undef GS
-            ddx += dx_ * dRGB; ddy += dy_ * dRGB; ddz += dz_ * dRGB;
-        }
-        const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-        dmean[0] += ((sum2 - vx * vx) * ddx - vy * vx * ddy - vz * vx * ddz) * invsum32;
-        dmean[1] += (-vx * vy * ddx + (sum2 - vy * vy) * ddy - vz * vy * ddz) * invsum32;
-        dmean[2] += (-vx * vz * ddx - vy * vz * ddy + (sum2 - vz * vz) * ddz) * invsum32;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) PUTL(L_m3[k], dL_dmean3D, 3 * i + k, dmean[k], CSPLAT_ACC_MEAN3D);
-#pragma unroll
-    for (int k = 0; k < 6; k++) PUTL(L_c6[k], dL_dcov3D, 6 * i + k, g6[k], CSPLAT_ACC_COV3D);
-
-    // ---- cov3D -> scale, quaternion
-    if (!use_precomp_cov && dL_dscale && dL_drot) {
-        const float q[4] = {rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]};
-        float R[3][3];
-        quat_to_rot(q, R);
-        const float s[3] = {scale_mod * scales[3 * i], scale_mod * scales[3 * i + 1], scale_mod * scales[3 * i + 2]};
-        const float dS[3][3] = {{g6[0], 0.5f * g6[1], 0.5f * g6[2]},
-                                {0.5f * g6[1], g6[3], 0.5f * g6[4]},
-                                {0.5f * g6[2], 0.5f * g6[4], g6[5]}};
-        float dA[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-                dA[r][k] = 2.f * (dS[r][0] * R[0][k] * s[k] + dS[r][1] * R[1][k] * s[k] + dS[r][2] * R[2][k] * s[k]);
-#pragma unroll
-        for (int k = 0; k < 3; k++) PUTL(L_sc[k], dL_dscale, 3 * i + k, dA[0][k] * R[0][k] + dA[1][k] * R[1][k] + dA[2][k] * R[2][k], CSPLAT_ACC_SCALE);
-        float dR[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int k = 0; k < 3; k++) dR[r][k] = dA[r][k] * s[k];
-        const float qr = q[0], qx = q[1], qy = q[2], qz = q[3];
-        const float dq0 = 2.f * (-qz * dR[0][1] + qy * dR[0][2] + qz * dR[1][0] - qx * dR[1][2] - qy * dR[2][0] + qx * dR[2][1]);
-        const float dq1 = 2.f * (qy * dR[0][1] + qz * dR[0][2] + qy * dR[1][0] - 2.f * qx * dR[1][1] - qr * dR[1][2] +
-                                    qz * dR[2][0] + qr * dR[2][1] - 2.f * qx * dR[2][2]);
-        const float dq2 = 2.f * (-2.f * qy * dR[0][0] + qx * dR[0][1] + qr * dR[0][2] + qx * dR[1][0] + qz * dR[1][2] -
-                                    qr * dR[2][0] + qz * dR[2][1] - 2.f * qy * dR[2][2]);
-        const float dq3 = 2.f * (-2.f * qz * dR[0][0] - qr * dR[0][1] + qx * dR[0][2] + qr * dR[1][0] - 2.f * qz * dR[1][1] +
-                                    qy * dR[1][2] + qx * dR[2][0] + qy * dR[2][1]);
-        PUTL(L_rt[0], dL_drot, 4 * i, dq0, CSPLAT_ACC_ROT); PUTL(L_rt[1], dL_drot, 4 * i + 1, dq1, CSPLAT_ACC_ROT);
-        PUTL(L_rt[2], dL_drot, 4 * i + 2, dq2, CSPLAT_ACC_ROT); PUTL(L_rt[3], dL_drot, 4 * i + 3, dq3, CSPLAT_ACC_ROT);
-    }
-    }   // visible
-    }   // views
-    if (VL == 4) {   // the four lanes' sums over their views: ((v0 + v1) + (v2 + v3)) in every lane
-        auto quad_sum = [](float v) {
-            v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-            v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-            return v;
-        };
-        L_op = quad_sum(L_op);
-#pragma unroll
-        for (int k = 0; k < 3; k++) { L_col[k] = quad_sum(L_col[k]); L_m3[k] = quad_sum(L_m3[k]); L_sc[k] = quad_sum(L_sc[k]); }
-#pragma unroll
-        for (int k = 0; k < 6; k++) L_c6[k] = quad_sum(L_c6[k]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) L_rt[k] = quad_sum(L_rt[k]);
-    }
-    if (vl == 0) {   // gradients of the parameters every view shares: one write (added to the buffer only if the first view was asked to)
-        const unsigned accmask = tab.v[0].accmask;
-        const K8View &w = tab.v[0];
-#define PUTS(ptr, idx, val, bit) do { if (smask & (bit)) { float *p_ = (ptr) + (idx); *p_ = (accmask & (bit)) ? *p_ + (val) : (val); } } while (0)
-        PUTS(w.dL_dopacity, i, L_op, CSPLAT_ACC_OPACITY);
-#pragma unroll
-        for (int k = 0; k < 3; k++) PUTS(w.dL_dcolor, 3 * i + k, L_col[k], CSPLAT_ACC_COLOR);
-#pragma unroll
-        for (int k = 0; k < 3; k++) PUTS(w.dL_dmean3D, 3 * i + k, L_m3[k], CSPLAT_ACC_MEAN3D);
-#pragma unroll
-        for (int k = 0; k < 6; k++) PUTS(w.dL_dcov3D, 6 * i + k, L_c6[k], CSPLAT_ACC_COV3D);
-        if (w.dL_dscale)
-#pragma unroll
-            for (int k = 0; k < 3; k++) PUTS(w.dL_dscale, 3 * i + k, L_sc[k], CSPLAT_ACC_SCALE);
-        if (w.dL_drot)
-#pragma unroll
-            for (int k = 0; k < 4; k++) PUTS(w.dL_drot, 4 * i + k, L_rt[k], CSPLAT_ACC_ROT);
-#undef PUTS
-    }
-    }   // i < P
-    if (STAGE) {   // coalesced 16-byte stores of the workgroup's SH gradients
-        __syncthreads();
-        float4 *dst4 = reinterpret_cast<float4 *>(dL_dsh + (size_t)bx * NG * 48);
-        for (int t = threadIdx.x; t < rows * 12; t += NT) {
-            const int row = t / 12, c = (t - row * 12) * 4;
-            const float *sp = s_out + row * VL * SH_ROW + c;
-            float4 o = make_float4(sp[0], sp[1], sp[2], sp[3]);
-#pragma unroll
-            for (int v2 = 1; v2 < VL; v2++) {            // the rows of the Gaussian's other view lanes, in lane order
-                const float *sq = sp + v2 * SH_ROW;
-                o.x += sq[0]; o.y += sq[1]; o.z += sq[2]; o.w += sq[3];
-            }
-            if (tab.v[0].accmask & CSPLAT_ACC_SH) { const float4 u = dst4[t]; o.x += u.x; o.y += u.y; o.z += u.z; o.w += u.w; }
-            dst4[t] = o;
-        }
-    }
-#undef PUTL
+    constexpr bool DEPTH = false;
+#include "csplat_k8_views_body.h"
+}
+template <int NT, int VL>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd_views_depth(int P, int D, int M, const float *__restrict__ shs,
+                                                                     const float *__restrict__ scales, float scale_mod,
+                                                                     int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
+    constexpr bool DEPTH = true;
+#include "csplat_k8_views_body.h"
 }
 
 // ------------------------------------------------------------------------------------------- layouts
@@ -2883,6 +2716,16 @@ size_t csplat_temp_bytes(int P, int64_t R, int W, int H) { (void)P; (void)W; (vo
 static size_t det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 9 * 4); }
 size_t csplat_backward_scratch_bytes(int P, int64_t R) {
     return align256((size_t)(P > 0 ? P : 1) * ACC_STRIDE * 4) + ((g_debug_flags & 256u) ? det_bytes(R) : 0);
+}
+// the depth-gradient path: the per-Gaussian records, in the bit-reproducible mode the (entry, block) records of 10 floats, then the
+// per-(segment, pixel) depth partials of the prepass
+static size_t depth_det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 10 * 4); }
+static size_t depth_dpart_offset(int P, int64_t R) {
+    return align256((size_t)(P > 0 ? P : 1) * ACC_STRIDE * 4) + ((g_debug_flags & 256u) ? depth_det_bytes(R) : 0);
+}
+size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H) {
+    const int tiles = cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE);
+    return depth_dpart_offset(P, R) + align256((size_t)max_slots(R, tiles) * 256 * 4);
 }
 int csplat_geom_layout(int P, size_t *o8) { size_t off[G_NFIELDS]; geom_offsets(P, off); for (int k = 0; k < 8; k++) o8[k] = off[k]; return 0; }
 // every sub-buffer of the BINNING chunk (csplat.h: csplat_binning_fields): 0 keys 1 ids 2 seg_offset + blk_hi 3 slot_tile 4 checkpoints
@@ -3466,7 +3309,7 @@ static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with
                          const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, void *scratch,
                          float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot) {
+                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, bool depth_k8 = false) {
     CSPLAT_REQUIRE(geom && binning && image && out_color, "csplat_backward: missing saved state");
     CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
     CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward: scratch (csplat_backward_scratch_bytes) missing");
@@ -3518,6 +3361,23 @@ static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with
         CSPLAT_REQUIRE(ev != nullptr, "csplat_backward_views: no event");
         HIP_TRY(hipEventRecord(ev, s));
         HIP_TRY(hipStreamWaitEvent(k8s, ev, 0));
+    }
+    if (depth_k8) {      // (the depth-gradient path: csplat_view.dL_ddepth; record slot 9 -> dL/dmean3D)
+        ProfScope ps(PROF_K8_DEPTH, k8s);
+        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
+        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
+        if (stage)
+            k_preprocess_bwd_depth<true, 128><<<cdiv(P, 128), 128, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,
+                                                                              cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D,
+                                                                              dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
+                                                                              dL_dsh, dL_dscale, dL_drot, accmask);
+        else
+            k_preprocess_bwd_depth<false, 256><<<cdiv(P, 256), 256, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,
+                                                                               cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D,
+                                                                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
+                                                                               dL_dsh, dL_dscale, dL_drot, accmask);
+        LAUNCH_CHECK();
+        return 0;
     }
     {
         ProfScope ps(PROF_K8, k8s);
@@ -3802,9 +3662,117 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
 // one, and may hand the gradient rows of slice g to its collective while slice g + 1 computes.  Only the one-launch-per-stage path can be
 // cut (the views share P, SH, scales and the image size, as csplat_forward_views_faith requires); parts == 3 with one slice is
 // csplat_backward_views.  The sum of the parts is the whole call bit for bit: every Gaussian's arithmetic is the same in any slicing.
+// The depth-gradient path (some view has dL_ddepth): every stage runs on the join stream -- clearing, the depth prepass, the depth K7 of
+// all views in one launch (views without a depth gradient take it with zero depth terms), the depth K8.  Every view's scratch is laid out
+// by csplat_backward_depth_scratch_bytes.  The default path (backward_views_impl below) is not entered.
+static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices) {
+    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth gradient is taken for at most 8 views per call");
+    CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth gradient");
+    const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
+    bool shared = false;
+    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)CSPLAT_SCRATCH_ZEROED) != 0u;
+    K8Table tab;
+    const bool one_k8 = shared && k8_views_table(V, v, tab);
+    CSPLAT_REQUIRE(whole || one_k8, "csplat_backward_views_parts: only the one-launch-per-stage path can be cut into parts");
+    const bool det_mode = (g_debug_flags & 256u) != 0;
+    if (want_k7) {
+        DepthTable dtab;
+        DetTable dt;
+        dt.valid = nullptr;
+        int64_t slots = 0;
+        int Pmax = 0;
+        for (int i = 0; i < V; i++) {
+            const csplat_view &w = v[i];
+            CSPLAT_REQUIRE(w.geom && w.binning && w.image && w.out_color && w.scratch && w.dL_dpix && w.radii,
+                           "csplat_backward_views: missing saved state, scratch or dL_dpix");
+            DepthView &d = dtab.v[i];
+            const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
+            const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;   // what the chunk was laid out for
+            size_t ioff[5], boff[B_NFIELDS];
+            image_offsets(w.W, w.H, ioff);
+            binning_offsets(Rl, tiles, boff);
+            const char *b = (const char *)w.binning, *im = (const char *)w.image;
+            B2View &k = d.b;
+            k.ranges = (const int2 *)(im + ioff[0]); k.n_contrib = (const uint32_t *)(im + ioff[1]); k.final_T = (const float *)(im + ioff[2]);
+            k.ids_sorted = (const uint32_t *)(b + boff[1]); k.seg_offset = (const int *)(b + boff[2]); k.slot_tile = (const int *)(b + boff[3]);
+            k.ckpt = (const float4 *)(b + boff[4]); k.bbits = (const unsigned long long *)(b + boff[9]);
+            k.recA = (const float4 *)(b + boff[6]); k.recB = (const float4 *)(b + boff[7]); k.recC = (const float2 *)(b + boff[8]);
+            k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = (float *)w.scratch; k.R = (uint32_t)Rl;
+            k.det = det_mode ? (float *)((char *)w.scratch + align256((size_t)(w.P > 0 ? w.P : 1) * ACC_STRIDE * 4)) : nullptr;
+            d.dL_ddepth = w.dL_ddepth;
+            d.dpart = (float *)((char *)w.scratch + depth_dpart_offset(w.P, Rl));
+            d.W = w.W; d.H = w.H; d.gx = gx;
+            d.tiles = (w.P > 0 && w.num_rendered > 0) ? tiles : 0;
+            if (w.P <= 0) continue;
+            Pmax = w.P > Pmax ? w.P : Pmax;
+            // (the records start at zero: the bit-reproducible mode writes every one of them, CSPLAT_SCRATCH_ZEROED promises them)
+            if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, depth_det_bytes(Rl), join));
+            else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(k.acc, 0, (size_t)w.P * ACC_STRIDE * 4, join));
+            if (det_mode) {
+                DetView &e = dt.v[i];
+                make_cam(e.cam, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H);
+                const Geom g = geom_view((void *)w.geom, w.P);
+                e.xy = g.xy; e.depth = g.depth; e.radii = w.radii; e.ranges = k.ranges; e.keys_sorted = (const uint64_t *)(b + boff[0]);
+                e.ids_sorted = k.ids_sorted; e.det = k.det; e.acc = k.acc;
+            }
+            const int64_t sl = (w.busy_tiles > 0 && w.num_rendered > 0) ? (int64_t)w.num_rendered / SEG + w.busy_tiles + 1 : max_slots(Rl, tiles);
+            slots = sl > slots ? sl : slots;
+        }
+        if (slots > 0) {
+            {
+                ProfScope ps(PROF_K7_DEPTH_PARTIALS, join);
+                k_depth_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(dtab);
+                LAUNCH_CHECK();
+            }
+            ProfScope ps(PROF_K7_DEPTH, join);
+            const unsigned items = (unsigned)cdiv(slots, 8) * 32u;
+            if (det_mode)
+                k_depth_composite_bwd_views<true><<<dim3(items, V), 256, 0, join>>>(dtab);
+            else
+                k_depth_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(dtab);
+            LAUNCH_CHECK();
+        }
+        if (det_mode && Pmax > 0) {
+            // (a view with fewer Gaussians: its rows past P are not visited -- the launch is sized for the largest view and guarded per view)
+            for (int i = 0; i < V; i++) {
+                if (v[i].P <= 0) continue;
+                DetTable one;
+                one.valid = nullptr;
+                one.v[0] = dt.v[i];
+                k_depth_det_reduce_views<<<dim3((unsigned)cdiv(v[i].P, 256), 1), 256, 0, join>>>(v[i].P, one);
+                LAUNCH_CHECK();
+            }
+        }
+    }
+    if (!want_k8) return 0;
+    if (one_k8) {
+        ProfScope ps(PROF_K8_DEPTH, join);
+        const csplat_view &a = v[0];
+        const int nb = cdiv(a.P, 32);
+        const int b_lo = (int)((int64_t)nb * slice / nslices), b_hi = (int)((int64_t)nb * (slice + 1) / nslices);
+        if (b_hi > b_lo) {
+            k_preprocess_bwd_views_depth<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
+            LAUNCH_CHECK();
+        }
+        return 0;
+    }
+    for (int i = 0; i < V; i++) {       // per-view K8 on the join stream, in view order (views may add into one another's buffers)
+        const csplat_view &w = v[i];
+        if (int rc = backward_impl(join, join, false, true, w.accmask, w.P, w.D, w.M,
+                                   w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered, w.bg, w.W, w.H, w.means3D, w.shs, w.scales,
+                                   w.scale_modifier, w.rotations, w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii,
+                                   w.geom, w.binning, w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
+                                   w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, w.dL_ddepth != nullptr))
+            return rc;
+    }
+    return 0;
+}
+
 static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
     CSPLAT_REQUIRE(V >= 0 && (V == 0 || v != nullptr), "csplat_backward_views: bad view count");
     CSPLAT_REQUIRE(parts >= 1 && parts <= 3 && nslices >= 1 && slice >= 0 && slice < nslices, "csplat_backward_views_parts: bad parts / slice");
+    for (int i = 0; i < V; i++)
+        if (v[i].dL_ddepth) return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices);
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     hipStream_t join = (hipStream_t)join_stream;
     bool shared = false;   // any view adding into another view's buffers: all K8 run on the join stream, in view order
@@ -3919,6 +3887,37 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
     return rc ? rc : r2;
 }
 int csplat_backward_views(int V, csplat_view *v, void *join_stream) { return backward_views_impl(V, v, join_stream, 3u, 0, 1); }
+// csplat_backward with the depth image's gradient: the one view goes through the depth path of the batched entry (NULL dL_ddepth = the
+// call is csplat_backward's)
+int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                          const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                          const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
+                          const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
+                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, const float *dL_ddepth,
+                          void *scratch, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot) {
+    if (!dL_ddepth)
+        return csplat_backward(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                               view, proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, scratch, dL_dmean2D,
+                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+    CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward_depth: scratch (csplat_backward_depth_scratch_bytes) missing");
+    CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
+    if (P <= 0) return 0;
+    csplat_view w;
+    memset(&w, 0, sizeof(w));
+    w.stream = stream;
+    w.P = P; w.D = D; w.M = M; w.W = W; w.H = H;
+    w.scale_modifier = scale_modifier; w.tanfovx = tanfovx; w.tanfovy = tanfovy;
+    w.bg = bg; w.means3D = means3D; w.shs = shs; w.colors_precomp = colors_precomp; w.scales = scales; w.rotations = rotations;
+    w.cov3D_precomp = cov3D_precomp; w.view = view; w.proj = proj; w.campos = campos;
+    w.out_color = const_cast<float *>(out_color); w.radii = const_cast<int32_t *>(radii);
+    w.num_rendered = R; w.layout_rendered = R;
+    w.geom = const_cast<void *>(geom); w.binning = const_cast<void *>(binning); w.image = const_cast<void *>(image);
+    w.dL_dpix = dL_dpix; w.dL_ddepth = dL_ddepth; w.scratch = scratch;
+    w.dL_dmean2D = dL_dmean2D; w.dL_dconic = dL_dconic; w.dL_dopacity = dL_dopacity; w.dL_dcolor = dL_dcolor; w.dL_dmean3D = dL_dmean3D;
+    w.dL_dcov3D = dL_dcov3D; w.dL_dsh = dL_dsh; w.dL_dscale = dL_dscale; w.dL_drot = dL_drot;
+    return backward_views_depth(1, &w, (hipStream_t)stream, 3u, 0, 1);
+}
 int csplat_backward_views_parts(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
     return backward_views_impl(V, v, join_stream, parts, slice, nslices);
 }

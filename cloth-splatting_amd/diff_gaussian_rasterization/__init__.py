@@ -7,7 +7,10 @@ Mirrors the interface the reference binds at gaussian_renderer/__init__.py:16 an
                                         scales=None, rotations=None, cov3D_precomp=None) -> (color, radii, depth)
 Gradients are delivered for means3D, means2D (NDC-space screen gradient used by densification,
 scene_reconstruction/train_utils.py:290-292), shs, colors_precomp, opacities, scales, rotations, cov3D_precomp.
-The depth image carries no gradient (as upstream).  All compute is in libcsplat.so (csplat_forward_begin / _finish / csplat_backward).
+The depth image D = sum_i T_i alpha_i z_i (view-space z, no background term) is differentiable, as in the depth fork of the rasterizer
+the reference pins: a loss on it reaches means3D, means2D, opacities, scales / rotations / cov3D_precomp (csplat_backward_depth; without
+a depth gradient the backward is exactly the colour-only one).  All compute is in libcsplat.so (csplat_forward_begin / _finish /
+csplat_backward).
 `rasterize_views` renders several independent views in one call, one HIP stream per view.
 """
 import contextlib as _contextlib
@@ -138,11 +141,14 @@ class _View:
         self.alloc.cb = None  # break the allocator <-> callback cycle: TEMP / TABLE die here, not at the next cyclic GC
         self.alloc = None
 
-    def backward(self, grad_color, saved):
-        """K7 + K8 on the CURRENT stream; returns the per-input gradients in the Function's argument order."""
+    def backward(self, grad_color, saved, grad_depth=None):
+        """K7 + K8 on the CURRENT stream; returns the per-input gradients in the Function's argument order.  grad_depth None: the
+        colour-only call (csplat_backward); else the depth path (csplat_backward_depth), where a missing grad_color counts as zero."""
         means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = saved
         rs, dev, P, M = self.rs, self.dev, self.P, self.M
         geom, binning, image = self.chunks
+        if grad_color is None:
+            grad_color = torch.zeros(3, self.H, self.W, dtype=torch.float32, device=dev)
         grad_color = _f32c_grad(grad_color, dev)
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         d_mean2D, d_conic, d_opac, d_color = new(P, 3), new(P, 4), new(P, 1), new(P, 3)
@@ -150,6 +156,21 @@ class _View:
         d_sh = new(P, M, 3) if sh is not None else None
         d_scale = new(P, 3) if scales is not None else None
         d_rot = new(P, 4) if rotations is not None else None
+        if grad_depth is not None:
+            grad_depth = _f32c_grad(grad_depth, dev)
+            scratch = torch.empty(max(int(_n.lib.csplat_backward_depth_scratch_bytes(P, self.num_rendered, self.W, self.H)), 256),
+                                  dtype=torch.uint8, device=dev)
+            with _n.on_device(dev):
+                rc = _n.lib.csplat_backward_depth(
+                    _n.stream_handle(dev), P, int(rs.sh_degree), M, self.num_rendered, _n.ptr(self.bg), self.W, self.H,
+                    _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp), _n.ptr(scales), float(rs.scale_modifier),
+                    _n.ptr(rotations), _n.ptr(cov3Ds_precomp), _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos),
+                    float(rs.tanfovx), float(rs.tanfovy), _n.ptr(radii), _n.ptr(geom), _n.ptr(binning), _n.ptr(image),
+                    _n.ptr(color), _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch), _n.ptr(d_mean2D), _n.ptr(d_conic),
+                    _n.ptr(d_opac), _n.ptr(d_color), _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh), _n.ptr(d_scale), _n.ptr(d_rot))
+            _n.check(rc, "csplat_backward_depth")
+            return (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
+                    d_cov3D if cov3Ds_precomp is not None else None)
         scratch = torch.empty(max(int(_n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)), 256), dtype=torch.uint8,
                               device=dev)
         with _n.on_device(dev):
@@ -184,12 +205,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(*v.saved())
         v.drop_inputs()
         ctx.view_state = v
-        ctx.mark_non_differentiable(radii, depth)
+        ctx.mark_non_differentiable(radii)
+        if hasattr(ctx, "set_materialize_grads"):      # (an unused depth image arrives as None: the colour-only call)
+            ctx.set_materialize_grads(False)
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, _grad_depth):
-        return ctx.view_state.backward(grad_color, ctx.saved_tensors) + (None,)
+    def backward(ctx, grad_color, _grad_radii, grad_depth):
+        if grad_color is None and grad_depth is None:
+            return (None,) * 9
+        return ctx.view_state.backward(grad_color, ctx.saved_tensors, grad_depth) + (None,)
 
 
 _side_streams = {}
@@ -410,7 +435,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
             outs += [v.radii, v.depth] if stacked else [v.color, v.radii, v.depth]
             saved += list(v.saved()[:-1]) + ([] if stacked else [v.color])
-            ctx.mark_non_differentiable(v.radii, v.depth)
+            ctx.mark_non_differentiable(v.radii)
         if stacked:
             outs = [colors] + outs
             saved.append(colors)
@@ -422,6 +447,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         for v in views:
             v.drop_inputs()
         ctx.views, ctx.arr = views, arr
+        ctx.on_faith = _FAITH is not None
         ctx.set_materialize_grads(False)     # an unused view arrives as None in backward() and costs nothing
         ctx.plan = None
         if any(ctx.needs_input_grad):
@@ -557,9 +583,14 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         main = torch.cuda.current_stream(dev)
         if ctx.stacked:
             gcol = [None] * V if grads[0] is None else [grads[0][i] for i in range(V)]
+            gdep = [grads[2 + 2 * i] for i in range(V)]
         else:
             gcol = [grads[3 * i] for i in range(V)]
-        active = [i for i in range(V) if gcol[i] is not None]
+            gdep = [grads[3 * i + 2] for i in range(V)]
+        if any(g is not None for g in gdep) and ctx.on_faith:
+            raise RuntimeError("diff_gaussian_rasterization: a depth gradient reached a forward launched on faith (a captured / replayed step); "
+                               "those steps take no depth loss -- render the depth term in an eager step")
+        active = [i for i in range(V) if gcol[i] is not None or gdep[i] is not None]
         if not active:
             return (None, None) + (None,) * (V * _RasterizeGaussiansBatch.NIN)
         plan, ctx.plan = ctx.plan, None                         # (one use: the buffers are handed to autograd)
@@ -570,9 +601,22 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             if plan is not None:
                 _n.grad_release(plan["sinks"])
             plan = _RasterizeGaussiansBatch._plan_backward(views, ctx.saved_tensors, k, arr, ctx.first_of, active, dev)
-        gs = [_f32c_grad(gcol[i], dev) for i in active]
+        gs = [_f32c_grad(gcol[i], dev) if gcol[i] is not None else torch.zeros(3, views[i].H, views[i].W, dtype=torch.float32, device=dev)
+              for i in active]
         for a, g in enumerate(gs):
             plan["sub"][a].dL_dpix = _n.ptr(g)
+        if any(gdep[i] is not None for i in active):
+            # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout, allocated here (never on
+            # the colour-only path) and cleared by the library -- the persistent zeroed records are not used by this call
+            for a, i in enumerate(active):
+                v = views[i]
+                gd = _f32c_grad(gdep[i], dev) if gdep[i] is not None else None
+                buf = torch.empty(max(int(_n.lib.csplat_backward_depth_scratch_bytes(v.P, v.layout_rendered, v.W, v.H)), 256),
+                                  dtype=torch.uint8, device=dev)
+                plan["sub"][a].dL_ddepth = _n.ptr(gd)
+                plan["sub"][a].scratch = buf.data_ptr()
+                plan["sub"][a].accmask &= ~SCRATCH_ZEROED
+                gs += [gd, buf]
         if _K8_DEFER is not None:
             # K7 now, K8 in slices later (DeferredK8.launch): the plan -- the view array and every buffer it points into -- stays alive
             with _n.on_device(dev):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CSPLAT_ABI_VERSION 6   /* 6 (round 6): csplat_backward_views_parts / _slice_rows, csplat_gnn_edge_length_refine, csplat_rollout_head / _decode / _integrate, csplat_gnn_edge_features_ordered, csplat_gnn_rows_chain(_pack), csplat_binning_fields; round 4: csplat_view.busy_tiles / .valid, csplat_rows_dot_fwd's extra argument; 3: the binning chunk's layout (bbits, bmask); 4 (round 5): csplat_gather_words kind 2; 5: csplat_gnn_edge_mlp3* (e0_absmax, modes), csplat_absmax, csplat_linear_narrow128 */
+#define CSPLAT_ABI_VERSION 7   /* 7: the depth image's gradient (csplat_view.dL_ddepth, csplat_backward_depth, csplat_backward_depth_scratch_bytes); 6 (round 6): csplat_backward_views_parts / _slice_rows, csplat_gnn_edge_length_refine, csplat_rollout_head / _decode / _integrate, csplat_gnn_edge_features_ordered, csplat_gnn_rows_chain(_pack), csplat_binning_fields; round 4: csplat_view.busy_tiles / .valid, csplat_rows_dot_fwd's extra argument; 3: the binning chunk's layout (bbits, bmask); 4 (round 5): csplat_gather_words kind 2; 5: csplat_gnn_edge_mlp3* (e0_absmax, modes), csplat_absmax, csplat_linear_narrow128 */
 
 /* scratch chunks requested through the allocator callback */
 #define CSPLAT_CHUNK_GEOM 0    /* per-Gaussian state, kept for backward */
@@ -76,6 +76,11 @@ size_t csplat_image_bytes(int W, int H);
 size_t csplat_binning_bytes(int64_t R, int W, int H);
 size_t csplat_temp_bytes(int P, int64_t R, int W, int H);
 size_t csplat_backward_scratch_bytes(int P, int64_t R); /* per-Gaussian accumulation records used by csplat_backward */
+/* the scratch of a backward call that takes a depth gradient (csplat_backward_depth, or any view of csplat_backward_views* with
+ * dL_ddepth set -- then EVERY view of that call needs this size): the records above, 10-float (entry, block) records in the
+ * bit-reproducible mode, and one float per (list segment, pixel) for the depth partials.  Never smaller than
+ * csplat_backward_scratch_bytes(P, R). */
+size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H);
 
 /* Byte offsets of the named sub-buffers inside a chunk (for tests / debugging; see DESIGN.md "HBM layout").
  * geom:    0 depth f32[P] | 1 xy f32[P][2] | 2 conic_opacity f32[P][4] | 3 rgb f32[P][3] | 4 cov3D f32[P][6]
@@ -163,6 +168,10 @@ typedef struct csplat_view {
                                      * compositing backward's grid with it (segments <= R / 256 + busy_tiles + 1) */
     const uint32_t *valid;          /* NULL, or (csplat_forward_views_faith) the device word that says whether the forward took place:
                                      * the backward of views[0..V) does nothing when it is 0 */
+    const float *dL_ddepth;         /* ABI 7, backward input: the gradient of out_depth [1][H][W], NULL = none.  When any view of a
+                                     * backward call has one, the call takes the depth path (extra launches, see csplat_backward_depth;
+                                     * every view's scratch sized by csplat_backward_depth_scratch_bytes; not for views launched on faith,
+                                     * at most 8 views); when none has, the call is exactly the ABI 6 one */
 } csplat_view;
 int csplat_forward_views(int V, csplat_view *views, csplat_alloc_fn alloc, void *join_stream);
 /* The same call with its one host read (the views' counts) DEFERRED.  When the second phase can be launched on the previous call's
@@ -195,8 +204,8 @@ int csplat_forward_views_faith(int V, csplat_view *views, csplat_alloc_fn alloc,
 size_t csplat_image_info_offset(int W, int H);
 
 /* Backward: K7 compositing backward, K8 per-Gaussian backward.
- * out_color is the forward's colour image; dL_dpix[3][H][W] its gradient (the depth image carries no gradient,
- * as upstream).
+ * out_color is the forward's colour image; dL_dpix[3][H][W] its gradient.  The depth image's gradient is taken by
+ * csplat_backward_depth below.
  * scratch: device buffer of csplat_backward_scratch_bytes(P, R) bytes: one 64-byte-aligned accumulation record per Gaussian (9 floats
  * used).  ABI 3: K7 adds one 36-byte partial per (list entry, 4x4 pixel BLOCK that blended it) -- the nine lanes that hold the row sums
  * issue one float-atomic request to the Gaussian's record; K8 consumes the records.  In the bit-reproducible mode (csplat_debug_flags
@@ -212,6 +221,19 @@ int csplat_backward(void *stream, int P, int D, int M, int R, const float *bg, i
                     float *dL_dmean2D,
                     float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
                     float *dL_dsh, float *dL_dscale, float *dL_drot);
+/* csplat_backward plus the gradient of the depth image dL_ddepth[1][H][W] (device; NULL = exactly csplat_backward).  The depth image is
+ * D = sum_i T_i alpha_i z_i over the blended entries of a pixel (z = view-space depth, no background term; the depth fork of the
+ * rasterizer that the reference pins).  Its adjoint adds g (T_i z_i - D_behind_i / (1 - alpha_i)) to dL/dalpha_i (reaching means2D,
+ * conic / cov3D / scale / rotation and opacity as the colour term does) and sum_pix g T_i alpha_i (view[2], view[6], view[10]) to
+ * dL/dmean3D_i.  Launches: a prepass of per-(segment, pixel) depth partials, the depth variant of K7, the depth variant of K8.
+ * scratch: csplat_backward_depth_scratch_bytes(P, R, W, H) bytes. */
+int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                          const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                          const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
+                          const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
+                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, const float *dL_ddepth,
+                          void *scratch, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot);
 
 /* distCUDA2: out[i] = mean of squared distances from point i to its 3 nearest other points. */
 int csplat_dist2(void *stream, int P, const float *xyz, float *out);
@@ -410,6 +432,7 @@ int csplat_mesh_transform_bwd_views(void *stream, int T, int P, int V, const int
  * mask bit k enables bracketing of kernel class k with a start/stop event pair on the stream it is launched on:
  *   0 K1 preprocess | 1 K2 scan | 2 K3 key emission | 3 K4 radix sort (all passes) | 4 K5 tile ranges
  *   5 K6 compositing fwd | 6 K7 compositing bwd | 7 K8 preprocess bwd | 8 distCUDA2 | 9 GNN kernels
+ *   10 depth partials prepass | 11 K7 of the depth path | 12 K8 of the depth path (csplat_backward_depth, dL_ddepth)
  * csplat_prof_read synchronises the recorded events of class k, returns their summed duration (ms) and the
  * number of brackets, and recycles the events. */
 int csplat_prof_enable(unsigned mask);
