@@ -1,6 +1,6 @@
 // Body of the batched per-Gaussian backward (K8 of csplat_backward_views), included by csplat_raster.hip into k_preprocess_bwd_views
-// (DEPTH = false) and k_preprocess_bwd_views_depth (DEPTH = true).  Not a standalone header: it expects the kernels' parameters and a
-// constexpr bool DEPTH in scope.
+// (DEPTH = false), k_preprocess_bwd_views_depth (DEPTH = true) and k_preprocess_bwd_views_cam (CAM = true).  Not a standalone header: it
+// expects the kernels' parameters, constexpr bools DEPTH and CAM and a `const CamSlabs *cam_slabs` in scope.
     constexpr bool STAGE = true;
     if (tab.valid && *tab.valid == 0u) return;
     // (block0: first workgroup of a Gaussian-range SLICE of the launch -- csplat_backward_views_parts: the gradient rows of a finished slice
@@ -17,6 +17,8 @@
     constexpr int NG = NT / VL;                   // Gaussians per workgroup
     __shared__ float s_in[STAGE ? NG * SH_ROW : 1];
     __shared__ float s_out[STAGE ? NT * SH_ROW : 1];
+    __shared__ float s_cam[CAM ? K8_MAX_VIEWS * NG * CAM_NC : 1];     // (CAM) [view][Gaussian of the workgroup][CAM_NC]
+    __shared__ float s_cpart[CAM ? CAM_PARTS * CAM_NC : 1];
     const int gi = threadIdx.x / VL, vl = threadIdx.x % VL;
     const int i = bx * NG + gi;
     const int rows = min(NG, P - bx * NG);
@@ -53,6 +55,7 @@
     const unsigned accmask = w.accmask;
     (void)radii; (void)acc;
     const bool vis = vis_n;
+    float *const crow = s_cam + (CAM ? (vi * NG + gi) * CAM_NC : 0);   // (CAM) this (view, Gaussian)'s partials
     float a9[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) a9[k] = vis ? a9_n[k] : 0.f;
@@ -87,6 +90,7 @@
         if (dL_drot)
 #pragma unroll
             for (int k = 0; k < 4; k++) PUTL(L_rt[k], dL_drot, 4 * i + k, 0.f, CSPLAT_ACC_ROT);
+        if constexpr (CAM) cam_partials_zero(crow);
     } else {
     const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
     const float *view = cam.view, *proj = cam.proj;
@@ -140,6 +144,10 @@
         dmean[0] += view[0] * dtx + view[1] * dty + view[2] * dtz;
         dmean[1] += view[4] * dtx + view[5] * dty + view[6] * dtz;
         dmean[2] += view[8] * dtx + view[9] * dty + view[10] * dtz;
+        if constexpr (CAM) {
+            const float dpv[3] = {dtx, dty, dtz + dz};
+            cam_partials_view(crow, p, dpv, cam.fx * tz, -(cam.fx * pj.tx) * tz2, cam.fy * tz, -(cam.fy * pj.ty) * tz2, dT0, dT1);
+        }
     }
     // ---- mean2D (NDC) -> mean3D
     {
@@ -151,7 +159,9 @@
         dmean[0] += (proj[0] * m_w - proj[3] * mul1) * gx2 + (proj[1] * m_w - proj[3] * mul2) * gy2;
         dmean[1] += (proj[4] * m_w - proj[7] * mul1) * gx2 + (proj[5] * m_w - proj[7] * mul2) * gy2;
         dmean[2] += (proj[8] * m_w - proj[11] * mul1) * gx2 + (proj[9] * m_w - proj[11] * mul2) * gy2;
+        if constexpr (CAM) cam_partials_proj(crow, p, gx2 * m_w, gy2 * m_w, -(mul1 * gx2 + mul2 * gy2));
     }
+    if constexpr (CAM) { crow[32] = 0.f; crow[33] = 0.f; crow[34] = 0.f; }
     // ---- colour -> SH (+ view direction -> mean3D)
     if (shs && dL_dsh) {
         const float *sh = (const float *)(s_in + gi * SH_ROW);
@@ -212,6 +222,10 @@
         dmean[0] += ((sum2 - vx * vx) * ddx - vy * vx * ddy - vz * vx * ddz) * invsum32;
         dmean[1] += (-vx * vy * ddx + (sum2 - vy * vy) * ddy - vz * vy * ddz) * invsum32;
         dmean[2] += (-vx * vz * ddx - vy * vz * ddy + (sum2 - vz * vz) * ddz) * invsum32;
+        if constexpr (CAM) {   // dL/dcampos = -(the direction's part of dL/dmean3D) = -(dd - d (d . dd)) / |m - campos|
+            const float dd = x * ddx + y * ddy + z * ddz, il = 1.f / len;
+            crow[32] = (x * dd - ddx) * il; crow[33] = (y * dd - ddy) * il; crow[34] = (z * dd - ddz) * il;
+        }
     }
     if constexpr (DEPTH) { dmean[0] += dz * view[2]; dmean[1] += dz * view[6]; dmean[2] += dz * view[10]; }
 #pragma unroll
@@ -288,6 +302,8 @@
 #undef PUTS
     }
     }   // i < P
+    if constexpr (CAM)   // (every view of the call: each lane with i < P has written its rows of all the views it holds)
+        for (int vi = 0; vi < tab.n; vi++) cam_block_sum<NT>(s_cam + vi * NG * CAM_NC, rows, s_cpart, cam_slabs->p[vi] + (size_t)bx * CAM_NC);
     if (STAGE) {   // coalesced 16-byte stores of the workgroup's SH gradients
         __syncthreads();
         float4 *dst4 = reinterpret_cast<float4 *>(dL_dsh + (size_t)bx * NG * 48);

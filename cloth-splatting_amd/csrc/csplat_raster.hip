@@ -2256,9 +2256,65 @@ __device__ __forceinline__ void clear_record(const float *acc, int i) {
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     p[0] = z; p[1] = z; p[2] = z;
 }
+// ---- camera partials (the camera-gradient path: csplat_view.dL_dview / dL_dproj / dL_dcampos).  One slab row per (workgroup, view):
+// 0..15 dL/dview (flat 4 row + col; column 3 is unused by the kernels and stays 0) | 16..31 dL/dproj (column 2 unused, 0) | 32..34 dL/dcampos.
+// No float atomics: the rows are summed in a fixed order (cam_block_sum, then k_cam_sum), so the sums are as reproducible as their inputs.
+constexpr int CAM_NC = 35;
+constexpr int CAM_PARTS = 8;          // first level of cam_block_sum: CAM_PARTS x CAM_NC partial sums over contiguous row ranges
+__device__ __forceinline__ void cam_partials_zero(float *row) {
+#pragma unroll
+    for (int k = 0; k < CAM_NC; k++) row[k] = 0.f;
+}
+// dL/dview = ph (x) dL/dpv (ph = [m, 1], pv = ph view) plus, on the upper 3x3 block, the term through Rw = view[:3,:3]^T in T = J Rw:
+// dL/dview[4 r + k] += (J^T dL/dT)[k][r].  J: J00 = fx / tz, J02 = -fx tx / tz^2, J11 = fy / tz, J12 = -fy ty / tz^2 (tx, ty clamped).
+__device__ __forceinline__ void cam_partials_view(float *row, const float p[3], const float dpv[3], float J00, float J02, float J11, float J12,
+                                                  const float dT0[3], const float dT1[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        row[4 * r] = p[r] * dpv[0] + J00 * dT0[r];
+        row[4 * r + 1] = p[r] * dpv[1] + J11 * dT1[r];
+        row[4 * r + 2] = p[r] * dpv[2] + (J02 * dT0[r] + J12 * dT1[r]);
+        row[4 * r + 3] = 0.f;
+    }
+    row[12] = dpv[0]; row[13] = dpv[1]; row[14] = dpv[2]; row[15] = 0.f;
+}
+// dL/dproj = ph (x) dL/dhom, hom = ph proj, ndc = hom[:2] / (hom[3] + 1e-7): dL/dhom = (g.x m_w, g.y m_w, 0, -(hom0 g.x + hom1 g.y) m_w^2)
+__device__ __forceinline__ void cam_partials_proj(float *row, const float p[3], float dh0, float dh1, float dh3) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        row[16 + 4 * r] = p[r] * dh0; row[16 + 4 * r + 1] = p[r] * dh1; row[16 + 4 * r + 2] = 0.f; row[16 + 4 * r + 3] = p[r] * dh3;
+    }
+    row[28] = dh0; row[29] = dh1; row[30] = 0.f; row[31] = dh3;
+}
+// rows [0, nrows) of s[.][CAM_NC] (LDS) summed per column in a fixed order -> out[CAM_NC] (global): CAM_PARTS contiguous row ranges, then
+// the parts in order.  Every thread of the workgroup calls it (it synchronises).
+template <int NT>
+__device__ __forceinline__ void cam_block_sum(const float *s, int nrows, float *s_part, float *out) {
+    __syncthreads();
+    const int chunk = (nrows + CAM_PARTS - 1) / CAM_PARTS;
+    for (int t = threadIdx.x; t < CAM_PARTS * CAM_NC; t += NT) {
+        const int part = t / CAM_NC, c = t - part * CAM_NC;
+        const int r0 = part * chunk, r1 = min(nrows, r0 + chunk);
+        float a = 0.f;
+        for (int r = r0; r < r1; r++) a += s[r * CAM_NC + c];
+        s_part[t] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < CAM_NC) {
+        float a = 0.f;
+#pragma unroll
+        for (int q = 0; q < CAM_PARTS; q++) a += s_part[q * CAM_NC + threadIdx.x];
+        out[threadIdx.x] = a;
+    }
+}
+
 // DEPTH (k_preprocess_bwd_depth, the depth-gradient path only): record slot 9 holds dL/dz of the view-space depth z = view[2] x + view[6] y +
 // view[10] z + view[14] (summed g T alpha, K7), which adds dL/dz (view[2], view[6], view[10]) to dL/dmean3D
-template <bool STAGE, int NT, bool DEPTH>
+// CAM (k_preprocess_bwd_cam, the camera-gradient path only): every thread writes its Gaussian's camera partials (cam_partials_*) to its LDS
+// row, the workgroup sums them in a fixed order into slab row blockIdx.x (cam_block_sum).  The Gaussian's own gradients are computed by
+// exactly the same expressions: the partials only read values the body has formed (never a product that feeds a sum), so no FMA
+// contraction of the default arithmetic changes.
+template <bool STAGE, int NT, bool DEPTH, bool CAM = false>
 __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const float *__restrict__ means3D,
                                                          const float *__restrict__ shs, const float *__restrict__ scales,
                                                          float scale_mod, const float *__restrict__ rotations,
@@ -2268,7 +2324,7 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
                                                          float *__restrict__ dL_dopacity, float *__restrict__ dL_dcolor,
                                                          float *__restrict__ dL_dmean3D, float *__restrict__ dL_dcov3D,
                                                          float *__restrict__ dL_dsh, float *__restrict__ dL_dscale,
-                                                         float *__restrict__ dL_drot, unsigned accmask) {
+                                                         float *__restrict__ dL_drot, unsigned accmask, float *__restrict__ cam_slab = nullptr) {
     // accmask (CSPLAT_ACC_*): outputs that are ADDED to instead of written -- several views of one step share the
     // gradient buffer of a shared parameter (csplat_backward_views), which replaces autograd's per-view temporaries
     // and its V-1 summation launches per parameter.
@@ -2277,6 +2333,9 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
     // lane-per-Gaussian 4-byte stores at a 192-byte stride wrote 2.7x the algorithmic bytes)
     __shared__ float s_in[STAGE ? NT * SH_ROW : 1];
     __shared__ float s_out[STAGE ? NT * SH_ROW : 1];
+    __shared__ float s_cam[CAM ? NT * CAM_NC : 1];
+    __shared__ float s_cpart[CAM ? CAM_PARTS * CAM_NC : 1];
+    float *const crow = s_cam + (CAM ? threadIdx.x * CAM_NC : 0);     // (CAM) this thread's partials
     const int i = blockIdx.x * NT + threadIdx.x;
     const int rows = min(NT, P - blockIdx.x * NT);
     if (STAGE) {
@@ -2310,6 +2369,7 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
         if (dL_dsh && !STAGE) for (int k = 0; k < M * 3; k++) dL_dsh[(size_t)i * M * 3 + k] = 0.f;
         if (dL_dscale) for (int k = 0; k < 3; k++) PUT(dL_dscale, 3 * i + k, 0.f, CSPLAT_ACC_SCALE);
         if (dL_drot) for (int k = 0; k < 4; k++) PUT(dL_drot, 4 * i + k, 0.f, CSPLAT_ACC_ROT);
+        if constexpr (CAM) cam_partials_zero(crow);
     } else {
     const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
     const float *view = cam.view, *proj = cam.proj;
@@ -2363,6 +2423,10 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
         dmean[0] += view[0] * dtx + view[1] * dty + view[2] * dtz;
         dmean[1] += view[4] * dtx + view[5] * dty + view[6] * dtz;
         dmean[2] += view[8] * dtx + view[9] * dty + view[10] * dtz;
+        if constexpr (CAM) {
+            const float dpv[3] = {dtx, dty, dtz + dz};
+            cam_partials_view(crow, p, dpv, cam.fx * tz, -(cam.fx * pj.tx) * tz2, cam.fy * tz, -(cam.fy * pj.ty) * tz2, dT0, dT1);
+        }
     }
     // ---- mean2D (NDC) -> mean3D
     {
@@ -2374,7 +2438,9 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
         dmean[0] += (proj[0] * m_w - proj[3] * mul1) * gx2 + (proj[1] * m_w - proj[3] * mul2) * gy2;
         dmean[1] += (proj[4] * m_w - proj[7] * mul1) * gx2 + (proj[5] * m_w - proj[7] * mul2) * gy2;
         dmean[2] += (proj[8] * m_w - proj[11] * mul1) * gx2 + (proj[9] * m_w - proj[11] * mul2) * gy2;
+        if constexpr (CAM) cam_partials_proj(crow, p, gx2 * m_w, gy2 * m_w, -(mul1 * gx2 + mul2 * gy2));
     }
+    if constexpr (CAM) { crow[32] = 0.f; crow[33] = 0.f; crow[34] = 0.f; }
     // ---- colour -> SH (+ view direction -> mean3D)
     if (shs && dL_dsh) {
         const float *sh = STAGE ? (const float *)(s_in + threadIdx.x * SH_ROW) : shs + (size_t)i * M * 3;
@@ -2436,6 +2502,10 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
         dmean[0] += ((sum2 - vx * vx) * ddx - vy * vx * ddy - vz * vx * ddz) * invsum32;
         dmean[1] += (-vx * vy * ddx + (sum2 - vy * vy) * ddy - vz * vy * ddz) * invsum32;
         dmean[2] += (-vx * vz * ddx - vy * vz * ddy + (sum2 - vz * vz) * ddz) * invsum32;
+        if constexpr (CAM) {   // dL/dcampos = -(the direction's part of dL/dmean3D) = -(dd - d (d . dd)) / |m - campos|
+            const float dd = x * ddx + y * ddy + z * ddz, il = 1.f / len;
+            crow[32] = (x * dd - ddx) * il; crow[33] = (y * dd - ddy) * il; crow[34] = (z * dd - ddz) * il;
+        }
     }
     if constexpr (DEPTH) { dmean[0] += dz * view[2]; dmean[1] += dz * view[6]; dmean[2] += dz * view[10]; }
 #pragma unroll
@@ -2478,6 +2548,7 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
     }
     }   // visible
     }   // i < P
+    if constexpr (CAM) cam_block_sum<NT>(s_cam, rows, s_cpart, cam_slab + (size_t)blockIdx.x * CAM_NC);
     if (STAGE) {   // coalesced 16-byte stores of the workgroup's SH gradients
         __syncthreads();
         float4 *dst4 = reinterpret_cast<float4 *>(dL_dsh + (size_t)blockIdx.x * NT * 48);
@@ -2503,6 +2574,10 @@ template <bool STAGE, int NT>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd(CSPLAT_K8_ARGS) { preprocess_bwd_body<STAGE, NT, false>(CSPLAT_K8_PASS); }
 template <bool STAGE, int NT>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_depth(CSPLAT_K8_ARGS) { preprocess_bwd_body<STAGE, NT, true>(CSPLAT_K8_PASS); }
+template <bool STAGE, int NT, bool DEPTH>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd_cam(CSPLAT_K8_ARGS, float *__restrict__ cam_slab) {
+    preprocess_bwd_body<STAGE, NT, DEPTH, true>(CSPLAT_K8_PASS, cam_slab);
+}
 #undef CSPLAT_K8_ARGS
 #undef CSPLAT_K8_PASS
 
@@ -2533,19 +2608,113 @@ struct K8Table {
 // The batched K8's body lives in csplat_k8_views_body.h and is included into both kernels below, so that the default kernel is compiled
 // exactly as before (a shared __device__ body changed its register allocation).  DEPTH: k_preprocess_bwd_views_depth, the depth-gradient
 // path -- every view's record slot 9 (dL/dz, zero for a view without a depth gradient) adds dL/dz (view[2], view[6], view[10]) to dL/dmean3D.
+// CAM: k_preprocess_bwd_views_cam<.., DEPTH>, the camera-gradient path -- per view, one slab row per workgroup (CamSlabs, see
+// cam_partials_view): the lanes of a quad hold different views, so the partials go to LDS rows [view][Gaussian] and only rows of one view
+// are summed together.
+struct CamSlabs {
+    float *p[K8_MAX_VIEWS];   // per view: the slab (rows of CAM_NC floats, one per workgroup)
+};
 template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
                                                                const float *__restrict__ scales, float scale_mod,
                                                                int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = false;
+    constexpr bool DEPTH = false, CAM = false;
+    const CamSlabs *const cam_slabs = nullptr;
 #include "csplat_k8_views_body.h"
 }
 template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_depth(int P, int D, int M, const float *__restrict__ shs,
                                                                      const float *__restrict__ scales, float scale_mod,
                                                                      int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = true;
+    constexpr bool DEPTH = true, CAM = false;
+    const CamSlabs *const cam_slabs = nullptr;
 #include "csplat_k8_views_body.h"
+}
+template <int NT, int VL, bool DEPTH>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd_views_cam(int P, int D, int M, const float *__restrict__ shs,
+                                                                   const float *__restrict__ scales, float scale_mod,
+                                                                   int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
+                                                                   CamSlabs slabs) {
+    constexpr bool CAM = true;
+    const CamSlabs *const cam_slabs = &slabs;
+#include "csplat_k8_views_body.h"
+}
+
+// ---- the fixed-order sums of the camera path.  dL/dbg_c = sum_pix dL/dC_c(pix) T_final(pix) (the depth image has no background term):
+// k_bg_partials writes one row of 3 per (pixel block, view), BG_BLOCKS contiguous pixel ranges per view.  k_cam_sum then sums, per view,
+// the K8 slab (rows of CAM_NC) and the background slab (rows of 3) in index order: thread t takes rows t, t + 256, ..., and the 256
+// partial rows meet in a fixed LDS tree.
+constexpr int BG_BLOCKS = 256;
+struct BgView {
+    const float *final_T, *dL_dpix;
+    float *slab;           // NULL: the view takes no background gradient
+    int npix;
+};
+struct BgTable {
+    BgView v[K8_MAX_VIEWS];
+};
+__global__ __launch_bounds__(256) void k_bg_partials(BgTable tab) {
+    const BgView w = tab.v[blockIdx.y];
+    if (!w.slab) return;
+    const int64_t n = w.npix, lo = n * blockIdx.x / BG_BLOCKS, hi = n * (blockIdx.x + 1) / BG_BLOCKS;
+    float a[3] = {0.f, 0.f, 0.f};
+    for (int64_t q = lo + threadIdx.x; q < hi; q += 256) {
+        const float T = w.final_T[q];
+        a[0] += w.dL_dpix[q] * T; a[1] += w.dL_dpix[n + q] * T; a[2] += w.dL_dpix[2 * n + q] * T;
+    }
+    __shared__ float s[3][256];
+#pragma unroll
+    for (int c = 0; c < 3; c++) s[c][threadIdx.x] = a[c];
+    for (int st = 128; st > 0; st >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < st)
+#pragma unroll
+            for (int c = 0; c < 3; c++) s[c][threadIdx.x] += s[c][threadIdx.x + st];
+    }
+    if (threadIdx.x < 3) w.slab[blockIdx.x * 3 + threadIdx.x] = s[threadIdx.x][0];
+}
+struct CamSumView {
+    const float *slab, *bg_slab;    // K8 slab (rows of CAM_NC), background slab (rows of 3; NULL: no background gradient)
+    int rows, bg_rows;
+    float *dL_dview, *dL_dproj, *dL_dcampos, *dL_dbg;   // each may be NULL
+};
+struct CamSumTable {
+    CamSumView v[K8_MAX_VIEWS];
+};
+// columns [0, NC) of rows [0, rows) summed in a fixed order; the result is left in s[0 .. NC) (s: 256 x NC floats of LDS)
+template <int NC>
+__device__ __forceinline__ void slab_sum(const float *slab, int rows, float *s) {
+    float a[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) a[c] = 0.f;
+    for (int r = threadIdx.x; r < rows; r += 256)
+#pragma unroll
+        for (int c = 0; c < NC; c++) a[c] += slab[(size_t)r * NC + c];
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NC; c++) s[threadIdx.x * NC + c] = a[c];
+    for (int st = 128; st > 0; st >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < st)
+#pragma unroll
+            for (int c = 0; c < NC; c++) s[threadIdx.x * NC + c] += s[(threadIdx.x + st) * NC + c];
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(256) void k_cam_sum(CamSumTable tab) {
+    const CamSumView w = tab.v[blockIdx.y];
+    __shared__ float s[256 * CAM_NC];
+    const int t = threadIdx.x;
+    if (w.dL_dview || w.dL_dproj || w.dL_dcampos) {
+        slab_sum<CAM_NC>(w.slab, w.rows, s);
+        if (w.dL_dview && t < 16) w.dL_dview[t] = s[t];
+        if (w.dL_dproj && t < 16) w.dL_dproj[t] = s[16 + t];
+        if (w.dL_dcampos && t < 3) w.dL_dcampos[t] = s[32 + t];
+    }
+    if (w.dL_dbg) {
+        slab_sum<3>(w.bg_slab, w.bg_rows, s);
+        if (t < 3) w.dL_dbg[t] = s[t];
+    }
 }
 
 // ------------------------------------------------------------------------------------------- layouts
@@ -2726,6 +2895,15 @@ static size_t depth_dpart_offset(int P, int64_t R) {
 size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H) {
     const int tiles = cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE);
     return depth_dpart_offset(P, R) + align256((size_t)max_slots(R, tiles) * 256 * 4);
+}
+// the camera path's slabs live behind everything the depth path lays out: the K8 slab (at most one row per 32 Gaussians: the batched K8's
+// workgroup), then the background slab
+static size_t cam_slab_offset(int P, int64_t R, int W, int H) { return csplat_backward_depth_scratch_bytes(P, R, W, H); }
+static size_t cam_bg_offset(int P, int64_t R, int W, int H) {
+    return cam_slab_offset(P, R, W, H) + align256((size_t)cdiv(P > 0 ? P : 1, 32) * CAM_NC * 4);
+}
+size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H) {
+    return cam_bg_offset(P, R, W, H) + align256((size_t)BG_BLOCKS * 3 * 4);
 }
 int csplat_geom_layout(int P, size_t *o8) { size_t off[G_NFIELDS]; geom_offsets(P, off); for (int k = 0; k < 8; k++) o8[k] = off[k]; return 0; }
 // every sub-buffer of the BINNING chunk (csplat.h: csplat_binning_fields): 0 keys 1 ids 2 seg_offset + blk_hi 3 slot_tile 4 checkpoints
@@ -3309,7 +3487,8 @@ static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with
                          const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, void *scratch,
                          float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, bool depth_k8 = false) {
+                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, bool depth_k8 = false,
+                         float *cam_slab = nullptr, int *cam_rows = nullptr) {
     CSPLAT_REQUIRE(geom && binning && image && out_color, "csplat_backward: missing saved state");
     CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
     CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward: scratch (csplat_backward_scratch_bytes) missing");
@@ -3361,6 +3540,25 @@ static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with
         CSPLAT_REQUIRE(ev != nullptr, "csplat_backward_views: no event");
         HIP_TRY(hipEventRecord(ev, s));
         HIP_TRY(hipStreamWaitEvent(k8s, ev, 0));
+    }
+    if (cam_slab) {      // (the camera-gradient path: one slab row per workgroup, summed by k_cam_sum; *cam_rows = the number of rows)
+        ProfScope ps(PROF_K8_CAM, k8s);
+        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
+        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
+        const int nt = stage ? 128 : 256, grid = cdiv(P, nt);
+#define CSPLAT_K8_CAM_LAUNCH(ST, NT_, DP)                                                                                                  \
+    k_preprocess_bwd_cam<ST, NT_, DP><<<grid, NT_, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,                   \
+                                                             cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D, dL_dconic,       \
+                                                             dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, \
+                                                             accmask, cam_slab)
+        if (stage && depth_k8) CSPLAT_K8_CAM_LAUNCH(true, 128, true);
+        else if (stage) CSPLAT_K8_CAM_LAUNCH(true, 128, false);
+        else if (depth_k8) CSPLAT_K8_CAM_LAUNCH(false, 256, true);
+        else CSPLAT_K8_CAM_LAUNCH(false, 256, false);
+#undef CSPLAT_K8_CAM_LAUNCH
+        LAUNCH_CHECK();
+        if (cam_rows) *cam_rows = grid;
+        return 0;
     }
     if (depth_k8) {      // (the depth-gradient path: csplat_view.dL_ddepth; record slot 9 -> dL/dmean3D)
         ProfScope ps(PROF_K8_DEPTH, k8s);
@@ -3665,7 +3863,47 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
 // The depth-gradient path (some view has dL_ddepth): every stage runs on the join stream -- clearing, the depth prepass, the depth K7 of
 // all views in one launch (views without a depth gradient take it with zero depth terms), the depth K8.  Every view's scratch is laid out
 // by csplat_backward_depth_scratch_bytes.  The default path (backward_views_impl below) is not entered.
-static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices) {
+// ---- the camera-gradient path (ABI 8: csplat_view.dL_dview / dL_dproj / dL_dcampos / dL_dbg).  The compositing backward is the call's
+// own (default or depth); only K8 changes, to its CAM variant (when a view / projection / centre gradient is asked for), and two small
+// launches follow on the join stream, behind every view's K8: k_bg_partials (when a background gradient is asked for) and k_cam_sum.
+static bool cam_k8_wanted(const csplat_view &w) { return w.dL_dview || w.dL_dproj || w.dL_dcampos; }
+static float *cam_slab_of(const csplat_view &w) {
+    const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
+    return (float *)((char *)w.scratch + cam_slab_offset(w.P, Rl, w.W, w.H));
+}
+static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *rows) {
+    BgTable bt;
+    CamSumTable ct;
+    bool any_bg = false;
+    for (int i = 0; i < V; i++) {
+        const csplat_view &w = v[i];
+        const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
+        BgView &b = bt.v[i];
+        b.slab = nullptr; b.final_T = nullptr; b.dL_dpix = w.dL_dpix; b.npix = w.W * w.H;
+        if (w.dL_dbg && w.image && w.dL_dpix && w.scratch) {
+            size_t ioff[5];
+            image_offsets(w.W, w.H, ioff);
+            b.final_T = (const float *)((const char *)w.image + ioff[2]);
+            b.slab = (float *)((char *)w.scratch + cam_bg_offset(w.P, Rl, w.W, w.H));
+            any_bg = true;
+        }
+        CamSumView &c = ct.v[i];
+        c.slab = w.scratch ? cam_slab_of(w) : nullptr; c.rows = w.scratch ? rows[i] : 0;
+        c.bg_slab = b.slab; c.bg_rows = b.slab ? BG_BLOCKS : 0;
+        c.dL_dview = w.dL_dview; c.dL_dproj = w.dL_dproj; c.dL_dcampos = w.dL_dcampos; c.dL_dbg = w.dL_dbg;
+    }
+    ProfScope ps(PROF_CAM_SUM, join);
+    if (any_bg) {
+        k_bg_partials<<<dim3(BG_BLOCKS, V), 256, 0, join>>>(bt);
+        LAUNCH_CHECK();
+    }
+    k_cam_sum<<<dim3(1, V), 256, 0, join>>>(ct);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices, bool cam = false,
+                                bool cam_k8 = false) {
     CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth gradient is taken for at most 8 views per call");
     CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth gradient");
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
@@ -3745,6 +3983,17 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
         }
     }
     if (!want_k8) return 0;
+    int cam_rows[K8_MAX_VIEWS] = {0};
+    if (one_k8 && cam_k8) {      // (whole calls only: no slices)
+        ProfScope ps(PROF_K8_CAM, join);
+        const csplat_view &a = v[0];
+        const int nb = cdiv(a.P, 32);
+        CamSlabs sl;
+        for (int i = 0; i < V; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
+        k_preprocess_bwd_views_cam<128, 4, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
+        LAUNCH_CHECK();
+        return cam ? cam_tail(V, v, join, cam_rows) : 0;
+    }
     if (one_k8) {
         ProfScope ps(PROF_K8_DEPTH, join);
         const csplat_view &a = v[0];
@@ -3754,7 +4003,7 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             k_preprocess_bwd_views_depth<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
             LAUNCH_CHECK();
         }
-        return 0;
+        return cam ? cam_tail(V, v, join, cam_rows) : 0;
     }
     for (int i = 0; i < V; i++) {       // per-view K8 on the join stream, in view order (views may add into one another's buffers)
         const csplat_view &w = v[i];
@@ -3762,17 +4011,31 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
                                    w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered, w.bg, w.W, w.H, w.means3D, w.shs, w.scales,
                                    w.scale_modifier, w.rotations, w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii,
                                    w.geom, w.binning, w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
-                                   w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, w.dL_ddepth != nullptr))
+                                   w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, w.dL_ddepth != nullptr,
+                                   cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i]))
             return rc;
     }
-    return 0;
+    return cam ? cam_tail(V, v, join, cam_rows) : 0;
 }
 
 static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
     CSPLAT_REQUIRE(V >= 0 && (V == 0 || v != nullptr), "csplat_backward_views: bad view count");
     CSPLAT_REQUIRE(parts >= 1 && parts <= 3 && nslices >= 1 && slice >= 0 && slice < nslices, "csplat_backward_views_parts: bad parts / slice");
+    bool cam = false, cam_k8 = false;
+    for (int i = 0; i < V; i++) {
+        cam_k8 = cam_k8 || cam_k8_wanted(v[i]);
+        cam = cam || cam_k8_wanted(v[i]) || v[i].dL_dbg != nullptr;
+    }
+    if (cam) {
+        CSPLAT_REQUIRE(V <= K8_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per call");
+        CSPLAT_REQUIRE(parts == 3u && nslices == 1, "csplat_backward_views_parts: camera / background gradients are taken by the whole call only");
+        CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no camera / background gradient");
+        for (int i = 0; i < V; i++)
+            CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: camera gradients need scratch of csplat_backward_camera_scratch_bytes");
+    }
     for (int i = 0; i < V; i++)
-        if (v[i].dL_ddepth) return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices);
+        if (v[i].dL_ddepth) return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8);
+    int cam_rows[K8_MAX_VIEWS] = {0};
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     hipStream_t join = (hipStream_t)join_stream;
     bool shared = false;   // any view adding into another view's buffers: all K8 run on the join stream, in view order
@@ -3860,7 +4123,8 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
                                        w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered, w.bg, w.W, w.H, w.means3D, w.shs, w.scales, w.scale_modifier, w.rotations,
                                        w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii, w.geom, w.binning,
                                        w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
-                                       w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot))
+                                       w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, false,
+                                       cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i]))
                 return rc;
         }
         if (one_k8 && want_k8) {   // every view's K7 is queued on its own stream: the join stream waits for all of them, then ONE K8
@@ -3870,6 +4134,16 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
                 CSPLAT_REQUIRE(ev != nullptr, "csplat_backward_views: no event");
                 HIP_TRY(hipEventRecord(ev, (hipStream_t)v[i].stream));
                 HIP_TRY(hipStreamWaitEvent(join, ev, 0));
+            }
+            if (cam_k8) {      // (whole calls only: no slices)
+                ProfScope ps(PROF_K8_CAM, join);
+                const csplat_view &a = v[0];
+                const int nb = cdiv(a.P, 32);
+                CamSlabs sl;
+                for (int i = 0; i < V; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
+                k_preprocess_bwd_views_cam<128, 4, false><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
+                LAUNCH_CHECK();
+                return 0;
             }
             ProfScope ps(PROF_K8, join);
             const csplat_view &a = v[0];
@@ -3884,6 +4158,7 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
     };
     const int rc = body();
     const int r2 = side_streams ? fence_out(V, v, join) : 0;
+    if (!rc && !r2 && cam) return cam_tail(V, v, join, cam_rows);     // (behind every view's K8: the exit fence has joined their streams)
     return rc ? rc : r2;
 }
 int csplat_backward_views(int V, csplat_view *v, void *join_stream) { return backward_views_impl(V, v, join_stream, 3u, 0, 1); }

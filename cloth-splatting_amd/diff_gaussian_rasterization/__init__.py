@@ -9,8 +9,10 @@ Gradients are delivered for means3D, means2D (NDC-space screen gradient used by 
 scene_reconstruction/train_utils.py:290-292), shs, colors_precomp, opacities, scales, rotations, cov3D_precomp.
 The depth image D = sum_i T_i alpha_i z_i (view-space z, no background term) is differentiable, as in the depth fork of the rasterizer
 the reference pins: a loss on it reaches means3D, means2D, opacities, scales / rotations / cov3D_precomp (csplat_backward_depth; without
-a depth gradient the backward is exactly the colour-only one).  All compute is in libcsplat.so (csplat_forward_begin / _finish /
-csplat_backward).
+a depth gradient the backward is exactly the colour-only one).  The camera tensors of the settings (viewmatrix, projmatrix, campos, bg)
+receive gradients when they require grad (camera refinement, a learnable background; include/csplat.h csplat_view.dL_dview .. dL_dbg):
+only then are they inputs of the autograd Functions, so without them the call is exactly the one without camera gradients.  All compute
+is in libcsplat.so (csplat_forward_begin / _finish / csplat_backward).
 `rasterize_views` renders several independent views in one call, one HIP stream per view.
 """
 import contextlib as _contextlib
@@ -66,6 +68,35 @@ def _f32c_grad(t, device):
     return t.contiguous()
 
 
+def _cam_tensors(rs):
+    """the settings tensors that can take a gradient, in the order of a view's trailing argument group"""
+    return (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg)
+
+
+def _cam_group(rs):
+    """the view's trailing argument group when a settings tensor wants a gradient, else () -- the Functions then see exactly the
+    inputs they saw before camera gradients existed"""
+    cam = _cam_tensors(rs)
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in cam):
+        return cam
+    return ()
+
+
+_CAM_FIELDS = ("dL_dview", "dL_dproj", "dL_dcampos", "dL_dbg")
+_CAM_NUMEL = (16, 16, 3, 3)
+
+
+def _cam_outputs(need, dev):
+    """the gradient buffers of one view's camera group (None where no gradient is wanted)"""
+    return [torch.empty(n, dtype=torch.float32, device=dev) if w else None for w, n in zip(need, _CAM_NUMEL)]
+
+
+def _cam_returns(outs, cam_inputs):
+    """the buffers in the shape, dtype and device of the tensors the caller passed (autograd routes them on to the leaves, through a
+    `.transpose(0, 1)` view too)"""
+    return tuple(None if g is None else g.view(t.shape).to(device=t.device, dtype=t.dtype) for g, t in zip(outs, cam_inputs))
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
     """One camera (what GaussianRasterizer.forward calls, gaussian_renderer/__init__.py:156-164).  Since round 5 a single view goes
@@ -73,11 +104,12 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     on, the second forward phase is launched on the previous call's capacities and the counts are read AFTER the host has prepared the
     backward -- a camera-by-camera loop (the reference's train_utils.py:259-272) no longer leaves the GPU idle for a host round trip per
     camera.  Images, radii, depth and gradients are those of _RasterizeGaussians (tests: test_batched_views_equal_single_view_calls)."""
+    cam = _cam_group(raster_settings)
     if PER_CALL_SPECULATION and means3D.is_cuda:
         return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                              cov3Ds_precomp)
+                                              cov3Ds_precomp, *cam)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, *cam)
 
 
 PER_CALL_SPECULATION = True      # False: every call waits for its own counts (csplat_forward_begin / _finish, the path of rounds 1-4)
@@ -141,9 +173,11 @@ class _View:
         self.alloc.cb = None  # break the allocator <-> callback cycle: TEMP / TABLE die here, not at the next cyclic GC
         self.alloc = None
 
-    def backward(self, grad_color, saved, grad_depth=None):
+    def backward(self, grad_color, saved, grad_depth=None, cam_need=None):
         """K7 + K8 on the CURRENT stream; returns the per-input gradients in the Function's argument order.  grad_depth None: the
-        colour-only call (csplat_backward); else the depth path (csplat_backward_depth), where a missing grad_color counts as zero."""
+        colour-only call (csplat_backward); else the depth path (csplat_backward_depth), where a missing grad_color counts as zero.
+        cam_need: which of (viewmatrix, projmatrix, campos, bg) want a gradient -- any does: the camera path, csplat_backward_views with
+        this one view (it takes the chunks csplat_forward_finish leaves), and a second tuple of the four camera gradients is returned."""
         means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = saved
         rs, dev, P, M = self.rs, self.dev, self.P, self.M
         geom, binning, image = self.chunks
@@ -156,6 +190,31 @@ class _View:
         d_sh = new(P, M, 3) if sh is not None else None
         d_scale = new(P, 3) if scales is not None else None
         d_rot = new(P, 4) if rotations is not None else None
+        if cam_need is not None and any(cam_need):
+            grad_depth = _f32c_grad(grad_depth, dev)
+            scratch = new(max(int(_n.lib.csplat_backward_camera_scratch_bytes(P, self.num_rendered, self.W, self.H)), 256) // 4 + 1)
+            cam_out = _cam_outputs(cam_need, dev)
+            w = _n.CsplatView()
+            w.stream = _n.stream_handle(dev)
+            w.P, w.D, w.M, w.W, w.H = P, int(rs.sh_degree), M, self.W, self.H
+            w.scale_modifier, w.tanfovx, w.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
+            w.bg, w.means3D, w.shs, w.colors_precomp = _n.ptr(self.bg), _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp)
+            w.scales, w.rotations, w.cov3D_precomp = _n.ptr(scales), _n.ptr(rotations), _n.ptr(cov3Ds_precomp)
+            w.view, w.proj, w.campos = _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos)
+            w.out_color, w.radii = _n.ptr(color), _n.ptr(radii)
+            w.num_rendered = w.layout_rendered = self.num_rendered
+            w.geom, w.binning, w.image = _n.ptr(geom), _n.ptr(binning), _n.ptr(image)
+            w.dL_dpix, w.dL_ddepth, w.scratch = _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch)
+            w.dL_dmean2D, w.dL_dconic, w.dL_dopacity, w.dL_dcolor = _n.ptr(d_mean2D), _n.ptr(d_conic), _n.ptr(d_opac), _n.ptr(d_color)
+            w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh = _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh)
+            w.dL_dscale, w.dL_drot = _n.ptr(d_scale), _n.ptr(d_rot)
+            for f, g in zip(_CAM_FIELDS, cam_out):
+                setattr(w, f, _n.ptr(g))
+            with _n.on_device(dev):
+                rc = _n.lib.csplat_backward_views(1, C.addressof(w), w.stream)
+            _n.check(rc, "csplat_backward_views")
+            return (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
+                    d_cov3D if cov3Ds_precomp is not None else None), cam_out
         if grad_depth is not None:
             grad_depth = _f32c_grad(grad_depth, dev)
             scratch = torch.empty(max(int(_n.lib.csplat_backward_depth_scratch_bytes(P, self.num_rendered, self.W, self.H)), 256),
@@ -197,7 +256,9 @@ class _View:
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, *cam):
+        # cam: (viewmatrix, projmatrix, campos, bg) when one of them wants a gradient (_cam_group), else nothing
+        ctx.ncam = len(cam)
         v = _View(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs)
         v.begin()
         v.finish()
@@ -213,8 +274,12 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth):
         if grad_color is None and grad_depth is None:
-            return (None,) * 9
-        return ctx.view_state.backward(grad_color, ctx.saved_tensors, grad_depth) + (None,)
+            return (None,) * (9 + ctx.ncam)
+        if ctx.ncam and any(ctx.needs_input_grad[9:]):
+            v = ctx.view_state
+            g, cam_out = v.backward(grad_color, ctx.saved_tensors, grad_depth, ctx.needs_input_grad[9:])
+            return g + (None,) + _cam_returns(cam_out, _cam_tensors(v.rs))
+        return ctx.view_state.backward(grad_color, ctx.saved_tensors, grad_depth) + (None,) * (1 + ctx.ncam)
 
 
 _side_streams = {}
@@ -357,8 +422,12 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, settings, stacked, *flat):
+        # flat: V groups of NIN per-view inputs, then -- only when a settings tensor wants a gradient (_cam_group) -- V groups of
+        # (viewmatrix, projmatrix, campos, bg)
         V, n = len(settings), _RasterizeGaussiansBatch.NIN
-        assert len(flat) == V * n
+        assert len(flat) in (V * n, V * (n + 4))
+        ctx.cam = len(flat) > V * n
+        flat = flat[:V * n]
         views = []
         for i in range(V):
             means3D, _means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = flat[i * n:(i + 1) * n]
@@ -581,6 +650,9 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         V = len(views)
         dev = views[0].dev
         main = torch.cuda.current_stream(dev)
+        n = _RasterizeGaussiansBatch.NIN
+        cam_need = [tuple(ctx.needs_input_grad[2 + V * n + 4 * i:2 + V * n + 4 * i + 4]) for i in range(V)] if ctx.cam else [()] * V
+        tail = (None,) * (4 * V) if ctx.cam else ()
         if ctx.stacked:
             gcol = [None] * V if grads[0] is None else [grads[0][i] for i in range(V)]
             gdep = [grads[2 + 2 * i] for i in range(V)]
@@ -592,7 +664,14 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                                "those steps take no depth loss -- render the depth term in an eager step")
         active = [i for i in range(V) if gcol[i] is not None or gdep[i] is not None]
         if not active:
-            return (None, None) + (None,) * (V * _RasterizeGaussiansBatch.NIN)
+            return (None, None) + (None,) * (V * _RasterizeGaussiansBatch.NIN) + tail
+        want_cam = any(any(cam_need[i]) for i in active)
+        if want_cam and ctx.on_faith:
+            raise RuntimeError("diff_gaussian_rasterization: a camera / background gradient reached a forward launched on faith (a captured / "
+                               "replayed step); those steps take no camera gradient -- refine the camera in an eager step")
+        if want_cam and _K8_DEFER is not None:
+            raise RuntimeError("diff_gaussian_rasterization: a camera / background gradient reached a backward inside deferred_k8(); the sliced "
+                               "per-Gaussian backward takes no camera gradient")
         plan, ctx.plan = ctx.plan, None                         # (one use: the buffers are handed to autograd)
         if plan is not None and plan["acc"] and (int(_n.lib.csplat_debug_flags_query()) & 256):
             _n.grad_release(plan["sinks"])                      # (the bit-reproducible mode was switched on after the forward: its scratch
@@ -605,14 +684,23 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
               for i in active]
         for a, g in enumerate(gs):
             plan["sub"][a].dL_dpix = _n.ptr(g)
-        if any(gdep[i] is not None for i in active):
-            # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout, allocated here (never on
-            # the colour-only path) and cleared by the library -- the persistent zeroed records are not used by this call
+        cam_out = {}
+        if want_cam:
+            # the camera path (csplat_view.dL_dview .. dL_dbg): the gradient buffers of the views that want them; the scratch follows below
+            for a, i in enumerate(active):
+                cam_out[i] = _cam_outputs(cam_need[i], dev)
+                for f, g in zip(_CAM_FIELDS, cam_out[i]):
+                    setattr(plan["sub"][a], f, _n.ptr(g))
+                gs += [g for g in cam_out[i] if g is not None]
+        if want_cam or any(gdep[i] is not None for i in active):
+            # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout (the camera path: of the
+            # camera layout), allocated here (never on the colour-only path) and cleared by the library -- the persistent zeroed records
+            # are not used by this call
+            scratch_bytes = _n.lib.csplat_backward_camera_scratch_bytes if want_cam else _n.lib.csplat_backward_depth_scratch_bytes
             for a, i in enumerate(active):
                 v = views[i]
                 gd = _f32c_grad(gdep[i], dev) if gdep[i] is not None else None
-                buf = torch.empty(max(int(_n.lib.csplat_backward_depth_scratch_bytes(v.P, v.layout_rendered, v.W, v.H)), 256),
-                                  dtype=torch.uint8, device=dev)
+                buf = torch.empty(max(int(scratch_bytes(v.P, v.layout_rendered, v.W, v.H)), 256), dtype=torch.uint8, device=dev)
                 plan["sub"][a].dL_ddepth = _n.ptr(gd)
                 plan["sub"][a].scratch = buf.data_ptr()
                 plan["sub"][a].accmask &= ~SCRATCH_ZEROED
@@ -626,11 +714,13 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             #  gradient only when nobody else holds it, and would otherwise snapshot the still unwritten buffer into a copy)
             outs, plan["out"] = tuple(plan["out"]), None
             _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, ctx.saved_tensors)))
-            return (None, None) + outs
+            return (None, None) + outs + tail
         with _n.on_device(dev):
             rc = _n.lib.csplat_backward_views(len(active), C.cast(plan["sub"], C.c_void_p), main.cuda_stream)
         _n.check(rc, "csplat_backward_views")
-        return (None, None) + tuple(plan["out"])
+        if ctx.cam:
+            tail = sum((_cam_returns(cam_out.get(i, (None,) * 4), _cam_tensors(views[i].rs)) for i in range(V)), ())
+        return (None, None) + tuple(plan["out"]) + tail
 
 
 def rasterize_views(settings, inputs, stacked=False):
@@ -649,6 +739,9 @@ def rasterize_views(settings, inputs, stacked=False):
         if ((sc is None or ro is None) and cov is None) or ((sc is not None or ro is not None) and cov is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         flat += [kw["means3D"], kw["means2D"], shs, cp, kw["opacities"], sc, ro, cov]
+    if any(_cam_group(rs) for rs in settings):      # (a settings tensor wants a gradient: every view's camera group follows)
+        for rs in settings:
+            flat += list(_cam_tensors(rs))
     res = _RasterizeGaussiansBatch.apply(tuple(settings), bool(stacked), *flat)
     if stacked:
         colors = res[0]

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CSPLAT_ABI_VERSION 7   /* 7: the depth image's gradient (csplat_view.dL_ddepth, csplat_backward_depth, csplat_backward_depth_scratch_bytes); 6 (round 6): csplat_backward_views_parts / _slice_rows, csplat_gnn_edge_length_refine, csplat_rollout_head / _decode / _integrate, csplat_gnn_edge_features_ordered, csplat_gnn_rows_chain(_pack), csplat_binning_fields; round 4: csplat_view.busy_tiles / .valid, csplat_rows_dot_fwd's extra argument; 3: the binning chunk's layout (bbits, bmask); 4 (round 5): csplat_gather_words kind 2; 5: csplat_gnn_edge_mlp3* (e0_absmax, modes), csplat_absmax, csplat_linear_narrow128 */
+#define CSPLAT_ABI_VERSION 8   /* 8: camera and background gradients (csplat_view.dL_dview / dL_dproj / dL_dcampos / dL_dbg, csplat_backward_camera_scratch_bytes); 7: the depth image's gradient (csplat_view.dL_ddepth, csplat_backward_depth, csplat_backward_depth_scratch_bytes); 6 (round 6): csplat_backward_views_parts / _slice_rows, csplat_gnn_edge_length_refine, csplat_rollout_head / _decode / _integrate, csplat_gnn_edge_features_ordered, csplat_gnn_rows_chain(_pack), csplat_binning_fields; round 4: csplat_view.busy_tiles / .valid, csplat_rows_dot_fwd's extra argument; 3: the binning chunk's layout (bbits, bmask); 4 (round 5): csplat_gather_words kind 2; 5: csplat_gnn_edge_mlp3* (e0_absmax, modes), csplat_absmax, csplat_linear_narrow128 */
 
 /* scratch chunks requested through the allocator callback */
 #define CSPLAT_CHUNK_GEOM 0    /* per-Gaussian state, kept for backward */
@@ -81,6 +81,11 @@ size_t csplat_backward_scratch_bytes(int P, int64_t R); /* per-Gaussian accumula
  * bit-reproducible mode, and one float per (list segment, pixel) for the depth partials.  Never smaller than
  * csplat_backward_scratch_bytes(P, R). */
 size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H);
+/* the scratch of a backward call that takes a camera or background gradient (any view of csplat_backward_views* with dL_dview,
+ * dL_dproj, dL_dcampos or dL_dbg set -- then EVERY view of that call needs this size): the depth layout above, then the camera slab
+ * (one 35-float row per K8 workgroup) and the background slab (256 rows of 3).  Never smaller than
+ * csplat_backward_depth_scratch_bytes(P, R, W, H). */
+size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H);
 
 /* Byte offsets of the named sub-buffers inside a chunk (for tests / debugging; see DESIGN.md "HBM layout").
  * geom:    0 depth f32[P] | 1 xy f32[P][2] | 2 conic_opacity f32[P][4] | 3 rgb f32[P][3] | 4 cov3D f32[P][6]
@@ -172,6 +177,22 @@ typedef struct csplat_view {
                                      * backward call has one, the call takes the depth path (extra launches, see csplat_backward_depth;
                                      * every view's scratch sized by csplat_backward_depth_scratch_bytes; not for views launched on faith,
                                      * at most 8 views); when none has, the call is exactly the ABI 6 one */
+    /* ABI 8, backward outputs (device, each NULL = not wanted): the gradients of the camera tensors of the view, WRITTEN (never added).
+     * Notation: V = view, Pm = proj (row-vector form, flat index 4 row + col), ph = [m, 1] for a mean m; pv = ph V, hom = ph Pm,
+     * ndc = hom[:2] / (hom[3] + 1e-7), Rw = V[:3,:3]^T, cov2D = J(pv) Rw Sigma Rw^T J(pv)^T, the SH direction (m - campos) / |m - campos|,
+     * the depth z = pv[2], C = sum T_i alpha_i c_i + T_final bg.  The gradients are the chain rule through exactly these uses, with the
+     * conventions of the Gaussian gradients: tile lists, sort order, culling and termination are constants, alpha is straight-through
+     * at the 0.99 cap, the 1.3 tanfov clamp stops the gradient of a clamped axis of pv, radii are not differentiable.
+     *   dL_dview[16]   sum over visible Gaussians of ph (x) dL/dpv (covariance term through J(pv), the depth term dL/dz when dL_ddepth
+     *                  is set), plus (J^T dL/dT)^T on the upper 3x3 block (T = J Rw); column 3 (flat 3, 7, 11, 15) is exactly 0
+     *   dL_dproj[16]   sum of ph (x) dL/dhom through the projected centre only (J uses fx = W / (2 tanfovx), not Pm); column 2 is 0
+     *   dL_dcampos[3]  minus the sum of the SH-direction part of dL/dmean3D; 0 with colors_precomp
+     *   dL_dbg[3]      sum_pix dL/dC_c(pix) T_final(pix)
+     * The sums over Gaussians run in a fixed order (a slab row per K8 workgroup and view, then a fixed-order sum; no float atomics), so
+     * they are bit-reproducible whenever their per-Gaussian inputs are (csplat_debug_flags bit 256).  Every view's scratch is sized by
+     * csplat_backward_camera_scratch_bytes.  Not for views launched on faith, nor csplat_backward_views_parts with parts != 3 or
+     * nslices != 1; at most 8 views.  All NULL: the call is exactly the ABI 7 one. */
+    float *dL_dview, *dL_dproj, *dL_dcampos, *dL_dbg;
 } csplat_view;
 int csplat_forward_views(int V, csplat_view *views, csplat_alloc_fn alloc, void *join_stream);
 /* The same call with its one host read (the views' counts) DEFERRED.  When the second phase can be launched on the previous call's
@@ -433,6 +454,7 @@ int csplat_mesh_transform_bwd_views(void *stream, int T, int P, int V, const int
  *   0 K1 preprocess | 1 K2 scan | 2 K3 key emission | 3 K4 radix sort (all passes) | 4 K5 tile ranges
  *   5 K6 compositing fwd | 6 K7 compositing bwd | 7 K8 preprocess bwd | 8 distCUDA2 | 9 GNN kernels
  *   10 depth partials prepass | 11 K7 of the depth path | 12 K8 of the depth path (csplat_backward_depth, dL_ddepth)
+ *   13 K8 of the camera path | 14 the camera path's background partials and fixed-order sums (csplat_view.dL_dview .. dL_dbg)
  * csplat_prof_read synchronises the recorded events of class k, returns their summed duration (ms) and the
  * number of brackets, and recycles the events. */
 int csplat_prof_enable(unsigned mask);
