@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CSPLAT_LIB=<path>: load another build of the library (same-box A/B of kernel variants: tools/ab_libs.sh) -- the shipped file is never
 # overwritten by an experiment
 LIB_PATH = os.environ.get("CSPLAT_LIB") or os.path.join(_HERE, "libcsplat.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -34,6 +34,7 @@ EXPORTS = {
     "csplat_backward_scratch_bytes": (_sz, [_i, _i64]),
     "csplat_backward_depth_scratch_bytes": (_sz, [_i, _i64, _i, _i]),
     "csplat_backward_camera_scratch_bytes": (_sz, [_i, _i64, _i, _i]),
+    "csplat_backward_feature_scratch_bytes": (_sz, [_i, _i64, _i, _i]),
     "csplat_geom_layout": (_i, [_i, C.POINTER(_sz)]),
     "csplat_binning_layout": (_i, [_i64, _i, _i, C.POINTER(_sz)]),
     "csplat_binning_fields": (_i, [_i64, _i, _i, C.POINTER(_sz)]),
@@ -340,7 +341,9 @@ class CsplatView(C.Structure):
                 [("accmask", C.c_uint)] +
                 [(n, _vp) for n in ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D",
                                     "dL_dsh", "dL_dscale", "dL_drot")] + [("busy_tiles", _i), ("valid", _vp), ("dL_ddepth", _vp)] +
-                [(n, _vp) for n in ("dL_dview", "dL_dproj", "dL_dcampos", "dL_dbg")])
+                [(n, _vp) for n in ("dL_dview", "dL_dproj", "dL_dcampos", "dL_dbg")] +
+                [("features", _vp), ("n_features", _i)] + [(n, _vp) for n in ("out_features", "out_alpha", "dL_dfeatures", "dL_dalpha",
+                                                                                "dL_dfeat_in")])
 
 
 ACC_OPACITY, ACC_COLOR, ACC_MEAN3D, ACC_COV3D, ACC_SH, ACC_SCALE, ACC_ROT = 1, 2, 4, 8, 16, 32, 64
@@ -380,7 +383,8 @@ def group_by_key(keys, n_keys):
 
 PROF_CLASSES = ["K1_preprocess", "K2_scan", "K3_emit_keys", "K4_radix_sort", "K5_tile_ranges", "K6_render_fwd",
                 "K7_render_bwd", "K8_preprocess_bwd", "K9_dist2", "GNN", "K7_depth_partials", "K7_depth_bwd", "K8_depth_bwd",
-                "K8_camera_bwd", "camera_sums"]
+                "K8_camera_bwd", "camera_sums", "K6_features", "K7_feature_partials", "K7_feature_bwd", "feature_grads"]
+MAX_FEATURES = 6      # csplat.h: CSPLAT_MAX_FEATURES
 
 
 def prof_enable(classes=()):

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <chrono>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -1241,6 +1242,7 @@ struct WordStreamT {
 };
 
 struct Trip { float4 a, b; float2 c; int pos; uint32_t id; };   // the lane's survivor of a group (row r's), pos = list position or -1
+struct TripF { float4 a, b; float2 c; int pos; uint32_t id; float wf; };   // (K7's feature path) + sum_c gf_c f_c of the survivor at the pixel
 
 // ---- which entries a block BLENDED (round 4).  K5b's masks say which entries can REACH a 4x4 block (ellipse vs box); K6 finds out which
 // of them any pixel of the block actually blends -- alpha >= 1/255 at some pixel centre that is still open -- and K7 only ever does
@@ -1761,7 +1763,13 @@ constexpr int RING7 = SEG;     // a segment's survivors of one block, padded to 
 // adds g (T_i z_i - D_behind_i / (1 - alpha_i)) to dL/dalpha, with D_behind_i = (sum of the partials dpart of this and the later segments
 // of the tile, k_depth_bwd_partials) - (the in-segment prefix of T alpha z through entry i), and the block's sum of g T_i alpha_i goes to
 // record slot 9 (dL/dz of the Gaussian, K8).  With DEPTH = false every added line below is compiled out.
-template <bool DET, bool DEPTH = false>
+// FEAT (the feature / alpha path, k_feature_composite_bwd_views, always with DEPTH; never the default launches): with the pixel's feature
+// gradients gf_c = dL_dfeat[c][pix] (c < nf <= 6), wf_i = sum_c gf_c f[id_i][c] and the alpha image's gradient gA = dL_dalpha[pix], adds
+// Tr_i wf_i - (Fsuf - gA T_final - SF_i) / (1 - alpha_i) to dL/dalpha, where Fsuf = the prepass partials (k_feature_bwd_partials: T alpha wf
+// summed per segment) of this and the tile's later segments and SF_i = the in-segment prefix of T alpha wf through entry i; the block's
+// sums of gf_c T_i alpha_i go to record slots 10 + c (dL/df of the Gaussian: k_feature_grads).  Lanes 6, 7, 10, 13, 14, 15 of a row -- free
+// in the default record layout -- carry them, so an (entry, block) pair is still ONE atomic request to one 64-byte record.
+template <bool DET, bool DEPTH = false, bool FEAT = false>
 __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int gx, const int2 *__restrict__ ranges,
                                                    const uint32_t *__restrict__ ids_sorted,
                                                    const unsigned long long *__restrict__ bbits, const float4 *__restrict__ recA,
@@ -1772,13 +1780,20 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
                                                    const float *__restrict__ out_color, const float *__restrict__ dL_dpix,
                                                    float *__restrict__ acc, float *__restrict__ det,
                                                    unsigned long long *stamp = nullptr, int wg = (int)blockIdx.x,
-                                                   const float *__restrict__ dL_ddepth = nullptr, const float *__restrict__ dpart = nullptr) {
-    constexpr int DS = DEPTH ? 10 : 9;                              // floats per stored (entry, block) record in the DET mode
+                                                   const float *__restrict__ dL_ddepth = nullptr, const float *__restrict__ dpart = nullptr,
+                                                   const float *__restrict__ features = nullptr, int nf = 0,
+                                                   const float *__restrict__ dL_dfeat = nullptr, const float *__restrict__ dL_dalpha = nullptr,
+                                                   const float *__restrict__ wpart = nullptr) {
+    static_assert(!FEAT || DEPTH, "the feature path is instantiated on the depth path");
+    constexpr int DS = FEAT ? 16 : (DEPTH ? 10 : 9);                // floats per stored (entry, block) record in the DET mode
+    using TT = std::conditional_t<FEAT, TripF, Trip>;
     __shared__ int s_ring[4][RING7];
     __shared__ float4 s_ra[4][64], s_rb[4][64];                     // one batch of 64 survivors' records per wave (see `stage`)
     __shared__ float s_rc[4][64];
-    __shared__ uint32_t s_rid[DET ? 1 : 4][DET ? 1 : 64];
+    constexpr bool IDS = !DET || FEAT;                              // the survivors' Gaussian ids are staged
+    __shared__ uint32_t s_rid[IDS ? 4 : 1][IDS ? 64 : 1];
     __shared__ float s_rz[DEPTH ? 4 : 1][DEPTH ? 64 : 1];          // (DEPTH) the survivors' view-space depths
+    __shared__ float s_rf[FEAT ? 4 : 1][FEAT ? CSPLAT_MAX_FEATURES : 1][FEAT ? 64 : 1];   // (FEAT) the survivors' feature rows
     // in-kernel stamps (csplat_debug_stamps; tools/k7_stamps.py): wave 0 of every workgroup leaves s_memtime at the phase boundaries
     unsigned long long *my_stamp = stamp ? stamp + ((size_t)blockIdx.y * gridDim.x + (size_t)wg) * 12 : nullptr;
     auto mark = [&](int k) {
@@ -1849,6 +1864,25 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
             for (int s2 = slot; s2 < s_end; s2++) Dsuf += dpart[(size_t)s2 * 256 + blk * 16 + l16];
         }
     }
+    float gf[FEAT ? CSPLAT_MAX_FEATURES : 1], OFA = 0.f;  // (FEAT) the pixel's feature gradients; Fsuf - gA T_final
+    if constexpr (FEAT) {
+#pragma unroll
+        for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) gf[c] = 0.f;
+        if (live) {
+            float Fsuf = 0.f, gA = 0.f;
+            if (inside) {
+                if (dL_dfeat)
+#pragma unroll
+                    for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) gf[c] = c < nf ? dL_dfeat[c * HW + pix] : 0.f;
+                if (dL_dalpha) gA = dL_dalpha[pix] * final_T[pix];
+            }
+            if (dL_dfeat) {
+                const int s_end = seg_offset[tile + 1];
+                for (int s2 = slot; s2 < s_end; s2++) Fsuf += wpart[(size_t)s2 * 256 + blk * 16 + l16];
+            }
+            OFA = Fsuf - gA;
+        }
+    }
     // the wave's survivor list: list positions of the set bits, in order, padded with -1 to a multiple of four (wave-private LDS)
     int *ring = s_ring[w];
     int total = 0;
@@ -1878,7 +1912,7 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
         // before the first group; later batches (a block that blended more than 64 of the segment's 256 entries) wait once per batch.
         float4 *ra = s_ra[w], *rb = s_rb[w];
         float *rc = s_rc[w];
-        uint32_t *rid = s_rid[DET ? 0 : w];
+        uint32_t *rid = s_rid[IDS ? w : 0];
         auto stage = [&](int b0) {      // survivors b0 .. b0 + 63 -> the strip
             const int idx = b0 + lane;
             const int pos = idx < total ? ring[idx] : -1;
@@ -1886,15 +1920,19 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
             const float4 A = recA[ri], B = recB[ri];
             const float C = reinterpret_cast<const float *>(recC)[2 * (size_t)ri];      // (c.y, the depth, is K6's)
             uint32_t id = 0u;
-            if (!DET) id = ids_sorted[pos >= 0 ? rx + (uint32_t)pos : rx];
+            if (IDS) id = ids_sorted[pos >= 0 ? rx + (uint32_t)pos : rx];
             ra[lane] = A; rb[lane] = B; rc[lane] = C;
-            if (!DET) rid[lane] = id;
+            if (IDS) rid[lane] = id;
             if constexpr (DEPTH) s_rz[w][lane] = reinterpret_cast<const float *>(recC)[2 * (size_t)ri + 1];
+            if constexpr (FEAT)
+#pragma unroll
+                for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) s_rf[w][c][lane] = c < nf ? features[(size_t)id * nf + c] : 0.f;
         };
         stage(0);
         const float OD = oc0 * dp0 + oc1 * dp1 + oc2 * dp2;
         float T = 1.f, S = 0.f;
         float SD = 0.f;                 // (DEPTH) in-segment running sum of T alpha z
+        float SF = 0.f;                 // (FEAT) in-segment running sum of T alpha wf
         if (ncontrib > seg_lo) {
             T = ck.x;
             S = ck.y * dp0 + ck.z * dp1 + ck.w * dp2;
@@ -1909,22 +1947,31 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
 #pragma unroll
         for (int q = 0; q < 16; q++) red_t_ = l16 == q ? RED_T[q] : red_t_;
         if constexpr (DEPTH) red_t_ = l16 == 5 ? 9 : red_t_;          // (lane 5 of a row carries the depth sum: slot 9, same 64-byte record)
+        // (FEAT) lanes 6, 7, 10, 13, 14, 15 of a row carry the feature sums of channels 0..5: slots 10..15
+        const int fch = !FEAT ? -1 : (l16 == 6 ? 0 : (l16 == 7 ? 1 : (l16 == 10 ? 2 : (l16 == 13 ? 3 : (l16 == 14 ? 4 : (l16 == 15 ? 5 : -1))))));
+        if constexpr (FEAT) red_t_ = (fch >= 0 && fch < nf) ? 10 + fch : red_t_;
         const bool red_active = red_t_ >= 0;
         const int red_t = red_active ? red_t_ : 0;
         int base = 0;                   // first survivor of the batch in the strip
         // (every LDS read of the loop is unconditional, with a clamped slot: the compiler's lgkmcnt bookkeeping assumes the path on which
         //  a conditional read was NOT issued, and then waits for the youngest ones)
-        auto fetch = [&](Trip &t, int k) {
+        auto fetch = [&](TT &t, int k) {
             const int sl = 4 * k + r;
             t.pos = ring[base + sl];
             t.a = ra[sl]; t.b = rb[sl]; t.c.x = rc[sl];
             if (!DET) t.id = rid[sl];
             if constexpr (DEPTH) t.c.y = s_rz[w][sl];
+            if constexpr (FEAT) {
+                float wf = 0.f;
+#pragma unroll
+                for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) wf += gf[c] * s_rf[w][c][sl];
+                t.wf = wf;
+            }
         };
         // N groups at once, statement by statement: a group is one dependent chain of ~110 vector instructions (~10 cycles from one to the
         // next: ~1,200 cycles a group for a wave on its own, tools/k7_stamps.py -- the same with the atomics removed); groups k and k + 1
         // only meet where T and S pass from one to the other, so written side by side the two chains fill each other's waits.
-        auto processN = [&](auto NC, const Trip *const *t) {
+        auto processN = [&](auto NC, const TT *const *t) {
             constexpr int N = decltype(NC)::value;
             float dx[N], dy[N], G[N], al[N], F[N], gdot[N], Tr[N], Sr[N], dcc[N], tot[N];
             bool act[N];
@@ -1956,10 +2003,16 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
                     zs[u] = v;
                 }
             }
+            float SFr[N];
+            if constexpr (FEAT) {
+#pragma unroll
+                for (int u = 0; u < N; u++) rows_scan_add(act[u] ? dcc[u] * t[u]->wf : 0.f, SF, SFr[u], SF);
+            }
 #pragma unroll
             for (int u = 0; u < N; u++) {
                 float dL_dalpha = act[u] ? Tr[u] * gdot[u] - (OD - Sr[u]) * __builtin_amdgcn_rcpf(F[u]) : 0.f;
                 if constexpr (DEPTH) dL_dalpha += act[u] ? gz * (Tr[u] * t[u]->c.y - (Dsuf - SDr[u]) * __builtin_amdgcn_rcpf(F[u])) : 0.f;
+                if constexpr (FEAT) dL_dalpha += act[u] ? Tr[u] * t[u]->wf - (OFA - SFr[u]) * __builtin_amdgcn_rcpf(F[u]) : 0.f;
                 // Round 6: the row's lanes no longer form the nine GRADIENT values and reduce each over the 16 pixels (14 multiplications + a
                 // 4-level butterfly of ~24 DPP operations); they reduce the MOMENTS of m = G dL/dalpha about the Gaussian's centre,
                 //   M0 = sum m, Mx = sum m dx, My = sum m dy, Mxx = sum m dx^2, Mxy = sum m dx dy, Myy = sum m dy^2,
@@ -1997,6 +2050,15 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
                 // column t of the block's lane grid keeps: t = 0 the plain sums, t = 1 the dx-weighted, t = 2 the dx^2-weighted, t = 3 colours 1 / 2
                 tot[u] = lq0 ? R : (lq1 ? b1 : (lq2 ? b2 : X));
                 if constexpr (DEPTH) tot[u] = l16 == 5 ? zs[u] : tot[u];
+                if constexpr (FEAT) {   // the block's sums of gf_c T alpha over the row's 16 pixels (dL/df_c of the survivor)
+                    float fsel = tot[u];
+#pragma unroll
+                    for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) {
+                        const float fsum = row_total(gf[c] * dcc[u]);
+                        fsel = fch == c ? fsum : fsel;
+                    }
+                    tot[u] = fsel;
+                }
             }
             // (every survivor of the list was blended at one of the block's pixels: the row always has something to add, padding aside)
 #pragma unroll
@@ -2007,8 +2069,8 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
                     else asm volatile("" :: "v"(tot[u]));        // (elimination build CSPLAT_K7X=1: the sums are formed, nothing is sent)
                 }
         };
-        auto process = [&](const Trip &t0) { const Trip *t[1] = {&t0}; processN(std::integral_constant<int, 1>{}, t); };
-        auto process2 = [&](const Trip &t0, const Trip &t1) { const Trip *t[2] = {&t0, &t1}; processN(std::integral_constant<int, 2>{}, t); };
+        auto process = [&](const TT &t0) { const TT *t[1] = {&t0}; processN(std::integral_constant<int, 1>{}, t); };
+        auto process2 = [&](const TT &t0, const TT &t1) { const TT *t[2] = {&t0, &t1}; processN(std::integral_constant<int, 2>{}, t); };
         bool first = true;
         // (round 6, tried and dropped: requesting the NEXT batch's records before this batch's atomics are issued -- vmcnt retires in order and
         //  a load queued behind a float atomic waits for it -- costs ten registers across the batch (44 bytes of scratch at the 64-register
@@ -2017,7 +2079,7 @@ __device__ __forceinline__ void composite_bwd_body(int tiles, int W, int H, int 
             if (!first) stage(base);
             const int ngroups = min(64, total - base) >> 2, last_g = ngroups - 1;
             // two groups in flight: group k + 2 is read from the strip when group k has been composited
-            Trip ta, tb;
+            TT ta, tb;
             fetch(ta, 0);
             fetch(tb, min(1, last_g));
             if (first) {
@@ -2237,6 +2299,182 @@ __global__ __launch_bounds__(256) void k_depth_composite_bwd_views(DepthTable ta
                                   (int)blockIdx.x, w.dL_ddepth, w.dpart);
 }
 __global__ __launch_bounds__(256) void k_depth_det_reduce_views(int P, DetTable tab) { det_reduce_views_body<10>(P, tab); }
+
+// ------------------------------------------------------------------------------------------- feature channels and the alpha image
+// (ABI 9: csplat_view.features / out_features / out_alpha and their gradients.)  Launched only when a view asks for them; K6, K7 and K8
+// of the default, depth and camera paths are untouched.
+// Forward: a pass BEHIND K6, one thread per pixel and one workgroup per tile.  The pixel walks its tile's segments; each segment starts
+// from K6's checkpointed T and visits the entries its block blended (K6's bbits words), with K7's blend test (alpha, 1/255, n_contrib):
+// feat[c] = sum T alpha f[id][c] over exactly the entries the colour blended, front to back.  alpha = 1 - final_T, the factor of the colour's
+// background term.  (K6 itself is not touched: a feature variant of it would carry F more accumulators through its transmittance chain.)
+struct FeatFwdView {
+    const int2 *ranges;
+    const uint32_t *ids_sorted;
+    const unsigned long long *bbits;
+    const float4 *recA, *recB;
+    const int *seg_offset;
+    const float4 *ckpt;
+    const float *final_T;
+    const uint32_t *n_contrib;
+    const float *features;    // [P][nf], NULL when nf = 0
+    float *out_features;      // [nf][H][W], NULL: not asked for
+    float *out_alpha;         // [H][W], NULL: not asked for
+    int nf, W, H, gx, tiles;  // tiles = 0: the view has no list entries (feat = 0, alpha = 0)
+};
+struct FeatFwdTable { FeatFwdView v[B2_MAX_VIEWS]; };
+// one pixel's walk over the blended entries of one segment (slot) from transmittance T: calls f(T alpha, list position) per blended entry
+template <typename Fn>
+__device__ __forceinline__ void walk_segment(const float4 *__restrict__ recA, const float4 *__restrict__ recB,
+                                             const unsigned long long *__restrict__ bbits, int slot, int blk, int seg_lo, int nc,
+                                             uint32_t rx, float fx, float fy, float T, Fn &&f) {
+    constexpr int NW = SEG / 64;
+    const unsigned long long *bw = bbits + ((size_t)slot * 16 + (size_t)blk) * NW;
+    for (int c = 0; c < NW; c++) {
+        unsigned long long m = bw[c];
+        while (m) {
+            const int pos = seg_lo + 64 * c + __builtin_ctzll(m);
+            m &= m - 1ull;
+            if (pos >= nc) return;
+            const uint32_t ri = rx + (uint32_t)pos;
+            const float4 A = recA[ri], B = recB[ri];
+            const float dx = A.x - fx, dy = A.y - fy;
+            const float power = -0.5f * (A.z * dx * dx + B.x * dy * dy) - A.w * dx * dy;
+            const float a = fminf(0.99f, B.y * __expf(power));
+            if (power > 0.f || a < ALPHA_MIN) continue;
+            f(a * T, ri);
+            T *= 1.f - a;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_feature_fwd_views(FeatFwdTable tab) {
+    const FeatFwdView &w = tab.v[blockIdx.y];
+    const int tile = blockIdx.x;
+    const int ntiles = w.gx * ((w.H + CSPLAT_TILE - 1) / CSPLAT_TILE);
+    if (tile >= ntiles) return;
+    const int blk = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+    const int px = (tile % w.gx) * CSPLAT_TILE + (blk & 3) * 4 + (l16 & 3);
+    const int py = (tile / w.gx) * CSPLAT_TILE + (blk >> 2) * 4 + (l16 >> 2);
+    if (px >= w.W || py >= w.H) return;
+    const int pix = py * w.W + px;
+    float acc[CSPLAT_MAX_FEATURES];
+#pragma unroll
+    for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) acc[c] = 0.f;
+    float alpha = 0.f;
+    if (w.tiles > 0) {
+        alpha = 1.f - w.final_T[pix];
+        const int nc = (int)w.n_contrib[pix];
+        if (w.nf > 0 && nc > 0) {
+            const int s0 = w.seg_offset[tile], s1 = w.seg_offset[tile + 1];
+            const uint32_t rx = (uint32_t)w.ranges[tile].x;
+            const float *feat = w.features;
+            const int nf = w.nf;
+            for (int slot = s0; slot < s1; slot++) {
+                const int seg_lo = (slot - s0) * SEG;
+                if (nc <= seg_lo) break;
+                walk_segment(w.recA, w.recB, w.bbits, slot, blk, seg_lo, nc, rx, (float)px, (float)py,
+                             w.ckpt[(size_t)slot * 256 + threadIdx.x].x, [&](float wt, uint32_t ri) {
+                                 const float *fr = feat + (size_t)w.ids_sorted[ri] * nf;
+#pragma unroll
+                                 for (int c = 0; c < CSPLAT_MAX_FEATURES; c++)
+                                     if (c < nf) acc[c] += wt * fr[c];
+                             });
+            }
+        }
+    }
+    const size_t HW = (size_t)w.H * w.W;
+    if (w.out_features)
+#pragma unroll
+        for (int c = 0; c < CSPLAT_MAX_FEATURES; c++)
+            if (c < w.nf) w.out_features[c * HW + pix] = acc[c];
+    if (w.out_alpha) w.out_alpha[pix] = alpha;
+}
+
+// Backward.  K7 needs, per entry, what lies behind it in every channel, weighted by the pixel's feature gradients; a prepass (as the depth
+// path's) leaves per (segment, pixel) wpart = sum over the segment's blended entries of T alpha wf, wf = sum_c dL/dfeat_c f[id][c] -- one
+// float per (segment, pixel) whatever F, in backward scratch only; the forward keeps nothing for it.
+struct FeatView {
+    DepthView d;
+    const int32_t *radii;
+    const float *features;    // [P][nf]
+    const float *dL_dfeat;    // [nf][H][W], NULL: no feature gradient in this view
+    const float *dL_dalpha;   // [H][W], NULL: no alpha gradient in this view
+    float *wpart;             // [slots][256]
+    float *dL_dfeat_in;       // [P][nf] (written, or added when an earlier view of the call has the same buffer), NULL: not wanted
+    int nf, P;
+    unsigned accmask;
+};
+struct FeatTable { FeatView v[B2_MAX_VIEWS]; int n; };
+__global__ __launch_bounds__(256) void k_feature_bwd_partials(FeatTable tab) {
+    const FeatView &fv = tab.v[blockIdx.y];
+    const DepthView &w = fv.d;
+    if (!fv.dL_dfeat || w.tiles == 0) return;
+    const int slot = blockIdx.x;
+    const int *seg_offset = w.b.seg_offset;
+    if (slot >= seg_offset[w.tiles]) return;
+    const int tile = w.b.slot_tile[slot];
+    const int seg_lo = (slot - seg_offset[tile]) * SEG;
+    const int blk = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+    const uint32_t *blk_hi = reinterpret_cast<const uint32_t *>(seg_offset) + w.tiles + 1 + tile * 16;
+    const int px = (tile % w.gx) * CSPLAT_TILE + (blk & 3) * 4 + (l16 & 3);
+    const int py = (tile / w.gx) * CSPLAT_TILE + (blk >> 2) * 4 + (l16 >> 2);
+    float S = 0.f;
+    if ((int)blk_hi[blk] > seg_lo && px < w.W && py < w.H) {
+        const int pix = py * w.W + px;
+        const int nc = (int)w.b.n_contrib[pix];
+        if (nc > seg_lo) {
+            const int nf = fv.nf;
+            const size_t HW = (size_t)w.H * w.W;
+            float gf[CSPLAT_MAX_FEATURES];
+#pragma unroll
+            for (int c = 0; c < CSPLAT_MAX_FEATURES; c++) gf[c] = c < nf ? fv.dL_dfeat[c * HW + pix] : 0.f;
+            const float *feat = fv.features;
+            walk_segment(w.b.recA, w.b.recB, w.b.bbits, slot, blk, seg_lo, nc, (uint32_t)w.b.ranges[tile].x, (float)px, (float)py,
+                         w.b.ckpt[(size_t)slot * 256 + threadIdx.x].x, [&](float wt, uint32_t ri) {
+                             const float *fr = feat + (size_t)w.b.ids_sorted[ri] * nf;
+                             float wf = 0.f;
+#pragma unroll
+                             for (int c = 0; c < CSPLAT_MAX_FEATURES; c++)
+                                 if (c < nf) wf += gf[c] * fr[c];
+                             S += wt * wf;
+                         });
+        }
+    }
+    fv.wpart[(size_t)slot * 256 + threadIdx.x] = S;
+}
+template <bool DET>
+__global__ __launch_bounds__(256) void k_feature_composite_bwd_views(FeatTable tab) {
+    const FeatView &fv = tab.v[blockIdx.y];
+    const DepthView &w = fv.d;
+    if (w.tiles == 0) return;
+    const B2View &b = w.b;
+    composite_bwd_body<DET, true, true>(w.tiles, w.W, w.H, w.gx, b.ranges, b.ids_sorted, b.bbits, b.recA, b.recB, b.recC, b.R, b.seg_offset,
+                                        b.slot_tile, b.ckpt, b.final_T, b.n_contrib, b.out_color, b.dL_dpix, b.acc, b.det, nullptr,
+                                        (int)blockIdx.x, w.dL_ddepth, w.dpart, fv.features, fv.nf, fv.dL_dfeat, fv.dL_dalpha, fv.wpart);
+}
+__global__ __launch_bounds__(256) void k_feature_det_reduce_views(int P, DetTable tab) { det_reduce_views_body<16>(P, tab); }
+// record slots 10 .. 10 + nf - 1 of every view -> dL_dfeat_in, the views in call order (a buffer shared with an earlier view of the call
+// is added to: a fixed order).  Runs between K7 and K8; slots 12..15 are cleared here when the records must be left zero (K8's
+// clear_record takes 0..11).
+__global__ __launch_bounds__(256) void k_feature_grads(FeatTable tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    for (int vi = 0; vi < tab.n; vi++) {
+        const FeatView &fv = tab.v[vi];
+        if (i >= fv.P) continue;
+        float *acc = fv.d.b.acc + (size_t)i * ACC_STRIDE;
+        const bool vis = fv.radii[i] > 0;
+        if (fv.dL_dfeat_in) {
+            bool add = false;
+            for (int vj = 0; vj < vi; vj++) add = add || tab.v[vj].dL_dfeat_in == fv.dL_dfeat_in;
+            float *out = fv.dL_dfeat_in + (size_t)i * fv.nf;
+            for (int c = 0; c < fv.nf; c++) {
+                const float g = vis ? acc[10 + c] : 0.f;
+                out[c] = add ? out[c] + g : g;
+            }
+        }
+        if (vis && (fv.accmask & CSPLAT_SCRATCH_ZEROED))
+            *reinterpret_cast<float4 *>(acc + 12) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
 
 // ------------------------------------------------------------------------------------------- K8
 // K7's per-Gaussian record (round 6) holds the MOMENTS of m = G dL/dalpha over the pixels the Gaussian was blended at, about its centre:
@@ -2904,6 +3142,17 @@ static size_t cam_bg_offset(int P, int64_t R, int W, int H) {
 }
 size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H) {
     return cam_bg_offset(P, R, W, H) + align256((size_t)BG_BLOCKS * 3 * 4);
+}
+// the feature / alpha path (ABI 9) lays out everything the camera path does, then the feature partials of the prepass (one float per
+// (segment, pixel)) and, in the bit-reproducible mode, its own 16-float (entry, block) records (the depth layout's 10-float ones go unused)
+static size_t feat_wpart_offset(int P, int64_t R, int W, int H) { return csplat_backward_camera_scratch_bytes(P, R, W, H); }
+static size_t feat_det_offset(int P, int64_t R, int W, int H) {
+    const int tiles = cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE);
+    return feat_wpart_offset(P, R, W, H) + align256((size_t)max_slots(R, tiles) * 256 * 4);
+}
+static size_t feat_det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 16 * 4); }
+size_t csplat_backward_feature_scratch_bytes(int P, int64_t R, int W, int H) {
+    return feat_det_offset(P, R, W, H) + ((g_debug_flags & 256u) ? feat_det_bytes(R) : 0);
 }
 int csplat_geom_layout(int P, size_t *o8) { size_t off[G_NFIELDS]; geom_offsets(P, off); for (int k = 0; k < 8; k++) o8[k] = off[k]; return 0; }
 // every sub-buffer of the BINNING chunk (csplat.h: csplat_binning_fields): 0 keys 1 ids 2 seg_offset + blk_hi 3 slot_tile 4 checkpoints
@@ -3709,8 +3958,50 @@ static int forward_views_impl(int V, csplat_view *v, csplat_alloc_fn alloc, void
     return finish_views_one_by_one(V, v, tickets, begun, join, fenced, rc);
 }
 
+// ABI 9: the feature / alpha images of a finished forward (csplat_view.out_features / out_alpha), on the join stream behind every view's
+// K6.  Nothing is launched when no view asks for them.
+static bool feat_out_wanted(const csplat_view &w) { return w.out_features || w.out_alpha; }
+static int feature_forward(int V, csplat_view *v, hipStream_t join) {
+    bool any = false;
+    for (int i = 0; i < V; i++) any = any || feat_out_wanted(v[i]);
+    if (!any) return 0;
+    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_forward_views: feature / alpha images are rendered for at most 8 views per call");
+    FeatFwdTable t;
+    memset(&t, 0, sizeof(t));
+    int maxtiles = 0;
+    for (int i = 0; i < V; i++) {
+        const csplat_view &w = v[i];
+        CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES && (w.n_features == 0) == (w.features == nullptr),
+                       "csplat_forward_views: n_features must be 0..6, with features set exactly when it is not 0");
+        CSPLAT_REQUIRE(!w.out_features || w.n_features > 0, "csplat_forward_views: out_features without features");
+        FeatFwdView &f = t.v[i];
+        const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
+        f.W = w.W; f.H = w.H; f.gx = gx; f.nf = w.n_features; f.features = w.features;
+        f.out_features = w.out_features; f.out_alpha = w.out_alpha;
+        if (!feat_out_wanted(w)) continue;
+        maxtiles = tiles > maxtiles ? tiles : maxtiles;
+        if (w.P <= 0 || w.num_rendered <= 0) continue;       // (no list entry: feat = 0, alpha = 0)
+        CSPLAT_REQUIRE(w.image && w.binning, "csplat_forward_views: missing chunks");
+        const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
+        size_t ioff[5], boff[B_NFIELDS];
+        image_offsets(w.W, w.H, ioff);
+        binning_offsets(Rl, tiles, boff);
+        const char *b = (const char *)w.binning, *im = (const char *)w.image;
+        f.ranges = (const int2 *)(im + ioff[0]); f.n_contrib = (const uint32_t *)(im + ioff[1]); f.final_T = (const float *)(im + ioff[2]);
+        f.ids_sorted = (const uint32_t *)(b + boff[1]); f.seg_offset = (const int *)(b + boff[2]); f.ckpt = (const float4 *)(b + boff[4]);
+        f.recA = (const float4 *)(b + boff[6]); f.recB = (const float4 *)(b + boff[7]); f.bbits = (const unsigned long long *)(b + boff[9]);
+        f.tiles = tiles;
+    }
+    if (maxtiles == 0) return 0;
+    ProfScope ps(PROF_K6_FEAT, join);
+    k_feature_fwd_views<<<dim3((unsigned)maxtiles, V), 256, 0, join>>>(t);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int csplat_forward_views(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream) {
-    return forward_views_impl(V, v, alloc, join_stream, nullptr);
+    const int rc = forward_views_impl(V, v, alloc, join_stream, nullptr);
+    return rc ? rc : feature_forward(V, v, (hipStream_t)join_stream);
 }
 
 // csplat_forward_views WITHOUT any host read: both phases are launched with the caller's capacities (caps[0] list entries per view,
@@ -3720,6 +4011,8 @@ int csplat_forward_views(int V, csplat_view *v, csplat_alloc_fn alloc, void *joi
 // qualify for the one-launch-per-stage path (2..8 views sharing P, SH, opacities, scales and the image size), else an error.
 int csplat_forward_views_faith(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream, const uint32_t *caps, uint32_t *valid) {
     CSPLAT_REQUIRE(V >= 2 && V <= P2_MAX_VIEWS && v != nullptr && caps != nullptr && valid != nullptr, "csplat_forward_views_faith: bad arguments");
+    for (int i = 0; i < V; i++)
+        CSPLAT_REQUIRE(!feat_out_wanted(v[i]), "csplat_forward_views_faith: views launched on faith render no feature or alpha image");
     CSPLAT_REQUIRE(caps[0] > 0 && caps[0] <= 0x7FFFFF00u && caps[1] > 0 && caps[1] <= tile_sort_cap() && caps[2] > 0,
                    "csplat_forward_views_faith: capacities out of range");
     hipStream_t join = (hipStream_t)join_stream;
@@ -3761,13 +4054,19 @@ size_t csplat_image_info_offset(int W, int H) { size_t off[5]; image_offsets(W, 
 // csplat_forward_views_settle with the SAME array.  *pending = 0: the call was complete (first call of a shape, views that do not qualify).
 int csplat_forward_views_deferred(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream, int *pending) {
     CSPLAT_REQUIRE(pending != nullptr, "csplat_forward_views_deferred: pending missing");
-    return forward_views_impl(V, v, alloc, join_stream, pending);
+    const int rc = forward_views_impl(V, v, alloc, join_stream, pending);
+    return (rc || *pending) ? rc : feature_forward(V, v, (hipStream_t)join_stream);      // (pending: settle renders them)
 }
 
 // Reads the counts of a pending call.  They fit the capacities: num_rendered is filled in, nothing else changes (*relaunched = 0).
 // They do not: the second phase is repeated with exact sizes -- new BINNING chunks through the allocator of the call, layout_rendered /
 // binning updated -- and *relaunched = 1: whatever the caller derived from layout_rendered must be rebuilt.
+static int forward_views_settle_impl(int V, csplat_view *v, void *join_stream, int *relaunched);
 int csplat_forward_views_settle(int V, csplat_view *v, void *join_stream, int *relaunched) {
+    const int rc = forward_views_settle_impl(V, v, join_stream, relaunched);
+    return rc ? rc : feature_forward(V, v, (hipStream_t)join_stream);
+}
+static int forward_views_settle_impl(int V, csplat_view *v, void *join_stream, int *relaunched) {
     CSPLAT_REQUIRE(v != nullptr && relaunched != nullptr, "csplat_forward_views_settle: bad arguments");
     *relaunched = 0;
     PendingViews pend;
@@ -3902,11 +4201,13 @@ static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *ro
     return 0;
 }
 
+static bool feat_wanted(const csplat_view &w) { return w.dL_dfeatures || w.dL_dalpha; }
 static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices, bool cam = false,
-                                bool cam_k8 = false) {
-    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth gradient is taken for at most 8 views per call");
-    CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth gradient");
+                                bool cam_k8 = false, bool feat = false) {
+    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth, feature or alpha gradient is taken for at most 8 views per call");
+    CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth, feature or alpha gradient");
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
+    CSPLAT_REQUIRE(!feat || whole, "csplat_backward_views_parts: feature / alpha gradients are taken by the whole call only");
     bool shared = false;
     for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)CSPLAT_SCRATCH_ZEROED) != 0u;
     K8Table tab;
@@ -3915,6 +4216,9 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
     const bool det_mode = (g_debug_flags & 256u) != 0;
     if (want_k7) {
         DepthTable dtab;
+        FeatTable ftab;
+        ftab.n = V;
+        bool any_fgrad = false;
         DetTable dt;
         dt.valid = nullptr;
         int64_t slots = 0;
@@ -3936,15 +4240,28 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             k.ckpt = (const float4 *)(b + boff[4]); k.bbits = (const unsigned long long *)(b + boff[9]);
             k.recA = (const float4 *)(b + boff[6]); k.recB = (const float4 *)(b + boff[7]); k.recC = (const float2 *)(b + boff[8]);
             k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = (float *)w.scratch; k.R = (uint32_t)Rl;
-            k.det = det_mode ? (float *)((char *)w.scratch + align256((size_t)(w.P > 0 ? w.P : 1) * ACC_STRIDE * 4)) : nullptr;
+            k.det = !det_mode ? nullptr
+                    : feat ? (float *)((char *)w.scratch + feat_det_offset(w.P, Rl, w.W, w.H))
+                           : (float *)((char *)w.scratch + align256((size_t)(w.P > 0 ? w.P : 1) * ACC_STRIDE * 4));
             d.dL_ddepth = w.dL_ddepth;
             d.dpart = (float *)((char *)w.scratch + depth_dpart_offset(w.P, Rl));
             d.W = w.W; d.H = w.H; d.gx = gx;
             d.tiles = (w.P > 0 && w.num_rendered > 0) ? tiles : 0;
+            if (feat) {
+                CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES && (w.n_features == 0) == (w.features == nullptr),
+                               "csplat_backward_views: n_features must be 0..6, with features set exactly when it is not 0");
+                CSPLAT_REQUIRE(!w.dL_dfeatures || w.n_features > 0, "csplat_backward_views: dL_dfeatures without features");
+                FeatView &f = ftab.v[i];
+                f.d = d;
+                f.radii = w.radii; f.features = w.features; f.nf = w.n_features; f.dL_dfeat = w.dL_dfeatures; f.dL_dalpha = w.dL_dalpha;
+                f.wpart = (float *)((char *)w.scratch + feat_wpart_offset(w.P, Rl, w.W, w.H));
+                f.dL_dfeat_in = w.n_features > 0 ? w.dL_dfeat_in : nullptr; f.P = w.P; f.accmask = w.accmask;
+                any_fgrad = any_fgrad || w.dL_dfeatures;
+            }
             if (w.P <= 0) continue;
             Pmax = w.P > Pmax ? w.P : Pmax;
             // (the records start at zero: the bit-reproducible mode writes every one of them, CSPLAT_SCRATCH_ZEROED promises them)
-            if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, depth_det_bytes(Rl), join));
+            if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, feat ? feat_det_bytes(Rl) : depth_det_bytes(Rl), join));
             else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(k.acc, 0, (size_t)w.P * ACC_STRIDE * 4, join));
             if (det_mode) {
                 DetView &e = dt.v[i];
@@ -3956,7 +4273,45 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             const int64_t sl = (w.busy_tiles > 0 && w.num_rendered > 0) ? (int64_t)w.num_rendered / SEG + w.busy_tiles + 1 : max_slots(Rl, tiles);
             slots = sl > slots ? sl : slots;
         }
-        if (slots > 0) {
+        if (feat) {
+            for (int i = 0; i < V; i++) ftab.v[i].d = dtab.v[i];
+            bool any_depth = false;
+            for (int i = 0; i < V; i++) any_depth = any_depth || v[i].dL_ddepth;
+            if (slots > 0) {
+                if (any_depth) {
+                    ProfScope ps(PROF_K7_DEPTH_PARTIALS, join);
+                    k_depth_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(dtab);
+                    LAUNCH_CHECK();
+                }
+                if (any_fgrad) {
+                    ProfScope ps(PROF_K7_FEAT_PARTIALS, join);
+                    k_feature_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(ftab);
+                    LAUNCH_CHECK();
+                }
+                ProfScope ps(PROF_K7_FEAT, join);
+                const unsigned items = (unsigned)cdiv(slots, 8) * 32u;
+                if (det_mode)
+                    k_feature_composite_bwd_views<true><<<dim3(items, V), 256, 0, join>>>(ftab);
+                else
+                    k_feature_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(ftab);
+                LAUNCH_CHECK();
+            }
+            if (det_mode && Pmax > 0) {
+                for (int i = 0; i < V; i++) {
+                    if (v[i].P <= 0) continue;
+                    DetTable one;
+                    one.valid = nullptr;
+                    one.v[0] = dt.v[i];
+                    k_feature_det_reduce_views<<<dim3((unsigned)cdiv(v[i].P, 256), 1), 256, 0, join>>>(v[i].P, one);
+                    LAUNCH_CHECK();
+                }
+            }
+            if (Pmax > 0) {     // the feature gradients leave the records before K8 reads (and may clear) them
+                ProfScope ps(PROF_FEAT_GRADS, join);
+                k_feature_grads<<<dim3((unsigned)cdiv(Pmax, 256), 1), 256, 0, join>>>(ftab);
+                LAUNCH_CHECK();
+            }
+        } else if (slots > 0) {
             {
                 ProfScope ps(PROF_K7_DEPTH_PARTIALS, join);
                 k_depth_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(dtab);
@@ -3970,7 +4325,7 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
                 k_depth_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(dtab);
             LAUNCH_CHECK();
         }
-        if (det_mode && Pmax > 0) {
+        if (det_mode && Pmax > 0 && !feat) {
             // (a view with fewer Gaussians: its rows past P are not visited -- the launch is sized for the largest view and guarded per view)
             for (int i = 0; i < V; i++) {
                 if (v[i].P <= 0) continue;
@@ -4032,6 +4387,14 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
         CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no camera / background gradient");
         for (int i = 0; i < V; i++)
             CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: camera gradients need scratch of csplat_backward_camera_scratch_bytes");
+    }
+    bool feat = false;
+    for (int i = 0; i < V; i++) feat = feat || feat_wanted(v[i]);
+    if (feat) {
+        CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no feature or alpha gradient");
+        for (int i = 0; i < V; i++)
+            CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: feature / alpha gradients need scratch of csplat_backward_feature_scratch_bytes");
+        return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8, true);
     }
     for (int i = 0; i < V; i++)
         if (v[i].dL_ddepth) return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8);

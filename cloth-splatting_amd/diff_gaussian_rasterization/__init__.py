@@ -14,6 +14,9 @@ receive gradients when they require grad (camera refinement, a learnable backgro
 only then are they inputs of the autograd Functions, so without them the call is exactly the one without camera gradients.  All compute
 is in libcsplat.so (csplat_forward_begin / _finish / csplat_backward).
 `rasterize_views` renders several independent views in one call, one HIP stream per view.
+Beyond upstream, `features=` ([P, F] float32, 1 <= F <= 6) composites per-Gaussian feature channels with the colour's weights and
+`return_alpha=True` returns the alpha image 1 - T_final, both differentiable (include/csplat.h, csplat_view.features .. dL_dfeat_in);
+without them the call is exactly the upstream one.
 """
 import contextlib as _contextlib
 import ctypes as C
@@ -97,14 +100,52 @@ def _cam_returns(outs, cam_inputs):
     return tuple(None if g is None else g.view(t.shape).to(device=t.device, dtype=t.dtype) for g, t in zip(outs, cam_inputs))
 
 
+class _FeatSpec:
+    """the feature / alpha request of a batched call, one (F, return_alpha) per view (F = 0: no features); the last argument of
+    _RasterizeGaussiansBatch.apply, behind the views' feature tensors, when any view asks for either"""
+
+    def __init__(self, per_view):
+        self.per_view = [(int(f), bool(a)) for f, a in per_view]
+
+
+def _check_features(features, means3D):
+    """-> F of a `features` argument; ValueError unless it is a float32 [P, F] tensor on the device of means3D with 1 <= F <= 6"""
+    if not torch.is_tensor(features):
+        raise ValueError("features must be a torch.Tensor")
+    if features.dtype != torch.float32:
+        raise ValueError(f"features must be float32, got {features.dtype}")
+    if features.dim() != 2 or features.shape[0] != means3D.shape[0]:
+        raise ValueError(f"features must be [P, F] with P = {int(means3D.shape[0])}, got {tuple(features.shape)}")
+    if not 1 <= int(features.shape[1]) <= _n.MAX_FEATURES:
+        raise ValueError(f"features must have 1 to {_n.MAX_FEATURES} channels, got {int(features.shape[1])}")
+    if features.device != means3D.device:
+        raise ValueError(f"features must be on {means3D.device}, got {features.device}")
+    return int(features.shape[1])
+
+
+def _feature_mode_check():
+    """feature / alpha images are rendered by eager steps only"""
+    if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        raise RuntimeError("diff_gaussian_rasterization: feature / alpha images are not rendered by a forward launched on faith or a "
+                           "captured / replayed step -- render them in an eager step")
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, features=None, return_alpha=False):
     """One camera (what GaussianRasterizer.forward calls, gaussian_renderer/__init__.py:156-164).  Since round 5 a single view goes
     through the same library entry as a batch of views (csplat_forward_views_deferred with V = 1): from the second call of an image size
     on, the second forward phase is launched on the previous call's capacities and the counts are read AFTER the host has prepared the
     backward -- a camera-by-camera loop (the reference's train_utils.py:259-272) no longer leaves the GPU idle for a host round trip per
     camera.  Images, radii, depth and gradients are those of _RasterizeGaussians (tests: test_batched_views_equal_single_view_calls)."""
     cam = _cam_group(raster_settings)
+    if features is not None or return_alpha:
+        # (the feature / alpha path: always the batched Function with one view -- csplat_forward_views_* render the extra images,
+        #  csplat_backward_views takes their gradients)
+        F = _check_features(features, means3D) if features is not None else 0
+        _feature_mode_check()
+        _n.require_cuda(means3D)
+        return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                              cov3Ds_precomp, *cam, features, _FeatSpec([(F, return_alpha)]))
     if PER_CALL_SPECULATION and means3D.is_cuda:
         return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                               cov3Ds_precomp, *cam)
@@ -425,6 +466,14 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         # flat: V groups of NIN per-view inputs, then -- only when a settings tensor wants a gradient (_cam_group) -- V groups of
         # (viewmatrix, projmatrix, campos, bg)
         V, n = len(settings), _RasterizeGaussiansBatch.NIN
+        # (then, when a view asks for feature or alpha images: V feature tensors (None where a view has none) and the _FeatSpec)
+        spec = flat[-1] if flat and isinstance(flat[-1], _FeatSpec) else None
+        feats = list(flat[-1 - V:-1]) if spec is not None else [None] * V
+        if spec is not None:
+            flat = flat[:-1 - V]
+            _feature_mode_check()
+        ctx.fspec = spec.per_view if spec is not None else None
+        ctx.feat_first = [next(j for j in range(i + 1) if feats[j] is feats[i]) for i in range(V)]     # (one gradient per tensor object)
         assert len(flat) in (V * n, V * (n + 4))
         ctx.cam = len(flat) > V * n
         flat = flat[:V * n]
@@ -464,6 +513,16 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             w.cov3D_precomp, w.view, w.proj, w.campos = _n.ptr(v.cov3Ds_precomp), _n.ptr(v.view), _n.ptr(v.proj), _n.ptr(v.campos)
             w.alloc_ctx = i
             w.out_color, w.out_depth, w.radii = _n.ptr(v.color), _n.ptr(v.depth), _n.ptr(v.radii)
+            v.feat = v.alpha = v.features = None
+            if spec is not None:
+                F, want_alpha = spec.per_view[i]
+                if F:
+                    v.features = feats[i].contiguous()
+                    v.feat = torch.empty(F, v.H, v.W, dtype=torch.float32, device=dev)
+                    w.features, w.n_features, w.out_features = _n.ptr(v.features), F, _n.ptr(v.feat)
+                if want_alpha:
+                    v.alpha = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
+                    w.out_alpha = _n.ptr(v.alpha)
         # the one host read of the call (its counts) is DEFERRED when the library can launch the second phase on the previous call's
         # capacities: everything below that does not need the counts -- the output lists, the backward plan -- is host work done
         # while the GPU runs K1..K6, instead of after a ~45 us wait for K1 / K2
@@ -503,6 +562,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             v.layout_rendered = int(arr[i].layout_rendered)      # >= num_rendered: what the binning chunk was laid out for
             v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
             outs += [v.radii, v.depth] if stacked else [v.color, v.radii, v.depth]
+            outs += [t for t in (v.feat, v.alpha) if t is not None]
             saved += list(v.saved()[:-1]) + ([] if stacked else [v.color])
             ctx.mark_non_differentiable(v.radii)
         if stacked:
@@ -510,11 +570,16 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             saved.append(colors)
         ctx.stacked = bool(stacked)
         ctx.nsaved = len(views[0].saved()) - (1 if stacked else 0)
+        ctx.nfeat_saved = 0
+        if ctx.fspec is not None:       # (behind everything the colour path saves: the views' feature tensors, None where a view has none)
+            saved += [v.features for v in views]
+            ctx.nfeat_saved = V
         ctx.save_for_backward(*saved)
         # which view first received each input tensor OBJECT (shared parameters get one gradient buffer)
         ctx.first_of = [[next(j for j in range(i + 1) if flat[j * n + k] is flat[i * n + k]) for k in range(n)] for i in range(V)]
         for v in views:
             v.drop_inputs()
+            v.features = v.feat = v.alpha = None
         ctx.views, ctx.arr = views, arr
         ctx.on_faith = _FAITH is not None
         ctx.set_materialize_grads(False)     # an unused view arrives as None in backward() and costs nothing
@@ -653,18 +718,31 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         n = _RasterizeGaussiansBatch.NIN
         cam_need = [tuple(ctx.needs_input_grad[2 + V * n + 4 * i:2 + V * n + 4 * i + 4]) for i in range(V)] if ctx.cam else [()] * V
         tail = (None,) * (4 * V) if ctx.cam else ()
+        fspec = ctx.fspec or [(0, False)] * V
+        ftail = (None,) * (V + 1) if ctx.fspec is not None else ()      # the views' feature tensors and the _FeatSpec
+        per = [(2 if ctx.stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]     # outputs per view
+        first = [sum(per[:i]) + (1 if ctx.stacked else 0) for i in range(V)]                          # a view's first output
         if ctx.stacked:
             gcol = [None] * V if grads[0] is None else [grads[0][i] for i in range(V)]
-            gdep = [grads[2 + 2 * i] for i in range(V)]
+            gdep = [grads[first[i] + 1] for i in range(V)]
         else:
-            gcol = [grads[3 * i] for i in range(V)]
-            gdep = [grads[3 * i + 2] for i in range(V)]
+            gcol = [grads[first[i]] for i in range(V)]
+            gdep = [grads[first[i] + 2] for i in range(V)]
+        gfeat = [grads[first[i] + per[i] - (2 if fspec[i][1] else 1)] if fspec[i][0] else None for i in range(V)]
+        galpha = [grads[first[i] + per[i] - 1] if fspec[i][1] else None for i in range(V)]
         if any(g is not None for g in gdep) and ctx.on_faith:
             raise RuntimeError("diff_gaussian_rasterization: a depth gradient reached a forward launched on faith (a captured / replayed step); "
                                "those steps take no depth loss -- render the depth term in an eager step")
-        active = [i for i in range(V) if gcol[i] is not None or gdep[i] is not None]
+        active = [i for i in range(V) if gcol[i] is not None or gdep[i] is not None or gfeat[i] is not None or galpha[i] is not None]
         if not active:
-            return (None, None) + (None,) * (V * _RasterizeGaussiansBatch.NIN) + tail
+            return (None, None) + (None,) * (V * _RasterizeGaussiansBatch.NIN) + tail + ftail
+        want_feat = any(gfeat[i] is not None or galpha[i] is not None for i in active)
+        if want_feat and ctx.on_faith:
+            raise RuntimeError("diff_gaussian_rasterization: a feature / alpha gradient reached a forward launched on faith (a captured / "
+                               "replayed step); render feature and alpha images in an eager step")
+        if want_feat and _K8_DEFER is not None:
+            raise RuntimeError("diff_gaussian_rasterization: a feature / alpha gradient reached a backward inside deferred_k8(); the sliced "
+                               "per-Gaussian backward takes no feature or alpha gradient")
         want_cam = any(any(cam_need[i]) for i in active)
         if want_cam and ctx.on_faith:
             raise RuntimeError("diff_gaussian_rasterization: a camera / background gradient reached a forward launched on faith (a captured / "
@@ -692,11 +770,34 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 for f, g in zip(_CAM_FIELDS, cam_out[i]):
                     setattr(plan["sub"][a], f, _n.ptr(g))
                 gs += [g for g in cam_out[i] if g is not None]
-        if want_cam or any(gdep[i] is not None for i in active):
+        ftail_out = ftail
+        if want_feat:
+            # the feature path (csplat_view.dL_dfeatures / dL_dalpha): one dL_dfeat_in buffer per feature tensor OBJECT that wants a
+            # gradient, shared by the views it was passed to (the library adds their sums in view order)
+            fsaved = ctx.saved_tensors[len(ctx.saved_tensors) - ctx.nfeat_saved:]
+            fin = ctx.needs_input_grad[2 + V * n + (4 * V if ctx.cam else 0):]
+            fout, owner = [None] * V, {}
+            for a, i in enumerate(active):
+                w, F = plan["sub"][a], fspec[i][0]
+                gf = _f32c_grad(gfeat[i], dev) if gfeat[i] is not None else None
+                ga = _f32c_grad(galpha[i], dev) if galpha[i] is not None else None
+                w.features, w.n_features = _n.ptr(fsaved[i]), F
+                w.dL_dfeatures, w.dL_dalpha = _n.ptr(gf), _n.ptr(ga)
+                buf = None
+                if F and fin[i]:
+                    key = ctx.feat_first[i]
+                    if key not in owner:
+                        owner[key] = fout[i] = torch.empty(views[i].P, F, dtype=torch.float32, device=dev)
+                    buf = owner[key]
+                w.dL_dfeat_in = _n.ptr(buf)
+                gs += [gf, ga]
+            ftail_out = tuple(fout) + (None,)
+        if want_feat or want_cam or any(gdep[i] is not None for i in active):
             # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout (the camera path: of the
-            # camera layout), allocated here (never on the colour-only path) and cleared by the library -- the persistent zeroed records
-            # are not used by this call
-            scratch_bytes = _n.lib.csplat_backward_camera_scratch_bytes if want_cam else _n.lib.csplat_backward_depth_scratch_bytes
+            # camera layout; the feature path: of the feature layout), allocated here (never on the colour-only path) and cleared by the
+            # library -- the persistent zeroed records are not used by this call
+            scratch_bytes = _n.lib.csplat_backward_feature_scratch_bytes if want_feat else \
+                _n.lib.csplat_backward_camera_scratch_bytes if want_cam else _n.lib.csplat_backward_depth_scratch_bytes
             for a, i in enumerate(active):
                 v = views[i]
                 gd = _f32c_grad(gdep[i], dev) if gdep[i] is not None else None
@@ -714,13 +815,13 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             #  gradient only when nobody else holds it, and would otherwise snapshot the still unwritten buffer into a copy)
             outs, plan["out"] = tuple(plan["out"]), None
             _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, ctx.saved_tensors)))
-            return (None, None) + outs + tail
+            return (None, None) + outs + tail + ftail
         with _n.on_device(dev):
             rc = _n.lib.csplat_backward_views(len(active), C.cast(plan["sub"], C.c_void_p), main.cuda_stream)
         _n.check(rc, "csplat_backward_views")
         if ctx.cam:
             tail = sum((_cam_returns(cam_out.get(i, (None,) * 4), _cam_tensors(views[i].rs)) for i in range(V)), ())
-        return (None, None) + tuple(plan["out"]) + tail
+        return (None, None) + tuple(plan["out"]) + tail + ftail_out
 
 
 def rasterize_views(settings, inputs, stacked=False):
@@ -729,9 +830,13 @@ def rasterize_views(settings, inputs, stacked=False):
     dicts with the keyword names of GaussianRasterizer.forward.  Returns a list of (color, radii, depth); with
     stacked=True (equal image sizes) returns (colors [V,3,H,W], [(colors[i], radii, depth), ...]) where `colors` is the
     differentiable output -- the batch the reference assembles with torch.cat before its losses -- and colors[i] are
-    plain slices of it."""
-    flat = []
+    plain slices of it.  A dict may also carry `features` ([P, F], the same F in every view) and `return_alpha`: that view's tuple
+    then grows by feat [F,H,W] and / or alpha [1,H,W] (GaussianRasterizer.forward)."""
+    flat, fspec, feats = [], [], []
     for kw in inputs:
+        f, want_alpha = kw.get("features"), bool(kw.get("return_alpha", False))
+        fspec.append((_check_features(f, kw["means3D"]) if f is not None else 0, want_alpha))
+        feats.append(f)
         shs, cp = kw.get("shs"), kw.get("colors_precomp")
         sc, ro, cov = kw.get("scales"), kw.get("rotations"), kw.get("cov3D_precomp")
         if (shs is None) == (cp is None):
@@ -742,11 +847,19 @@ def rasterize_views(settings, inputs, stacked=False):
     if any(_cam_group(rs) for rs in settings):      # (a settings tensor wants a gradient: every view's camera group follows)
         for rs in settings:
             flat += list(_cam_tensors(rs))
+    extra = any(f or a for f, a in fspec)
+    if extra:
+        if len({f for f, _a in fspec}) > 1:
+            raise ValueError(f"rasterize_views: every view must have the same number of feature channels, got {[f for f, _a in fspec]}")
+        _feature_mode_check()
+        flat += feats + [_FeatSpec(fspec)]
     res = _RasterizeGaussiansBatch.apply(tuple(settings), bool(stacked), *flat)
+    per = [(2 if stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]
+    at = [sum(per[:i]) + (1 if stacked else 0) for i in range(len(settings))]
     if stacked:
         colors = res[0]
-        return colors, [(colors[i], res[1 + 2 * i], res[2 + 2 * i]) for i in range(len(settings))]
-    return [tuple(res[3 * i:3 * i + 3]) for i in range(len(settings))]
+        return colors, [(colors[i],) + tuple(res[at[i]:at[i] + per[i]]) for i in range(len(settings))]
+    return [tuple(res[at[i]:at[i] + per[i]]) for i in range(len(settings))]
 
 
 _n_GEOM, _n_BINNING, _n_IMAGE = 0, 1, 2
@@ -765,11 +878,15 @@ class GaussianRasterizer(nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, features=None, return_alpha=False):
+        """-> (color [3,H,W], radii [P], depth [1,H,W]), then feat [F,H,W] when `features` ([P, F] float32, 1 <= F <= 6, on the device of
+        means3D) is given -- feat[c] = sum_i T_i alpha_i features[i, c] over exactly the Gaussians the colour blends, no background term --
+        then alpha [1,H,W] = 1 - T_final when `return_alpha` (color = sum T alpha c + (1 - alpha) bg).  Both are differentiable; neither
+        is rendered by a forward launched on faith or a captured step (RuntimeError), nor differentiated inside deferred_k8()."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings)
+                                   self.raster_settings, features, bool(return_alpha))

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CSPLAT_ABI_VERSION 8   /* 8: camera and background gradients (csplat_view.dL_dview / dL_dproj / dL_dcampos / dL_dbg, csplat_backward_camera_scratch_bytes); 7: the depth image's gradient (csplat_view.dL_ddepth, csplat_backward_depth, csplat_backward_depth_scratch_bytes); 6 (round 6): csplat_backward_views_parts / _slice_rows, csplat_gnn_edge_length_refine, csplat_rollout_head / _decode / _integrate, csplat_gnn_edge_features_ordered, csplat_gnn_rows_chain(_pack), csplat_binning_fields; round 4: csplat_view.busy_tiles / .valid, csplat_rows_dot_fwd's extra argument; 3: the binning chunk's layout (bbits, bmask); 4 (round 5): csplat_gather_words kind 2; 5: csplat_gnn_edge_mlp3* (e0_absmax, modes), csplat_absmax, csplat_linear_narrow128 */
+#define CSPLAT_ABI_VERSION 9   /* 9: feature channels and the alpha image (csplat_view.features .. dL_dfeat_in, csplat_backward_feature_scratch_bytes); 8: camera and background gradients (csplat_view.dL_dview / dL_dproj / dL_dcampos / dL_dbg, csplat_backward_camera_scratch_bytes); 7: the depth image's gradient (csplat_view.dL_ddepth, csplat_backward_depth, csplat_backward_depth_scratch_bytes); 6 (round 6): csplat_backward_views_parts / _slice_rows, csplat_gnn_edge_length_refine, csplat_rollout_head / _decode / _integrate, csplat_gnn_edge_features_ordered, csplat_gnn_rows_chain(_pack), csplat_binning_fields; round 4: csplat_view.busy_tiles / .valid, csplat_rows_dot_fwd's extra argument; 3: the binning chunk's layout (bbits, bmask); 4 (round 5): csplat_gather_words kind 2; 5: csplat_gnn_edge_mlp3* (e0_absmax, modes), csplat_absmax, csplat_linear_narrow128 */
 
 /* scratch chunks requested through the allocator callback */
 #define CSPLAT_CHUNK_GEOM 0    /* per-Gaussian state, kept for backward */
@@ -86,6 +86,11 @@ size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H);
  * (one 35-float row per K8 workgroup) and the background slab (256 rows of 3).  Never smaller than
  * csplat_backward_depth_scratch_bytes(P, R, W, H). */
 size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H);
+/* the scratch of a backward call that takes a feature or alpha gradient (any view of csplat_backward_views with dL_dfeatures or
+ * dL_dalpha set -- then EVERY view of that call needs this size): the camera layout above, then one float per (list segment, pixel) for
+ * the feature partials and, in the bit-reproducible mode, 16-float (entry, block) records.  Never smaller than
+ * csplat_backward_camera_scratch_bytes(P, R, W, H). */
+size_t csplat_backward_feature_scratch_bytes(int P, int64_t R, int W, int H);
 
 /* Byte offsets of the named sub-buffers inside a chunk (for tests / debugging; see DESIGN.md "HBM layout").
  * geom:    0 depth f32[P] | 1 xy f32[P][2] | 2 conic_opacity f32[P][4] | 3 rgb f32[P][3] | 4 cov3D f32[P][6]
@@ -152,6 +157,7 @@ enum { CSPLAT_ACC_OPACITY = 1, CSPLAT_ACC_COLOR = 2, CSPLAT_ACC_MEAN3D = 4, CSPL
         * every record it has consumed) -- a caller that keeps the buffer from step to step on one stream then needs no clearing launch per
         * step (25.6 MB of zero fill for four views of 100k Gaussians).  Without the bit the library clears the records itself. */
        CSPLAT_SCRATCH_ZEROED = 256 };
+#define CSPLAT_MAX_FEATURES 6    /* ABI 9: csplat_view.n_features <= 6 (record slots 10..15 of the compositing backward) */
 typedef struct csplat_view {
     void *stream;
     int P, D, M, W, H, prefiltered;
@@ -193,6 +199,23 @@ typedef struct csplat_view {
      * csplat_backward_camera_scratch_bytes.  Not for views launched on faith, nor csplat_backward_views_parts with parts != 3 or
      * nslices != 1; at most 8 views.  All NULL: the call is exactly the ABI 7 one. */
     float *dL_dview, *dL_dproj, *dL_dcampos, *dL_dbg;
+    /* ABI 9, feature channels and the alpha image.  features [P][n_features] (device, 1 <= n_features <= CSPLAT_MAX_FEATURES; NULL and 0
+     * = none) are composited with the colour's weights over exactly the entries the colour blends (same alpha, 0.99 cap, 1/255 skip,
+     * stop rule, n_contrib), without a background term:  out_features[c][pix] = sum_i T_i alpha_i f[i][c]  ([n_features][H][W]);
+     * out_alpha[pix] = 1 - T_final(pix)  ([1][H][W]; T_final = the factor of the colour's background term).  Both are written by
+     * csplat_forward_views, csplat_forward_views_deferred (when not pending) and csplat_forward_views_settle, in one launch behind the
+     * views' K6 on the join stream; each NULL = not wanted (not for csplat_forward_views_faith).
+     * Backward inputs dL_dfeatures [n_features][H][W] and dL_dalpha [1][H][W] (NULL = none): when any view of a csplat_backward_views
+     * call has one, the call takes the feature path (every view's scratch sized by csplat_backward_feature_scratch_bytes; at most 8
+     * views; not for views launched on faith nor csplat_backward_views_parts with parts != 3 or nslices != 1), which composes with the
+     * depth and camera paths; dL/dalpha_i gains sum_c g_c (T_i f_ic - F_behind_c / (1 - alpha_i)) + g_A T_final / (1 - alpha_i).
+     * dL_dfeat_in [P][n_features] (output, NULL = not wanted): sum over pixels of T_i alpha_i dL_dfeatures[c][pix], WRITTEN, or added when
+     * an earlier view of the same call has the same buffer.  All NULL / 0: every call is exactly the ABI 8 one. */
+    const float *features;
+    int n_features;
+    float *out_features, *out_alpha;
+    const float *dL_dfeatures, *dL_dalpha;
+    float *dL_dfeat_in;
 } csplat_view;
 int csplat_forward_views(int V, csplat_view *views, csplat_alloc_fn alloc, void *join_stream);
 /* The same call with its one host read (the views' counts) DEFERRED.  When the second phase can be launched on the previous call's
@@ -455,6 +478,8 @@ int csplat_mesh_transform_bwd_views(void *stream, int T, int P, int V, const int
  *   5 K6 compositing fwd | 6 K7 compositing bwd | 7 K8 preprocess bwd | 8 distCUDA2 | 9 GNN kernels
  *   10 depth partials prepass | 11 K7 of the depth path | 12 K8 of the depth path (csplat_backward_depth, dL_ddepth)
  *   13 K8 of the camera path | 14 the camera path's background partials and fixed-order sums (csplat_view.dL_dview .. dL_dbg)
+ *   15 the feature / alpha forward pass | 16 feature partials prepass | 17 K7 of the feature path | 18 feature gradient extraction
+ *   (csplat_view.features .. dL_dfeat_in)
  * csplat_prof_read synchronises the recorded events of class k, returns their summed duration (ms) and the
  * number of brackets, and recycles the events. */
 int csplat_prof_enable(unsigned mask);
