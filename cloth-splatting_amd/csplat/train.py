@@ -807,7 +807,8 @@ class CapturedStep:
       * ONE host read per step, at its end: [valid, PSNR, loss, the views' counts] arrive in pinned memory through a copy node of the
         graph.  valid == 0 -> the step is repeated eagerly (exact sizes) and the graph is re-recorded with new capacities at the next
         call; counts within 3 % of a capacity re-record too, before a miss happens.
-    One graph per step SHAPE: (number of cameras, image size, field of view, number of Gaussians, active SH degree, parameter storage).
+    One graph per step SHAPE: (number of cameras, image size, field of view, number of Gaussians, active SH degree, parameter storage,
+    pipe.antialiasing).
     Falls back to the eager train_step for what it does not cover: masks, a static stage, view-parallel runs, densification steps."""
 
     MARGIN = 8          # capacities = counts + counts / MARGIN (+ a constant)
@@ -826,7 +827,7 @@ class CapturedStep:
         g = self.g
         return (len(cams), int(c0.image_height), int(c0.image_width), float(c0.FoVx), float(c0.FoVy), int(g.num_gaussians),
                 int(g.active_sh_degree), tuple(int(p.data_ptr()) for p in g.parameters()),
-                tuple(int(p.data_ptr()) for p in self.sim.parameters()))
+                tuple(int(p.data_ptr()) for p in self.sim.parameters()), bool(getattr(self.pipe, "antialiasing", False)))
 
     def _coverable(self, cams):
         from .optim import GroupedAdam

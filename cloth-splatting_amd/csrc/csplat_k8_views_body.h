@@ -1,6 +1,7 @@
 // Body of the batched per-Gaussian backward (K8 of csplat_backward_views), included by csplat_raster.hip into k_preprocess_bwd_views
-// (DEPTH = false), k_preprocess_bwd_views_depth (DEPTH = true) and k_preprocess_bwd_views_cam (CAM = true).  Not a standalone header: it
-// expects the kernels' parameters, constexpr bools DEPTH and CAM and a `const CamSlabs *cam_slabs` in scope.
+// (DEPTH = false), k_preprocess_bwd_views_depth (DEPTH = true), k_preprocess_bwd_views_cam (CAM = true) and k_preprocess_bwd_views_aa
+// (AA = true: antialiasing, see preprocess_bwd_body).  Not a standalone header: it expects the kernels' parameters, constexpr bools DEPTH,
+// CAM and AA, a `const CamSlabs *cam_slabs` and a `const float *aa_opacities` (the raw opacities when AA) in scope.
     constexpr bool STAGE = true;
     if (tab.valid && *tab.valid == 0u) return;
     // (block0: first workgroup of a Gaussian-range SLICE of the launch -- csplat_backward_views_parts: the gradient rows of a finished slice
@@ -73,13 +74,14 @@
     }
     dL_dmean2D[3 * i] = a9[0]; dL_dmean2D[3 * i + 1] = a9[1]; dL_dmean2D[3 * i + 2] = 0.f;
     dL_dconic[4 * i] = a9[2]; dL_dconic[4 * i + 1] = a9[3]; dL_dconic[4 * i + 2] = 0.f; dL_dconic[4 * i + 3] = a9[4];
-    PUTL(L_op, dL_dopacity, i, a9[5], CSPLAT_ACC_OPACITY);
+    if constexpr (!AA) PUTL(L_op, dL_dopacity, i, a9[5], CSPLAT_ACC_OPACITY);     // (AA: h dL/do', below)
     PUTL(L_col[0], dL_dcolor, 3 * i, a9[6], CSPLAT_ACC_COLOR); PUTL(L_col[1], dL_dcolor, 3 * i + 1, a9[7], CSPLAT_ACC_COLOR);
     PUTL(L_col[2], dL_dcolor, 3 * i + 2, a9[8], CSPLAT_ACC_COLOR);
 
     float dmean[3] = {0.f, 0.f, 0.f};
     float g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (!vis) {
+        if constexpr (AA) PUTL(L_op, dL_dopacity, i, 0.f, CSPLAT_ACC_OPACITY);
 #pragma unroll
         for (int k = 0; k < 3; k++) PUTL(L_m3[k], dL_dmean3D, 3 * i + k, 0.f, CSPLAT_ACC_MEAN3D);
 #pragma unroll
@@ -105,7 +107,16 @@
 #pragma unroll
         for (int k = 0; k < 6; k++) c6[k] = g.cov3D[6 * i + k];
         float a, b, c;
-        cov2d_from_cov3d(c6, pj, a, b, c);
+        float aa_ga = 0.f, aa_gb = 0.f, aa_gc = 0.f;     // (AA) o dL/do' dh/d(a0, b, c0)
+        if constexpr (AA) {
+            float a0, c0;
+            cov2d_undilated(c6, pj, a0, b, c0);
+            a = a0 + AA_DILATE; c = c0 + AA_DILATE;
+            const float h = aa_backward(a0, b, c0, aa_opacities[i] * a9[5], aa_ga, aa_gb, aa_gc);
+            PUTL(L_op, dL_dopacity, i, h * a9[5], CSPLAT_ACC_OPACITY);
+        } else {
+            cov2d_from_cov3d(c6, pj, a, b, c);
+        }
         const float denom = a * c - b * b;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
         const float gcx = a9[2], gcy = a9[3], gcz = a9[4];
@@ -115,6 +126,7 @@
             dL_da = denom2inv * (-c * c * gcx + 2.f * b * c * gcy + (denom - a * c) * gcz);
             dL_dc = denom2inv * (-a * a * gcz + 2.f * a * b * gcy + (denom - a * c) * gcx);
             dL_db = denom2inv * 2.f * (b * c * gcx - (denom + 2.f * b * b) * gcy + a * b * gcz);
+            if constexpr (AA) { dL_da += aa_ga; dL_db += aa_gb; dL_dc += aa_gc; }
             g6[0] = t0[0] * t0[0] * dL_da + t0[0] * t1[0] * dL_db + t1[0] * t1[0] * dL_dc;
             g6[3] = t0[1] * t0[1] * dL_da + t0[1] * t1[1] * dL_db + t1[1] * t1[1] * dL_dc;
             g6[5] = t0[2] * t0[2] * dL_da + t0[2] * t1[2] * dL_db + t1[2] * t1[2] * dL_dc;

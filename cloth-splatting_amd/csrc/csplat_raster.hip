@@ -138,6 +138,50 @@ __device__ __forceinline__ void cov2d_from_cov3d(const float *c6, const ProjJac 
     c = (u1[0] * t1[0] + u1[1] * t1[1] + u1[2] * t1[2]) + 0.3f;
 }
 
+// ---- antialiasing (csplat_view.prefiltered & CSPLAT_ANTIALIAS): the opacity is scaled by the ratio of the footprint areas of the
+// undilated and the dilated cov2D, o' = o h with h = sqrt(max(2.5e-5, det0 / det1)).  (a0, b, c0) = T Sigma T^T without the 0.3 px^2
+// dilation: the same sums cov2d_from_cov3d forms before it adds 0.3, so a0 + 0.3f / c0 + 0.3f are its a / c bit for bit.  K1 and K8
+// form h with these helpers (contraction off), so both see the same h.
+__device__ __forceinline__ void cov2d_undilated(const float *c6, const ProjJac &pj, float &a0, float &b, float &c0) {
+#pragma clang fp contract(off)
+    const float *t0 = pj.t0, *t1 = pj.t1;
+    const float Vm[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
+    float u0[3], u1[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        u0[j] = t0[0] * Vm[0][j] + t0[1] * Vm[1][j] + t0[2] * Vm[2][j];
+        u1[j] = t1[0] * Vm[0][j] + t1[1] * Vm[1][j] + t1[2] * Vm[2][j];
+    }
+    a0 = u0[0] * t0[0] + u0[1] * t0[1] + u0[2] * t0[2];
+    b = u0[0] * t1[0] + u0[1] * t1[1] + u0[2] * t1[2];
+    c0 = u1[0] * t1[0] + u1[1] * t1[1] + u1[2] * t1[2];
+}
+constexpr float AA_DILATE = 0.3f, AA_FLOOR = 2.5e-5f;
+// h of (a0, b, c0); det1 = (a0 + 0.3)(c0 + 0.3) - b^2 is the determinant K1 inverts for the conic
+__device__ __forceinline__ float aa_factor(float a0, float b, float c0) {
+#pragma clang fp contract(off)
+    const float det0 = a0 * c0 - b * b;
+    const float det1 = (a0 + AA_DILATE) * (c0 + AA_DILATE) - b * b;
+    return sqrtf(fmaxf(AA_FLOOR, det0 / det1));
+}
+// K8: g = o dL/do' (the raw opacity times the opacity moment M0); adds g dh/d(a0, b, c0) to (ga, gb, gc) -- b is the one scalar
+// off-diagonal entry, as in dL_db.  With f = det0 / det1, w = 0.3: df/da0 = w (c0^2 + w c0 + b^2) / det1^2, df/dc0 = w (a0^2 + w a0 + b^2)
+// / det1^2, df/db = -2 w b (a0 + c0 + w) / det1^2, dh = df / (2 h); nothing where the floor is active.  Returns h.
+__device__ __forceinline__ float aa_backward(float a0, float b, float c0, float g, float &ga, float &gb, float &gc) {
+#pragma clang fp contract(off)
+    const float det0 = a0 * c0 - b * b;
+    const float det1 = (a0 + AA_DILATE) * (c0 + AA_DILATE) - b * b;
+    const float f = det0 / det1;
+    const float h = sqrtf(fmaxf(AA_FLOOR, f));
+    if (f > AA_FLOOR) {
+        const float k = g * AA_DILATE / (2.f * h * det1 * det1);
+        ga += k * (c0 * c0 + AA_DILATE * c0 + b * b);
+        gc += k * (a0 * a0 + AA_DILATE * a0 + b * b);
+        gb += k * (-2.f * b * (a0 + c0 + AA_DILATE));
+    }
+    return h;
+}
+
 __device__ __forceinline__ void tile_rect(float px, float py, int rad, const Cam &c, int &minx, int &miny, int &maxx,
                                           int &maxy) {
 #pragma clang fp contract(off)
@@ -165,8 +209,9 @@ __device__ __forceinline__ void stage_sh_rows(const float *__restrict__ src, int
 
 // ------------------------------------------------------------------------------------------- K1
 // s_shrows: the workgroup's SH rows in LDS when STAGE (filled by the caller: once per workgroup, also when it serves
-// several views)
-template <bool STAGE>
+// several views).  AA (k_preprocess_aa / k_preprocess_views_aa): the stored opacity is o' = o h (aa_factor) -- conic_opacity.w, the pack
+// record, cut2 and everything downstream see o'; the conic, radius and tile rectangle still come from the dilated cov2D.
+template <bool STAGE, bool AA = false>
 __device__ __forceinline__ void preprocess_body(int P, int D, int M, const float *__restrict__ means3D,
                                                 const float *__restrict__ shs,
                                                 const float *__restrict__ colors_precomp,
@@ -206,7 +251,15 @@ __device__ __forceinline__ void preprocess_body(int P, int D, int M, const float
         ProjJac pj;
         proj_jacobian(pv, cam, pj);
         float a, b, c;
-        cov2d_from_cov3d(c6, pj, a, b, c);
+        float aa_h = 1.f;
+        if constexpr (AA) {
+            float a0, c0;
+            cov2d_undilated(c6, pj, a0, b, c0);
+            a = a0 + AA_DILATE; c = c0 + AA_DILATE;
+            aa_h = aa_factor(a0, b, c0);
+        } else {
+            cov2d_from_cov3d(c6, pj, a, b, c);
+        }
         const float det = a * c - b * b;
         if (det == 0.0f) break;
         const float det_inv = 1.f / det;
@@ -257,7 +310,8 @@ __device__ __forceinline__ void preprocess_body(int P, int D, int M, const float
         depth = pv[2];
         rad = r;
         px = ix; py = iy;
-        const float op = opacities[i];
+        float op = opacities[i];
+        if constexpr (AA) op = op * aa_h;
         co = make_float4(c * det_inv, -b * det_inv, a * det_inv, op);
         touched = (uint32_t)((maxy - miny) * (maxx - minx));
         // culling radius: alpha >= 1/255 needs d^2 <= 2*lambda_max*ln(255*opacity).  lam1 >= lambda_max (the max(0.1,.)
@@ -303,6 +357,25 @@ __global__ __launch_bounds__(256) void k_preprocess(int P, int D, int M, const f
     preprocess_body<STAGE>(P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_mod, rotations, cov3D_precomp, cam, g, radii,
                            nocull, s_shrows, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)threadIdx.x);
 }
+// (the antialiased K1: k_preprocess with o' = o h; a kernel of its own so that k_preprocess is compiled exactly as before)
+template <bool STAGE>
+__global__ __launch_bounds__(256) void k_preprocess_aa(int P, int D, int M, const float *__restrict__ means3D,
+                                                        const float *__restrict__ shs,
+                                                        const float *__restrict__ colors_precomp,
+                                                        const float *__restrict__ opacities,
+                                                        const float *__restrict__ scales, float scale_mod,
+                                                        const float *__restrict__ rotations,
+                                                        const float *__restrict__ cov3D_precomp, Cam cam, Geom g,
+                                                        int32_t *__restrict__ radii, int nocull) {
+    __shared__ float s_shrows[STAGE ? 256 * SH_ROW : 1];
+    if (STAGE) {
+        const int base = blockIdx.x * 256;
+        stage_sh_rows<256>(shs + (size_t)base * 48, min(256, P - base), s_shrows);
+        __syncthreads();
+    }
+    preprocess_body<STAGE, true>(P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_mod, rotations, cov3D_precomp, cam, g,
+                                 radii, nocull, s_shrows, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)threadIdx.x);
+}
 
 // The first phase of the forward (K1 + the three counting kernels) for ALL views of a step, one launch each (blockIdx.y =
 // view): a 4-view step otherwise spends 16 launches (~10 us of host time each, the GPU idling in between) before its one
@@ -340,6 +413,24 @@ __global__ __launch_bounds__(256) void k_preprocess_views(int P, int D, int M, c
         const K1View &w = tab.v[vi];
         preprocess_body<STAGE>(P, D, M, w.means3D, shs, nullptr, opacities, scales, scale_mod, w.rotations, nullptr, w.cam, w.g, w.radii, nocull,
                                s_shrows, base + lane, lane);
+    }
+}
+template <bool STAGE>
+__global__ __launch_bounds__(256) void k_preprocess_views_aa(int P, int D, int M, const float *__restrict__ shs,
+                                                              const float *__restrict__ opacities,
+                                                              const float *__restrict__ scales, float scale_mod, K1Table tab,
+                                                              int nocull) {
+    __shared__ float s_shrows[STAGE ? K1V_G * SH_ROW : 1];
+    const int base = blockIdx.x * K1V_G;
+    if (STAGE) {
+        stage_sh_rows<256>(shs + (size_t)base * 48, min(K1V_G, P - base), s_shrows);
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    for (int vi = threadIdx.x >> 6; vi < tab.n; vi += 4) {
+        const K1View &w = tab.v[vi];
+        preprocess_body<STAGE, true>(P, D, M, w.means3D, shs, nullptr, opacities, scales, scale_mod, w.rotations, nullptr, w.cam, w.g, w.radii,
+                                     nocull, s_shrows, base + lane, lane);
     }
 }
 
@@ -2552,7 +2643,10 @@ __device__ __forceinline__ void cam_block_sum(const float *s, int nrows, float *
 // row, the workgroup sums them in a fixed order into slab row blockIdx.x (cam_block_sum).  The Gaussian's own gradients are computed by
 // exactly the same expressions: the partials only read values the body has formed (never a product that feeds a sum), so no FMA
 // contraction of the default arithmetic changes.
-template <bool STAGE, int NT, bool DEPTH, bool CAM = false>
+// AA (k_preprocess_bwd_aa, antialiasing only): record slot 5 holds dL/do' of the view's o' = o h; dL/dopacity = h dL/do' and o dL/do' dh
+// (aa_backward) joins the cov2D gradient before it is turned into the cov3D / scale / rotation / mean (and, with CAM, camera) gradients.
+// aa_opacities = the raw opacities o.
+template <bool STAGE, int NT, bool DEPTH, bool CAM = false, bool AA = false>
 __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const float *__restrict__ means3D,
                                                          const float *__restrict__ shs, const float *__restrict__ scales,
                                                          float scale_mod, const float *__restrict__ rotations,
@@ -2562,7 +2656,8 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
                                                          float *__restrict__ dL_dopacity, float *__restrict__ dL_dcolor,
                                                          float *__restrict__ dL_dmean3D, float *__restrict__ dL_dcov3D,
                                                          float *__restrict__ dL_dsh, float *__restrict__ dL_dscale,
-                                                         float *__restrict__ dL_drot, unsigned accmask, float *__restrict__ cam_slab = nullptr) {
+                                                         float *__restrict__ dL_drot, unsigned accmask, float *__restrict__ cam_slab = nullptr,
+                                                         const float *__restrict__ aa_opacities = nullptr) {
     // accmask (CSPLAT_ACC_*): outputs that are ADDED to instead of written -- several views of one step share the
     // gradient buffer of a shared parameter (csplat_backward_views), which replaces autograd's per-view temporaries
     // and its V-1 summation launches per parameter.
@@ -2593,13 +2688,14 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
     a9[0] *= (float)cam.W; a9[1] *= (float)cam.H;      // (K7 leaves dL/dmean2D without the pixel <- NDC factors 2 * 0.5 W, 2 * 0.5 H)
     dL_dmean2D[3 * i] = a9[0]; dL_dmean2D[3 * i + 1] = a9[1]; dL_dmean2D[3 * i + 2] = 0.f;
     dL_dconic[4 * i] = a9[2]; dL_dconic[4 * i + 1] = a9[3]; dL_dconic[4 * i + 2] = 0.f; dL_dconic[4 * i + 3] = a9[4];
-    PUT(dL_dopacity, i, a9[5], CSPLAT_ACC_OPACITY);
+    if constexpr (!AA) PUT(dL_dopacity, i, a9[5], CSPLAT_ACC_OPACITY);     // (AA: h dL/do', below)
     PUT(dL_dcolor, 3 * i, a9[6], CSPLAT_ACC_COLOR); PUT(dL_dcolor, 3 * i + 1, a9[7], CSPLAT_ACC_COLOR);
     PUT(dL_dcolor, 3 * i + 2, a9[8], CSPLAT_ACC_COLOR);
 
     float dmean[3] = {0.f, 0.f, 0.f};
     float g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (!vis) {
+        if constexpr (AA) PUT(dL_dopacity, i, 0.f, CSPLAT_ACC_OPACITY);
 #pragma unroll
         for (int k = 0; k < 3; k++) PUT(dL_dmean3D, 3 * i + k, 0.f, CSPLAT_ACC_MEAN3D);
 #pragma unroll
@@ -2622,7 +2718,16 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
 #pragma unroll
         for (int k = 0; k < 6; k++) c6[k] = g.cov3D[6 * i + k];
         float a, b, c;
-        cov2d_from_cov3d(c6, pj, a, b, c);
+        float aa_ga = 0.f, aa_gb = 0.f, aa_gc = 0.f;     // (AA) o dL/do' dh/d(a0, b, c0)
+        if constexpr (AA) {
+            float a0, c0;
+            cov2d_undilated(c6, pj, a0, b, c0);
+            a = a0 + AA_DILATE; c = c0 + AA_DILATE;
+            const float h = aa_backward(a0, b, c0, aa_opacities[i] * a9[5], aa_ga, aa_gb, aa_gc);
+            PUT(dL_dopacity, i, h * a9[5], CSPLAT_ACC_OPACITY);
+        } else {
+            cov2d_from_cov3d(c6, pj, a, b, c);
+        }
         const float denom = a * c - b * b;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
         const float gcx = a9[2], gcy = a9[3], gcz = a9[4];
@@ -2632,6 +2737,7 @@ __device__ __forceinline__ void preprocess_bwd_body(int P, int D, int M, const f
             dL_da = denom2inv * (-c * c * gcx + 2.f * b * c * gcy + (denom - a * c) * gcz);
             dL_dc = denom2inv * (-a * a * gcz + 2.f * a * b * gcy + (denom - a * c) * gcx);
             dL_db = denom2inv * 2.f * (b * c * gcx - (denom + 2.f * b * b) * gcy + a * b * gcz);
+            if constexpr (AA) { dL_da += aa_ga; dL_db += aa_gb; dL_dc += aa_gc; }
             g6[0] = t0[0] * t0[0] * dL_da + t0[0] * t1[0] * dL_db + t1[0] * t1[0] * dL_dc;
             g6[3] = t0[1] * t0[1] * dL_da + t0[1] * t1[1] * dL_db + t1[1] * t1[1] * dL_dc;
             g6[5] = t0[2] * t0[2] * dL_da + t0[2] * t1[2] * dL_db + t1[2] * t1[2] * dL_dc;
@@ -2816,6 +2922,11 @@ template <bool STAGE, int NT, bool DEPTH>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_cam(CSPLAT_K8_ARGS, float *__restrict__ cam_slab) {
     preprocess_bwd_body<STAGE, NT, DEPTH, true>(CSPLAT_K8_PASS, cam_slab);
 }
+// the antialiased K8 (every combination of the DEPTH / CAM paths; cam_slab NULL without CAM), opacities = the raw o
+template <bool STAGE, int NT, bool DEPTH, bool CAM>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd_aa(CSPLAT_K8_ARGS, float *__restrict__ cam_slab, const float *__restrict__ opacities) {
+    preprocess_bwd_body<STAGE, NT, DEPTH, CAM, true>(CSPLAT_K8_PASS, cam_slab, opacities);
+}
 #undef CSPLAT_K8_ARGS
 #undef CSPLAT_K8_PASS
 
@@ -2856,16 +2967,20 @@ template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
                                                                const float *__restrict__ scales, float scale_mod,
                                                                int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = false, CAM = false;
+    constexpr bool DEPTH = false, CAM = false, AA = false;
     const CamSlabs *const cam_slabs = nullptr;
+    const float *const aa_opacities = nullptr;
+    (void)aa_opacities;
 #include "csplat_k8_views_body.h"
 }
 template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_depth(int P, int D, int M, const float *__restrict__ shs,
                                                                      const float *__restrict__ scales, float scale_mod,
                                                                      int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = true, CAM = false;
+    constexpr bool DEPTH = true, CAM = false, AA = false;
     const CamSlabs *const cam_slabs = nullptr;
+    const float *const aa_opacities = nullptr;
+    (void)aa_opacities;
 #include "csplat_k8_views_body.h"
 }
 template <int NT, int VL, bool DEPTH>
@@ -2873,8 +2988,22 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_cam(int P, int D, i
                                                                    const float *__restrict__ scales, float scale_mod,
                                                                    int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
                                                                    CamSlabs slabs) {
-    constexpr bool CAM = true;
+    constexpr bool CAM = true, AA = false;
     const CamSlabs *const cam_slabs = &slabs;
+    const float *const aa_opacities = nullptr;
+    (void)aa_opacities;
+#include "csplat_k8_views_body.h"
+}
+// AA: the antialiased batched K8 on any of the paths above (slabs used with CAM only); opacities = the raw o every view shares
+template <int NT, int VL, bool DEPTH, bool CAM>
+__global__ __launch_bounds__(NT) void k_preprocess_bwd_views_aa(int P, int D, int M, const float *__restrict__ shs,
+                                                                  const float *__restrict__ scales, float scale_mod,
+                                                                  int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
+                                                                  CamSlabs slabs, const float *__restrict__ opacities) {
+    constexpr bool AA = true;
+    const CamSlabs *const cam_slabs = &slabs;
+    const float *const aa_opacities = opacities;
+    (void)cam_slabs;
 #include "csplat_k8_views_body.h"
 }
 
@@ -3185,6 +3314,7 @@ struct FwdTicket {
     void *alloc_ctx = nullptr;
     uint32_t *mb_dev = nullptr;
     int D = 0, M = 0;
+    bool aa = false;        // prefiltered & CSPLAT_ANTIALIAS: K1 stores o' = o h (k_preprocess_aa / k_preprocess_views_aa)
     float scale_modifier = 1.f;
     const float *means3D = nullptr, *shs = nullptr, *colors_precomp = nullptr, *opacities = nullptr, *scales = nullptr, *rotations = nullptr,
                 *cov3D_precomp = nullptr;
@@ -3200,7 +3330,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
                          const float *proj, const float *campos, float tanfovx, float tanfovy, int prefiltered,
                          csplat_alloc_fn alloc, void *alloc_ctx, int32_t *radii, int *ticket_out) {
     hipStream_t s = (hipStream_t)stream;
-    (void)prefiltered;
+    // (bit 0, upstream's prefiltered, is ignored; bit 1 is CSPLAT_ANTIALIAS)
     CSPLAT_REQUIRE(P >= 0 && W > 0 && H > 0, "csplat_forward: bad sizes");
     CSPLAT_REQUIRE(ticket_out != nullptr, "csplat_forward_begin: ticket_out missing");
     // (an empty input, P == 0, legitimately arrives with NULL data pointers)
@@ -3251,6 +3381,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
     t.table = table; t.bg = bg; t.radii = radii; t.alloc = alloc; t.alloc_ctx = alloc_ctx;
     t.D = D; t.M = M; t.means3D = means3D; t.shs = shs; t.colors_precomp = colors_precomp; t.opacities = opacities; t.scales = scales;
     t.scale_modifier = scale_modifier; t.rotations = rotations; t.cov3D_precomp = cov3D_precomp;
+    t.aa = (prefiltered & CSPLAT_ANTIALIAS) != 0;
     *ticket_out = tk;
     return 0;
 }
@@ -3265,7 +3396,13 @@ static int begin_launch(const FwdTicket &t) {
     if (P > 0) {
         ProfScope ps(PROF_K1, s);
         const bool stage = t.shs != nullptr && t.M == 16 && ((uintptr_t)t.shs & 15u) == 0;
-        if (stage)
+        if (t.aa && stage)
+            k_preprocess_aa<true><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
+                                                                t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
+        else if (t.aa)
+            k_preprocess_aa<false><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
+                                                                 t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
+        else if (stage)
             k_preprocess<true><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
                                                              t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
         else
@@ -3302,7 +3439,7 @@ static bool begin_views_compatible(int V, const int *tk) {
         const FwdTicket &w = g_tickets[tk[i]];
         if (w.P != a.P || w.D != a.D || w.M != a.M || w.W != a.W || w.H != a.H || w.shs != a.shs || w.opacities != a.opacities ||
             w.scales != a.scales || w.scale_modifier != a.scale_modifier || w.colors_precomp || w.cov3D_precomp || !w.rotations ||
-            !w.can_bucket)
+            !w.can_bucket || w.aa != a.aa)
             return false;
     }
     return true;
@@ -3321,7 +3458,13 @@ static int begin_launch_views(int V, const int *tk, hipStream_t join) {
     {
         ProfScope ps(PROF_K1, join);
         const bool stage = a.M == 16 && ((uintptr_t)a.shs & 15u) == 0;
-        if (stage)
+        if (a.aa && stage)
+            k_preprocess_views_aa<true><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
+                                                                        nocull_mode());
+        else if (a.aa)
+            k_preprocess_views_aa<false><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
+                                                                         nocull_mode());
+        else if (stage)
             k_preprocess_views<true><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
                                                                      nocull_mode());
         else
@@ -3346,6 +3489,8 @@ int csplat_forward_begin(void *stream, int P, int D, int M, const float *bg, int
                          float scale_modifier, const float *rotations, const float *cov3D_precomp, const float *view,
                          const float *proj, const float *campos, float tanfovx, float tanfovy, int prefiltered,
                          csplat_alloc_fn alloc, void *alloc_ctx, int32_t *radii, int *ticket_out) {
+    CSPLAT_REQUIRE(!(prefiltered & CSPLAT_ANTIALIAS), "csplat_forward / csplat_forward_begin: CSPLAT_ANTIALIAS needs a csplat_view entry point "
+                                                      "(csplat_forward_views*), whose backward knows the bit");
     if (int rc = begin_prepare(stream, P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
                                cov3D_precomp, view, proj, campos, tanfovx, tanfovy, prefiltered, alloc, alloc_ctx, radii, ticket_out))
         return rc;
@@ -3737,7 +3882,7 @@ static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with
                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, void *scratch,
                          float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, bool depth_k8 = false,
-                         float *cam_slab = nullptr, int *cam_rows = nullptr) {
+                         float *cam_slab = nullptr, int *cam_rows = nullptr, const float *aa_opacities = nullptr) {
     CSPLAT_REQUIRE(geom && binning && image && out_color, "csplat_backward: missing saved state");
     CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
     CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward: scratch (csplat_backward_scratch_bytes) missing");
@@ -3789,6 +3934,27 @@ static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with
         CSPLAT_REQUIRE(ev != nullptr, "csplat_backward_views: no event");
         HIP_TRY(hipEventRecord(ev, s));
         HIP_TRY(hipStreamWaitEvent(k8s, ev, 0));
+    }
+    if (aa_opacities) {  // (antialiasing: the AA variant of whichever K8 the call takes -- default, DEPTH, CAM)
+        ProfScope ps(cam_slab ? PROF_K8_CAM : depth_k8 ? PROF_K8_DEPTH : PROF_K8, k8s);
+        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
+        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
+        const int nt = stage ? 128 : 256, grid = cdiv(P, nt);
+#define CSPLAT_K8_AA_LAUNCH(ST, NT_, DP, CM)                                                                                               \
+    k_preprocess_bwd_aa<ST, NT_, DP, CM><<<grid, NT_, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,                \
+                                                                cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D, dL_dconic,    \
+                                                                dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,       \
+                                                                dL_drot, accmask, cam_slab, aa_opacities)
+#define CSPLAT_K8_AA_STAGE(DP, CM) do { if (stage) CSPLAT_K8_AA_LAUNCH(true, 128, DP, CM); else CSPLAT_K8_AA_LAUNCH(false, 256, DP, CM); } while (0)
+        if (cam_slab && depth_k8) CSPLAT_K8_AA_STAGE(true, true);
+        else if (cam_slab) CSPLAT_K8_AA_STAGE(false, true);
+        else if (depth_k8) CSPLAT_K8_AA_STAGE(true, false);
+        else CSPLAT_K8_AA_STAGE(false, false);
+#undef CSPLAT_K8_AA_STAGE
+#undef CSPLAT_K8_AA_LAUNCH
+        LAUNCH_CHECK();
+        if (cam_slab && cam_rows) *cam_rows = grid;
+        return 0;
     }
     if (cam_slab) {      // (the camera-gradient path: one slab row per workgroup, summed by k_cam_sum; *cam_rows = the number of rows)
         ProfScope ps(PROF_K8_CAM, k8s);
@@ -4095,6 +4261,10 @@ static int forward_views_settle_impl(int V, csplat_view *v, void *join_stream, i
     return finish_views_one_by_one(V, v, pend.tk, V, join, rc == 0, rc);
 }
 
+// antialiasing (csplat_view.prefiltered & CSPLAT_ANTIALIAS): K1 stored o' = o h; K8 takes its AA variant and reads the raw opacities
+static bool aa_of(const csplat_view &w) { return (w.prefiltered & CSPLAT_ANTIALIAS) != 0; }
+static const float *aa_opacities_of(const csplat_view &w) { return aa_of(w) ? w.opacities : nullptr; }
+
 // Can ONE K8 serve all views?  Same Gaussians (P, D, M, scale modifier, SH and scale tensors), SH staging applicable, and every
 // gradient output either the SAME buffer in all views (then views after the first must have been asked to add into it) or
 // a DIFFERENT buffer in every view.  Fills the table and returns true; anything else keeps the per-view launches.
@@ -4109,7 +4279,9 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
         if (w.P != a.P || w.D != a.D || w.M != a.M || w.scale_modifier != a.scale_modifier || w.shs != a.shs || w.dL_dsh != a.dL_dsh ||
             w.scales != a.scales || w.cov3D_precomp || !w.rotations || !w.dL_dscale || !w.dL_drot || !(w.accmask & CSPLAT_ACC_SH))
             return false;
+        if (aa_of(w) != aa_of(a) || (aa_of(a) && w.opacities != a.opacities)) return false;     // (the AA K8 reads ONE opacity tensor)
     }
+    if (aa_of(a) && !a.opacities) return false;
     unsigned sharedmask = 0;
     auto classify = [&](auto get, unsigned bit) {      // -> false when the buffers are neither all equal nor all different
         bool all_same = true, all_diff = true;
@@ -4345,7 +4517,11 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
         const int nb = cdiv(a.P, 32);
         CamSlabs sl;
         for (int i = 0; i < V; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
-        k_preprocess_bwd_views_cam<128, 4, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
+        if (aa_of(a))
+            k_preprocess_bwd_views_aa<128, 4, true, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl,
+                                                                             a.opacities);
+        else
+            k_preprocess_bwd_views_cam<128, 4, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
         LAUNCH_CHECK();
         return cam ? cam_tail(V, v, join, cam_rows) : 0;
     }
@@ -4355,7 +4531,11 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
         const int nb = cdiv(a.P, 32);
         const int b_lo = (int)((int64_t)nb * slice / nslices), b_hi = (int)((int64_t)nb * (slice + 1) / nslices);
         if (b_hi > b_lo) {
-            k_preprocess_bwd_views_depth<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
+            if (aa_of(a))
+                k_preprocess_bwd_views_aa<128, 4, true, false><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0,
+                                                                                            a.dL_dsh, tab, b_lo, CamSlabs{}, a.opacities);
+            else
+                k_preprocess_bwd_views_depth<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
             LAUNCH_CHECK();
         }
         return cam ? cam_tail(V, v, join, cam_rows) : 0;
@@ -4367,7 +4547,7 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
                                    w.scale_modifier, w.rotations, w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii,
                                    w.geom, w.binning, w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
                                    w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, w.dL_ddepth != nullptr,
-                                   cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i]))
+                                   cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i], aa_opacities_of(w)))
             return rc;
     }
     return cam ? cam_tail(V, v, join, cam_rows) : 0;
@@ -4388,6 +4568,8 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
         for (int i = 0; i < V; i++)
             CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: camera gradients need scratch of csplat_backward_camera_scratch_bytes");
     }
+    for (int i = 0; i < V; i++)
+        CSPLAT_REQUIRE(!aa_of(v[i]) || v[i].opacities || v[i].P <= 0, "csplat_backward_views: CSPLAT_ANTIALIAS needs the view's opacities");
     bool feat = false;
     for (int i = 0; i < V; i++) feat = feat || feat_wanted(v[i]);
     if (feat) {
@@ -4487,7 +4669,7 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
                                        w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii, w.geom, w.binning,
                                        w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
                                        w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, false,
-                                       cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i]))
+                                       cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i], aa_opacities_of(w)))
                 return rc;
         }
         if (one_k8 && want_k8) {   // every view's K7 is queued on its own stream: the join stream waits for all of them, then ONE K8
@@ -4504,7 +4686,11 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
                 const int nb = cdiv(a.P, 32);
                 CamSlabs sl;
                 for (int i = 0; i < V; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
-                k_preprocess_bwd_views_cam<128, 4, false><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
+                if (aa_of(a))
+                    k_preprocess_bwd_views_aa<128, 4, false, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab,
+                                                                                      0, sl, a.opacities);
+                else
+                    k_preprocess_bwd_views_cam<128, 4, false><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
                 LAUNCH_CHECK();
                 return 0;
             }
@@ -4513,7 +4699,11 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
             const int nb = cdiv(a.P, 32);
             const int b_lo = (int)((int64_t)nb * slice / nslices), b_hi = (int)((int64_t)nb * (slice + 1) / nslices);
             if (b_hi > b_lo) {
-                k_preprocess_bwd_views<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
+                if (aa_of(a))
+                    k_preprocess_bwd_views_aa<128, 4, false, false><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0,
+                                                                                                 a.dL_dsh, tab, b_lo, CamSlabs{}, a.opacities);
+                else
+                    k_preprocess_bwd_views<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
                 LAUNCH_CHECK();
             }
         }

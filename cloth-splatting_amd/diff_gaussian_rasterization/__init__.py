@@ -17,6 +17,9 @@ is in libcsplat.so (csplat_forward_begin / _finish / csplat_backward).
 Beyond upstream, `features=` ([P, F] float32, 1 <= F <= 6) composites per-Gaussian feature channels with the colour's weights and
 `return_alpha=True` returns the alpha image 1 - T_final, both differentiable (include/csplat.h, csplat_view.features .. dL_dfeat_in);
 without them the call is exactly the upstream one.
+`antialiasing=True` (upstream's option of that name; gsplat's rasterize_mode="antialiased") scales every opacity by the ratio of the
+footprint areas of the undilated and the 0.3 px^2-dilated 2-D covariance, o' = o sqrt(max(2.5e-5, det0 / det1)), and renders and
+differentiates with o' (include/csplat.h, CSPLAT_ANTIALIAS); it composes with everything above.  Without it the call is unchanged.
 """
 import contextlib as _contextlib
 import ctypes as C
@@ -123,6 +126,15 @@ def _check_features(features, means3D):
     return int(features.shape[1])
 
 
+class _Antialias:
+    """marker: the LAST argument of _RasterizeGaussiansBatch.apply when the call renders antialiased (csplat_view.prefiltered |=
+    CSPLAT_ANTIALIAS in every view); absent otherwise, so that a call without antialiasing sees exactly the inputs it saw before"""
+
+
+_ANTIALIAS = _Antialias()
+CSPLAT_ANTIALIAS = 2      # csplat.h
+
+
 def _feature_mode_check():
     """feature / alpha images are rendered by eager steps only"""
     if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
@@ -131,13 +143,14 @@ def _feature_mode_check():
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, features=None, return_alpha=False):
+                        raster_settings, features=None, return_alpha=False, antialiasing=False):
     """One camera (what GaussianRasterizer.forward calls, gaussian_renderer/__init__.py:156-164).  Since round 5 a single view goes
     through the same library entry as a batch of views (csplat_forward_views_deferred with V = 1): from the second call of an image size
     on, the second forward phase is launched on the previous call's capacities and the counts are read AFTER the host has prepared the
     backward -- a camera-by-camera loop (the reference's train_utils.py:259-272) no longer leaves the GPU idle for a host round trip per
     camera.  Images, radii, depth and gradients are those of _RasterizeGaussians (tests: test_batched_views_equal_single_view_calls)."""
     cam = _cam_group(raster_settings)
+    aa = (_ANTIALIAS,) if antialiasing else ()
     if features is not None or return_alpha:
         # (the feature / alpha path: always the batched Function with one view -- csplat_forward_views_* render the extra images,
         #  csplat_backward_views takes their gradients)
@@ -145,7 +158,12 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         _feature_mode_check()
         _n.require_cuda(means3D)
         return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                              cov3Ds_precomp, *cam, features, _FeatSpec([(F, return_alpha)]))
+                                              cov3Ds_precomp, *cam, features, _FeatSpec([(F, return_alpha)]), *aa)
+    if antialiasing:
+        # (antialiasing: the batched Function with one view as well -- only the csplat_view entry points carry the bit to K1 and K8)
+        _n.require_cuda(means3D)
+        return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                              cov3Ds_precomp, *cam, *aa)
     if PER_CALL_SPECULATION and means3D.is_cuda:
         return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                               cov3Ds_precomp, *cam)
@@ -466,6 +484,10 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         # flat: V groups of NIN per-view inputs, then -- only when a settings tensor wants a gradient (_cam_group) -- V groups of
         # (viewmatrix, projmatrix, campos, bg)
         V, n = len(settings), _RasterizeGaussiansBatch.NIN
+        # (last of all, when the call renders antialiased: the _ANTIALIAS marker)
+        ctx.aa = bool(flat) and flat[-1] is _ANTIALIAS
+        if ctx.aa:
+            flat = flat[:-1]
         # (then, when a view asks for feature or alpha images: V feature tensors (None where a view has none) and the _FeatSpec)
         spec = flat[-1] if flat and isinstance(flat[-1], _FeatSpec) else None
         feats = list(flat[-1 - V:-1]) if spec is not None else [None] * V
@@ -506,7 +528,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             v.depth = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
             v.radii = torch.empty(v.P, dtype=torch.int32, device=dev)
             w.stream = st.cuda_stream
-            w.P, w.D, w.M, w.W, w.H, w.prefiltered = v.P, int(rs.sh_degree), v.M, v.W, v.H, int(bool(rs.prefiltered))
+            w.P, w.D, w.M, w.W, w.H, w.prefiltered = v.P, int(rs.sh_degree), v.M, v.W, v.H, int(bool(rs.prefiltered)) | (CSPLAT_ANTIALIAS if ctx.aa else 0)
             w.scale_modifier, w.tanfovx, w.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
             w.bg, w.means3D, w.shs, w.colors_precomp = _n.ptr(v.bg), _n.ptr(v.means3D), _n.ptr(v.sh), _n.ptr(v.colors_precomp)
             w.opacities, w.scales, w.rotations = _n.ptr(v.opacities), _n.ptr(v.scales), _n.ptr(v.rotations)
@@ -577,6 +599,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         ctx.save_for_backward(*saved)
         # which view first received each input tensor OBJECT (shared parameters get one gradient buffer)
         ctx.first_of = [[next(j for j in range(i + 1) if flat[j * n + k] is flat[i * n + k]) for k in range(n)] for i in range(V)]
+        # (antialiasing: K8 reads the raw opacities through the views' `opacities` pointers -- those tensors live as long as the node)
+        ctx.aa_opacities = [v.opacities for v in views] if ctx.aa else None
         for v in views:
             v.drop_inputs()
             v.features = v.feat = v.alpha = None
@@ -720,6 +744,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         tail = (None,) * (4 * V) if ctx.cam else ()
         fspec = ctx.fspec or [(0, False)] * V
         ftail = (None,) * (V + 1) if ctx.fspec is not None else ()      # the views' feature tensors and the _FeatSpec
+        if ctx.aa:
+            ftail = ftail + (None,)                                       # the _ANTIALIAS marker
         per = [(2 if ctx.stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]     # outputs per view
         first = [sum(per[:i]) + (1 if ctx.stacked else 0) for i in range(V)]                          # a view's first output
         if ctx.stacked:
@@ -791,7 +817,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                     buf = owner[key]
                 w.dL_dfeat_in = _n.ptr(buf)
                 gs += [gf, ga]
-            ftail_out = tuple(fout) + (None,)
+            ftail_out = tuple(fout) + (None,) + ((None,) if ctx.aa else ())
         if want_feat or want_cam or any(gdep[i] is not None for i in active):
             # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout (the camera path: of the
             # camera layout; the feature path: of the feature layout), allocated here (never on the colour-only path) and cleared by the
@@ -814,7 +840,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             # (kept alive: the MEMORY the K8 slices write -- never the gradient tensor objects themselves: AccumulateGrad adopts a
             #  gradient only when nobody else holds it, and would otherwise snapshot the still unwritten buffer into a copy)
             outs, plan["out"] = tuple(plan["out"]), None
-            _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, ctx.saved_tensors)))
+            _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, ctx.saved_tensors,
+                                                                                          ctx.aa_opacities)))
             return (None, None) + outs + tail + ftail
         with _n.on_device(dev):
             rc = _n.lib.csplat_backward_views(len(active), C.cast(plan["sub"], C.c_void_p), main.cuda_stream)
@@ -831,8 +858,13 @@ def rasterize_views(settings, inputs, stacked=False):
     stacked=True (equal image sizes) returns (colors [V,3,H,W], [(colors[i], radii, depth), ...]) where `colors` is the
     differentiable output -- the batch the reference assembles with torch.cat before its losses -- and colors[i] are
     plain slices of it.  A dict may also carry `features` ([P, F], the same F in every view) and `return_alpha`: that view's tuple
-    then grows by feat [F,H,W] and / or alpha [1,H,W] (GaussianRasterizer.forward)."""
+    then grows by feat [F,H,W] and / or alpha [1,H,W] (GaussianRasterizer.forward).  `antialiasing` (GaussianRasterizer.forward) must be
+    the same in every dict of a call (ValueError otherwise)."""
     flat, fspec, feats = [], [], []
+    aa = {bool(kw.get("antialiasing", False)) for kw in inputs}
+    if len(aa) > 1:
+        raise ValueError("rasterize_views: antialiasing must be the same in every view of a call, got "
+                         f"{[bool(kw.get('antialiasing', False)) for kw in inputs]}")
     for kw in inputs:
         f, want_alpha = kw.get("features"), bool(kw.get("return_alpha", False))
         fspec.append((_check_features(f, kw["means3D"]) if f is not None else 0, want_alpha))
@@ -853,6 +885,8 @@ def rasterize_views(settings, inputs, stacked=False):
             raise ValueError(f"rasterize_views: every view must have the same number of feature channels, got {[f for f, _a in fspec]}")
         _feature_mode_check()
         flat += feats + [_FeatSpec(fspec)]
+    if True in aa:
+        flat.append(_ANTIALIAS)
     res = _RasterizeGaussiansBatch.apply(tuple(settings), bool(stacked), *flat)
     per = [(2 if stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]
     at = [sum(per[:i]) + (1 if stacked else 0) for i in range(len(settings))]
@@ -878,15 +912,19 @@ class GaussianRasterizer(nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, features=None, return_alpha=False):
+                cov3D_precomp=None, features=None, return_alpha=False, antialiasing=False):
         """-> (color [3,H,W], radii [P], depth [1,H,W]), then feat [F,H,W] when `features` ([P, F] float32, 1 <= F <= 6, on the device of
         means3D) is given -- feat[c] = sum_i T_i alpha_i features[i, c] over exactly the Gaussians the colour blends, no background term --
         then alpha [1,H,W] = 1 - T_final when `return_alpha` (color = sum T alpha c + (1 - alpha) bg).  Both are differentiable; neither
-        is rendered by a forward launched on faith or a captured step (RuntimeError), nor differentiated inside deferred_k8()."""
+        is rendered by a forward launched on faith or a captured step (RuntimeError), nor differentiated inside deferred_k8().
+        antialiasing=True: every opacity o becomes o' = o h, h = sqrt(max(2.5e-5, det0 / det1)) with det0 / det1 the determinants of
+        the 2-D covariance before / after its 0.3 px^2 dilation -- a footprint below pixel size keeps the coverage of its true size.
+        Images and gradients (opacities.grad = h dL/do', the covariance and camera terms through h) all use o'; it works eagerly, on
+        faith, in captured / replayed steps and under deferred_k8()."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, features, bool(return_alpha))
+                                   self.raster_settings, features, bool(return_alpha), bool(antialiasing))

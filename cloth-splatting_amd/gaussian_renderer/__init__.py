@@ -156,6 +156,8 @@ def _prepare(viewpoint_camera, pc, simulator, pipe, bg_color, scaling_modifier, 
     # tests/golden/render_wiring.npz holds what the reference's own render() hands over in every branch)
     kwargs = dict(means3D=means3D_deform, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
                   opacities=opacity, scales=scales, rotations=rotations_deform, cov3D_precomp=cov3D_precomp)
+    if getattr(pipe, "antialiasing", False):     # (upstream's pipeline flag; passed only when set, so the call is otherwise unchanged)
+        kwargs["antialiasing"] = True
     return raster_settings, kwargs, (screenspace_points, means3D_deform, vertice_deform, rotations_deform, opacity)
 
 

@@ -158,9 +158,25 @@ enum { CSPLAT_ACC_OPACITY = 1, CSPLAT_ACC_COLOR = 2, CSPLAT_ACC_MEAN3D = 4, CSPL
         * step (25.6 MB of zero fill for four views of 100k Gaussians).  Without the bit the library clears the records itself. */
        CSPLAT_SCRATCH_ZEROED = 256 };
 #define CSPLAT_MAX_FEATURES 6    /* ABI 9: csplat_view.n_features <= 6 (record slots 10..15 of the compositing backward) */
+/* csplat_view.prefiltered is a bit word.  Bit 0 is upstream's `prefiltered` flag and is ignored, as before.
+ * CSPLAT_ANTIALIAS (bit 1): antialiased rendering with opacity compensation (upstream's `antialiasing` option).  K1 widens every projected
+ * covariance by 0.3 px^2; with the bit it also scales the opacity by the ratio of the footprint areas it has widened.  With
+ * (a0, b, c0) = T Sigma T^T, the cov2D before the 0.3 is added:
+ *     det0 = a0 c0 - b^2,   det1 = (a0 + 0.3)(c0 + 0.3) - b^2   (the determinant the conic inverts),
+ *     h = sqrt(max(2.5e-5, det0 / det1)),   o' = opacity h,
+ * and every later use of the view's opacity is o': conic_opacity.w, the culling radius 2 lambda ln(255 o'), the 1/255 skip, the 0.99 cap,
+ * the stop rule, n_contrib, the colour, depth, feature and alpha images.  Conic, radius and tile rectangle are those of the widened cov2D,
+ * unchanged.  The backward is the chain rule through h: dL/dopacity = h dL/do', and opacity dL/do' dh/d(a0, b, c0) joins the cov2D
+ * gradient (b the one scalar off-diagonal entry; dh = 0 where the 2.5e-5 floor is active) before it reaches cov3D, scales, rotations,
+ * means3D and the camera gradients.  It composes with the depth, camera, feature / alpha paths, launches on faith, captured steps and
+ * csplat_backward_views_parts slices.  Honoured by csplat_forward_views, _deferred / _settle, _faith, csplat_backward_views and _parts
+ * (the backward reads the view's `opacities`: keep them alive and unchanged until it has run); the views of one batched launch share
+ * the bit (views that differ take the per-view launches; csplat_forward_views_faith refuses them).  csplat_forward / csplat_forward_begin
+ * return an error when it is set: their backward cannot see it. */
+#define CSPLAT_ANTIALIAS 2
 typedef struct csplat_view {
     void *stream;
-    int P, D, M, W, H, prefiltered;
+    int P, D, M, W, H, prefiltered;   /* prefiltered: bit 0 ignored, CSPLAT_ANTIALIAS */
     float scale_modifier, tanfovx, tanfovy;
     const float *bg, *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp, *view, *proj, *campos;
     void *alloc_ctx;
