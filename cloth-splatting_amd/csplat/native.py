@@ -50,6 +50,8 @@ EXPORTS = {
     "csplat_forward_views_settle": (_i, [_i, _vp, _vp, _vp]),
     "csplat_forward_views_faith": (_i, [_i, _vp, ALLOC_FN, _vp, _vp, _vp]),
     "csplat_image_info_offset": (C.c_size_t, [_i, _i]),
+    "csplat_visibility_scratch_bytes": (_sz, [_i, _i64, _i, _i]),
+    "csplat_visibility_views": (_i, [_i, _vp, _vp, _vp]),
     "csplat_backward_views": (_i, [_i, _vp, _vp]),
     "csplat_backward_views_parts": (_i, [_i, _vp, _vp, C.c_uint, _i, _i]),
     "csplat_backward_slice_rows": (_i, [_i, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -346,6 +348,11 @@ class CsplatView(C.Structure):
                                                                                 "dL_dfeat_in")])
 
 
+class CsplatVisibility(C.Structure):
+    """mirror of `csplat_visibility` (include/csplat.h): one view's visibility outputs and scratch, each NULL = not wanted"""
+    _fields_ = [(n, _vp) for n in ("weight_max", "weight_sum", "pixel_count", "top_id", "scratch")]
+
+
 ACC_OPACITY, ACC_COLOR, ACC_MEAN3D, ACC_COV3D, ACC_SH, ACC_SCALE, ACC_ROT = 1, 2, 4, 8, 16, 32, 64
 
 
@@ -383,7 +390,8 @@ def group_by_key(keys, n_keys):
 
 PROF_CLASSES = ["K1_preprocess", "K2_scan", "K3_emit_keys", "K4_radix_sort", "K5_tile_ranges", "K6_render_fwd",
                 "K7_render_bwd", "K8_preprocess_bwd", "K9_dist2", "GNN", "K7_depth_partials", "K7_depth_bwd", "K8_depth_bwd",
-                "K8_camera_bwd", "camera_sums", "K6_features", "K7_feature_partials", "K7_feature_bwd", "feature_grads"]
+                "K8_camera_bwd", "camera_sums", "K6_features", "K7_feature_partials", "K7_feature_bwd", "feature_grads",
+                "visibility"]
 MAX_FEATURES = 6      # csplat.h: CSPLAT_MAX_FEATURES
 
 

@@ -2567,6 +2567,195 @@ __global__ __launch_bounds__(256) void k_feature_grads(FeatTable tab) {
     }
 }
 
+// ------------------------------------------------------------------------------------------- Gaussian visibility, top-contributor map
+// (csplat_visibility_views.)  Forward-only, launched only when asked for; K1..K8 and the feature kernels are untouched.  w_i(pix) = T_i alpha_i is
+// the colour's blending weight (walk_segment's test: alpha with the 0.99 cap, 1/255 skip, n_contrib).  No float atomics: every sum runs in
+// a fixed order, so the outputs are bit-reproducible in the default mode.
+// Walk: one workgroup per tile, the pixels as in the feature forward.  The 16 lanes of a 4x4 block (one 16-lane row of a wave) step through
+// their block's bbits positions in lockstep (the walk ends at the row's largest n_contrib; a lane past its own contributes 0) and join
+// their weights per entry with DPP row scans (max, sum, count).  The 16 blocks of the tile meet in LDS: the sum as one slot per (block,
+// entry), added in block order; max and count are order-free LDS atomics.  One (max, sum, count) record per LIST ENTRY leaves per segment,
+// zeros included, so that every position of every list is written.  The pixel's top contributor (strictly larger weight, front to back:
+// a tie keeps the front-most) stays in registers.
+struct VisView {
+    const int2 *ranges;
+    const uint32_t *ids_sorted;
+    const unsigned long long *bbits;
+    const float4 *recA, *recB;
+    const int *seg_offset;
+    const float4 *ckpt;
+    const uint32_t *n_contrib;
+    int32_t *top_id;           // [H][W], NULL: not wanted
+    float *rec_max, *rec_sum;  // [R] per list entry (scratch), NULL: no per-Gaussian output wanted
+    int32_t *rec_cnt;
+    int W, H, gx, tiles;       // tiles = 0: the view has no list entries (top_id = -1 everywhere)
+};
+struct VisTable { VisView v[B2_MAX_VIEWS]; };
+static_assert(SEG == 256, "the visibility join keeps one list entry per thread of a segment");
+// inclusive scans over the 16 lanes of a DPP row (row_shr 1, 2, 4, 8; lanes shifted in from outside the row read 0): lane 15 of the row then
+// holds the row's sum / max / count, formed in the same order in every run
+template <int N> __device__ __forceinline__ float row_shr_f(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x110 + N, 0xF, 0xF, true)); }
+template <int N> __device__ __forceinline__ int row_shr_i(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x110 + N, 0xF, 0xF, true); }
+__device__ __forceinline__ void row16_join(float &mx, float &sm, int &cn) {     // (mx >= 0: the 0 shifted in is neutral)
+    mx = fmaxf(mx, row_shr_f<1>(mx)); sm += row_shr_f<1>(sm); cn += row_shr_i<1>(cn);
+    mx = fmaxf(mx, row_shr_f<2>(mx)); sm += row_shr_f<2>(sm); cn += row_shr_i<2>(cn);
+    mx = fmaxf(mx, row_shr_f<4>(mx)); sm += row_shr_f<4>(sm); cn += row_shr_i<4>(cn);
+    mx = fmaxf(mx, row_shr_f<8>(mx)); sm += row_shr_f<8>(sm); cn += row_shr_i<8>(cn);
+}
+__global__ __launch_bounds__(256) void k_visibility_walk_views(VisTable tab) {
+    const VisView &w = tab.v[blockIdx.y];
+    const int tile = blockIdx.x;
+    const int ntiles = w.gx * ((w.H + CSPLAT_TILE - 1) / CSPLAT_TILE);
+    if (tile >= ntiles) return;                                         // (uniform in the workgroup)
+    __shared__ float s_sum[16][SEG];
+    __shared__ uint32_t s_max[SEG];
+    __shared__ int s_cnt[SEG];
+    const int blk = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+    const int px = (tile % w.gx) * CSPLAT_TILE + (blk & 3) * 4 + (l16 & 3);
+    const int py = (tile / w.gx) * CSPLAT_TILE + (blk >> 2) * 4 + (l16 >> 2);
+    const bool inside = px < w.W && py < w.H;
+    const int pix = py * w.W + px;
+    const bool recs = w.rec_sum != nullptr;
+    float best = 0.f;
+    int best_id = -1;
+    if (w.tiles > 0) {
+        const int nc = inside ? (int)w.n_contrib[pix] : 0;
+        int ncr = nc;                                                   // the row's (block's) largest n_contrib
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) ncr = max(ncr, __shfl_xor(ncr, o, 16));
+        const int s0 = w.seg_offset[tile], s1 = w.seg_offset[tile + 1];
+        const uint32_t rx = (uint32_t)w.ranges[tile].x;
+        const int len = w.ranges[tile].y - (int)rx;
+        constexpr int NW = SEG / 64;
+        for (int slot = s0; slot < s1; slot++) {                        // (every segment, in every thread: the join below syncs)
+            const int seg_lo = (slot - s0) * SEG;
+            if (recs) {
+                float4 *z = reinterpret_cast<float4 *>(&s_sum[blk][l16 * 16]);
+                const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+                z[0] = zero; z[1] = zero; z[2] = zero; z[3] = zero;
+                s_max[threadIdx.x] = 0u;
+                s_cnt[threadIdx.x] = 0;
+                __syncthreads();
+            }
+            if (ncr > seg_lo) {                                         // (uniform in the row; K6 wrote this block's bbits / checkpoints)
+                float T = nc > seg_lo ? w.ckpt[(size_t)slot * 256 + threadIdx.x].x : 0.f;
+                const unsigned long long *bw = w.bbits + ((size_t)slot * 16 + (size_t)blk) * NW;
+                const float fx = (float)px, fy = (float)py;
+                int c = 0;
+                unsigned long long m = bw[0];
+                auto next = [&](int &p) -> bool {                       // the block's next blended position below ncr, in list order
+                    while (m == 0ull) {
+                        if (++c >= NW) return false;
+                        m = bw[c];
+                    }
+                    p = seg_lo + 64 * c + __builtin_ctzll(m);
+                    m &= m - 1ull;
+                    return p < ncr;
+                };
+                int pos = 0;
+                bool have = next(pos);
+                float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
+                if (have) { A = w.recA[rx + (uint32_t)pos]; B = w.recB[rx + (uint32_t)pos]; }
+                while (have) {
+                    int npos = 0;
+                    const bool nhave = next(npos);                      // (the next entry's records are loaded before this one is used)
+                    float4 nA = A, nB = B;
+                    if (nhave) { nA = w.recA[rx + (uint32_t)npos]; nB = w.recB[rx + (uint32_t)npos]; }
+                    const float dx = A.x - fx, dy = A.y - fy;
+                    const float power = -0.5f * (A.z * dx * dx + B.x * dy * dy) - A.w * dx * dy;
+                    const float a = fminf(0.99f, B.y * __expf(power));
+                    const bool bl = pos < nc && !(power > 0.f || a < ALPHA_MIN);
+                    const float wt = bl ? a * T : 0.f;
+                    if (bl) {
+                        if (wt > best) { best = wt; best_id = (int)w.ids_sorted[rx + (uint32_t)pos]; }
+                        T *= 1.f - a;
+                    }
+                    if (recs) {
+                        float mx = wt, sm = wt;
+                        int cn = bl ? 1 : 0;
+                        row16_join(mx, sm, cn);
+                        if (l16 == 15) {
+                            s_sum[blk][pos - seg_lo] = sm;
+                            if (cn > 0) {
+                                atomicMax(&s_max[pos - seg_lo], __float_as_uint(mx));     // (non-negative floats order as their bits)
+                                atomicAdd(&s_cnt[pos - seg_lo], cn);
+                            }
+                        }
+                    }
+                    pos = npos; A = nA; B = nB; have = nhave;
+                }
+            }
+            if (recs) {
+                __syncthreads();
+                const int e = seg_lo + (int)threadIdx.x;
+                if (e < len) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int b = 0; b < 16; b++) s += s_sum[b][threadIdx.x];
+                    w.rec_max[rx + e] = __uint_as_float(s_max[threadIdx.x]);
+                    w.rec_sum[rx + e] = s;
+                    w.rec_cnt[rx + e] = s_cnt[threadIdx.x];
+                }
+                __syncthreads();
+            }
+        }
+    }
+    if (inside && w.top_id) w.top_id[pix] = best_id;
+}
+// Per Gaussian, one 16-lane row: its records in the tiles of its rectangle (the entry found by binary search on the unique (depth bits, id)
+// key, as det_reduce_views_body does), lane l16 taking the tiles l16, l16 + 16, ... in y-major order, then the row's fixed-order join.
+// Every output row is written, zeros for radii == 0.
+struct VisRedView {
+    Cam cam;
+    const float2 *xy;
+    const float *depth;
+    const int32_t *radii;
+    const int2 *ranges;
+    const uint64_t *keys_sorted;
+    const uint32_t *ids_sorted;
+    const float *rec_max, *rec_sum;
+    const int32_t *rec_cnt;
+    float *weight_max, *weight_sum;   // [P], each NULL = not wanted
+    int32_t *pixel_count;
+    int P, tiles;                     // tiles = 0: no list entries (zeros); P = 0: nothing asked of this view
+};
+struct VisRedTable { VisRedView v[B2_MAX_VIEWS]; };
+__global__ __launch_bounds__(256) void k_visibility_reduce_views(VisRedTable tab) {
+    const VisRedView &w = tab.v[blockIdx.y];
+    const int i = blockIdx.x * 16 + (int)(threadIdx.x >> 4);            // 16 lanes (one DPP row) per Gaussian
+    const int l16 = threadIdx.x & 15;
+    if (i >= w.P) return;                                               // (uniform in the row)
+    float m = 0.f, s = 0.f;
+    int n = 0;
+    const int rad = w.tiles > 0 ? w.radii[i] : 0;
+    if (rad > 0) {
+        const float2 p = w.xy[i];
+        int minx, miny, maxx, maxy;
+        tile_rect(p.x, p.y, rad, w.cam, minx, miny, maxx, maxy);
+        const uint64_t want = ((uint64_t)__float_as_uint(w.depth[i]) << 32) | (uint32_t)i;
+        const int nx = maxx - minx, nt = nx * (maxy - miny);
+        for (int k = l16; k < nt; k += 16) {                            // lane l16: the rectangle's tiles k = l16 (mod 16), y-major
+            const int y = miny + k / nx, x = minx + k % nx;
+            const int2 rg = w.ranges[y * w.cam.gx + x];
+            int lo = rg.x, hi = rg.y;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                const uint64_t key = ((w.keys_sorted[mid] & 0xFFFFFFFFull) << 32) | w.ids_sorted[mid];
+                if (key < want) lo = mid + 1; else hi = mid;
+            }
+            if (lo >= rg.y || w.ids_sorted[lo] != (uint32_t)i) continue;
+            m = fmaxf(m, w.rec_max[lo]);
+            s += w.rec_sum[lo];
+            n += w.rec_cnt[lo];
+        }
+    }
+    row16_join(m, s, n);
+    if (l16 != 15) return;
+    if (w.weight_max) w.weight_max[i] = m;
+    if (w.weight_sum) w.weight_sum[i] = s;
+    if (w.pixel_count) w.pixel_count[i] = n;
+}
+
 // ------------------------------------------------------------------------------------------- K8
 // K7's per-Gaussian record (round 6) holds the MOMENTS of m = G dL/dalpha over the pixels the Gaussian was blended at, about its centre:
 // 0 Mx  1 My  2 Mxx  3 Mxy  4 Myy  5 M0  6..8 dL/dcolour.  With conic (a, b, c) and opacity o the pixel-level gradients upstream sums
@@ -4168,6 +4357,71 @@ static int feature_forward(int V, csplat_view *v, hipStream_t join) {
 int csplat_forward_views(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream) {
     const int rc = forward_views_impl(V, v, alloc, join_stream, nullptr);
     return rc ? rc : feature_forward(V, v, (hipStream_t)join_stream);
+}
+
+// Gaussian visibility and the top-contributor map of finished forward views: the per-entry records (max, sum, count) of the walk, back to
+// back in the scratch, each array 256-byte aligned.
+size_t csplat_visibility_scratch_bytes(int P, int64_t R, int W, int H) {
+    (void)P; (void)W; (void)H;
+    const size_t n = R > 0 ? (size_t)R : 0;
+    return 3 * align256(n * 4 + 4);
+}
+int csplat_visibility_views(int V, const csplat_view *v, const csplat_visibility *outs, void *join_stream) {
+    CSPLAT_REQUIRE(V >= 1 && V <= B2_MAX_VIEWS && v != nullptr && outs != nullptr, "csplat_visibility_views: 1 to 8 views and their outputs");
+    hipStream_t join = (hipStream_t)join_stream;
+    VisTable t;
+    VisRedTable r;
+    memset(&t, 0, sizeof(t));
+    memset(&r, 0, sizeof(r));
+    int maxtiles = 0, maxP = 0;
+    for (int i = 0; i < V; i++) {
+        const csplat_view &w = v[i];
+        const csplat_visibility &o = outs[i];
+        const bool per_g = o.weight_max || o.weight_sum || o.pixel_count;
+        if (!per_g && !o.top_id) continue;
+        CSPLAT_REQUIRE(w.num_rendered >= 0, "csplat_visibility_views: the view's forward is still pending (settle it first)");
+        CSPLAT_REQUIRE(w.valid == nullptr, "csplat_visibility_views: views launched on faith have no visibility pass");
+        CSPLAT_REQUIRE(w.P >= 0 && w.W > 0 && w.H > 0, "csplat_visibility_views: bad view size");
+        const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
+        const bool lists = w.P > 0 && w.num_rendered > 0;
+        CSPLAT_REQUIRE(!lists || (w.geom && w.binning && w.image), "csplat_visibility_views: missing chunks");
+        CSPLAT_REQUIRE(!lists || !per_g || o.scratch, "csplat_visibility_views: per-Gaussian outputs need the scratch");
+        CSPLAT_REQUIRE(!per_g || w.P == 0 || w.radii, "csplat_visibility_views: per-Gaussian outputs need the view's radii");
+        VisView &f = t.v[i];
+        f.W = w.W; f.H = w.H; f.gx = gx; f.top_id = o.top_id;
+        VisRedView &g = r.v[i];
+        g.P = per_g ? w.P : 0;
+        g.weight_max = o.weight_max; g.weight_sum = o.weight_sum; g.pixel_count = o.pixel_count; g.radii = w.radii;
+        maxtiles = tiles > maxtiles ? tiles : maxtiles;      // (the walk also writes top_id = -1 of a view without list entries)
+        maxP = g.P > maxP ? g.P : maxP;
+        if (!lists) continue;
+        const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
+        size_t ioff[5], boff[B_NFIELDS];
+        image_offsets(w.W, w.H, ioff);
+        binning_offsets(Rl, tiles, boff);
+        const char *b = (const char *)w.binning, *im = (const char *)w.image;
+        f.ranges = (const int2 *)(im + ioff[0]); f.n_contrib = (const uint32_t *)(im + ioff[1]);
+        f.ids_sorted = (const uint32_t *)(b + boff[1]); f.seg_offset = (const int *)(b + boff[2]); f.ckpt = (const float4 *)(b + boff[4]);
+        f.recA = (const float4 *)(b + boff[6]); f.recB = (const float4 *)(b + boff[7]); f.bbits = (const unsigned long long *)(b + boff[9]);
+        f.tiles = tiles;
+        if (per_g) {
+            const size_t a = align256((size_t)Rl * 4 + 4);
+            f.rec_max = (float *)o.scratch; f.rec_sum = (float *)((char *)o.scratch + a); f.rec_cnt = (int32_t *)((char *)o.scratch + 2 * a);
+            make_cam(g.cam, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H);
+            const Geom gm = geom_view((void *)w.geom, w.P);
+            g.xy = gm.xy; g.depth = gm.depth; g.ranges = f.ranges; g.keys_sorted = (const uint64_t *)(b + boff[0]); g.ids_sorted = f.ids_sorted;
+            g.rec_max = f.rec_max; g.rec_sum = f.rec_sum; g.rec_cnt = f.rec_cnt; g.tiles = tiles;
+        }
+    }
+    if (maxtiles == 0) return 0;
+    ProfScope ps(PROF_VISIBILITY, join);
+    k_visibility_walk_views<<<dim3((unsigned)maxtiles, V), 256, 0, join>>>(t);
+    LAUNCH_CHECK();
+    if (maxP > 0) {
+        k_visibility_reduce_views<<<dim3((unsigned)cdiv(maxP, 16), V), 256, 0, join>>>(r);
+        LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 // csplat_forward_views WITHOUT any host read: both phases are launched with the caller's capacities (caps[0] list entries per view,

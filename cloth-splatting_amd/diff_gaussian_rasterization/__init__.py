@@ -20,6 +20,9 @@ without them the call is exactly the upstream one.
 `antialiasing=True` (upstream's option of that name; gsplat's rasterize_mode="antialiased") scales every opacity by the ratio of the
 footprint areas of the undilated and the 0.3 px^2-dilated 2-D covariance, o' = o sqrt(max(2.5e-5, det0 / det1)), and renders and
 differentiates with o' (include/csplat.h, CSPLAT_ANTIALIAS); it composes with everything above.  Without it the call is unchanged.
+`return_visibility=True` appends a `Visibility(weight_max, weight_sum, pixel_count, top_id)`: per Gaussian the peak and the summed blending
+weight T alpha and the number of pixels it blended into, per pixel the id of the Gaussian with the largest weight (include/csplat.h,
+csplat_visibility_views) -- forward only, bit-reproducible.  Without it the call is unchanged.
 """
 import contextlib as _contextlib
 import ctypes as C
@@ -135,6 +138,48 @@ _ANTIALIAS = _Antialias()
 CSPLAT_ANTIALIAS = 2      # csplat.h
 
 
+class Visibility(NamedTuple):
+    """what a view's `return_visibility=True` adds (non-differentiable).  With w_i(pix) = T_i alpha_i, the weight with which the colour
+    blended Gaussian i at pix: weight_max [P] float32 = max over pixels (0 where i blends nowhere), weight_sum [P] float32 = the sum,
+    pixel_count [P] int32 = the pixels where i blended, top_id [1, H, W] int32 = argmax_i w_i(pix), the front-most on a tie, -1 where
+    nothing blended.  `weight_max > thr` is an occlusion-aware replacement of `radii > 0`."""
+    weight_max: torch.Tensor
+    weight_sum: torch.Tensor
+    pixel_count: torch.Tensor
+    top_id: torch.Tensor
+
+
+class _VisSpec:
+    """the visibility request of a batched call, one bool per view; the argument of _RasterizeGaussiansBatch.apply behind the feature
+    arguments (in front of the _ANTIALIAS marker) when any view asks for it, absent otherwise"""
+
+    def __init__(self, per_view):
+        self.per_view = [bool(x) for x in per_view]
+
+
+NVIS = len(Visibility._fields)      # outputs a view's visibility adds to the Function's outputs
+
+
+def _check_visibility_flag(flag):
+    """-> the flag; TypeError unless it is a bool"""
+    if not isinstance(flag, bool):
+        raise TypeError(f"return_visibility must be a bool, got {type(flag).__name__}")
+    return flag
+
+
+def _visibility_mode_check():
+    """visibility is computed by eager steps only"""
+    if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        raise RuntimeError("diff_gaussian_rasterization: visibility is not computed by a forward launched on faith or a captured / "
+                           "replayed step -- compute it in an eager step")
+
+
+def _group_visibility(outs, per_view):
+    """a view's flat outputs -> the same tuple with its last NVIS tensors as one Visibility when the view asked for it"""
+    outs = tuple(outs)
+    return outs[:-NVIS] + (Visibility(*outs[-NVIS:]),) if per_view else outs
+
+
 def _feature_mode_check():
     """feature / alpha images are rendered by eager steps only"""
     if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
@@ -143,7 +188,7 @@ def _feature_mode_check():
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, features=None, return_alpha=False, antialiasing=False):
+                        raster_settings, features=None, return_alpha=False, antialiasing=False, return_visibility=False):
     """One camera (what GaussianRasterizer.forward calls, gaussian_renderer/__init__.py:156-164).  Since round 5 a single view goes
     through the same library entry as a batch of views (csplat_forward_views_deferred with V = 1): from the second call of an image size
     on, the second forward phase is launched on the previous call's capacities and the counts are read AFTER the host has prepared the
@@ -151,6 +196,18 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     camera.  Images, radii, depth and gradients are those of _RasterizeGaussians (tests: test_batched_views_equal_single_view_calls)."""
     cam = _cam_group(raster_settings)
     aa = (_ANTIALIAS,) if antialiasing else ()
+    if _check_visibility_flag(return_visibility):
+        # (visibility: the batched Function with one view -- csplat_visibility_views reads what csplat_forward_views_* leave)
+        extra = ()
+        if features is not None or return_alpha:
+            F = _check_features(features, means3D) if features is not None else 0
+            _feature_mode_check()
+            extra = (features, _FeatSpec([(F, return_alpha)]))
+        _visibility_mode_check()
+        _n.require_cuda(means3D)
+        res = _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                             cov3Ds_precomp, *cam, *extra, _VisSpec([True]), *aa)
+        return _group_visibility(res, True)
     if features is not None or return_alpha:
         # (the feature / alpha path: always the batched Function with one view -- csplat_forward_views_* render the extra images,
         #  csplat_backward_views takes their gradients)
@@ -488,6 +545,12 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         ctx.aa = bool(flat) and flat[-1] is _ANTIALIAS
         if ctx.aa:
             flat = flat[:-1]
+        # (then, when a view asks for visibility: the _VisSpec)
+        vspec = flat[-1] if flat and isinstance(flat[-1], _VisSpec) else None
+        if vspec is not None:
+            flat = flat[:-1]
+            _visibility_mode_check()
+        ctx.vspec = vspec.per_view if vspec is not None else None
         # (then, when a view asks for feature or alpha images: V feature tensors (None where a view has none) and the _FeatSpec)
         spec = flat[-1] if flat and isinstance(flat[-1], _FeatSpec) else None
         feats = list(flat[-1 - V:-1]) if spec is not None else [None] * V
@@ -585,8 +648,15 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
             outs += [v.radii, v.depth] if stacked else [v.color, v.radii, v.depth]
             outs += [t for t in (v.feat, v.alpha) if t is not None]
+            v.vis = None
+            if ctx.vspec is not None and ctx.vspec[i]:
+                v.vis = [torch.empty(v.P, dtype=torch.float32, device=dev), torch.empty(v.P, dtype=torch.float32, device=dev),
+                         torch.empty(v.P, dtype=torch.int32, device=dev), torch.empty(1, v.H, v.W, dtype=torch.int32, device=dev)]
+                outs += v.vis
             saved += list(v.saved()[:-1]) + ([] if stacked else [v.color])
             ctx.mark_non_differentiable(v.radii)
+        if ctx.vspec is not None:        # (mark_non_differentiable keeps its last call's tensors only: all of them in one call)
+            ctx.mark_non_differentiable(*[v.radii for v in views], *[t for v in views if v.vis is not None for t in v.vis])
         if stacked:
             outs = [colors] + outs
             saved.append(colors)
@@ -633,10 +703,33 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 for a, i in enumerate(ctx.plan["active"]):
                     ctx.plan["sub"][a].num_rendered = arr[i].num_rendered
                     ctx.plan["sub"][a].busy_tiles = arr[i].busy_tiles
+        if ctx.vspec is not None:
+            _RasterizeGaussiansBatch._visibility(views, arr, dev, main)
         if _KEEP_INFO and _FAITH is None and len({(v.W, v.H) for v in views}) == 1 and all(_n_IMAGE in c for c in chunks):
             off = int(_n.lib.csplat_image_info_offset(views[0].W, views[0].H))
             LAST_INFO[:] = [chunks[i][_n_IMAGE][off:off + 12].view(torch.int32) for i in range(V)]
         return tuple(outs)
+
+    @staticmethod
+    def _visibility(views, arr, dev, main):
+        """csplat_visibility_views on the views that asked for it (the forward is settled: counts and chunks are final); the scratch is
+        freed on the caller's stream, behind the launch"""
+        outs = (_n.CsplatVisibility * len(views))()
+        keep = []
+        for i, v in enumerate(views):
+            if v.vis is None:
+                continue
+            scratch = torch.empty(max(int(_n.lib.csplat_visibility_scratch_bytes(v.P, max(v.layout_rendered, v.num_rendered, 0), v.W, v.H)), 256),
+                                  dtype=torch.uint8, device=dev)
+            keep.append(scratch)
+            o = outs[i]
+            o.weight_max, o.weight_sum, o.pixel_count, o.top_id = (_n.ptr(t) for t in v.vis)
+            o.scratch = scratch.data_ptr()
+        with _n.on_device(dev):
+            rc = _n.lib.csplat_visibility_views(len(views), C.cast(arr, C.c_void_p), C.cast(outs, C.c_void_p), main.cuda_stream)
+        _n.check(rc, "csplat_visibility_views")
+        for v in views:
+            v.vis = None
 
     @staticmethod
     def _plan_backward(views, saved, k, arr, first_of, active, dev, inputs=None):
@@ -744,9 +837,11 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         tail = (None,) * (4 * V) if ctx.cam else ()
         fspec = ctx.fspec or [(0, False)] * V
         ftail = (None,) * (V + 1) if ctx.fspec is not None else ()      # the views' feature tensors and the _FeatSpec
-        if ctx.aa:
-            ftail = ftail + (None,)                                       # the _ANTIALIAS marker
-        per = [(2 if ctx.stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]     # outputs per view
+        vtail = (None,) if ctx.vspec is not None else ()                 # the _VisSpec
+        atail = (None,) if ctx.aa else ()                                # the _ANTIALIAS marker
+        ftail = ftail + vtail + atail
+        base = [(2 if ctx.stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]    # outputs per view before visibility
+        per = [b + (NVIS if ctx.vspec is not None and ctx.vspec[i] else 0) for i, b in enumerate(base)]
         first = [sum(per[:i]) + (1 if ctx.stacked else 0) for i in range(V)]                          # a view's first output
         if ctx.stacked:
             gcol = [None] * V if grads[0] is None else [grads[0][i] for i in range(V)]
@@ -754,8 +849,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         else:
             gcol = [grads[first[i]] for i in range(V)]
             gdep = [grads[first[i] + 2] for i in range(V)]
-        gfeat = [grads[first[i] + per[i] - (2 if fspec[i][1] else 1)] if fspec[i][0] else None for i in range(V)]
-        galpha = [grads[first[i] + per[i] - 1] if fspec[i][1] else None for i in range(V)]
+        gfeat = [grads[first[i] + base[i] - (2 if fspec[i][1] else 1)] if fspec[i][0] else None for i in range(V)]
+        galpha = [grads[first[i] + base[i] - 1] if fspec[i][1] else None for i in range(V)]
         if any(g is not None for g in gdep) and ctx.on_faith:
             raise RuntimeError("diff_gaussian_rasterization: a depth gradient reached a forward launched on faith (a captured / replayed step); "
                                "those steps take no depth loss -- render the depth term in an eager step")
@@ -817,7 +912,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                     buf = owner[key]
                 w.dL_dfeat_in = _n.ptr(buf)
                 gs += [gf, ga]
-            ftail_out = tuple(fout) + (None,) + ((None,) if ctx.aa else ())
+            ftail_out = tuple(fout) + (None,) + vtail + atail
         if want_feat or want_cam or any(gdep[i] is not None for i in active):
             # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout (the camera path: of the
             # camera layout; the feature path: of the feature layout), allocated here (never on the colour-only path) and cleared by the
@@ -859,8 +954,10 @@ def rasterize_views(settings, inputs, stacked=False):
     differentiable output -- the batch the reference assembles with torch.cat before its losses -- and colors[i] are
     plain slices of it.  A dict may also carry `features` ([P, F], the same F in every view) and `return_alpha`: that view's tuple
     then grows by feat [F,H,W] and / or alpha [1,H,W] (GaussianRasterizer.forward).  `antialiasing` (GaussianRasterizer.forward) must be
-    the same in every dict of a call (ValueError otherwise)."""
+    the same in every dict of a call (ValueError otherwise).  `return_visibility=True` in a dict appends that view's Visibility (last, a
+    NamedTuple; GaussianRasterizer.forward); the views of a call may differ in it."""
     flat, fspec, feats = [], [], []
+    vis = [_check_visibility_flag(kw.get("return_visibility", False)) for kw in inputs]
     aa = {bool(kw.get("antialiasing", False)) for kw in inputs}
     if len(aa) > 1:
         raise ValueError("rasterize_views: antialiasing must be the same in every view of a call, got "
@@ -885,15 +982,18 @@ def rasterize_views(settings, inputs, stacked=False):
             raise ValueError(f"rasterize_views: every view must have the same number of feature channels, got {[f for f, _a in fspec]}")
         _feature_mode_check()
         flat += feats + [_FeatSpec(fspec)]
+    if any(vis):
+        _visibility_mode_check()
+        flat.append(_VisSpec(vis))
     if True in aa:
         flat.append(_ANTIALIAS)
     res = _RasterizeGaussiansBatch.apply(tuple(settings), bool(stacked), *flat)
-    per = [(2 if stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]
+    per = [(2 if stacked else 3) + (1 if f else 0) + (1 if a else 0) + (NVIS if vv else 0) for (f, a), vv in zip(fspec, vis)]
     at = [sum(per[:i]) + (1 if stacked else 0) for i in range(len(settings))]
     if stacked:
         colors = res[0]
-        return colors, [(colors[i],) + tuple(res[at[i]:at[i] + per[i]]) for i in range(len(settings))]
-    return [tuple(res[at[i]:at[i] + per[i]]) for i in range(len(settings))]
+        return colors, [_group_visibility((colors[i],) + tuple(res[at[i]:at[i] + per[i]]), vis[i]) for i in range(len(settings))]
+    return [_group_visibility(res[at[i]:at[i] + per[i]], vis[i]) for i in range(len(settings))]
 
 
 _n_GEOM, _n_BINNING, _n_IMAGE = 0, 1, 2
@@ -912,7 +1012,7 @@ class GaussianRasterizer(nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, features=None, return_alpha=False, antialiasing=False):
+                cov3D_precomp=None, features=None, return_alpha=False, antialiasing=False, return_visibility=False):
         """-> (color [3,H,W], radii [P], depth [1,H,W]), then feat [F,H,W] when `features` ([P, F] float32, 1 <= F <= 6, on the device of
         means3D) is given -- feat[c] = sum_i T_i alpha_i features[i, c] over exactly the Gaussians the colour blends, no background term --
         then alpha [1,H,W] = 1 - T_final when `return_alpha` (color = sum T alpha c + (1 - alpha) bg).  Both are differentiable; neither
@@ -920,11 +1020,15 @@ class GaussianRasterizer(nn.Module):
         antialiasing=True: every opacity o becomes o' = o h, h = sqrt(max(2.5e-5, det0 / det1)) with det0 / det1 the determinants of
         the 2-D covariance before / after its 0.3 px^2 dilation -- a footprint below pixel size keeps the coverage of its true size.
         Images and gradients (opacities.grad = h dL/do', the covariance and camera terms through h) all use o'; it works eagerly, on
-        faith, in captured / replayed steps and under deferred_k8()."""
+        faith, in captured / replayed steps and under deferred_k8().
+        return_visibility=True: one more element at the very end, a Visibility(weight_max, weight_sum, pixel_count, top_id) of this view
+        (non-differentiable, bit-reproducible; not for a forward launched on faith or a captured step: RuntimeError).  It composes with
+        everything above."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, features, bool(return_alpha), bool(antialiasing))
+                                   self.raster_settings, features, bool(return_alpha), bool(antialiasing),
+                                   _check_visibility_flag(return_visibility))

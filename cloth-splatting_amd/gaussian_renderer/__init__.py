@@ -184,6 +184,17 @@ def render(viewpoint_camera, pc, simulator, pipe, bg_color: torch.Tensor, scalin
     return _package(viewpoint_camera, out, extras, project_vertices)
 
 
+def render_visibility(viewpoint_camera, pc, simulator, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, render_static=False):
+    """-> diff_gaussian_rasterization.Visibility of one camera: per Gaussian the peak / summed blending weight and the pixels it blended
+    into, per pixel the dominant Gaussian's id.  The settings and inputs are render()'s for the same arguments; the call runs under
+    no_grad.  `visibility.weight_max > thr` is an occlusion-aware `visibility_filter`: radii > 0 holds for a Gaussian hidden behind a
+    fold of the cloth too (the reference's flow loss and tracking take radii > 0, train.py:52-90, render.py:195-230)."""
+    with torch.no_grad():
+        settings, kwargs, _extras = _prepare(viewpoint_camera, pc, simulator, pipe, bg_color, scaling_modifier, None, None,
+                                             render_static)
+        return GaussianRasterizer(raster_settings=settings)(**kwargs, return_visibility=True)[-1]
+
+
 def render_views(viewpoint_cameras, pc, simulator, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
                  no_shadow=False, render_static=False, project_vertices=False, return_stacked=False, vertice_deforms=None,
                  by_products=True):

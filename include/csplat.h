@@ -14,6 +14,9 @@
  *       GaussianRasterizer.forward, gaussian_renderer/__init__.py:16,76,156-164 (backward runs from
  *       loss.backward(), scene_reconstruction/train_utils.py:288).  Sources of that extension are an empty
  *       submodule (.gitmodules:7-9); the argument list mirrors its published rasterize_points.h.
+ *   csplat_visibility_views
+ *       no counterpart there: which Gaussians a view really sees (peak / summed blending weight, pixel count) and which one dominates
+ *       each pixel, for an occlusion-aware `visibility_filter` (the reference uses radii > 0, train_utils.py:270-300, train.py:52-90).
  *   csplat_dist2
  *       `simple_knn._C.distCUDA2`, scene_reconstruction/gaussian_mesh.py:26,250; gaussian_model.py:20,134.
  *   csplat_gnn_*
@@ -263,6 +266,30 @@ int csplat_backward_slice_rows(int P, int slice, int nslices, int64_t *row_lo, i
 int csplat_forward_views_faith(int V, csplat_view *views, csplat_alloc_fn alloc, void *join_stream, const uint32_t *caps, uint32_t *valid);
 size_t csplat_image_info_offset(int W, int H);
 
+/* Gaussian visibility and the top-contributor map (forward only, no gradient; ABI 9, csplat_view unchanged).  With w_i(pix) = T_i alpha_i,
+ * exactly the weight with which the colour image blended Gaussian i at pix (the same alpha, 0.99 cap, 1/255 skip, stop rule and n_contrib;
+ * o' under CSPLAT_ANTIALIAS):
+ *   weight_max[i]  = max_pix w_i(pix)       (0 where i blends nowhere)         [P] float
+ *   weight_sum[i]  = sum_pix w_i(pix)                                           [P] float
+ *   pixel_count[i] = number of pixels where i blended                           [P] int32
+ *   top_id[pix]    = argmax_i w_i(pix), the front-most on a tie, -1 where nothing blended   [H][W] int32
+ * Each pointer NULL = not wanted; every wanted output is fully written (zeros for radii == 0, -1 for a view without list entries).  No float
+ * atomics: the per-entry records are joined in a fixed order (16 lanes of a block, then the 16 blocks of a tile), the per-Gaussian sums in
+ * tile order, so every output is bit-reproducible in the default mode.  scratch: csplat_visibility_scratch_bytes(P, layout_rendered, W, H)
+ * bytes per view when any per-Gaussian output is wanted (NULL is fine for top_id alone), no initial state.
+ * csplat_visibility_views runs on the join stream, behind views that a finished csplat_forward_views (or _deferred + _settle) filled in,
+ * and reads their geom, binning and image chunks.  Errors: V outside 1..8, a pending view (num_rendered < 0), a view launched on faith
+ * (valid != NULL), a missing chunk or scratch. */
+typedef struct csplat_visibility {
+    float *weight_max;     /* [P]     NULL = not wanted */
+    float *weight_sum;     /* [P]     NULL = not wanted */
+    int32_t *pixel_count;  /* [P]     NULL = not wanted */
+    int32_t *top_id;       /* [H][W]  NULL = not wanted */
+    void *scratch;         /* csplat_visibility_scratch_bytes(P, R, W, H) bytes, or NULL when only top_id is wanted */
+} csplat_visibility;
+size_t csplat_visibility_scratch_bytes(int P, int64_t R, int W, int H);
+int csplat_visibility_views(int V, const csplat_view *views, const csplat_visibility *outs, void *join_stream);
+
 /* Backward: K7 compositing backward, K8 per-Gaussian backward.
  * out_color is the forward's colour image; dL_dpix[3][H][W] its gradient.  The depth image's gradient is taken by
  * csplat_backward_depth below.
@@ -495,7 +522,7 @@ int csplat_mesh_transform_bwd_views(void *stream, int T, int P, int V, const int
  *   10 depth partials prepass | 11 K7 of the depth path | 12 K8 of the depth path (csplat_backward_depth, dL_ddepth)
  *   13 K8 of the camera path | 14 the camera path's background partials and fixed-order sums (csplat_view.dL_dview .. dL_dbg)
  *   15 the feature / alpha forward pass | 16 feature partials prepass | 17 K7 of the feature path | 18 feature gradient extraction
- *   (csplat_view.features .. dL_dfeat_in)
+ *   (csplat_view.features .. dL_dfeat_in) | 19 the visibility walk and per-Gaussian reduce (csplat_visibility_views)
  * csplat_prof_read synchronises the recorded events of class k, returns their summed duration (ms) and the
  * number of brackets, and recycles the events. */
 int csplat_prof_enable(unsigned mask);
