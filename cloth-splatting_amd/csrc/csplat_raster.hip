@@ -2492,8 +2492,10 @@ struct FeatView {
     float *wpart;             // [slots][256]
     float *dL_dfeat_in;       // [P][nf] (written, or added when an earlier view of the call has the same buffer), NULL: not wanted
     int nf, P;
-    unsigned accmask;
+    unsigned accmask;         // the view's CSPLAT_ACC_* / CSPLAT_SCRATCH_ZEROED bits, plus FEAT_ADD_IN
 };
+// not an ABI bit: an earlier group of views of the same call (backward_views_impl) already wrote dL_dfeat_in -- add to it
+constexpr unsigned FEAT_ADD_IN = 1u << 31;
 struct FeatTable { FeatView v[B2_MAX_VIEWS]; int n; };
 __global__ __launch_bounds__(256) void k_feature_bwd_partials(FeatTable tab) {
     const FeatView &fv = tab.v[blockIdx.y];
@@ -2554,7 +2556,7 @@ __global__ __launch_bounds__(256) void k_feature_grads(FeatTable tab) {
         float *acc = fv.d.b.acc + (size_t)i * ACC_STRIDE;
         const bool vis = fv.radii[i] > 0;
         if (fv.dL_dfeat_in) {
-            bool add = false;
+            bool add = (fv.accmask & FEAT_ADD_IN) != 0u;      // (a view of an earlier group of the call wrote the buffer)
             for (int vj = 0; vj < vi; vj++) add = add || tab.v[vj].dL_dfeat_in == fv.dL_dfeat_in;
             float *out = fv.dL_dfeat_in + (size_t)i * fv.nf;
             for (int c = 0; c < fv.nf; c++) {
@@ -3215,7 +3217,7 @@ __global__ __launch_bounds__(256) void k_bg_partials(BgTable tab) {
     const int64_t n = w.npix, lo = n * blockIdx.x / BG_BLOCKS, hi = n * (blockIdx.x + 1) / BG_BLOCKS;
     float a[3] = {0.f, 0.f, 0.f};
     for (int64_t q = lo + threadIdx.x; q < hi; q += 256) {
-        const float T = w.final_T[q];
+        const float T = w.final_T ? w.final_T[q] : 1.f;      // (no image chunk: a view without Gaussians is all background)
         a[0] += w.dL_dpix[q] * T; a[1] += w.dL_dpix[n + q] * T; a[2] += w.dL_dpix[2 * n + q] * T;
     }
     __shared__ float s[3][256];
@@ -4314,19 +4316,29 @@ static int forward_views_impl(int V, csplat_view *v, csplat_alloc_fn alloc, void
 }
 
 // ABI 9: the feature / alpha images of a finished forward (csplat_view.out_features / out_alpha), on the join stream behind every view's
-// K6.  Nothing is launched when no view asks for them.
+// K6.  Nothing is launched when no view asks for them.  One launch per group of views (view_group): a call of up to 8 views is one launch.
 static bool feat_out_wanted(const csplat_view &w) { return w.out_features || w.out_alpha; }
-static int feature_forward(int V, csplat_view *v, hipStream_t join) {
+// The per-view tables of the extended paths hold B2_MAX_VIEWS views: a call of more views runs in ceil(V / 8) groups of as equal a size as
+// possible, one after the other on the join stream, in view order.  Group g is views [lo, hi); a call of up to 8 views is one group.
+static int view_groups(int V) { return V > B2_MAX_VIEWS ? cdiv(V, B2_MAX_VIEWS) : 1; }
+static void view_group(int V, int g, int *lo, int *hi) {
+    const int ng = view_groups(V);
+    *lo = (int)((int64_t)V * g / ng);
+    *hi = (int)((int64_t)V * (g + 1) / ng);
+}
+static int feature_forward_group(int V, csplat_view *v, hipStream_t join) {
     bool any = false;
     for (int i = 0; i < V; i++) any = any || feat_out_wanted(v[i]);
     if (!any) return 0;
-    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_forward_views: feature / alpha images are rendered for at most 8 views per call");
+    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_forward_views: feature / alpha images are rendered for at most 8 views per launch");
     FeatFwdTable t;
     memset(&t, 0, sizeof(t));
     int maxtiles = 0;
     for (int i = 0; i < V; i++) {
         const csplat_view &w = v[i];
-        CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES && (w.n_features == 0) == (w.features == nullptr),
+        // (a view without Gaussians may leave features NULL whatever its n_features: an empty [0][F] array has no storage)
+        CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES &&
+                       ((w.n_features == 0) == (w.features == nullptr) || (w.P <= 0 && w.features == nullptr)),
                        "csplat_forward_views: n_features must be 0..6, with features set exactly when it is not 0");
         CSPLAT_REQUIRE(!w.out_features || w.n_features > 0, "csplat_forward_views: out_features without features");
         FeatFwdView &f = t.v[i];
@@ -4353,6 +4365,14 @@ static int feature_forward(int V, csplat_view *v, hipStream_t join) {
     LAUNCH_CHECK();
     return 0;
 }
+static int feature_forward(int V, csplat_view *v, hipStream_t join) {
+    for (int g = 0, ng = view_groups(V); g < ng; g++) {
+        int lo, hi;
+        view_group(V, g, &lo, &hi);
+        if (int rc = feature_forward_group(hi - lo, v + lo, join)) return rc;
+    }
+    return 0;
+}
 
 int csplat_forward_views(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream) {
     const int rc = forward_views_impl(V, v, alloc, join_stream, nullptr);
@@ -4366,9 +4386,7 @@ size_t csplat_visibility_scratch_bytes(int P, int64_t R, int W, int H) {
     const size_t n = R > 0 ? (size_t)R : 0;
     return 3 * align256(n * 4 + 4);
 }
-int csplat_visibility_views(int V, const csplat_view *v, const csplat_visibility *outs, void *join_stream) {
-    CSPLAT_REQUIRE(V >= 1 && V <= B2_MAX_VIEWS && v != nullptr && outs != nullptr, "csplat_visibility_views: 1 to 8 views and their outputs");
-    hipStream_t join = (hipStream_t)join_stream;
+static int visibility_views_group(int V, const csplat_view *v, const csplat_visibility *outs, hipStream_t join) {
     VisTable t;
     VisRedTable r;
     memset(&t, 0, sizeof(t));
@@ -4420,6 +4438,15 @@ int csplat_visibility_views(int V, const csplat_view *v, const csplat_visibility
     if (maxP > 0) {
         k_visibility_reduce_views<<<dim3((unsigned)cdiv(maxP, 16), V), 256, 0, join>>>(r);
         LAUNCH_CHECK();
+    }
+    return 0;
+}
+int csplat_visibility_views(int V, const csplat_view *v, const csplat_visibility *outs, void *join_stream) {
+    CSPLAT_REQUIRE(V >= 1 && V <= MAX_TICKETS && v != nullptr && outs != nullptr, "csplat_visibility_views: 1 to 64 views and their outputs");
+    for (int g = 0, ng = view_groups(V); g < ng; g++) {      // (a group of at most 8 views per walk / reduce pair)
+        int lo, hi;
+        view_group(V, g, &lo, &hi);
+        if (int rc = visibility_views_group(hi - lo, v + lo, outs + lo, (hipStream_t)join_stream)) return rc;
     }
     return 0;
 }
@@ -4605,10 +4632,10 @@ static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *ro
         const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
         BgView &b = bt.v[i];
         b.slab = nullptr; b.final_T = nullptr; b.dL_dpix = w.dL_dpix; b.npix = w.W * w.H;
-        if (w.dL_dbg && w.image && w.dL_dpix && w.scratch) {
+        if (w.dL_dbg && w.dL_dpix && w.scratch) {
             size_t ioff[5];
             image_offsets(w.W, w.H, ioff);
-            b.final_T = (const float *)((const char *)w.image + ioff[2]);
+            b.final_T = w.image ? (const float *)((const char *)w.image + ioff[2]) : nullptr;
             b.slab = (float *)((char *)w.scratch + cam_bg_offset(w.P, Rl, w.W, w.H));
             any_bg = true;
         }
@@ -4628,9 +4655,10 @@ static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *ro
 }
 
 static bool feat_wanted(const csplat_view &w) { return w.dL_dfeatures || w.dL_dalpha; }
+// earlier[0 .. n_earlier): the views of the call's earlier groups (backward_views_impl), whose dL_dfeat_in this group adds to
 static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices, bool cam = false,
-                                bool cam_k8 = false, bool feat = false) {
-    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth, feature or alpha gradient is taken for at most 8 views per call");
+                                bool cam_k8 = false, bool feat = false, const csplat_view *earlier = nullptr, int n_earlier = 0) {
+    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth, feature or alpha gradient is taken for at most 8 views per group");
     CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth, feature or alpha gradient");
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     CSPLAT_REQUIRE(!feat || whole, "csplat_backward_views_parts: feature / alpha gradients are taken by the whole call only");
@@ -4651,7 +4679,8 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
         int Pmax = 0;
         for (int i = 0; i < V; i++) {
             const csplat_view &w = v[i];
-            CSPLAT_REQUIRE(w.geom && w.binning && w.image && w.out_color && w.scratch && w.dL_dpix && w.radii,
+            // (a view without Gaussians has no chunks nor radii: its tables keep tiles = 0 and nothing reads them)
+            CSPLAT_REQUIRE(w.P <= 0 || (w.geom && w.binning && w.image && w.out_color && w.scratch && w.dL_dpix && w.radii),
                            "csplat_backward_views: missing saved state, scratch or dL_dpix");
             DepthView &d = dtab.v[i];
             const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
@@ -4674,7 +4703,8 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             d.W = w.W; d.H = w.H; d.gx = gx;
             d.tiles = (w.P > 0 && w.num_rendered > 0) ? tiles : 0;
             if (feat) {
-                CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES && (w.n_features == 0) == (w.features == nullptr),
+                CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES &&
+                               ((w.n_features == 0) == (w.features == nullptr) || (w.P <= 0 && w.features == nullptr)),
                                "csplat_backward_views: n_features must be 0..6, with features set exactly when it is not 0");
                 CSPLAT_REQUIRE(!w.dL_dfeatures || w.n_features > 0, "csplat_backward_views: dL_dfeatures without features");
                 FeatView &f = ftab.v[i];
@@ -4682,6 +4712,8 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
                 f.radii = w.radii; f.features = w.features; f.nf = w.n_features; f.dL_dfeat = w.dL_dfeatures; f.dL_dalpha = w.dL_dalpha;
                 f.wpart = (float *)((char *)w.scratch + feat_wpart_offset(w.P, Rl, w.W, w.H));
                 f.dL_dfeat_in = w.n_features > 0 ? w.dL_dfeat_in : nullptr; f.P = w.P; f.accmask = w.accmask;
+                for (int j = 0; j < n_earlier && f.dL_dfeat_in; j++)
+                    if (earlier[j].n_features > 0 && earlier[j].dL_dfeat_in == f.dL_dfeat_in) f.accmask |= FEAT_ADD_IN;
                 any_fgrad = any_fgrad || w.dL_dfeatures;
             }
             if (w.P <= 0) continue;
@@ -4807,6 +4839,11 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
     return cam ? cam_tail(V, v, join, cam_rows) : 0;
 }
 
+static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices, bool cam, bool cam_k8);
+// The path (default, depth, feature; camera or not) is the call's.  A call of more than 8 views that takes the depth, feature or camera
+// path runs in groups of at most 8 views (view_group), one after the other on the join stream, each as a call of its own views would run:
+// every group writes or adds into the call's gradient buffers as the views' accmask says (an accumulating view of a later group adds to
+// what an earlier group wrote), dL_dfeat_in included.  A call of up to 8 views is one group: its launches are those of the ungrouped call.
 static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
     CSPLAT_REQUIRE(V >= 0 && (V == 0 || v != nullptr), "csplat_backward_views: bad view count");
     CSPLAT_REQUIRE(parts >= 1 && parts <= 3 && nslices >= 1 && slice >= 0 && slice < nslices, "csplat_backward_views_parts: bad parts / slice");
@@ -4816,7 +4853,6 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
         cam = cam || cam_k8_wanted(v[i]) || v[i].dL_dbg != nullptr;
     }
     if (cam) {
-        CSPLAT_REQUIRE(V <= K8_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per call");
         CSPLAT_REQUIRE(parts == 3u && nslices == 1, "csplat_backward_views_parts: camera / background gradients are taken by the whole call only");
         CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no camera / background gradient");
         for (int i = 0; i < V; i++)
@@ -4824,16 +4860,30 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
     }
     for (int i = 0; i < V; i++)
         CSPLAT_REQUIRE(!aa_of(v[i]) || v[i].opacities || v[i].P <= 0, "csplat_backward_views: CSPLAT_ANTIALIAS needs the view's opacities");
-    bool feat = false;
-    for (int i = 0; i < V; i++) feat = feat || feat_wanted(v[i]);
+    bool feat = false, depth = false;
+    for (int i = 0; i < V; i++) {
+        feat = feat || feat_wanted(v[i]);
+        depth = depth || v[i].dL_ddepth != nullptr;
+    }
     if (feat) {
         CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no feature or alpha gradient");
         for (int i = 0; i < V; i++)
             CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: feature / alpha gradients need scratch of csplat_backward_feature_scratch_bytes");
-        return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8, true);
     }
-    for (int i = 0; i < V; i++)
-        if (v[i].dL_ddepth) return backward_views_depth(V, v, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8);
+    if (!feat && !depth && !cam) return backward_views_colour(V, v, join_stream, parts, slice, nslices, false, false);
+    for (int g = 0, ng = view_groups(V); g < ng; g++) {
+        int lo, hi;
+        view_group(V, g, &lo, &hi);
+        const int rc = (feat || depth) ? backward_views_depth(hi - lo, v + lo, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8, feat,
+                                                              v, lo)
+                                       : backward_views_colour(hi - lo, v + lo, join_stream, parts, slice, nslices, cam, cam_k8);
+        if (rc) return rc;
+    }
+    return 0;
+}
+// the colour path (no view has a depth, feature or alpha gradient); cam / cam_k8: the call takes camera / background gradients
+static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices, bool cam, bool cam_k8) {
+    CSPLAT_REQUIRE(!cam || V <= K8_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per group");
     int cam_rows[K8_MAX_VIEWS] = {0};
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     hipStream_t join = (hipStream_t)join_stream;

@@ -955,7 +955,9 @@ def rasterize_views(settings, inputs, stacked=False):
     plain slices of it.  A dict may also carry `features` ([P, F], the same F in every view) and `return_alpha`: that view's tuple
     then grows by feat [F,H,W] and / or alpha [1,H,W] (GaussianRasterizer.forward).  `antialiasing` (GaussianRasterizer.forward) must be
     the same in every dict of a call (ValueError otherwise).  `return_visibility=True` in a dict appends that view's Visibility (last, a
-    NamedTuple; GaussianRasterizer.forward); the views of a call may differ in it."""
+    NamedTuple; GaussianRasterizer.forward); the views of a call may differ in it.  Every output and gradient -- features, alpha,
+    visibility, the depth, camera and background gradients, antialiasing -- is taken for up to 64 views per call; the library runs a
+    call of more than 8 views in groups of at most 8 (include/csplat.h, "More than 8 views"), adding every group into the same gradients."""
     flat, fspec, feats = [], [], []
     vis = [_check_visibility_flag(kw.get("return_visibility", False)) for kw in inputs]
     aa = {bool(kw.get("antialiasing", False)) for kw in inputs}

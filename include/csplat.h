@@ -200,8 +200,8 @@ typedef struct csplat_view {
                                      * the backward of views[0..V) does nothing when it is 0 */
     const float *dL_ddepth;         /* ABI 7, backward input: the gradient of out_depth [1][H][W], NULL = none.  When any view of a
                                      * backward call has one, the call takes the depth path (extra launches, see csplat_backward_depth;
-                                     * every view's scratch sized by csplat_backward_depth_scratch_bytes; not for views launched on faith,
-                                     * at most 8 views); when none has, the call is exactly the ABI 6 one */
+                                     * every view's scratch sized by csplat_backward_depth_scratch_bytes; not for views launched on faith;
+                                     * more than 8 views: see "More than 8 views" below); when none has, the call is exactly the ABI 6 one */
     /* ABI 8, backward outputs (device, each NULL = not wanted): the gradients of the camera tensors of the view, WRITTEN (never added).
      * Notation: V = view, Pm = proj (row-vector form, flat index 4 row + col), ph = [m, 1] for a mean m; pv = ph V, hom = ph Pm,
      * ndc = hom[:2] / (hom[3] + 1e-7), Rw = V[:3,:3]^T, cov2D = J(pv) Rw Sigma Rw^T J(pv)^T, the SH direction (m - campos) / |m - campos|,
@@ -216,20 +216,26 @@ typedef struct csplat_view {
      * The sums over Gaussians run in a fixed order (a slab row per K8 workgroup and view, then a fixed-order sum; no float atomics), so
      * they are bit-reproducible whenever their per-Gaussian inputs are (csplat_debug_flags bit 256).  Every view's scratch is sized by
      * csplat_backward_camera_scratch_bytes.  Not for views launched on faith, nor csplat_backward_views_parts with parts != 3 or
-     * nslices != 1; at most 8 views.  All NULL: the call is exactly the ABI 7 one. */
+     * nslices != 1; more than 8 views: see "More than 8 views" below.  All NULL: the call is exactly the ABI 7 one. */
     float *dL_dview, *dL_dproj, *dL_dcampos, *dL_dbg;
     /* ABI 9, feature channels and the alpha image.  features [P][n_features] (device, 1 <= n_features <= CSPLAT_MAX_FEATURES; NULL and 0
-     * = none) are composited with the colour's weights over exactly the entries the colour blends (same alpha, 0.99 cap, 1/255 skip,
+     * = none; a view with P = 0 may leave it NULL whatever n_features) are composited with the colour's weights over exactly the entries the colour blends (same alpha, 0.99 cap, 1/255 skip,
      * stop rule, n_contrib), without a background term:  out_features[c][pix] = sum_i T_i alpha_i f[i][c]  ([n_features][H][W]);
      * out_alpha[pix] = 1 - T_final(pix)  ([1][H][W]; T_final = the factor of the colour's background term).  Both are written by
      * csplat_forward_views, csplat_forward_views_deferred (when not pending) and csplat_forward_views_settle, in one launch behind the
      * views' K6 on the join stream; each NULL = not wanted (not for csplat_forward_views_faith).
      * Backward inputs dL_dfeatures [n_features][H][W] and dL_dalpha [1][H][W] (NULL = none): when any view of a csplat_backward_views
-     * call has one, the call takes the feature path (every view's scratch sized by csplat_backward_feature_scratch_bytes; at most 8
-     * views; not for views launched on faith nor csplat_backward_views_parts with parts != 3 or nslices != 1), which composes with the
-     * depth and camera paths; dL/dalpha_i gains sum_c g_c (T_i f_ic - F_behind_c / (1 - alpha_i)) + g_A T_final / (1 - alpha_i).
+     * call has one, the call takes the feature path (every view's scratch sized by csplat_backward_feature_scratch_bytes; more than 8
+     * views: see below; not for views launched on faith nor csplat_backward_views_parts with parts != 3 or nslices != 1), which composes
+     * with the depth and camera paths; dL/dalpha_i gains sum_c g_c (T_i f_ic - F_behind_c / (1 - alpha_i)) + g_A T_final / (1 - alpha_i).
      * dL_dfeat_in [P][n_features] (output, NULL = not wanted): sum over pixels of T_i alpha_i dL_dfeatures[c][pix], WRITTEN, or added when
      * an earlier view of the same call has the same buffer.  All NULL / 0: every call is exactly the ABI 8 one. */
+    /* More than 8 views: the feature / alpha images, csplat_visibility_views and the depth, feature, alpha, camera and background
+     * gradients take any number of views a call takes (csplat_forward_views: up to 64).  A call of more than 8 views runs them in
+     * ceil(V / 8) groups of as equal a size as possible (9 views: 5 + 4), one group after the other on the join stream, each with the
+     * launches of a call of its own views; accumulation (accmask, a shared dL_dfeat_in) spans the groups: a view adds to what a view of
+     * an earlier group wrote, in view order, and the bit-reproducible mode stays bit-reproducible.  A call of up to 8 views is one group:
+     * its launches are those it always made. */
     const float *features;
     int n_features;
     float *out_features, *out_alpha;
@@ -278,8 +284,8 @@ size_t csplat_image_info_offset(int W, int H);
  * tile order, so every output is bit-reproducible in the default mode.  scratch: csplat_visibility_scratch_bytes(P, layout_rendered, W, H)
  * bytes per view when any per-Gaussian output is wanted (NULL is fine for top_id alone), no initial state.
  * csplat_visibility_views runs on the join stream, behind views that a finished csplat_forward_views (or _deferred + _settle) filled in,
- * and reads their geom, binning and image chunks.  Errors: V outside 1..8, a pending view (num_rendered < 0), a view launched on faith
- * (valid != NULL), a missing chunk or scratch. */
+ * and reads their geom, binning and image chunks.  Errors: V outside 1..64, a pending view (num_rendered < 0), a view launched on faith
+ * (valid != NULL), a missing chunk or scratch.  More than 8 views: see "More than 8 views" at csplat_view. */
 typedef struct csplat_visibility {
     float *weight_max;     /* [P]     NULL = not wanted */
     float *weight_sum;     /* [P]     NULL = not wanted */

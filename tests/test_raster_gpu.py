@@ -6,6 +6,7 @@ import pytest
 
 import util
 from util import image_err, make_case, oracle_forward, rel_err
+from util import wild_case as _wild_case
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -479,31 +480,6 @@ def test_two_phase_forward_tickets_and_errors():
     rc, tk = begin()
     assert rc == 0 and finish(tk)[0] == 0                                      # and usable again
     torch.cuda.synchronize()
-
-
-def _wild_case(seed):
-    """random cloud far from scene_1's statistics: Gaussians in front of, beside and BEHIND the camera and across the near
-    plane, footprints from sub-pixel to half the image, 100:1 anisotropy, opacities below the 1/255 threshold and at 0.99+,
-    ragged image sizes."""
-    from csplat import synthetic as syn
-    rng = np.random.default_rng(seed)
-    P = int(rng.integers(40, 2500))
-    W, H = int(rng.integers(17, 180)), int(rng.integers(17, 150))
-    cam = syn.make_camera(float(rng.uniform(-180, 180)), W, H, phi_deg=float(rng.uniform(-80, 10)),
-                          radius=float(rng.uniform(0.3, 5.0)), fovx=float(rng.uniform(0.3, 1.6)))
-    means = rng.uniform(-1.5, 1.5, (P, 3)) * rng.choice([0.3, 1.0, 3.0])
-    # 80 %: base size over 2.5 decades, anisotropy up to 10:1; 20 %: needles / flakes, any axis anywhere in 2e-3 .. 0.6 (300:1)
-    scales = np.exp(rng.uniform(np.log(2e-3), np.log(0.5), (P, 1))) * np.exp(rng.uniform(np.log(0.1), 0.0, (P, 3)))
-    needle = rng.random(P) < 0.2
-    scales[needle] = np.exp(rng.uniform(np.log(2e-3), np.log(0.6), (int(needle.sum()), 3)))
-    quats = rng.normal(size=(P, 4)); quats /= np.linalg.norm(quats, axis=1, keepdims=True)
-    opac = 1.0 / (1.0 + np.exp(-rng.normal(0, 3.0, (P, 1))))
-    opac[rng.random(P) < 0.05] = 0.002            # below 1/255: never contributes
-    opac[rng.random(P) < 0.05] = 0.9995
-    shs = np.concatenate([rng.normal(0, 1.0, (P, 1, 3)), rng.normal(0, 0.3, (P, 15, 3))], 1)
-    g = dict(means3D=means.astype(np.float32), scales=scales.astype(np.float32), rotations=quats.astype(np.float32),
-             opacities=opac.astype(np.float32), shs=shs.astype(np.float32))
-    return dict(g=g, cam=cam, W=W, H=H, P=P, bg=rng.random(3).astype(np.float32), sh_degree=int(rng.integers(0, 4)))
 
 
 def _fuzz_seeds():

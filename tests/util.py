@@ -207,3 +207,39 @@ def oracle_render_views(cams, pc, sim, pipe, bg, render_static=False, return_sta
         color, radii = F.apply(xyz, m2d, pc.get_opacity, pc.get_features, pc.get_scaling, rots, cam, bg_np, pc.active_sh_degree)
         res.append(SimpleNamespace(render=color, radii=radii, visibility_filter=radii > 0, viewspace_points=m2d, vertice_deform=verts))
     return (res, None) if return_stacked else res
+
+
+def wild_case(seed, needles=True):
+    """random cloud far from scene_1's statistics: Gaussians in front of, beside and BEHIND the camera and across the near
+    plane, footprints from sub-pixel to half the image, 100:1 anisotropy, opacities below the 1/255 threshold and at 0.99+,
+    ragged image sizes.  needles=False: the same draws (the same scene but for its shapes), without the 20 % needle / flake
+    draw and with every Gaussian's anisotropy capped at 30:1 -- the geometry fp32 arithmetic can hold to 1e-4 of fp64."""
+    from csplat import synthetic as syn
+    rng = np.random.default_rng(seed)
+    P = int(rng.integers(40, 2500))
+    W, H = int(rng.integers(17, 180)), int(rng.integers(17, 150))
+    cam = syn.make_camera(float(rng.uniform(-180, 180)), W, H, phi_deg=float(rng.uniform(-80, 10)),
+                          radius=float(rng.uniform(0.3, 5.0)), fovx=float(rng.uniform(0.3, 1.6)))
+    means = rng.uniform(-1.5, 1.5, (P, 3)) * rng.choice([0.3, 1.0, 3.0])
+    # 80 %: base size over 2.5 decades, anisotropy up to 10:1; 20 %: needles / flakes, any axis anywhere in 2e-3 .. 0.6 (300:1)
+    scales = np.exp(rng.uniform(np.log(2e-3), np.log(0.5), (P, 1))) * np.exp(rng.uniform(np.log(0.1), 0.0, (P, 3)))
+    needle = rng.random(P) < 0.2
+    needle_scales = np.exp(rng.uniform(np.log(2e-3), np.log(0.6), (int(needle.sum()), 3)))
+    if needles:
+        scales[needle] = needle_scales
+    else:
+        scales = np.maximum(scales, scales.max(1, keepdims=True) / 30.0)
+    quats = rng.normal(size=(P, 4)); quats /= np.linalg.norm(quats, axis=1, keepdims=True)
+    opac = 1.0 / (1.0 + np.exp(-rng.normal(0, 3.0, (P, 1))))
+    opac[rng.random(P) < 0.05] = 0.002            # below 1/255: never contributes
+    opac[rng.random(P) < 0.05] = 0.9995
+    shs = np.concatenate([rng.normal(0, 1.0, (P, 1, 3)), rng.normal(0, 0.3, (P, 15, 3))], 1)
+    g = dict(means3D=means.astype(np.float32), scales=scales.astype(np.float32), rotations=quats.astype(np.float32),
+             opacities=opac.astype(np.float32), shs=shs.astype(np.float32))
+    return dict(g=g, cam=cam, W=W, H=H, P=P, bg=rng.random(3).astype(np.float32), sh_degree=int(rng.integers(0, 4)))
+
+
+def fuzz_seeds(var, default):
+    """an env-selectable seed range "lo:hi" (wider sweeps: CSPLAT_FUZZ_SEEDS=200:400 ...)"""
+    lo, hi = (int(v) for v in os.environ.get(var, default).split(":"))
+    return list(range(lo, hi))
