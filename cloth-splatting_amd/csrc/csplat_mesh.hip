@@ -42,6 +42,19 @@ __device__ __forceinline__ void plane_basis(const T p0[3], const T p1[3], T u[3]
     n[2] = u[0] * v[1] - u[1] * v[0];
 }
 
+// a triangle's corners relative to its centroid, formed from the edges out of corner 0: for nearby corners y1 - y0 and y2 - y0 are exact,
+// so a small face far from the origin keeps the digits that y_k - mean(y) loses to the rounding of the mean (a first-order error of the
+// plane basis below; faces of 1e-2 at a distance of 1 turned it into quaternion errors of 2e-5)
+template <typename T>
+__device__ __forceinline__ void centre_face(const T y[3][3], T yh[3][3]) {
+    for (int c = 0; c < 3; c++) {
+        const T e1 = y[1][c] - y[0][c], e2 = y[2][c] - y[0][c];
+        yh[0][c] = (e1 + e2) * (-1.f / 3.f);
+        yh[1][c] = yh[0][c] + e1;
+        yh[2][c] = yh[0][c] + e2;
+    }
+}
+
 // y[3][3] deformed face vertices, bary[3], q0[4] raw rotation parameter -> pos[3], quat[4]
 template <typename T>
 __device__ __forceinline__ void transform_one(const T y[3][3], const T bary[3], const T q0[4], const RestFace &rf, T pos[3],
@@ -51,10 +64,7 @@ __device__ __forceinline__ void transform_one(const T y[3][3], const T bary[3], 
     for (int c = 0; c < 3; c++) pos[c] = (bary[0] * y[0][c] + bary[1] * y[1][c] + bary[2] * y[2][c]) / bs;
     // ---- closed-form Kabsch of the rest triangle onto the deformed one
     T yh[3][3];
-    for (int c = 0; c < 3; c++) {
-        const T m = (y[0][c] + y[1][c] + y[2][c]) * (1.f / 3.f);
-        for (int k = 0; k < 3; k++) yh[k][c] = y[k][c] - m;
-    }
+    centre_face(y, yh);
     T uy[3], vy[3], ny[3];
     plane_basis(yh[0], yh[1], uy, vy, ny);
     T a = lift<T>(0.f), b = lift<T>(0.f), c_ = lift<T>(0.f), d = lift<T>(0.f);
@@ -119,10 +129,7 @@ __global__ __launch_bounds__(256) void k_rest_faces(int P, const int64_t *__rest
     float x[3][3], xh[3][3];
     for (int k = 0; k < 3; k++)
         for (int c = 0; c < 3; c++) x[k][c] = rest[3 * vid[3 * (size_t)i + k] + c];
-    for (int c = 0; c < 3; c++) {
-        const float m = (x[0][c] + x[1][c] + x[2][c]) * (1.f / 3.f);
-        for (int k = 0; k < 3; k++) xh[k][c] = x[k][c] - m;
-    }
+    centre_face(x, xh);
     RestFace rf;
     plane_basis(xh[0], xh[1], rf.ux, rf.vx, rf.nx);
     for (int k = 0; k < 3; k++) {
@@ -163,10 +170,7 @@ __device__ __forceinline__ void transform_one_bwd(const float y[3][3], const flo
     float pos[3];
     for (int c = 0; c < 3; c++) pos[c] = (bary[0] * y[0][c] + bary[1] * y[1][c] + bary[2] * y[2][c]) * ibs;
     float yh[3][3];
-    for (int c = 0; c < 3; c++) {
-        const float m = (y[0][c] + y[1][c] + y[2][c]) * (1.f / 3.f);
-        for (int k = 0; k < 3; k++) yh[k][c] = y[k][c] - m;
-    }
+    centre_face(y, yh);
     // plane_basis(yh[0], yh[1]) with its intermediates kept
     const float inv0 = rsqrt_(dot3(yh[0], yh[0]));
     float u[3], t[3], v[3], n[3];
