@@ -62,6 +62,10 @@ EXPORTS = {
     "csplat_dist2": (_i, [_vp, _i, _vp, _vp]),
     "csplat_dist2_temp_bytes": (_sz, [_i]),
     "csplat_dist2_ws": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "csplat_knn": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "csplat_knn_temp_bytes": (_sz, [_i, _i]),
+    "csplat_knn_ws": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "csplat_fps": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "csplat_mesh_rest_bytes": (_sz, [_i]),
     "csplat_mesh_rest": (_i, [_vp, _i, _vp, _vp, _vp]),
     "csplat_mesh_transform_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -222,3 +222,308 @@ extern "C" int csplat_dist2_ws(void *stream, int P, const float *xyz, float *out
     LAUNCH_CHECK();
     return 0;
 }
+
+// ================================================================================================================================
+// Exact k-NN with indices (csplat_knn / csplat_knn_ws) and farthest-point sampling (csplat_fps).  Nothing above is touched: the
+// pruned form reuses k_bbox_partial / k_morton / the radix sort / k_knn_boxes and the workspace layout of csplat_dist2_ws.
+//
+// The K best (d2, index) pairs of a query live in registers: KBest<CAP> with CAP in {4, 8, 16, 32}, every access through a fully
+// unrolled loop (a runtime-indexed private array would go to scratch memory).  Slots [0, CAP-K) hold the pair (-inf, -1), which no
+// candidate can precede, so the K real entries sit in slots [CAP-K, CAP) and slot CAP-1 is always the K-th best -- the skip test
+// and the box rejection use the exact bound for every K, not the bound of the rounded-up capacity.  Pairs are ordered by
+// (d2, index): the result does not depend on the order in which candidates arrive, which is what lets the Morton-ordered form
+// return the same bits and indices as the brute-force one.
+namespace {
+constexpr int KNN_IDX_NONE = 0x7fffffff;   // index of an empty slot and of the query itself: never precedes anything
+
+template <int CAP> struct KBest {
+    float d[CAP];
+    int id[CAP];
+    __device__ __forceinline__ void init(int K) {   // K = 0: a list that accepts nothing (lanes without a query)
+#pragma unroll
+        for (int r = 0; r < CAP; r++) {
+            const bool dead = r < CAP - K;
+            d[r] = dead ? -INFINITY : INFINITY;
+            id[r] = dead ? -1 : KNN_IDX_NONE;
+        }
+    }
+    __device__ __forceinline__ float worst() const { return d[CAP - 1]; }
+    __device__ __forceinline__ bool before(float cd, int ci, int r) const { return cd < d[r] || (cd == d[r] && ci < id[r]); }
+    // sorted insert; a pair that does not precede the worst entry changes nothing
+    __device__ __forceinline__ void insert(float cd, int ci) {
+        bool here = before(cd, ci, CAP - 1);
+#pragma unroll
+        for (int r = CAP - 1; r > 0; r--) {
+            const bool above = before(cd, ci, r - 1);   // the candidate goes above slot r: slot r takes its upper neighbour
+            d[r] = above ? d[r - 1] : (here ? cd : d[r]);
+            id[r] = above ? id[r - 1] : (here ? ci : id[r]);
+            here = above;
+        }
+        d[0] = here ? cd : d[0];
+        id[0] = here ? ci : id[0];
+    }
+    __device__ __forceinline__ void store(int K, size_t row, float *__restrict__ out_d2, int32_t *__restrict__ out_idx) const {
+#pragma unroll
+        for (int s = 0; s < CAP; s++) {
+            const int r = s - (CAP - K);
+            if (r >= 0) {
+                out_d2[row * K + r] = d[s];                              // an empty slot still holds +inf
+                out_idx[row * K + r] = id[s] == KNN_IDX_NONE ? -1 : id[s];
+            }
+        }
+    }
+};
+
+// one candidate against one query per lane.  The wave tests the candidate against every lane's K-th best first and skips the
+// insert together; `<=` (not the full pair order) keeps the test at one compare -- an equal distance enters the insert, which
+// then decides by index.
+template <int CAP>
+__device__ __forceinline__ void knn_offer(KBest<CAP> &b, float d, int ci, bool self) {
+    d = self ? INFINITY : d;
+    ci = self ? KNN_IDX_NONE : ci;
+    if (__builtin_amdgcn_ballot_w64(d <= b.worst()) != 0ull) b.insert(d, ci);
+}
+
+// four candidates at once: one wave-wide test and one branch for the four (after the first few hundred candidates almost every
+// group is skipped whole), then the single-candidate path for a group in which some lane still needs one
+template <int CAP>
+__device__ __forceinline__ void knn_offer4(KBest<CAP> &b, const float (&d)[4], const int (&ci)[4], const bool (&self)[4]) {
+    const float w = b.worst();
+    const bool any = (!self[0] && d[0] <= w) || (!self[1] && d[1] <= w) || (!self[2] && d[2] <= w) || (!self[3] && d[3] <= w);
+    if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;
+#pragma unroll
+    for (int u = 0; u < 4; u++) knn_offer(b, d[u], ci[u], self[u]);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(KNN_THREADS) void k_knn_brute(int P, int K, const float *__restrict__ pts, float *__restrict__ out_d2,
+                                                           int32_t *__restrict__ out_idx) {
+#pragma clang fp contract(off)
+    __shared__ float s_p[KNN_SLAB * 3];
+    const int i = blockIdx.x * KNN_THREADS + threadIdx.x;
+    const bool live = i < P;
+    const float x = live ? pts[3 * (size_t)i] : 0.f, y = live ? pts[3 * (size_t)i + 1] : 0.f, z = live ? pts[3 * (size_t)i + 2] : 0.f;
+    KBest<CAP> b;
+    b.init(live ? K : 0);
+    for (int base = 0; base < P; base += KNN_SLAB) {
+        const int cnt = min(KNN_SLAB, P - base);
+        __syncthreads();
+        for (int k = threadIdx.x; k < cnt * 3; k += KNN_THREADS) s_p[k] = pts[(size_t)base * 3 + k];
+        __syncthreads();
+        const int self = i - base;
+        int j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+            float d[4];
+            int ci[4];
+            bool me[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const float dx = s_p[3 * (j + u)] - x, dy = s_p[3 * (j + u) + 1] - y, dz = s_p[3 * (j + u) + 2] - z;
+                d[u] = dx * dx + dy * dy + dz * dz;
+                ci[u] = base + j + u;
+                me[u] = j + u == self;
+            }
+            knn_offer4(b, d, ci, me);
+        }
+        for (; j < cnt; j++) {
+            const float dx = s_p[3 * j] - x, dy = s_p[3 * j + 1] - y, dz = s_p[3 * j + 2] - z;
+            knn_offer(b, dx * dx + dy * dy + dz * dz, base + j, j == self);
+        }
+    }
+    if (live) b.store(K, (size_t)i, out_d2, out_idx);
+}
+
+// pruned form.  spts: the points in Morton order, .w = the caller's index.  A wave first takes its own stretch of the curve
+// (its 64 queries and K positions either side: at least K other points whenever P > K, so every lane starts with a finite
+// K-th distance), then scans the boxes that are not farther than a lane's current K-th best, leaving that stretch out.
+// Rejection is strict (`>`): a box at exactly the K-th distance may hold an equal distance with a smaller index.
+template <int CAP>
+__global__ __launch_bounds__(256) void k_knn_search_k(int P, int K, int nbox, const float4 *__restrict__ spts, const float *__restrict__ boxes,
+                                                      float *__restrict__ out_d2, int32_t *__restrict__ out_idx) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < P;
+    const float4 p = spts[live ? i : P - 1];
+    KBest<CAP> b;
+    b.init(live ? K : 0);
+    auto scan = [&](int lo, int hi) {
+        int j = lo;                              // wave-uniform addresses: one broadcast load per candidate
+        for (; j + 4 <= hi; j += 4) {
+            float d[4];
+            int ci[4];
+            bool me[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const float4 c = spts[j + u];
+                const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
+                d[u] = dx * dx + dy * dy + dz * dz;
+                ci[u] = (int)__float_as_uint(c.w);
+                me[u] = j + u == i;
+            }
+            knn_offer4(b, d, ci, me);
+        }
+        for (; j < hi; j++) {
+            const float4 c = spts[j];
+            const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
+            knn_offer(b, dx * dx + dy * dy + dz * dz, (int)__float_as_uint(c.w), j == i);
+        }
+    };
+    const int w0 = __builtin_amdgcn_readfirstlane(i & ~63);
+    const int wlo = max(0, w0 - K), whi = min(P, w0 + 64 + K);   // [wlo, whi)
+    scan(wlo, whi);
+    for (int bi = 0; bi < nbox; bi++) {
+        const float *bx = boxes + 6 * bi;
+        float ex = 0.f, ey = 0.f, ez = 0.f;     // distance from the query to the box, per axis
+        if (p.x < bx[0] || p.x > bx[3]) ex = fminf(fabsf(p.x - bx[0]), fabsf(p.x - bx[3]));
+        if (p.y < bx[1] || p.y > bx[4]) ey = fminf(fabsf(p.y - bx[1]), fabsf(p.y - bx[4]));
+        if (p.z < bx[2] || p.z > bx[5]) ez = fminf(fabsf(p.z - bx[2]), fabsf(p.z - bx[5]));
+        const float dist = ex * ex + ey * ey + ez * ez;
+        const bool need = !(dist > b.worst());   // lanes without a query hold -inf and never need a box
+        if (__builtin_amdgcn_ballot_w64(need) == 0ull) continue;
+        const int lo = bi * KNN_BOX, hi = min(P, lo + KNN_BOX);
+        scan(lo, min(hi, wlo));
+        scan(max(lo, whi), hi);
+    }
+    if (live) b.store(K, (size_t)__float_as_uint(p.w), out_d2, out_idx);
+}
+
+// ---- farthest-point sampling: S selections are a serial chain, so one workgroup stays resident for all of them.  Each round
+// lowers every point's distance to the selected set by the newest selection, reduces (value, index) to the workgroup's argmax --
+// equal values go to the smaller index, numpy's argmax rule -- and every lane reads the winner's coordinates back as one
+// wave-uniform load.  REG: N <= 1024 * FPS_REG points and their distances stay in registers; otherwise they stream from memory
+// (12 N + 4 N bytes a round, L2-resident at the sizes this is for).  One barrier a round: the LDS exchange is double-buffered.
+constexpr int FPS_THREADS = 1024, FPS_REG = 8, FPS_WAVES = FPS_THREADS / 64;
+
+template <bool REG>
+__global__ __launch_bounds__(FPS_THREADS) void k_fps(int N, int S, const float *__restrict__ pts, int start, float *__restrict__ min_d2,
+                                                     int32_t *__restrict__ out_idx) {
+#pragma clang fp contract(off)
+    __shared__ float s_v[2][FPS_WAVES];
+    __shared__ int s_i[2][FPS_WAVES];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    float px[FPS_REG], py[FPS_REG], pz[FPS_REG], md[FPS_REG];
+    if (REG) {
+#pragma unroll
+        for (int m = 0; m < FPS_REG; m++) {
+            const int i = t + FPS_THREADS * m;
+            const bool in = i < N;
+            px[m] = in ? pts[3 * i] : 0.f; py[m] = in ? pts[3 * i + 1] : 0.f; pz[m] = in ? pts[3 * i + 2] : 0.f;
+            md[m] = INFINITY;
+        }
+    } else {
+        for (int i = t; i < N; i += FPS_THREADS) min_d2[i] = INFINITY;
+    }
+    if (t == 0) out_idx[0] = start;
+    int cur = start;
+    for (int s = 1; s <= S; s++) {     // round S only folds the last selection into min_d2
+        const float cx = pts[3 * (size_t)cur], cy = pts[3 * (size_t)cur + 1], cz = pts[3 * (size_t)cur + 2];
+        float bv = -1.f;               // below every squared distance: the first point offered is taken
+        int bi = KNN_IDX_NONE;
+        if (REG) {
+#pragma unroll
+            for (int m = 0; m < FPS_REG; m++) {
+                const int i = t + FPS_THREADS * m;
+                const float dx = px[m] - cx, dy = py[m] - cy, dz = pz[m] - cz;
+                md[m] = fminf(md[m], dx * dx + dy * dy + dz * dz);
+                if (i < N && md[m] > bv) { bv = md[m]; bi = i; }   // ascending i: strict `>` keeps the smallest index
+            }
+        } else {
+            for (int i = t; i < N; i += FPS_THREADS) {
+                const float dx = pts[3 * (size_t)i] - cx, dy = pts[3 * (size_t)i + 1] - cy, dz = pts[3 * (size_t)i + 2] - cz;
+                const float m = fminf(min_d2[i], dx * dx + dy * dy + dz * dz);
+                min_d2[i] = m;
+                if (m > bv) { bv = m; bi = i; }
+            }
+        }
+        if (s == S) break;
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { s_v[s & 1][wv] = bv; s_i[s & 1][wv] = bi; }
+        __syncthreads();
+        bv = s_v[s & 1][lane & (FPS_WAVES - 1)];
+        bi = s_i[s & 1][lane & (FPS_WAVES - 1)];
+        for (int o = FPS_WAVES / 2; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        cur = __builtin_amdgcn_readfirstlane(bi);
+        if (t == 0) out_idx[s] = cur;
+    }
+    if (REG) {
+#pragma unroll
+        for (int m = 0; m < FPS_REG; m++) {
+            const int i = t + FPS_THREADS * m;
+            if (i < N) min_d2[i] = md[m];
+        }
+    }
+}
+}  // namespace
+
+#define KNN_BY_CAPACITY(K, LAUNCH)                                  \
+    do {                                                            \
+        if ((K) <= 4) { LAUNCH(4); } else if ((K) <= 8) { LAUNCH(8); } else if ((K) <= 16) { LAUNCH(16); } else { LAUNCH(32); } \
+    } while (0)
+
+extern "C" int csplat_knn(void *stream, int P, int K, const float *xyz, float *out_d2, int32_t *out_idx) {
+    CSPLAT_REQUIRE(P >= 0, "csplat_knn: bad P");
+    CSPLAT_REQUIRE(K >= 1 && K <= CSPLAT_KNN_MAX_K, "csplat_knn: K outside 1 .. CSPLAT_KNN_MAX_K");
+    if (P == 0) return 0;
+    CSPLAT_REQUIRE(xyz && out_d2 && out_idx, "csplat_knn: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+#define LAUNCH(CAP) k_knn_brute<CAP><<<cdiv(P, KNN_THREADS), KNN_THREADS, 0, s>>>(P, K, xyz, out_d2, out_idx)
+    KNN_BY_CAPACITY(K, LAUNCH);
+#undef LAUNCH
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t csplat_knn_temp_bytes(int P, int K) { (void)K; return knn_ws(P).total; }
+
+// workspace form: Morton order + box pruning (exact; the same bits and indices as csplat_knn).  temp: csplat_knn_temp_bytes(P, K) bytes.
+extern "C" int csplat_knn_ws(void *stream, int P, int K, const float *xyz, float *out_d2, int32_t *out_idx, void *temp) {
+    CSPLAT_REQUIRE(P >= 0, "csplat_knn_ws: bad P");
+    CSPLAT_REQUIRE(K >= 1 && K <= CSPLAT_KNN_MAX_K, "csplat_knn_ws: K outside 1 .. CSPLAT_KNN_MAX_K");
+    if (P == 0) return 0;
+    CSPLAT_REQUIRE(xyz && out_d2 && out_idx && temp, "csplat_knn_ws: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+    const KnnWs w = knn_ws(P);
+    char *t = (char *)temp;
+    float *part = (float *)(t + w.part);
+    uint64_t *codes = (uint64_t *)(t + w.codes), *codes_o = (uint64_t *)(t + w.codes_o), *codes_t = (uint64_t *)(t + w.codes_t);
+    uint32_t *ids = (uint32_t *)(t + w.ids), *ids_o = (uint32_t *)(t + w.ids_o), *ids_t = (uint32_t *)(t + w.ids_t);
+    float4 *spts = (float4 *)(t + w.spts);
+    float *boxes = (float *)(t + w.boxes);
+    const int nparts = P < 256 * 256 ? cdiv(P, 256) : 256, nbox = cdiv(P, KNN_BOX);
+    k_bbox_partial<<<nparts, 256, 0, s>>>(P, xyz, part);
+    LAUNCH_CHECK();
+    k_morton<<<cdiv(P, 256), 256, 0, s>>>(P, nparts, xyz, part, codes, ids);
+    LAUNCH_CHECK();
+    if (int rc = csplat_sort_pairs(s, codes, ids, codes_o, ids_o, codes_t, ids_t, P, 63, t + w.stab)) return rc;
+    k_knn_boxes<<<nbox, 256, 0, s>>>(P, xyz, ids_o, spts, boxes);
+    LAUNCH_CHECK();
+#define LAUNCH(CAP) k_knn_search_k<CAP><<<cdiv(P, 256), 256, 0, s>>>(P, K, nbox, spts, boxes, out_d2, out_idx)
+    KNN_BY_CAPACITY(K, LAUNCH);
+#undef LAUNCH
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int csplat_fps(void *stream, int N, int S, const float *xyz, int start, float *min_d2, int32_t *out_idx) {
+    CSPLAT_REQUIRE(N >= 0 && S >= 0, "csplat_fps: bad N or S");
+    if (S == 0) return 0;
+    CSPLAT_REQUIRE(N >= 1, "csplat_fps: S > 0 needs at least one point");
+    CSPLAT_REQUIRE(start >= 0 && start < N, "csplat_fps: start outside 0 .. N-1");
+    CSPLAT_REQUIRE(xyz && min_d2 && out_idx, "csplat_fps: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+    if (N <= FPS_THREADS * FPS_REG) k_fps<true><<<1, FPS_THREADS, 0, s>>>(N, S, xyz, start, min_d2, out_idx);
+    else k_fps<false><<<1, FPS_THREADS, 0, s>>>(N, S, xyz, start, min_d2, out_idx);
+    LAUNCH_CHECK();
+    return 0;
+}

@@ -1,1 +1,57 @@
 """Drop-in for the `simple_knn` package (reference import: scene_reconstruction/gaussian_mesh.py:26)."""
+import torch
+
+from csplat import native as _n
+
+MAX_K = 32          # include/csplat.h: CSPLAT_KNN_MAX_K
+BOXED_FROM = 4096   # below this the single brute-force kernel is faster than sort + boxes (the threshold of distCUDA2)
+
+
+def _checked_points(points, k, what):
+    """argument errors are raised before anything touches the device"""
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k must be an integer in 1 .. {MAX_K}, got {k!r}")
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{what}: points must be a [P, 3] tensor, got {tuple(getattr(points, 'shape', ()))}")
+    if points.dtype != torch.float32:
+        raise ValueError(f"{what}: points must be float32, got {points.dtype}")
+
+
+def knn(points: torch.Tensor, k: int):
+    """points [P,3] float32 on the GPU -> (sq_dists float32 [P,k], indices int64 [P,k]): the k nearest OTHER points of every
+    point (self excluded by index, so coincident points are neighbours at distance 0), ascending in (sq_dist, index).  Exact:
+    ties go to the smaller index; rows with fewer than k other points end in (+inf, -1).  For k = 3 the row mean is
+    bit-identical to `simple_knn._C.distCUDA2`."""
+    _checked_points(points, k, "simple_knn.knn")
+    _n.require_cuda(points)
+    pts = points.detach().contiguous()
+    P, dev = int(pts.shape[0]), pts.device
+    d2 = torch.empty(P, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(P, k, dtype=torch.int32, device=dev)
+    with _n.on_device(dev):
+        if P >= BOXED_FROM:   # Morton order + box pruning; the same bits and indices
+            temp = torch.empty(int(_n.lib.csplat_knn_temp_bytes(P, k)), dtype=torch.uint8, device=dev)
+            _n.check(_n.lib.csplat_knn_ws(_n.stream_handle(dev), P, k, _n.ptr(pts), _n.ptr(d2), _n.ptr(idx), _n.ptr(temp)), "csplat_knn_ws")
+        else:
+            _n.check(_n.lib.csplat_knn(_n.stream_handle(dev), P, k, _n.ptr(pts), _n.ptr(d2), _n.ptr(idx)), "csplat_knn")
+    return d2, idx.to(torch.int64)
+
+
+def fps(points: torch.Tensor, num_samples: int, start: int):
+    """points [N,3] float32 on the GPU -> int64 [num_samples] farthest-point-sampling indices beginning at `start`: every
+    further index is the point farthest (squared distance, float32) from those already chosen, the smallest index among
+    equal maxima.  num_samples > N repeats indices as the reference's loop does."""
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"simple_knn.fps: points must be a float32 [N, 3] tensor, got {getattr(points, 'dtype', None)} "
+                         f"{tuple(getattr(points, 'shape', ()))}")
+    N, S = int(points.shape[0]), int(num_samples)
+    if S < 0 or (S > 0 and not 0 <= int(start) < N):
+        raise ValueError(f"simple_knn.fps: need num_samples >= 0 and 0 <= start < N, got num_samples={S}, start={start}, N={N}")
+    _n.require_cuda(points)
+    pts = points.detach().contiguous()
+    dev = pts.device
+    out = torch.empty(S, dtype=torch.int32, device=dev)
+    min_d2 = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+    with _n.on_device(dev):
+        _n.check(_n.lib.csplat_fps(_n.stream_handle(dev), N, S, _n.ptr(pts), int(start) if S else 0, _n.ptr(min_d2), _n.ptr(out)), "csplat_fps")
+    return out.to(torch.int64)

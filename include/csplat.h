@@ -19,6 +19,9 @@
  *       each pixel, for an occlusion-aware `visibility_filter` (the reference uses radii > 0, train_utils.py:270-300, train.py:52-90).
  *   csplat_dist2
  *       `simple_knn._C.distCUDA2`, scene_reconstruction/gaussian_mesh.py:26,250; gaussian_model.py:20,134.
+ *   csplat_knn, csplat_knn_ws, csplat_fps
+ *       the host neighbour queries of the reference: cKDTree in compute_edges_index (meshnet/data_utils.py:406-412), the Open3D
+ *       KD-tree of o3d_knn (utils/external.py:5-16), the numpy loop of farthest_point_sampling (meshnet/data_utils.py:134-160).
  *   csplat_gnn_*
  *       the torch_geometric MessagePassing gather / scatter-add inside InteractionNetwork.propagate,
  *       meshnet/graph_network.py:173-174 (gather x_i, x_j: PyG __lift__), :197 (concat), :136 (aggr='add').
@@ -334,6 +337,23 @@ int csplat_dist2(void *stream, int P, const float *xyz, float *out);
  * does; temp: csplat_dist2_temp_bytes(P) bytes of device memory. */
 size_t csplat_dist2_temp_bytes(int P);
 int csplat_dist2_ws(void *stream, int P, const float *xyz, float *out, void *temp);
+
+/* Exact k nearest neighbours WITH indices, self excluded by index (coincident points are neighbours at distance 0, as in
+ * csplat_dist2).  out_d2[i*K + r], out_idx[i*K + r]: the r-th nearest other point of point i, ascending in (d2, index) -- ties in
+ * d2 are broken by the smaller index, which makes the result unique.  Slots r >= P-1 (fewer than K other points): d2 = +inf,
+ * idx = -1.  d2 = dx*dx + dy*dy + dz*dz with d = candidate - query, FP contraction off (the arithmetic of csplat_dist2: for
+ * K = 3, (d2[0] + d2[1] + d2[2]) / 3.0f is bit-identical to it).  1 <= K <= CSPLAT_KNN_MAX_K; P = 0 is a no-op.  Indices are
+ * the caller's.  csplat_knn is the brute-force form, csplat_knn_ws the Morton-order + bounding-box form (the same bits and the
+ * same indices; temp: csplat_knn_temp_bytes(P, K) bytes of device memory).  Added exports: CSPLAT_ABI_VERSION is unchanged. */
+#define CSPLAT_KNN_MAX_K 32
+int csplat_knn(void *stream, int P, int K, const float *xyz, float *out_d2, int32_t *out_idx);
+size_t csplat_knn_temp_bytes(int P, int K);
+int csplat_knn_ws(void *stream, int P, int K, const float *xyz, float *out_d2, int32_t *out_idx, void *temp);
+/* Farthest-point sampling.  out_idx[0] = start; out_idx[s] = argmax_i min_{t<s} d2(i, out_idx[t]), the smallest i among equal
+ * maxima (numpy's argmax rule); the same d2 arithmetic as above.  min_d2: caller-provided float[N] work array (on return: each
+ * point's squared distance to the selected set).  S > N is legal and repeats indices (all min_d2 are 0, argmax is index 0).
+ * One workgroup runs all S rounds; 0 <= start < N. */
+int csplat_fps(void *stream, int N, int S, const float *xyz, int start, float *min_d2, int32_t *out_idx);
 
 /* Separable 11-tap window of the SSIM loss (utils/loss_utils.py:30-58), zero padded: out = G (x) G * in for every one of
  * the n_images [H][W] planes.  taps11 is a HOST pointer to the 11 normalised window weights.  Self-adjoint: the backward
