@@ -1,7 +1,7 @@
 // csplat_raster.hip -- the depth-aware differentiable Gaussian rasterizer for gfx950 (MI355X).
 //
 // Replaces the CUDA extension behind GaussianRasterizer.forward / backward
-// (/root/reference/gaussian_renderer/__init__.py:16,76,156-164; backward via
+// (the reference's gaussian_renderer/__init__.py:16,76,156-164; backward via
 // scene_reconstruction/train_utils.py:288).  Kernel inventory = SURVEY.md 2.1 K1..K8:
 //   K1 k_preprocess        per-Gaussian cull / projection / cov3D / cov2D / conic / radius / rect / SH->RGB
 //   K2 (csplat_sort.hip)   inclusive scan of tiles_touched
@@ -13,6 +13,18 @@
 //   K7 k_composite_bwd     per (segment, quadrant) workgroup, forward-ordered replay from the checkpoints, factored moment reduction
 //                          reduction, LDS records, one atomic per (entry, quadrant)
 //   K8 k_preprocess_bwd    conic->cov2D->cov3D/mean, mean2D(NDC)->mean3D, colour->SH, cov3D->(scale,quat)
+// Every stage has a `_views` form: all views of a step (at most RASTER_MAX_VIEWS) in one launch, blockIdx.y = view.
+// The extended paths, each launched only when a view asks for it (csplat_view, include/csplat.h):
+//   antialiasing           k_preprocess_aa, k_preprocess_bwd_aa (+ _views): K1 / K8 with the opacity compensation
+//   depth gradient         k_depth_bwd_partials, k_depth_composite_bwd_views, k_preprocess_bwd_depth (+ _views)
+//   camera / background    k_preprocess_bwd_cam (+ _views), k_bg_partials, k_cam_sum
+//   features, alpha        k_feature_fwd_views, k_feature_bwd_partials, k_feature_composite_bwd_views, k_feature_grads
+//   visibility             k_visibility_walk_views, k_visibility_reduce_views
+//   bit-reproducible mode  k_composite_bwd_rows<true>, *_det, k_*det_reduce*: ordered sums instead of float atomics (debug flag 256)
+//
+// The file has two halves.  Device code comes first, kernel by kernel under the "---- K<n>" rules.  The host half starts at the
+// "---- layouts" rule: the chunk layouts and their typed views (Geom, ImageView, BinView, TempView), the two-phase forward, the backward of
+// one view (backward_impl, launch_k8), then the batched entry points and the extended paths (fill_b2_view, launch_k8_views).
 //
 // Index-deciding arithmetic (radius, tile rectangle, sort key) is compiled with FP contraction OFF and is
 // written in the same association order as oracle/raster_ref.c, so tile/bin indices are bit-exact.
@@ -27,6 +39,9 @@
 namespace {
 
 constexpr float NEAR_Z = 0.2f;
+// views per batched launch: every per-view table a kernel takes by value (K1Table, P2Table, B2Table, K8Table, ...) holds this many, and the
+// host cuts larger calls into groups of at most this many (view_groups)
+constexpr int RASTER_MAX_VIEWS = 8;
 
 __device__ constexpr float SH_C0 = 0.28209479177387814f;
 __device__ constexpr float SH_C1 = 0.4886025119029199f;
@@ -380,7 +395,6 @@ __global__ __launch_bounds__(256) void k_preprocess_aa(int P, int D, int M, cons
 // The first phase of the forward (K1 + the three counting kernels) for ALL views of a step, one launch each (blockIdx.y =
 // view): a 4-view step otherwise spends 16 launches (~10 us of host time each, the GPU idling in between) before its one
 // host read.  Views share the Gaussians' view-independent inputs; means / rotations / cameras / outputs come per view.
-constexpr int K1_MAX_VIEWS = 8;
 struct K1View {
     const float *means3D, *rotations;
     Cam cam;
@@ -390,7 +404,7 @@ struct K1View {
     int2 *ranges;
     uint32_t tag;
 };
-struct K1Table { int n; K1View v[K1_MAX_VIEWS]; };
+struct K1Table { int n; K1View v[RASTER_MAX_VIEWS]; };
 
 // (the 192-byte SH row of a Gaussian is staged ONCE per workgroup and evaluated for every view's direction)
 constexpr int K1V_G = 64;
@@ -670,7 +684,6 @@ __global__ __launch_bounds__(BUCKET_G) void k_emit_bucket(int P, int tiles, cons
 // The second phase of the forward (after the one host read of the instance counts) for ALL views of a step, one launch per
 // stage (blockIdx.y = view): the GPU's dispatcher packs the views' workgroups instead of 4 x 5 launches staggered by the
 // host's launch rate.
-constexpr int P2_MAX_VIEWS = 8;
 struct P2View {
     Geom g;
     Cam cam;
@@ -699,7 +712,7 @@ struct P2View {
     uint32_t Bcap;              // non-empty tiles the compositing forward's grid was sized for
     int spec;
 };
-struct P2Table { P2View v[P2_MAX_VIEWS]; uint32_t *valid; int nviews; };     // valid: see csplat_forward_views_faith (NULL otherwise)
+struct P2Table { P2View v[RASTER_MAX_VIEWS]; uint32_t *valid; int nviews; };     // valid: see csplat_forward_views_faith (NULL otherwise)
 __device__ __forceinline__ bool p2_live(const P2View &w) { return !w.spec || (w.info[0] - 1u < w.R && w.info[1] <= w.Lcap && w.info[2] <= w.Bcap); }
 __device__ __forceinline__ void seg_plan_body(int tiles, const int2 *__restrict__ ranges, int *__restrict__ seg_offset,
                                               int *__restrict__ slot_tile);
@@ -2209,7 +2222,6 @@ __global__ __launch_bounds__(256) void k_composite_bwd_rows(int tiles, int W, in
 }
 
 // K7 for ALL views of a step in one launch (blockIdx.y = view), preceded by one launch that clears every view's records
-constexpr int B2_MAX_VIEWS = 8;
 struct B2View {
     const int2 *ranges;
     const uint32_t *ids_sorted;
@@ -2225,7 +2237,7 @@ struct B2View {
     uint32_t R;
     float *det;        // bit-reproducible mode: the (entry, block) records behind the per-Gaussian ones, else NULL
 };
-struct B2Table { B2View v[B2_MAX_VIEWS]; unsigned long long *stamp; const uint32_t *valid; };
+struct B2Table { B2View v[RASTER_MAX_VIEWS]; unsigned long long *stamp; const uint32_t *valid; };
 __global__ __launch_bounds__(256, 8) void k_composite_bwd_rows_views(int tiles, int W, int H, int gx, B2Table tab) {
     if (tab.valid && *tab.valid == 0u) return;     // (a forward launched on faith whose counts did not fit: its chunks hold nothing)
     const B2View &w = tab.v[blockIdx.y];
@@ -2290,7 +2302,7 @@ __global__ __launch_bounds__(256) void k_det_reduce(int P, Cam cam, const float2
 
 struct DetView { Cam cam; const float2 *xy; const float *depth; const int32_t *radii; const int2 *ranges; const uint64_t *keys_sorted;
                  const uint32_t *ids_sorted; const float *det; float *acc; };
-struct DetTable { DetView v[B2_MAX_VIEWS]; const uint32_t *valid; };
+struct DetTable { DetView v[RASTER_MAX_VIEWS]; const uint32_t *valid; };
 // NF floats per stored record: 9, or 10 on the depth path (slot 9 = dL/dz)
 template <int NF>
 __device__ __forceinline__ void det_reduce_views_body(int P, const DetTable &tab) {
@@ -2337,7 +2349,7 @@ struct DepthView {
     float *dpart;             // [slots][256] (segment, pixel of the tile in block-major order, as the checkpoints)
     int W, H, gx, tiles;      // tiles = 0: the view has no list entries -- nothing to do
 };
-struct DepthTable { DepthView v[B2_MAX_VIEWS]; };
+struct DepthTable { DepthView v[RASTER_MAX_VIEWS]; };
 __global__ __launch_bounds__(256) void k_depth_bwd_partials(DepthTable tab) {
     const DepthView &w = tab.v[blockIdx.y];
     if (!w.dL_ddepth || w.tiles == 0) return;
@@ -2412,7 +2424,7 @@ struct FeatFwdView {
     float *out_alpha;         // [H][W], NULL: not asked for
     int nf, W, H, gx, tiles;  // tiles = 0: the view has no list entries (feat = 0, alpha = 0)
 };
-struct FeatFwdTable { FeatFwdView v[B2_MAX_VIEWS]; };
+struct FeatFwdTable { FeatFwdView v[RASTER_MAX_VIEWS]; };
 // one pixel's walk over the blended entries of one segment (slot) from transmittance T: calls f(T alpha, list position) per blended entry
 template <typename Fn>
 __device__ __forceinline__ void walk_segment(const float4 *__restrict__ recA, const float4 *__restrict__ recB,
@@ -2496,7 +2508,7 @@ struct FeatView {
 };
 // not an ABI bit: an earlier group of views of the same call (backward_views_impl) already wrote dL_dfeat_in -- add to it
 constexpr unsigned FEAT_ADD_IN = 1u << 31;
-struct FeatTable { FeatView v[B2_MAX_VIEWS]; int n; };
+struct FeatTable { FeatView v[RASTER_MAX_VIEWS]; int n; };
 __global__ __launch_bounds__(256) void k_feature_bwd_partials(FeatTable tab) {
     const FeatView &fv = tab.v[blockIdx.y];
     const DepthView &w = fv.d;
@@ -2592,7 +2604,7 @@ struct VisView {
     int32_t *rec_cnt;
     int W, H, gx, tiles;       // tiles = 0: the view has no list entries (top_id = -1 everywhere)
 };
-struct VisTable { VisView v[B2_MAX_VIEWS]; };
+struct VisTable { VisView v[RASTER_MAX_VIEWS]; };
 static_assert(SEG == 256, "the visibility join keeps one list entry per thread of a segment");
 // inclusive scans over the 16 lanes of a DPP row (row_shr 1, 2, 4, 8; lanes shifted in from outside the row read 0): lane 15 of the row then
 // holds the row's sum / max / count, formed in the same order in every run
@@ -2721,7 +2733,7 @@ struct VisRedView {
     int32_t *pixel_count;
     int P, tiles;                     // tiles = 0: no list entries (zeros); P = 0: nothing asked of this view
 };
-struct VisRedTable { VisRedView v[B2_MAX_VIEWS]; };
+struct VisRedTable { VisRedView v[RASTER_MAX_VIEWS]; };
 __global__ __launch_bounds__(256) void k_visibility_reduce_views(VisRedTable tab) {
     const VisRedView &w = tab.v[blockIdx.y];
     const int i = blockIdx.x * 16 + (int)(threadIdx.x >> 4);            // 16 lanes (one DPP row) per Gaussian
@@ -3126,7 +3138,7 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_aa(CSPLAT_K8_ARGS, float 
 // keeps its Gaussian and loops over the views: inputs and SH rows are read once, gradients of parameters that all views
 // share are summed in registers (SH: in the LDS rows) and written once, per-view outputs (mean2D, conic, and mean3D /
 // rotation when every view has its own deformed copy) are written per view.  Same arithmetic per view as k_preprocess_bwd.
-constexpr int K8_MAX_VIEWS = 8;
+constexpr int K8_MAX_VIEWS = RASTER_MAX_VIEWS;      // (the name csplat_k8_views_body.h sizes its LDS rows with)
 struct K8View {
     Cam cam;
     Geom g;
@@ -3139,7 +3151,7 @@ struct K8Table {
     int n;
     unsigned sharedmask;   // CSPLAT_ACC_* bits of the outputs whose buffer is the same in every view
     const uint32_t *valid; // (csplat_forward_views_faith) 0 there: the forward left the views untouched -- nothing to differentiate
-    K8View v[K8_MAX_VIEWS];
+    K8View v[RASTER_MAX_VIEWS];
 };
 
 // VL lanes per Gaussian, lane vl takes the views vl, vl + VL, ...: with one lane per Gaussian the launch has P / 64 = 1564 waves (1.5 per
@@ -3152,7 +3164,7 @@ struct K8Table {
 // cam_partials_view): the lanes of a quad hold different views, so the partials go to LDS rows [view][Gaussian] and only rows of one view
 // are summed together.
 struct CamSlabs {
-    float *p[K8_MAX_VIEWS];   // per view: the slab (rows of CAM_NC floats, one per workgroup)
+    float *p[RASTER_MAX_VIEWS];   // per view: the slab (rows of CAM_NC floats, one per workgroup)
 };
 template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
@@ -3209,7 +3221,7 @@ struct BgView {
     int npix;
 };
 struct BgTable {
-    BgView v[K8_MAX_VIEWS];
+    BgView v[RASTER_MAX_VIEWS];
 };
 __global__ __launch_bounds__(256) void k_bg_partials(BgTable tab) {
     const BgView w = tab.v[blockIdx.y];
@@ -3237,7 +3249,7 @@ struct CamSumView {
     float *dL_dview, *dL_dproj, *dL_dcampos, *dL_dbg;   // each may be NULL
 };
 struct CamSumTable {
-    CamSumView v[K8_MAX_VIEWS];
+    CamSumView v[RASTER_MAX_VIEWS];
 };
 // columns [0, NC) of rows [0, rows) summed in a fixed order; the result is left in s[0 .. NC) (s: 256 x NC floats of LDS)
 template <int NC>
@@ -3276,18 +3288,24 @@ __global__ __launch_bounds__(256) void k_cam_sum(CamSumTable tab) {
 }
 
 // ------------------------------------------------------------------------------------------- layouts
-enum { G_DEPTH, G_XY, G_CONIC, G_RGB, G_COV3D, G_CLAMPED, G_TOUCHED, G_OFFSETS, G_CUT2, G_SCANTMP, G_PACK, G_NFIELDS };
-
-int64_t max_slots(int64_t R, int tiles) { return R / SEG + tiles + 1; }
-size_t geom_offsets(int P, size_t *off) {
+// The saved state of a view lives in chunks the caller allocates (GEOM, IMAGE, BINNING, TEMP): every field 256-byte aligned, in enum
+// order.  ONE function per chunk knows the sizes (*_offsets) and one hands out typed pointers (*_view): nothing else indexes a layout.
+size_t lay_out(const size_t *sz, int n, size_t *off) {
     size_t o = 0;
+    for (int k = 0; k < n; k++) { off[k] = o; o += align256(sz[k]); }
+    return o;
+}
+int tiles_of(int W, int H) { return cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE); }
+int64_t max_slots(int64_t R, int tiles) { return R / SEG + tiles + 1; }
+
+enum { G_DEPTH, G_XY, G_CONIC, G_RGB, G_COV3D, G_CLAMPED, G_TOUCHED, G_OFFSETS, G_CUT2, G_SCANTMP, G_PACK, G_NFIELDS };
+size_t geom_offsets(int P, size_t *off) {
     const size_t n = (size_t)(P > 0 ? P : 1);
     const size_t sz[G_NFIELDS] = {n * 4, n * 8, n * 16, n * 12, n * 24, n * 4, n * 4, n * 4, n * 4,
                                   csplat_scan_temp_bytes(P), n * 48};
-    for (int k = 0; k < G_NFIELDS; k++) { off[k] = o; o += align256(sz[k]); }
-    return o;
+    return lay_out(sz, G_NFIELDS, off);
 }
-Geom geom_view(void *base, int P) {
+Geom geom_view(const void *base, int P) {
     size_t off[G_NFIELDS];
     geom_offsets(P, off);
     char *b = (char *)base;
@@ -3301,52 +3319,70 @@ Geom geom_view(void *base, int P) {
     g.pack = (float4 *)(b + off[G_PACK]);
     return g;
 }
-// image: 0 ranges | 1 n_contrib | 2 final_T | 3 info u32[4] (R, longest tile list)
+// image: ranges int2[tiles] | n_contrib u32[H][W] | final_T f32[H][W] | info u32: [0] R, [1] longest list, [2] non-empty tiles; word 64: the
+//        number of non-empty tiles, their ids in tile order; word 64 + tiles + 4: the same ids, longest list first (K6's launch order)
+enum { I_RANGES, I_NCONTRIB, I_FINALT, I_INFO, I_NFIELDS };
+struct ImageView { int2 *ranges; uint32_t *n_contrib; float *final_T; uint32_t *info; };
 size_t image_offsets(int W, int H, size_t *off) {
-    const size_t tiles = (size_t)cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE), X = (size_t)W * H;
-    off[0] = 0;
-    off[1] = align256(tiles * 8);
-    off[2] = off[1] + align256(X * 4);
-    off[3] = off[2] + align256(X * 4);
-    off[4] = off[3] + align256(256 + 2 * (tiles + 4) * 4);   // info: [0] R, [1] longest list; word 64: number of non-empty tiles, their ids in
-                                                             // tile order; word 64 + tiles + 4: the same ids, longest list first (K6's launch order)
-    return off[4];
+    const size_t tiles = (size_t)tiles_of(W, H), X = (size_t)W * H;
+    const size_t sz[I_NFIELDS] = {tiles * 8, X * 4, X * 4, 256 + 2 * (tiles + 4) * 4};
+    return lay_out(sz, I_NFIELDS, off);
+}
+ImageView image_view(const void *base, int W, int H) {
+    size_t off[I_NFIELDS];
+    image_offsets(W, H, off);
+    char *b = (char *)base;
+    return {(int2 *)(b + off[I_RANGES]), (uint32_t *)(b + off[I_NCONTRIB]), (float *)(b + off[I_FINALT]), (uint32_t *)(b + off[I_INFO])};
 }
 // per-(counting workgroup, tile) table of the bucketed binning path; requested as its own TEMP-class chunk
 size_t bucket_table_bytes(int P, int tiles) { return align256(((size_t)cdiv(P > 0 ? P : 1, BUCKET_G) + 1) * tiles * 4); }
-// binning: 0 keys_sorted u64[R] | 1 ids_sorted u32[R] | 2 seg_offset i32[tiles+1] + blk_hi u32[tiles][16] (largest n_contrib of every
-//          4x4 pixel block, written by K6: K7 drops the (segment, quadrant) workgroups behind it on ONE scalar load) | 3 slot_tile i32[slots]
-//          | 4 ckpt float4[slots][16 blocks][16 pixels]   (slots = R/SEG + tiles + 1 bounds sum_t ceil(n_t/SEG))
-//          | 5 mask16 u16[R+1] | 6 recA float4[R+1] | 7 recB float4[R+1] | 8 recC float2[R+1]   (entry R = the null record)
-//          | 9 bbits u64[slots][16 blocks][SEG / 64]: per segment and block, which of the segment's 256 entries the block BLENDED (K6 -> K7)
-//          | 10 bmask u64[R / 64 + 4][16 blocks]: mask16 TRANSPOSED -- per 64 list entries (global index >> 6) and block, which entries
-//            reach the block (K5b -> K6, one scalar 8-byte load per chunk instead of 64 mask loads and a ballot)
-constexpr int B_NFIELDS = 11;
+// binning (the field numbers are ABI: csplat_binning_fields hands all eleven offsets out, in this order):
+//   B_KEYS keys_sorted u64[R] | B_IDS ids_sorted u32[R] | B_SEG seg_offset i32[tiles+1] + blk_hi u32[tiles][16] (largest n_contrib of every
+//   4x4 pixel block, written by K6: K7 drops the (segment, quadrant) workgroups behind it on ONE scalar load; the kernels find it behind
+//   seg_offset themselves) | B_SLOT slot_tile i32[slots]
+//   | B_CKPT ckpt float4[slots][16 blocks][16 pixels]   (slots = R/SEG + tiles + 1 bounds sum_t ceil(n_t/SEG))
+//   | B_MASK mask16 u16[R+1] | B_RECA recA float4[R+1] | B_RECB recB float4[R+1] | B_RECC recC float2[R+1]   (entry R = the null record)
+//   | B_BBITS bbits u64[slots][16 blocks][SEG / 64]: per segment and block, which of the segment's 256 entries the block BLENDED (K6 -> K7)
+//   | B_BMASK bmask u64[R / 64 + 4][16 blocks]: mask16 TRANSPOSED -- per 64 list entries (global index >> 6) and block, which entries
+//     reach the block (K5b -> K6, one scalar 8-byte load per chunk instead of 64 mask loads and a ballot)
+enum { B_KEYS, B_IDS, B_SEG, B_SLOT, B_CKPT, B_MASK, B_RECA, B_RECB, B_RECC, B_BBITS, B_BMASK, B_NFIELDS };
+struct BinView {
+    uint64_t *keys_sorted; uint32_t *ids_sorted; int *seg_offset, *slot_tile; float4 *ckpt; uint16_t *mask16; float4 *recA, *recB; float2 *recC;
+    unsigned long long *bbits, *bmask;
+};
 size_t binning_offsets(int64_t R, int tiles, size_t *off) {
-    const size_t n = (size_t)(R > 0 ? R : 1);
-    const size_t slots = (size_t)max_slots(R, tiles);
-    off[0] = 0;
-    off[1] = align256(n * 8);
-    off[2] = off[1] + align256(n * 4);
-    off[3] = off[2] + align256((size_t)(tiles + 1) * 4 + (size_t)tiles * 16 * 4);   // seg_offset[tiles + 1], then blk_hi[tiles][16]
-    off[4] = off[3] + align256(slots * 4);
-    off[5] = off[4] + align256(slots * 256 * 16);
-    off[6] = off[5] + align256((n + 1) * 2);
-    off[7] = off[6] + align256((n + 1) * 16);
-    off[8] = off[7] + align256((n + 1) * 16);
-    off[9] = off[8] + align256((n + 1) * 8);
-    off[10] = off[9] + align256(slots * 16 * (SEG / 8));
-    return off[10] + align256(((n + 63) / 64 + 4) * 16 * 8);
+    const size_t n = (size_t)(R > 0 ? R : 1), slots = (size_t)max_slots(R, tiles);
+    const size_t sz[B_NFIELDS] = {n * 8, n * 4, (size_t)(tiles + 1) * 4 + (size_t)tiles * 16 * 4, slots * 4, slots * 256 * 16, (n + 1) * 2,
+                                  (n + 1) * 16, (n + 1) * 16, (n + 1) * 8, slots * 16 * (SEG / 8), ((n + 63) / 64 + 4) * 16 * 8};
+    return lay_out(sz, B_NFIELDS, off);
 }
-// temp: 0 keys_unsorted | 1 ids_unsorted | 2 keys_tmp | 3 ids_tmp | 4 sort table
+BinView binning_view(const void *base, int64_t R, int tiles) {
+    size_t off[B_NFIELDS];
+    binning_offsets(R, tiles, off);
+    char *b = (char *)base;
+    BinView v;
+    v.keys_sorted = (uint64_t *)(b + off[B_KEYS]); v.ids_sorted = (uint32_t *)(b + off[B_IDS]);
+    v.seg_offset = (int *)(b + off[B_SEG]); v.slot_tile = (int *)(b + off[B_SLOT]); v.ckpt = (float4 *)(b + off[B_CKPT]);
+    v.mask16 = (uint16_t *)(b + off[B_MASK]); v.recA = (float4 *)(b + off[B_RECA]); v.recB = (float4 *)(b + off[B_RECB]);
+    v.recC = (float2 *)(b + off[B_RECC]); v.bbits = (unsigned long long *)(b + off[B_BBITS]);
+    v.bmask = (unsigned long long *)(b + off[B_BMASK]);
+    return v;
+}
+// temp: the unsorted keys and ids, the radix sort's ping-pong copies and its table (the bucketed path uses keys_u only)
+enum { T_KEYS_U, T_IDS_U, T_KEYS_T, T_IDS_T, T_SORT, T_NFIELDS };
+struct TempView { uint64_t *keys_u; uint32_t *ids_u; uint64_t *keys_t; uint32_t *ids_t; void *sort_tmp; };
 size_t temp_offsets(int64_t R, size_t *off) {
     const size_t n = (size_t)(R > 0 ? R : 1);
-    off[0] = 0;
-    off[1] = off[0] + align256(n * 8);
-    off[2] = off[1] + align256(n * 4);
-    off[3] = off[2] + align256(n * 8);
-    off[4] = off[3] + align256(n * 4);
-    return off[4] + csplat_sort_temp_bytes(R);
+    const size_t sz[T_SORT] = {n * 8, n * 4, n * 8, n * 4};
+    off[T_SORT] = lay_out(sz, T_SORT, off);
+    return off[T_SORT] + csplat_sort_temp_bytes(R);
+}
+TempView temp_view(void *base, int64_t R) {
+    size_t off[T_NFIELDS];
+    temp_offsets(R, off);
+    char *b = (char *)base;
+    return {(uint64_t *)(b + off[T_KEYS_U]), (uint32_t *)(b + off[T_IDS_U]), (uint64_t *)(b + off[T_KEYS_T]), (uint32_t *)(b + off[T_IDS_T]),
+            (void *)(b + off[T_SORT])};
 }
 
 // camera constants stay in HBM (80 bytes, read through the scalar cache by every wave): no host round trip
@@ -3356,6 +3392,35 @@ int make_cam(Cam &c, const float *view, const float *proj, const float *campos, 
     c.fx = (float)W / (2.0f * tanfovx); c.fy = (float)H / (2.0f * tanfovy);
     c.W = W; c.H = H; c.gx = cdiv(W, CSPLAT_TILE); c.gy = cdiv(H, CSPLAT_TILE);
     return 0;
+}
+void make_cam(Cam &c, const csplat_view &w) { make_cam(c, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H); }
+
+// ---- a finished view (csplat_view) as the backward and the extended passes read it
+// the list capacity the view's BINNING chunk (and its scratch) was laid out for
+int layout_R(const csplat_view &w) { return w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered; }
+// segments of the view: <= R / SEG + (non-empty tiles) + 1 with the EXACT counts the forward read -- the layout's bound (capacity / SEG +
+// all tiles + 1) launches twice as many workgroups that find no segment
+int64_t k7_slots(const csplat_view &w, int tiles) {
+    return (w.busy_tiles > 0 && w.num_rendered > 0) ? (int64_t)w.num_rendered / SEG + w.busy_tiles + 1 : max_slots(layout_R(w), tiles);
+}
+// what every walk over a view's tile lists reads (FeatFwdView, VisView, B2View): the fields have the chunk views' names
+template <typename T>
+void fill_list_view(const BinView &b, const ImageView &im, T &k) {
+    k.ranges = im.ranges; k.n_contrib = im.n_contrib;
+    k.ids_sorted = b.ids_sorted; k.seg_offset = b.seg_offset; k.ckpt = b.ckpt; k.bbits = b.bbits; k.recA = b.recA; k.recB = b.recB;
+}
+// the view's K7 record; det = where the caller's path keeps the (entry, block) records of the bit-reproducible mode, else NULL
+void fill_b2_view(const csplat_view &w, const BinView &b, const ImageView &im, float *det, B2View &k) {
+    fill_list_view(b, im, k);
+    k.final_T = im.final_T; k.slot_tile = b.slot_tile; k.recC = b.recC;
+    k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = (float *)w.scratch; k.R = (uint32_t)layout_R(w); k.det = det;
+}
+// ... and what the fixed-order sum of those records reads (bit-reproducible mode only)
+void fill_det_view(const csplat_view &w, const BinView &b, const B2View &k, DetView &e) {
+    make_cam(e.cam, w);
+    const Geom g = geom_view(w.geom, w.P);
+    e.xy = g.xy; e.depth = g.depth; e.radii = w.radii; e.ranges = k.ranges; e.keys_sorted = b.keys_sorted; e.ids_sorted = k.ids_sorted;
+    e.det = k.det; e.acc = k.acc;
 }
 
 // Mailboxes for the one host read of the forward (R and the longest tile list): 64 slots of host-pinned, device-mapped
@@ -3435,24 +3500,20 @@ extern "C" {
 const char *csplat_last_error(void) { return g_csplat_err; }
 
 size_t csplat_geom_bytes(int P) { size_t off[G_NFIELDS]; return geom_offsets(P, off); }
-size_t csplat_image_bytes(int W, int H) { size_t off[5]; return image_offsets(W, H, off); }
-size_t csplat_binning_bytes(int64_t R, int W, int H) { size_t off[B_NFIELDS]; return binning_offsets(R, cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE), off); }
-size_t csplat_temp_bytes(int P, int64_t R, int W, int H) { (void)P; (void)W; (void)H; size_t off[5]; return temp_offsets(R, off); }
+size_t csplat_image_bytes(int W, int H) { size_t off[I_NFIELDS]; return image_offsets(W, H, off); }
+size_t csplat_binning_bytes(int64_t R, int W, int H) { size_t off[B_NFIELDS]; return binning_offsets(R, tiles_of(W, H), off); }
+size_t csplat_temp_bytes(int P, int64_t R, int W, int H) { (void)P; (void)W; (void)H; size_t off[T_NFIELDS]; return temp_offsets(R, off); }
 // backward scratch: the per-Gaussian records; in the bit-reproducible mode (csplat_debug_flags bit 8) also one 9-float record
 // per (list entry, quadrant)
+static size_t acc_bytes(int P) { return align256((size_t)(P > 0 ? P : 1) * ACC_STRIDE * 4); }
 static size_t det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 9 * 4); }
-size_t csplat_backward_scratch_bytes(int P, int64_t R) {
-    return align256((size_t)(P > 0 ? P : 1) * ACC_STRIDE * 4) + ((g_debug_flags & 256u) ? det_bytes(R) : 0);
-}
+size_t csplat_backward_scratch_bytes(int P, int64_t R) { return acc_bytes(P) + ((g_debug_flags & 256u) ? det_bytes(R) : 0); }
 // the depth-gradient path: the per-Gaussian records, in the bit-reproducible mode the (entry, block) records of 10 floats, then the
 // per-(segment, pixel) depth partials of the prepass
 static size_t depth_det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 10 * 4); }
-static size_t depth_dpart_offset(int P, int64_t R) {
-    return align256((size_t)(P > 0 ? P : 1) * ACC_STRIDE * 4) + ((g_debug_flags & 256u) ? depth_det_bytes(R) : 0);
-}
+static size_t depth_dpart_offset(int P, int64_t R) { return acc_bytes(P) + ((g_debug_flags & 256u) ? depth_det_bytes(R) : 0); }
 size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H) {
-    const int tiles = cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE);
-    return depth_dpart_offset(P, R) + align256((size_t)max_slots(R, tiles) * 256 * 4);
+    return depth_dpart_offset(P, R) + align256((size_t)max_slots(R, tiles_of(W, H)) * 256 * 4);
 }
 // the camera path's slabs live behind everything the depth path lays out: the K8 slab (at most one row per 32 Gaussians: the batched K8's
 // workgroup), then the background slab
@@ -3467,8 +3528,7 @@ size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H) {
 // (segment, pixel)) and, in the bit-reproducible mode, its own 16-float (entry, block) records (the depth layout's 10-float ones go unused)
 static size_t feat_wpart_offset(int P, int64_t R, int W, int H) { return csplat_backward_camera_scratch_bytes(P, R, W, H); }
 static size_t feat_det_offset(int P, int64_t R, int W, int H) {
-    const int tiles = cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE);
-    return feat_wpart_offset(P, R, W, H) + align256((size_t)max_slots(R, tiles) * 256 * 4);
+    return feat_wpart_offset(P, R, W, H) + align256((size_t)max_slots(R, tiles_of(W, H)) * 256 * 4);
 }
 static size_t feat_det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 16 * 4); }
 size_t csplat_backward_feature_scratch_bytes(int P, int64_t R, int W, int H) {
@@ -3478,9 +3538,20 @@ int csplat_geom_layout(int P, size_t *o8) { size_t off[G_NFIELDS]; geom_offsets(
 // every sub-buffer of the BINNING chunk (csplat.h: csplat_binning_fields): 0 keys 1 ids 2 seg_offset + blk_hi 3 slot_tile 4 checkpoints
 // 5 masks 6-8 records A / B / C 9 bbits 10 bmask; o11[11] = byte offsets for a chunk laid out for R list entries (diagnostics: tools/,
 // bench.py's count of K7's atomic requests)
-int csplat_binning_fields(int64_t R, int W, int H, size_t *o11) { binning_offsets(R, cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE), o11); return 0; }
-int csplat_binning_layout(int64_t R, int W, int H, size_t *o2) { size_t off[B_NFIELDS]; binning_offsets(R, cdiv(W, CSPLAT_TILE) * cdiv(H, CSPLAT_TILE), off); o2[0] = off[0]; o2[1] = off[1]; return 0; }
-int csplat_image_layout(int W, int H, size_t *o3) { size_t off[5]; image_offsets(W, H, off); o3[0] = off[0]; o3[1] = off[1]; o3[2] = off[2]; return 0; }
+static_assert(B_NFIELDS == 11 && B_KEYS == 0 && B_IDS == 1 && I_RANGES == 0 && I_NCONTRIB == 1 && I_FINALT == 2, "field numbers csplat.h documents");
+int csplat_binning_fields(int64_t R, int W, int H, size_t *o11) { binning_offsets(R, tiles_of(W, H), o11); return 0; }
+int csplat_binning_layout(int64_t R, int W, int H, size_t *o2) {
+    size_t off[B_NFIELDS];
+    binning_offsets(R, tiles_of(W, H), off);
+    o2[0] = off[B_KEYS]; o2[1] = off[B_IDS];
+    return 0;
+}
+int csplat_image_layout(int W, int H, size_t *o3) {
+    size_t off[I_NFIELDS];
+    image_offsets(W, H, off);
+    o3[0] = off[I_RANGES]; o3[1] = off[I_NCONTRIB]; o3[2] = off[I_FINALT];
+    return 0;
+}
 
 // ---- two-phase forward.  begin: K1 + the counting half of the binning, everything that does not need num_rendered;
 // finish: reads num_rendered (mailbox poll), allocates the R-sized chunks, K3..K6.  A caller with several independent
@@ -3536,8 +3607,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
     void *gbase = alloc(alloc_ctx, CSPLAT_CHUNK_GEOM, csplat_geom_bytes(P));
     void *ibase = alloc(alloc_ctx, CSPLAT_CHUNK_IMAGE, csplat_image_bytes(W, H));
     CSPLAT_REQUIRE(gbase && ibase, "allocator returned NULL");
-    size_t ioff[5];
-    image_offsets(W, H, ioff);
+    const ImageView im = image_view(ibase, W, H);
     const int tiles = cam.gx * cam.gy;
     const bool can_bucket = tiles <= BUCKET_TILES && !(g_debug_flags & 2u);
     uint32_t *table = nullptr;
@@ -3565,10 +3635,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
         t.mb_dev = g_mail.dev + slot * MAIL_WORDS;
     }
     t.cam = cam; t.g = geom_view(gbase, P); t.gbase = gbase; t.ibase = ibase;
-    t.ranges = (int2 *)((char *)ibase + ioff[0]);
-    t.n_contrib = (uint32_t *)((char *)ibase + ioff[1]);
-    t.final_T = (float *)((char *)ibase + ioff[2]);
-    t.info = (uint32_t *)((char *)ibase + ioff[3]);
+    t.ranges = im.ranges; t.n_contrib = im.n_contrib; t.final_T = im.final_T; t.info = im.info;
     t.table = table; t.bg = bg; t.radii = radii; t.alloc = alloc; t.alloc_ctx = alloc_ctx;
     t.D = D; t.M = M; t.means3D = means3D; t.shs = shs; t.colors_precomp = colors_precomp; t.opacities = opacities; t.scales = scales;
     t.scale_modifier = scale_modifier; t.rotations = rotations; t.cov3D_precomp = cov3D_precomp;
@@ -3623,7 +3690,7 @@ static int begin_launch(const FwdTicket &t) {
 static bool begin_views_compatible(int V, const int *tk) {
     // (V == 1 qualifies too since round 5: a camera-by-camera caller -- the reference's own loop, train_utils.py:259-272 -- then gets the
     //  speculative second phase as well instead of a blocking read of its counts per camera)
-    if (V < 1 || V > K1_MAX_VIEWS || (g_debug_flags & 512u)) return false;
+    if (V < 1 || V > RASTER_MAX_VIEWS || (g_debug_flags & 512u)) return false;
     const FwdTicket &a = g_tickets[tk[0]];
     if (a.P <= 0 || !a.can_bucket || !a.shs || a.colors_precomp || a.cov3D_precomp || !a.scales || !a.rotations) return false;
     for (int i = 1; i < V; i++) {
@@ -3752,8 +3819,8 @@ static std::mutex g_spec_mu;
 struct PendingViews {
     bool used = false;
     const csplat_view *key = nullptr;
-    int V = 0, tk[P2_MAX_VIEWS];
-    uint32_t Rcap[P2_MAX_VIEWS], Lcap = 0, Bcap = 0;
+    int V = 0, tk[RASTER_MAX_VIEWS];
+    uint32_t Rcap[RASTER_MAX_VIEWS], Lcap = 0, Bcap = 0;
 };
 constexpr int MAX_PENDING = 8;
 static PendingViews g_pending[MAX_PENDING];
@@ -3776,22 +3843,12 @@ static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, con
             void *bbase = t.alloc(t.alloc_ctx, CSPLAT_CHUNK_BINNING, csplat_binning_bytes(R, W, H));
             void *tbase = t.alloc(t.alloc_ctx, CSPLAT_CHUNK_TEMP, csplat_temp_bytes(P, R, W, H));
             CSPLAT_REQUIRE(bbase && tbase, "allocator returned NULL");
-            size_t boff[B_NFIELDS], toff[5];
-            binning_offsets(R, tiles, boff);
-            temp_offsets(R, toff);
+            const BinView b = binning_view(bbase, R, tiles);
             P2View &k = tab.v[i];
             k.g = t.g; k.cam = t.cam; k.radii = t.radii; k.table = t.table; k.ranges = t.ranges;
-            k.keys_u = (uint64_t *)((char *)tbase + toff[0]);
-            k.keys_sorted = (uint64_t *)((char *)bbase + boff[0]);
-            k.ids_sorted = (uint32_t *)((char *)bbase + boff[1]);
-            k.seg_offset = (int *)((char *)bbase + boff[2]);
-            k.slot_tile = (int *)((char *)bbase + boff[3]);
-            k.ckpt = (float4 *)((char *)bbase + boff[4]);
-            k.mask16 = (uint16_t *)((char *)bbase + boff[5]);
-            k.bbits = (unsigned long long *)((char *)bbase + boff[9]);
-            k.bmask = (unsigned long long *)((char *)bbase + boff[10]);
-            k.recA = (float4 *)((char *)bbase + boff[6]); k.recB = (float4 *)((char *)bbase + boff[7]);
-            k.recC = (float2 *)((char *)bbase + boff[8]);
+            k.keys_u = temp_view(tbase, R).keys_u;
+            k.keys_sorted = b.keys_sorted; k.ids_sorted = b.ids_sorted; k.seg_offset = b.seg_offset; k.slot_tile = b.slot_tile;
+            k.ckpt = b.ckpt; k.mask16 = b.mask16; k.bbits = b.bbits; k.bmask = b.bmask; k.recA = b.recA; k.recB = b.recB; k.recC = b.recC;
             k.bg = t.bg; k.final_T = t.final_T; k.n_contrib = t.n_contrib; k.out_color = v[i].out_color; k.out_depth = v[i].out_depth;
             k.R = R; k.info = t.info; k.Lcap = Lcap; k.Bcap = Bcap; k.spec = spec;
             v[i].layout_rendered = (int)R; v[i].geom = t.gbase; v[i].binning = bbase; v[i].image = t.ibase;
@@ -3842,7 +3899,7 @@ static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, con
 static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_t join, bool *done, int mode = 0,
                                 PendingViews *pend = nullptr, int *relaunched = nullptr) {
     *done = false;
-    if (V < 1 || V > P2_MAX_VIEWS || (g_debug_flags & 512u)) return 0;
+    if (V < 1 || V > RASTER_MAX_VIEWS || (g_debug_flags & 512u)) return 0;
     const FwdTicket &a = g_tickets[tk[0]];
     for (int i = 0; i < V; i++) {
         const FwdTicket &t = g_tickets[tk[i]];
@@ -3850,7 +3907,7 @@ static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_
     }
     const int P = a.P, W = a.W, H = a.H, tiles = a.tiles;
     const uint32_t cap = tile_sort_cap();
-    uint32_t info[P2_MAX_VIEWS][3];
+    uint32_t info[RASTER_MAX_VIEWS][3];
     bool have_info = false;
     auto read_counts = [&]() -> int {   // the one host read of the call: instances and longest tile list of every view
         for (int i = 0; i < V && !have_info; i++)
@@ -3891,7 +3948,7 @@ static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_
             }
     }
     if (mode == 2 || (!(g_debug_flags & 1024u) && hist.R > 0)) {
-        uint32_t Rcap[P2_MAX_VIEWS];
+        uint32_t Rcap[RASTER_MAX_VIEWS];
         uint32_t Lcap, Bcap;
         if (mode == 2) {        // the capacities the pending call was launched with
             for (int i = 0; i < V; i++) Rcap[i] = pend->Rcap[i];
@@ -3925,7 +3982,7 @@ static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_
         }
     }
     if (int rc = read_counts()) return rc;
-    uint32_t longest = 0, busiest = 0, Rex[P2_MAX_VIEWS];
+    uint32_t longest = 0, busiest = 0, Rex[RASTER_MAX_VIEWS];
     for (int i = 0; i < V; i++) {
         if (info[i][1] > cap || info[i][0] == 0) return 0;      // a list too long for the in-LDS sort, an empty view: view by view
         longest = info[i][1] > longest ? info[i][1] : longest;
@@ -3970,81 +4027,65 @@ int csplat_forward_finish(int ticket, float *out_color, float *out_depth, int *n
     *num_rendered = (int)R;
     void *bbase = alloc(alloc_ctx, CSPLAT_CHUNK_BINNING, csplat_binning_bytes(R, W, H));
     CSPLAT_REQUIRE(bbase, "allocator returned NULL");
-    size_t boff[B_NFIELDS];
-    binning_offsets(R, tiles, boff);
-    uint64_t *keys_sorted = (uint64_t *)((char *)bbase + boff[0]);
-    uint32_t *ids_sorted = (uint32_t *)((char *)bbase + boff[1]);
-    int *seg_offset = (int *)((char *)bbase + boff[2]);
-    int *slot_tile = (int *)((char *)bbase + boff[3]);
-    float4 *ckpt = (float4 *)((char *)bbase + boff[4]);
-    uint16_t *mask16 = (uint16_t *)((char *)bbase + boff[5]);
-    float4 *recA = (float4 *)((char *)bbase + boff[6]), *recB = (float4 *)((char *)bbase + boff[7]);
-    float2 *recC = (float2 *)((char *)bbase + boff[8]);
-    unsigned long long *bbits = (unsigned long long *)((char *)bbase + boff[9]);
-    unsigned long long *bmask = (unsigned long long *)((char *)bbase + boff[10]);
+    const BinView b = binning_view(bbase, R, tiles);
     if (R > 0) {
         void *tbase = alloc(alloc_ctx, CSPLAT_CHUNK_TEMP, csplat_temp_bytes(P, R, W, H));
         CSPLAT_REQUIRE(tbase, "allocator returned NULL");
-        size_t toff[5];
-        temp_offsets(R, toff);
-        uint64_t *keys_u = (uint64_t *)((char *)tbase + toff[0]);
+        const TempView tmp = temp_view(tbase, R);
         if (bucketed) {
             {
                 ProfScope ps(PROF_K3, s);
-                k_emit_bucket<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, g.xy, g.depth, radii, cam, table, ranges, keys_u);
+                k_emit_bucket<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, g.xy, g.depth, radii, cam, table, ranges, tmp.keys_u);
                 LAUNCH_CHECK();
             }
             const size_t lds = tsort_lds_bytes((int)host_info[1]);
             ProfScope ps(PROF_K4, s);
-            k_tile_sort<<<tiles < TSORT_GRID ? tiles : TSORT_GRID, TSORT_THREADS, lds, s>>>(ranges, keys_u, keys_sorted, ids_sorted, t.info, tsort_mode(P));
+            k_tile_sort<<<tiles < TSORT_GRID ? tiles : TSORT_GRID, TSORT_THREADS, lds, s>>>(ranges, tmp.keys_u, b.keys_sorted, b.ids_sorted, t.info, tsort_mode(P));
             LAUNCH_CHECK();
         } else {
             // a tile list longer than the LDS sort takes: the global stable radix sort (upstream's pipeline shape)
-            uint32_t *ids_u = (uint32_t *)((char *)tbase + toff[1]);
-            uint64_t *keys_t = (uint64_t *)((char *)tbase + toff[2]);
-            uint32_t *ids_t = (uint32_t *)((char *)tbase + toff[3]);
-            void *stab = (char *)tbase + toff[4];
             if (can_bucket) {   // (the bucket path was attempted: the P-scan has not run yet)
                 ProfScope ps(PROF_K2, s);
                 if (int rc = csplat_inclusive_scan_u32(s, g.tiles_touched, g.offsets, P, g.scan_tmp)) return rc;
             }
             {
                 ProfScope ps(PROF_K3, s);
-                k_emit_keys<<<cdiv(P, 256), 256, 0, s>>>(P, g.xy, g.depth, g.offsets, radii, cam, keys_u, ids_u);
+                k_emit_keys<<<cdiv(P, 256), 256, 0, s>>>(P, g.xy, g.depth, g.offsets, radii, cam, tmp.keys_u, tmp.ids_u);
                 LAUNCH_CHECK();
             }
             const int end_bit = 32 + higher_msb((uint32_t)tiles);
             {
                 ProfScope ps(PROF_K4, s);
-                if (int rc = csplat_sort_pairs(s, keys_u, ids_u, keys_sorted, ids_sorted, keys_t, ids_t, R, end_bit, stab)) return rc;
+                if (int rc = csplat_sort_pairs(s, tmp.keys_u, tmp.ids_u, b.keys_sorted, b.ids_sorted, tmp.keys_t, tmp.ids_t, R, end_bit, tmp.sort_tmp))
+                    return rc;
             }
             {
                 ProfScope ps(PROF_K5, s);
                 HIP_TRY(hipMemsetAsync(ranges, 0, (size_t)tiles * 8, s));
-                k_tile_ranges<<<cdiv(R, 256), 256, 0, s>>>(R, keys_sorted, ranges);
+                k_tile_ranges<<<cdiv(R, 256), 256, 0, s>>>(R, b.keys_sorted, ranges);
                 LAUNCH_CHECK();
             }
         }
     }
     {
         ProfScope ps(PROF_K5, s);
-        k_seg_plan<<<1, 1024, 0, s>>>(tiles, ranges, seg_offset, slot_tile);
+        k_seg_plan<<<1, 1024, 0, s>>>(tiles, ranges, b.seg_offset, b.slot_tile);
         LAUNCH_CHECK();
     }
     {
         ProfScope ps(PROF_K5, s);
-        k_block_masks<<<cdiv((int64_t)R + 1, 256), 256, 0, s>>>((int64_t)R, cam.gx, keys_sorted, ids_sorted, g.pack, mask16, recA, recB, recC,
-                                                                 (g_debug_flags & (1u | 16u | 32u)) ? 0 : 1, bmask);
+        k_block_masks<<<cdiv((int64_t)R + 1, 256), 256, 0, s>>>((int64_t)R, cam.gx, b.keys_sorted, b.ids_sorted, g.pack, b.mask16, b.recA, b.recB,
+                                                                 b.recC, (g_debug_flags & (1u | 16u | 32u)) ? 0 : 1, b.bmask);
         LAUNCH_CHECK();
     }
     {
         ProfScope ps(PROF_K6, s);
         if (g_debug_flags & 32768u)       // (bit 15: the row form, four survivors a step; default: the survivor-column form, 74 -> 67 us alone)
-            k_composite_fwd<true><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, mask16, recA, recB, recC, R, bg, seg_offset, ckpt,
-                                                                      final_T, n_contrib, out_color, out_depth, bbits, bmask);
+            k_composite_fwd<true><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, bg, b.seg_offset,
+                                                                      b.ckpt, final_T, n_contrib, out_color, out_depth, b.bbits, b.bmask);
         else
-            k_composite_fwd<false><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, mask16, recA, recB, recC, R, bg, seg_offset, ckpt,
-                                                                       final_T, n_contrib, out_color, out_depth, bbits, bmask);
+            k_composite_fwd<false><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, bg, b.seg_offset,
+                                                                       b.ckpt, final_T, n_contrib, out_color, out_depth, b.bbits, b.bmask);
         LAUNCH_CHECK();
     }
     *geom_out = gbase; *binning_out = bbase; *image_out = ibase;
@@ -4065,141 +4106,116 @@ int csplat_forward(void *stream, int P, int D, int M, const float *bg, int W, in
     return csplat_forward_finish(ticket, out_color, out_depth, num_rendered, geom_out, binning_out, image_out);
 }
 
-// K7 on `stream`; K8 on `k8_stream` (after an event wait when it differs); accmask see k_preprocess_bwd
-static int backward_impl(hipStream_t s, hipStream_t k8s, bool with_k7, bool with_k8, unsigned accmask, int P, int D, int M, int R, const float *bg, int W, int H,
-                         const float *means3D, const float *shs, const float *scales, float scale_modifier,
-                         const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
-                         const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
-                         const void *binning, const void *image, const float *out_color, const float *dL_dpix, void *scratch,
-                         float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, bool depth_k8 = false,
-                         float *cam_slab = nullptr, int *cam_rows = nullptr, const float *aa_opacities = nullptr) {
-    CSPLAT_REQUIRE(geom && binning && image && out_color, "csplat_backward: missing saved state");
-    CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
-    CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward: scratch (csplat_backward_scratch_bytes) missing");
-    if (P <= 0) return 0;
+// antialiasing (csplat_view.prefiltered & CSPLAT_ANTIALIAS): K1 stored o' = o h; K8 takes its AA variant and reads the raw opacities
+static bool aa_of(const csplat_view &w) { return (w.prefiltered & CSPLAT_ANTIALIAS) != 0; }
+
+// The single-view K8 of `w` on `k8s`: one of k_preprocess_bwd / _depth / _cam<DEPTH> / _aa<DEPTH, CAM>, each with the SH rows staged in
+// LDS (128 threads) or not (256).  depth: record slot 9 -> dL/dmean3D (csplat_view.dL_ddepth); cam_slab != NULL: the camera-gradient
+// form, one slab row per workgroup, summed by k_cam_sum (*cam_rows = the number of rows); an antialiased view takes the AA variant of
+// whichever form the call takes.
+static int launch_k8(hipStream_t k8s, const csplat_view &w, bool depth, float *cam_slab, int *cam_rows) {
+    ProfScope ps(cam_slab ? PROF_K8_CAM : depth ? PROF_K8_DEPTH : PROF_K8, k8s);
+    const bool stage = w.shs != nullptr && w.dL_dsh != nullptr && w.M == 16 && (((uintptr_t)w.shs | (uintptr_t)w.dL_dsh) & 15u) == 0;
+    CSPLAT_REQUIRE(stage || !(w.accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
     Cam cam;
-    make_cam(cam, view, proj, campos, tanfovx, tanfovy, W, H);
-    Geom g = geom_view((void *)geom, P);
-    const int tiles = cam.gx * cam.gy;
-    size_t ioff[5], boff[B_NFIELDS];
-    image_offsets(W, H, ioff);
-    binning_offsets(R, tiles, boff);
-    const int2 *ranges = (const int2 *)((const char *)image + ioff[0]);
-    const uint32_t *n_contrib = (const uint32_t *)((const char *)image + ioff[1]);
-    const float *final_T = (const float *)((const char *)image + ioff[2]);
-    const uint32_t *ids_sorted = (const uint32_t *)((const char *)binning + boff[1]);
-    const int *seg_offset = (const int *)((const char *)binning + boff[2]);
-    const int *slot_tile = (const int *)((const char *)binning + boff[3]);
-    const float4 *ckpt = (const float4 *)((const char *)binning + boff[4]);
-    const uint64_t *keys_sorted = (const uint64_t *)((const char *)binning + boff[0]);
-    const unsigned long long *bbits = (const unsigned long long *)((const char *)binning + boff[9]);
-    const float4 *recA = (const float4 *)((const char *)binning + boff[6]), *recB = (const float4 *)((const char *)binning + boff[7]);
-    const float2 *recC = (const float2 *)((const char *)binning + boff[8]);
-    float *acc = (float *)scratch;
-    // (with_k7 = false: K7 of all views was launched as one batch by the caller)
-    const bool det_mode = (g_debug_flags & 256u) != 0;
-    float *det = det_mode ? (float *)((char *)scratch + align256((size_t)P * ACC_STRIDE * 4)) : nullptr;
-    if (with_k7 && det_mode) HIP_TRY(hipMemsetAsync(det, 0, (size_t)(R > 0 ? R : 1) * 16 * 9 * 4, s));
-    else if (with_k7 && !(accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(acc, 0, (size_t)P * ACC_STRIDE * 4, s));
+    make_cam(cam, w);
+    const Geom g = geom_view(w.geom, w.P);
+    auto form = [&](auto staged) {
+        constexpr bool STAGE = decltype(staged)::value;
+        constexpr int NT = STAGE ? 128 : 256;
+        const int grid = cdiv(w.P, NT);
+        auto go = [&](auto kernel, auto... extra) {
+            kernel<<<grid, NT, 0, k8s>>>(w.P, w.D, w.M, w.means3D, w.shs, w.scales, w.scale_modifier, w.rotations, w.cov3D_precomp != nullptr, cam,
+                                         g, w.radii, (const float *)w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity, w.dL_dcolor,
+                                         w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, w.accmask, extra...);
+        };
+        if (aa_of(w)) {
+            if (cam_slab && depth) go(k_preprocess_bwd_aa<STAGE, NT, true, true>, cam_slab, w.opacities);
+            else if (cam_slab) go(k_preprocess_bwd_aa<STAGE, NT, false, true>, cam_slab, w.opacities);
+            else if (depth) go(k_preprocess_bwd_aa<STAGE, NT, true, false>, cam_slab, w.opacities);
+            else go(k_preprocess_bwd_aa<STAGE, NT, false, false>, cam_slab, w.opacities);
+        } else if (cam_slab) {
+            if (depth) go(k_preprocess_bwd_cam<STAGE, NT, true>, cam_slab);
+            else go(k_preprocess_bwd_cam<STAGE, NT, false>, cam_slab);
+        } else if (depth) {
+            go(k_preprocess_bwd_depth<STAGE, NT>);
+        } else {
+            go(k_preprocess_bwd<STAGE, NT>);
+        }
+        if (cam_slab && cam_rows) *cam_rows = grid;
+    };
+    if (stage) form(std::true_type{});
+    else form(std::false_type{});
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// One view's backward: K7 on `s` (with_k7; false = the caller launched K7 of all views as one batch), K8 on `k8s` (with_k8; after an
+// event wait when the streams differ; false = the caller runs one K8 over all views afterwards).  accmask see k_preprocess_bwd.
+static int backward_impl(const csplat_view &w, hipStream_t s, hipStream_t k8s, bool with_k7, bool with_k8, bool depth_k8 = false,
+                         float *cam_slab = nullptr, int *cam_rows = nullptr) {
+    CSPLAT_REQUIRE(w.geom && w.binning && w.image && w.out_color, "csplat_backward: missing saved state");
+    CSPLAT_REQUIRE(w.dL_dmean2D && w.dL_dconic && w.dL_dopacity && w.dL_dcolor && w.dL_dmean3D && w.dL_dcov3D, "missing gradient outputs");
+    CSPLAT_REQUIRE(w.scratch != nullptr, "csplat_backward: scratch (csplat_backward_scratch_bytes) missing");
+    const int P = w.P, R = layout_R(w), tiles = tiles_of(w.W, w.H);
+    if (P <= 0) return 0;
     if (with_k7) {
+        const bool det_mode = (g_debug_flags & 256u) != 0;
+        const BinView b = binning_view(w.binning, R, tiles);
+        B2View k;
+        fill_b2_view(w, b, image_view(w.image, w.W, w.H), det_mode ? (float *)((char *)w.scratch + acc_bytes(P)) : nullptr, k);
+        if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, (size_t)(R > 0 ? R : 1) * 16 * 9 * 4, s));
+        else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(k.acc, 0, (size_t)P * ACC_STRIDE * 4, s));
         ProfScope ps(PROF_K7, s);
         if (R > 0) {
             const unsigned grid = (unsigned)cdiv(max_slots(R, tiles), 8) * 32u;
-            if (det_mode)
-                k_composite_bwd_rows<true><<<grid, 256, 0, s>>>(tiles, W, H, cam.gx, ranges, ids_sorted, bbits, recA, recB, recC, (uint32_t)R,
-                                                                seg_offset, slot_tile, ckpt, final_T, n_contrib, out_color, dL_dpix, acc, det);
-            else
-                k_composite_bwd_rows<false><<<grid, 256, 0, s>>>(tiles, W, H, cam.gx, ranges, ids_sorted, bbits, recA, recB, recC, (uint32_t)R,
-                                                                 seg_offset, slot_tile, ckpt, final_T, n_contrib, out_color, dL_dpix, acc, det);
+            auto go = [&](auto kernel) {
+                kernel<<<grid, 256, 0, s>>>(tiles, w.W, w.H, cdiv(w.W, CSPLAT_TILE), k.ranges, k.ids_sorted, k.bbits, k.recA, k.recB, k.recC, k.R,
+                                            k.seg_offset, k.slot_tile, k.ckpt, k.final_T, k.n_contrib, k.out_color, k.dL_dpix, k.acc, k.det);
+            };
+            if (det_mode) go(k_composite_bwd_rows<true>);
+            else go(k_composite_bwd_rows<false>);
             LAUNCH_CHECK();
         }
         if (det_mode) {   // fixed-order sum of every Gaussian's instance records (writes all of acc)
-            k_det_reduce<<<cdiv(P, 256), 256, 0, s>>>(P, cam, g.xy, g.depth, radii, ranges, keys_sorted, ids_sorted, det, acc);
+            DetView e;
+            fill_det_view(w, b, k, e);
+            k_det_reduce<<<cdiv(P, 256), 256, 0, s>>>(P, e.cam, e.xy, e.depth, e.radii, e.ranges, e.keys_sorted, e.ids_sorted, e.det, e.acc);
             LAUNCH_CHECK();
         }
     }
-    if (!with_k8) return 0;   // (csplat_backward_views runs one K8 over all views afterwards)
+    if (!with_k8) return 0;
     if (with_k7 && k8s != s) {
         hipEvent_t ev = pooled_event();
         CSPLAT_REQUIRE(ev != nullptr, "csplat_backward_views: no event");
         HIP_TRY(hipEventRecord(ev, s));
         HIP_TRY(hipStreamWaitEvent(k8s, ev, 0));
     }
-    if (aa_opacities) {  // (antialiasing: the AA variant of whichever K8 the call takes -- default, DEPTH, CAM)
-        ProfScope ps(cam_slab ? PROF_K8_CAM : depth_k8 ? PROF_K8_DEPTH : PROF_K8, k8s);
-        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
-        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
-        const int nt = stage ? 128 : 256, grid = cdiv(P, nt);
-#define CSPLAT_K8_AA_LAUNCH(ST, NT_, DP, CM)                                                                                               \
-    k_preprocess_bwd_aa<ST, NT_, DP, CM><<<grid, NT_, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,                \
-                                                                cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D, dL_dconic,    \
-                                                                dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,       \
-                                                                dL_drot, accmask, cam_slab, aa_opacities)
-#define CSPLAT_K8_AA_STAGE(DP, CM) do { if (stage) CSPLAT_K8_AA_LAUNCH(true, 128, DP, CM); else CSPLAT_K8_AA_LAUNCH(false, 256, DP, CM); } while (0)
-        if (cam_slab && depth_k8) CSPLAT_K8_AA_STAGE(true, true);
-        else if (cam_slab) CSPLAT_K8_AA_STAGE(false, true);
-        else if (depth_k8) CSPLAT_K8_AA_STAGE(true, false);
-        else CSPLAT_K8_AA_STAGE(false, false);
-#undef CSPLAT_K8_AA_STAGE
-#undef CSPLAT_K8_AA_LAUNCH
-        LAUNCH_CHECK();
-        if (cam_slab && cam_rows) *cam_rows = grid;
-        return 0;
-    }
-    if (cam_slab) {      // (the camera-gradient path: one slab row per workgroup, summed by k_cam_sum; *cam_rows = the number of rows)
-        ProfScope ps(PROF_K8_CAM, k8s);
-        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
-        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
-        const int nt = stage ? 128 : 256, grid = cdiv(P, nt);
-#define CSPLAT_K8_CAM_LAUNCH(ST, NT_, DP)                                                                                                  \
-    k_preprocess_bwd_cam<ST, NT_, DP><<<grid, NT_, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,                   \
-                                                             cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D, dL_dconic,       \
-                                                             dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, \
-                                                             accmask, cam_slab)
-        if (stage && depth_k8) CSPLAT_K8_CAM_LAUNCH(true, 128, true);
-        else if (stage) CSPLAT_K8_CAM_LAUNCH(true, 128, false);
-        else if (depth_k8) CSPLAT_K8_CAM_LAUNCH(false, 256, true);
-        else CSPLAT_K8_CAM_LAUNCH(false, 256, false);
-#undef CSPLAT_K8_CAM_LAUNCH
-        LAUNCH_CHECK();
-        if (cam_rows) *cam_rows = grid;
-        return 0;
-    }
-    if (depth_k8) {      // (the depth-gradient path: csplat_view.dL_ddepth; record slot 9 -> dL/dmean3D)
-        ProfScope ps(PROF_K8_DEPTH, k8s);
-        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
-        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
-        if (stage)
-            k_preprocess_bwd_depth<true, 128><<<cdiv(P, 128), 128, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,
-                                                                              cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D,
-                                                                              dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
-                                                                              dL_dsh, dL_dscale, dL_drot, accmask);
-        else
-            k_preprocess_bwd_depth<false, 256><<<cdiv(P, 256), 256, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,
-                                                                               cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D,
-                                                                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
-                                                                               dL_dsh, dL_dscale, dL_drot, accmask);
-        LAUNCH_CHECK();
-        return 0;
-    }
-    {
-        ProfScope ps(PROF_K8, k8s);
-        const bool stage = shs != nullptr && dL_dsh != nullptr && M == 16 && (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0;
-        CSPLAT_REQUIRE(stage || !(accmask & CSPLAT_ACC_SH), "accumulating dL_dsh needs M == 16 and 16-byte aligned buffers");
-        if (stage)
-            k_preprocess_bwd<true, 128><<<cdiv(P, 128), 128, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,
-                                                                        cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D,
-                                                                        dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
-                                                                        dL_dsh, dL_dscale, dL_drot, accmask);
-        else
-            k_preprocess_bwd<false, 256><<<cdiv(P, 256), 256, 0, k8s>>>(P, D, M, means3D, shs, scales, scale_modifier, rotations,
-                                                                         cov3D_precomp != nullptr, cam, g, radii, acc, dL_dmean2D,
-                                                                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
-                                                                         dL_dsh, dL_dscale, dL_drot, accmask);
-        LAUNCH_CHECK();
-    }
-    return 0;
+    return launch_k8(k8s, w, depth_k8, cam_slab, cam_rows);
+}
+
+// the arguments of the single-view C entry points as a csplat_view (everything else zero: no accumulation, no antialiasing, no extras)
+static csplat_view pack_view(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
+                             const float *colors_precomp, const float *scales, float scale_modifier, const float *rotations,
+                             const float *cov3D_precomp, const float *view, const float *proj, const float *campos, float tanfovx,
+                             float tanfovy, const int32_t *radii, const void *geom, const void *binning, const void *image,
+                             const float *out_color, const float *dL_dpix, void *scratch, float *dL_dmean2D, float *dL_dconic,
+                             float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
+                             float *dL_drot) {
+    csplat_view w;
+    memset(&w, 0, sizeof(w));
+    w.stream = stream;
+    w.P = P; w.D = D; w.M = M; w.W = W; w.H = H;
+    w.scale_modifier = scale_modifier; w.tanfovx = tanfovx; w.tanfovy = tanfovy;
+    w.bg = bg; w.means3D = means3D; w.shs = shs; w.colors_precomp = colors_precomp; w.scales = scales; w.rotations = rotations;
+    w.cov3D_precomp = cov3D_precomp; w.view = view; w.proj = proj; w.campos = campos;
+    w.out_color = const_cast<float *>(out_color); w.radii = const_cast<int32_t *>(radii);
+    w.num_rendered = R; w.layout_rendered = R;
+    w.geom = const_cast<void *>(geom); w.binning = const_cast<void *>(binning); w.image = const_cast<void *>(image);
+    w.dL_dpix = dL_dpix; w.scratch = scratch;
+    w.dL_dmean2D = dL_dmean2D; w.dL_dconic = dL_dconic; w.dL_dopacity = dL_dopacity; w.dL_dcolor = dL_dcolor; w.dL_dmean3D = dL_dmean3D;
+    w.dL_dcov3D = dL_dcov3D; w.dL_dsh = dL_dsh; w.dL_dscale = dL_dscale; w.dL_drot = dL_drot;
+    return w;
 }
 
 int csplat_backward(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -4210,11 +4226,10 @@ int csplat_backward(void *stream, int P, int D, int M, int R, const float *bg, i
                     float *dL_dmean2D,
                     float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
                     float *dL_dsh, float *dL_dscale, float *dL_drot) {
-    (void)colors_precomp;
-    return backward_impl((hipStream_t)stream, (hipStream_t)stream, true, true, 0u, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier,
-                         rotations, cov3D_precomp, view, proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color,
-                         dL_dpix, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                         dL_drot);
+    const csplat_view w = pack_view(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                    view, proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, scratch, dL_dmean2D,
+                                    dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+    return backward_impl(w, (hipStream_t)stream, (hipStream_t)stream, true, true);
 }
 
 // ---- batched entry points: V independent views, one stream each, fenced against `join_stream`
@@ -4318,9 +4333,10 @@ static int forward_views_impl(int V, csplat_view *v, csplat_alloc_fn alloc, void
 // ABI 9: the feature / alpha images of a finished forward (csplat_view.out_features / out_alpha), on the join stream behind every view's
 // K6.  Nothing is launched when no view asks for them.  One launch per group of views (view_group): a call of up to 8 views is one launch.
 static bool feat_out_wanted(const csplat_view &w) { return w.out_features || w.out_alpha; }
-// The per-view tables of the extended paths hold B2_MAX_VIEWS views: a call of more views runs in ceil(V / 8) groups of as equal a size as
+// The per-view tables of the extended paths hold RASTER_MAX_VIEWS views: a call of more views runs in ceil(V / 8) groups of as equal a size as
 // possible, one after the other on the join stream, in view order.  Group g is views [lo, hi); a call of up to 8 views is one group.
-static int view_groups(int V) { return V > B2_MAX_VIEWS ? cdiv(V, B2_MAX_VIEWS) : 1; }
+static int view_groups(int V) { return V > RASTER_MAX_VIEWS ? cdiv(V, RASTER_MAX_VIEWS) : 1; }
+static_assert(RASTER_MAX_VIEWS == 8, "csplat.h and the CSPLAT_REQUIRE texts of the grouped paths promise groups of at most 8 views");
 static void view_group(int V, int g, int *lo, int *hi) {
     const int ng = view_groups(V);
     *lo = (int)((int64_t)V * g / ng);
@@ -4330,7 +4346,7 @@ static int feature_forward_group(int V, csplat_view *v, hipStream_t join) {
     bool any = false;
     for (int i = 0; i < V; i++) any = any || feat_out_wanted(v[i]);
     if (!any) return 0;
-    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_forward_views: feature / alpha images are rendered for at most 8 views per launch");
+    CSPLAT_REQUIRE(V <= RASTER_MAX_VIEWS, "csplat_forward_views: feature / alpha images are rendered for at most 8 views per launch");
     FeatFwdTable t;
     memset(&t, 0, sizeof(t));
     int maxtiles = 0;
@@ -4342,21 +4358,16 @@ static int feature_forward_group(int V, csplat_view *v, hipStream_t join) {
                        "csplat_forward_views: n_features must be 0..6, with features set exactly when it is not 0");
         CSPLAT_REQUIRE(!w.out_features || w.n_features > 0, "csplat_forward_views: out_features without features");
         FeatFwdView &f = t.v[i];
-        const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
+        const int gx = cdiv(w.W, CSPLAT_TILE), tiles = tiles_of(w.W, w.H);
         f.W = w.W; f.H = w.H; f.gx = gx; f.nf = w.n_features; f.features = w.features;
         f.out_features = w.out_features; f.out_alpha = w.out_alpha;
         if (!feat_out_wanted(w)) continue;
         maxtiles = tiles > maxtiles ? tiles : maxtiles;
         if (w.P <= 0 || w.num_rendered <= 0) continue;       // (no list entry: feat = 0, alpha = 0)
         CSPLAT_REQUIRE(w.image && w.binning, "csplat_forward_views: missing chunks");
-        const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
-        size_t ioff[5], boff[B_NFIELDS];
-        image_offsets(w.W, w.H, ioff);
-        binning_offsets(Rl, tiles, boff);
-        const char *b = (const char *)w.binning, *im = (const char *)w.image;
-        f.ranges = (const int2 *)(im + ioff[0]); f.n_contrib = (const uint32_t *)(im + ioff[1]); f.final_T = (const float *)(im + ioff[2]);
-        f.ids_sorted = (const uint32_t *)(b + boff[1]); f.seg_offset = (const int *)(b + boff[2]); f.ckpt = (const float4 *)(b + boff[4]);
-        f.recA = (const float4 *)(b + boff[6]); f.recB = (const float4 *)(b + boff[7]); f.bbits = (const unsigned long long *)(b + boff[9]);
+        const ImageView im = image_view(w.image, w.W, w.H);
+        fill_list_view(binning_view(w.binning, layout_R(w), tiles), im, f);
+        f.final_T = im.final_T;
         f.tiles = tiles;
     }
     if (maxtiles == 0) return 0;
@@ -4400,7 +4411,7 @@ static int visibility_views_group(int V, const csplat_view *v, const csplat_visi
         CSPLAT_REQUIRE(w.num_rendered >= 0, "csplat_visibility_views: the view's forward is still pending (settle it first)");
         CSPLAT_REQUIRE(w.valid == nullptr, "csplat_visibility_views: views launched on faith have no visibility pass");
         CSPLAT_REQUIRE(w.P >= 0 && w.W > 0 && w.H > 0, "csplat_visibility_views: bad view size");
-        const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
+        const int gx = cdiv(w.W, CSPLAT_TILE), tiles = tiles_of(w.W, w.H);
         const bool lists = w.P > 0 && w.num_rendered > 0;
         CSPLAT_REQUIRE(!lists || (w.geom && w.binning && w.image), "csplat_visibility_views: missing chunks");
         CSPLAT_REQUIRE(!lists || !per_g || o.scratch, "csplat_visibility_views: per-Gaussian outputs need the scratch");
@@ -4413,21 +4424,15 @@ static int visibility_views_group(int V, const csplat_view *v, const csplat_visi
         maxtiles = tiles > maxtiles ? tiles : maxtiles;      // (the walk also writes top_id = -1 of a view without list entries)
         maxP = g.P > maxP ? g.P : maxP;
         if (!lists) continue;
-        const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
-        size_t ioff[5], boff[B_NFIELDS];
-        image_offsets(w.W, w.H, ioff);
-        binning_offsets(Rl, tiles, boff);
-        const char *b = (const char *)w.binning, *im = (const char *)w.image;
-        f.ranges = (const int2 *)(im + ioff[0]); f.n_contrib = (const uint32_t *)(im + ioff[1]);
-        f.ids_sorted = (const uint32_t *)(b + boff[1]); f.seg_offset = (const int *)(b + boff[2]); f.ckpt = (const float4 *)(b + boff[4]);
-        f.recA = (const float4 *)(b + boff[6]); f.recB = (const float4 *)(b + boff[7]); f.bbits = (const unsigned long long *)(b + boff[9]);
+        const BinView b = binning_view(w.binning, layout_R(w), tiles);
+        fill_list_view(b, image_view(w.image, w.W, w.H), f);
         f.tiles = tiles;
         if (per_g) {
-            const size_t a = align256((size_t)Rl * 4 + 4);
+            const size_t a = align256((size_t)layout_R(w) * 4 + 4);
             f.rec_max = (float *)o.scratch; f.rec_sum = (float *)((char *)o.scratch + a); f.rec_cnt = (int32_t *)((char *)o.scratch + 2 * a);
-            make_cam(g.cam, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H);
-            const Geom gm = geom_view((void *)w.geom, w.P);
-            g.xy = gm.xy; g.depth = gm.depth; g.ranges = f.ranges; g.keys_sorted = (const uint64_t *)(b + boff[0]); g.ids_sorted = f.ids_sorted;
+            make_cam(g.cam, w);
+            const Geom gm = geom_view(w.geom, w.P);
+            g.xy = gm.xy; g.depth = gm.depth; g.ranges = f.ranges; g.keys_sorted = b.keys_sorted; g.ids_sorted = f.ids_sorted;
             g.rec_max = f.rec_max; g.rec_sum = f.rec_sum; g.rec_cnt = f.rec_cnt; g.tiles = tiles;
         }
     }
@@ -4457,13 +4462,13 @@ int csplat_visibility_views(int V, const csplat_view *v, const csplat_visibility
 // here waits for the GPU or reads from it: the call can be recorded into a hipGraph (stream capture) and replayed.  The views must
 // qualify for the one-launch-per-stage path (2..8 views sharing P, SH, opacities, scales and the image size), else an error.
 int csplat_forward_views_faith(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream, const uint32_t *caps, uint32_t *valid) {
-    CSPLAT_REQUIRE(V >= 2 && V <= P2_MAX_VIEWS && v != nullptr && caps != nullptr && valid != nullptr, "csplat_forward_views_faith: bad arguments");
+    CSPLAT_REQUIRE(V >= 2 && V <= RASTER_MAX_VIEWS && v != nullptr && caps != nullptr && valid != nullptr, "csplat_forward_views_faith: bad arguments");
     for (int i = 0; i < V; i++)
         CSPLAT_REQUIRE(!feat_out_wanted(v[i]), "csplat_forward_views_faith: views launched on faith render no feature or alpha image");
     CSPLAT_REQUIRE(caps[0] > 0 && caps[0] <= 0x7FFFFF00u && caps[1] > 0 && caps[1] <= tile_sort_cap() && caps[2] > 0,
                    "csplat_forward_views_faith: capacities out of range");
     hipStream_t join = (hipStream_t)join_stream;
-    int tickets[P2_MAX_VIEWS];
+    int tickets[RASTER_MAX_VIEWS];
     int rc = 0, begun = 0;
     for (; begun < V; begun++) {
         csplat_view &w = v[begun];
@@ -4482,7 +4487,7 @@ int csplat_forward_views_faith(int V, csplat_view *v, csplat_alloc_fn alloc, voi
     }
     if (rc == 0) rc = begin_launch_views(V, tickets, join);
     if (rc == 0) {
-        uint32_t Rcap[P2_MAX_VIEWS];
+        uint32_t Rcap[RASTER_MAX_VIEWS];
         for (int i = 0; i < V; i++) Rcap[i] = caps[0];
         const uint32_t tiles = (uint32_t)g_tickets[tickets[0]].tiles;
         rc = p2_launch(V, tickets, v, join, Rcap, caps[1], 1, caps[2] > tiles ? tiles : caps[2], valid);
@@ -4493,7 +4498,7 @@ int csplat_forward_views_faith(int V, csplat_view *v, csplat_alloc_fn alloc, voi
 }
 // byte offset, inside the IMAGE chunk, of the three counts a view's first phase leaves (u32: tile instances, longest tile list, non-empty
 // tiles) -- what a caller that launched on faith reads, at a time of its choosing, to size the next launch
-size_t csplat_image_info_offset(int W, int H) { size_t off[5]; image_offsets(W, H, off); return off[3]; }
+size_t csplat_image_info_offset(int W, int H) { size_t off[I_NFIELDS]; image_offsets(W, H, off); return off[I_INFO]; }
 
 // csplat_forward_views with the one host read DEFERRED.  When the second phase can be launched speculatively (capacities from the
 // previous call of the same shape) the call returns right behind that launch with *pending = 1: views[i].layout_rendered is the capacity,
@@ -4542,15 +4547,11 @@ static int forward_views_settle_impl(int V, csplat_view *v, void *join_stream, i
     return finish_views_one_by_one(V, v, pend.tk, V, join, rc == 0, rc);
 }
 
-// antialiasing (csplat_view.prefiltered & CSPLAT_ANTIALIAS): K1 stored o' = o h; K8 takes its AA variant and reads the raw opacities
-static bool aa_of(const csplat_view &w) { return (w.prefiltered & CSPLAT_ANTIALIAS) != 0; }
-static const float *aa_opacities_of(const csplat_view &w) { return aa_of(w) ? w.opacities : nullptr; }
-
 // Can ONE K8 serve all views?  Same Gaussians (P, D, M, scale modifier, SH and scale tensors), SH staging applicable, and every
 // gradient output either the SAME buffer in all views (then views after the first must have been asked to add into it) or
 // a DIFFERENT buffer in every view.  Fills the table and returns true; anything else keeps the per-view launches.
 static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
-    if (V < 2 || V > K8_MAX_VIEWS || (g_debug_flags & 128u)) return false;
+    if (V < 2 || V > RASTER_MAX_VIEWS || (g_debug_flags & 128u)) return false;
     const csplat_view &a = v[0];
     if (a.P <= 0 || a.cov3D_precomp || !a.shs || !a.dL_dsh || a.M != 16 || !a.scales || !a.rotations || !a.dL_dscale || !a.dL_drot ||
         ((((uintptr_t)a.shs | (uintptr_t)a.dL_dsh) & 15u) != 0))
@@ -4596,8 +4597,8 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
             !w.means3D || !w.radii)
             return false;
         K8View &k = tab.v[i];
-        make_cam(k.cam, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H);
-        k.g = geom_view((void *)w.geom, w.P);
+        make_cam(k.cam, w);
+        k.g = geom_view(w.geom, w.P);
         k.radii = w.radii; k.acc = (const float *)w.scratch; k.means3D = w.means3D; k.rotations = w.rotations;
         k.dL_dmean2D = w.dL_dmean2D; k.dL_dconic = w.dL_dconic; k.dL_dopacity = w.dL_dopacity; k.dL_dcolor = w.dL_dcolor;
         k.dL_dmean3D = w.dL_dmean3D; k.dL_dcov3D = w.dL_dcov3D; k.dL_dscale = w.dL_dscale; k.dL_drot = w.dL_drot;
@@ -4619,24 +4620,18 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
 // own (default or depth); only K8 changes, to its CAM variant (when a view / projection / centre gradient is asked for), and two small
 // launches follow on the join stream, behind every view's K8: k_bg_partials (when a background gradient is asked for) and k_cam_sum.
 static bool cam_k8_wanted(const csplat_view &w) { return w.dL_dview || w.dL_dproj || w.dL_dcampos; }
-static float *cam_slab_of(const csplat_view &w) {
-    const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
-    return (float *)((char *)w.scratch + cam_slab_offset(w.P, Rl, w.W, w.H));
-}
+static float *cam_slab_of(const csplat_view &w) { return (float *)((char *)w.scratch + cam_slab_offset(w.P, layout_R(w), w.W, w.H)); }
 static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *rows) {
     BgTable bt;
     CamSumTable ct;
     bool any_bg = false;
     for (int i = 0; i < V; i++) {
         const csplat_view &w = v[i];
-        const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;
         BgView &b = bt.v[i];
         b.slab = nullptr; b.final_T = nullptr; b.dL_dpix = w.dL_dpix; b.npix = w.W * w.H;
         if (w.dL_dbg && w.dL_dpix && w.scratch) {
-            size_t ioff[5];
-            image_offsets(w.W, w.H, ioff);
-            b.final_T = w.image ? (const float *)((const char *)w.image + ioff[2]) : nullptr;
-            b.slab = (float *)((char *)w.scratch + cam_bg_offset(w.P, Rl, w.W, w.H));
+            b.final_T = w.image ? image_view(w.image, w.W, w.H).final_T : nullptr;
+            b.slab = (float *)((char *)w.scratch + cam_bg_offset(w.P, layout_R(w), w.W, w.H));
             any_bg = true;
         }
         CamSumView &c = ct.v[i];
@@ -4654,11 +4649,43 @@ static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *ro
     return 0;
 }
 
+// The batched K8 (k8_views_table filled `tab`) on the join stream: k_preprocess_bwd_views / _depth / _cam<DEPTH> / _aa<DEPTH, CAM>.  depth:
+// the call takes the depth / feature path; cam_k8: the camera form, one slab row per workgroup and view (cam_rows[i] = their number), whole
+// calls only; every other form runs the workgroups of slice `slice` of `nslices`.
+static int launch_k8_views(int V, const csplat_view *v, const K8Table &tab, bool depth, bool cam_k8, int slice, int nslices, hipStream_t join,
+                           int *cam_rows) {
+    ProfScope ps(cam_k8 ? PROF_K8_CAM : depth ? PROF_K8_DEPTH : PROF_K8, join);
+    const csplat_view &a = v[0];
+    const int nb = cdiv(a.P, 32);
+    const int b_lo = cam_k8 ? 0 : (int)((int64_t)nb * slice / nslices), b_hi = cam_k8 ? nb : (int)((int64_t)nb * (slice + 1) / nslices);
+    CamSlabs sl{};       // (stays empty without cam_k8: the antialiased kernel takes the argument on every path)
+    for (int i = 0; i < V && cam_k8; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
+    if (b_hi <= b_lo) return 0;
+    auto go = [&](auto kernel, auto... extra) {
+        kernel<<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo, extra...);
+    };
+    if (aa_of(a)) {
+        if (depth && cam_k8) go(k_preprocess_bwd_views_aa<128, 4, true, true>, sl, a.opacities);
+        else if (depth) go(k_preprocess_bwd_views_aa<128, 4, true, false>, sl, a.opacities);
+        else if (cam_k8) go(k_preprocess_bwd_views_aa<128, 4, false, true>, sl, a.opacities);
+        else go(k_preprocess_bwd_views_aa<128, 4, false, false>, sl, a.opacities);
+    } else if (cam_k8) {
+        if (depth) go(k_preprocess_bwd_views_cam<128, 4, true>, sl);
+        else go(k_preprocess_bwd_views_cam<128, 4, false>, sl);
+    } else if (depth) {
+        go(k_preprocess_bwd_views_depth<128, 4>);
+    } else {
+        go(k_preprocess_bwd_views<128, 4>);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
 static bool feat_wanted(const csplat_view &w) { return w.dL_dfeatures || w.dL_dalpha; }
 // earlier[0 .. n_earlier): the views of the call's earlier groups (backward_views_impl), whose dL_dfeat_in this group adds to
 static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices, bool cam = false,
                                 bool cam_k8 = false, bool feat = false, const csplat_view *earlier = nullptr, int n_earlier = 0) {
-    CSPLAT_REQUIRE(V <= B2_MAX_VIEWS, "csplat_backward_views: a depth, feature or alpha gradient is taken for at most 8 views per group");
+    CSPLAT_REQUIRE(V <= RASTER_MAX_VIEWS, "csplat_backward_views: a depth, feature or alpha gradient is taken for at most 8 views per group");
     CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth, feature or alpha gradient");
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     CSPLAT_REQUIRE(!feat || whole, "csplat_backward_views_parts: feature / alpha gradients are taken by the whole call only");
@@ -4683,21 +4710,11 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             CSPLAT_REQUIRE(w.P <= 0 || (w.geom && w.binning && w.image && w.out_color && w.scratch && w.dL_dpix && w.radii),
                            "csplat_backward_views: missing saved state, scratch or dL_dpix");
             DepthView &d = dtab.v[i];
-            const int gx = cdiv(w.W, CSPLAT_TILE), tiles = gx * cdiv(w.H, CSPLAT_TILE);
-            const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;   // what the chunk was laid out for
-            size_t ioff[5], boff[B_NFIELDS];
-            image_offsets(w.W, w.H, ioff);
-            binning_offsets(Rl, tiles, boff);
-            const char *b = (const char *)w.binning, *im = (const char *)w.image;
+            const int gx = cdiv(w.W, CSPLAT_TILE), tiles = tiles_of(w.W, w.H), Rl = layout_R(w);
+            const BinView b = binning_view(w.binning, Rl, tiles);
             B2View &k = d.b;
-            k.ranges = (const int2 *)(im + ioff[0]); k.n_contrib = (const uint32_t *)(im + ioff[1]); k.final_T = (const float *)(im + ioff[2]);
-            k.ids_sorted = (const uint32_t *)(b + boff[1]); k.seg_offset = (const int *)(b + boff[2]); k.slot_tile = (const int *)(b + boff[3]);
-            k.ckpt = (const float4 *)(b + boff[4]); k.bbits = (const unsigned long long *)(b + boff[9]);
-            k.recA = (const float4 *)(b + boff[6]); k.recB = (const float4 *)(b + boff[7]); k.recC = (const float2 *)(b + boff[8]);
-            k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = (float *)w.scratch; k.R = (uint32_t)Rl;
-            k.det = !det_mode ? nullptr
-                    : feat ? (float *)((char *)w.scratch + feat_det_offset(w.P, Rl, w.W, w.H))
-                           : (float *)((char *)w.scratch + align256((size_t)(w.P > 0 ? w.P : 1) * ACC_STRIDE * 4));
+            fill_b2_view(w, b, image_view(w.image, w.W, w.H),
+                         !det_mode ? nullptr : (float *)((char *)w.scratch + (feat ? feat_det_offset(w.P, Rl, w.W, w.H) : acc_bytes(w.P))), k);
             d.dL_ddepth = w.dL_ddepth;
             d.dpart = (float *)((char *)w.scratch + depth_dpart_offset(w.P, Rl));
             d.W = w.W; d.H = w.H; d.gx = gx;
@@ -4721,14 +4738,8 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             // (the records start at zero: the bit-reproducible mode writes every one of them, CSPLAT_SCRATCH_ZEROED promises them)
             if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, feat ? feat_det_bytes(Rl) : depth_det_bytes(Rl), join));
             else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(k.acc, 0, (size_t)w.P * ACC_STRIDE * 4, join));
-            if (det_mode) {
-                DetView &e = dt.v[i];
-                make_cam(e.cam, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H);
-                const Geom g = geom_view((void *)w.geom, w.P);
-                e.xy = g.xy; e.depth = g.depth; e.radii = w.radii; e.ranges = k.ranges; e.keys_sorted = (const uint64_t *)(b + boff[0]);
-                e.ids_sorted = k.ids_sorted; e.det = k.det; e.acc = k.acc;
-            }
-            const int64_t sl = (w.busy_tiles > 0 && w.num_rendered > 0) ? (int64_t)w.num_rendered / SEG + w.busy_tiles + 1 : max_slots(Rl, tiles);
+            if (det_mode) fill_det_view(w, b, k, dt.v[i]);
+            const int64_t sl = k7_slots(w, tiles);
             slots = sl > slots ? sl : slots;
         }
         if (feat) {
@@ -4796,45 +4807,13 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
         }
     }
     if (!want_k8) return 0;
-    int cam_rows[K8_MAX_VIEWS] = {0};
-    if (one_k8 && cam_k8) {      // (whole calls only: no slices)
-        ProfScope ps(PROF_K8_CAM, join);
-        const csplat_view &a = v[0];
-        const int nb = cdiv(a.P, 32);
-        CamSlabs sl;
-        for (int i = 0; i < V; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
-        if (aa_of(a))
-            k_preprocess_bwd_views_aa<128, 4, true, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl,
-                                                                             a.opacities);
-        else
-            k_preprocess_bwd_views_cam<128, 4, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
-        LAUNCH_CHECK();
-        return cam ? cam_tail(V, v, join, cam_rows) : 0;
-    }
+    int cam_rows[RASTER_MAX_VIEWS] = {0};
     if (one_k8) {
-        ProfScope ps(PROF_K8_DEPTH, join);
-        const csplat_view &a = v[0];
-        const int nb = cdiv(a.P, 32);
-        const int b_lo = (int)((int64_t)nb * slice / nslices), b_hi = (int)((int64_t)nb * (slice + 1) / nslices);
-        if (b_hi > b_lo) {
-            if (aa_of(a))
-                k_preprocess_bwd_views_aa<128, 4, true, false><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0,
-                                                                                            a.dL_dsh, tab, b_lo, CamSlabs{}, a.opacities);
-            else
-                k_preprocess_bwd_views_depth<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
-            LAUNCH_CHECK();
-        }
-        return cam ? cam_tail(V, v, join, cam_rows) : 0;
-    }
-    for (int i = 0; i < V; i++) {       // per-view K8 on the join stream, in view order (views may add into one another's buffers)
-        const csplat_view &w = v[i];
-        if (int rc = backward_impl(join, join, false, true, w.accmask, w.P, w.D, w.M,
-                                   w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered, w.bg, w.W, w.H, w.means3D, w.shs, w.scales,
-                                   w.scale_modifier, w.rotations, w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii,
-                                   w.geom, w.binning, w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
-                                   w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, w.dL_ddepth != nullptr,
-                                   cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i], aa_opacities_of(w)))
-            return rc;
+        if (int rc = launch_k8_views(V, v, tab, true, cam_k8, slice, nslices, join, cam_rows)) return rc;
+    } else {
+        for (int i = 0; i < V; i++)       // per-view K8 on the join stream, in view order (views may add into one another's buffers)
+            if (int rc = backward_impl(v[i], join, join, false, true, v[i].dL_ddepth != nullptr, cam_k8 ? cam_slab_of(v[i]) : nullptr, &cam_rows[i]))
+                return rc;
     }
     return cam ? cam_tail(V, v, join, cam_rows) : 0;
 }
@@ -4883,8 +4862,8 @@ static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigne
 }
 // the colour path (no view has a depth, feature or alpha gradient); cam / cam_k8: the call takes camera / background gradients
 static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices, bool cam, bool cam_k8) {
-    CSPLAT_REQUIRE(!cam || V <= K8_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per group");
-    int cam_rows[K8_MAX_VIEWS] = {0};
+    CSPLAT_REQUIRE(!cam || V <= RASTER_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per group");
+    int cam_rows[RASTER_MAX_VIEWS] = {0};
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     hipStream_t join = (hipStream_t)join_stream;
     bool shared = false;   // any view adding into another view's buffers: all K8 run on the join stream, in view order
@@ -4893,7 +4872,7 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
     const bool one_k8 = shared && k8_views_table(V, v, tab);
     // K7 of all views in ONE launch on the join stream (plus one launch clearing the records) when the views are alike
     const bool det_mode = (g_debug_flags & 256u) != 0;
-    bool batch_k7 = V >= 2 && V <= B2_MAX_VIEWS && !(g_debug_flags & 512u);
+    bool batch_k7 = V >= 2 && V <= RASTER_MAX_VIEWS && !(g_debug_flags & 512u);
     for (int i = 0; i < V && batch_k7; i++)
         batch_k7 = v[i].P == v[0].P && v[i].P > 0 && v[i].W == v[0].W && v[i].H == v[0].H && v[i].num_rendered > 0 && v[i].geom &&
                    v[i].binning && v[i].image && v[i].out_color && v[i].scratch && v[i].dL_dpix;
@@ -4908,36 +4887,17 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
     // from here on side streams may hold work on caller-owned buffers: whatever fails, the exit fence is still issued
     auto body = [&]() -> int {
         if (batch_k7 && want_k7) {
-            const int W = v[0].W, H = v[0].H, P = v[0].P, gx = cdiv(W, CSPLAT_TILE), tiles = gx * cdiv(H, CSPLAT_TILE);
+            const int W = v[0].W, H = v[0].H, P = v[0].P, gx = cdiv(W, CSPLAT_TILE), tiles = tiles_of(W, H);
             B2Table bt;
             DetTable dt;
             dt.valid = v[0].valid;
             int64_t slots = 0;
-            size_t ioff[5];
-            image_offsets(W, H, ioff);
             for (int i = 0; i < V; i++) {
                 const csplat_view &w = v[i];
-                size_t boff[B_NFIELDS];
-                const int Rl = w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered;   // what the chunk was laid out for
-                binning_offsets(Rl, tiles, boff);
-                const char *b = (const char *)w.binning, *im = (const char *)w.image;
-                B2View &k = bt.v[i];
-                k.ranges = (const int2 *)(im + ioff[0]); k.n_contrib = (const uint32_t *)(im + ioff[1]); k.final_T = (const float *)(im + ioff[2]);
-                k.ids_sorted = (const uint32_t *)(b + boff[1]); k.seg_offset = (const int *)(b + boff[2]); k.slot_tile = (const int *)(b + boff[3]);
-                k.ckpt = (const float4 *)(b + boff[4]); k.bbits = (const unsigned long long *)(b + boff[9]);
-                k.recA = (const float4 *)(b + boff[6]); k.recB = (const float4 *)(b + boff[7]); k.recC = (const float2 *)(b + boff[8]);
-                k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = (float *)w.scratch; k.R = (uint32_t)Rl;
-                k.det = det_mode ? (float *)((char *)w.scratch + align256((size_t)P * ACC_STRIDE * 4)) : nullptr;
-                if (det_mode) {
-                    DetView &d = dt.v[i];
-                    make_cam(d.cam, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H);
-                    const Geom g = geom_view((void *)w.geom, P);
-                    d.xy = g.xy; d.depth = g.depth; d.radii = w.radii; d.ranges = k.ranges; d.keys_sorted = (const uint64_t *)(b + boff[0]);
-                    d.ids_sorted = k.ids_sorted; d.det = k.det; d.acc = k.acc;
-                }
-                // segments of the view: <= R / SEG + (non-empty tiles) + 1 with the EXACT counts the forward read -- the layout's bound
-                // (capacity / SEG + all tiles + 1) launches twice as many workgroups that find no segment
-                const int64_t sl = (w.busy_tiles > 0 && w.num_rendered > 0) ? (int64_t)w.num_rendered / SEG + w.busy_tiles + 1 : max_slots(Rl, tiles);
+                const BinView b = binning_view(w.binning, layout_R(w), tiles);
+                fill_b2_view(w, b, image_view(w.image, W, H), det_mode ? (float *)((char *)w.scratch + acc_bytes(P)) : nullptr, bt.v[i]);
+                if (det_mode) fill_det_view(w, b, bt.v[i], dt.v[i]);
+                const int64_t sl = k7_slots(w, tiles);
                 slots = sl > slots ? sl : slots;
             }
             {   // (measurement hook, off unless csplat_debug_stamps handed over a buffer large enough for this launch)
@@ -4967,13 +4927,8 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
         }
         for (int i = 0; i < V && !(batch_k7 && one_k8); i++) {
             const csplat_view &w = v[i];
-            if (int rc = backward_impl((hipStream_t)w.stream, (shared || batch_k7) ? join : (hipStream_t)w.stream, !batch_k7, !one_k8,
-                                       w.accmask, w.P, w.D, w.M,
-                                       w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered, w.bg, w.W, w.H, w.means3D, w.shs, w.scales, w.scale_modifier, w.rotations,
-                                       w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.radii, w.geom, w.binning,
-                                       w.image, w.out_color, w.dL_dpix, w.scratch, w.dL_dmean2D, w.dL_dconic, w.dL_dopacity,
-                                       w.dL_dcolor, w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh, w.dL_dscale, w.dL_drot, false,
-                                       cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i], aa_opacities_of(w)))
+            if (int rc = backward_impl(w, (hipStream_t)w.stream, (shared || batch_k7) ? join : (hipStream_t)w.stream, !batch_k7, !one_k8, false,
+                                       cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i]))
                 return rc;
         }
         if (one_k8 && want_k8) {   // every view's K7 is queued on its own stream: the join stream waits for all of them, then ONE K8
@@ -4984,32 +4939,7 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
                 HIP_TRY(hipEventRecord(ev, (hipStream_t)v[i].stream));
                 HIP_TRY(hipStreamWaitEvent(join, ev, 0));
             }
-            if (cam_k8) {      // (whole calls only: no slices)
-                ProfScope ps(PROF_K8_CAM, join);
-                const csplat_view &a = v[0];
-                const int nb = cdiv(a.P, 32);
-                CamSlabs sl;
-                for (int i = 0; i < V; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
-                if (aa_of(a))
-                    k_preprocess_bwd_views_aa<128, 4, false, true><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab,
-                                                                                      0, sl, a.opacities);
-                else
-                    k_preprocess_bwd_views_cam<128, 4, false><<<nb, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, 0, sl);
-                LAUNCH_CHECK();
-                return 0;
-            }
-            ProfScope ps(PROF_K8, join);
-            const csplat_view &a = v[0];
-            const int nb = cdiv(a.P, 32);
-            const int b_lo = (int)((int64_t)nb * slice / nslices), b_hi = (int)((int64_t)nb * (slice + 1) / nslices);
-            if (b_hi > b_lo) {
-                if (aa_of(a))
-                    k_preprocess_bwd_views_aa<128, 4, false, false><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0,
-                                                                                                 a.dL_dsh, tab, b_lo, CamSlabs{}, a.opacities);
-                else
-                    k_preprocess_bwd_views<128, 4><<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo);
-                LAUNCH_CHECK();
-            }
+            return launch_k8_views(V, v, tab, false, cam_k8, slice, nslices, join, cam_rows);
         }
         return 0;
     };
@@ -5035,19 +4965,10 @@ int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float 
     CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward_depth: scratch (csplat_backward_depth_scratch_bytes) missing");
     CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
     if (P <= 0) return 0;
-    csplat_view w;
-    memset(&w, 0, sizeof(w));
-    w.stream = stream;
-    w.P = P; w.D = D; w.M = M; w.W = W; w.H = H;
-    w.scale_modifier = scale_modifier; w.tanfovx = tanfovx; w.tanfovy = tanfovy;
-    w.bg = bg; w.means3D = means3D; w.shs = shs; w.colors_precomp = colors_precomp; w.scales = scales; w.rotations = rotations;
-    w.cov3D_precomp = cov3D_precomp; w.view = view; w.proj = proj; w.campos = campos;
-    w.out_color = const_cast<float *>(out_color); w.radii = const_cast<int32_t *>(radii);
-    w.num_rendered = R; w.layout_rendered = R;
-    w.geom = const_cast<void *>(geom); w.binning = const_cast<void *>(binning); w.image = const_cast<void *>(image);
-    w.dL_dpix = dL_dpix; w.dL_ddepth = dL_ddepth; w.scratch = scratch;
-    w.dL_dmean2D = dL_dmean2D; w.dL_dconic = dL_dconic; w.dL_dopacity = dL_dopacity; w.dL_dcolor = dL_dcolor; w.dL_dmean3D = dL_dmean3D;
-    w.dL_dcov3D = dL_dcov3D; w.dL_dsh = dL_dsh; w.dL_dscale = dL_dscale; w.dL_drot = dL_drot;
+    csplat_view w = pack_view(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, view,
+                              proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, scratch, dL_dmean2D, dL_dconic,
+                              dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+    w.dL_ddepth = dL_ddepth;
     return backward_views_depth(1, &w, (hipStream_t)stream, 3u, 0, 1);
 }
 int csplat_backward_views_parts(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {

@@ -14,16 +14,13 @@ case = dict(g=syn.gaussians_at(sc), cam=sc["cameras"][0], W=W, H=H, P=P, bg=sc["
 color, radii, depth, st = util.gpu_forward_raw(case)
 R = st["R"]
 import diff_gaussian_rasterization as dgr  # noqa
-# raw binning chunk: recompute the layout (csplat_raster.hip: binning_offsets)
-a256 = lambda x: (x + 255) // 256 * 256
+# raw binning chunk: the library's own layout (csplat_binning_fields: the byte offset of each of its eleven fields)
+import ctypes
+from csplat import native
 tiles = ((W + 15) // 16) * ((H + 15) // 16)
 SEG = 256
-n = max(R, 1)
-slots = R // SEG + tiles + 1
-off = [0]
-off.append(a256(n * 8)); off.append(off[1] + a256(n * 4)); off.append(off[2] + a256((tiles + 1) * 4 + tiles * 16 * 4))
-off.append(off[3] + a256(slots * 4)); off.append(off[4] + a256(slots * 256 * 16)); off.append(off[5] + a256((n + 1) * 2))
-off.append(off[6] + a256((n + 1) * 16)); off.append(off[7] + a256((n + 1) * 16)); off.append(off[8] + a256((n + 1) * 8))
+off = (ctypes.c_size_t * 11)()
+native.lib.csplat_binning_fields(int(R), W, H, off)
 raw = st["_binning_raw"] if "_binning_raw" in st else None
 if raw is None:
     raise SystemExit("util.gpu_forward_raw does not expose the raw binning chunk (st['_binning_raw'])")
