@@ -134,6 +134,15 @@ class FusedL1(torch.autograd.Function):
         return ga, gb, None
 
 
+_MAX_PLANES = 65535          # one launch of the tile kernels carries the plane in blockIdx.z
+
+
+def _plane_chunks(n_planes):
+    """[start, end) ranges of at most _MAX_PLANES planes: the tile kernels are called once per range (their sums are per plane, so
+    the result is the same sum)"""
+    return [(s, min(s + _MAX_PLANES, n_planes)) for s in range(0, n_planes, _MAX_PLANES)]
+
+
 class GaussianBlur11(torch.autograd.Function):
     """zero-padded 11x11 Gaussian window (sigma 1.5) on every [H, W] plane, HIP kernel csplat_blur11; self-adjoint."""
 
@@ -143,9 +152,13 @@ class GaussianBlur11(torch.autograd.Function):
         x = x.contiguous().float()
         H, W = x.shape[-2:]
         out = torch.empty_like(x)
+        if x.numel() == 0:
+            return out
+        xp, op = x.view(-1, H, W), out.view(-1, H, W)
         with _n.on_device(x.device):
-            _n.check(_n.lib.csplat_blur11(_n.stream_handle(x.device), x.numel() // (H * W), H, W, _taps(), _n.ptr(x), _n.ptr(out)),
-                     "csplat_blur11")
+            for s, e in _plane_chunks(xp.shape[0]):
+                _n.check(_n.lib.csplat_blur11(_n.stream_handle(x.device), e - s, H, W, _taps(), _n.ptr(xp[s:e]), _n.ptr(op[s:e])),
+                         "csplat_blur11")
         return out
 
     @staticmethod
@@ -184,11 +197,15 @@ class FusedSSIM(torch.autograd.Function):
         n_img = x.numel() // (H * W)
         need = img1.requires_grad
         p = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=x.device) if need else None
-        partial = torch.empty(int(_n.lib.csplat_ssim_partial_count(n_img, H, W)), dtype=torch.float32, device=x.device)
+        per_plane = int(_n.lib.csplat_ssim_partial_count(1, H, W))
+        partial = torch.empty(n_img * per_plane, dtype=torch.float32, device=x.device)
+        xp, yp, pp = x.view(-1, H, W), y.view(-1, H, W), (p.view(3, -1, H, W) if need else None)
         with _n.on_device(x.device):
-            _n.check(_n.lib.csplat_ssim_fwd(_n.stream_handle(x.device), n_img, H, W, _taps(), _n.ptr(x), _n.ptr(y),
-                                            _n.ptr(p[0]) if need else None, _n.ptr(p[1]) if need else None,
-                                            _n.ptr(p[2]) if need else None, None, _n.ptr(partial)), "csplat_ssim_fwd")
+            for s, e in _plane_chunks(n_img):
+                _n.check(_n.lib.csplat_ssim_fwd(_n.stream_handle(x.device), e - s, H, W, _taps(), _n.ptr(xp[s:e]), _n.ptr(yp[s:e]),
+                                                _n.ptr(pp[0, s:e]) if need else None, _n.ptr(pp[1, s:e]) if need else None,
+                                                _n.ptr(pp[2, s:e]) if need else None, None, _n.ptr(partial[s * per_plane:e * per_plane])),
+                         "csplat_ssim_fwd")
         ctx.save_for_backward(x, y, p)
         ctx.dims = (n_img, H, W)
         return partial.sum() / float(x.numel())
@@ -199,10 +216,12 @@ class FusedSSIM(torch.autograd.Function):
         n_img, H, W = ctx.dims
         g = g.reshape(1).float().contiguous()
         dx = torch.empty_like(x)
+        xp, yp, pp, dp = x.view(-1, H, W), y.view(-1, H, W), p.view(3, -1, H, W), dx.view(-1, H, W)
         with _n.on_device(x.device):
-            _n.check(_n.lib.csplat_ssim_bwd(_n.stream_handle(x.device), n_img, H, W, _taps(), _n.ptr(x), _n.ptr(y), _n.ptr(p[0]),
-                                            _n.ptr(p[1]), _n.ptr(p[2]), _n.ptr(g), 1.0 / float(x.numel()), None, None, _n.ptr(dx)),
-                     "csplat_ssim_bwd")
+            for s, e in _plane_chunks(n_img):
+                _n.check(_n.lib.csplat_ssim_bwd(_n.stream_handle(x.device), e - s, H, W, _taps(), _n.ptr(xp[s:e]), _n.ptr(yp[s:e]),
+                                                _n.ptr(pp[0, s:e]), _n.ptr(pp[1, s:e]), _n.ptr(pp[2, s:e]), _n.ptr(g), 1.0 / float(x.numel()),
+                                                None, None, _n.ptr(dp[s:e])), "csplat_ssim_bwd")
         return dx, None
 
 
@@ -283,7 +302,7 @@ class FusedImageLoss(torch.autograd.Function):
 def _image_loss_fusable(image_tensor, gt_image_tensor, opt, mask_tensor):
     return bool(opt.lambda_dssim != 0 and image_tensor.is_cuda and image_tensor.dtype == torch.float32 and
                 gt_image_tensor.dtype == torch.float32 and image_tensor.shape == gt_image_tensor.shape and image_tensor.dim() in (3, 4)
-                and image_tensor.numel() > 0 and image_tensor.numel() // (image_tensor.shape[-1] * image_tensor.shape[-2]) < 65536
+                and image_tensor.numel() > 0 and image_tensor.numel() // (image_tensor.shape[-1] * image_tensor.shape[-2]) <= _MAX_PLANES
                 and not gt_image_tensor.requires_grad and
                 (mask_tensor is None or (image_tensor.dim() == 4 and _mask_layout(image_tensor, mask_tensor) is not None)))
 
@@ -340,8 +359,10 @@ def image_losses(image_tensor, gt_image_tensor, opt, mask_tensor=None):
     if _image_loss_fusable(image_tensor, gt_image_tensor, opt, mask_tensor):
         return FusedImageLoss.apply(image_tensor, gt_image_tensor, opt.lambda_dssim, mask_tensor)[0]
     if opt.lambda_dssim != 0:
-        _n.composed_fallback("train.image_losses", "dtype" if image_tensor.shape == gt_image_tensor.shape and image_tensor.numel() else "shape",
-                             image_tensor)
+        # (more planes than one launch of the fused kernel carries is a miss on SHAPE; l1_loss + ssim below take any plane count)
+        planes = image_tensor.numel() // max(image_tensor.shape[-1] * image_tensor.shape[-2], 1) if image_tensor.dim() >= 2 else 0
+        _n.composed_fallback("train.image_losses", "dtype" if image_tensor.shape == gt_image_tensor.shape and image_tensor.numel() and
+                             planes <= _MAX_PLANES else "shape", image_tensor)
     loss = l1_loss(image_tensor, gt_image_tensor, mask_tensor)
     if opt.lambda_dssim != 0:
         if mask_tensor is None:

@@ -396,18 +396,18 @@ __global__ __launch_bounds__(SSIM_THREADS) void k_image_loss_finish(size_t per_p
     const float ssim_sum = block_sum(partial, 0, nwg);
     const float l1_sum = block_sum(partial + nwg, 0, nwg);
     const int n_batch = planes / channels;
-    float psnr_sum = 0.f;
+    double psnr_sum = 0.0;         // (a float sum of 21 845 images' PSNR, added one by one, is off by 1e-6 of its value)
     for (int b = 0; b < n_batch; b++) {
         const float q = block_sum(partial + 2 * nwg, (size_t)b * channels * per_plane, (size_t)(b + 1) * channels * per_plane);
         const float mse = q / ((float)channels * (float)H * (float)W);
-        psnr_sum += 20.f * log10f(1.f / sqrtf(mse));
+        psnr_sum += (double)(20.f * log10f(1.f / sqrtf(mse)));
     }
     if (threadIdx.x == 0) {
         const float n = (float)planes * (float)H * (float)W;
         const float l1 = l1_sum / n;
         const float image_loss = masked ? l1 + lam * (ssim_sum / n) : l1 + lam * (1.f - ssim_sum / n);
         out[0] = img_weight * image_loss + (add ? add_weight * add[0] : 0.f);
-        out[1] = psnr_scale * psnr_sum;
+        out[1] = psnr_scale * (float)psnr_sum;
         out[2] = image_loss;
         out[3] = l1;
     }
@@ -430,7 +430,10 @@ __global__ __launch_bounds__(L1_THREADS) void k_l1(int64_t n, const float *__res
         const int64_t plane = e / hw;
         return (mask_channels == 1 ? plane / channels : plane) * hw + (e - plane * hw);
     };
-    const int64_t n4 = (mask && (hw & 3)) ? 0 : n >> 2;    // a 4-pixel group stays inside one image plane
+    // 16-byte groups need a 4-pixel group inside one image plane AND 16-byte-aligned operands (a contiguous view into a batch whose plane
+    // size is not a multiple of 4 floats starts anywhere); otherwise every element takes the scalar form below, as in k_psnr / adam_span
+    const bool al = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad | (uintptr_t)mask) & 15u) == 0);
+    const int64_t n4 = ((mask && (hw & 3)) || !al) ? 0 : n >> 2;
     auto one = [&](int64_t i, const float4 x, const float4 y) {
         float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
         if (mask) {
@@ -463,7 +466,7 @@ __global__ __launch_bounds__(L1_THREADS) void k_l1(int64_t n, const float *__res
         one(i + stride, x1, y1);
     }
     if (i < n4) one(i, reinterpret_cast<const float4 *>(a)[i], reinterpret_cast<const float4 *>(b)[i]);
-    // tail: n not a multiple of 4 (<= 3 elements, all on workgroup 0), or every element when the planes are not 4-aligned
+    // tail: n not a multiple of 4 (<= 3 elements, all on workgroup 0), or every element when the planes or the operands are not 16-byte-aligned
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * L1_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * L1_THREADS) {
         float d = a[i] - b[i];
         float m = 1.f;
@@ -569,7 +572,7 @@ __global__ __launch_bounds__(256) void k_l1_bwd(int64_t n, const signed char *__
         const int64_t plane = e / hw;
         return (mask_channels == 1 ? plane / channels : plane) * hw + (e - plane * hw);
     };
-    const int64_t n4 = (mask && (hw & 3)) ? 0 : n >> 2;
+    const int64_t n4 = ((mask && (hw & 3)) || ((uintptr_t)mask & 15u)) ? 0 : n >> 2;      // (a misaligned mask: scalar form, as k_l1)
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
         const char4 s = reinterpret_cast<const char4 *>(sign8)[i];
@@ -587,9 +590,10 @@ __global__ __launch_bounds__(256) void k_l1_bwd(int64_t n, const signed char *__
 static int l1_launch(void *stream, int64_t n, const float *a, const float *b, void *scratch, float *loss, float *grad,
                      const float *mask, int64_t hw, int channels, int mask_channels, const char *who, signed char *sign8 = nullptr) {
     CSPLAT_REQUIRE(n > 0 && a && b && scratch && loss, "csplat_l1: bad arguments");
-    CSPLAT_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad | (uintptr_t)mask) & 15u) == 0, "csplat_l1: operands must be 16-byte aligned");
+    CSPLAT_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad | (uintptr_t)mask) & 3u) == 0, "csplat_l1: operands must be 4-byte aligned");
+    const bool al = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad | (uintptr_t)mask) & 15u) == 0);      // else k_l1 takes its scalar form
     float *partial = (float *)scratch;
-    const int64_t units = (mask && (hw & 3)) ? n : n / 4;
+    const int64_t units = ((mask && (hw & 3)) || !al) ? n : n / 4;
     const int64_t work = (units + L1_THREADS - 1) / L1_THREADS;
     const int grid = (int)(work < 1 ? 1 : (work > L1_BLOCKS ? L1_BLOCKS : work));
     CSPLAT_REQUIRE(((uintptr_t)sign8 & 3u) == 0, "csplat_l1: the sign buffer must be 4-byte aligned");
@@ -621,7 +625,7 @@ extern "C" int csplat_l1_signs(void *stream, int64_t n_batch, int channels, int6
 extern "C" int csplat_l1_signs_bwd(void *stream, int64_t n_batch, int channels, int64_t hw, const signed char *sign8, const float *mask,
                                    int mask_channels, const float *g_scalar, float *out) {
     CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && hw > 0 && sign8 && g_scalar && out, "csplat_l1_signs_bwd: bad arguments");
-    CSPLAT_REQUIRE((((uintptr_t)out | (uintptr_t)mask) & 15u) == 0 && ((uintptr_t)sign8 & 3u) == 0, "csplat_l1_signs_bwd: operands must be aligned");
+    CSPLAT_REQUIRE(((uintptr_t)out & 15u) == 0 && (((uintptr_t)sign8 | (uintptr_t)mask) & 3u) == 0, "csplat_l1_signs_bwd: operands must be aligned");
     const int64_t n = n_batch * channels * hw;
     const int64_t work = (n / 4 + 255) / 256;
     const int grid = (int)(work < 1 ? 1 : (work > 4096 ? 4096 : work));

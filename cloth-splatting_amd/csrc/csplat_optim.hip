@@ -111,21 +111,26 @@ __global__ void k_adam_tick(int *state, const uint32_t *__restrict__ valid) {
 extern "C" int csplat_adam_step_dev(void *stream, int n_tensors, float *const *params, const float *const *grads, float *const *exp_avg,
                                     float *const *exp_avg_sq, const int64_t *numel, const double *lr_dev, double beta1, double beta2,
                                     double eps, int *state_dev, const uint32_t *valid_dev) {
-    CSPLAT_REQUIRE(n_tensors >= 1 && n_tensors <= CSPLAT_ADAM_MAX_TENSORS && params && grads && exp_avg && exp_avg_sq && numel && lr_dev &&
-                   state_dev, "csplat_adam_step_dev: bad arguments (1..48 tensors)");
-    AdamDevTable tab;
-    memset(&tab, 0, sizeof(tab));
-    int64_t longest = 0;
-    for (int i = 0; i < n_tensors; i++) {
-        CSPLAT_REQUIRE(numel[i] == 0 || (params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i]), "csplat_adam_step_dev: NULL tensor");
-        tab.d[i] = AdamDevDesc{params[i], grads[i], exp_avg[i], exp_avg_sq[i], (long long)numel[i]};
-        longest = numel[i] > longest ? numel[i] : longest;
-    }
-    if (longest > 0) {
-        const int64_t want = (longest + 4095) / 4096;
-        dim3 grid((unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want)), (unsigned)n_tensors);
-        k_adam_dev<<<grid, 256, 0, (hipStream_t)stream>>>(tab, lr_dev, beta1, beta2, (float)eps, state_dev, valid_dev);
-        LAUNCH_CHECK();
+    CSPLAT_REQUIRE(n_tensors >= 1 && params && grads && exp_avg && exp_avg_sq && numel && lr_dev && state_dev,
+                   "csplat_adam_step_dev: bad arguments");
+    // one launch per CSPLAT_ADAM_MAX_TENSORS tensors, as csplat_adam_step; every launch reads the same count, the tick follows the last
+    for (int base = 0; base < n_tensors; base += CSPLAT_ADAM_MAX_TENSORS) {
+        AdamDevTable tab;
+        memset(&tab, 0, sizeof(tab));
+        const int cnt = n_tensors - base < CSPLAT_ADAM_MAX_TENSORS ? n_tensors - base : CSPLAT_ADAM_MAX_TENSORS;
+        int64_t longest = 0;
+        for (int i = 0; i < cnt; i++) {
+            const int t = base + i;
+            CSPLAT_REQUIRE(numel[t] == 0 || (params[t] && grads[t] && exp_avg[t] && exp_avg_sq[t]), "csplat_adam_step_dev: NULL tensor");
+            tab.d[i] = AdamDevDesc{params[t], grads[t], exp_avg[t], exp_avg_sq[t], (long long)numel[t]};
+            longest = numel[t] > longest ? numel[t] : longest;
+        }
+        if (longest > 0) {
+            const int64_t want = (longest + 4095) / 4096;
+            dim3 grid((unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want)), (unsigned)cnt);
+            k_adam_dev<<<grid, 256, 0, (hipStream_t)stream>>>(tab, lr_dev + base, beta1, beta2, (float)eps, state_dev, valid_dev);
+            LAUNCH_CHECK();
+        }
     }
     k_adam_tick<<<1, 64, 0, (hipStream_t)stream>>>(state_dev, valid_dev);
     LAUNCH_CHECK();

@@ -371,7 +371,8 @@ int csplat_adam_step(void *stream, int n_tensors, float *const *params, const fl
 /* The same step with NOTHING of the launch depending on a per-step host value (for a training step recorded into a hipGraph):
  * state_dev[0] (int32, device) = steps taken so far -- the kernel uses state_dev[0] + 1 for its bias corrections and a trailing
  * one-thread launch advances it; lr_dev = the tensors' learning rates as doubles in device memory; valid_dev (may be NULL) = a device
- * word: 0 there -> parameters, moments and the step count are left untouched.  At most CSPLAT_ADAM_MAX_TENSORS tensors. */
+ * word: 0 there -> parameters, moments and the step count are left untouched.  One launch per CSPLAT_ADAM_MAX_TENSORS tensors
+ * (all of them read the same count), then the one that advances the count. */
 int csplat_adam_step_dev(void *stream, int n_tensors, float *const *params, const float *const *grads, float *const *exp_avg,
                          float *const *exp_avg_sq, const int64_t *numel, const double *lr_dev, double beta1, double beta2, double eps,
                          int *state_dev, const uint32_t *valid_dev);
@@ -499,7 +500,9 @@ int csplat_image_loss_bwd(void *stream, int64_t n_batch, int channels, int H, in
  * csplat_l1_masked: *loss = mean_i |(a[i] - b[i]) * m[i]|, grad[i] = sign((a-b)*m) * m / n, with the mask laid out as for
  * csplat_ssim_fwd_masked (hw = H*W values per plane).
  * scratch: csplat_l1_scratch_bytes() bytes whose last word is zero on entry (the kernel restores it), not shared between
- * calls that may run concurrently.  Deterministic (fixed summation order). */
+ * calls that may run concurrently.  Deterministic (fixed summation order).  a, b, mask and grad need only their natural 4-byte
+ * alignment (a contiguous view into a batch with odd plane sizes): 16-byte groups are used when all of them are 16-byte aligned,
+ * element-wise accesses otherwise (csplat_l1_signs_bwd: likewise for its mask; out is 16-byte aligned). */
 size_t csplat_l1_scratch_bytes(void);
 int csplat_l1(void *stream, int64_t n, const float *a, const float *b, void *scratch, float *loss, float *grad);
 int csplat_l1_masked(void *stream, int64_t n_batch, int channels, int64_t hw, const float *a, const float *b, const float *mask,
