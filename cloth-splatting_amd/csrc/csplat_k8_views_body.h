@@ -1,23 +1,25 @@
 // Body of the batched per-Gaussian backward (K8 of csplat_backward_views), included by csplat_raster.hip into k_preprocess_bwd_views
 // (DEPTH = false), k_preprocess_bwd_views_depth (DEPTH = true), k_preprocess_bwd_views_cam (CAM = true) and k_preprocess_bwd_views_aa
 // (AA = true: antialiasing, see preprocess_bwd_body).  Not a standalone header: it expects the kernels' parameters, constexpr bools DEPTH,
-// CAM and AA, a `const CamSlabs *cam_slabs` and a `const float *aa_opacities` (the raw opacities when AA) in scope.
+// CAM, AA and UNREAD (the caller reads no dL_dconic / dL_dcolor / dL_dcov3D, known at compile time: the default kernel's second
+// instantiation, which then drops their nine running sums from the view loop), a `const CamSlabs *cam_slabs` and a `const float *aa_opacities` (the raw opacities when AA) in scope.
     constexpr bool STAGE = true;
     if (tab.valid && *tab.valid == 0u) return;
     // (block0: first workgroup of a Gaussian-range SLICE of the launch -- csplat_backward_views_parts: the gradient rows of a finished slice
     //  can leave for the other ranks while the next slice computes)
     const int bx = (int)blockIdx.x + block0;
     const unsigned smask = tab.sharedmask;
+    // CSPLAT_K8_OUTPUTS_UNREAD on every view: dL_dconic, dL_dcolor and dL_dcov3D are not stored (wave-uniform, from the kernel argument)
+    const bool put3 = !UNREAD && tab.unread == 0u;
     // shared output: add to the thread's running sum; per-view output: write (or add, by that view's accmask)
 #define PUTL(local, ptr, idx, val, bit)                                                    \
     do {                                                                                   \
         if (smask & (bit)) (local) += (val);                                               \
         else { float *p_ = (ptr) + (idx); *p_ = (accmask & (bit)) ? *p_ + (val) : (val); } \
     } while (0)
-    static_assert(VL == 1 || VL == 4, "one lane or one quad per Gaussian");
+    static_assert(VL == 4 && K8_MAX_VIEWS <= 2 * VL, "one quad per Gaussian, at most two views per lane");
     constexpr int NG = NT / VL;                   // Gaussians per workgroup
     __shared__ float s_in[STAGE ? NG * SH_ROW : 1];
-    __shared__ float s_out[STAGE ? NT * SH_ROW : 1];
     __shared__ float s_cam[CAM ? K8_MAX_VIEWS * NG * CAM_NC : 1];     // (CAM) [view][Gaussian of the workgroup][CAM_NC]
     __shared__ float s_cpart[CAM ? CAM_PARTS * CAM_NC : 1];
     const int gi = threadIdx.x / VL, vl = threadIdx.x % VL;
@@ -25,7 +27,6 @@
     const int rows = min(NG, P - bx * NG);
     if (STAGE) {
         stage_sh_rows<NT>(shs + (size_t)bx * NG * 48, rows, s_in);
-        for (int k = 0; k < 48; k++) s_out[threadIdx.x * SH_ROW + k] = 0.f;
         __syncthreads();
     }
     if (i < P) {
@@ -36,13 +37,19 @@
     bool vis_n = false;
     float a9_n[9];
     float dz_n = 0.f;                                    // (DEPTH) record slot 9
-    float4 co_n = make_float4(0.f, 0.f, 0.f, 0.f);       // (the view's conic + opacity travel with its record: moments_to_gradients)
+    // the 64-byte-aligned record as three 16-byte loads (slots 0-3, 4-7, 8-11): slot 9 rides along
+    auto load_record = [](const float *acc_, int i_, float (&a)[9], float &dz_) {
+        const float4 *r4 = reinterpret_cast<const float4 *>(acc_ + (size_t)i_ * ACC_STRIDE);
+        const float4 q0 = r4[0], q1 = r4[1], q2 = r4[2];
+        a[0] = q0.x; a[1] = q0.y; a[2] = q0.z; a[3] = q0.w; a[4] = q1.x; a[5] = q1.y; a[6] = q1.z; a[7] = q1.w; a[8] = q2.x;
+        if constexpr (DEPTH) dz_ = q2.y;
+    };
+    // what the SH gradient of this lane's FIRST view (views 0..3) is formed from after the loop: direction, dRGB (0 where clamped); all
+    // zero for a view that is culled or absent.  A second view's (4..7) six values go to the quad's own row of s_in: see below.
+    float e0[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (vl < tab.n) {
         vis_n = tab.v[vl].radii[i] > 0;
-        co_n = tab.v[vl].g.conic_opacity[i];
-#pragma unroll
-        for (int k = 0; k < 9; k++) a9_n[k] = tab.v[vl].acc[(size_t)i * ACC_STRIDE + k];
-        if constexpr (DEPTH) dz_n = tab.v[vl].acc[(size_t)i * ACC_STRIDE + 9];
+        load_record(tab.v[vl].acc, i, a9_n, dz_n);
         if (vis_n && (tab.v[vl].accmask & CSPLAT_SCRATCH_ZEROED)) clear_record(tab.v[vl].acc, i);
     }
     for (int vi = vl; vi < tab.n; vi += VL) {
@@ -61,31 +68,33 @@
 #pragma unroll
     for (int k = 0; k < 9; k++) a9[k] = vis ? a9_n[k] : 0.f;
     const float dz = vis ? dz_n : 0.f;
-    moments_to_gradients(a9, vis ? co_n : make_float4(0.f, 0.f, 0.f, 0.f));
+    // (the view's conic + opacity are not requested ahead: four registers across the body that the one-round case, V <= 4, would pay too)
+    moments_to_gradients(a9, vis ? g.conic_opacity[i] : make_float4(0.f, 0.f, 0.f, 0.f));
     a9[0] *= (float)cam.W; a9[1] *= (float)cam.H;      // (see k_preprocess_bwd)
     if (vi + VL < tab.n) {
         const K8View &wn = tab.v[vi + VL];
         vis_n = wn.radii[i] > 0;
-#pragma unroll
-        for (int k = 0; k < 9; k++) a9_n[k] = wn.acc[(size_t)i * ACC_STRIDE + k];
-        if constexpr (DEPTH) dz_n = wn.acc[(size_t)i * ACC_STRIDE + 9];
-        co_n = wn.g.conic_opacity[i];
+        load_record(wn.acc, i, a9_n, dz_n);
         if (vis_n && (wn.accmask & CSPLAT_SCRATCH_ZEROED)) clear_record(wn.acc, i);
     }
     dL_dmean2D[3 * i] = a9[0]; dL_dmean2D[3 * i + 1] = a9[1]; dL_dmean2D[3 * i + 2] = 0.f;
-    dL_dconic[4 * i] = a9[2]; dL_dconic[4 * i + 1] = a9[3]; dL_dconic[4 * i + 2] = 0.f; dL_dconic[4 * i + 3] = a9[4];
+    if (put3) { dL_dconic[4 * i] = a9[2]; dL_dconic[4 * i + 1] = a9[3]; dL_dconic[4 * i + 2] = 0.f; dL_dconic[4 * i + 3] = a9[4]; }
     if constexpr (!AA) PUTL(L_op, dL_dopacity, i, a9[5], CSPLAT_ACC_OPACITY);     // (AA: h dL/do', below)
-    PUTL(L_col[0], dL_dcolor, 3 * i, a9[6], CSPLAT_ACC_COLOR); PUTL(L_col[1], dL_dcolor, 3 * i + 1, a9[7], CSPLAT_ACC_COLOR);
-    PUTL(L_col[2], dL_dcolor, 3 * i + 2, a9[8], CSPLAT_ACC_COLOR);
+    if (put3) {
+        PUTL(L_col[0], dL_dcolor, 3 * i, a9[6], CSPLAT_ACC_COLOR); PUTL(L_col[1], dL_dcolor, 3 * i + 1, a9[7], CSPLAT_ACC_COLOR);
+        PUTL(L_col[2], dL_dcolor, 3 * i + 2, a9[8], CSPLAT_ACC_COLOR);
+    }
 
+    float e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float dmean[3] = {0.f, 0.f, 0.f};
     float g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (!vis) {
         if constexpr (AA) PUTL(L_op, dL_dopacity, i, 0.f, CSPLAT_ACC_OPACITY);
 #pragma unroll
         for (int k = 0; k < 3; k++) PUTL(L_m3[k], dL_dmean3D, 3 * i + k, 0.f, CSPLAT_ACC_MEAN3D);
+        if (put3)
 #pragma unroll
-        for (int k = 0; k < 6; k++) PUTL(L_c6[k], dL_dcov3D, 6 * i + k, 0.f, CSPLAT_ACC_COV3D);
+            for (int k = 0; k < 6; k++) PUTL(L_c6[k], dL_dcov3D, 6 * i + k, 0.f, CSPLAT_ACC_COV3D);
         if (dL_dscale)
 #pragma unroll
             for (int k = 0; k < 3; k++) PUTL(L_sc[k], dL_dscale, 3 * i + k, 0.f, CSPLAT_ACC_SCALE);
@@ -177,43 +186,28 @@
     // ---- colour -> SH (+ view direction -> mean3D)
     if (shs && dL_dsh) {
         const float *sh = (const float *)(s_in + gi * SH_ROW);
-        float *gsh = s_out + threadIdx.x * SH_ROW;
         const uint32_t cl = g.clamped[i];
         const float vx = p[0] - cam.campos[0], vy = p[1] - cam.campos[1], vz = p[2] - cam.campos[2];
         const float sum2 = vx * vx + vy * vy + vz * vz;
         const float len = sqrtf(sum2);
         const float x = vx / len, y = vy / len, z = vz / len;
         float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+        // (the SH gradient itself, basis_k(x, y, z) dRGB, is formed after the view loop: sh_quad_rows)
+        e[0] = x; e[1] = y; e[2] = z;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
             const float dRGB = ((cl >> ch) & 1u) ? 0.f : a9[6 + ch];
+            e[3 + ch] = dRGB;
             float dx_ = 0.f, dy_ = 0.f, dz_ = 0.f;
 #define S(k) sh[(k) * 3 + ch]
-#define GS(k) gsh[(k) * 3 + ch]
-            GS(0) += SH_C0 * dRGB;
             if (D > 0) {
-                GS(1) += -SH_C1 * y * dRGB;
-                GS(2) += SH_C1 * z * dRGB;
-                GS(3) += -SH_C1 * x * dRGB;
                 dx_ = -SH_C1 * S(3); dy_ = -SH_C1 * S(1); dz_ = SH_C1 * S(2);
                 if (D > 1) {
                     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    GS(4) += SH_C2[0] * xy * dRGB;
-                    GS(5) += SH_C2[1] * yz * dRGB;
-                    GS(6) += SH_C2[2] * (2.f * zz - xx - yy) * dRGB;
-                    GS(7) += SH_C2[3] * xz * dRGB;
-                    GS(8) += SH_C2[4] * (xx - yy) * dRGB;
                     dx_ += SH_C2[0] * y * S(4) + SH_C2[2] * 2.f * -x * S(6) + SH_C2[3] * z * S(7) + SH_C2[4] * 2.f * x * S(8);
                     dy_ += SH_C2[0] * x * S(4) + SH_C2[1] * z * S(5) + SH_C2[2] * 2.f * -y * S(6) + SH_C2[4] * 2.f * -y * S(8);
                     dz_ += SH_C2[1] * y * S(5) + SH_C2[2] * 4.f * z * S(6) + SH_C2[3] * x * S(7);
                     if (D > 2) {
-                        GS(9) += SH_C3[0] * y * (3.f * xx - yy) * dRGB;
-                        GS(10) += SH_C3[1] * xy * z * dRGB;
-                        GS(11) += SH_C3[2] * y * (4.f * zz - xx - yy) * dRGB;
-                        GS(12) += SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * dRGB;
-                        GS(13) += SH_C3[4] * x * (4.f * zz - xx - yy) * dRGB;
-                        GS(14) += SH_C3[5] * z * (xx - yy) * dRGB;
-                        GS(15) += SH_C3[6] * x * (xx - 3.f * yy) * dRGB;
                         dx_ += SH_C3[0] * S(9) * 6.f * xy + SH_C3[1] * S(10) * yz + SH_C3[2] * S(11) * -2.f * xy +
                                SH_C3[3] * S(12) * -6.f * xz + SH_C3[4] * S(13) * (-3.f * xx + 4.f * zz - yy) +
                                SH_C3[5] * S(14) * 2.f * xz + SH_C3[6] * S(15) * 3.f * (xx - yy);
@@ -227,7 +221,6 @@
                 }
             }
 #undef S
-#undef GS
             ddx += dx_ * dRGB; ddy += dy_ * dRGB; ddz += dz_ * dRGB;
         }
         const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
@@ -242,8 +235,9 @@
     if constexpr (DEPTH) { dmean[0] += dz * view[2]; dmean[1] += dz * view[6]; dmean[2] += dz * view[10]; }
 #pragma unroll
     for (int k = 0; k < 3; k++) PUTL(L_m3[k], dL_dmean3D, 3 * i + k, dmean[k], CSPLAT_ACC_MEAN3D);
+    if (put3)
 #pragma unroll
-    for (int k = 0; k < 6; k++) PUTL(L_c6[k], dL_dcov3D, 6 * i + k, g6[k], CSPLAT_ACC_COV3D);
+        for (int k = 0; k < 6; k++) PUTL(L_c6[k], dL_dcov3D, 6 * i + k, g6[k], CSPLAT_ACC_COV3D);
 
     // ---- cov3D -> scale, quaternion
     if (!use_precomp_cov && dL_dscale && dL_drot) {
@@ -279,7 +273,17 @@
         PUTL(L_rt[2], dL_drot, 4 * i + 2, dq2, CSPLAT_ACC_ROT); PUTL(L_rt[3], dL_drot, 4 * i + 3, dq3, CSPLAT_ACC_ROT);
     }
     }   // visible
+    if (vi < VL) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) e0[k] = e[k];
+    } else {
+        // the lane's second and last view: this view's reads were the quad's last of its SH row (no other quad reads it, and a wave's LDS
+        // accesses keep their order), so the row now carries the four lanes' values to the exchange below -- no register held for V <= 4
+#pragma unroll
+        for (int k = 0; k < 6; k++) s_in[gi * SH_ROW + vl * 6 + k] = e[k];
+    }
     }   // views
+    __builtin_amdgcn_wave_barrier();
     if (VL == 4) {   // the four lanes' sums over their views: ((v0 + v1) + (v2 + v3)) in every lane
         auto quad_sum = [](float v) {
             v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
@@ -294,17 +298,77 @@
 #pragma unroll
         for (int k = 0; k < 4; k++) L_rt[k] = quad_sum(L_rt[k]);
     }
+    // ---- the SH gradient.  Every lane of the quad takes all four lanes' (direction, dRGB) by DPP and forms coefficients 12 vl .. 12 vl + 11
+    // (basis functions 4 vl .. 4 vl + 3, three channels) of each: the quad stores the Gaussian's 192-byte row as 4 x 3 16-byte stores, no LDS.
+    // Association as ever: lane order ((r0 + r1) + r2) + r3, r = the sum over that lane's views in order.
+    if (VL == 4 && shs && dL_dsh) {
+        float o[12];
+        auto coeffs = [&](const float (&b)[6], float (&c)[12]) {
+            const float x = b[0], y = b[1], z = b[2];
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            const float b0[4] = {SH_C0, -SH_C1 * y, SH_C1 * z, -SH_C1 * x};
+            const float b1[4] = {SH_C2[0] * xy, SH_C2[1] * yz, SH_C2[2] * (2.f * zz - xx - yy), SH_C2[3] * xz};
+            const float b2[4] = {SH_C2[4] * (xx - yy), SH_C3[0] * y * (3.f * xx - yy), SH_C3[1] * xy * z, SH_C3[2] * y * (4.f * zz - xx - yy)};
+            const float b3[4] = {SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy), SH_C3[4] * x * (4.f * zz - xx - yy), SH_C3[5] * z * (xx - yy),
+                                 SH_C3[6] * x * (xx - 3.f * yy)};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float lo = (vl & 1) ? b1[k] : b0[k], hi = (vl & 1) ? b3[k] : b2[k];
+                const float f = (vl & 2) ? hi : lo;        // basis function 4 vl + k
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) c[k * 3 + ch] = f * b[3 + ch];
+            }
+        };
+        auto lane_of_quad = [](float v, auto J) {      // lane J of the quad, in all four
+            constexpr int j = decltype(J)::value;
+            return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), j * 0x55, 0xF, 0xF, false));
+        };
+        auto add_lane = [&](auto J) {
+            constexpr int j = decltype(J)::value;
+            float b[6], c[12];
+#pragma unroll
+            for (int k = 0; k < 6; k++) b[k] = lane_of_quad(e0[k], J);
+            coeffs(b, c);
+            if (VL + j < tab.n) {      // lane j's second view: from the quad's row
+                float c1[12];
+#pragma unroll
+                for (int k = 0; k < 6; k++) b[k] = s_in[gi * SH_ROW + j * 6 + k];
+                coeffs(b, c1);
+#pragma unroll
+                for (int k = 0; k < 12; k++) c[k] += c1[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 12; k++) o[k] = j == 0 ? c[k] : o[k] + c[k];
+        };
+        add_lane(std::integral_constant<int, 0>{}); add_lane(std::integral_constant<int, 1>{});
+        add_lane(std::integral_constant<int, 2>{}); add_lane(std::integral_constant<int, 3>{});
+        // the basis functions above the active degree D take no gradient
+        const int nbasis = (D + 1) * (D + 1);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (4 * vl + k >= nbasis) { o[3 * k] = 0.f; o[3 * k + 1] = 0.f; o[3 * k + 2] = 0.f; }
+        float4 *dst4 = reinterpret_cast<float4 *>(dL_dsh + (size_t)i * 48 + 12 * vl);
+        const bool add_in = (tab.v[0].accmask & CSPLAT_ACC_SH) != 0u;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float4 w4 = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+            if (add_in) { const float4 u = dst4[k]; w4.x += u.x; w4.y += u.y; w4.z += u.z; w4.w += u.w; }
+            dst4[k] = w4;
+        }
+    }
     if (vl == 0) {   // gradients of the parameters every view shares: one write (added to the buffer only if the first view was asked to)
         const unsigned accmask = tab.v[0].accmask;
         const K8View &w = tab.v[0];
 #define PUTS(ptr, idx, val, bit) do { if (smask & (bit)) { float *p_ = (ptr) + (idx); *p_ = (accmask & (bit)) ? *p_ + (val) : (val); } } while (0)
         PUTS(w.dL_dopacity, i, L_op, CSPLAT_ACC_OPACITY);
+        if (put3)
 #pragma unroll
-        for (int k = 0; k < 3; k++) PUTS(w.dL_dcolor, 3 * i + k, L_col[k], CSPLAT_ACC_COLOR);
+            for (int k = 0; k < 3; k++) PUTS(w.dL_dcolor, 3 * i + k, L_col[k], CSPLAT_ACC_COLOR);
 #pragma unroll
         for (int k = 0; k < 3; k++) PUTS(w.dL_dmean3D, 3 * i + k, L_m3[k], CSPLAT_ACC_MEAN3D);
+        if (put3)
 #pragma unroll
-        for (int k = 0; k < 6; k++) PUTS(w.dL_dcov3D, 6 * i + k, L_c6[k], CSPLAT_ACC_COV3D);
+            for (int k = 0; k < 6; k++) PUTS(w.dL_dcov3D, 6 * i + k, L_c6[k], CSPLAT_ACC_COV3D);
         if (w.dL_dscale)
 #pragma unroll
             for (int k = 0; k < 3; k++) PUTS(w.dL_dscale, 3 * i + k, L_sc[k], CSPLAT_ACC_SCALE);
@@ -316,20 +380,4 @@
     }   // i < P
     if constexpr (CAM)   // (every view of the call: each lane with i < P has written its rows of all the views it holds)
         for (int vi = 0; vi < tab.n; vi++) cam_block_sum<NT>(s_cam + vi * NG * CAM_NC, rows, s_cpart, cam_slabs->p[vi] + (size_t)bx * CAM_NC);
-    if (STAGE) {   // coalesced 16-byte stores of the workgroup's SH gradients
-        __syncthreads();
-        float4 *dst4 = reinterpret_cast<float4 *>(dL_dsh + (size_t)bx * NG * 48);
-        for (int t = threadIdx.x; t < rows * 12; t += NT) {
-            const int row = t / 12, c = (t - row * 12) * 4;
-            const float *sp = s_out + row * VL * SH_ROW + c;
-            float4 o = make_float4(sp[0], sp[1], sp[2], sp[3]);
-#pragma unroll
-            for (int v2 = 1; v2 < VL; v2++) {            // the rows of the Gaussian's other view lanes, in lane order
-                const float *sq = sp + v2 * SH_ROW;
-                o.x += sq[0]; o.y += sq[1]; o.z += sq[2]; o.w += sq[3];
-            }
-            if (tab.v[0].accmask & CSPLAT_ACC_SH) { const float4 u = dst4[t]; o.x += u.x; o.y += u.y; o.z += u.z; o.w += u.w; }
-            dst4[t] = o;
-        }
-    }
 #undef PUTL

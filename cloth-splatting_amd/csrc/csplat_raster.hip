@@ -2504,7 +2504,7 @@ struct FeatView {
     float *wpart;             // [slots][256]
     float *dL_dfeat_in;       // [P][nf] (written, or added when an earlier view of the call has the same buffer), NULL: not wanted
     int nf, P;
-    unsigned accmask;         // the view's CSPLAT_ACC_* / CSPLAT_SCRATCH_ZEROED bits, plus FEAT_ADD_IN
+    unsigned accmask;         // the view's CSPLAT_ACC_* / CSPLAT_SCRATCH_ZEROED / CSPLAT_K8_OUTPUTS_UNREAD bits, plus FEAT_ADD_IN
 };
 // not an ABI bit: an earlier group of views of the same call (backward_views_impl) already wrote dL_dfeat_in -- add to it
 constexpr unsigned FEAT_ADD_IN = 1u << 31;
@@ -3136,7 +3136,7 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_aa(CSPLAT_K8_ARGS, float 
 // K8 for ALL views of a step in one launch (csplat_backward_views).  The per-view kernels above add into shared gradient
 // buffers and therefore run one after the other behind the concurrent K7s (a tail of ~27 us per view).  Here a thread
 // keeps its Gaussian and loops over the views: inputs and SH rows are read once, gradients of parameters that all views
-// share are summed in registers (SH: in the LDS rows) and written once, per-view outputs (mean2D, conic, and mean3D /
+// share are summed in registers (SH: across the quad, see the body) and written once, per-view outputs (mean2D, conic, and mean3D /
 // rotation when every view has its own deformed copy) are written per view.  Same arithmetic per view as k_preprocess_bwd.
 constexpr int K8_MAX_VIEWS = RASTER_MAX_VIEWS;      // (the name csplat_k8_views_body.h sizes its LDS rows with)
 struct K8View {
@@ -3150,13 +3150,15 @@ struct K8View {
 struct K8Table {
     int n;
     unsigned sharedmask;   // CSPLAT_ACC_* bits of the outputs whose buffer is the same in every view
+    unsigned unread;       // != 0: every view carries CSPLAT_K8_OUTPUTS_UNREAD -- dL_dconic, dL_dcolor and dL_dcov3D are not stored
     const uint32_t *valid; // (csplat_forward_views_faith) 0 there: the forward left the views untouched -- nothing to differentiate
     K8View v[RASTER_MAX_VIEWS];
 };
 
 // VL lanes per Gaussian, lane vl takes the views vl, vl + VL, ...: with one lane per Gaussian the launch has P / 64 = 1564 waves (1.5 per
 // SIMD) that each walk V dependent load -> compute rounds; with VL = 4 it has four times the waves and (V <= 4) one round each.  The
-// sums over the views of the shared-parameter gradients cross the VL lanes with quad DPP adds (fixed association), the SH rows in LDS.
+// sums over the views of the shared-parameter gradients cross the VL lanes with quad DPP adds (fixed association); for the SH gradient
+// the lanes exchange (direction, dRGB) by DPP and each forms and stores a quarter of the Gaussian's row.
 // The batched K8's body lives in csplat_k8_views_body.h and is included into both kernels below, so that the default kernel is compiled
 // exactly as before (a shared __device__ body changed its register allocation).  DEPTH: k_preprocess_bwd_views_depth, the depth-gradient
 // path -- every view's record slot 9 (dL/dz, zero for a view without a depth gradient) adds dL/dz (view[2], view[6], view[10]) to dL/dmean3D.
@@ -3166,7 +3168,7 @@ struct K8Table {
 struct CamSlabs {
     float *p[RASTER_MAX_VIEWS];   // per view: the slab (rows of CAM_NC floats, one per workgroup)
 };
-template <int NT, int VL>
+template <int NT, int VL, bool UNREAD>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
                                                                const float *__restrict__ scales, float scale_mod,
                                                                int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
@@ -3180,7 +3182,7 @@ template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_depth(int P, int D, int M, const float *__restrict__ shs,
                                                                      const float *__restrict__ scales, float scale_mod,
                                                                      int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = true, CAM = false, AA = false;
+    constexpr bool DEPTH = true, CAM = false, AA = false, UNREAD = false;
     const CamSlabs *const cam_slabs = nullptr;
     const float *const aa_opacities = nullptr;
     (void)aa_opacities;
@@ -3191,7 +3193,7 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_cam(int P, int D, i
                                                                    const float *__restrict__ scales, float scale_mod,
                                                                    int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
                                                                    CamSlabs slabs) {
-    constexpr bool CAM = true, AA = false;
+    constexpr bool CAM = true, AA = false, UNREAD = false;
     const CamSlabs *const cam_slabs = &slabs;
     const float *const aa_opacities = nullptr;
     (void)aa_opacities;
@@ -3203,7 +3205,7 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_aa(int P, int D, in
                                                                   const float *__restrict__ scales, float scale_mod,
                                                                   int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
                                                                   CamSlabs slabs, const float *__restrict__ opacities) {
-    constexpr bool AA = true;
+    constexpr bool AA = true, UNREAD = false;
     const CamSlabs *const cam_slabs = &slabs;
     const float *const aa_opacities = opacities;
     (void)cam_slabs;
@@ -4590,6 +4592,8 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
             if (v[i].dL_dmean2D == v[j].dL_dmean2D || v[i].dL_dconic == v[j].dL_dconic || v[i].scratch == v[j].scratch) return false;
     tab.n = V;
     tab.sharedmask = sharedmask;
+    tab.unread = CSPLAT_K8_OUTPUTS_UNREAD;
+    for (int i = 0; i < V; i++) tab.unread &= v[i].accmask;
     tab.valid = v[0].valid;
     for (int i = 0; i < V; i++) {
         const csplat_view &w = v[i];
@@ -4675,7 +4679,9 @@ static int launch_k8_views(int V, const csplat_view *v, const K8Table &tab, bool
     } else if (depth) {
         go(k_preprocess_bwd_views_depth<128, 4>);
     } else {
-        go(k_preprocess_bwd_views<128, 4>);
+        // (the flagship form: with every view's CSPLAT_K8_OUTPUTS_UNREAD the three outputs' running sums leave the registers as well)
+        if (tab.unread) go(k_preprocess_bwd_views<128, 4, true>);
+        else go(k_preprocess_bwd_views<128, 4, false>);
     }
     LAUNCH_CHECK();
     return 0;
@@ -4690,7 +4696,7 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     CSPLAT_REQUIRE(!feat || whole, "csplat_backward_views_parts: feature / alpha gradients are taken by the whole call only");
     bool shared = false;
-    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)CSPLAT_SCRATCH_ZEROED) != 0u;
+    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)(CSPLAT_SCRATCH_ZEROED | CSPLAT_K8_OUTPUTS_UNREAD)) != 0u;
     K8Table tab;
     const bool one_k8 = shared && k8_views_table(V, v, tab);
     CSPLAT_REQUIRE(whole || one_k8, "csplat_backward_views_parts: only the one-launch-per-stage path can be cut into parts");
@@ -4867,7 +4873,7 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
     const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
     hipStream_t join = (hipStream_t)join_stream;
     bool shared = false;   // any view adding into another view's buffers: all K8 run on the join stream, in view order
-    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)CSPLAT_SCRATCH_ZEROED) != 0u;
+    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)(CSPLAT_SCRATCH_ZEROED | CSPLAT_K8_OUTPUTS_UNREAD)) != 0u;
     K8Table tab;
     const bool one_k8 = shared && k8_views_table(V, v, tab);
     // K7 of all views in ONE launch on the join stream (plus one launch clearing the records) when the views are alike

@@ -406,6 +406,7 @@ _side_streams = {}
 _ACC_SCRATCH = {}
 _n.TICKET_CACHES.append(_ACC_SCRATCH)
 SCRATCH_ZEROED = 256       # csplat.h: CSPLAT_SCRATCH_ZEROED
+K8_OUTPUTS_UNREAD = 512    # csplat.h: CSPLAT_K8_OUTPUTS_UNREAD
 
 
 def _acc_scratch(dev, P, slot):
@@ -766,6 +767,10 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             ent = {"scratch": acc_buf if zeroed else reserve(int(_n.lib.csplat_backward_scratch_bytes(P, v.layout_rendered)) // 4 + 64),
                    "dL_dmean2D": reserve(3 * P), "dL_dconic": reserve(4 * P), "mask": SCRATCH_ZEROED if zeroed else 0, "ret": {}}
             ent["ret"][1] = (ent["dL_dmean2D"], (P, 3))
+            # dL_dconic is never handed back; dL_dcolor / dL_dcov3D only to a precomputed colour / covariance input: without those the
+            # batched K8 may leave the three unwritten (they keep their place in the allocation: address space, no traffic)
+            if colors_precomp is None and cov3Ds is None:
+                ent["mask"] |= K8_OUTPUTS_UNREAD
             shapes = {0: (P, 3), 2: (P, M, 3) if sh is not None else None, 3: (P, 3), 4: (P, 1),
                       5: (P, 3) if scales is not None else None, 6: (P, 4) if rotations is not None else None, 7: (P, 6)}
             present = {0: True, 2: sh is not None, 3: colors_precomp is not None, 4: True, 5: scales is not None,

@@ -156,13 +156,19 @@ int csplat_forward_finish(int ticket, float *out_color, float *out_depth, int *n
  * num_rendered read, and in the backward runs the views' K7 concurrently.  accmask (CSPLAT_ACC_*): gradient outputs of
  * this view that are ADDED to a buffer an earlier view of the same call wrote (a parameter shared by several views then
  * needs no per-view temporaries and no summation launches); when any view accumulates, K8 of all views runs on the join
- * stream in view order.  dL_dmean2D / dL_dconic are always written.  Field meanings as in csplat_forward / csplat_backward. */
+ * stream in view order.  dL_dmean2D is always written, dL_dconic unless CSPLAT_K8_OUTPUTS_UNREAD lets it be skipped.  Field meanings as in csplat_forward / csplat_backward. */
 enum { CSPLAT_ACC_OPACITY = 1, CSPLAT_ACC_COLOR = 2, CSPLAT_ACC_MEAN3D = 4, CSPLAT_ACC_COV3D = 8, CSPLAT_ACC_SH = 16,
        CSPLAT_ACC_SCALE = 32, CSPLAT_ACC_ROT = 64,
        /* not an accumulate bit: the view's `scratch` records are ALL ZERO on entry and the call leaves them all zero again (K8 clears
         * every record it has consumed) -- a caller that keeps the buffer from step to step on one stream then needs no clearing launch per
         * step (25.6 MB of zero fill for four views of 100k Gaussians).  Without the bit the library clears the records itself. */
-       CSPLAT_SCRATCH_ZEROED = 256 };
+       CSPLAT_SCRATCH_ZEROED = 256,
+       /* not an accumulate bit either: the caller does not read dL_dconic, dL_dcolor and dL_dcov3D of this call, and the library MAY leave
+        * them unwritten.  The three pointers stay required and valid (every per-view launch still writes them).  The one-launch K8 of
+        * csplat_backward_views / _parts skips their stores when ALL views of the call carry the bit: each of the three buffers is then
+        * either written in full or not touched at all.  A caller that passes scales and rotations (no cov3D_precomp) and SH (no
+        * colors_precomp) has no use for the three and should set it.  An older caller does not, and gets every output as before. */
+       CSPLAT_K8_OUTPUTS_UNREAD = 512 };
 #define CSPLAT_MAX_FEATURES 6    /* ABI 9: csplat_view.n_features <= 6 (record slots 10..15 of the compositing backward) */
 /* csplat_view.prefiltered is a bit word.  Bit 0 is upstream's `prefiltered` flag and is ignored, as before.
  * CSPLAT_ANTIALIAS (bit 1): antialiased rendering with opacity compensation (upstream's `antialiasing` option).  K1 widens every projected
