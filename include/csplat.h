@@ -279,6 +279,14 @@ int csplat_backward_slice_rows(int P, int slice, int nslices, int64_t *row_lo, i
  * the counts stay on the device, at csplat_image_info_offset(W, H) inside each view's IMAGE chunk (u32 x 3).  The views must qualify
  * for the one-launch-per-stage path (2..8 views sharing P, SH, opacities, scales, image size); otherwise an error is returned. */
 int csplat_forward_views_faith(int V, csplat_view *views, csplat_alloc_fn alloc, void *join_stream, const uint32_t *caps, uint32_t *valid);
+/* Images of more than 12288 tiles (16 x 16 pixels each; 2048 x 1536 is the largest 4:3 image within it): a view of that size has no tile-bucket
+ * table and does not qualify for the one-launch-per-stage forward.  csplat_forward_views and csplat_forward_views_deferred run such views
+ * one by one through the global sort, with the same results; _deferred completes the call itself (*pending = 0, nothing to settle) however
+ * often the shape repeats.  csplat_forward_views_faith refuses them (the views do not qualify: the error its comment names).
+ * csplat_backward_views, csplat_backward_views_parts, csplat_visibility_views and the feature / alpha images do not depend on the tile
+ * count. */
+
+/* byte offset of a view's counts (u32 x 3, see csplat_forward_views_faith) inside its IMAGE chunk */
 size_t csplat_image_info_offset(int W, int H);
 
 /* Gaussian visibility and the top-contributor map (forward only, no gradient; ABI 9, csplat_view unchanged).  With w_i(pix) = T_i alpha_i,

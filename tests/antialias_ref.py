@@ -76,11 +76,10 @@ def render(o, means3D, means2D, opacities, V, Pm, campos, bg, features=None, shs
     depth = pv[:, 2]
     h = aa_factor(cov2[:, 0, 0], b, cov2[:, 1, 1])
     op = opacities.reshape(-1) * h if antialiasing else opacities.reshape(-1)
-    color = torch.zeros(3, H, W, dtype=f64)
-    dimg = torch.zeros(1, H, W, dtype=f64)
     F = features.shape[1] if features is not None else 0
-    fimg = torch.zeros(F, H, W, dtype=f64)
-    aimg = torch.zeros(1, H, W, dtype=f64)
+    # every non-empty tile's pixels (flat indices) and values are collected and written into the images ONCE behind the loop: a slice assignment per
+    # tile costs autograd a copy of the whole image per tile in the backward (hours at 30 000 tiles); the values are the same
+    where, cparts, dparts, fparts, aparts = [], [], [], [], []
     gx = (W + 15) // 16
     ids_all = torch.from_numpy(o.ids.astype(np.int64))
     ncon = torch.from_numpy(o.n_contrib.astype(np.int64))
@@ -91,12 +90,13 @@ def render(o, means3D, means2D, opacities, V, Pm, campos, bg, features=None, shs
         x1, y1 = min(x0 + 16, W), min(y0 + 16, H)
         if x1 <= x0 or y1 <= y0:
             continue
-        ys, xs = torch.meshgrid(torch.arange(y0, y1), torch.arange(x0, x1), indexing="ij")
-        xs = xs.reshape(-1).to(f64); ys = ys.reshape(-1).to(f64)
-        npx = xs.shape[0]
-        if e <= s:
-            color[:, y0:y1, x0:x1] = bg[:, None, None].expand(3, y1 - y0, x1 - x0)
+        if e <= s:          # (an empty tile keeps the background the colour image starts from)
             continue
+        ys, xs = torch.meshgrid(torch.arange(y0, y1), torch.arange(x0, x1), indexing="ij")
+        xs = xs.reshape(-1); ys = ys.reshape(-1)
+        npx = xs.shape[0]
+        where.append(ys * W + xs)
+        xs = xs.to(f64); ys = ys.to(f64)
         g = ids_all[s:e]
         dx = px[g][None, :] - xs[:, None]
         dy = py[g][None, :] - ys[:, None]
@@ -124,11 +124,17 @@ def render(o, means3D, means2D, opacities, V, Pm, campos, bg, features=None, shs
         Tbefore = torch.cat([torch.ones(npx, 1, dtype=f64), Tincl[:, :-1]], 1)
         w = alpha * Tbefore
         Cpix = w @ rgb[g] + Tincl[:, -1][:, None] * bg[None, :]
-        color[:, y0:y1, x0:x1] = Cpix.T.reshape(3, y1 - y0, x1 - x0)
-        dimg[0, y0:y1, x0:x1] = (w @ depth[g]).reshape(y1 - y0, x1 - x0)
-        if F:
-            fimg[:, y0:y1, x0:x1] = (w @ features[g]).T.reshape(F, y1 - y0, x1 - x0)
-        aimg[0, y0:y1, x0:x1] = (1.0 - Tincl[:, -1]).reshape(y1 - y0, x1 - x0)
+        cparts.append(Cpix.T)
+        dparts.append(w @ depth[g])
+        fparts.append((w @ features[g]).T if F else torch.zeros(0, npx, dtype=f64))
+        aparts.append(1.0 - Tincl[:, -1])
+    at = torch.cat(where) if where else None
+
+    def image(parts, C, base=None):      # [C, H, W] from the tiles' [C, pixels] pieces, over `base` (zeros) where no tile has a list
+        base = torch.zeros(C, H * W, dtype=f64) if base is None else base
+        return (base.index_copy(1, at, torch.cat(parts, 1)) if where else base.clone()).reshape(C, H, W)
+    color, fimg = image(cparts, 3, bg[:, None].expand(3, H * W)), image(fparts, F)
+    dimg, aimg = image([p_[None] for p_ in dparts], 1), image([p_[None] for p_ in aparts], 1)
     return color, dimg, (fimg if F else None), aimg, ncon_out, dict(h=h, cov2=cov2.detach())
 
 

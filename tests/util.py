@@ -83,10 +83,11 @@ def image_err(a, b, outlier_frac=1e-4, outlier_tol=1e-2):
     scale = np.abs(b).max() + 1e-30
     d = np.abs(a - b) / scale
     per_px = d.reshape(-1, d.shape[-2] * d.shape[-1]).max(0) if d.ndim == 3 else d.reshape(-1)
-    k = int(np.ceil(outlier_frac * per_px.size))
-    srt = np.sort(per_px)
-    assert srt[-1] <= outlier_tol, f"pixel error {srt[-1]:.3e} exceeds the threshold-tie bound {outlier_tol}"
-    return float(srt[-(k + 1)])
+    k = min(int(np.ceil(outlier_frac * per_px.size)), per_px.size - 1)     # (a 1-pixel image: nothing is exempt)
+    worst = per_px.max()
+    assert worst <= outlier_tol, f"pixel error {worst:.3e} exceeds the threshold-tie bound {outlier_tol}"
+    at = per_px.size - (k + 1)      # the (k + 1)-th largest, by selection (a full sort of a 17 M-pixel image costs 1.5 s a call)
+    return float(np.partition(per_px, at)[at])
 
 
 # ---------------------------------------------------------------- GPU side (imports torch lazily)
