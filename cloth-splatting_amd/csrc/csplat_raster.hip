@@ -555,76 +555,85 @@ __global__ __launch_bounds__(256) void k_tile_colscan_views(int tiles, int nb, K
 // single workgroup: exclusive scan of the per-tile totals -> tile ranges, R, longest list
 constexpr int INFO_BUSY = 64;   // word offset of the non-empty-tile list inside the info block: [count, tile ids ...]
 constexpr int LPT_BINS = 512;   // bins of the longest-list-first order (list length / 16, BUCKET_CAP / 16 = 512)
+constexpr int TSCAN_ITEMS = BUCKET_TILES / 1024;   // consecutive tiles per thread of the tile scan, at most
 __device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__restrict__ cnt, int2 *__restrict__ ranges,
                                                uint32_t *__restrict__ info, volatile uint32_t *mailbox, uint32_t tag) {
     // ONE scan over the tiles of two running sums packed in 64 bits: low word = instances (the tile ranges), high word = number of
-    // non-empty tiles (their compact list: the tile sort launches over it instead of over a grid that is ~90 % empty on scene_1)
+    // non-empty tiles (their compact list: the tile sort launches over it instead of over a grid that is ~90 % empty on scene_1).
+    // A thread takes `per` CONSECUTIVE tiles (tiles <= BUCKET_TILES on the bucketed path, the only caller: at most TSCAN_ITEMS), so the
+    // counts are read from memory once, in one round trip, the workgroup scans once (two barriers, where 1024 tiles a round took three
+    // rounds of three on the 2500 tiles of an 800 x 800 image), and the counts stay in registers for the longest-first pass below --
+    // which walks the tiles, not the busy list, so nothing written here is read back.
     __shared__ unsigned long long s_w[17];
     __shared__ uint32_t s_max[16];
+    __shared__ uint32_t s_bin[LPT_BINS + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long carry = 0ull;
-    uint32_t mx = 0;
     uint32_t *busy = info + INFO_BUSY;
-    for (int base = 0; base < tiles; base += 1024) {
-        const int t = base + threadIdx.x;
-        const uint32_t c = t < tiles ? cnt[t] : 0u;
-        mx = max(mx, c);
-        const unsigned long long v0 = (unsigned long long)c | ((unsigned long long)(c ? 1u : 0u) << 32);
-        unsigned long long inc = v0;
+    uint32_t *lpt = busy + tiles + 4;
+    const int per = (tiles + 1023) / 1024, t0 = threadIdx.x * per;
+    uint32_t c[TSCAN_ITEMS];
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        if (w == 0) {
-            unsigned long long v = lane < 16 ? s_w[lane] : 0ull, vi = v;
+    for (int k = 0; k < TSCAN_ITEMS; k++) c[k] = (k < per && t0 + k < tiles) ? cnt[t0 + k] : 0u;
+    for (int i = threadIdx.x; i <= LPT_BINS; i += 1024) s_bin[i] = 0u;
+    uint32_t mx = 0;
+    unsigned long long v0 = 0ull;
 #pragma unroll
-            for (int d = 1; d < 16; d <<= 1) { const unsigned long long o = __shfl_up(vi, d, 64); if (lane >= d) vi += o; }
-            if (lane < 16) s_w[lane] = vi - v;
-            if (lane == 15) s_w[16] = vi;
-        }
-        __syncthreads();
-        const unsigned long long exl = carry + s_w[w] + inc - v0;
-        const uint32_t ex = (uint32_t)exl;
-        if (t < tiles) {
-            ranges[t] = c ? make_int2((int)ex, (int)(ex + c)) : make_int2(0, 0);
-            if (c) busy[1 + (uint32_t)(exl >> 32)] = (uint32_t)t;
-            else busy[tiles + 4 + tiles - 1 - (t - (int)(uint32_t)(exl >> 32))] = (uint32_t)t;   // launch-order list: empty tiles from the end
-        }
-        carry += s_w[16];
-        __syncthreads();
+    for (int k = 0; k < TSCAN_ITEMS; k++) { mx = max(mx, c[k]); v0 += (unsigned long long)c[k] | ((unsigned long long)(c[k] ? 1u : 0u) << 32); }
+    unsigned long long inc = v0;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();                                       // (also: the zeroed bins)
+    if (w == 0) {
+        unsigned long long v = lane < 16 ? s_w[lane] : 0ull, vi = v;
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) { const unsigned long long o = __shfl_up(vi, d, 64); if (lane >= d) vi += o; }
+        if (lane < 16) s_w[lane] = vi - v;
+        if (lane == 15) s_w[16] = vi;
     }
+    __syncthreads();
+    const unsigned long long carry = s_w[16];
+    {
+        unsigned long long exl = s_w[w] + inc - v0;
+#pragma unroll
+        for (int k = 0; k < TSCAN_ITEMS; k++) {
+            const int t = t0 + k;
+            if (k < per && t < tiles) {
+                const uint32_t ex = (uint32_t)exl, nz = (uint32_t)(exl >> 32);
+                ranges[t] = c[k] ? make_int2((int)ex, (int)(ex + c[k])) : make_int2(0, 0);
+                if (c[k]) {
+                    busy[1 + nz] = (uint32_t)t;
+                    // length bins of the longest-first order below (a counting sort on length / 16)
+                    atomicAdd(&s_bin[LPT_BINS - 1 - min(c[k] >> 4, (uint32_t)(LPT_BINS - 1))], 1u);
+                } else {
+                    lpt[tiles - 1 - (t - (int)nz)] = (uint32_t)t;   // launch-order list: empty tiles from the end
+                }
+                exl += (unsigned long long)c[k] | ((unsigned long long)(c[k] ? 1u : 0u) << 32);
+            }
+        }
+    }
+    __syncthreads();
     // the non-empty tiles once more, LONGEST LIST FIRST (a counting sort on length / 16): the launch order of the compositing forward.
     // Its waves -- one per (tile, 4x4 block), ~14 k of them with work on scene_1 for 8192 wave slots, 40-75 us each -- are handed out in
     // grid order to whichever slot frees: in tile order the longest lists (the middle of the image) start in the middle of the launch and
     // the slots that draw three of them in a row set the kernel's duration while the others idle (4.5 of 8 waves resident on average);
-    // longest first, what is still running at the end are the short lists.
+    // longest first, what is still running at the end are the short lists.  The tile sort walks the same list.
     {
-        __shared__ uint32_t s_bin[LPT_BINS + 1];
-        const uint32_t nbusy = (uint32_t)(carry >> 32);
-        uint32_t *lpt = busy + tiles + 4;          // (its tail, the empty tiles, was filled in the loop above)
-        for (int i = threadIdx.x; i <= LPT_BINS; i += 1024) s_bin[i] = 0u;
-        __syncthreads();                                   // (also: the busy list written above is visible to the whole workgroup)
-        for (uint32_t i = threadIdx.x; i < nbusy; i += 1024) {
-            const uint32_t c = cnt[busy[1 + i]];
-            atomicAdd(&s_bin[LPT_BINS - 1 - min(c >> 4, (uint32_t)(LPT_BINS - 1))], 1u);
-        }
-        __syncthreads();
         if (w == 0) {                                      // exclusive scan of the bins by one wave: 8 consecutive bins per lane
             uint32_t v[LPT_BINS / 64], run = 0;
 #pragma unroll
             for (int k = 0; k < LPT_BINS / 64; k++) { v[k] = s_bin[lane * (LPT_BINS / 64) + k]; run += v[k]; }
-            uint32_t inc = run;
+            uint32_t binc = run;
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64); if (lane >= d) inc += o; }
-            uint32_t base = inc - run;
+            for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)binc, d, 64); if (lane >= d) binc += o; }
+            uint32_t base = binc - run;
 #pragma unroll
             for (int k = 0; k < LPT_BINS / 64; k++) { s_bin[lane * (LPT_BINS / 64) + k] = base; base += v[k]; }
         }
         __syncthreads();
-        for (uint32_t i = threadIdx.x; i < nbusy; i += 1024) {
-            const uint32_t t = busy[1 + i], c = cnt[t];
-            lpt[atomicAdd(&s_bin[LPT_BINS - 1 - min(c >> 4, (uint32_t)(LPT_BINS - 1))], 1u)] = t;
-        }
+#pragma unroll
+        for (int k = 0; k < TSCAN_ITEMS; k++)
+            if (c[k]) lpt[atomicAdd(&s_bin[LPT_BINS - 1 - min(c[k] >> 4, (uint32_t)(LPT_BINS - 1))], 1u)] = (uint32_t)(t0 + k);
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
@@ -727,7 +736,6 @@ __global__ __launch_bounds__(BUCKET_G) void k_emit_bucket_views(int P, int tiles
 
 constexpr int TSORT_THREADS = 1024;
 constexpr int TSORT_WAVES = TSORT_THREADS / 64;
-constexpr int TSORT_ITEMS = BUCKET_CAP / TSORT_THREADS;   // 8 keys per lane at most
 constexpr int TSORT_NB = 4 * TSORT_THREADS;               // interpolation buckets: every thread owns 4 consecutive ones
 constexpr int TSORT_GRID = 512;                           // workgroups per view striding over the non-empty tiles
 constexpr int TSORT_LONG = 64;                            // most keys in one bucket before the tile takes the radix fallback
@@ -751,6 +759,7 @@ __host__ __device__ inline size_t tsort_lds_bytes(int longest) {
 //     csplat_debug_flags bit 11): the round-2 stable LSD radix sort -- keys live in registers between passes (lane l of wave w
 //     owns positions w*64*items + i*64 + l), every pass ranks the 8-bit digit with 8 ballots per key and per-wave LDS counters.
 // mode: bit 0 = ids < 2^24 (radix: skip byte 3), bit 1 = radix only, bit 2 = bucket limit 1 (tests the fallback path)
+template <int ITEMS>
 __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, const uint64_t *__restrict__ comp,
                                                uint64_t *__restrict__ keys_sorted,
                                                uint32_t *__restrict__ ids_sorted, int mode, int tile) {
@@ -762,13 +771,16 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
     const int items = (n + TSORT_THREADS - 1) / TSORT_THREADS;
     uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_key + (size_t)items * TSORT_THREADS);   // [TSORT_NB] buckets / [TSORT_WAVES][256]
     uint32_t *s_dig = s_cnt + TSORT_NB + 4;                                                   // [256] + [4] (+ 4 spare)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // (lane and wave are re-derived for every tile behind an empty asm: hoisted out of the callers' tile loop, what depends on them alone
+    //  -- a dozen offsets and masks -- stays live across the whole sort and no longer fits the 64 registers of two workgroups per CU)
+    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    asm volatile("" : "+v"(lane), "+v"(w));
     const int wbase = w * items * 64;
     const uint64_t lt = (1ull << lane) - 1ull;
-    uint64_t key[TSORT_ITEMS];
-    uint32_t rank[TSORT_ITEMS];
+    uint64_t key[ITEMS];
+    uint32_t rank[ITEMS];
 #pragma unroll
-    for (int i = 0; i < TSORT_ITEMS; i++) {
+    for (int i = 0; i < ITEMS; i++) {
         const int idx = wbase + i * 64 + lane;
         key[i] = (i < items && idx < n) ? comp[r.x + idx] : ~0ull;
     }
@@ -780,7 +792,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         // ---- interpolation bucket sort
         uint32_t dmin = ~0u, dmax = 0u;
 #pragma unroll
-        for (int i = 0; i < TSORT_ITEMS; i++) {
+        for (int i = 0; i < ITEMS; i++) {
             const int idx = wbase + i * 64 + lane;
             if (i < items && idx < n) { const uint32_t d = (uint32_t)(key[i] >> 32); dmin = min(dmin, d); dmax = max(dmax, d); }
         }
@@ -799,9 +811,9 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
             // monotone map of the depth bits onto [0, TSORT_NB): uint -> float conversion, a positive scale and truncation
             // are all non-decreasing, so bucket order never contradicts depth order
             const float scale = (float)TSORT_NB / ((float)(dmax - dmin) + 1.0f);
-            uint32_t bs[TSORT_ITEMS];                         // bucket << 16 | slot inside the bucket
+            uint32_t bs[ITEMS];                         // bucket << 16 | slot inside the bucket
 #pragma unroll
-            for (int i = 0; i < TSORT_ITEMS; i++) {
+            for (int i = 0; i < ITEMS; i++) {
                 const int idx = wbase + i * 64 + lane;
                 if (i < items && idx < n) {
                     const uint32_t b = min((uint32_t)(TSORT_NB - 1), (uint32_t)((float)((uint32_t)(key[i] >> 32) - dmin) * scale));
@@ -823,7 +835,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
             if (threadIdx.x == 0) s_cnt[TSORT_NB] = (uint32_t)n;
             __syncthreads();
 #pragma unroll
-            for (int i = 0; i < TSORT_ITEMS; i++) {
+            for (int i = 0; i < ITEMS; i++) {
                 const int idx = wbase + i * 64 + lane;
                 if (i < items && idx < n) s_key[s_cnt[bs[i] >> 16] + (bs[i] & 0xFFFFu)] = key[i];
             }
@@ -832,9 +844,9 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
             // (independent LDS reads, a bucket holds ~1 key on average; the composite keys are unique) ...
             const int limit = (mode & 4) ? 1 : TSORT_LONG;
             bool long_run = false;
-            uint32_t dst[TSORT_ITEMS];
+            uint32_t dst[ITEMS];
 #pragma unroll
-            for (int i = 0; i < TSORT_ITEMS; i++) {
+            for (int i = 0; i < ITEMS; i++) {
                 const int idx = wbase + i * 64 + lane;
                 if (i < items && idx < n) {
                     const uint32_t b = bs[i] >> 16;
@@ -842,20 +854,21 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
                     uint32_t rk = 0;
                     if (cb > (uint32_t)limit) long_run = true;
                     else
-                        for (uint32_t j = 0; j < cb; j++) rk += s_key[lo + j] < key[i] ? 1u : 0u;
+#pragma unroll 1
+                        for (uint32_t j = 0; j < cb; j++) rk += s_key[lo + j] < key[i] ? 1u : 0u;     // (cb ~ 1: unrolled, it costs 30 registers)
                     dst[i] = lo + rk;
                 }
             }
             if (!__syncthreads_or(long_run)) {
                 // ... and moves there (the keys are still in registers: in place, behind a barrier)
 #pragma unroll
-                for (int i = 0; i < TSORT_ITEMS; i++) {
+                for (int i = 0; i < ITEMS; i++) {
                     const int idx = wbase + i * 64 + lane;
                     if (i < items && idx < n) s_key[dst[i]] = key[i];
                 }
                 __syncthreads();
 #pragma unroll
-                for (int i = 0; i < TSORT_ITEMS; i++) {
+                for (int i = 0; i < ITEMS; i++) {
                     const int idx = wbase + i * 64 + lane;
                     if (i < items && idx < n) {
                         const uint64_t k = s_key[idx];
@@ -879,7 +892,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         const uint64_t k0 = comp[r.x];
         uint64_t dv = 0ull;
 #pragma unroll
-        for (int i = 0; i < TSORT_ITEMS; i++) {
+        for (int i = 0; i < ITEMS; i++) {
             const int idx = wbase + i * 64 + lane;
             if (i < items && idx < n) dv |= key[i] ^ k0;
         }
@@ -894,7 +907,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         for (int t = threadIdx.x; t < TSORT_WAVES * 256; t += TSORT_THREADS) s_cnt[t] = 0u;
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < TSORT_ITEMS; i++) {
+        for (int i = 0; i < ITEMS; i++) {
             if (i < items) {   // workgroup-uniform
                 const int idx = wbase + i * 64 + lane;
                 const bool valid = idx < n;
@@ -913,11 +926,10 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
             }
         }
         __syncthreads();
-        uint32_t c[TSORT_WAVES];
-        uint32_t tot = 0;
+        uint32_t tot = 0;   // (the per-wave counts are read again below instead of kept: 16 registers of the fallback the bucket path would pay for)
         if (threadIdx.x < 256) {
 #pragma unroll
-            for (int k = 0; k < TSORT_WAVES; k++) { c[k] = s_cnt[k * 256 + threadIdx.x]; tot += c[k]; }
+            for (int k = 0; k < TSORT_WAVES; k++) tot += s_cnt[k * 256 + threadIdx.x];
             uint32_t inc = tot;   // inclusive scan of the digit totals over 4 waves of 64 digits
 #pragma unroll
             for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o = __shfl_up(inc, dd, 64); if (lane >= dd) inc += o; }
@@ -929,11 +941,11 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
             uint32_t run = s_dig[threadIdx.x];
             for (int k = 0; k < w; k++) run += s_dig[256 + k];
 #pragma unroll
-            for (int k = 0; k < TSORT_WAVES; k++) { s_cnt[k * 256 + threadIdx.x] = run; run += c[k]; }
+            for (int k = 0; k < TSORT_WAVES; k++) { const uint32_t ck = s_cnt[k * 256 + threadIdx.x]; s_cnt[k * 256 + threadIdx.x] = run; run += ck; }
         }
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < TSORT_ITEMS; i++) {
+        for (int i = 0; i < ITEMS; i++) {
             if (i < items) {
                 const int idx = wbase + i * 64 + lane;
                 if (idx < n) {
@@ -944,7 +956,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         }
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < TSORT_ITEMS; i++) {
+        for (int i = 0; i < ITEMS; i++) {
             const int idx = wbase + i * 64 + lane;
             if (i < items && idx < n) key[i] = s_key[idx];
         }
@@ -964,7 +976,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         // (s_key now holds the keys in depth order, key[] = this lane's elements of it)
         bool long_run = false;
 #pragma unroll
-        for (int i = 0; i < TSORT_ITEMS; i++) {
+        for (int i = 0; i < ITEMS; i++) {
             const int idx = wbase + i * 64 + lane;
             if (i < items && idx + 1 < n) {
                 const uint32_t d = (uint32_t)(key[i] >> 32);
@@ -986,7 +998,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         full = __syncthreads_or(long_run);
         if (!full) {
 #pragma unroll
-            for (int i = 0; i < TSORT_ITEMS; i++) {
+            for (int i = 0; i < ITEMS; i++) {
                 const int idx = wbase + i * 64 + lane;
                 if (i < items && idx < n) key[i] = s_key[idx];
             }
@@ -996,7 +1008,7 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         for (int byte = 0; byte < 8; byte++)
             if (varies(byte)) pass(byte * 8);
 #pragma unroll
-    for (int i = 0; i < TSORT_ITEMS; i++) {
+    for (int i = 0; i < ITEMS; i++) {
         const int idx = wbase + i * 64 + lane;
         if (i < items && idx < n) {
             keys_sorted[r.x + idx] = hi | (key[i] >> 32);
@@ -1004,24 +1016,34 @@ __device__ __forceinline__ void tile_sort_body(const int2 *__restrict__ ranges, 
         }
     }
 }
-__global__ __launch_bounds__(TSORT_THREADS) void k_tile_sort(const int2 *__restrict__ ranges, const uint64_t *__restrict__ comp,
+// ITEMS = keys per lane the instantiation holds in registers (the host picks the smallest that takes the launch's longest list:
+// tile_sort_launch).  The workgroups stride over the non-empty tiles LONGEST LIST FIRST (the order the tile scan leaves for K6).
+// DENSE: compiled for 8 waves per SIMD (64 VGPRs), so that TWO workgroups share a CU.  A tile's sort is a chain of ~10 workgroup barriers
+// and a second workgroup fills the waits, but the 64-register code takes a fifth longer per tile (MI355X, 800 x 800 scene_1: 14.4 against
+// 12.0 us for the 267 tiles of one view, 20.5 / 20.9 for two views, 26.2 / 28.3 for three, 31.1 / 34.6 for four): the host takes it for
+// launches of more than 2.5 non-empty tiles per CU (tsort_dense).
+template <int ITEMS, bool DENSE>
+__global__ __launch_bounds__(TSORT_THREADS, DENSE ? 8 : 4) void k_tile_sort(const int2 *__restrict__ ranges, const uint64_t *__restrict__ comp,
                                                               uint64_t *__restrict__ keys_sorted,
-                                                              uint32_t *__restrict__ ids_sorted, const uint32_t *__restrict__ info, int mode) {
-    // the workgroups stride over the compact list of non-empty tiles the tile scan left behind the counts
-    const uint32_t *busy = info + INFO_BUSY;
+                                                              uint32_t *__restrict__ ids_sorted, const uint32_t *__restrict__ info, int tiles, int mode) {
+    const uint32_t *busy = info + INFO_BUSY, *lpt = busy + tiles + 4;
     const int nbusy = (int)busy[0];
     for (int b = blockIdx.x; b < nbusy; b += gridDim.x) {
-        tile_sort_body(ranges, comp, keys_sorted, ids_sorted, mode, (int)busy[1 + b]);
+        tile_sort_body<ITEMS>(ranges, comp, keys_sorted, ids_sorted, mode, (int)lpt[b]);
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(TSORT_THREADS) void k_tile_sort_views(P2Table tab, int mode) {
-    const P2View &w = tab.v[blockIdx.y];
+template <int ITEMS, bool DENSE>
+__global__ __launch_bounds__(TSORT_THREADS, DENSE ? 8 : 4) void k_tile_sort_views(P2Table tab, int tiles, int mode) {
+    // (workgroups are handed out in the order of their linear index: view = index % views puts the longest lists of EVERY view in
+    //  front, where blockIdx.y = view started the last view's longest lists behind all the others' short ones)
+    const int lin = blockIdx.y * gridDim.x + blockIdx.x, nv = gridDim.y;
+    const P2View &w = tab.v[lin % nv];
     if (!p2_live(w)) return;
-    const uint32_t *busy = w.info + INFO_BUSY;
+    const uint32_t *busy = w.info + INFO_BUSY, *lpt = busy + tiles + 4;
     const int nbusy = (int)busy[0];
-    for (int b = blockIdx.x; b < nbusy; b += gridDim.x) {
-        tile_sort_body(w.ranges, w.keys_u, w.keys_sorted, w.ids_sorted, mode, (int)busy[1 + b]);
+    for (int b = lin / nv; b < nbusy; b += gridDim.x) {
+        tile_sort_body<ITEMS>(w.ranges, w.keys_u, w.keys_sorted, w.ids_sorted, mode, (int)lpt[b]);
         __syncthreads();
     }
 }
@@ -3793,15 +3815,69 @@ static int finish_read(const FwdTicket &t, uint32_t host_info[3], hipStream_t la
     CSPLAT_REQUIRE(host_info[0] <= 0x7FFFFFFFu, "csplat_forward: more than 2^31 - 1 tile instances (Gaussian x tile pairs) in one view");
     return 0;
 }
+// The tile sort's instantiations: keys per lane held in registers -- the launch takes the smallest that holds its longest list (the exact
+// count, or the speculative capacity Lcap), so a launch of short lists is not charged the registers of an 8192-key one -- and, up to 6
+// keys per lane (two workgroups' LDS fits a CU up to there), the two-workgroups-per-CU form (see k_tile_sort).
+#define TSORT_FOR_ITEMS(X) X(2) X(4) X(6) X(8)
+static int tsort_items(uint32_t longest) {
+    const uint32_t items = (longest + TSORT_THREADS - 1) / TSORT_THREADS;
+    return items <= 2 ? 2 : items <= 4 ? 4 : items <= 6 ? 6 : 8;
+}
+// busy: non-empty tiles of the whole launch (exact, or the capacity a speculative launch was sized for)
+static bool tsort_dense(int items, uint64_t busy) {
+    static int s_cus = 0;
+    if (s_cus <= 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&s_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || s_cus <= 0)
+            s_cus = 256;
+        (void)hipGetLastError();
+    }
+    return items <= 6 && 2 * busy > 5 * (uint64_t)s_cus;
+}
 // longest tile list the in-LDS sort takes (64 KB of keys + 17 KB of counters when the device grants 96 KB per workgroup)
 static uint32_t tile_sort_cap() {
     static int s_lds_big = -1;
     if (s_lds_big < 0) {
-        s_lds_big = hipFuncSetAttribute((const void *)k_tile_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess &&
-                    hipFuncSetAttribute((const void *)k_tile_sort_views, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
+        bool ok = true;
+#define X(I) ok = ok && hipFuncSetAttribute((const void *)k_tile_sort<I, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess && \
+                  hipFuncSetAttribute((const void *)k_tile_sort<I, I <= 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess &&  \
+                  hipFuncSetAttribute((const void *)k_tile_sort_views<I, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess && \
+                  hipFuncSetAttribute((const void *)k_tile_sort_views<I, I <= 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
+        TSORT_FOR_ITEMS(X)
+#undef X
+        s_lds_big = ok;
         (void)hipGetLastError();   // a refusal must not poison the launch checks below
     }
     return s_lds_big ? (uint32_t)BUCKET_CAP : 5120u;
+}
+// `longest`: no tile list of the launch is longer (LDS and the keys per lane are sized from it); `busy`: its non-empty tiles
+static void tile_sort_launch(hipStream_t s, int tiles, uint32_t longest, uint32_t busy, const int2 *ranges, const uint64_t *comp,
+                             uint64_t *keys_sorted, uint32_t *ids_sorted, const uint32_t *info, int mode) {
+    const size_t lds = tsort_lds_bytes((int)longest);
+    const int grid = tiles < TSORT_GRID ? tiles : TSORT_GRID, items = tsort_items(longest);
+    const bool dense = tsort_dense(items, busy);
+    switch (items) {
+#define X(I) case I:                                                                                                                        \
+        if (dense) k_tile_sort<I, I <= 6><<<grid, TSORT_THREADS, lds, s>>>(ranges, comp, keys_sorted, ids_sorted, info, tiles, mode);       \
+        else k_tile_sort<I, false><<<grid, TSORT_THREADS, lds, s>>>(ranges, comp, keys_sorted, ids_sorted, info, tiles, mode);              \
+        break;
+        TSORT_FOR_ITEMS(X)
+#undef X
+    }
+}
+static void tile_sort_views_launch(hipStream_t s, int tiles, int V, uint32_t Lcap, uint32_t Bcap, const P2Table &tab, int mode) {
+    const size_t lds = tsort_lds_bytes((int)Lcap);
+    const dim3 grid(tiles < TSORT_GRID ? tiles : TSORT_GRID, V);
+    const int items = tsort_items(Lcap);
+    const bool dense = tsort_dense(items, (uint64_t)V * (Bcap < (uint32_t)tiles ? Bcap : (uint32_t)tiles));
+    switch (items) {
+#define X(I) case I:                                                                                           \
+        if (dense) k_tile_sort_views<I, I <= 6><<<grid, TSORT_THREADS, lds, s>>>(tab, tiles, mode);            \
+        else k_tile_sort_views<I, false><<<grid, TSORT_THREADS, lds, s>>>(tab, tiles, mode);                   \
+        break;
+        TSORT_FOR_ITEMS(X)
+#undef X
+    }
 }
 
 // Second phase of ALL views in one launch per stage on `join` (see P2Table).  *done = false (and nothing launched or
@@ -3861,9 +3937,8 @@ static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, con
             LAUNCH_CHECK();
         }
         {
-            const size_t lds = tsort_lds_bytes((int)Lcap);
             ProfScope ps(PROF_K4, join);
-            k_tile_sort_views<<<dim3(tiles < TSORT_GRID ? tiles : TSORT_GRID, V), TSORT_THREADS, lds, join>>>(tab, tsort_mode(P));
+            tile_sort_views_launch(join, tiles, V, Lcap, Bcap, tab, tsort_mode(P));
             LAUNCH_CHECK();
         }
         {
@@ -4040,9 +4115,8 @@ int csplat_forward_finish(int ticket, float *out_color, float *out_depth, int *n
                 k_emit_bucket<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, g.xy, g.depth, radii, cam, table, ranges, tmp.keys_u);
                 LAUNCH_CHECK();
             }
-            const size_t lds = tsort_lds_bytes((int)host_info[1]);
             ProfScope ps(PROF_K4, s);
-            k_tile_sort<<<tiles < TSORT_GRID ? tiles : TSORT_GRID, TSORT_THREADS, lds, s>>>(ranges, tmp.keys_u, b.keys_sorted, b.ids_sorted, t.info, tsort_mode(P));
+            tile_sort_launch(s, tiles, host_info[1], host_info[2], ranges, tmp.keys_u, b.keys_sorted, b.ids_sorted, t.info, tsort_mode(P));
             LAUNCH_CHECK();
         } else {
             // a tile list longer than the LDS sort takes: the global stable radix sort (upstream's pipeline shape)
