@@ -360,7 +360,7 @@ __global__ __launch_bounds__(SIM_H) void k_sim_hidden_fwd(int K0, const float *_
     }
 #pragma unroll
     for (int t = 0; t < T; t++) {
-        a[t] = fmaxf(a[t], 0.f);
+        a[t] = relu_keep_nan(a[t]);         // (a NaN weight or time code must reach the vertices: fmaxf would turn it into 0)
         s_h1[t][j] = a[t];
         if (j / (SIM_H / SIM_FWD_WGS) == g) h1[t * SIM_H + j] = a[t];
     }
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(SIM_H) void k_sim_hidden_fwd(int K0, const float *_
         v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
         v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));   // row_half_mirror
         v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));   // row_mirror
-        if (l == 0) h2[t * SIM_H + unit] = fmaxf(v + b2[unit], 0.f);
+        if (l == 0) h2[t * SIM_H + unit] = relu_keep_nan(v + b2[unit]);
     }
 }
 
@@ -471,6 +471,7 @@ int csplat_rows_dot_fwd(void *stream, int T, int R, int K, const float *W, const
     CSPLAT_REQUIRE(T >= 0 && T <= SIM_TMAX && R >= 0, "csplat_rows_dot_fwd: T must be 0..8, R >= 0");
     if (T == 0 || R == 0) return 0;
     CSPLAT_REQUIRE(W && b && h && y, "csplat_rows_dot_fwd: NULL");
+    CSPLAT_REQUIRE((((uintptr_t)W | (uintptr_t)h) & 15u) == 0, "csplat_rows_dot_fwd: W and h must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     switch (T) {
         case 1: return launch_fwd<1>(s, R, W, b, h, y, add);
@@ -490,6 +491,8 @@ int csplat_rows_dot_bwd(void *stream, int T, int R, int K, const float *W, const
     CSPLAT_REQUIRE(T >= 0 && T <= SIM_TMAX && R >= 0, "csplat_rows_dot_bwd: T must be 0..8, R >= 0");
     if (T == 0) return 0;
     CSPLAT_REQUIRE(h && dh && scratch && (R == 0 || (W && dy && dW && db)), "csplat_rows_dot_bwd: NULL");
+    CSPLAT_REQUIRE((((uintptr_t)W | (uintptr_t)h | (uintptr_t)dW | (uintptr_t)scratch) & 15u) == 0,
+                   "csplat_rows_dot_bwd: W, h, dW and scratch must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     switch (T) {
         case 1: return launch_bwd<1>(s, R, W, h, dy, dW, db, dh, scratch);
@@ -518,7 +521,7 @@ int csplat_cloth_regs(void *stream, int T, int V, int64_t E, const float *D, con
     const bool node_terms = T >= 3 && V > 0 && (lambda_deform != 0.f || lambda_momentum != 0.f);
     const bool edge_terms = T > 0 && E > 0 && V > 0 && lambda_rigid != 0.f;
     const bool csr = dst_rowptr != nullptr;
-    CSPLAT_REQUIRE(!csr || (dst_perm && src_rowptr && src_perm), "csplat_cloth_regs: incomplete CSR");
+    CSPLAT_REQUIRE(!csr || (src_rowptr && (E == 0 || (dst_perm && src_perm))), "csplat_cloth_regs: incomplete CSR");   // (no edges: no lists)
     CSPLAT_REQUIRE(T < 65536, "csplat_cloth_regs: T too large");
     if (T > 0 && V > 0) {
         CSPLAT_REQUIRE(D && grad, "csplat_cloth_regs: NULL D / grad");

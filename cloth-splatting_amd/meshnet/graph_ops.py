@@ -73,6 +73,13 @@ def _f32(t):
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
 
+def _f32a(t):
+    """_f32 on a 16-byte boundary: the operands a kernel reads or writes as float4 (a view that starts one float into a larger buffer is
+    contiguous and misaligned: it is copied)"""
+    t = _f32(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def piece_numbering(dst_sorted, rowptr, group=8):
     """The numbering of the "pieces" the one-launch edge MLP leaves instead of messages (csplat_gnn_edge_mlp3 with `pieces`): rows are edges in
     destination order; a piece = a maximal run of rows with one destination, cut additionally at every multiple of `group` rows (a wave
@@ -160,7 +167,7 @@ class RowsDot(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, weight, bias, add=None):
-        h, weight, bias = _f32(h), _f32(weight), _f32(bias)
+        h, weight, bias = _f32a(h), _f32a(weight), _f32(bias)
         T, K = h.shape
         R = weight.shape[0]
         y = torch.empty(T, R, dtype=torch.float32, device=h.device)
@@ -191,7 +198,7 @@ _n.TICKET_CACHES.append(_SIMH_SCRATCH)
 
 
 def _sim_hidden_fwd(e, W1, b1, W2, b2):
-    e, W1, b1, W2, b2 = (_f32(t) for t in (e, W1, b1, W2, b2))
+    e, W1, b1, W2, b2 = _f32(e), _f32(W1), _f32(b1), _f32a(W2), _f32(b2)
     T, K0 = int(e.shape[0]), int(e.shape[1])
     h1 = torch.empty(T, 256, dtype=torch.float32, device=e.device)
     h2 = torch.empty(T, 256, dtype=torch.float32, device=e.device)
@@ -236,7 +243,7 @@ class SimHidden(torch.autograd.Function):
 
 
 def _rows_dot_fwd(h2, Wo, bo, base=None):
-    Wo, bo = _f32(Wo), _f32(bo)
+    h2, Wo, bo = _f32a(h2), _f32a(Wo), _f32(bo)
     T, R = int(h2.shape[0]), int(Wo.shape[0])
     y = torch.empty(T, R, dtype=torch.float32, device=h2.device)
     add = None if base is None else _f32(base.reshape(T, R))
@@ -247,7 +254,7 @@ def _rows_dot_fwd(h2, Wo, bo, base=None):
 
 
 def _rows_dot_bwd(Wo, h2, g, sinks=(None, None)):
-    g = _f32(g)
+    g, Wo, h2 = _f32(g), _f32a(Wo), _f32a(h2)
     T, R = int(h2.shape[0]), int(Wo.shape[0])
     dWo, dbo, dh = _n.grad_out(sinks[0], Wo.shape, g.device), _n.grad_out(sinks[1], (R,), g.device), torch.empty_like(h2)
     scratch = torch.empty(_n.lib.csplat_rows_dot_scratch_bytes(T), dtype=torch.uint8, device=g.device)
@@ -273,7 +280,7 @@ class SimResidual(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, W1, b1, W2, b2, Wo, bo, base=None):
         e, W2, h1, h2 = _sim_hidden_fwd(e, W1, b1, W2, b2)
-        Wo, bo = _f32(Wo), _f32(bo)
+        Wo, bo = _f32a(Wo), _f32(bo)
         T, R = int(h2.shape[0]), int(Wo.shape[0])
         y = torch.empty(T, R, dtype=torch.float32, device=h2.device)
         add = None if base is None else _f32(base.reshape(T, R))

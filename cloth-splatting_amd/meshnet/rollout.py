@@ -124,6 +124,8 @@ class _FusedClothStep:
                 actions.dim() == 2 and actions.shape[1] == 3 and edge_index.dtype == torch.int64 and int(edge_index.shape[1]) > 0):
             return False
         N, H, T = int(positions.shape[0]), int(velocity_history.shape[0]), int(sim._node_type_embedding_size)
+        if not 0 <= grasped_particle < N:        # (k_rollout_integrate pins nothing outside [0, N); `v_next[-1] = act` of the generic step does)
+            return False
         F = 3 * H + T
         lins_n = list(epd._encoder.node_fn[0].children())[0::2]
         lins_e = list(epd._encoder.edge_fn[0].children())[0::2]

@@ -415,15 +415,20 @@ int csplat_rows_scatter(void *stream, int n_tensors, const void *const *src, voi
  * T = 3 such calls, train_utils.py:204-260):
  *   forward:  y[t][r] = b[r] + sum_k W[r][k] h[t][k]               W [R][K] row-major (torch Linear.weight), h [T][K], y [T][R]
  *   backward: dW[r][k] = sum_t dy[t][r] h[t][k], db[r] = sum_t dy[t][r], dh[t][k] = sum_r dy[t][r] W[r][k]   (deterministic)
- * K must be 256, 0 <= T <= 8.  scratch: csplat_rows_dot_scratch_bytes(T) bytes, not shared between concurrent calls. */
+ * K must be 256, 0 <= T <= 8 (T = 0 or R = 0: nothing is written).  W, h, dW and scratch are accessed 16 bytes at a time and must be
+ * 16-byte aligned (refused otherwise).  scratch: csplat_rows_dot_scratch_bytes(T) bytes, contents irrelevant, not shared between
+ * concurrent calls.  Non-finite data propagate as in the sums above: a NaN in h[t] reaches y[t][:], an Inf in W[r] reaches y[:][r]. */
 /* The two hidden layers in front of it (meshnet_network.py:337-338,364-366), for the same T time rows, one launch each way:
  *   forward : h1 = relu(e W1^T + b1) [T][256], h2 = relu(h1 W2^T + b2) [T][256]      e [T][K0] (the sinusoidal code, K0 <= 16),
  *             W1 [256][K0], W2 [256][256] row-major (torch Linear.weight)
- *   backward: from dh2 = dL/dh2 [T][256]: dW1 [256][K0], db1 [256], dW2 [256][256], db2 [256]   (e has no gradient: parameter-free code) */
+ *   backward: from dh2 = dL/dh2 [T][256]: dW1 [256][K0], db1 [256], dW2 [256][256], db2 [256]   (e has no gradient: parameter-free code)
+ * 1 <= T <= 8, 1 <= K0 <= 16; W2 16-byte aligned.  relu(x) = x < 0 ? 0 : x, torch.relu's values: -0.0 stays -0.0, a NaN stays a NaN (a NaN in e[t] makes rows t of h1 and h2 NaN,
+ * a NaN in a row of W1 that unit of h1 in every row and all of h2), its derivative at 0 is 0.  The order of every sum does not depend
+ * on T: row t of a T-row call has the bits of the same row in any other call. */
 int csplat_sim_hidden_fwd(void *stream, int T, int K0, const float *e, const float *W1, const float *b1, const float *W2, const float *b2,
                           float *h1, float *h2);
-/* scratch: csplat_sim_hidden_scratch_bytes(T) bytes whose first word is zero on entry (the kernel leaves it zero), not shared between
- * calls that may run concurrently */
+/* scratch: csplat_sim_hidden_scratch_bytes(T) bytes whose first word (the ticket) is zero on entry and left at zero: one buffer of
+ * csplat_sim_hidden_scratch_bytes(8) bytes serves calls of any T in a row; not shared between calls that may run concurrently */
 size_t csplat_sim_hidden_scratch_bytes(int T);
 int csplat_sim_hidden_bwd(void *stream, int T, int K0, const float *e, const float *W2, const float *h1, const float *h2, const float *dh2,
                           float *dW1, float *db1, float *dW2, float *db2, void *scratch);
@@ -438,11 +443,14 @@ int csplat_rows_dot_bwd(void *stream, int T, int R, int K, const float *W, const
  *   *loss = lambda_deform * 0.5 * (mean_v |D1-D0|_2 + mean_v |D2-D1|_2)          (only when T >= 3)
  *         + lambda_rigid * mean_{t,e} | rest_len[e] - |D[t][edge_index[1][e]] - D[t][edge_index[0][e]]|_2 |
  *         + lambda_momentum * mean_v |D2 - 2 D1 + D0|_1                          (only when T >= 3)
- *   grad [T][V][3] = d loss / d D (norms have gradient 0 at 0, as torch defines them).
- * scratch: csplat_cloth_regs_scratch_bytes(T, V, E) bytes, ZERO before the first call (every call leaves it reusable), not shared
- * between concurrent calls.  The loss value is summed in a fixed order.  Gradient: with the CSR of the graph (dst_rowptr / src_rowptr [V+1], dst_perm / src_perm [E], int32: edge ids
- * grouped by edge_index[1] / edge_index[0], ascending within a group) every vertex gathers its edges -- deterministic, no
- * atomics; with NULLs the edges scatter with float atomics (summation order not fixed). */
+ *   grad [T][V][3] = d loss / d D (norms have gradient 0 at 0, as torch defines them; sign(0) = 0).  The two node terms read time
+ *   rows 0, 1 and 2 only, whatever T >= 3 is: rows 3 .. T-1 get the rigidity gradient alone.  With no active term (all lambdas 0, or
+ *   only node terms at T < 3) *loss = 0 and grad is zeroed in either form.
+ * scratch: csplat_cloth_regs_scratch_bytes(T, V, E) bytes (enough for either form), ZERO before the first call; the ticket word in its
+ * last 256 bytes is left at zero by every call, so one buffer serves calls of the same (T, V, E) in a row; not shared between
+ * concurrent calls.  The loss value is summed in a fixed order.  Gradient: with the CSR of the graph (dst_rowptr / src_rowptr [V+1], dst_perm / src_perm [E], int32: edge ids
+ * grouped by edge_index[1] / edge_index[0], ascending within a group; the two perm lists may be NULL when E = 0) every vertex gathers
+ * its edges -- deterministic, no atomics; with NULLs the edges scatter with float atomics (summation order not fixed). */
 size_t csplat_cloth_regs_scratch_bytes(int T, int V, int64_t E);
 int csplat_cloth_regs(void *stream, int T, int V, int64_t E, const float *D, const int64_t *edge_index, const float *rest_len,
                       float lambda_deform, float lambda_rigid, float lambda_momentum, float *loss, float *grad, void *scratch,
@@ -620,7 +628,12 @@ int csplat_gnn_edge_features_ordered(void *stream, int64_t E, const float *pos, 
  *   decode:    v[n] = last_v[n] + denormalise(W h[n] + b)   (the decoder's last Linear 128 -> D <= 4 and cloth_network.py:163-193); *fine = 0
  *              when a row is not finite (the fp16-piece arithmetic's overflow signal, meshnet/graph_network.py)
  *   integrate: v[grasped] = actions[*counter - 1]; preds[*counter - 1] = v; pos += v; hist <- (hist[1:], v)
- *              (/root/reference/train_meshnet_sim.py:176,256-262).  hist [H][N][D], pos / v [N][D], actions / preds [steps][..]. */
+ *              (/root/reference/train_meshnet_sim.py:176,256-262).  hist [H][N][D], pos / v [N][D], actions / preds [steps][..].
+ * head: N >= 0 (the counter goes up at N = 0 too; counter may be NULL), 1 <= H <= 16, 0 <= T <= 16, a node type outside 0 .. T-1 has
+ * an all-zero one-hot; the absmax word is only ever raised (atomicMax on the bits of max |stored feature|): zero it before a step.
+ * decode: 1 <= D <= 4, h and W 16-byte aligned; *fine is only ever cleared, by a row of v that holds a NaN or an Inf; every other row is
+ * unaffected.  integrate: H >= 1, *counter >= 1 (the head ran); a grasped index outside [0, N) pins NOTHING (callers that give -1
+ * Python's meaning must resolve it first: meshnet.rollout takes its generic step for such an index). */
 int csplat_rollout_head(void *stream, int N, int H, int T, const float *hist, const int32_t *node_type, const float *mean, const float *stdv,
                         float *feats, int32_t *counter, float *absmax /* or NULL: max |feature|, as csplat_absmax */);
 int csplat_rollout_decode(void *stream, int N, int D, const float *h, const float *W, const float *b, const float *omean, const float *ostd,
@@ -631,7 +644,7 @@ int csplat_rollout_integrate(void *stream, int N, int H, int D, float *v, const 
  * torch.optim.Adam(lr = 1e-3) on the predicted velocities against sum_e w_e (|(pos + v)[row_e] - (pos + v)[col_e]| - rest_len_e)^2).
  * v [N][3] is updated in place; edge_w [E] or NULL (the reference zeroes ONE deviation: `length_deviation[grasped_particle] *= 0`);
  * the CSR orderings by destination (edge_index[1]) and by source (edge_index[0]) as csplat_gnn_build_csr leaves them; scratch = 9 N
- * floats.  One launch per iteration (gradient gathered per node over both orderings -- no atomics -- and the Adam step of the node's own
+ * floats, contents irrelevant.  iters = 0, and a node without edges at any iters, leave v as it is bit for bit.  One launch per iteration (gradient gathered per node over both orderings -- no atomics -- and the Adam step of the node's own
  * coordinates in the same pass), nothing read back. */
 int csplat_gnn_edge_length_refine(void *stream, int N, int64_t E, const float *pos, float *v, const int64_t *edge_index, const float *rest_len,
                                   const float *edge_w, const int32_t *dst_rowptr, const int32_t *dst_perm, const int32_t *src_rowptr,
