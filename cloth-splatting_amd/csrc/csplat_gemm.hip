@@ -707,6 +707,9 @@ extern "C" int csplat_linear128_ex(void *stream, int64_t M, const float *A, cons
                                    const float *add_pre, const float *add_post, const float *mask, float *ln_stats, float *out) {
     CSPLAT_REQUIRE(M >= 0 && (M == 0 || (A && W && out)) && ldw >= 128, "csplat_linear128: bad arguments");
     CSPLAT_REQUIRE((((uintptr_t)A | (uintptr_t)out | (uintptr_t)W) & 15u) == 0, "csplat_linear128: A / W / out must be 16-byte aligned");
+    // (the transposed-accumulator epilogue of the bf16-split kernel reads these four as float4)
+    CSPLAT_REQUIRE((((uintptr_t)bias | (uintptr_t)add_pre | (uintptr_t)add_post | (uintptr_t)mask) & 15u) == 0 && ((uintptr_t)ln_stats & 7u) == 0,
+                   "csplat_linear128: bias / add_pre / add_post / mask must be 16-byte aligned (ln_stats: 8-byte)");
     const int wt = w_transposed ? 1 : 0;
     if (M == 0) return 0;
     const bool gather = gather_a != nullptr;

@@ -220,6 +220,13 @@ __device__ __forceinline__ void kadd(float &acc, float &comp, float v) {
 __device__ __forceinline__ void kadd(float4 &acc, float4 &comp, float4 v) {
     kadd(acc.x, comp.x, v.x); kadd(acc.y, comp.y, v.y); kadd(acc.z, comp.z, v.z); kadd(acc.w, comp.w, v.w);
 }
+// the sum: acc + comp -- unless the running sum itself left the finite range (a message of +-Inf, an overflow, a NaN): the correction
+// then holds Inf - Inf, and the running sum alone is what a plain sequence of adds (index_add_) gives.  A finite acc has only ever seen
+// finite terms, so every finite sum keeps its bits.
+__device__ __forceinline__ float kfinish(float acc, float comp) { return acc - acc == 0.f ? acc + comp : acc; }
+__device__ __forceinline__ float4 kfinish(float4 acc, float4 comp) {
+    return make_float4(kfinish(acc.x, comp.x), kfinish(acc.y, comp.y), kfinish(acc.z, comp.z), kfinish(acc.w, comp.w));
+}
 template <typename VT>
 __global__ __launch_bounds__(256) void k_segment_sum(int N, int LV, const VT *__restrict__ msg,
                                                       const int32_t *__restrict__ rowptr, const int32_t *__restrict__ perm,
@@ -238,7 +245,7 @@ __global__ __launch_bounds__(256) void k_segment_sum(int N, int LV, const VT *__
         kadd(acc, comp, v0); kadd(acc, comp, v1); kadd(acc, comp, v2); kadd(acc, comp, v3);
     }
     for (; i < e; i++) kadd(acc, comp, msg[(int64_t)perm[i] * LV + c]);
-    agg[t] = vadd(acc, comp);
+    agg[t] = kfinish(acc, comp);
 }
 
 template <typename VT>
@@ -425,6 +432,8 @@ int csplat_gnn_edge_combine_fwd(void *stream, int N, int64_t E, int L, const int
                                 const float *xb, const float *ec, int relu, float *out) {
     (void)N;
     CSPLAT_REQUIRE(L > 0, "latent width must be positive");
+    CSPLAT_REQUIRE(L % 4 != 0 || (((uintptr_t)xa | (uintptr_t)xb | (uintptr_t)ec | (uintptr_t)out) & 15u) == 0,
+                   "csplat_gnn_edge_combine_fwd: xa / xb / ec / out must be 16-byte aligned when L is a multiple of 4");
     if (E == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_GNN, s);
@@ -442,6 +451,8 @@ int csplat_gnn_segment_sum(void *stream, int N, int64_t E, int L, const float *m
                            const int32_t *perm, float *agg) {
     (void)E;
     CSPLAT_REQUIRE(L > 0, "latent width must be positive");
+    CSPLAT_REQUIRE(L % 4 != 0 || (((uintptr_t)msg | (uintptr_t)agg) & 15u) == 0,
+                   "csplat_gnn_segment_sum: msg / agg must be 16-byte aligned when L is a multiple of 4");
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_GNN, s);
@@ -458,6 +469,8 @@ int csplat_gnn_edge_combine_bwd(void *stream, int N, int64_t E, int L, const flo
                                 const int32_t *rowptr_dst, const int32_t *perm_dst, const int32_t *rowptr_src,
                                 const int32_t *perm_src, float *g_masked, float *dxa, float *dxb) {
     CSPLAT_REQUIRE(L > 0, "latent width must be positive");
+    CSPLAT_REQUIRE(L % 4 != 0 || (((uintptr_t)g | (uintptr_t)dxa | (uintptr_t)dxb | (relu ? (uintptr_t)out | (uintptr_t)g_masked : 0)) & 15u) == 0,
+                   "csplat_gnn_edge_combine_bwd: g / out / g_masked / dxa / dxb must be 16-byte aligned when L is a multiple of 4");
     hipStream_t s = (hipStream_t)stream;
     const float *gm = g;
     if (relu) {
@@ -478,6 +491,8 @@ int csplat_gnn_edge_combine_bwd(void *stream, int N, int64_t E, int L, const flo
 
 int csplat_gnn_gather_rows(void *stream, int64_t E, int L, const float *rows, const int64_t *keys, float *out) {
     CSPLAT_REQUIRE(L > 0, "latent width must be positive");
+    CSPLAT_REQUIRE(L % 4 != 0 || (((uintptr_t)rows | (uintptr_t)out) & 15u) == 0,
+                   "csplat_gnn_gather_rows: rows / out must be 16-byte aligned when L is a multiple of 4");
     if (E == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_GNN, s);
@@ -637,6 +652,8 @@ int csplat_ln128_fwd(void *stream, int64_t M, const float *x, const float *gamma
 int csplat_ln128_bwd(void *stream, int64_t M, const float *g, const float *x, const float *stats, const float *gamma, float *dx,
                      float *dgamma, float *dbeta, float *dxsum, const int64_t *g_rows, int x_normalized, float *partials) {
     CSPLAT_REQUIRE(M >= 0 && (M == 0 || (g && x && stats && gamma && dx && dgamma && dbeta && partials)), "csplat_ln128_bwd: bad arguments");
+    CSPLAT_REQUIRE((((uintptr_t)g | (uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx | (uintptr_t)partials) & 15u) == 0 && ((uintptr_t)stats & 7u) == 0,
+                   "csplat_ln128_bwd: g / x / gamma / dx / partials must be 16-byte aligned (stats: 8-byte)");
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
         HIP_TRY(hipMemsetAsync(dgamma, 0, 512, s)); HIP_TRY(hipMemsetAsync(dbeta, 0, 512, s));
@@ -660,6 +677,8 @@ int csplat_ln128_bwd(void *stream, int64_t M, const float *g, const float *x, co
 /* gm = out > 0 ? g : 0 (out NULL: gm = g; gm NULL: not written), dbias[c] = sum_rows gm[row][c]; partials: csplat_ln128_partial_floats(M) floats */
 int csplat_relu_mask_bias128(void *stream, int64_t M, const float *g, const float *out, float *gm, float *dbias, float *partials) {
     CSPLAT_REQUIRE(M >= 0 && (M == 0 || (g && dbias && partials)), "csplat_relu_mask_bias128: bad arguments");
+    CSPLAT_REQUIRE((((uintptr_t)g | (uintptr_t)out | (uintptr_t)gm | (uintptr_t)partials) & 15u) == 0,
+                   "csplat_relu_mask_bias128: g / out / gm / partials must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) { HIP_TRY(hipMemsetAsync(dbias, 0, 512, s)); return 0; }
     const int nb = ln_blocks(M);

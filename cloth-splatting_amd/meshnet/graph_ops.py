@@ -106,7 +106,7 @@ class EdgeCombine(torch.autograd.Function):
     def forward(ctx, xa, xb, ec, csr, relu, grad_premasked=False):
         """grad_premasked: the consumer (EdgeTailAggregate) hands back the gradient of the PRE-activation -- it folds this ReLU's
         backward into the GEMM that produces the gradient -- so backward() must not mask again"""
-        xa, xb, ec = _f32(xa), _f32(xb), _f32(ec)
+        xa, xb, ec = _f32a(xa), _f32a(xb), _f32a(ec)
         E, L = ec.shape
         out = torch.empty_like(ec)
         with _n.on_device(ec.device):
@@ -121,7 +121,7 @@ class EdgeCombine(torch.autograd.Function):
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
         csr = ctx.csr
-        g = _f32(g)
+        g = _f32a(g)
         E, L = out.shape
         gm = torch.empty_like(g) if ctx.relu else g
         dxa = torch.empty(csr.N, L, dtype=torch.float32, device=g.device)
@@ -139,7 +139,7 @@ class SegmentSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, msg, csr):
-        msg = _f32(msg)
+        msg = _f32a(msg)
         E, L = msg.shape
         agg = torch.empty(csr.N, L, dtype=torch.float32, device=msg.device)
         with _n.on_device(msg.device):
@@ -152,7 +152,7 @@ class SegmentSum(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         csr = ctx.csr
-        g = _f32(g)
+        g = _f32a(g)
         L = g.shape[1]
         out = torch.empty(csr.E, L, dtype=torch.float32, device=g.device)
         with _n.on_device(g.device):
@@ -385,15 +385,20 @@ def linear128(A, weight, bias=None, alpha=1.0, relu=False, gather=None, layer_no
     if layer_norm is not None:
         assert tuple(layer_norm.normalized_shape) == (128,) and layer_norm.elementwise_affine
         g, b, eps = layer_norm.weight.detach().contiguous(), layer_norm.bias.detach().contiguous(), float(layer_norm.eps)
-    bias = None if bias is None else bias.detach().contiguous()
-    add_pre = None if add_pre is None else _f32(add_pre)
-    add_post = None if add_post is None else _f32(add_post)
-    mask = None if mask is None else _f32(mask)
+    bias = None if bias is None else _f32a(bias.detach())
+    add_pre = None if add_pre is None else _f32a(add_pre)
+    add_post = None if add_post is None else _f32a(add_post)
+    mask = None if mask is None else _f32a(mask)
+    stats_out = ln_stats
+    if ln_stats is not None and (not ln_stats.is_contiguous() or ln_stats.data_ptr() % 8):      # (written as float2: through a temporary)
+        stats_out = torch.empty(ln_stats.shape, dtype=torch.float32, device=ln_stats.device)
     with _n.on_device(A.device):
         _n.check(_n.lib.csplat_linear128_ex(_n.stream_handle(A.device), M, _n.ptr(A), weight.data_ptr(), ldw, wt, _n.ptr(bias), float(alpha),
                                             int(relu), _n.ptr(ga), _n.ptr(ia), _n.ptr(gb), _n.ptr(ib), _n.ptr(g), _n.ptr(b), eps,
-                                            _n.ptr(add_pre), _n.ptr(add_post), _n.ptr(mask), _n.ptr(ln_stats), _n.ptr(out)),
+                                            _n.ptr(add_pre), _n.ptr(add_post), _n.ptr(mask), _n.ptr(stats_out), _n.ptr(out)),
                  "csplat_linear128_ex")
+    if stats_out is not ln_stats:
+        ln_stats.copy_(stats_out)
     return out
 
 
@@ -418,7 +423,7 @@ def gather_rows(rows, keys, with_absmax=False):
     """rows[keys] for [.,L] fp32 rows and int64 keys (csplat_gnn_gather_rows), no autograd; with_absmax: also max |value| of the result as a
     one-element device tensor, from the same pass (csplat_gnn_gather_rows_absmax)"""
     _n.require_cuda(rows)
-    rows, keys = _f32(rows), keys.contiguous()
+    rows, keys = _f32a(rows), keys.contiguous()
     assert keys.dtype == torch.int64
     out = torch.empty(keys.numel(), rows.shape[1], dtype=torch.float32, device=rows.device)
     with _n.on_device(rows.device):
@@ -434,7 +439,7 @@ def gather_rows(rows, keys, with_absmax=False):
 
 def segment_sum_rows(rows, rowptr, perm, N):
     """out[v] = sum of rows[perm[rowptr[v] .. rowptr[v + 1] - 1]] in that order (csplat_gnn_segment_sum), no autograd"""
-    rows = _f32(rows)
+    rows = _f32a(rows)
     out = torch.empty(N, rows.shape[1], dtype=torch.float32, device=rows.device)
     with _n.on_device(rows.device):
         _n.check(_n.lib.csplat_gnn_segment_sum(_n.stream_handle(rows.device), N, rows.shape[0], rows.shape[1], _n.ptr(rows), _n.ptr(rowptr), _n.ptr(perm),
@@ -623,6 +628,10 @@ def ln128_fwd(x, gamma, beta, eps):
 def ln128_bwd(g, x, stats, gamma, want_dxsum=False, g_rows=None, x_normalized=False):
     """(dx, dgamma, dbeta, column sums of dx or None) of LayerNorm over [M, 128] rows: csplat_ln128_bwd.  g_rows: row r of the incoming
     gradient is g[g_rows[r]] (g then has as many rows as g_rows addresses); x_normalized: x is the normalised row xhat itself."""
+    g, x, gamma = _f32a(g), _f32a(x), _f32a(gamma)
+    stats = stats.contiguous()
+    if stats.data_ptr() % 8:          # (read as float2)
+        stats = stats.clone()
     M = x.shape[0]
     dx = torch.empty_like(x)
     dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
@@ -665,7 +674,7 @@ def layer_norm_rows(x, ln: torch.nn.LayerNorm):
 
 def relu_mask_bias128(g, out):
     """(g masked by out > 0, column sums of the masked g): ReLU backward + bias gradient in one pass; out None = no mask"""
-    g = _f32(g)
+    g, out = _f32a(g), (None if out is None else _f32a(out))
     M = g.shape[0]
     gm = torch.empty_like(g) if out is not None else None
     db = torch.empty(128, dtype=torch.float32, device=g.device)
@@ -827,7 +836,7 @@ class EdgeFirstLayer(torch.autograd.Function):
         csr = ctx.csr
         de = dw = dxa = dxb = None
         if g is not None:
-            g = _f32(g)
+            g = _f32a(g)
             E = g.shape[0]
             dxa = torch.empty(csr.N, 128, dtype=torch.float32, device=g.device)
             dxb = torch.empty_like(dxa)

