@@ -90,6 +90,9 @@ EXPORTS = {
     "csplat_image_loss_fwd": (_i, [_vp, _i64, _i, _i, _i, C.POINTER(C.c_float), _vp, _vp, _vp, _i, _f, _f, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csplat_image_loss_bwd": (_i, [_vp, _i64, _i, _i, _i, C.POINTER(C.c_float), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp]),
     "csplat_step_stats": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_geom_loss_scratch_bytes": (_sz, [_i, _i64]),
+    "csplat_geom_loss_fwd": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _f, _vp, _vp, _vp]),
+    "csplat_geom_loss_bwd": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "csplat_psnr_scratch_bytes": (_sz, [_i64]),
     "csplat_psnr": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "csplat_sim_hidden_fwd": (_i, [_vp, _i, _i] + [_vp] * 7),
@@ -396,18 +399,20 @@ PROF_CLASSES = ["K1_preprocess", "K2_scan", "K3_emit_keys", "K4_radix_sort", "K5
                 "K7_render_bwd", "K8_preprocess_bwd", "K9_dist2", "GNN", "K7_depth_partials", "K7_depth_bwd", "K8_depth_bwd",
                 "K8_camera_bwd", "camera_sums", "K6_features", "K7_feature_partials", "K7_feature_bwd", "feature_grads",
                 "visibility"]
+# the train step's own classes follow the rasterizer's (csplat.h numbers them 20, 21); prof_enable / prof_read take their names too
+PROF_TRAIN_CLASSES = ["geometry_loss_fwd", "geometry_loss_bwd"]
 MAX_FEATURES = 6      # csplat.h: CSPLAT_MAX_FEATURES
 
 
 def prof_enable(classes=()):
     mask = 0
     for c in classes:
-        mask |= 1 << (PROF_CLASSES.index(c) if isinstance(c, str) else int(c))
+        mask |= 1 << ((PROF_CLASSES + PROF_TRAIN_CLASSES).index(c) if isinstance(c, str) else int(c))
     check(lib.csplat_prof_enable(mask), "csplat_prof_enable")
 
 
 def prof_read(cls):
-    k = PROF_CLASSES.index(cls) if isinstance(cls, str) else int(cls)
+    k = (PROF_CLASSES + PROF_TRAIN_CLASSES).index(cls) if isinstance(cls, str) else int(cls)
     ms, n = C.c_double(0), _i64(0)
     check(lib.csplat_prof_read(k, C.byref(ms), C.byref(n)), "csplat_prof_read")
     return ms.value, n.value

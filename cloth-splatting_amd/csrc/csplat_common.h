@@ -54,7 +54,7 @@ unsigned long long *csplat_stamp_buffer(size_t need_words);
 // ---- optional event bracketing (csplat_prof_*), implemented in csplat_sort.hip --------------------
 enum { PROF_K1 = 0, PROF_K2, PROF_K3, PROF_K4, PROF_K5, PROF_K6, PROF_K7, PROF_K8, PROF_KNN, PROF_GNN, PROF_K7_DEPTH_PARTIALS, PROF_K7_DEPTH,
        PROF_K8_DEPTH, PROF_K8_CAM, PROF_CAM_SUM, PROF_K6_FEAT, PROF_K7_FEAT_PARTIALS, PROF_K7_FEAT, PROF_FEAT_GRADS,
-       PROF_VISIBILITY, PROF_NCLASSES };
+       PROF_VISIBILITY, PROF_GEOM_LOSS_FWD, PROF_GEOM_LOSS_BWD, PROF_NCLASSES };
 extern unsigned g_csplat_prof_mask;
 void csplat_prof_mark(int cls, hipStream_t s, bool begin);
 struct ProfScope {

@@ -499,6 +499,164 @@ __global__ __launch_bounds__(L1_BLOCKS) void k_l1_finish(int nparts, const float
         *loss = tt * inv_n;
     }
 }
+// ---- geometry loss of a train step: depth and silhouette supervision on the rasterizer's depth image D = sum T alpha z and alpha image
+// A = 1 - T_final (include/csplat.h, csplat_geom_loss_fwd, states the semantics).  No counterpart in the reference, whose losses never
+// touch `depth`.  The views of a step arrive as per-view pointer tables (as k_step_stats takes them): the rasterizer's images are separate
+// allocations, a stacked form would cost a copy of each every step.  One pass over all pixels writes ONE BYTE per pixel -- two 2-bit codes of
+// sign(r_d w_d) and sign(r_s w_s) -- and two partial sums per workgroup; k_geom_loss_finish (one workgroup) sums them in index order, as
+// k_l1_finish does: no ticket, no float atomics.  Algorithmic bytes per pixel: <= 5 floats read + 1 byte written forward (D, A, Z, S, M),
+// 1 byte + <= 2 floats read (Z, M) + 2 floats written backward.
+constexpr int GL_THREADS = 256, GL_MAX_BLOCKS = 1024, GL_VIEWS = 16;      // workgroups per view <= GL_MAX_BLOCKS; views per launch <= GL_VIEWS
+struct GeomTable {
+    const float *D[GL_VIEWS], *A[GL_VIEWS], *Z[GL_VIEWS], *S[GL_VIEWS], *M[GL_VIEWS];
+};
+// 2-bit code of sign(r * w): 0 -> -1, 1 -> 0, 2 -> +1, 3 -> NaN.  From the two signs, not from the rounded product (which may underflow to 0)
+__device__ __forceinline__ unsigned geom_code(float r, float w) {
+    if (r != r || w != w) return 3u;
+    const int sr = (r > 0.f) - (r < 0.f), sw = (w > 0.f) - (w < 0.f);
+    return (unsigned)(sr * sw + 1);
+}
+__device__ __forceinline__ float geom_sign(unsigned code) { return code == 3u ? __builtin_nanf("") : (float)((int)code - 1); }
+// a sensor map's hole is 0, negative, NaN or Inf
+__device__ __forceinline__ bool geom_valid(float z) { return z > 0.f && z < __builtin_inff(); }
+
+// one pixel: adds its two terms to acc_d / acc_s and returns its byte.  SELECTION: a pixel of weight 0 adds exactly 0 and gets the code of
+// sign 0, whatever D, A, Z hold there (NaN, Inf); D, Z, S are only looked at when their term is on
+// (selects, not branches: a load that is only used inside a divergent branch is sunk into it by the compiler, one dword at a time -- the
+//  first form of this kernel had 21 4-byte loads where five 16-byte ones were written)
+template <bool HAS_Z, bool HAS_S>
+__device__ __forceinline__ unsigned geom_pixel(float d, float a, float z, float s, float m, float &acc_d, float &acc_s) {
+    unsigned code_d = 1u, code_s = 1u;
+    if (HAS_Z) {
+        const float w = geom_valid(z) ? m : 0.f;
+        const bool on = w != 0.f;
+        const float r = fmaf(-a, z, d);           // ONE rounding: the sign is the exact sign of D - A Z (a separate multiply may flip it near a tie)
+        acc_d += on ? fabsf(r * w) : 0.f;
+        code_d = on ? geom_code(r, w) : 1u;
+    }
+    if (HAS_S) {
+        const bool on = m != 0.f;
+        const float r = a - s;
+        acc_s += on ? fabsf(r * m) : 0.f;
+        code_s = on ? geom_code(r, m) : 1u;
+    }
+    return code_d | (code_s << 2);
+}
+
+// grid (workgroups per view, views of this launch).  partial [2][n_parts]: the depth sums, then the silhouette sums, at
+// (view0 + blockIdx.y) * gridDim.x + blockIdx.x.  vec: every pointer of the call is 16-byte aligned and hw % 4 == 0
+template <bool HAS_Z, bool HAS_S, bool HAS_M>
+__global__ __launch_bounds__(GL_THREADS) void k_geom_loss_fwd(int64_t hw, GeomTable tab, int view0, int64_t n_parts, int vec,
+                                                              float *__restrict__ partial, unsigned char *__restrict__ sign8) {
+    __shared__ float s_red[2][GL_THREADS / 64];
+    const int v = blockIdx.y;
+    const float *__restrict__ D = tab.D[v], *__restrict__ A = tab.A[v], *__restrict__ Z = tab.Z[v], *__restrict__ S = tab.S[v],
+                *__restrict__ M = tab.M[v];
+    unsigned char *sg = sign8 ? sign8 + (int64_t)(view0 + v) * hw : nullptr;
+    float acc_d = 0.f, acc_s = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * GL_THREADS;
+    if (vec) {
+        const int64_t n4 = hw >> 2;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f), one = make_float4(1.f, 1.f, 1.f, 1.f);
+        for (int64_t i = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x; i < n4; i += stride) {
+            const float4 a = reinterpret_cast<const float4 *>(A)[i];
+            const float4 d = HAS_Z ? reinterpret_cast<const float4 *>(D)[i] : zero, z = HAS_Z ? reinterpret_cast<const float4 *>(Z)[i] : zero;
+            const float4 s = HAS_S ? reinterpret_cast<const float4 *>(S)[i] : zero, m = HAS_M ? reinterpret_cast<const float4 *>(M)[i] : one;
+            const unsigned c0 = geom_pixel<HAS_Z, HAS_S>(d.x, a.x, z.x, s.x, m.x, acc_d, acc_s);
+            const unsigned c1 = geom_pixel<HAS_Z, HAS_S>(d.y, a.y, z.y, s.y, m.y, acc_d, acc_s);
+            const unsigned c2 = geom_pixel<HAS_Z, HAS_S>(d.z, a.z, z.z, s.z, m.z, acc_d, acc_s);
+            const unsigned c3 = geom_pixel<HAS_Z, HAS_S>(d.w, a.w, z.w, s.w, m.w, acc_d, acc_s);
+            if (sg) reinterpret_cast<uchar4 *>(sg)[i] = make_uchar4((unsigned char)c0, (unsigned char)c1, (unsigned char)c2, (unsigned char)c3);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x; i < hw; i += stride) {
+            const unsigned c = geom_pixel<HAS_Z, HAS_S>(HAS_Z ? D[i] : 0.f, A[i], HAS_Z ? Z[i] : 0.f, HAS_S ? S[i] : 0.f, HAS_M ? M[i] : 1.f,
+                                                        acc_d, acc_s);
+            if (sg) sg[i] = (unsigned char)c;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { acc_d += __shfl_xor(acc_d, o, 64); acc_s += __shfl_xor(acc_s, o, 64); }
+    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = acc_d; s_red[1][threadIdx.x >> 6] = acc_s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float td = 0.f, ts = 0.f;
+        for (int k = 0; k < GL_THREADS / 64; k++) { td += s_red[0][k]; ts += s_red[1][k]; }
+        const int64_t at = (int64_t)(view0 + v) * gridDim.x + blockIdx.x;
+        partial[at] = td;
+        partial[n_parts + at] = ts;
+    }
+}
+
+// the second (one-workgroup) launch: a fixed tree over the partials in index order -- any number of them, each thread walks its residue
+// class -- then out[3] = {weight * (lam_d L_depth + lam_s L_sil) + add_weight * add[0], L_depth, L_sil}
+__global__ __launch_bounds__(GL_THREADS) void k_geom_loss_finish(int64_t n_parts, const float *__restrict__ partial, float n_pixels, float lam_d,
+                                                                 float lam_s, float weight, const float *__restrict__ add, float add_weight,
+                                                                 float *__restrict__ out) {
+    __shared__ float s_red[2][GL_THREADS / 64];
+    float td = 0.f, ts = 0.f;
+    for (int64_t i = threadIdx.x; i < n_parts; i += GL_THREADS) { td += partial[i]; ts += partial[n_parts + i]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { td += __shfl_xor(td, o, 64); ts += __shfl_xor(ts, o, 64); }
+    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = td; s_red[1][threadIdx.x >> 6] = ts; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float sd = 0.f, ss = 0.f;
+        for (int k = 0; k < GL_THREADS / 64; k++) { sd += s_red[0][k]; ss += s_red[1][k]; }
+        const float ld = sd / n_pixels, ls = ss / n_pixels;
+        out[0] = weight * (lam_d * ld + lam_s * ls) + (add ? add_weight * add[0] : 0.f);
+        out[1] = ld;
+        out[2] = ls;
+    }
+}
+
+// backward, one launch: dD = g lam_d w_d sign_d / n, dA = g (-lam_d w_d Z sign_d + lam_s w_s sign_s) / n from the sign bytes, Z and M; a pixel
+// of weight 0 gets exactly 0 (selection: its Z may be NaN).  dD / dA [views][hw], either may be NULL.  scale_d / scale_s = lam / n
+template <bool HAS_Z, bool HAS_S, bool HAS_M>
+__global__ __launch_bounds__(GL_THREADS) void k_geom_loss_bwd(int64_t hw, GeomTable tab, int view0, int vec, const unsigned char *__restrict__ sign8,
+                                                              const float *__restrict__ g, float scale_d, float scale_s,
+                                                              float *__restrict__ dD, float *__restrict__ dA) {
+    const int v = blockIdx.y;
+    const float *__restrict__ Z = tab.Z[v], *__restrict__ M = tab.M[v];      // (only these two tables are read here)
+    const int64_t base = (int64_t)(view0 + v) * hw;
+    const unsigned char *sg = sign8 + base;
+    float *od = dD ? dD + base : nullptr, *oa = dA ? dA + base : nullptr;
+    const float sc_d = g[0] * scale_d, sc_s = g[0] * scale_s;
+    auto one = [&](unsigned code, float z, float m, float &gd, float &ga) {
+        gd = 0.f; ga = 0.f;
+        if (HAS_Z) {
+            const float w = geom_valid(z) ? m : 0.f;
+            const float t = sc_d * w * geom_sign(code & 3u);
+            gd = w != 0.f ? t : 0.f;              // (selects: see geom_pixel)
+            ga = w != 0.f ? -t * z : 0.f;
+        }
+        if (HAS_S) ga += m != 0.f ? sc_s * m * geom_sign((code >> 2) & 3u) : 0.f;
+    };
+    const int64_t stride = (int64_t)gridDim.x * GL_THREADS;
+    if (vec) {
+        const int64_t n4 = hw >> 2;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f), ones = make_float4(1.f, 1.f, 1.f, 1.f);
+        for (int64_t i = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x; i < n4; i += stride) {
+            const uchar4 c = reinterpret_cast<const uchar4 *>(sg)[i];
+            const float4 z = HAS_Z ? reinterpret_cast<const float4 *>(Z)[i] : zero, m = HAS_M ? reinterpret_cast<const float4 *>(M)[i] : ones;
+            float4 gd, ga;
+            one(c.x, z.x, m.x, gd.x, ga.x);
+            one(c.y, z.y, m.y, gd.y, ga.y);
+            one(c.z, z.z, m.z, gd.z, ga.z);
+            one(c.w, z.w, m.w, gd.w, ga.w);
+            if (od) reinterpret_cast<float4 *>(od)[i] = gd;
+            if (oa) reinterpret_cast<float4 *>(oa)[i] = ga;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x; i < hw; i += stride) {
+            float gd, ga;
+            one(sg[i], HAS_Z ? Z[i] : 0.f, HAS_M ? M[i] : 1.f, gd, ga);
+            if (od) od[i] = gd;
+            if (oa) oa[i] = ga;
+        }
+    }
+}
+
 // ---- PSNR per image (utils/image_utils.py psnr: mse over all channels and pixels of an image, 20 log10(1 / sqrt(mse))).
 // The reference logs it every training step; as torch ops it is ~10 launches.  gridDim.y = image, PSNR_BLOCKS slices per
 // image, last slice of an image (ticket) sums the slice partials in fixed order.
@@ -631,6 +789,116 @@ extern "C" int csplat_l1_signs_bwd(void *stream, int64_t n_batch, int channels, 
     const int grid = (int)(work < 1 ? 1 : (work > 4096 ? 4096 : work));
     k_l1_bwd<<<grid, 256, 0, (hipStream_t)stream>>>(n, sign8, g_scalar, 1.0f / (float)n, mask, hw, channels, mask ? mask_channels : 1, out);
     LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- geometry loss (k_geom_loss_fwd + k_geom_loss_finish / k_geom_loss_bwd; include/csplat.h states the semantics)
+static int geom_blocks(int64_t hw, bool vec) {
+    const int64_t work = ((vec ? hw >> 2 : hw) + GL_THREADS - 1) / GL_THREADS;
+    return (int)(work < 1 ? 1 : (work > GL_MAX_BLOCKS ? GL_MAX_BLOCKS : work));
+}
+// 16-byte accesses need every pointer of the call 16-byte aligned and 4-pixel groups that stay inside a view; all need 4-byte alignment
+static int geom_alignment(int n_views, int64_t hw, const float *const *const tabs[], int n_tabs, bool *vec) {
+    uintptr_t bits = 0;
+    for (int t = 0; t < n_tabs; t++)
+        if (tabs[t])
+            for (int v = 0; v < n_views; v++) {
+                CSPLAT_REQUIRE(tabs[t][v], "csplat_geom_loss: a NULL view in a table that is given");
+                bits |= (uintptr_t)tabs[t][v];
+            }
+    CSPLAT_REQUIRE((bits & 3u) == 0, "csplat_geom_loss: operands must be 4-byte aligned");
+    *vec = (bits & 15u) == 0 && (hw & 3) == 0;
+    return 0;
+}
+extern "C" size_t csplat_geom_loss_scratch_bytes(int n_views, int64_t hw) {
+    return align256((size_t)2 * (size_t)(n_views > 0 ? n_views : 1) * geom_blocks(hw > 0 ? hw : 1, false) * 4);      // [2][views * workgroups]
+}
+extern "C" int csplat_geom_loss_fwd(void *stream, int n_views, int64_t hw, const float *const *depth, const float *const *alpha,
+                                    const float *const *gt_depth, const float *const *silhouette, const float *const *mask,
+                                    float lambda_depth, float lambda_silhouette, float weight, const float *add, float add_weight,
+                                    unsigned char *sign8, void *scratch, float *out) {
+    CSPLAT_REQUIRE(n_views > 0 && hw > 0 && alpha && scratch && out, "csplat_geom_loss_fwd: bad arguments");
+    CSPLAT_REQUIRE(lambda_depth >= 0.f && lambda_silhouette >= 0.f, "csplat_geom_loss_fwd: the weights are >= 0");
+    if (!(lambda_depth > 0.f)) gt_depth = nullptr;             // a term is on when its weight is > 0 and its data are given
+    if (!(lambda_silhouette > 0.f)) silhouette = nullptr;
+    CSPLAT_REQUIRE(gt_depth || silhouette, "csplat_geom_loss_fwd: no term is on (both tables NULL or both weights 0)");
+    CSPLAT_REQUIRE(!gt_depth || depth, "csplat_geom_loss_fwd: the depth term needs the depth images");
+    CSPLAT_REQUIRE((int64_t)n_views * hw < ((int64_t)1 << 40), "csplat_geom_loss_fwd: too many pixels");
+    const float *const *const tabs[5] = {gt_depth ? depth : nullptr, alpha, gt_depth, silhouette, mask};
+    bool vec = false;
+    if (int rc = geom_alignment(n_views, hw, tabs, 5, &vec)) return rc;
+    CSPLAT_REQUIRE(((uintptr_t)sign8 & 3u) == 0, "csplat_geom_loss_fwd: the sign bytes must be 4-byte aligned");
+    const int gx = geom_blocks(hw, vec);
+    const int64_t n_parts = (int64_t)n_views * gx;
+    float *partial = (float *)scratch;
+    ProfScope ps(PROF_GEOM_LOSS_FWD, (hipStream_t)stream);
+    for (int v0 = 0; v0 < n_views; v0 += GL_VIEWS) {          // more views than a table holds: one launch per GL_VIEWS, the partials of all
+        const int nv = n_views - v0 < GL_VIEWS ? n_views - v0 : GL_VIEWS;      // launches side by side, summed in index order below
+        GeomTable tab;
+        memset(&tab, 0, sizeof(tab));
+        for (int v = 0; v < nv; v++) {
+            tab.A[v] = alpha[v0 + v];
+            if (gt_depth) { tab.D[v] = depth[v0 + v]; tab.Z[v] = gt_depth[v0 + v]; }
+            if (silhouette) tab.S[v] = silhouette[v0 + v];
+            if (mask) tab.M[v] = mask[v0 + v];
+        }
+        const dim3 grid(gx, nv);
+#define GEOM_FWD(Z_, S_, M_) k_geom_loss_fwd<Z_, S_, M_><<<grid, GL_THREADS, 0, (hipStream_t)stream>>>(hw, tab, v0, n_parts, vec ? 1 : 0, partial, sign8)
+        switch ((gt_depth ? 4 : 0) | (silhouette ? 2 : 0) | (mask ? 1 : 0)) {       // (no term on was refused above)
+        case 2: GEOM_FWD(false, true, false); break;
+        case 3: GEOM_FWD(false, true, true); break;
+        case 4: GEOM_FWD(true, false, false); break;
+        case 5: GEOM_FWD(true, false, true); break;
+        case 6: GEOM_FWD(true, true, false); break;
+        default: GEOM_FWD(true, true, true); break;
+        }
+#undef GEOM_FWD
+        LAUNCH_CHECK();
+    }
+    k_geom_loss_finish<<<1, GL_THREADS, 0, (hipStream_t)stream>>>(n_parts, partial, (float)n_views * (float)hw, gt_depth ? lambda_depth : 0.f,
+                                                                  silhouette ? lambda_silhouette : 0.f, weight, add, add_weight, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int csplat_geom_loss_bwd(void *stream, int n_views, int64_t hw, const unsigned char *sign8, const float *const *gt_depth,
+                                    const float *const *mask, float lambda_depth, float lambda_silhouette, float weight,
+                                    const float *g_scalar, float *d_depth, float *d_alpha) {
+    CSPLAT_REQUIRE(n_views > 0 && hw > 0 && sign8 && g_scalar && (d_depth || d_alpha), "csplat_geom_loss_bwd: bad arguments");
+    CSPLAT_REQUIRE(lambda_depth >= 0.f && lambda_silhouette >= 0.f, "csplat_geom_loss_bwd: the weights are >= 0");
+    if (!(lambda_depth > 0.f)) gt_depth = nullptr;
+    const bool sil = lambda_silhouette > 0.f;
+    CSPLAT_REQUIRE(gt_depth || sil, "csplat_geom_loss_bwd: no term is on (no depth table and no silhouette weight)");
+    const float *const *const tabs[2] = {gt_depth, mask};
+    bool vec = false;
+    if (int rc = geom_alignment(n_views, hw, tabs, 2, &vec)) return rc;
+    CSPLAT_REQUIRE((((uintptr_t)sign8 | (uintptr_t)d_depth | (uintptr_t)d_alpha) & 3u) == 0, "csplat_geom_loss_bwd: operands must be 4-byte aligned");
+    vec = vec && (((uintptr_t)d_depth | (uintptr_t)d_alpha) & 15u) == 0;
+    const int gx = geom_blocks(hw, vec);
+    const float inv_n = 1.0f / ((float)n_views * (float)hw);
+    ProfScope ps(PROF_GEOM_LOSS_BWD, (hipStream_t)stream);
+    for (int v0 = 0; v0 < n_views; v0 += GL_VIEWS) {
+        const int nv = n_views - v0 < GL_VIEWS ? n_views - v0 : GL_VIEWS;
+        GeomTable tab;
+        memset(&tab, 0, sizeof(tab));
+        for (int v = 0; v < nv; v++) {
+            if (gt_depth) tab.Z[v] = gt_depth[v0 + v];
+            if (mask) tab.M[v] = mask[v0 + v];
+        }
+        const dim3 grid(gx, nv);
+#define GEOM_BWD(Z_, S_, M_)                                                                                                              \
+    k_geom_loss_bwd<Z_, S_, M_><<<grid, GL_THREADS, 0, (hipStream_t)stream>>>(hw, tab, v0, vec ? 1 : 0, sign8, g_scalar, weight * lambda_depth * inv_n, \
+                                                                              weight * lambda_silhouette * inv_n, d_depth, d_alpha)
+        switch ((gt_depth ? 4 : 0) | (sil ? 2 : 0) | (mask ? 1 : 0)) {
+        case 2: GEOM_BWD(false, true, false); break;
+        case 3: GEOM_BWD(false, true, true); break;
+        case 4: GEOM_BWD(true, false, false); break;
+        case 5: GEOM_BWD(true, false, true); break;
+        case 6: GEOM_BWD(true, true, false); break;
+        default: GEOM_BWD(true, true, true); break;
+        }
+#undef GEOM_BWD
+        LAUNCH_CHECK();
+    }
     return 0;
 }
 

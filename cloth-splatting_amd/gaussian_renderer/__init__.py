@@ -197,12 +197,14 @@ def render_visibility(viewpoint_camera, pc, simulator, pipe, bg_color: torch.Ten
 
 def render_views(viewpoint_cameras, pc, simulator, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
                  no_shadow=False, render_static=False, project_vertices=False, return_stacked=False, vertice_deforms=None,
-                 by_products=True):
+                 by_products=True, return_alpha=False):
     """render() for every camera of a training step in one rasterizer call (diff_gaussian_rasterization.rasterize_views:
     one HIP stream per view, the views' kernels overlap, shared parameters get one gradient buffer).  Same results as
     [render(c, ...) for c in viewpoint_cameras]; no counterpart upstream, whose train loop renders camera by camera
     (scene_reconstruction/train_utils.py:204-260).  return_stacked=True also returns the [V,3,H,W] image batch (None when
-    the cameras differ in size) so that the caller's losses need no torch.cat."""
+    the cameras differ in size) so that the caller's losses need no torch.cat.  return_alpha=True asks every view's rasterizer call for
+    its alpha image (GaussianRasterizer.forward, return_alpha) and returns the list of these [1,H,W] images, differentiable, as one more
+    element at the end: (results, alphas) or (results, stacked, alphas).  RenderResults itself is unchanged."""
     shared, prepared = {}, []
     viewpoint_cameras = list(viewpoint_cameras)
     deforms = vertice_deforms      # [T, V, 3] when the caller already evaluated the simulator for these cameras
@@ -230,11 +232,19 @@ def render_views(viewpoint_cameras, pc, simulator, pipe, bg_color: torch.Tensor,
                                  shared, None if deforms is None else deform_views[i],
                                  None if moved is None else (moved[0][i], moved[1][i])))
     if not prepared:
+        if return_alpha:
+            return ([], None, []) if return_stacked else ([], [])
         return ([], None) if return_stacked else []
+    if return_alpha:
+        for p in prepared:
+            p[1]["return_alpha"] = True
     sizes = {(p[0].image_height, p[0].image_width) for p in prepared}
     if len(sizes) == 1:   # the images of the step in ONE [V,3,H,W] tensor: each RenderResults.render is a slice of it
         stacked, outs = rasterize_views([p[0] for p in prepared], [p[1] for p in prepared], stacked=True)
     else:
         stacked, outs = None, rasterize_views([p[0] for p in prepared], [p[1] for p in prepared])
-    res = [_package(cam, out, p[2], project_vertices, by_products) for cam, out, p in zip(viewpoint_cameras, outs, prepared)]
+    res = [_package(cam, out[:3], p[2], project_vertices, by_products) for cam, out, p in zip(viewpoint_cameras, outs, prepared)]
+    if return_alpha:
+        alphas = [out[3] for out in outs]        # (no features are asked for: a view's tuple is (color, radii, depth, alpha))
+        return (res, stacked, alphas) if return_stacked else (res, alphas)
     return (res, stacked) if return_stacked else res

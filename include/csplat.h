@@ -537,6 +537,40 @@ int csplat_l1_signs(void *stream, int64_t n_batch, int channels, int64_t hw, con
                     int mask_channels, void *scratch, float *loss, signed char *sign8);
 int csplat_l1_signs_bwd(void *stream, int64_t n_batch, int channels, int64_t hw, const signed char *sign8, const float *mask,
                         int mask_channels, const float *g_scalar, float *out);
+/* Depth and silhouette supervision of a training step on the rasterizer's depth image D = sum_i T_i alpha_i z_i (view-space z, no
+ * background term) and alpha image A = 1 - T_final (csplat_view.out_depth / out_alpha), two launches forward and one backward.  The reference
+ * has no such loss.  The n_views views of a step are all of hw = H * W pixels, n = n_views * hw, and arrive as tables of n_views device
+ * pointers, one float image per view: depth (D), alpha (A), gt_depth (Z: measured z-depth in scene units), silhouette (S in [0, 1], 1 =
+ * cloth), mask (M: the camera's mask, 1 = keep).  gt_depth, silhouette and mask may each be NULL: no Z = no depth term (depth may then be
+ * NULL too), no S = no silhouette term, no M = 1 everywhere.  A term is on when its table is given and its weight is > 0; with no term on
+ * the call returns an argument error and launches nothing.
+ *   valid   = isfinite(Z) and Z > 0                    (a hole in a sensor map is 0, negative, NaN or Inf)
+ *   w_d     = valid ? M : 0                            w_s = M
+ *   r_d     = D - A Z   (= sum_i T_i alpha_i (z_i - Z): no division by alpha; formed with ONE fused multiply-add, so that its sign is exact)
+ *   r_s     = A - S
+ *   L_depth = (1/n) sum_{w_d != 0} |r_d w_d|           L_sil = (1/n) sum_{w_s != 0} |r_s w_s|
+ *   out[0]  = weight * (lambda_depth L_depth + lambda_silhouette L_sil) + add_weight * add[0]   (add may be NULL)
+ *   out[1]  = L_depth        out[2] = L_sil            (0 for a term that is off)
+ *   d_depth = g weight lambda_depth w_d sign(r_d w_d) / n
+ *   d_alpha = g weight (-lambda_depth w_d Z sign(r_d w_d) + lambda_silhouette w_s sign(r_s w_s)) / n       (g = g_scalar[0], on the device)
+ * SELECTION, not multiplication: a pixel with w == 0 adds exactly 0 and gets exactly 0 gradient whatever D, A, Z hold there (NaN, Inf);
+ * a NaN in D or A where w != 0 makes that term (and that pixel's gradient) NaN.  sign(0) = 0, as in csplat_l1_signs: pixels where nothing
+ * blended (D = A = 0) are exact ties of r_d.  The division is by n, ALL pixels of the call (the convention of the reference's masked L1,
+ * abs((x - y) * mask).mean(), utils/loss_utils.py:20-23).
+ * sign8 [n_views][hw]: one byte per pixel, bits 0-1 the code of sign(r_d w_d), bits 2-3 of sign(r_s w_s) (0: -1, 1: 0, 2: +1, 3: NaN);
+ * NULL = no gradient wanted, nothing is stored.  d_depth / d_alpha [n_views][hw] floats, either may be NULL.  scratch:
+ * csplat_geom_loss_scratch_bytes bytes, no initial state, not shared between concurrent calls.  Bit-reproducible: workgroup partials summed
+ * in index order by a one-workgroup second launch, no float atomics.  More than 16 views run as one launch per 16 (the kernel's table
+ * size) with the same result.  Every image needs 4-byte alignment; 16-byte accesses are used when all of them (and d_depth / d_alpha)
+ * are 16-byte aligned and hw is a multiple of 4. */
+size_t csplat_geom_loss_scratch_bytes(int n_views, int64_t hw);
+int csplat_geom_loss_fwd(void *stream, int n_views, int64_t hw, const float *const *depth, const float *const *alpha,
+                         const float *const *gt_depth, const float *const *silhouette, const float *const *mask, float lambda_depth,
+                         float lambda_silhouette, float weight, const float *add, float add_weight, unsigned char *sign8, void *scratch,
+                         float *out);
+int csplat_geom_loss_bwd(void *stream, int n_views, int64_t hw, const unsigned char *sign8, const float *const *gt_depth,
+                         const float *const *mask, float lambda_depth, float lambda_silhouette, float weight, const float *g_scalar,
+                         float *d_depth, float *d_alpha);
 
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
@@ -574,6 +608,7 @@ int csplat_mesh_transform_bwd_views(void *stream, int T, int P, int V, const int
  *   13 K8 of the camera path | 14 the camera path's background partials and fixed-order sums (csplat_view.dL_dview .. dL_dbg)
  *   15 the feature / alpha forward pass | 16 feature partials prepass | 17 K7 of the feature path | 18 feature gradient extraction
  *   (csplat_view.features .. dL_dfeat_in) | 19 the visibility walk and per-Gaussian reduce (csplat_visibility_views)
+ *   20 csplat_geom_loss_fwd (both launches) | 21 csplat_geom_loss_bwd
  * csplat_prof_read synchronises the recorded events of class k, returns their summed duration (ms) and the
  * number of brackets, and recycles the events. */
 int csplat_prof_enable(unsigned mask);
