@@ -32,10 +32,20 @@
 //   0  two fp16 pieces per operand (x = h1 + h2 to 2^-22 |x|), three products per step (h1 h1 + h1 h2 + h2 h1): 24 MFMAs per tile-layer.
 //      fp16 has 5 exponent bits, so the values are kept where they are representable: the launch's max |e0| (csplat_absmax, once per
 //      rollout step: e0 is the same for all layers) gives the power of two cs that brings the edge rows to max in [8, 16), and ALL the
-//      arithmetic runs multiplied by s = cs / alpha (exact; ReLU is homogeneous, LayerNorm takes s^2 eps).  Domain: activations of the two
-//      inner layers within 2^12 of the edge rows' scale and |weights| >= ~1e-2 of their matrix' largest for full accuracy (an element
-//      below 2^-3 of fp16's normal range keeps an ABSOLUTE error of 2^-25 in the scaled units); an overflow shows as Inf / NaN rows.
-//      LayerNorm'd latents and trained / initialised MLPs sit in the middle of it; measured 3e-7 of the output scale against fp64.
+//      arithmetic runs multiplied by s = cs / alpha (exact; ReLU is homogeneous, LayerNorm takes s^2 eps).  An element below 2^-3 of
+//      fp16's normal range keeps an ABSOLUTE error of 2^-25 in the scaled units, and a row's LayerNorm divides that by the row's own
+//      size: what a row loses depends on how far its inner activations sit below the LAUNCH's scale (max |e0| x alpha: alpha multiplies
+//      the edge term only, so a row whose edge features are small or zero -- its node terms s (b0 + xa + xb) alone -- sits alpha times
+//      lower).  Per row, in units of max(max_j |out|, 1), against fp64, from the float64 model of this arithmetic (tests/edge_mlp_ref.py,
+//      table in tests/test_edge_mlp_cpu.py; fp32 itself: 5e-7):
+//        rows within 2^6 of the launch's scale (ordinary, one-hot, zero and 2^-20 rows at alpha <= 64; one edge row 2^6 above the
+//        others or e0_absmax overstated by 2^6 at alpha <= 1)                                                        4e-7 .. 9e-7
+//        the same with weight elements down to 1e-3 of their matrix' largest: 4e-7 at alpha <= 1, 1.7e-6 at alpha 64
+//        2^12 (one edge row 2^12 above the others: THEIR rows; or 2^6 at alpha 64)                                   3e-5 .. 5e-5
+//        2^14 (alpha 16384 on rows without edge features) 1e-4; 2^20 and beyond: 1e-2 .. O(1)
+//      The largest row of a launch always keeps 2e-7 .. 1e-6.  Upwards: an inner activation beyond 65504 in the scaled units (2^12 above the
+//      edge rows' scale; an understated e0_absmax, or edge rows far BELOW O(1) node terms -- max |e0| = 1e-6 puts s at 2^23) leaves fp16's
+//      range and shows as a NaN row, never as a wrong finite one.  LayerNorm'd latents and trained / initialised MLPs sit in the middle.
 //   1  three bf16 pieces per operand, the six products that matter: 48 MFMAs per tile-layer, fp32's exponent range, no scaling beyond
 //      1 / alpha.  7e-7 against fp64 on anything fp32 can hold.
 //

@@ -80,6 +80,15 @@ def _f32a(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _vec(t):
+    """a bias / gamma / beta vector as the one-launch kernels read it: detached, float32, contiguous, on a 16-byte boundary"""
+    return None if t is None else _f32a(t.detach())
+
+
+def _i32_on(t, device, what):
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.device == device, f"{what}: a contiguous int32 tensor on {device}"
+
+
 def piece_numbering(dst_sorted, rowptr, group=8):
     """The numbering of the "pieces" the one-launch edge MLP leaves instead of messages (csplat_gnn_edge_mlp3 with `pieces`): rows are edges in
     destination order; a piece = a maximal run of rows with one destination, cut additionally at every multiple of `group` rows (a wave
@@ -454,9 +463,11 @@ def edge_mlp3_mode(mode=None):
 
 
 def absmax(x):
-    """max |x| as a one-element device tensor (csplat_absmax: one pass, no host read) -- what edge_mlp3 takes its fp16 scale from"""
+    """max |x| as a one-element device tensor (csplat_absmax: one pass, no host read) -- what edge_mlp3 takes its fp16 scale from.
+    The kernel's fmaxf IGNORES a NaN: the result is the maximum over the elements that are not NaN (0 when all are, and for no elements);
+    an Inf is returned as Inf."""
     _n.require_cuda(x)
-    x = _f32(x)
+    x = _f32a(x)
     assert x.numel() % 4 == 0
     out = torch.empty(1, dtype=torch.float32, device=x.device)
     with _n.on_device(x.device):
@@ -491,7 +502,7 @@ def edge_mlp3(e0, alpha, xa, ia, xb, ib, image, b0, b1, b2, layer_norm, out=None
     agg = (gp0, pieces) -- rows in destination order (GraphCSR.agg_plan): the messages are not written, their per-run sums land in
     `pieces` [npieces,128] (returned); mode 0 only."""
     _n.require_cuda(e0)
-    e0, xa, xb = _f32(e0), _f32(xa), _f32(xb)
+    e0, xa, xb = _f32a(e0), _f32a(xa), _f32a(xb)
     E = e0.shape[0]
     assert e0.shape[1] == 128 and xa.shape[1] == 128 and xb.shape[1] == 128
     ia, ib = ia.contiguous(), ib.contiguous()
@@ -499,16 +510,20 @@ def edge_mlp3(e0, alpha, xa, ia, xb, ib, image, b0, b1, b2, layer_norm, out=None
     gp0 = pieces = None
     if agg is not None:
         gp0, pieces = agg
-        assert gp0.dtype == torch.int32 and gp0.numel() == (E + 7) // 8 and pieces.dtype == torch.float32 and pieces.shape[1] == 128
-    else:
-        out = torch.empty_like(e0) if out is None else out
+        _i32_on(gp0, e0.device, "gp0")
+        assert gp0.numel() == (E + 7) // 8 and pieces.dtype == torch.float32 and pieces.dim() == 2 and pieces.shape[1] == 128
+        assert pieces.is_contiguous() and pieces.device == e0.device and pieces.data_ptr() % 16 == 0, "pieces: contiguous, 16-byte aligned, on e0's device"
+    elif out is None:
+        out = torch.empty_like(e0)
+    elif not (out.dtype == torch.float32 and out.is_cuda and out.device == e0.device and tuple(out.shape) == (E, 128)
+              and out.is_contiguous() and out.data_ptr() % 16 == 0):
+        raise ValueError("edge_mlp3: out must be a contiguous, 16-byte aligned float32 tensor of shape (E, 128) on e0's device")
     if e0_absmax is None and E > 0 and edge_mlp3_mode() == 0:
         e0_absmax = absmax(e0)
-    c = lambda t: t.detach().contiguous()  # noqa: E731
+    vs = [_vec(t) for t in (b0, b1, b2, layer_norm.weight, layer_norm.bias)]       # (a copy must outlive the launch call: held here)
     with _n.on_device(e0.device):
         _n.check(_n.lib.csplat_gnn_edge_mlp3(_n.stream_handle(e0.device), E, _n.ptr(e0), float(alpha), _n.ptr(e0_absmax), _n.ptr(xa), _n.ptr(ia),
-                                             _n.ptr(xb), _n.ptr(ib), _n.ptr(image), _n.ptr(c(b0)), _n.ptr(c(b1)), _n.ptr(c(b2)),
-                                             _n.ptr(c(layer_norm.weight)), _n.ptr(c(layer_norm.bias)), float(layer_norm.eps), _n.ptr(out),
+                                             _n.ptr(xb), _n.ptr(ib), _n.ptr(image), *[_n.ptr(t) for t in vs], float(layer_norm.eps), _n.ptr(out),
                                              _n.ptr(gp0), _n.ptr(pieces)),
                  "csplat_gnn_edge_mlp3")
     return out if agg is None else pieces
@@ -542,16 +557,16 @@ def mlp3_rows(x, image, b0, b1, b2, layer_norm, x_absmax=None):
     (csplat_gnn_mlp3_rows: the one-launch edge MLP's kernel without gathers).  image = edge_mlp3_pack(W0 zero-padded to [128,128], W1, W2)
     under edge_mlp3_mode 0; x_absmax = absmax(x), computed here when not handed in."""
     _n.require_cuda(x)
-    x = _f32(x)
+    x = _f32a(x)
     M, K = x.shape
     assert K % 4 == 0 and 4 <= K <= 128 and edge_mlp3_mode() == 0
     out = torch.empty(M, 128, dtype=torch.float32, device=x.device)
     if x_absmax is None and M > 0:
         x_absmax = absmax(x)
-    c = lambda t: t.detach().contiguous()  # noqa: E731
+    vs = [_vec(t) for t in (b0, b1, b2, layer_norm.weight, layer_norm.bias)]       # (a copy must outlive the launch call: held here)
     with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_mlp3_rows(_n.stream_handle(x.device), M, _n.ptr(x), K, _n.ptr(x_absmax), _n.ptr(image), _n.ptr(c(b0)), _n.ptr(c(b1)),
-                                             _n.ptr(c(b2)), _n.ptr(c(layer_norm.weight)), _n.ptr(c(layer_norm.bias)), float(layer_norm.eps), _n.ptr(out)),
+        _n.check(_n.lib.csplat_gnn_mlp3_rows(_n.stream_handle(x.device), M, _n.ptr(x), K, _n.ptr(x_absmax), _n.ptr(image), *[_n.ptr(t) for t in vs],
+                                             float(layer_norm.eps), _n.ptr(out)),
                  "csplat_gnn_mlp3_rows")
     return out
 
@@ -583,14 +598,14 @@ def rows_chain_pack(mode, w_first, w_second):
 def rows_chain(x, image, mode, b0=None, b1=None):
     """csplat_gnn_rows_chain (include/csplat.h), no autograd: mode 0 -> (x Wa^T, x Wb^T); mode 1 -> relu(W1 relu(W0 x + b0) + b1)"""
     _n.require_cuda(x)
-    x = _f32(x)
+    x = _f32a(x)
     N = x.shape[0]
     assert x.shape[1] == 128
     out_a = torch.empty_like(x)
     out_b = torch.empty_like(x) if mode == 0 else None
-    c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+    vs = [_vec(b0), _vec(b1)]       # (a copy must outlive the launch call: held here)
     with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_rows_chain(_n.stream_handle(x.device), N, int(mode), _n.ptr(x), _n.ptr(image), _n.ptr(c(b0)), _n.ptr(c(b1)),
+        _n.check(_n.lib.csplat_gnn_rows_chain(_n.stream_handle(x.device), N, int(mode), _n.ptr(x), _n.ptr(image), _n.ptr(vs[0]), _n.ptr(vs[1]),
                                               _n.ptr(out_a), _n.ptr(out_b)), "csplat_gnn_rows_chain")
     return (out_a, out_b) if mode == 0 else out_a
 
@@ -599,17 +614,18 @@ def node_update_packed(agg, x, image, b0, b2, b3, layer_norm, has_next, piece_pt
     """node_update() on the pre-packed weights (csplat_gnn_node_update_packed, include/csplat.h): returns (x_new, xa', xb').  piece_ptr
     (int32 [N + 1]): `agg` is the pieces array of edge_mlp3's fused aggregation, a node's aggregate = the sum of its pieces"""
     _n.require_cuda(x)
-    agg, x = _f32(agg), _f32(x)
+    agg, x = _f32a(agg), _f32a(x)
     N = x.shape[0]
     assert agg.shape[1] == 128 and x.shape[1] == 128 and (piece_ptr is not None or agg.shape[0] == N)
-    assert piece_ptr is None or (piece_ptr.dtype == torch.int32 and piece_ptr.numel() == N + 1)
-    c = lambda t: t.detach().contiguous()  # noqa: E731
+    if piece_ptr is not None:
+        _i32_on(piece_ptr, x.device, "piece_ptr")
+        assert piece_ptr.numel() == N + 1
+    vs = [_vec(t) for t in (b0, b2, b3, layer_norm.weight, layer_norm.bias)]       # (a copy must outlive the launch call: held here)
     x_new = torch.empty_like(x)
     xa = torch.empty_like(x) if has_next else None
     xb = torch.empty_like(x) if has_next else None
     with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_node_update_packed(_n.stream_handle(x.device), N, _n.ptr(agg), _n.ptr(x), _n.ptr(image), _n.ptr(c(b0)), _n.ptr(c(b2)),
-                                                      _n.ptr(c(b3)), _n.ptr(c(layer_norm.weight)), _n.ptr(c(layer_norm.bias)), float(layer_norm.eps),
+        _n.check(_n.lib.csplat_gnn_node_update_packed(_n.stream_handle(x.device), N, _n.ptr(agg), _n.ptr(x), _n.ptr(image), *[_n.ptr(t) for t in vs], float(layer_norm.eps),
                                                       int(bool(has_next)), _n.ptr(x_new), _n.ptr(xa), _n.ptr(xb), _n.ptr(piece_ptr)), "csplat_gnn_node_update_packed")
     return x_new, xa, xb
 

@@ -793,11 +793,16 @@ int csplat_linear_narrow128(void *stream, int64_t M, int K, const float *x, int 
  * kernel the 16-bit pieces of its 32 output rows of the three W as MFMA A operands, in the order the kernel loads them into registers.
  * Pack once per weight version AND mode: W_l is read as W_l[j * ld_l + k] (a Linear.weight or a 128-column slice of a wider one).
  * csplat_gnn_edge_mlp3_mode(mode) selects the arithmetic and returns the previous mode (any other value only queries):
- *   0 (default)  two fp16 pieces per operand, three products: 3e-7 of the output scale against fp64 inside its domain -- the values are
- *                brought into fp16's range by a power of two taken from e0_absmax = the device word csplat_absmax leaves (max |e0| over
- *                the launch's rows or over a superset of them; NULL = 1.0).  Domain and failure mode: header of csplat_edge_mlp.hip.
+ *   0 (default)  two fp16 pieces per operand, three products.  The values are brought into fp16's range by ONE power of two per launch,
+ *                taken from e0_absmax = the device word csplat_absmax leaves (max |e0| over the launch's rows or over a superset of them;
+ *                NULL = 1.0).  Per row, in units of max(max_j |out|, 1), against fp64 (fp32 itself: 5e-7): 4e-7 .. 9e-7 for rows whose inner
+ *                activations are within 2^6 of the launch's scale max |e0| x alpha; 3e-5 .. 5e-5 at 2^12 (the OTHER rows of a launch that
+ *                holds one edge row 2^12 above them); 1e-4 at 2^14 (rows without edge features at alpha 16384) and up to O(1) beyond.  An
+ *                inner activation 2^12 ABOVE the edge rows' scale, or an understated e0_absmax, leaves fp16's range: a NaN row, never a
+ *                wrong finite one.  Table: tests/test_edge_mlp_cpu.py; the arithmetic: header of csplat_edge_mlp.hip.
  *   1            three bf16 pieces per operand, six products: fp32's exponent range, 7e-7 against fp64; e0_absmax is not read.
- * csplat_absmax(n, x, out): *out = max |x[i]| (n a multiple of 4, x 16-byte aligned; one pass, asynchronous on `stream`).
+ * csplat_absmax(n, x, out): *out = max |x[i]| over the elements that are not NaN (fmaxf ignores a NaN; 0 for n = 0 and when all are NaN;
+ * Inf for an Inf) -- n a multiple of 4, x 16-byte aligned; one pass, asynchronous on `stream`.
  * Fused aggregation (mode 0; pieces != NULL, out may be NULL and is not written): the rows are in DESTINATION order (index_a
  * non-decreasing: the caller permuted e0 / index_a / index_b by the CSR order), and instead of E message rows the launch writes their sums
  * over runs of equal index_a, cut additionally every 8 rows: piece p = sum of the rows of run p, [npieces][128] fp32, numbered in row
