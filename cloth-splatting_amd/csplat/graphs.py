@@ -13,7 +13,7 @@ import torch
 from . import native as _n
 
 MARGIN = 8          # capacities = counts + counts / MARGIN (+ a constant)
-LIST_CAP = 8192     # longest tile list the in-LDS tile sort takes (csplat_raster.hip)
+LIST_CAP = 8192     # longest tile list the in-LDS tile sort takes (BUCKET_CAP, csplat_raster_binning.h)
 
 
 @_contextlib.contextmanager

@@ -31,7 +31,7 @@ import numpy as np
 import util
 from util import make_case
 
-BUCKET_TILES = 12288          # csplat_raster.hip: most tiles of the bucket path
+BUCKET_TILES = 12288          # csplat_raster_binning.h: most tiles of the bucket path
 RADIX_DIGIT_BITS = 8          # csplat_sort.hip: RADIX = 256
 TILE_SORT_SMALL_CAP = 5120    # csplat_raster.hip: tile_sort_cap() when the device refuses 96 KB of LDS per workgroup
 TILE = 16
@@ -58,7 +58,7 @@ def tiles_of(W, H):
 
 
 def higher_msb(n):
-    """csplat_raster.hip higher_msb: bits needed for tile ids < n, at least 1"""
+    """csplat_raster.hip (host half) higher_msb: bits needed for tile ids < n, at least 1"""
     b = 0
     while (1 << b) < n and b < 31:
         b += 1
@@ -73,10 +73,18 @@ def radix_passes(tiles):
     return (end_bit(tiles) + RADIX_DIGIT_BITS - 1) // RADIX_DIGIT_BITS
 
 
+RASTER_PART = re.compile(r'^#include "(csplat_raster_\w+\.h)"[^\n]*$', re.M)
+
+
+def raster_source(csrc):
+    """csplat_raster.hip with its parts (csrc/csplat_raster_*.h) in the place of their #include lines: the rasterizer's text in include order"""
+    return RASTER_PART.sub(lambda m: open(os.path.join(csrc, m.group(1))).read(), open(os.path.join(csrc, "csplat_raster.hip")).read())
+
+
 def source_constants():
     """the launch constants this module restates, read from the HIP sources"""
     csrc = os.path.join(util.ROOT, "cloth-splatting_amd", "csrc")
-    raster = open(os.path.join(csrc, "csplat_raster.hip")).read()
+    raster = raster_source(csrc)
     sort = open(os.path.join(csrc, "csplat_sort.hip")).read()
     one = lambda pat, text: re.search(pat, text, re.S).group(1)  # noqa: E731
     return dict(

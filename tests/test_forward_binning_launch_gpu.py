@@ -17,7 +17,7 @@ from util import oracle_forward, rel_err, syn
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-BUCKET_CAP = 8192       # longest list the in-LDS sort takes (csrc/csplat_raster.hip)
+BUCKET_CAP = 8192       # longest list the in-LDS sort takes (csrc/csplat_raster_binning.h)
 INFO_BUSY = 64          # word offset of the busy list inside the info block; the longest-first order follows at INFO_BUSY + tiles + 4
 RADIX_ONLY = 2048       # csplat_debug_flags bit 11
 FORCED_FALLBACK = 4096  # bit 12: bucket limit 1

@@ -850,7 +850,7 @@ def test_preprocess_full_size_against_a_numpy_fp64_restatement():
     """K1 at BASELINE configs[1] size against a restatement written here in numpy float64 from the published algorithm (SURVEY Appendix
     A.1) -- view transform, near cull at 0.2, homogeneous divide with the 1e-7 guard, Sigma = (S R)^T (S R) from the UN-normalised
     quaternion, the 1.3 tan(fov) frustum clamp, J W Sigma W^T J^T + 0.3 I, conic, radius = ceil(3 sqrt(lambda_max)) with the
-    max(0.1, mid^2 - det) guard, ndc2pix -- sharing no line with oracle/raster_ref.c or csplat_raster.hip.  The fp32 oracle must agree
+    max(0.1, mid^2 - det) guard, ndc2pix -- sharing no line with oracle/raster_ref.c or csplat_raster_k1.h.  The fp32 oracle must agree
     with it: depth / centre / conic to fp32 rounding, the cull decision everywhere, the integer radius everywhere except where
     3 sqrt(lambda_max) lies within fp32 rounding of an integer (counted: < 1e-4 of the Gaussians, off by exactly one)."""
     case, o = _full_size_case()

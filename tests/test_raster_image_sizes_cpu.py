@@ -1,8 +1,11 @@
 """The size table and scenes of tests/image_sizes_ref.py are what they claim (CPU): every size crosses the host-code switch it is in the
-table for (the constants restated from csplat_raster.hip / csplat_sort.hip and compared with the sources, as tests/test_train_kernels_cpu.py
+table for (the constants restated from csplat_raster*.{hip,h} / csplat_sort.hip and compared with the sources, as tests/test_train_kernels_cpu.py
 does for the train-step launches), the scenes put visible Gaussians where the tile grid ends, and the reference pair of the GPU test -- the
 C oracle in fp32 against fp64 -- itself stays inside the bars and the threshold-tie allowances the GPU test applies, so that an allowance
 cannot hide a GPU error that the references do not show themselves."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -25,6 +28,18 @@ def test_constants_are_the_sources():
     assert c["RADIX"] == 1 << S.RADIX_DIGIT_BITS
     assert c["passes"].replace(" ", "") == "(end_bit+7)/8" and c["shifts"] == ["p * 8", "p * 8"]
     assert c["digit_masks"] and all(int(m, 16) == c["RADIX"] - 1 for m in c["digit_masks"])
+
+
+def test_every_raster_part_is_included_once_by_the_rasterizer_only():
+    csrc = os.path.join(util.ROOT, "cloth-splatting_amd", "csrc")
+    parts = sorted(f for f in os.listdir(csrc) if re.fullmatch(r"csplat_raster_\w+\.h", f))
+    assert parts
+    included = {f: re.findall(r'^\s*#\s*include\s*["<](?:[^">]*/)?(csplat_raster_\w+\.h)[">]', open(os.path.join(csrc, f)).read(), re.M)
+                for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
+    assert sorted(included["csplat_raster.hip"]) == parts                  # each one, once
+    assert all(not inc for f, inc in included.items() if f != "csplat_raster.hip"), included
+    # what source_constants reads is the whole translation unit: no part's #include line is left in it
+    assert not S.RASTER_PART.search(S.raster_source(csrc))
 
 
 TABLE = {   # name -> (tiles, gx, gy, higher_msb, key bits, radix passes)

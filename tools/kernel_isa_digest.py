@@ -5,6 +5,10 @@ FILE.s is what `hipcc <flags of csrc/build.sh> -save-temps=obj -c X.hip` leaves 
 covers its instruction lines (comments stripped; local labels .LBB<n>_<m> without <n>, the function's number in the file) and its
 .amdhsa_* resource block, so two builds whose outputs `diff` empty run the same device code with the same registers, LDS and scratch:
 the check a host-only change of a .hip file has to pass.  Sorted by name; a kernel that is missing or new shows up in the diff as well.
+
+profiles/raster_isa_digest.txt is this tool's output for csplat_raster.hip (with its parts, csrc/csplat_raster_*.h) as committed, under two
+`#` heading lines that name the commit and the flags: a change that must not touch device code diffs its own output against that file
+(`grep -v "^#"`) instead of rebuilding its parent, and a change that does touch it commits the new listing.
 """
 import hashlib
 import re
