@@ -23,9 +23,14 @@ differentiates with o' (include/csplat.h, CSPLAT_ANTIALIAS); it composes with ev
 `return_visibility=True` appends a `Visibility(weight_max, weight_sum, pixel_count, top_id)`: per Gaussian the peak and the summed blending
 weight T alpha and the number of pixels it blended into, per pixel the id of the Gaussian with the largest weight (include/csplat.h,
 csplat_visibility_views) -- forward only, bit-reproducible.  Without it the call is unchanged.
+Which tensor argument, output and returned gradient of the batched Function belongs to which view is the business of one object,
+`_CallLayout`, built once per call by `rasterize_gaussians` / `rasterize_views`; what a per-Gaussian input is called, where it is saved
+and which gradient field and shape it has is one table, `_INPUTS` (tests/test_raster_call_layout_cpu.py needs no GPU).
 """
 import contextlib as _contextlib
 import ctypes as C
+from math import prod as _prod
+from operator import attrgetter as _attrgetter
 from typing import NamedTuple
 
 import torch
@@ -106,14 +111,6 @@ def _cam_returns(outs, cam_inputs):
     return tuple(None if g is None else g.view(t.shape).to(device=t.device, dtype=t.dtype) for g, t in zip(outs, cam_inputs))
 
 
-class _FeatSpec:
-    """the feature / alpha request of a batched call, one (F, return_alpha) per view (F = 0: no features); the last argument of
-    _RasterizeGaussiansBatch.apply, behind the views' feature tensors, when any view asks for either"""
-
-    def __init__(self, per_view):
-        self.per_view = [(int(f), bool(a)) for f, a in per_view]
-
-
 def _check_features(features, means3D):
     """-> F of a `features` argument; ValueError unless it is a float32 [P, F] tensor on the device of means3D with 1 <= F <= 6"""
     if not torch.is_tensor(features):
@@ -129,13 +126,7 @@ def _check_features(features, means3D):
     return int(features.shape[1])
 
 
-class _Antialias:
-    """marker: the LAST argument of _RasterizeGaussiansBatch.apply when the call renders antialiased (csplat_view.prefiltered |=
-    CSPLAT_ANTIALIAS in every view); absent otherwise, so that a call without antialiasing sees exactly the inputs it saw before"""
-
-
-_ANTIALIAS = _Antialias()
-CSPLAT_ANTIALIAS = 2      # csplat.h
+CSPLAT_ANTIALIAS = 2      # csplat.h: csplat_view.prefiltered |= CSPLAT_ANTIALIAS in every view of an antialiased call
 
 
 class Visibility(NamedTuple):
@@ -147,14 +138,6 @@ class Visibility(NamedTuple):
     weight_sum: torch.Tensor
     pixel_count: torch.Tensor
     top_id: torch.Tensor
-
-
-class _VisSpec:
-    """the visibility request of a batched call, one bool per view; the argument of _RasterizeGaussiansBatch.apply behind the feature
-    arguments (in front of the _ANTIALIAS marker) when any view asks for it, absent otherwise"""
-
-    def __init__(self, per_view):
-        self.per_view = [bool(x) for x in per_view]
 
 
 NVIS = len(Visibility._fields)      # outputs a view's visibility adds to the Function's outputs
@@ -174,17 +157,146 @@ def _visibility_mode_check():
                            "replayed step -- compute it in an eager step")
 
 
-def _group_visibility(outs, per_view):
-    """a view's flat outputs -> the same tuple with its last NVIS tensors as one Visibility when the view asked for it"""
-    outs = tuple(outs)
-    return outs[:-NVIS] + (Visibility(*outs[-NVIS:]),) if per_view else outs
-
-
 def _feature_mode_check():
     """feature / alpha images are rendered by eager steps only"""
     if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
         raise RuntimeError("diff_gaussian_rasterization: feature / alpha images are not rendered by a forward launched on faith or a "
                            "captured / replayed step -- render them in an eager step")
+
+
+class _Input(NamedTuple):
+    """one per-Gaussian input of a view"""
+    name: str           # the _View attribute (rasterize_gaussians' parameter)
+    slot: int           # position among a view's NIN tensor arguments
+    saved: object       # position in _View.saved(); None: not saved for the backward
+    field: str          # the csplat_view gradient field
+    acc: object         # the accumulate bit of a gradient buffer shared between views; None: K7's own output, one buffer per view
+    shape: object       # (P, M) -> shape of the gradient
+    optional: bool      # may be None: present when its saved tensor is; else always present
+    temp: bool = False  # K8 writes the buffer even when the input is absent (it is never handed back then)
+
+
+_INPUTS = (
+    _Input("means3D", 0, 0, "dL_dmean3D", _n.ACC_MEAN3D, lambda P, M: (P, 3), False),
+    _Input("means2D", 1, None, "dL_dmean2D", None, lambda P, M: (P, 3), False),      # (K7's own output, one per view)
+    _Input("sh", 2, 1, "dL_dsh", _n.ACC_SH, lambda P, M: (P, M, 3), True),
+    _Input("colors_precomp", 3, 2, "dL_dcolor", _n.ACC_COLOR, lambda P, M: (P, 3), True, True),
+    _Input("opacities", 4, None, "dL_dopacity", _n.ACC_OPACITY, lambda P, M: (P, 1), False),
+    _Input("scales", 5, 3, "dL_dscale", _n.ACC_SCALE, lambda P, M: (P, 3), True),
+    _Input("rotations", 6, 4, "dL_drot", _n.ACC_ROT, lambda P, M: (P, 4), True),
+    _Input("cov3Ds_precomp", 7, 5, "dL_dcov3D", _n.ACC_COV3D, lambda P, M: (P, 6), True, True),
+)
+NIN = len(_INPUTS)
+_IN = {r.name: r for r in _INPUTS}
+_SAVED = sorted((r for r in _INPUTS if r.saved is not None), key=lambda r: r.saved)
+_SAVED_OF = _attrgetter(*(r.name for r in _SAVED), "radii", "color")      # what _View.saved() saves, in that order
+_GRAD_FIELDS = ("dL_dconic",) + tuple(r.field for r in _INPUTS)     # every gradient pointer of a csplat_view the plan sets
+_K7_OUT = tuple(r for r in _INPUTS if r.acc is None)        # gradients K7 writes itself
+_K8_OUT = tuple(r for r in _INPUTS if r.acc is not None)    # gradients K8 writes, into a buffer of their view or a shared one
+
+
+class _CallLayout:
+    """How one call of _RasterizeGaussiansBatch is laid out: the order of its tensor arguments, the order of its outputs and the tuple
+    its backward returns.  Beside the settings it holds no tensor, and it calls nothing; `_call_layout` builds it once per call and it
+    travels as the Function's first argument.  Index arithmetic on either sequence lives here and nowhere else.
+    Tensor arguments: V groups of the NIN per-Gaussian inputs (the slots of _INPUTS); then, when `cam`, V groups of (viewmatrix,
+    projmatrix, campos, bg); then, when a view asks for features or alpha (`has_feat`), V feature tensors (None where a view has none).
+    An optional group is absent otherwise: the node then has exactly the inputs it had before the option existed.
+    Outputs: the stacked colours [V, 3, H, W] when `stacked`; then per view colour (unless stacked), radii, depth, feat (F > 0), alpha
+    (when asked for), the NVIS tensors of a Visibility (when asked for)."""
+
+    OUTPUTS = ("color", "radii", "depth", "feat", "alpha") + Visibility._fields
+
+    def __init__(self, settings, stacked, cam, antialias, feat, vis):
+        V = self.V = len(settings)
+        self.settings, self.stacked, self.cam, self.aa = tuple(settings), bool(stacked), bool(cam), bool(antialias)
+        self.feat = [(int(f), bool(a)) for f, a in feat]       # per view (F, return_alpha); F = 0: no features
+        self.vis = [bool(x) for x in vis]                      # per view: return_visibility
+        self.has_feat = any(f or a for f, a in self.feat)
+        self.has_vis = any(self.vis)
+        self._cam0 = V * NIN
+        self._feat0 = self._cam0 + (4 * V if self.cam else 0)
+        self.n_tensors = self._feat0 + (V if self.has_feat else 0)
+        self.stacked_output = 0 if self.stacked else None
+        self.outputs, at = [], 1 if self.stacked else 0       # per view {output name: index}, in output order
+        for (F, alpha), v in zip(self.feat, self.vis):
+            names = [n for n, w in zip(self.OUTPUTS, (not self.stacked, True, True, F > 0, alpha) + (v,) * NVIS) if w]
+            self.outputs.append(dict(zip(names, range(at, at + len(names)))))
+            at += len(names)
+        self.n_outputs = at
+
+    # ---- the tensor arguments.  An index counts from the first tensor: argument 1 + index of apply(), ctx.needs_input_grad[1:][index]
+    def index(self, i, slot):
+        return i * NIN + slot
+
+    def cam_index(self, i, k):
+        return self._cam0 + 4 * i + k if self.cam else None
+
+    def feat_index(self, i):
+        return self._feat0 + i if self.has_feat else None
+
+    def pack(self, inputs, feats):
+        """per view the NIN inputs and the feature tensor (or None) -> the tensor arguments (the camera groups come from the settings)"""
+        tensors = [t for group in inputs for t in group]
+        if self.cam:
+            tensors += [t for rs in self.settings for t in _cam_tensors(rs)]
+        return tensors + list(feats) if self.has_feat else tensors
+
+    # (the accessors take any sequence laid out like the tensor arguments: the arguments themselves, ctx.needs_input_grad[1:])
+    def view_inputs(self, tensors, i):
+        return tensors[self.index(i, 0):self.index(i, NIN)]
+
+    def cam_group(self, tensors, i):
+        return tensors[self.cam_index(i, 0):self.cam_index(i, 4)] if self.cam else ()
+
+    def features(self, tensors, i):
+        return tensors[self.feat_index(i)] if self.has_feat else None
+
+    # ---- the outputs
+    def output(self, res, i, name):
+        """view i's output `name` out of a sequence laid out like the outputs (the outputs, backward's gradients); None: it has none"""
+        j = self.outputs[i].get(name)
+        return None if j is None else res[j]
+
+    def split(self, res):
+        """the Function's outputs -> what rasterize_views returns: per view (color, radii, depth[, feat][, alpha][, Visibility]); with
+        `stacked` (colors, [those tuples, color = colors[i]])"""
+        colors = res[0] if self.stacked else None
+        views = []
+        for i, o in enumerate(self.outputs):
+            t = [colors[i]] if self.stacked else []
+            t += [res[j] for j in o.values()]
+            if self.vis[i]:
+                t[-NVIS:] = [Visibility(*t[-NVIS:])]
+            views.append(tuple(t))
+        return (colors, views) if self.stacked else views
+
+    # ---- what backward returns
+    def grads(self, per_gaussian=None, cam=None, feat=None):
+        """backward's return value: per_gaussian[i] = view i's NIN gradients, cam[i] = the 4 of its camera group, feat[i] = its feature
+        tensor's -- each, and each entry, may be None; None for the layout and for every other input"""
+        out = [None] * (1 + self.n_tensors)
+        for seq, index, n in ((per_gaussian, self.index, NIN), (cam, self.cam_index, 4)):
+            for i, g in enumerate(seq or ()):
+                if g is not None:
+                    out[1 + index(i, 0):1 + index(i, n)] = g
+        for i, g in enumerate(feat or ()):
+            out[1 + self.feat_index(i)] = g
+        return tuple(out)
+
+
+def _call_layout(settings, stacked, antialias, feat, vis):
+    """the layout of one call (feat / vis: per view (F, return_alpha) / return_visibility, already checked).  The camera groups are
+    passed only when a settings tensor wants a gradient.  Raises, before any launch, what a call with features or visibility may raise."""
+    layout = _CallLayout(settings, stacked, any(_cam_group(rs) for rs in settings), antialias, feat, vis)
+    if layout.has_feat:
+        if len({f for f, _a in layout.feat}) > 1:
+            raise ValueError("rasterize_views: every view must have the same number of feature channels, got "
+                             f"{[f for f, _a in layout.feat]}")
+        _feature_mode_check()
+    if layout.has_vis:
+        _visibility_mode_check()
+    return layout
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -194,38 +306,19 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     on, the second forward phase is launched on the previous call's capacities and the counts are read AFTER the host has prepared the
     backward -- a camera-by-camera loop (the reference's train_utils.py:259-272) no longer leaves the GPU idle for a host round trip per
     camera.  Images, radii, depth and gradients are those of _RasterizeGaussians (tests: test_batched_views_equal_single_view_calls)."""
-    cam = _cam_group(raster_settings)
-    aa = (_ANTIALIAS,) if antialiasing else ()
-    if _check_visibility_flag(return_visibility):
-        # (visibility: the batched Function with one view -- csplat_visibility_views reads what csplat_forward_views_* leave)
-        extra = ()
-        if features is not None or return_alpha:
-            F = _check_features(features, means3D) if features is not None else 0
-            _feature_mode_check()
-            extra = (features, _FeatSpec([(F, return_alpha)]))
-        _visibility_mode_check()
+    vis = _check_visibility_flag(return_visibility)
+    F = _check_features(features, means3D) if features is not None else 0
+    # features, alpha, antialiasing and visibility exist in the batched Function only: csplat_forward_views_* render the extra images and
+    # carry the antialiasing bit to K1 and K8, csplat_backward_views takes the gradients, csplat_visibility_views reads what they leave
+    extended = bool(F or return_alpha or antialiasing or vis)
+    if not extended and not (PER_CALL_SPECULATION and means3D.is_cuda):
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, *_cam_group(raster_settings))
+    layout = _call_layout((raster_settings,), False, antialiasing, [(F, return_alpha)], [vis])
+    if extended:
         _n.require_cuda(means3D)
-        res = _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                             cov3Ds_precomp, *cam, *extra, _VisSpec([True]), *aa)
-        return _group_visibility(res, True)
-    if features is not None or return_alpha:
-        # (the feature / alpha path: always the batched Function with one view -- csplat_forward_views_* render the extra images,
-        #  csplat_backward_views takes their gradients)
-        F = _check_features(features, means3D) if features is not None else 0
-        _feature_mode_check()
-        _n.require_cuda(means3D)
-        return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                              cov3Ds_precomp, *cam, features, _FeatSpec([(F, return_alpha)]), *aa)
-    if antialiasing:
-        # (antialiasing: the batched Function with one view as well -- only the csplat_view entry points carry the bit to K1 and K8)
-        _n.require_cuda(means3D)
-        return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                              cov3Ds_precomp, *cam, *aa)
-    if PER_CALL_SPECULATION and means3D.is_cuda:
-        return _RasterizeGaussiansBatch.apply((raster_settings,), False, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                              cov3Ds_precomp, *cam)
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, *cam)
+    tensors = layout.pack([(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)], [features])
+    return layout.split(_RasterizeGaussiansBatch.apply(layout, *tensors))[0]
 
 
 PER_CALL_SPECULATION = True      # False: every call waits for its own counts (csplat_forward_begin / _finish, the path of rounds 1-4)
@@ -250,11 +343,25 @@ class _View:
         self.proj = _f32c(rs.projmatrix, dev, "projmatrix", False)
         self.campos = _f32c(rs.campos, dev, "campos", False)
         self.M = int(self.sh.shape[1]) if self.sh is not None else 0
-        self.ticket = None
+        self.ticket = self.chunks = None
 
-    def inputs(self):
-        return [t for t in (self.means3D, self.sh, self.colors_precomp, self.opacities, self.scales, self.rotations,
-                            self.cov3Ds_precomp, self.bg, self.view, self.proj, self.campos) if t is not None]
+    def fill(self, w, stream, tensors=None):
+        """the csplat_view fields a forward and a backward call share: sizes, scalars, the input and camera pointers, out_color, radii and,
+        once a forward has left them, the chunks and their counts.  tensors: (means3D, sh, colors_precomp, opacities, scales, rotations,
+        cov3Ds_precomp, color, radii) where the view no longer holds them (a backward: they come out of ctx.saved_tensors)"""
+        rs = self.rs
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, color, radii = tensors or (
+            self.means3D, self.sh, self.colors_precomp, self.opacities, self.scales, self.rotations, self.cov3Ds_precomp, self.color, self.radii)
+        w.stream = stream
+        w.P, w.D, w.M, w.W, w.H = self.P, int(rs.sh_degree), self.M, self.W, self.H
+        w.scale_modifier, w.tanfovx, w.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
+        w.bg, w.means3D, w.shs, w.colors_precomp = _n.ptr(self.bg), _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp)
+        w.opacities, w.scales, w.rotations = _n.ptr(opacities), _n.ptr(scales), _n.ptr(rotations)
+        w.cov3D_precomp, w.view, w.proj, w.campos = _n.ptr(cov3Ds_precomp), _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos)
+        w.out_color, w.radii = _n.ptr(color), _n.ptr(radii)
+        if self.chunks is not None:
+            w.num_rendered = w.layout_rendered = self.num_rendered
+            w.geom, w.binning, w.image = (_n.ptr(c) for c in self.chunks)
 
     def begin(self):
         """K1 + the counting half of the binning on the CURRENT stream; nothing here waits for the GPU."""
@@ -296,7 +403,6 @@ class _View:
         this one view (it takes the chunks csplat_forward_finish leaves), and a second tuple of the four camera gradients is returned."""
         means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = saved
         rs, dev, P, M = self.rs, self.dev, self.P, self.M
-        geom, binning, image = self.chunks
         if grad_color is None:
             grad_color = torch.zeros(3, self.H, self.W, dtype=torch.float32, device=dev)
         grad_color = _f32c_grad(grad_color, dev)
@@ -306,20 +412,14 @@ class _View:
         d_sh = new(P, M, 3) if sh is not None else None
         d_scale = new(P, 3) if scales is not None else None
         d_rot = new(P, 4) if rotations is not None else None
+        grads = (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
+                 d_cov3D if cov3Ds_precomp is not None else None)
         if cam_need is not None and any(cam_need):
             grad_depth = _f32c_grad(grad_depth, dev)
             scratch = new(max(int(_n.lib.csplat_backward_camera_scratch_bytes(P, self.num_rendered, self.W, self.H)), 256) // 4 + 1)
             cam_out = _cam_outputs(cam_need, dev)
             w = _n.CsplatView()
-            w.stream = _n.stream_handle(dev)
-            w.P, w.D, w.M, w.W, w.H = P, int(rs.sh_degree), M, self.W, self.H
-            w.scale_modifier, w.tanfovx, w.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
-            w.bg, w.means3D, w.shs, w.colors_precomp = _n.ptr(self.bg), _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp)
-            w.scales, w.rotations, w.cov3D_precomp = _n.ptr(scales), _n.ptr(rotations), _n.ptr(cov3Ds_precomp)
-            w.view, w.proj, w.campos = _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos)
-            w.out_color, w.radii = _n.ptr(color), _n.ptr(radii)
-            w.num_rendered = w.layout_rendered = self.num_rendered
-            w.geom, w.binning, w.image = _n.ptr(geom), _n.ptr(binning), _n.ptr(image)
+            self.fill(w, _n.stream_handle(dev), (means3D, sh, colors_precomp, None, scales, rotations, cov3Ds_precomp, color, radii))
             w.dL_dpix, w.dL_ddepth, w.scratch = _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch)
             w.dL_dmean2D, w.dL_dconic, w.dL_dopacity, w.dL_dcolor = _n.ptr(d_mean2D), _n.ptr(d_conic), _n.ptr(d_opac), _n.ptr(d_color)
             w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh = _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh)
@@ -329,40 +429,27 @@ class _View:
             with _n.on_device(dev):
                 rc = _n.lib.csplat_backward_views(1, C.addressof(w), w.stream)
             _n.check(rc, "csplat_backward_views")
-            return (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
-                    d_cov3D if cov3Ds_precomp is not None else None), cam_out
-        if grad_depth is not None:
-            grad_depth = _f32c_grad(grad_depth, dev)
-            scratch = torch.empty(max(int(_n.lib.csplat_backward_depth_scratch_bytes(P, self.num_rendered, self.W, self.H)), 256),
-                                  dtype=torch.uint8, device=dev)
-            with _n.on_device(dev):
-                rc = _n.lib.csplat_backward_depth(
-                    _n.stream_handle(dev), P, int(rs.sh_degree), M, self.num_rendered, _n.ptr(self.bg), self.W, self.H,
-                    _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp), _n.ptr(scales), float(rs.scale_modifier),
-                    _n.ptr(rotations), _n.ptr(cov3Ds_precomp), _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos),
-                    float(rs.tanfovx), float(rs.tanfovy), _n.ptr(radii), _n.ptr(geom), _n.ptr(binning), _n.ptr(image),
-                    _n.ptr(color), _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch), _n.ptr(d_mean2D), _n.ptr(d_conic),
-                    _n.ptr(d_opac), _n.ptr(d_color), _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh), _n.ptr(d_scale), _n.ptr(d_rot))
-            _n.check(rc, "csplat_backward_depth")
-            return (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
-                    d_cov3D if cov3Ds_precomp is not None else None)
-        scratch = torch.empty(max(int(_n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)), 256), dtype=torch.uint8,
-                              device=dev)
-        with _n.on_device(dev):
-            rc = _n.lib.csplat_backward(
-                _n.stream_handle(dev), P, int(rs.sh_degree), M, self.num_rendered, _n.ptr(self.bg), self.W, self.H,
+            return grads, cam_out
+        # csplat_backward and csplat_backward_depth: one argument list, the depth entry takes dL_ddepth in front of the scratch
+        head = [_n.stream_handle(dev), P, int(rs.sh_degree), M, self.num_rendered, _n.ptr(self.bg), self.W, self.H,
                 _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp), _n.ptr(scales), float(rs.scale_modifier),
                 _n.ptr(rotations), _n.ptr(cov3Ds_precomp), _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos),
-                float(rs.tanfovx), float(rs.tanfovy), _n.ptr(radii), _n.ptr(geom), _n.ptr(binning), _n.ptr(image),
-                _n.ptr(color), _n.ptr(grad_color), _n.ptr(scratch), _n.ptr(d_mean2D), _n.ptr(d_conic), _n.ptr(d_opac),
-                _n.ptr(d_color), _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh), _n.ptr(d_scale), _n.ptr(d_rot))
-        _n.check(rc, "csplat_backward")
-        return (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
-                d_cov3D if cov3Ds_precomp is not None else None)
+                float(rs.tanfovx), float(rs.tanfovy), _n.ptr(radii), *(_n.ptr(c) for c in self.chunks), _n.ptr(color), _n.ptr(grad_color)]
+        outs = [_n.ptr(g) for g in (d_mean2D, d_conic, d_opac, d_color, d_mean3D, d_cov3D, d_sh, d_scale, d_rot)]
+        if grad_depth is not None:
+            entry, grad_depth = "csplat_backward_depth", _f32c_grad(grad_depth, dev)
+            nbytes = _n.lib.csplat_backward_depth_scratch_bytes(P, self.num_rendered, self.W, self.H)
+            head.append(_n.ptr(grad_depth))
+        else:
+            entry, nbytes = "csplat_backward", _n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)
+        scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        with _n.on_device(dev):
+            rc = getattr(_n.lib, entry)(*head, _n.ptr(scratch), *outs)
+        _n.check(rc, entry)
+        return grads
 
     def saved(self):
-        return (self.means3D, self.sh, self.colors_precomp, self.scales, self.rotations, self.cov3Ds_precomp, self.radii,
-                self.color)
+        return _SAVED_OF(self)
 
     def drop_inputs(self):
         """the tensors travel through ctx.save_for_backward; keep only constants and chunks here"""
@@ -524,49 +611,47 @@ def _view_streams(dev, n, main):
     return [main] + pool[:n - 1]
 
 
+# what _RasterizeGaussiansBatch.backward refuses, the first match is raised: (the gradient that arrived, where, the message)
+_REFUSALS = (
+    ("depth", "faith", "diff_gaussian_rasterization: a depth gradient reached a forward launched on faith (a captured / replayed step); "
+                       "those steps take no depth loss -- render the depth term in an eager step"),
+    ("feat", "faith", "diff_gaussian_rasterization: a feature / alpha gradient reached a forward launched on faith (a captured / "
+                      "replayed step); render feature and alpha images in an eager step"),
+    ("feat", "deferred_k8", "diff_gaussian_rasterization: a feature / alpha gradient reached a backward inside deferred_k8(); the sliced "
+                            "per-Gaussian backward takes no feature or alpha gradient"),
+    ("cam", "faith", "diff_gaussian_rasterization: a camera / background gradient reached a forward launched on faith (a captured / "
+                     "replayed step); those steps take no camera gradient -- refine the camera in an eager step"),
+    ("cam", "deferred_k8", "diff_gaussian_rasterization: a camera / background gradient reached a backward inside deferred_k8(); the sliced "
+                           "per-Gaussian backward takes no camera gradient"),
+)
+
+
 class _RasterizeGaussiansBatch(torch.autograd.Function):
     """V independent views in one autograd node and ONE library call each way (csplat_forward_views /
     csplat_backward_views).  Every view runs on its own HIP stream (the caller's + V-1 side streams, fenced inside the
     library): all K1/K2 are issued before the first num_rendered read, the under-filled compositing kernels of the views
     overlap, and a parameter tensor passed to several views gets ONE gradient buffer that the views' K8 add into.
-    Images / radii / depth are bit-identical to V calls of _RasterizeGaussians."""
-
-    NIN = 8
-    # slot in the per-view argument list -> (csplat_view gradient field, accumulate bit)
-    _GRAD = {0: ("dL_dmean3D", _n.ACC_MEAN3D), 2: ("dL_dsh", _n.ACC_SH), 3: ("dL_dcolor", _n.ACC_COLOR),
-             4: ("dL_dopacity", _n.ACC_OPACITY), 5: ("dL_dscale", _n.ACC_SCALE), 6: ("dL_drot", _n.ACC_ROT),
-             7: ("dL_dcov3D", _n.ACC_COV3D)}
+    Images / radii / depth are bit-identical to V calls of _RasterizeGaussians.
+    apply(layout, *tensors): `layout` is the call's _CallLayout, `tensors` what its pack() returns.  forward() reads its inputs through
+    the layout's accessors and places its outputs by the layout's names, backward() finds each view's gradients by those names and
+    returns layout.grads(...) -- neither counts arguments itself."""
 
     @staticmethod
-    def forward(ctx, settings, stacked, *flat):
-        # flat: V groups of NIN per-view inputs, then -- only when a settings tensor wants a gradient (_cam_group) -- V groups of
-        # (viewmatrix, projmatrix, campos, bg)
-        V, n = len(settings), _RasterizeGaussiansBatch.NIN
-        # (last of all, when the call renders antialiased: the _ANTIALIAS marker)
-        ctx.aa = bool(flat) and flat[-1] is _ANTIALIAS
-        if ctx.aa:
-            flat = flat[:-1]
-        # (then, when a view asks for visibility: the _VisSpec)
-        vspec = flat[-1] if flat and isinstance(flat[-1], _VisSpec) else None
-        if vspec is not None:
-            flat = flat[:-1]
+    def forward(ctx, layout, *tensors):
+        V, stacked = layout.V, layout.stacked
+        assert len(tensors) == layout.n_tensors
+        ctx.layout = layout
+        if layout.has_vis:
             _visibility_mode_check()
-        ctx.vspec = vspec.per_view if vspec is not None else None
-        # (then, when a view asks for feature or alpha images: V feature tensors (None where a view has none) and the _FeatSpec)
-        spec = flat[-1] if flat and isinstance(flat[-1], _FeatSpec) else None
-        feats = list(flat[-1 - V:-1]) if spec is not None else [None] * V
-        if spec is not None:
-            flat = flat[:-1 - V]
+        if layout.has_feat:
             _feature_mode_check()
-        ctx.fspec = spec.per_view if spec is not None else None
+        groups = [layout.view_inputs(tensors, i) for i in range(V)]
+        feats = [layout.features(tensors, i) for i in range(V)]
         ctx.feat_first = [next(j for j in range(i + 1) if feats[j] is feats[i]) for i in range(V)]     # (one gradient per tensor object)
-        assert len(flat) in (V * n, V * (n + 4))
-        ctx.cam = len(flat) > V * n
-        flat = flat[:V * n]
         views = []
-        for i in range(V):
-            means3D, _means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = flat[i * n:(i + 1) * n]
-            views.append(_View(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, settings[i]))
+        for group, rs in zip(groups, layout.settings):
+            means3D, _means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = group
+            views.append(_View(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, rs))
         dev = views[0].dev
         main = torch.cuda.current_stream(dev)
         streams = _view_streams(dev, V, main)
@@ -587,28 +672,22 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 return None
         cb = _n.ALLOC_FN(_alloc)
         for i, (v, st) in enumerate(zip(views, streams)):
-            rs, w = v.rs, arr[i]
+            w = arr[i]
             v.color = colors[i] if stacked else torch.empty(3, v.H, v.W, dtype=torch.float32, device=dev)
             v.depth = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
             v.radii = torch.empty(v.P, dtype=torch.int32, device=dev)
-            w.stream = st.cuda_stream
-            w.P, w.D, w.M, w.W, w.H, w.prefiltered = v.P, int(rs.sh_degree), v.M, v.W, v.H, int(bool(rs.prefiltered)) | (CSPLAT_ANTIALIAS if ctx.aa else 0)
-            w.scale_modifier, w.tanfovx, w.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
-            w.bg, w.means3D, w.shs, w.colors_precomp = _n.ptr(v.bg), _n.ptr(v.means3D), _n.ptr(v.sh), _n.ptr(v.colors_precomp)
-            w.opacities, w.scales, w.rotations = _n.ptr(v.opacities), _n.ptr(v.scales), _n.ptr(v.rotations)
-            w.cov3D_precomp, w.view, w.proj, w.campos = _n.ptr(v.cov3Ds_precomp), _n.ptr(v.view), _n.ptr(v.proj), _n.ptr(v.campos)
-            w.alloc_ctx = i
-            w.out_color, w.out_depth, w.radii = _n.ptr(v.color), _n.ptr(v.depth), _n.ptr(v.radii)
+            v.fill(w, st.cuda_stream)
+            w.prefiltered = int(bool(v.rs.prefiltered)) | (CSPLAT_ANTIALIAS if layout.aa else 0)
+            w.alloc_ctx, w.out_depth = i, _n.ptr(v.depth)
             v.feat = v.alpha = v.features = None
-            if spec is not None:
-                F, want_alpha = spec.per_view[i]
-                if F:
-                    v.features = feats[i].contiguous()
-                    v.feat = torch.empty(F, v.H, v.W, dtype=torch.float32, device=dev)
-                    w.features, w.n_features, w.out_features = _n.ptr(v.features), F, _n.ptr(v.feat)
-                if want_alpha:
-                    v.alpha = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
-                    w.out_alpha = _n.ptr(v.alpha)
+            F, want_alpha = layout.feat[i]
+            if F:
+                v.features = feats[i].contiguous()
+                v.feat = torch.empty(F, v.H, v.W, dtype=torch.float32, device=dev)
+                w.features, w.n_features, w.out_features = _n.ptr(v.features), F, _n.ptr(v.feat)
+            if want_alpha:
+                v.alpha = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
+                w.out_alpha = _n.ptr(v.alpha)
         # the one host read of the call (its counts) is DEFERRED when the library can launch the second phase on the previous call's
         # capacities: everything below that does not need the counts -- the output lists, the backward plan -- is host work done
         # while the GPU runs K1..K6, instead of after a ~45 us wait for K1 / K2
@@ -627,8 +706,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 rc = _n.lib.csplat_forward_views_deferred(V, C.cast(arr, C.c_void_p), cb, main.cuda_stream, C.byref(pending))
             _n.check(rc, "csplat_forward_views_deferred")
         try:
-            return _RasterizeGaussiansBatch._finish_forward(ctx, views, arr, chunks, flat, stacked, colors if stacked else None, dev, main,
-                                                            pending, cb)
+            return _RasterizeGaussiansBatch._finish_forward(ctx, views, arr, chunks, groups, colors if stacked else None, dev, main, pending, cb)
         except BaseException:
             if pending.value:        # never leave a call pending in the library (its tickets stay reserved otherwise)
                 dummy = C.c_int(0)
@@ -640,38 +718,39 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             raise
 
     @staticmethod
-    def _finish_forward(ctx, views, arr, chunks, flat, stacked, colors, dev, main, pending, cb):
-        V, n = len(views), _RasterizeGaussiansBatch.NIN
-        outs, saved = [], []
+    def _finish_forward(ctx, views, arr, chunks, groups, colors, dev, main, pending, cb):
+        layout = ctx.layout
+        V, stacked = layout.V, layout.stacked
+        outs, saved = [None] * layout.n_outputs, []
         for i, v in enumerate(views):
             v.num_rendered = int(arr[i].num_rendered)            # (-1 while the call is pending)
             v.layout_rendered = int(arr[i].layout_rendered)      # >= num_rendered: what the binning chunk was laid out for
             v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
-            outs += [v.radii, v.depth] if stacked else [v.color, v.radii, v.depth]
-            outs += [t for t in (v.feat, v.alpha) if t is not None]
+            made = {"color": v.color, "radii": v.radii, "depth": v.depth, "feat": v.feat, "alpha": v.alpha}
             v.vis = None
-            if ctx.vspec is not None and ctx.vspec[i]:
+            if layout.vis[i]:
                 v.vis = [torch.empty(v.P, dtype=torch.float32, device=dev), torch.empty(v.P, dtype=torch.float32, device=dev),
                          torch.empty(v.P, dtype=torch.int32, device=dev), torch.empty(1, v.H, v.W, dtype=torch.int32, device=dev)]
-                outs += v.vis
+                made.update(zip(Visibility._fields, v.vis))
+            for name, j in layout.outputs[i].items():
+                outs[j] = made[name]
             saved += list(v.saved()[:-1]) + ([] if stacked else [v.color])
             ctx.mark_non_differentiable(v.radii)
-        if ctx.vspec is not None:        # (mark_non_differentiable keeps its last call's tensors only: all of them in one call)
+        if layout.has_vis:        # (mark_non_differentiable keeps its last call's tensors only: all of them in one call)
             ctx.mark_non_differentiable(*[v.radii for v in views], *[t for v in views if v.vis is not None for t in v.vis])
         if stacked:
-            outs = [colors] + outs
+            outs[layout.stacked_output] = colors
             saved.append(colors)
-        ctx.stacked = bool(stacked)
         ctx.nsaved = len(views[0].saved()) - (1 if stacked else 0)
         ctx.nfeat_saved = 0
-        if ctx.fspec is not None:       # (behind everything the colour path saves: the views' feature tensors, None where a view has none)
+        if layout.has_feat:       # (behind everything the colour path saves: the views' feature tensors, None where a view has none)
             saved += [v.features for v in views]
             ctx.nfeat_saved = V
         ctx.save_for_backward(*saved)
         # which view first received each input tensor OBJECT (shared parameters get one gradient buffer)
-        ctx.first_of = [[next(j for j in range(i + 1) if flat[j * n + k] is flat[i * n + k]) for k in range(n)] for i in range(V)]
+        ctx.first_of = [[next(j for j in range(i + 1) if groups[j][k] is groups[i][k]) for k in range(NIN)] for i in range(V)]
         # (antialiasing: K8 reads the raw opacities through the views' `opacities` pointers -- those tensors live as long as the node)
-        ctx.aa_opacities = [v.opacities for v in views] if ctx.aa else None
+        ctx.aa_opacities = [v.opacities for v in views] if layout.aa else None
         for v in views:
             v.drop_inputs()
             v.features = v.feat = v.alpha = None
@@ -681,7 +760,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         ctx.plan = None
         if any(ctx.needs_input_grad):
             # the GPU is busy with K1..K6 of the views right now: prepare the backward call in its shadow
-            ctx.plan = _RasterizeGaussiansBatch._plan_backward(views, saved, ctx.nsaved, arr, ctx.first_of, list(range(V)), dev, flat if _n.GRAD_SINK else None)
+            ctx.plan = _RasterizeGaussiansBatch._plan_backward(views, saved, ctx.nsaved, arr, ctx.first_of, list(range(V)), dev, groups if _n.GRAD_SINK else None)
         if not pending.value and _FAITH is None:
             SPEC_STATS["wait"] += 1
         if pending.value:
@@ -699,12 +778,12 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                     v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
                 if ctx.plan is not None:
                     _n.grad_release(ctx.plan["sinks"])
-                    ctx.plan = _RasterizeGaussiansBatch._plan_backward(views, saved, ctx.nsaved, arr, ctx.first_of, list(range(V)), dev, flat if _n.GRAD_SINK else None)
+                    ctx.plan = _RasterizeGaussiansBatch._plan_backward(views, saved, ctx.nsaved, arr, ctx.first_of, list(range(V)), dev, groups if _n.GRAD_SINK else None)
             elif ctx.plan is not None:
                 for a, i in enumerate(ctx.plan["active"]):
                     ctx.plan["sub"][a].num_rendered = arr[i].num_rendered
                     ctx.plan["sub"][a].busy_tiles = arr[i].busy_tiles
-        if ctx.vspec is not None:
+        if layout.has_vis:
             _RasterizeGaussiansBatch._visibility(views, arr, dev, main)
         if _KEEP_INFO and _FAITH is None and len({(v.W, v.H) for v in views}) == 1 and all(_n_IMAGE in c for c in chunks):
             off = int(_n.lib.csplat_image_info_offset(views[0].W, views[0].H))
@@ -740,7 +819,6 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         compositing kernels run, so that backward() is left with pointer patching and one library call.
         inputs: the call's input tensors -- one with a registered gradient SINK (csplat.native.GRAD_SINK: a view-parallel step's flat
         buffer) gets its gradient written there by K8 and handed to autograd as a fresh view of the sink."""
-        n = _RasterizeGaussiansBatch.NIN
         plan, owner, total = [], {}, 0
         sink_of = {}        # (view, slot) -> a fresh view of the input's gradient sink
         used_sinks = []
@@ -750,46 +828,44 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             off = total
             total += (int(numel) + 63) & ~63          # 256-byte granules
             return off
-        # per-view gradients of means3D (slot 0) / rotations (slot 6) that belong to DISTINCT input tensors of equal size -- the rows of
-        # one [T, P, .] tensor upstream (csplat.gaussians.UnbindViews) -- are laid out back to back, so that their stack is a view
+        # per-view gradients of means3D / rotations that belong to DISTINCT input tensors of equal size -- the rows of one [T, P, .]
+        # tensor upstream (csplat.gaussians.UnbindViews) -- are laid out back to back, so that their stack is a view
         pre = {}
-        for slot, width in ((0, 3), (6, 4)):
+        for row in (_IN["means3D"], _IN["rotations"]):
+            slot = row.slot
             if len(active) > 1 and all(first_of[i][slot] == i for i in active) and len({views[i].P for i in active}) == 1 and \
-                    all(saved[i * k + (0 if slot == 0 else 4)] is not None for i in active):
-                blk = reserve(len(active) * width * views[active[0]].P)
+                    all(not row.optional or saved[i * k + row.saved] is not None for i in active):
+                size = _prod(row.shape(views[active[0]].P, 0))
+                blk = reserve(len(active) * size)
                 for a, i in enumerate(active):
-                    pre[(i, slot)] = blk + a * width * views[i].P
+                    pre[(i, slot)] = blk + a * size
         for i in active:
-            v = views[i]
-            means3D, sh, colors_precomp, scales, rotations, cov3Ds, radii = saved[i * k:i * k + 7]
-            P, M = v.P, v.M
+            P, M = views[i].P, views[i].M
             acc_buf, zeroed = _acc_scratch(dev, P, len(plan))
-            ent = {"scratch": acc_buf if zeroed else reserve(int(_n.lib.csplat_backward_scratch_bytes(P, v.layout_rendered)) // 4 + 64),
-                   "dL_dmean2D": reserve(3 * P), "dL_dconic": reserve(4 * P), "mask": SCRATCH_ZEROED if zeroed else 0, "ret": {}}
-            ent["ret"][1] = (ent["dL_dmean2D"], (P, 3))
-            # dL_dconic is never handed back; dL_dcolor / dL_dcov3D only to a precomputed colour / covariance input: without those the
-            # batched K8 may leave the three unwritten (they keep their place in the allocation: address space, no traffic)
-            if colors_precomp is None and cov3Ds is None:
-                ent["mask"] |= K8_OUTPUTS_UNREAD
-            shapes = {0: (P, 3), 2: (P, M, 3) if sh is not None else None, 3: (P, 3), 4: (P, 1),
-                      5: (P, 3) if scales is not None else None, 6: (P, 4) if rotations is not None else None, 7: (P, 6)}
-            present = {0: True, 2: sh is not None, 3: colors_precomp is not None, 4: True, 5: scales is not None,
-                       6: rotations is not None, 7: cov3Ds is not None}
-            for slot, (field, bit) in _RasterizeGaussiansBatch._GRAD.items():
-                if shapes[slot] is None:
+            ent = {"scratch": acc_buf if zeroed else reserve(int(_n.lib.csplat_backward_scratch_bytes(P, views[i].layout_rendered)) // 4 + 64),
+                   "mask": SCRATCH_ZEROED if zeroed else 0, "ret": {}}
+            for row in _K7_OUT:
+                ent[row.field] = reserve(_prod(row.shape(P, M)))
+                ent["ret"][row.slot] = (ent[row.field], row.shape(P, M))
+            ent["dL_dconic"] = reserve(4 * P)
+            unread = True
+            for row in _K8_OUT:
+                slot, field = row.slot, row.field
+                present = not row.optional or saved[i * k + row.saved] is not None
+                if not present and not row.temp:
                     ent[field] = None
                     continue
+                unread = unread and not (row.temp and present)
                 j = first_of[i][slot]
-                if present[slot] and j != i and j in active and (slot != 2 or M == 16):
+                if present and j != i and j in active and (row.name != "sh" or M == 16):
                     ent[field] = owner[(j, slot)]
-                    ent["mask"] |= bit
+                    ent["mask"] |= row.acc
                 else:
-                    numel = 1
-                    for d in shapes[slot]:
-                        numel *= d
-                    sk = _n.grad_sink(inputs[i * n + slot]) if (inputs is not None and present[slot] and (i, slot) not in pre and
-                                                                inputs[i * n + slot] is not None) else None
-                    sv = _n.grad_out(sk, inputs[i * n + slot].shape, dev) if sk is not None else None
+                    shape = row.shape(P, M)
+                    numel = _prod(shape)
+                    t = inputs[i][slot] if inputs is not None and present and (i, slot) not in pre else None
+                    sk = _n.grad_sink(t) if t is not None else None
+                    sv = _n.grad_out(sk, t.shape, dev) if sk is not None else None
                     if sv is not None and sv.numel() == numel and sv.data_ptr() % 16 == 0:
                         sink_of[(i, slot)] = sv
                         # (only a sink this plan really CLAIMED is given back when the plan is rebuilt: grad_out() hands out fresh memory
@@ -797,85 +873,63 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                         if sv.data_ptr() == sk[0].data_ptr() + 4 * int(sk[1]):
                             used_sinks.append(sk)
                         ent[field] = owner[(i, slot)] = ("sink", i, slot)
-                        ent["ret"][slot] = (ent[field], shapes[slot])
+                        ent["ret"][slot] = (ent[field], shape)
                         continue
                     ent[field] = owner[(i, slot)] = pre[(i, slot)] if (i, slot) in pre else reserve(numel)
-                    if present[slot]:
-                        ent["ret"][slot] = (ent[field], shapes[slot])
+                    if present:
+                        ent["ret"][slot] = (ent[field], shape)
+            # dL_dconic is never handed back; dL_dcolor / dL_dcov3D (the `temp` rows) only to a precomputed colour / covariance input:
+            # without those the batched K8 may leave the three unwritten (they keep their place in the allocation: address space, no traffic)
+            if unread:
+                ent["mask"] |= K8_OUTPUTS_UNREAD
             plan.append(ent)
         big = torch.empty(max(total, 64), dtype=torch.float32, device=dev)
         base = big.data_ptr()
         sub = (_n.CsplatView * len(active))()
-        out = [None] * (len(views) * n)
+        out = [None] * len(views)       # per active view its NIN gradients, in slot order
         for a, i in enumerate(active):
             ent = plan[a]
             C.memmove(C.byref(sub[a]), C.byref(arr[i]), C.sizeof(_n.CsplatView))
             w = sub[a]
             w.scratch = ent["scratch"].data_ptr() if torch.is_tensor(ent["scratch"]) else base + 4 * ent["scratch"]
             w.accmask = ent["mask"]
-            for field in ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D", "dL_dsh",
-                          "dL_dscale", "dL_drot"):
+            for field in _GRAD_FIELDS:
                 off = ent.get(field)
                 if isinstance(off, tuple):
                     setattr(w, field, sink_of[off[1:]].data_ptr())
                 else:
                     setattr(w, field, None if off is None else base + 4 * off)
+            out[i] = [None] * NIN
             for slot, (off, shape) in ent["ret"].items():
-                if isinstance(off, tuple):
-                    out[i * n + slot] = sink_of[off[1:]]
-                    continue
-                numel = 1
-                for d in shape:
-                    numel *= d
-                out[i * n + slot] = big[off:off + numel].view(shape)
+                out[i][slot] = sink_of[off[1:]] if isinstance(off, tuple) else big[off:off + _prod(shape)].view(shape)
         return {"active": list(active), "big": big, "sub": sub, "out": out, "sinks": used_sinks,
                 "acc": [e["scratch"] for e in plan if torch.is_tensor(e["scratch"])]}      # (kept alive with the plan)
 
     @staticmethod
     def backward(ctx, *grads):
-        views, k, arr = ctx.views, ctx.nsaved, ctx.arr
-        V = len(views)
+        layout, views, k, arr = ctx.layout, ctx.views, ctx.nsaved, ctx.arr
+        V = layout.V
         dev = views[0].dev
         main = torch.cuda.current_stream(dev)
-        n = _RasterizeGaussiansBatch.NIN
-        cam_need = [tuple(ctx.needs_input_grad[2 + V * n + 4 * i:2 + V * n + 4 * i + 4]) for i in range(V)] if ctx.cam else [()] * V
-        tail = (None,) * (4 * V) if ctx.cam else ()
-        fspec = ctx.fspec or [(0, False)] * V
-        ftail = (None,) * (V + 1) if ctx.fspec is not None else ()      # the views' feature tensors and the _FeatSpec
-        vtail = (None,) if ctx.vspec is not None else ()                 # the _VisSpec
-        atail = (None,) if ctx.aa else ()                                # the _ANTIALIAS marker
-        ftail = ftail + vtail + atail
-        base = [(2 if ctx.stacked else 3) + (1 if f else 0) + (1 if a else 0) for f, a in fspec]    # outputs per view before visibility
-        per = [b + (NVIS if ctx.vspec is not None and ctx.vspec[i] else 0) for i, b in enumerate(base)]
-        first = [sum(per[:i]) + (1 if ctx.stacked else 0) for i in range(V)]                          # a view's first output
-        if ctx.stacked:
-            gcol = [None] * V if grads[0] is None else [grads[0][i] for i in range(V)]
-            gdep = [grads[first[i] + 1] for i in range(V)]
+        need = ctx.needs_input_grad[1:]
+        cam_need = [tuple(layout.cam_group(need, i)) for i in range(V)]
+        fspec = layout.feat
+        if layout.stacked:
+            gstack = grads[layout.stacked_output]
+            gcol = [None] * V if gstack is None else [gstack[i] for i in range(V)]
         else:
-            gcol = [grads[first[i]] for i in range(V)]
-            gdep = [grads[first[i] + 2] for i in range(V)]
-        gfeat = [grads[first[i] + base[i] - (2 if fspec[i][1] else 1)] if fspec[i][0] else None for i in range(V)]
-        galpha = [grads[first[i] + base[i] - 1] if fspec[i][1] else None for i in range(V)]
-        if any(g is not None for g in gdep) and ctx.on_faith:
-            raise RuntimeError("diff_gaussian_rasterization: a depth gradient reached a forward launched on faith (a captured / replayed step); "
-                               "those steps take no depth loss -- render the depth term in an eager step")
+            gcol = [layout.output(grads, i, "color") for i in range(V)]
+        gdep, gfeat, galpha = ([layout.output(grads, i, name) for i in range(V)] for name in ("depth", "feat", "alpha"))
         active = [i for i in range(V) if gcol[i] is not None or gdep[i] is not None or gfeat[i] is not None or galpha[i] is not None]
         if not active:
-            return (None, None) + (None,) * (V * _RasterizeGaussiansBatch.NIN) + tail + ftail
+            return layout.grads()
         want_feat = any(gfeat[i] is not None or galpha[i] is not None for i in active)
-        if want_feat and ctx.on_faith:
-            raise RuntimeError("diff_gaussian_rasterization: a feature / alpha gradient reached a forward launched on faith (a captured / "
-                               "replayed step); render feature and alpha images in an eager step")
-        if want_feat and _K8_DEFER is not None:
-            raise RuntimeError("diff_gaussian_rasterization: a feature / alpha gradient reached a backward inside deferred_k8(); the sliced "
-                               "per-Gaussian backward takes no feature or alpha gradient")
         want_cam = any(any(cam_need[i]) for i in active)
-        if want_cam and ctx.on_faith:
-            raise RuntimeError("diff_gaussian_rasterization: a camera / background gradient reached a forward launched on faith (a captured / "
-                               "replayed step); those steps take no camera gradient -- refine the camera in an eager step")
-        if want_cam and _K8_DEFER is not None:
-            raise RuntimeError("diff_gaussian_rasterization: a camera / background gradient reached a backward inside deferred_k8(); the sliced "
-                               "per-Gaussian backward takes no camera gradient")
+        arrived = {"depth": any(gdep[i] is not None for i in active), "feat": want_feat, "cam": want_cam}
+        where = {"faith": ctx.on_faith, "deferred_k8": _K8_DEFER is not None}
+        for what, place, message in _REFUSALS:
+            if arrived[what] and where[place]:
+                raise RuntimeError(message)
         plan, ctx.plan = ctx.plan, None                         # (one use: the buffers are handed to autograd)
         if plan is not None and plan["acc"] and (int(_n.lib.csplat_debug_flags_query()) & 256):
             _n.grad_release(plan["sinks"])                      # (the bit-reproducible mode was switched on after the forward: its scratch
@@ -896,12 +950,11 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 for f, g in zip(_CAM_FIELDS, cam_out[i]):
                     setattr(plan["sub"][a], f, _n.ptr(g))
                 gs += [g for g in cam_out[i] if g is not None]
-        ftail_out = ftail
+        fout = None
         if want_feat:
             # the feature path (csplat_view.dL_dfeatures / dL_dalpha): one dL_dfeat_in buffer per feature tensor OBJECT that wants a
             # gradient, shared by the views it was passed to (the library adds their sums in view order)
             fsaved = ctx.saved_tensors[len(ctx.saved_tensors) - ctx.nfeat_saved:]
-            fin = ctx.needs_input_grad[2 + V * n + (4 * V if ctx.cam else 0):]
             fout, owner = [None] * V, {}
             for a, i in enumerate(active):
                 w, F = plan["sub"][a], fspec[i][0]
@@ -910,14 +963,13 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 w.features, w.n_features = _n.ptr(fsaved[i]), F
                 w.dL_dfeatures, w.dL_dalpha = _n.ptr(gf), _n.ptr(ga)
                 buf = None
-                if F and fin[i]:
+                if F and layout.features(need, i):
                     key = ctx.feat_first[i]
                     if key not in owner:
                         owner[key] = fout[i] = torch.empty(views[i].P, F, dtype=torch.float32, device=dev)
                     buf = owner[key]
                 w.dL_dfeat_in = _n.ptr(buf)
                 gs += [gf, ga]
-            ftail_out = tuple(fout) + (None,) + vtail + atail
         if want_feat or want_cam or any(gdep[i] is not None for i in active):
             # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout (the camera path: of the
             # camera layout; the feature path: of the feature layout), allocated here (never on the colour-only path) and cleared by the
@@ -939,16 +991,15 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             _n.check(rc, "csplat_backward_views_parts")
             # (kept alive: the MEMORY the K8 slices write -- never the gradient tensor objects themselves: AccumulateGrad adopts a
             #  gradient only when nobody else holds it, and would otherwise snapshot the still unwritten buffer into a copy)
-            outs, plan["out"] = tuple(plan["out"]), None
+            outs, plan["out"] = plan["out"], None
             _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, ctx.saved_tensors,
                                                                                           ctx.aa_opacities)))
-            return (None, None) + outs + tail + ftail
+            return layout.grads(outs)
         with _n.on_device(dev):
             rc = _n.lib.csplat_backward_views(len(active), C.cast(plan["sub"], C.c_void_p), main.cuda_stream)
         _n.check(rc, "csplat_backward_views")
-        if ctx.cam:
-            tail = sum((_cam_returns(cam_out.get(i, (None,) * 4), _cam_tensors(views[i].rs)) for i in range(V)), ())
-        return (None, None) + tuple(plan["out"]) + tail + ftail_out
+        cam = [_cam_returns(cam_out[i], _cam_tensors(views[i].rs)) if i in cam_out else None for i in range(V)]
+        return layout.grads(plan["out"], cam, fout)
 
 
 def rasterize_views(settings, inputs, stacked=False):
@@ -963,7 +1014,7 @@ def rasterize_views(settings, inputs, stacked=False):
     NamedTuple; GaussianRasterizer.forward); the views of a call may differ in it.  Every output and gradient -- features, alpha,
     visibility, the depth, camera and background gradients, antialiasing -- is taken for up to 64 views per call; the library runs a
     call of more than 8 views in groups of at most 8 (include/csplat.h, "More than 8 views"), adding every group into the same gradients."""
-    flat, fspec, feats = [], [], []
+    groups, fspec, feats = [], [], []
     vis = [_check_visibility_flag(kw.get("return_visibility", False)) for kw in inputs]
     aa = {bool(kw.get("antialiasing", False)) for kw in inputs}
     if len(aa) > 1:
@@ -979,28 +1030,9 @@ def rasterize_views(settings, inputs, stacked=False):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((sc is None or ro is None) and cov is None) or ((sc is not None or ro is not None) and cov is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        flat += [kw["means3D"], kw["means2D"], shs, cp, kw["opacities"], sc, ro, cov]
-    if any(_cam_group(rs) for rs in settings):      # (a settings tensor wants a gradient: every view's camera group follows)
-        for rs in settings:
-            flat += list(_cam_tensors(rs))
-    extra = any(f or a for f, a in fspec)
-    if extra:
-        if len({f for f, _a in fspec}) > 1:
-            raise ValueError(f"rasterize_views: every view must have the same number of feature channels, got {[f for f, _a in fspec]}")
-        _feature_mode_check()
-        flat += feats + [_FeatSpec(fspec)]
-    if any(vis):
-        _visibility_mode_check()
-        flat.append(_VisSpec(vis))
-    if True in aa:
-        flat.append(_ANTIALIAS)
-    res = _RasterizeGaussiansBatch.apply(tuple(settings), bool(stacked), *flat)
-    per = [(2 if stacked else 3) + (1 if f else 0) + (1 if a else 0) + (NVIS if vv else 0) for (f, a), vv in zip(fspec, vis)]
-    at = [sum(per[:i]) + (1 if stacked else 0) for i in range(len(settings))]
-    if stacked:
-        colors = res[0]
-        return colors, [_group_visibility((colors[i],) + tuple(res[at[i]:at[i] + per[i]]), vis[i]) for i in range(len(settings))]
-    return [_group_visibility(res[at[i]:at[i] + per[i]], vis[i]) for i in range(len(settings))]
+        groups.append((kw["means3D"], kw["means2D"], shs, cp, kw["opacities"], sc, ro, cov))
+    layout = _call_layout(settings, stacked, True in aa, fspec, vis)
+    return layout.split(_RasterizeGaussiansBatch.apply(layout, *layout.pack(groups, feats)))
 
 
 _n_GEOM, _n_BINNING, _n_IMAGE = 0, 1, 2

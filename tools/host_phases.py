@@ -37,7 +37,8 @@ for n in ("forward", "backward", "_plan_backward"):
         return staticmethod(timed)
     setattr(B, n, mk(f, n))
 sys.argv = ["bench.py", "--steps", "40", "--warmup", "10", "--no-cpu-baseline", "--no-train-step"]
-exec(open(os.path.join(ROOT, "bench.py")).read())
+__file__ = os.path.join(ROOT, "bench.py")      # (bench.py finds the repository through its own __file__)
+exec(open(__file__).read())
 for k, v in acc.items():
     v = v[len(v) // 2:]
     print("%-28s calls/step %.1f  mean %.1f us" % (k, 1.0, 1e6 * sum(v) / len(v)))
