@@ -17,7 +17,10 @@ class GraphCSR:
     def __init__(self, edge_index: torch.Tensor, num_nodes: int):
         _n.require_cuda(edge_index)
         assert edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.shape[0] == 2
-        self.ei = edge_index.contiguous()
+        # a copy of its own: the CSR orderings below describe THESE edges, also after the caller edits edge_index in place (a backward
+        # that runs after the edit reads ei next to rowptr / perm), and a cached CSR must not keep the tensor it is keyed on alive
+        ei = edge_index.detach()
+        self.ei = ei.clone() if ei.is_contiguous() else ei.contiguous()
         self.N, self.E = int(num_nodes), int(edge_index.shape[1])
         dev = edge_index.device
         self.rowptr, self.perm = {}, {}
@@ -724,6 +727,7 @@ class SplitKLinear(torch.autograd.Function):
     M.  Other shapes / dtypes: plain torch, with the weight gradient as a chunked batched GEMM."""
 
     CHUNK = 3072
+    MIN_ROWS = 512         # linear_rows: 128 -> 128 layers whose weight wants a gradient take this node from here on
     BIG_ROWS = 16384       # (measured again in round 4 with the node level on csplat_linear128 too -- BIG_ROWS = 64: train step 24.3 against 22.4 ms)
 
     @staticmethod
@@ -945,7 +949,7 @@ def linear_rows(x, lin_weight, lin_bias, min_rows: int = 16384, relu: bool = Fal
     for 128 -> 128 fp32 GPU layers from 512 rows up (the library's weight-gradient GEMM reduces the rows inside 16 workgroups)."""
     rows = x.shape[0]
     if torch.is_grad_enabled() and (lin_weight.requires_grad or x.requires_grad) and \
-            (rows >= min_rows or (rows >= 512 and lin_weight.requires_grad and SplitKLinear._fast(x, lin_weight))):
+            (rows >= min_rows or (rows >= SplitKLinear.MIN_ROWS and lin_weight.requires_grad and SplitKLinear._fast(x, lin_weight))):
         return SplitKLinear.apply(x, lin_weight, lin_bias, relu)
     y = torch.nn.functional.linear(x, lin_weight, lin_bias)
     return y.relu() if relu else y
