@@ -66,6 +66,12 @@ EXPORTS = {
     "csplat_knn_temp_bytes": (_sz, [_i, _i]),
     "csplat_knn_ws": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "csplat_fps": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "csplat_knn_query": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "csplat_knn_query_temp_bytes": (_sz, [_i, _i, _i]),
+    "csplat_knn_query_ws": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_chamfer_fwd": (_i, [_vp, _i, _vp, _f, _vp]),
+    "csplat_chamfer_bwd_temp_bytes": (_sz, [_i, _i]),
+    "csplat_chamfer_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "csplat_mesh_rest_bytes": (_sz, [_i]),
     "csplat_mesh_rest": (_i, [_vp, _i, _vp, _vp, _vp]),
     "csplat_mesh_transform_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -879,6 +879,34 @@ def _geometry_targets(cams, lam_d, lam_s):
             [field(c, "silhouette", "lambda_silhouette > 0") for c in cams] if lam_s > 0.0 else None)
 
 
+def _chamfer_weight(opt):
+    """(lambda_chamfer, squared cap or None) of an options namespace; absent = 0.  The term is on when the weight is > 0."""
+    lam = float(getattr(opt, "lambda_chamfer", 0.0) or 0.0)
+    if not lam >= 0.0:
+        raise ValueError(f"train_step: lambda_chamfer is >= 0, got {lam}")
+    cap = getattr(opt, "chamfer_max_dist", None)
+    if cap is not None:
+        cap = float(cap)
+        if not cap >= 0.0:
+            raise ValueError(f"train_step: chamfer_max_dist is a distance >= 0 (or None), got {cap}")
+        cap = cap * cap
+    return lam, cap
+
+
+def _chamfer_targets(cams):
+    """the cameras' observed point clouds (`points`, float32 [n,3], n >= 1, world coordinates); ValueError for a camera that lacks the
+    field or carries another shape or dtype -- from the host-side attributes, before anything is launched"""
+    out = []
+    for cam in cams:
+        t = getattr(cam, "points", None)
+        if not torch.is_tensor(t):
+            raise ValueError(f"train_step: lambda_chamfer > 0 needs every camera's `points` (a float32 [n,3] tensor), got {type(t).__name__}")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] == 0:
+            raise ValueError(f"train_step: camera.points is {t.dtype} {tuple(t.shape)}, expected float32 [n,3] with n >= 1")
+        out.append(t)
+    return out
+
+
 def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimizer, pipe=DEFAULT_PIPE, opt=DEFAULT_OPT,
                background=None, static=False, view_parallel=False, batched_views=True, densify_opt=None, time_allreduce=False, captured=False,
                _cap=None):
@@ -905,7 +933,15 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
     "depth_loss" / "silhouette_loss" (detached device scalars) for the terms that are on.  ValueError before the simulator runs: a camera
     without the field of a term that is on, or with another shape or dtype; cameras of different sizes.  NotImplementedError, also before
     anything runs: a view-parallel step (csplat.dist.is_dist()) and batched_views=False -- the terms are computed on the batched path only.
-    captured=True runs such a step eagerly.  With both weights 0 or absent the step is exactly the one above."""
+    captured=True runs such a step eagerly.  With both weights 0 or absent the step is exactly the one above.
+
+    Point-cloud supervision: `opt.lambda_chamfer` (absent = 0; on when > 0) adds lambda_chamfer * the mean over the step's cameras of
+    csplat.pointcloud.chamfer_distance(camera.points, the camera's deformed Gaussian centres, two_sided=False, max_sq_dist=
+    opt.chamfer_max_dist ** 2 when that option is set) -- `camera.points`: the observed cloud, float32 [n,3] in world coordinates, n
+    free per camera.  stats then holds "chamfer_loss" (the detached mean, a device scalar).  The rules are the geometry terms':
+    ValueError before the simulator runs for a camera without `points` or with another shape or dtype; NotImplementedError before
+    anything runs for a view-parallel step and for batched_views=False; captured=True runs such a step eagerly.  With the weight 0 or
+    absent nothing is added to the step."""
     if captured and _cap is None:     # the step as a replayed hipGraph (CapturedStep below); falls back to this function when it must
         cs = gaussians.__dict__.get("_captured_step")
         if cs is None or not cs.matches(simulator, meshnet_optimizer, pipe, opt, background):
@@ -922,6 +958,14 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
         if not batched_views:
             raise NotImplementedError("train_step: the depth and silhouette terms need batched_views=True")
         geom_z, geom_s = _geometry_targets(all_cams, lam_depth, lam_sil)
+    lam_chamfer, chamfer_cap = _chamfer_weight(opt)
+    chamfer_pts = None
+    if lam_chamfer > 0.0 and all_cams:
+        if view_parallel and cd.is_dist():
+            raise NotImplementedError("train_step: the Chamfer term is not part of the view-parallel step")
+        if not batched_views:
+            raise NotImplementedError("train_step: the Chamfer term needs batched_views=True")
+        chamfer_pts = _chamfer_targets(all_cams)
     if iteration % 1000 == 0 and _cap is None:
         gaussians.oneupSHdegree()
     _DEFERRED.clear()                 # (a launch queued by a step that raised before issuing it)
@@ -994,6 +1038,15 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
             geom_stats["depth_loss"] = gl_d.detach()
         if lam_sil > 0.0:
             geom_stats["silhouette_loss"] = gl_s.detach()
+    if chamfer_pts is not None:
+        # observed cloud -> deformed Gaussian centres, per camera (the clouds differ in size); the mean rides into the image loss with the
+        # regularisers
+        from .pointcloud import chamfer_distance
+        terms = [chamfer_distance(t.to(pkg.means3D_deform.device), pkg.means3D_deform, two_sided=False, max_sq_dist=chamfer_cap)
+                 for t, pkg in zip(chamfer_pts, pkgs)]
+        chamfer_mean = torch.stack(terms).mean()
+        reg = reg + lam_chamfer * chamfer_mean
+        geom_stats["chamfer_loss"] = chamfer_mean.detach()
     if cams:
         image_tensor = stacked if stacked is not None else torch.cat(images, 0)
         gt_image_tensor = _gt_stack(cams, image_tensor.device) if _cap is None else _cap["gt"]
@@ -1083,7 +1136,7 @@ class CapturedStep:
     One graph per step SHAPE: (number of cameras, image size, field of view, number of Gaussians, active SH degree, parameter storage,
     pipe.antialiasing).
     Falls back to the eager train_step for what it does not cover: masks, a static stage, view-parallel runs, densification steps, the
-    depth and silhouette terms (opt.lambda_depth / opt.lambda_silhouette > 0)."""
+    depth and silhouette terms (opt.lambda_depth / opt.lambda_silhouette > 0), the Chamfer term (opt.lambda_chamfer > 0)."""
 
     MARGIN = 8          # capacities = counts + counts / MARGIN (+ a constant)
 
@@ -1107,6 +1160,7 @@ class CapturedStep:
         from .optim import GroupedAdam
         return (len(cams) >= 2 and len(cams) <= 8 and all(getattr(c, "mask", None) is None for c in cams) and
                 max(_geometry_weights(self.opt)) == 0.0 and       # (a depth / silhouette term: the rasterizer refuses its gradients on a forward launched on faith)
+                _chamfer_weight(self.opt)[0] == 0.0 and           # (the Chamfer term: the observed clouds' sizes are per camera, not part of a step's shape)
                 len({(int(c.image_height), int(c.image_width), float(c.FoVx), float(c.FoVy)) for c in cams}) == 1 and
                 self.g.mesh.pos.is_cuda and isinstance(self.g.optimizer, GroupedAdam) and isinstance(self.mopt, GroupedAdam) and
                 not (int(_n.lib.csplat_debug_flags_query()) & (2 | 128 | 512)) and      # (global sort, per-view launches; the bit-reproducible K7, bit 8, is served by the batched path since round 6)

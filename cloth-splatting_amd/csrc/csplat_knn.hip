@@ -527,3 +527,356 @@ extern "C" int csplat_fps(void *stream, int N, int S, const float *xyz, int star
     LAUNCH_CHECK();
     return 0;
 }
+
+// ================================================================================================================================
+// Two-cloud search (csplat_knn_query / csplat_knn_query_ws) and the one-sided Chamfer distance on top of it (csplat_chamfer_fwd /
+// csplat_chamfer_bwd).  Nothing above is touched: KBest, knn_offer / knn_offer4 and the CAP dispatch are used as they are, the
+// pruned form orders the POINTS with k_bbox_partial / k_morton / the radix sort / k_knn_boxes in the workspace layout of
+// csplat_dist2_ws and appends its own query-side arrays behind it.
+namespace {
+// one query per lane, slabs of `points` through LDS as in k_knn_brute; nothing is excluded.  N = 0: the list stays empty and
+// every slot is stored as (+inf, -1) -- `points` is never read.
+template <int CAP>
+__global__ __launch_bounds__(KNN_THREADS) void k_knn_query_brute(int Q, int N, int K, const float *__restrict__ qry, const float *__restrict__ pts,
+                                                                 float *__restrict__ out_d2, int32_t *__restrict__ out_idx) {
+#pragma clang fp contract(off)
+    __shared__ float s_p[KNN_SLAB * 3];
+    const int i = blockIdx.x * KNN_THREADS + threadIdx.x;
+    const bool live = i < Q;
+    const float x = live ? qry[3 * (size_t)i] : 0.f, y = live ? qry[3 * (size_t)i + 1] : 0.f, z = live ? qry[3 * (size_t)i + 2] : 0.f;
+    KBest<CAP> b;
+    b.init(live ? K : 0);
+    for (int base = 0; base < N; base += KNN_SLAB) {
+        const int cnt = min(KNN_SLAB, N - base);
+        __syncthreads();
+        for (int k = threadIdx.x; k < cnt * 3; k += KNN_THREADS) s_p[k] = pts[(size_t)base * 3 + k];
+        __syncthreads();
+        int j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+            float d[4];
+            int ci[4];
+            const bool me[4] = {false, false, false, false};
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const float dx = s_p[3 * (j + u)] - x, dy = s_p[3 * (j + u) + 1] - y, dz = s_p[3 * (j + u) + 2] - z;
+                d[u] = dx * dx + dy * dy + dz * dz;
+                ci[u] = base + j + u;
+            }
+            knn_offer4(b, d, ci, me);
+        }
+        for (; j < cnt; j++) {
+            const float dx = s_p[3 * j] - x, dy = s_p[3 * j + 1] - y, dz = s_p[3 * j + 2] - z;
+            knn_offer(b, dx * dx + dy * dy + dz * dz, base + j, false);
+        }
+    }
+    if (live) b.store(K, (size_t)i, out_d2, out_idx);
+}
+
+// the queries are ordered by the upper 31 bits of their 63-bit code (10 levels of the octree and one bit more): four passes of the
+// radix sort instead of eight, and no coarser a grouping than that for any cloud of fewer than 2^30 queries
+constexpr int KNN_QUERY_CODE_SHIFT = 32, KNN_QUERY_CODE_BITS = 63 - KNN_QUERY_CODE_SHIFT;
+
+// Morton codes of the queries in the POINTS' bounding box (part: the partials of k_bbox_partial over the points); a query outside
+// the box clamps to its faces.  The codes only group nearby queries in one wave -- the search is exact for any order.
+__global__ __launch_bounds__(256) void k_morton_query(int Q, int nparts, const float *__restrict__ qry, const float *__restrict__ part,
+                                                      uint64_t *__restrict__ codes, uint32_t *__restrict__ ids) {
+    __shared__ float s_box[6];
+    if (threadIdx.x < 6) {
+        float v = part[threadIdx.x];
+        for (int b = 1; b < nparts; b++) v = threadIdx.x < 3 ? fminf(v, part[b * 6 + threadIdx.x]) : fmaxf(v, part[b * 6 + threadIdx.x]);
+        s_box[threadIdx.x] = v;
+    }
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q) return;
+    uint32_t q[3];
+    for (int a = 0; a < 3; a++) {
+        const float ext = s_box[3 + a] - s_box[a];
+        const float t = ext > 0.f ? (qry[3 * (size_t)i + a] - s_box[a]) / ext : 0.f;
+        q[a] = (uint32_t)fminf(fmaxf(t * 2097151.f, 0.f), 2097151.f);
+    }
+    codes[i] = (spread21(q[0]) | spread21(q[1]) << 1 | spread21(q[2]) << 2) >> KNN_QUERY_CODE_SHIFT;
+    ids[i] = (uint32_t)i;
+}
+
+// pruned form.  Lane i takes the i-th query of the queries' Morton order (qids), so a wave's queries are neighbours in space.
+// The wave seeds its lists from a stretch of the sorted points around the place where its first query's code would be inserted
+// (binary search in the sorted codes; K + KNN_QUERY_SEED positions either side: at least min(K, N) points), then scans the
+// boxes that are not farther than a lane's current K-th best, leaving that stretch out.  Rejection is strict as in
+// k_knn_search_k.  The result is stored at the caller's query index.
+// A wave scans the UNION of the boxes its queries need, one candidate after the other, so its time is that union's size whatever
+// the number of lanes at work: with few queries a wave takes only `lanes` of them (a power of two, 1 .. 64; the other lanes hold
+// lists that accept nothing) -- smaller unions, and enough waves to fill the machine.  knn_query_lanes() chooses it.
+constexpr int KNN_QUERY_SEED = 32, KNN_QUERY_MIN_WAVES = 4096;
+
+inline int knn_query_lanes(int Q) {
+    int lanes = 64;
+    while (lanes > 1 && Q / lanes < KNN_QUERY_MIN_WAVES) lanes >>= 1;
+    return lanes;
+}
+
+template <int CAP>
+__global__ __launch_bounds__(256) void k_knn_query_search(int Q, int N, int K, int nbox, int lanes, const float *__restrict__ qry,
+                                                          const uint64_t *__restrict__ qcodes, const uint32_t *__restrict__ qids,
+                                                          const uint64_t *__restrict__ pcodes, const float4 *__restrict__ spts,
+                                                          const float *__restrict__ boxes, float *__restrict__ out_d2, int32_t *__restrict__ out_idx) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int w0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4 + (threadIdx.x >> 6)) * lanes);   // the wave's first query
+    if (w0 >= Q) return;                         // a wave without a query (no barrier in this kernel)
+    const int i = w0 + lane;
+    const bool live = lane < lanes && i < Q;
+    const size_t qi = qids[live ? i : Q - 1];
+    const float px = qry[3 * qi], py = qry[3 * qi + 1], pz = qry[3 * qi + 2];
+    KBest<CAP> b;
+    b.init(live ? K : 0);
+    auto scan = [&](int lo, int hi) {
+        int j = lo;                              // wave-uniform addresses: one broadcast load per candidate
+        for (; j + 4 <= hi; j += 4) {
+            float d[4];
+            int ci[4];
+            const bool me[4] = {false, false, false, false};
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const float4 c = spts[j + u];
+                const float dx = c.x - px, dy = c.y - py, dz = c.z - pz;
+                d[u] = dx * dx + dy * dy + dz * dz;
+                ci[u] = (int)__float_as_uint(c.w);
+            }
+            knn_offer4(b, d, ci, me);
+        }
+        for (; j < hi; j++) {
+            const float4 c = spts[j];
+            const float dx = c.x - px, dy = c.y - py, dz = c.z - pz;
+            knn_offer(b, dx * dx + dy * dy + dz * dz, (int)__float_as_uint(c.w), false);
+        }
+    };
+    const uint64_t code0 = qcodes[w0] << KNN_QUERY_CODE_SHIFT;
+    int lo = 0, hi = N;                          // first position whose code is not below code0, in [0, N]
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (pcodes[mid] < code0) lo = mid + 1; else hi = mid;
+    }
+    const int pos = __builtin_amdgcn_readfirstlane(lo);
+    const int wlo = max(0, pos - K - KNN_QUERY_SEED), whi = min(N, pos + K + KNN_QUERY_SEED);   // [wlo, whi)
+    scan(wlo, whi);
+    for (int bi = 0; bi < nbox; bi++) {
+        const float *bx = boxes + 6 * bi;
+        float ex = 0.f, ey = 0.f, ez = 0.f;     // distance from the query to the box, per axis
+        if (px < bx[0] || px > bx[3]) ex = fminf(fabsf(px - bx[0]), fabsf(px - bx[3]));
+        if (py < bx[1] || py > bx[4]) ey = fminf(fabsf(py - bx[1]), fabsf(py - bx[4]));
+        if (pz < bx[2] || pz > bx[5]) ez = fminf(fabsf(pz - bx[2]), fabsf(pz - bx[5]));
+        const float dist = ex * ex + ey * ey + ez * ez;
+        const bool need = !(dist > b.worst());   // lanes without a query hold -inf and never need a box
+        if (__builtin_amdgcn_ballot_w64(need) == 0ull) continue;
+        const int blo = bi * KNN_BOX, bhi = min(N, blo + KNN_BOX);
+        scan(blo, min(bhi, wlo));
+        scan(max(blo, whi), bhi);
+    }
+    if (live) b.store(K, qi, out_d2, out_idx);
+}
+
+// ---- one direction of the Chamfer distance from a K = 1 result.  w_i = 1 when the cap is off (< 0) or d2[i] <= cap.
+constexpr int CHAMFER_THREADS = 1024, CHAMFER_WAVES = CHAMFER_THREADS / 64;
+
+__device__ __forceinline__ float chamfer_weight(float d2, float cap) { return (cap < 0.f || d2 <= cap) ? 1.f : 0.f; }
+
+// loss[0] = (1/Q) sum_i w_i d2[i]: ONE workgroup, a fixed order (lane t takes i = t, t + 1024, ...; lanes, then waves, join in a
+// fixed tree), accumulated in fp64 so that the only rounding is the last conversion.
+__global__ __launch_bounds__(CHAMFER_THREADS) void k_chamfer_fwd(int Q, const float *__restrict__ d2, float cap, float *__restrict__ loss) {
+    __shared__ double s_w[CHAMFER_WAVES];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < Q; i += CHAMFER_THREADS) {
+        const float d = d2[i];
+        acc += chamfer_weight(d, cap) != 0.f ? (double)d : 0.0;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < CHAMFER_WAVES; w++) t += s_w[w];
+        loss[0] = (float)(t / (double)Q);
+    }
+}
+
+// the term both gradients are made of: t_i = g (2/Q) w_i (q_i - p_idx[i])
+// (an index outside 0 .. N-1 is not a result of csplat_knn_query on a non-empty cloud: its term is zero and nothing is read)
+__device__ __forceinline__ void chamfer_term(int i, int N, float c, float cap, const float *__restrict__ qry, const float *__restrict__ pts,
+                                             const float *__restrict__ d2, const int32_t *__restrict__ idx, float (&t)[3]) {
+#pragma clang fp contract(off)
+    const int j = idx[i];
+    if ((unsigned)j >= (unsigned)N) { t[0] = t[1] = t[2] = 0.f; return; }
+    const float cw = c * chamfer_weight(d2[i], cap);
+    for (int a = 0; a < 3; a++) t[a] = cw * (qry[3 * (size_t)i + a] - pts[3 * (size_t)j + a]);
+}
+
+__global__ __launch_bounds__(256) void k_chamfer_bwd_queries(int Q, int N, const float *__restrict__ qry, const float *__restrict__ pts,
+                                                             const float *__restrict__ d2, const int32_t *__restrict__ idx, float cap,
+                                                             const float *__restrict__ g, float *__restrict__ dq) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q) return;
+    const float c = g[0] * (2.0f / (float)Q);
+    float t[3];
+    chamfer_term(i, N, c, cap, qry, pts, d2, idx, t);
+    for (int a = 0; a < 3; a++) dq[3 * (size_t)i + a] = t[a];
+}
+
+__global__ __launch_bounds__(256) void k_chamfer_keys(int Q, const int32_t *__restrict__ idx, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q) return;
+    keys[i] = (uint64_t)(uint32_t)idx[i];
+    vals[i] = (uint32_t)i;
+}
+
+// keys / vals: (idx, i) sorted by idx, equal idx in ascending i (the sort is stable).  The lane at the first position of a run
+// sums the run's terms in that order and writes the point's row; rows nobody selected keep the zeros they were cleared to.
+__global__ __launch_bounds__(256) void k_chamfer_bwd_points(int Q, int N, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                                            const float *__restrict__ qry, const float *__restrict__ pts, const float *__restrict__ d2,
+                                                            const int32_t *__restrict__ idx, float cap, const float *__restrict__ g,
+                                                            float *__restrict__ dp) {
+#pragma clang fp contract(off)
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= Q) return;
+    const uint64_t j = keys[s];
+    if (s > 0 && keys[s - 1] == j) return;       // not a run start
+    if (j >= (uint64_t)N) return;                // (an index outside the cloud: not a result of csplat_knn_query; nothing is written)
+    const float c = g[0] * (2.0f / (float)Q);
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int r = s; r < Q && keys[r] == j; r++) {
+        float t[3];
+        chamfer_term((int)vals[r], N, c, cap, qry, pts, d2, idx, t);
+        for (int a = 0; a < 3; a++) acc[a] = acc[a] + t[a];
+    }
+    for (int a = 0; a < 3; a++) dp[3 * (size_t)j + a] = -acc[a];
+}
+
+struct KnnQueryWs { size_t codes, ids, codes_o, ids_o, codes_t, ids_t, stab, total; };
+KnnQueryWs knn_query_ws(int Q, int N) {
+    KnnQueryWs w;
+    size_t o = knn_ws(N).total;                  // the points' side: the layout of csplat_dist2_ws, unchanged
+    auto take = [&](size_t b) { const size_t at = o; o += align256(b); return at; };
+    const size_t n = (size_t)(Q > 0 ? Q : 1);
+    w.codes = take(n * 8); w.ids = take(n * 4); w.codes_o = take(n * 8); w.ids_o = take(n * 4);
+    w.codes_t = take(n * 8); w.ids_t = take(n * 4); w.stab = take(csplat_sort_temp_bytes((int64_t)n));
+    w.total = o;
+    return w;
+}
+
+struct ChamferWs { size_t keys, vals, keys_o, vals_o, keys_t, vals_t, stab, total; };
+ChamferWs chamfer_ws(int Q) {
+    ChamferWs w;
+    size_t o = 0;
+    auto take = [&](size_t b) { const size_t at = o; o += align256(b); return at; };
+    const size_t n = (size_t)(Q > 0 ? Q : 1);
+    w.keys = take(n * 8); w.vals = take(n * 4); w.keys_o = take(n * 8); w.vals_o = take(n * 4);
+    w.keys_t = take(n * 8); w.vals_t = take(n * 4); w.stab = take(csplat_sort_temp_bytes((int64_t)n));
+    w.total = o;
+    return w;
+}
+}  // namespace
+
+extern "C" int csplat_knn_query(void *stream, int Q, int N, int K, const float *queries, const float *points, float *out_d2,
+                                int32_t *out_idx) {
+    CSPLAT_REQUIRE(Q >= 0 && N >= 0, "csplat_knn_query: bad Q or N");
+    CSPLAT_REQUIRE(K >= 1 && K <= CSPLAT_KNN_MAX_K, "csplat_knn_query: K outside 1 .. CSPLAT_KNN_MAX_K");
+    if (Q == 0) return 0;
+    CSPLAT_REQUIRE(queries && out_d2 && out_idx && (points || N == 0), "csplat_knn_query: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+#define LAUNCH(CAP) k_knn_query_brute<CAP><<<cdiv(Q, KNN_THREADS), KNN_THREADS, 0, s>>>(Q, N, K, queries, points, out_d2, out_idx)
+    KNN_BY_CAPACITY(K, LAUNCH);
+#undef LAUNCH
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t csplat_knn_query_temp_bytes(int Q, int N, int K) { (void)K; return knn_query_ws(Q, N).total; }
+
+extern "C" int csplat_knn_query_ws(void *stream, int Q, int N, int K, const float *queries, const float *points, float *out_d2,
+                                   int32_t *out_idx, void *temp) {
+    CSPLAT_REQUIRE(Q >= 0 && N >= 0, "csplat_knn_query_ws: bad Q or N");
+    CSPLAT_REQUIRE(K >= 1 && K <= CSPLAT_KNN_MAX_K, "csplat_knn_query_ws: K outside 1 .. CSPLAT_KNN_MAX_K");
+    if (Q == 0) return 0;
+    CSPLAT_REQUIRE(queries && out_d2 && out_idx && (points || N == 0) && (temp || N == 0), "csplat_knn_query_ws: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+    if (N == 0) {                                // nothing to order: the brute-force kernel stores the empty lists
+#define LAUNCH(CAP) k_knn_query_brute<CAP><<<cdiv(Q, KNN_THREADS), KNN_THREADS, 0, s>>>(Q, N, K, queries, points, out_d2, out_idx)
+        KNN_BY_CAPACITY(K, LAUNCH);
+#undef LAUNCH
+        LAUNCH_CHECK();
+        return 0;
+    }
+    const KnnWs w = knn_ws(N);
+    const KnnQueryWs wq = knn_query_ws(Q, N);
+    char *t = (char *)temp;
+    float *part = (float *)(t + w.part);
+    uint64_t *codes = (uint64_t *)(t + w.codes), *codes_o = (uint64_t *)(t + w.codes_o), *codes_t = (uint64_t *)(t + w.codes_t);
+    uint32_t *ids = (uint32_t *)(t + w.ids), *ids_o = (uint32_t *)(t + w.ids_o), *ids_t = (uint32_t *)(t + w.ids_t);
+    float4 *spts = (float4 *)(t + w.spts);
+    float *boxes = (float *)(t + w.boxes);
+    uint64_t *qcodes = (uint64_t *)(t + wq.codes), *qcodes_o = (uint64_t *)(t + wq.codes_o), *qcodes_t = (uint64_t *)(t + wq.codes_t);
+    uint32_t *qids = (uint32_t *)(t + wq.ids), *qids_o = (uint32_t *)(t + wq.ids_o), *qids_t = (uint32_t *)(t + wq.ids_t);
+    const int nparts = N < 256 * 256 ? cdiv(N, 256) : 256, nbox = cdiv(N, KNN_BOX);
+    k_bbox_partial<<<nparts, 256, 0, s>>>(N, points, part);
+    LAUNCH_CHECK();
+    k_morton<<<cdiv(N, 256), 256, 0, s>>>(N, nparts, points, part, codes, ids);
+    LAUNCH_CHECK();
+    if (int rc = csplat_sort_pairs(s, codes, ids, codes_o, ids_o, codes_t, ids_t, N, 63, t + w.stab)) return rc;
+    k_knn_boxes<<<nbox, 256, 0, s>>>(N, points, ids_o, spts, boxes);
+    LAUNCH_CHECK();
+    k_morton_query<<<cdiv(Q, 256), 256, 0, s>>>(Q, nparts, queries, part, qcodes, qids);
+    LAUNCH_CHECK();
+    if (int rc = csplat_sort_pairs(s, qcodes, qids, qcodes_o, qids_o, qcodes_t, qids_t, Q, KNN_QUERY_CODE_BITS, t + wq.stab)) return rc;
+    const int lanes = knn_query_lanes(Q);
+#define LAUNCH(CAP) k_knn_query_search<CAP><<<cdiv(cdiv(Q, lanes), 4), 256, 0, s>>>(Q, N, K, nbox, lanes, queries, qcodes_o, qids_o, codes_o, spts, boxes, out_d2, out_idx)
+    KNN_BY_CAPACITY(K, LAUNCH);
+#undef LAUNCH
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int csplat_chamfer_fwd(void *stream, int Q, const float *d2, float max_sq_dist, float *loss) {
+    CSPLAT_REQUIRE(Q >= 1, "csplat_chamfer_fwd: Q must be >= 1 (the loss divides by it)");
+    CSPLAT_REQUIRE(d2 && loss, "csplat_chamfer_fwd: NULL argument");
+    CSPLAT_REQUIRE(!(max_sq_dist != max_sq_dist), "csplat_chamfer_fwd: max_sq_dist is NaN");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+    k_chamfer_fwd<<<1, CHAMFER_THREADS, 0, s>>>(Q, d2, max_sq_dist, loss);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t csplat_chamfer_bwd_temp_bytes(int Q, int N) { (void)N; return chamfer_ws(Q).total; }
+
+extern "C" int csplat_chamfer_bwd(void *stream, int Q, int N, const float *queries, const float *points, const float *d2,
+                                  const int32_t *idx, float max_sq_dist, const float *g, float *dL_dqueries, float *dL_dpoints,
+                                  void *temp) {
+    CSPLAT_REQUIRE(Q >= 1 && N >= 1, "csplat_chamfer_bwd: Q and N must be >= 1");
+    CSPLAT_REQUIRE(queries && points && d2 && idx && g, "csplat_chamfer_bwd: NULL argument");
+    CSPLAT_REQUIRE(!dL_dpoints || temp, "csplat_chamfer_bwd: dL_dpoints needs temp");
+    CSPLAT_REQUIRE(!(max_sq_dist != max_sq_dist), "csplat_chamfer_bwd: max_sq_dist is NaN");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+    if (dL_dqueries) {
+        k_chamfer_bwd_queries<<<cdiv(Q, 256), 256, 0, s>>>(Q, N, queries, points, d2, idx, max_sq_dist, g, dL_dqueries);
+        LAUNCH_CHECK();
+    }
+    if (dL_dpoints) {
+        const ChamferWs w = chamfer_ws(Q);
+        char *t = (char *)temp;
+        uint64_t *keys = (uint64_t *)(t + w.keys), *keys_o = (uint64_t *)(t + w.keys_o), *keys_t = (uint64_t *)(t + w.keys_t);
+        uint32_t *vals = (uint32_t *)(t + w.vals), *vals_o = (uint32_t *)(t + w.vals_o), *vals_t = (uint32_t *)(t + w.vals_t);
+        int bits = 1;
+        while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)N) bits++;
+        HIP_TRY(hipMemsetAsync(dL_dpoints, 0, (size_t)N * 3 * sizeof(float), s));
+        k_chamfer_keys<<<cdiv(Q, 256), 256, 0, s>>>(Q, idx, keys, vals);
+        LAUNCH_CHECK();
+        if (int rc = csplat_sort_pairs(s, keys, vals, keys_o, vals_o, keys_t, vals_t, Q, bits, t + w.stab)) return rc;
+        k_chamfer_bwd_points<<<cdiv(Q, 256), 256, 0, s>>>(Q, N, keys_o, vals_o, queries, points, d2, idx, max_sq_dist, g, dL_dpoints);
+        LAUNCH_CHECK();
+    }
+    return 0;
+}

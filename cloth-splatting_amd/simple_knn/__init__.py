@@ -55,3 +55,49 @@ def fps(points: torch.Tensor, num_samples: int, start: int):
     with _n.on_device(dev):
         _n.check(_n.lib.csplat_fps(_n.stream_handle(dev), N, S, _n.ptr(pts), int(start) if S else 0, _n.ptr(min_d2), _n.ptr(out)), "csplat_fps")
     return out.to(torch.int64)
+
+
+# knn_query: from this many POINTS on the Morton-ordered form (csplat_knn_query_ws) is taken.  Measured: profiles/knn_query_cost.txt
+# (tools/knn_query_cost.py; N in {1k, 4k, 16k, 100k} x Q in {1k, 16k, 100k} x K in {1, 8}) -- the smallest N of the table from which the
+# pruned form wins at every Q and K of the table.  At N = 16k it wins for K = 8 (x 1.5 .. 1.8) but loses for K = 1 at Q >= 16k
+# (0.95 against 0.82 ms at Q = 16k, 1.05 against 0.83 at Q = 100k); at N = 100k it wins everywhere, x 2.4 .. 3.7.  No condition on Q: at N = 100k the order is the same at every Q.
+QUERY_BOXED_FROM = 100_000
+
+
+def _checked_query(queries, points, k, what):
+    """argument errors of a two-cloud search, raised before anything touches the device"""
+    _checked_points(points, k, what)
+    if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != 3:
+        raise ValueError(f"{what}: queries must be a [Q, 3] tensor, got {tuple(getattr(queries, 'shape', ()))}")
+    if queries.dtype != torch.float32:
+        raise ValueError(f"{what}: queries must be float32, got {queries.dtype}")
+    if queries.device != points.device:
+        raise ValueError(f"{what}: queries are on {queries.device}, points on {points.device}")
+
+
+def _knn_query_i32(qry, pts, k, boxed=None):
+    """(d2 float32 [Q,k], idx int32 [Q,k]) of checked, detached, contiguous GPU clouds; boxed: None = by QUERY_BOXED_FROM"""
+    Q, N, dev = int(qry.shape[0]), int(pts.shape[0]), pts.device
+    d2 = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    if boxed is None:
+        boxed = N >= QUERY_BOXED_FROM
+    with _n.on_device(dev):
+        if boxed:   # Morton order + box pruning; the same bits and indices
+            temp = torch.empty(int(_n.lib.csplat_knn_query_temp_bytes(Q, N, k)), dtype=torch.uint8, device=dev)
+            _n.check(_n.lib.csplat_knn_query_ws(_n.stream_handle(dev), Q, N, k, _n.ptr(qry), _n.ptr(pts), _n.ptr(d2), _n.ptr(idx),
+                                                _n.ptr(temp)), "csplat_knn_query_ws")
+        else:
+            _n.check(_n.lib.csplat_knn_query(_n.stream_handle(dev), Q, N, k, _n.ptr(qry), _n.ptr(pts), _n.ptr(d2), _n.ptr(idx)),
+                     "csplat_knn_query")
+    return d2, idx
+
+
+def knn_query(queries: torch.Tensor, points: torch.Tensor, k: int):
+    """queries [Q,3], points [N,3], float32 on one GPU -> (sq_dists float32 [Q,k], indices int64 [Q,k]): the k nearest of `points`
+    to every query, ascending in (sq_dist, index).  Nothing is excluded: a query that coincides with a point finds it at distance
+    0.  Exact: ties go to the smaller index; rows with fewer than k points end in (+inf, -1)."""
+    _checked_query(queries, points, k, "simple_knn.knn_query")
+    _n.require_cuda(queries, points)
+    d2, idx = _knn_query_i32(queries.detach().contiguous(), points.detach().contiguous(), k)
+    return d2, idx.to(torch.int64)

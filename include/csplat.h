@@ -369,6 +369,35 @@ int csplat_knn_ws(void *stream, int P, int K, const float *xyz, float *out_d2, i
  * One workgroup runs all S rounds; 0 <= start < N. */
 int csplat_fps(void *stream, int N, int S, const float *xyz, int start, float *min_d2, int32_t *out_idx);
 
+/* Exact k nearest neighbours between TWO clouds.  out_d2[i*K + r], out_idx[i*K + r]: the r-th nearest of `points` [N,3] to
+ * query i of `queries` [Q,3], ascending in (d2, index) -- ties in d2 go to the smaller index, so the result is unique.  Nothing
+ * is excluded: a query that coincides with a point finds it at distance 0.  Slots r >= N: d2 = +inf, idx = -1.
+ * d2 = dx*dx + dy*dy + dz*dz with d = point - query, FP contraction off (the arithmetic of csplat_knn).
+ * 1 <= K <= CSPLAT_KNN_MAX_K.  Q = 0 is a no-op; N = 0 fills every slot with (+inf, -1) (`points`, and `temp`, may then be
+ * NULL).  Negative sizes, a K outside the range and NULL with non-zero sizes are errors whose text names the entry point.
+ * csplat_knn_query is the brute-force form; csplat_knn_query_ws orders the points along a Morton curve, prunes by the bounding
+ * boxes of 1024-point runs and orders the queries along the same curve (clamped to the points' bounding box), temp:
+ * csplat_knn_query_temp_bytes(Q, N, K) bytes of device memory.  Both forms return the same bits and the same indices for
+ * every input.  Added exports: CSPLAT_ABI_VERSION is unchanged. */
+int csplat_knn_query(void *stream, int Q, int N, int K, const float *queries, const float *points, float *out_d2, int32_t *out_idx);
+size_t csplat_knn_query_temp_bytes(int Q, int N, int K);
+int csplat_knn_query_ws(void *stream, int Q, int N, int K, const float *queries, const float *points, float *out_d2, int32_t *out_idx,
+                        void *temp);
+
+/* One direction of the Chamfer distance from a K = 1 result (d2 [Q], idx [Q]) of csplat_knn_query(queries -> points).
+ * w_i = 1 when max_sq_dist < 0 (no cap) or d2[i] <= max_sq_dist, else 0.
+ * csplat_chamfer_fwd: loss[0] = (1/Q) sum_i w_i d2[i].  The divisor is always Q; the sum runs in a fixed order inside one
+ * workgroup (fp64 accumulation, one rounding at the end).  Q >= 1.
+ * csplat_chamfer_bwd: g is a DEVICE scalar, the upstream gradient (no host value enters a launch: the path records into a
+ * hipGraph).  dL_dqueries[i] = g (2/Q) w_i (q_i - p_idx[i]); dL_dpoints[j] = - the sum of the same terms over the queries with
+ * idx[i] = j, in ascending i (stable sort of (idx, i), one lane sums a run: no float atomics, the result is reproducible bit
+ * for bit); every row of dL_dpoints is written, exact zeros for a point nobody selected.  Either output may be NULL.
+ * temp: csplat_chamfer_bwd_temp_bytes(Q, N) bytes of device memory (needed for dL_dpoints only).  Q >= 1, N >= 1. */
+int csplat_chamfer_fwd(void *stream, int Q, const float *d2, float max_sq_dist, float *loss);
+size_t csplat_chamfer_bwd_temp_bytes(int Q, int N);
+int csplat_chamfer_bwd(void *stream, int Q, int N, const float *queries, const float *points, const float *d2, const int32_t *idx,
+                       float max_sq_dist, const float *g, float *dL_dqueries, float *dL_dpoints, void *temp);
+
 /* Separable 11-tap window of the SSIM loss (utils/loss_utils.py:30-58), zero padded: out = G (x) G * in for every one of
  * the n_images [H][W] planes.  taps11 is a HOST pointer to the 11 normalised window weights.  Self-adjoint: the backward
  * of the operator is the operator.  (SURVEY.md 8(f) "next" row N2.) */
