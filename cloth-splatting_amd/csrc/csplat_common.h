@@ -39,11 +39,16 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ---- device-wide primitives implemented in csplat_sort.hip -------------------------------------
-// inclusive scan of n uint32 (in -> out), total also written to *total_dev (device u32).  temp >= scan_temp_bytes(n)
+// inclusive scan of n uint32 (in -> out), sums modulo 2^32; the total is out[n - 1] (there is no separate total output).  `in` and `out`
+// must not alias (the kernels read `in` through __restrict__ after `out` is being written).  temp >= scan_temp_bytes(n); n <= 0: no-op
 size_t csplat_scan_temp_bytes(int64_t n);
 int csplat_inclusive_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, int64_t n, void *temp);
 
-// stable LSD radix sort of (u64 key, u32 value) pairs on key bits [0, end_bit).  Result ends in keys_out/vals_out.
+// stable LSD radix sort of (u64 key, u32 value) pairs in whole 8-bit digits: the order is that of key bits [0, 8 * ceil(end_bit / 8)),
+// NOT [0, end_bit) -- for end_bit = 10, bits 10..15 take part.  Bits at or above 8 * ceil(end_bit / 8) travel with their key and do not
+// affect the order.  1 <= end_bit <= 64 (anything else is refused: zero passes would leave the outputs unwritten).  ceil(end_bit / 8)
+// passes alternate between the output and the temporary buffers so that the last one lands in keys_out / vals_out; keys_tmp / vals_tmp
+// [n] are needed from two passes on.  Inputs are not written.  temp >= sort_temp_bytes(n); n <= 0: no-op
 size_t csplat_sort_temp_bytes(int64_t n);
 int csplat_sort_pairs(hipStream_t s, const uint64_t *keys_in, const uint32_t *vals_in, uint64_t *keys_out,
                       uint32_t *vals_out, uint64_t *keys_tmp, uint32_t *vals_tmp, int64_t n, int end_bit, void *temp);

@@ -294,6 +294,7 @@ size_t csplat_sort_temp_bytes(int64_t n) {
 int csplat_sort_pairs(hipStream_t s, const uint64_t *keys_in, const uint32_t *vals_in, uint64_t *keys_out,
                       uint32_t *vals_out, uint64_t *keys_tmp, uint32_t *vals_tmp, int64_t n, int end_bit, void *temp) {
     if (n <= 0) return 0;
+    CSPLAT_REQUIRE(end_bit >= 1 && end_bit <= 64, "csplat_sort_pairs: end_bit outside 1..64");
     const int passes = (end_bit + 7) / 8;
     const int nb = cdiv(n, SORT_TILE);
     uint32_t *table = (uint32_t *)temp;
@@ -314,4 +315,45 @@ int csplat_sort_pairs(hipStream_t s, const uint64_t *keys_in, const uint32_t *va
         vsrc = vdst;
     }
     return 0;
+}
+
+// ---- the two primitives as entry points of their own (tests/test_sort_scan_gpu.py): the consumers above are poor witnesses -- the k-NN
+// searches are exact for any order of the sorted codes, and the rasterizer reaches one or two pass counts
+namespace {
+struct SortPairsCarve { size_t keys_tmp, vals_tmp, table, total; };
+SortPairsCarve sort_pairs_carve(int64_t n) {
+    const size_t m = (size_t)(n > 0 ? n : 0);
+    SortPairsCarve c;
+    c.keys_tmp = 0;
+    c.vals_tmp = c.keys_tmp + align256(m * sizeof(uint64_t));
+    c.table = c.vals_tmp + align256(m * sizeof(uint32_t));
+    c.total = c.table + csplat_sort_temp_bytes(n);
+    return c;
+}
+}  // namespace
+
+extern "C" size_t csplat_sort_pairs_temp_bytes(int64_t n) { return sort_pairs_carve(n).total; }
+
+extern "C" int csplat_sort_pairs_u64(void *stream, int64_t n, int end_bit, const uint64_t *keys_in, const uint32_t *vals_in,
+                                     uint64_t *keys_out, uint32_t *vals_out, void *temp) {
+    CSPLAT_REQUIRE(n >= 0, "csplat_sort_pairs_u64: bad n");
+    CSPLAT_REQUIRE(end_bit >= 1 && end_bit <= 64, "csplat_sort_pairs_u64: end_bit outside 1..64");
+    if (n == 0) return 0;
+    CSPLAT_REQUIRE(keys_in && vals_in && keys_out && vals_out && temp, "csplat_sort_pairs_u64: NULL");
+    CSPLAT_REQUIRE(keys_out != keys_in, "csplat_sort_pairs_u64: in place (keys_out is keys_in)");
+    CSPLAT_REQUIRE(vals_out != vals_in, "csplat_sort_pairs_u64: in place (vals_out is vals_in)");
+    const SortPairsCarve c = sort_pairs_carve(n);
+    char *t = (char *)temp;
+    return csplat_sort_pairs((hipStream_t)stream, keys_in, vals_in, keys_out, vals_out, (uint64_t *)(t + c.keys_tmp),
+                             (uint32_t *)(t + c.vals_tmp), n, end_bit, t + c.table);
+}
+
+extern "C" size_t csplat_scan_u32_temp_bytes(int64_t n) { return csplat_scan_temp_bytes(n > 0 ? n : 0); }
+
+extern "C" int csplat_scan_u32(void *stream, int64_t n, const uint32_t *in, uint32_t *out, void *temp) {
+    CSPLAT_REQUIRE(n >= 0, "csplat_scan_u32: bad n");
+    if (n == 0) return 0;
+    CSPLAT_REQUIRE(in && out && temp, "csplat_scan_u32: NULL");
+    CSPLAT_REQUIRE(out != in, "csplat_scan_u32: in place (out is in)");
+    return csplat_inclusive_scan_u32((hipStream_t)stream, in, out, n, temp);
 }

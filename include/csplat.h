@@ -865,6 +865,25 @@ int csplat_gauss_act_bwd(void *stream, int64_t P, const float *opacity, const fl
                          const float *g_scales, const float *g_shs, float *d_opacity_raw, float *d_scaling_raw,
                          float *d_features_dc, float *d_features_rest);
 
+/* The two device-wide primitives the library is built on (csrc/csplat_sort.hip), as entry points of their own so that a test can reach
+ * them: the rasterizer's tile sort and tiles_touched scan, the k-NN Morton sorts, the Chamfer backward's (index, query) sort, the GNN CSR
+ * build and csplat_mask_to_map all run on them.  Added exports: CSPLAT_ABI_VERSION is unchanged.
+ *
+ * csplat_sort_pairs_u64: stable LSD radix sort of n (u64 key, u32 value) pairs, 8 bits per pass, ceil(end_bit / 8) passes.
+ *   The order is that of key bits [0, 8 * ceil(end_bit / 8)) -- whole digits, NOT [0, end_bit): for end_bit = 10 the bits 10..15 take
+ *   part.  Key bits at or above 8 * ceil(end_bit / 8) travel with their key into keys_out and do not affect the order.  Pairs whose
+ *   ordered bits are equal keep their input order.  1 <= end_bit <= 64; n >= 0 (n = 0: a no-op that accepts NULL pointers); n below 2^32.
+ *   The inputs are not written; keys_out / vals_out [n] must not be the inputs (refused) nor overlap them.
+ *   temp: csplat_sort_pairs_temp_bytes(n) bytes of device memory (a second key and value buffer and the 256 x ceil(n / 4096) digit table).
+ * csplat_scan_u32: out[i] = in[0] + ... + in[i] modulo 2^32, n >= 0 (n = 0: a no-op that accepts NULL pointers).  `out` must not be `in`
+ *   (refused) nor overlap it.  temp: csplat_scan_u32_temp_bytes(n) bytes of device memory.
+ * Errors (non-zero, text from csplat_last_error names the entry point) are raised before any launch. */
+size_t csplat_sort_pairs_temp_bytes(int64_t n);
+int csplat_sort_pairs_u64(void *stream, int64_t n, int end_bit, const uint64_t *keys_in, const uint32_t *vals_in, uint64_t *keys_out,
+                          uint32_t *vals_out, void *temp);
+size_t csplat_scan_u32_temp_bytes(int64_t n);
+int csplat_scan_u32(void *stream, int64_t n, const uint32_t *in, uint32_t *out, void *temp);
+
 #ifdef __cplusplus
 }
 #endif
