@@ -72,6 +72,11 @@ EXPORTS = {
     "csplat_chamfer_fwd": (_i, [_vp, _i, _vp, _f, _vp]),
     "csplat_chamfer_bwd_temp_bytes": (_sz, [_i, _i]),
     "csplat_chamfer_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "csplat_knn_regs_graph_temp_bytes": (_sz, [_i, _i]),
+    "csplat_knn_regs_graph": (_i, [_vp, _i, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_knn_regs_fwd_scratch_bytes": (_sz, []),
+    "csplat_knn_regs_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp]),
+    "csplat_knn_regs_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _vp]),
     "csplat_mesh_rest_bytes": (_sz, [_i]),
     "csplat_mesh_rest": (_i, [_vp, _i, _vp, _vp, _vp]),
     "csplat_mesh_transform_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

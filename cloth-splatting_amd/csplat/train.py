@@ -907,6 +907,50 @@ def _chamfer_targets(cams):
     return out
 
 
+def _neighbour_options(opt, iteration=None, static=False):
+    """the kNN-graph regularisers' options of a namespace (absent = 0 / off): dict(lams=(isometric, spring, rigidity), lambda_w, k,
+    update, reg_iter, iso_abs); ValueError for a bad value.  With `iteration` given: None unless the term is ON -- some weight > 0, the
+    step is not static, iteration > reg_iter."""
+    lams = []
+    for name in ("lambda_isometric", "lambda_spring", "lambda_rigidity"):
+        v = float(getattr(opt, name, 0.0) or 0.0)
+        if not (v >= 0.0 and v <= 3.0e38):
+            raise ValueError(f"train_step: {name} is a finite number >= 0, got {v}")
+        lams.append(v)
+    o = dict(lams=tuple(lams), on=max(lams) > 0.0)
+    if not o["on"]:
+        return None if iteration is not None else o
+    lw = getattr(opt, "lambda_w", None)
+    o["lambda_w"] = 2000.0 if lw is None else float(lw)
+    if not (o["lambda_w"] >= 0.0 and o["lambda_w"] <= 3.0e38):
+        raise ValueError(f"train_step: lambda_w is a finite number >= 0, got {o['lambda_w']}")
+    for key, name, default, least in (("k", "k_nearest", 20, 1), ("update", "knn_update_iter", 1000, 1), ("reg_iter", "reg_iter", 0, 0)):
+        v = getattr(opt, name, None)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, int) or v < least:
+            raise ValueError(f"train_step: {name} is an integer >= {least}, got {v!r}")
+        o[key] = v
+    if o["k"] > 32:
+        raise ValueError(f"train_step: k_nearest is at most 32 (simple_knn.MAX_K), got {o['k']}")
+    o["iso_abs"] = bool(getattr(opt, "isometric_abs", False))
+    if iteration is not None and (static or iteration <= o["reg_iter"]):
+        return None
+    return o
+
+
+def _neighbour_graph(gaussians, iteration, o):
+    """the step's NeighbourGraph: the exact k-NN graph of the detached, UNDEFORMED centres, cached on the Gaussians object; rebuilt when
+    absent, when the number of Gaussians (or k / lambda_w) has changed, and every knn_update_iter iterations"""
+    from .knn_regs import NeighbourGraph
+    key = (int(gaussians.num_gaussians), o["k"], o["lambda_w"])
+    cached = gaussians.__dict__.get("_neighbour_graph")
+    if cached is None or cached[0] != key or iteration % o["update"] == 0:
+        with torch.no_grad():
+            pts = gaussians.get_xyz().detach().float().contiguous()
+        cached = gaussians._neighbour_graph = (key, NeighbourGraph.from_points(pts, o["k"], o["lambda_w"]), iteration)
+    return cached[1]
+
+
 def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimizer, pipe=DEFAULT_PIPE, opt=DEFAULT_OPT,
                background=None, static=False, view_parallel=False, batched_views=True, densify_opt=None, time_allreduce=False, captured=False,
                _cap=None):
@@ -941,7 +985,16 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
     free per camera.  stats then holds "chamfer_loss" (the detached mean, a device scalar).  The rules are the geometry terms':
     ValueError before the simulator runs for a camera without `points` or with another shape or dtype; NotImplementedError before
     anything runs for a view-parallel step and for batched_views=False; captured=True runs such a step eagerly.  With the weight 0 or
-    absent nothing is added to the step."""
+    absent nothing is added to the step.
+
+    kNN-graph regularisers (csplat.knn_regs): `opt.lambda_isometric`, `opt.lambda_spring`, `opt.lambda_rigidity` (absent = 0) add
+    neighbour_regularization(the views' means3D_deform, the views' rotations, in camera order) on the k-NN graph of the undeformed
+    centres -- `opt.k_nearest` (absent: 20), `opt.lambda_w` (absent: 2000; w = exp(-lambda_w d^2)), rebuilt every `opt.knn_update_iter`
+    iterations (absent: 1000) and after the number of Gaussians changed; `opt.isometric_abs` (absent: the reference's signed isometry
+    term).  The term is on when some weight is > 0, the step is not static and iteration > `opt.reg_iter` (absent: 0).  stats then
+    holds "isometric_loss", "spring_loss", "rigidity_loss" (detached device scalars, unweighted; 0 for rigidity without its weight).  ValueError before the simulator
+    runs: a bad option value, num_gaussians <= k_nearest; NotImplementedError before anything runs: a view-parallel step,
+    batched_views=False; captured=True runs such a step eagerly.  With all three weights 0 or absent nothing is added to the step."""
     if captured and _cap is None:     # the step as a replayed hipGraph (CapturedStep below); falls back to this function when it must
         cs = gaussians.__dict__.get("_captured_step")
         if cs is None or not cs.matches(simulator, meshnet_optimizer, pipe, opt, background):
@@ -966,6 +1019,14 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
         if not batched_views:
             raise NotImplementedError("train_step: the Chamfer term needs batched_views=True")
         chamfer_pts = _chamfer_targets(all_cams)
+    nbr = _neighbour_options(opt, iteration, static) if all_cams else None
+    if nbr is not None:
+        if view_parallel and cd.is_dist():
+            raise NotImplementedError("train_step: the kNN-graph regularisers are not part of the view-parallel step")
+        if not batched_views:
+            raise NotImplementedError("train_step: the kNN-graph regularisers need batched_views=True")
+        if int(gaussians.num_gaussians) <= nbr["k"]:
+            raise ValueError(f"train_step: {int(gaussians.num_gaussians)} Gaussians have no k_nearest = {nbr['k']} neighbours each")
     if iteration % 1000 == 0 and _cap is None:
         gaussians.oneupSHdegree()
     _DEFERRED.clear()                 # (a launch queued by a step that raised before issuing it)
@@ -1047,6 +1108,17 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
         chamfer_mean = torch.stack(terms).mean()
         reg = reg + lam_chamfer * chamfer_mean
         geom_stats["chamfer_loss"] = chamfer_mean.detach()
+    if nbr is not None:
+        # isometry, spring and rigidity of the deformed centres / rotations over the step's time rows: one launch (and one in backward);
+        # the sum rides into the image loss with the regularisers
+        from .knn_regs import neighbour_regularization
+        graph = _neighbour_graph(gaussians, iteration, nbr)
+        # (without a rigidity weight the rotations are not handed over: nothing of them is read, rigidity_loss reports 0)
+        nb_loss, nb_parts = neighbour_regularization(torch.stack([pkg.means3D_deform for pkg in pkgs]),
+                                                     torch.stack([pkg.rotations for pkg in pkgs]) if nbr["lams"][2] > 0.0 else None,
+                                                     graph, *nbr["lams"], isometric_abs=nbr["iso_abs"])
+        reg = reg + nb_loss
+        geom_stats["isometric_loss"], geom_stats["spring_loss"], geom_stats["rigidity_loss"] = nb_parts.unbind(0)
     if cams:
         image_tensor = stacked if stacked is not None else torch.cat(images, 0)
         gt_image_tensor = _gt_stack(cams, image_tensor.device) if _cap is None else _cap["gt"]
@@ -1136,7 +1208,8 @@ class CapturedStep:
     One graph per step SHAPE: (number of cameras, image size, field of view, number of Gaussians, active SH degree, parameter storage,
     pipe.antialiasing).
     Falls back to the eager train_step for what it does not cover: masks, a static stage, view-parallel runs, densification steps, the
-    depth and silhouette terms (opt.lambda_depth / opt.lambda_silhouette > 0), the Chamfer term (opt.lambda_chamfer > 0)."""
+    depth and silhouette terms (opt.lambda_depth / opt.lambda_silhouette > 0), the Chamfer term (opt.lambda_chamfer > 0), the kNN-graph
+    regularisers (opt.lambda_isometric / opt.lambda_spring / opt.lambda_rigidity > 0)."""
 
     MARGIN = 8          # capacities = counts + counts / MARGIN (+ a constant)
 
@@ -1161,6 +1234,7 @@ class CapturedStep:
         return (len(cams) >= 2 and len(cams) <= 8 and all(getattr(c, "mask", None) is None for c in cams) and
                 max(_geometry_weights(self.opt)) == 0.0 and       # (a depth / silhouette term: the rasterizer refuses its gradients on a forward launched on faith)
                 _chamfer_weight(self.opt)[0] == 0.0 and           # (the Chamfer term: the observed clouds' sizes are per camera, not part of a step's shape)
+                not _neighbour_options(self.opt)["on"] and          # (the kNN-graph regularisers: the graph is refreshed on the host's schedule)
                 len({(int(c.image_height), int(c.image_width), float(c.FoVx), float(c.FoVy)) for c in cams}) == 1 and
                 self.g.mesh.pos.is_cuda and isinstance(self.g.optimizer, GroupedAdam) and isinstance(self.mopt, GroupedAdam) and
                 not (int(_n.lib.csplat_debug_flags_query()) & (2 | 128 | 512)) and      # (global sort, per-view launches; the bit-reproducible K7, bit 8, is served by the batched path since round 6)

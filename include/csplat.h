@@ -398,6 +398,45 @@ size_t csplat_chamfer_bwd_temp_bytes(int Q, int N);
 int csplat_chamfer_bwd(void *stream, int Q, int N, const float *queries, const float *points, const float *d2, const int32_t *idx,
                        float max_sq_dist, const float *g, float *dL_dqueries, float *dL_dpoints, void *temp);
 
+/* Neighbourhood regularisers on a K-neighbour graph of N nodes (csplat.knn_regs): isometry, spring and local rigidity of the
+ * Gaussian centres M[t] [N,3] and rotations Q[t] [N,4] ((w,x,y,z), not assumed normalised) at the T time rows of a step.
+ * The graph: idx [N,K] (neighbour j of pair (i,k)), d0 [N,K] >= 0 (rest distance), w [N,K] >= 0 (weight).  Per pair and row
+ *   off_t = M[t][j] - M[t][i],   d_t = |off_t|   (derivative off_t / d_t, 0 where d_t == 0)
+ *   L_iso    = mean_t      mean_{i,k} (d_t - d0)            signed; |d_t - d0| with isometric_abs (sign(0) = 0)
+ *   L_spring = mean_{t>=1} mean_{i,k} |d_t - d_{t-1}|       (sign(0) = 0)
+ *   L_rigid  = mean_{t>=1} mean_{i,k} sqrt(w |R off_t - off_{t-1}|^2 + 1e-20),   R = rotmat(r / |r|),
+ *              r = Q[t-1][j] (x) conj(Q[t][j])  (Hamilton product, the NEIGHBOUR's rotations; the normalisation is differentiated)
+ *   L = lambda_isometric L_iso + lambda_spring L_spring + lambda_rigidity L_rigid;  T = 1: L_spring = L_rigid = 0.
+ * A pair whose idx is outside 0 .. N-1 contributes nothing (the divisors stay N K).  1 <= K <= CSPLAT_KNN_MAX_K, N >= 1,
+ * 1 <= T < 65536, N K < 2^31, T N < 2^31; weights >= 0 and finite.  Errors name the entry point.
+ *
+ * csplat_knn_regs_graph: built once per graph refresh.  With d2 != NULL (the squared distances of csplat_knn) it writes
+ * d0 = sqrt(d2) and w = exp(-lambda_w d2) (exponent and exp in fp64, rounded once); with d2 == NULL d0 / w are the caller's.
+ * Always: the REVERSE lists -- rev_offsets [N+1], rev_entries [N K]: rev_entries[rev_offsets[j] .. rev_offsets[j+1]) are the
+ * pair numbers i K + k with idx[i,k] == j in ascending order (integer counts + csplat_scan, stable csplat_sort_pairs).
+ * temp: csplat_knn_regs_graph_temp_bytes(N, K) bytes, 16-byte aligned, as rev_offsets.
+ *
+ * csplat_knn_regs_fwd: ONE kernel launch; out4 = (L_iso, L_spring, L_rigid, L) on the device.  rotations == NULL: L_rigid = 0
+ * and w is not read.  The sums run in fp64 in a fixed order (per-workgroup partials over contiguous pair ranges, joined by
+ * the last workgroup in index order): the result does not depend on scheduling, stream or graph replay.
+ * scratch: csplat_knn_regs_fwd_scratch_bytes() bytes, 16-byte aligned, any contents; not shared by launches that may overlap.
+ *
+ * csplat_knn_regs_bwd: g is a DEVICE scalar (dL/dL; the path records into a hipGraph).  Gather-only, no float atomics:
+ * dL_dmeans[t][n] = the fixed-order sum over n's K own pairs and the pairs of its reverse list, every pair quantity
+ * recomputed; dL_drotations[t][n] from the reverse list alone, exact zeros where it is empty.  Either output may be NULL.
+ * With lambda_rigidity == 0 the rotations are not read (and may be NULL); a dL_drotations given then is cleared. */
+size_t csplat_knn_regs_graph_temp_bytes(int N, int K);
+int csplat_knn_regs_graph(void *stream, int N, int K, const int32_t *idx, const float *d2, double lambda_w, float *d0, float *w,
+                          int32_t *rev_offsets, int32_t *rev_entries, void *temp);
+size_t csplat_knn_regs_fwd_scratch_bytes(void);
+int csplat_knn_regs_fwd(void *stream, int T, int N, int K, const float *means, const float *rotations, const int32_t *idx,
+                        const float *d0, const float *w, float lambda_isometric, float lambda_spring, float lambda_rigidity,
+                        int isometric_abs, float *out4, void *scratch);
+int csplat_knn_regs_bwd(void *stream, int T, int N, int K, const float *means, const float *rotations, const int32_t *idx,
+                        const float *d0, const float *w, const int32_t *rev_offsets, const int32_t *rev_entries,
+                        float lambda_isometric, float lambda_spring, float lambda_rigidity, int isometric_abs, const float *g,
+                        float *dL_dmeans, float *dL_drotations);
+
 /* Separable 11-tap window of the SSIM loss (utils/loss_utils.py:30-58), zero padded: out = G (x) G * in for every one of
  * the n_images [H][W] planes.  taps11 is a HOST pointer to the 11 normalised window weights.  Self-adjoint: the backward
  * of the operator is the operator.  (SURVEY.md 8(f) "next" row N2.) */
