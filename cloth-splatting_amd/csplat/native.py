@@ -433,6 +433,9 @@ def prof_read(cls):
     return ms.value, n.value
 
 
+# csplat.h: CSPLAT_DEBUG_* (the bits Python reads back through csplat_debug_flags_query)
+DEBUG_BIT_REPRODUCIBLE = 256      # the backward scratch has another layout and is sized per call
+DEBUG_UNBATCHED = 2 | 128 | 512   # global sort, per-view K8, per-view launches: the one-launch-per-stage paths are off
 # experiment hook: CSPLAT_DEBUG_FLAGS=<int> applies csplat_debug_flags at import (A/B runs of bench.py without code edits)
 if os.environ.get("CSPLAT_DEBUG_FLAGS"):
     check(lib.csplat_debug_flags(int(os.environ["CSPLAT_DEBUG_FLAGS"], 0)), "csplat_debug_flags")

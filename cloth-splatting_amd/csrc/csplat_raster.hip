@@ -32,8 +32,9 @@
 //                          (body: csplat_k8_views_body.h), k_bg_partials, k_cam_sum
 // (this file)               needs: every part
 //      from the "---- layouts" rule to the end, the host code: the chunk layouts and their typed views (Geom, ImageView, BinView,
-//      TempView), the two-phase forward, the backward of one view (backward_impl, launch_k8), then the batched entry points and the
-//      extended paths (fill_b2_view, launch_k8_views)
+//      TempView, ScratchView), the two-phase forward and the extended forward passes, then the backward: one view's launches
+//      (backward_one, launch_k8), the batched ones (launch_k8_views, backward_views_depth / _colour), the one way in (backward_views_impl)
+//      and the exported entries
 //
 // Every stage has a `_views` form: all views of a step (at most RASTER_MAX_VIEWS) in one launch, blockIdx.y = view.
 // The extended paths, each launched only when a view asks for it (csplat_view, include/csplat.h):
@@ -512,7 +513,7 @@ __global__ __launch_bounds__(256) void k_zero_det_views(B2Table tab) {
     if (tab.valid && *tab.valid == 0u) return;
     const B2View &w = tab.v[blockIdx.y];
     float4 *p = reinterpret_cast<float4 *>(w.det);
-    const int64_t n4 = ((int64_t)(w.R > 0 ? w.R : 1) * 16 * 9 + 3) / 4;        // (det_bytes() is a multiple of 256: the tail is ours)
+    const int64_t n4 = ((int64_t)(w.R > 0 ? w.R : 1) * 16 * 9 + 3) / 4;        // (the layout's field is a multiple of 256 bytes: the tail is ours)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) p[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 __global__ __launch_bounds__(256) void k_zero_acc_views(int64_t n4, B2Table tab) {
@@ -600,6 +601,13 @@ __global__ __launch_bounds__(256) void k_det_reduce_views(int P, DetTable tab) {
 #include "csplat_raster_k8.h"
 
 namespace {
+
+// csplat_debug_flags: the CSPLAT_DEBUG_* bits of csplat.h.  (bits 13, 14, 16-21 selected the shelved kernel forms of round 3; they left the
+// library in round 4 and are ignored)
+unsigned g_debug_flags = 0;
+bool dbg(unsigned bits) { return (g_debug_flags & bits) != 0; }
+// K5b's exact ellipse-against-block stage is off under any of these
+constexpr unsigned DBG_NO_ELLIPSE_STAGE = CSPLAT_DEBUG_NO_CULLING | CSPLAT_DEBUG_CULL_RADIUS_X4 | CSPLAT_DEBUG_CIRCLE_ONLY;
 
 // ------------------------------------------------------------------------------------------- layouts
 // The saved state of a view lives in chunks the caller allocates (GEOM, IMAGE, BINNING, TEMP): every field 256-byte aligned, in enum
@@ -699,6 +707,38 @@ TempView temp_view(void *base, int64_t R) {
             (void *)(b + off[T_SORT])};
 }
 
+// the list capacity the view's BINNING chunk (and its scratch) was laid out for
+int layout_R(const csplat_view &w) { return w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered; }
+// backward scratch.  Four nested layouts, one per path of the backward, each a prefix of the next in enum order:
+//   colour   S_ACC records f32[P][ACC_STRIDE] | S_DET (entry, block) records f32[R][16][9]
+//   depth    S_ACC | S_DET f32[R][16][10] (slot 9 = dL/dz) | S_DPART depth partials f32[slots][256], one per (segment, pixel)
+//   camera   the depth layout | S_CAMSLAB f32[ceil(P / 32)][CAM_NC] (at most one row per 32 Gaussians: the batched K8's workgroup)
+//            | S_BGSLAB f32[BG_BLOCKS][3]
+//   feature  the camera layout | S_WPART feature partials f32[slots][256] | S_FDET (entry, block) records f32[R][16][16]
+// The (entry, block) records exist in the bit-reproducible mode only (else 0 bytes).  The feature layout still carries the depth layout's
+// 10-float region, unused: its K7 writes S_FDET.  A camera call whose K7 is the colour one keeps its 9-float records in S_DET.
+enum ScratchPath { SP_COLOUR, SP_DEPTH, SP_CAMERA, SP_FEATURE };
+enum { S_ACC, S_DET, S_DPART, S_CAMSLAB, S_BGSLAB, S_WPART, S_FDET, S_NFIELDS };
+constexpr int S_LAST[] = {S_DET, S_DPART, S_BGSLAB, S_FDET};      // every path's last field
+size_t scratch_offsets(ScratchPath path, int P, int64_t R, int W, int H, bool det_mode, size_t *off) {
+    const size_t p = (size_t)(P > 0 ? P : 1), det = det_mode ? (size_t)(R > 0 ? R : 1) * 16 * 4 : 0;
+    const size_t part = (size_t)max_slots(R, tiles_of(W, H)) * 256 * 4;
+    const size_t sz[S_NFIELDS] = {p * ACC_STRIDE * 4, det * (path == SP_COLOUR ? 9 : 10), part, (size_t)cdiv(p, 32) * CAM_NC * 4,
+                                  (size_t)BG_BLOCKS * 3 * 4, part, det * 16};
+    return lay_out(sz, S_LAST[path] + 1, off);
+}
+// det: the (entry, block) records the path's K7 writes (NULL outside the bit-reproducible mode), det_bytes: their field, to be cleared;
+// a field the path does not lay out is NULL, and so is every field of a view without scratch
+struct ScratchView { float *acc, *det, *dpart, *cam_slab, *bg_slab, *wpart; size_t det_bytes; };
+ScratchView scratch_view(const csplat_view &w, ScratchPath path) {
+    size_t off[S_NFIELDS + 1];
+    const bool det_mode = dbg(CSPLAT_DEBUG_BIT_REPRODUCIBLE);
+    const int last = S_LAST[path], d = path == SP_FEATURE ? S_FDET : S_DET;
+    off[last + 1] = scratch_offsets(path, w.P, layout_R(w), w.W, w.H, det_mode, off);
+    auto at = [&](int f) { return w.scratch && f <= last ? (float *)((char *)w.scratch + off[f]) : nullptr; };
+    return {at(S_ACC), det_mode ? at(d) : nullptr, at(S_DPART), at(S_CAMSLAB), at(S_BGSLAB), at(S_WPART), det_mode ? off[d + 1] - off[d] : 0};
+}
+
 // camera constants stay in HBM (80 bytes, read through the scalar cache by every wave): no host round trip
 int make_cam(Cam &c, const float *view, const float *proj, const float *campos, float tanfovx, float tanfovy, int W, int H) {
     c.view = view; c.proj = proj; c.campos = campos;
@@ -710,8 +750,6 @@ int make_cam(Cam &c, const float *view, const float *proj, const float *campos, 
 void make_cam(Cam &c, const csplat_view &w) { make_cam(c, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy, w.W, w.H); }
 
 // ---- a finished view (csplat_view) as the backward and the extended passes read it
-// the list capacity the view's BINNING chunk (and its scratch) was laid out for
-int layout_R(const csplat_view &w) { return w.layout_rendered > 0 ? w.layout_rendered : w.num_rendered; }
 // segments of the view: <= R / SEG + (non-empty tiles) + 1 with the EXACT counts the forward read -- the layout's bound (capacity / SEG +
 // all tiles + 1) launches twice as many workgroups that find no segment
 int64_t k7_slots(const csplat_view &w, int tiles) {
@@ -723,14 +761,15 @@ void fill_list_view(const BinView &b, const ImageView &im, T &k) {
     k.ranges = im.ranges; k.n_contrib = im.n_contrib;
     k.ids_sorted = b.ids_sorted; k.seg_offset = b.seg_offset; k.ckpt = b.ckpt; k.bbits = b.bbits; k.recA = b.recA; k.recB = b.recB;
 }
-// the view's K7 record; det = where the caller's path keeps the (entry, block) records of the bit-reproducible mode, else NULL
-void fill_b2_view(const csplat_view &w, const BinView &b, const ImageView &im, float *det, B2View &k) {
+// the view's K7 record (tiles: of its image) and, in the bit-reproducible mode (sv.det), what the fixed-order sum of its (entry, block)
+// records reads
+void fill_k7_view(const csplat_view &w, const ScratchView &sv, int tiles, B2View &k, DetView &e) {
+    const BinView b = binning_view(w.binning, layout_R(w), tiles);
+    const ImageView im = image_view(w.image, w.W, w.H);
     fill_list_view(b, im, k);
     k.final_T = im.final_T; k.slot_tile = b.slot_tile; k.recC = b.recC;
-    k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = (float *)w.scratch; k.R = (uint32_t)layout_R(w); k.det = det;
-}
-// ... and what the fixed-order sum of those records reads (bit-reproducible mode only)
-void fill_det_view(const csplat_view &w, const BinView &b, const B2View &k, DetView &e) {
+    k.out_color = w.out_color; k.dL_dpix = w.dL_dpix; k.acc = sv.acc; k.R = (uint32_t)layout_R(w); k.det = sv.det;
+    if (!sv.det || w.P <= 0) return;      // (a view without Gaussians has no chunks: nothing sums its records)
     make_cam(e.cam, w);
     const Geom g = geom_view(w.geom, w.P);
     e.xy = g.xy; e.depth = g.depth; e.radii = w.radii; e.ranges = k.ranges; e.keys_sorted = b.keys_sorted; e.ids_sorted = k.ids_sorted;
@@ -766,18 +805,11 @@ bool mail_init() {
     return g_mail.host != nullptr;
 }
 
-// csplat_debug_flags: bit 0 no culling; bit 1 force the global radix sort; bit 2 no mailbox; bit 4 culling radius x4;
-// bit 5 circle test only; bit 7 per-view K8 launches; bit 8 bit-reproducible backward (ordered sums instead of float atomics);
-// bit 9 per-view launches on per-view streams; bit 10 no speculative second phase; bit 11 tile sort = the LSD radix sort only;
-// bit 12 tile sort: a tile with any multi-key bucket takes the radix fallback (test hook);
-// bit 15 K6 in the ROW form (four survivors per step; default: the survivor-column form, 16 per step, DPP row scans).
-// (bits 13, 14, 16-21 selected the shelved kernel forms of round 3; they left the library in round 4 and are ignored)
-unsigned g_debug_flags = 0;
 unsigned long long *g_stamp_buf = nullptr;     // csplat_debug_stamps: 12 u64 per K7 workgroup (rows form, batched launch)
 size_t g_stamp_words = 0;
 
 // `mode` argument of the tile sort kernels: bit 0 ids < 2^24, bit 1 radix only, bit 2 fallback limit 1
-int tsort_mode(int P) { return (P < (1 << 24) ? 1 : 0) | ((g_debug_flags & 2048u) ? 2 : 0) | ((g_debug_flags & 4096u) ? 4 : 0); }
+int tsort_mode(int P) { return (P < (1 << 24) ? 1 : 0) | (dbg(CSPLAT_DEBUG_SORT_RADIX_ONLY) ? 2 : 0) | (dbg(CSPLAT_DEBUG_SORT_RADIX_FALLBACK) ? 4 : 0); }
 
 int higher_msb(uint32_t n) {  // number of bits needed to represent tile ids < n (upstream getHigherMsb)
     int b = 0;
@@ -817,37 +849,15 @@ size_t csplat_geom_bytes(int P) { size_t off[G_NFIELDS]; return geom_offsets(P, 
 size_t csplat_image_bytes(int W, int H) { size_t off[I_NFIELDS]; return image_offsets(W, H, off); }
 size_t csplat_binning_bytes(int64_t R, int W, int H) { size_t off[B_NFIELDS]; return binning_offsets(R, tiles_of(W, H), off); }
 size_t csplat_temp_bytes(int P, int64_t R, int W, int H) { (void)P; (void)W; (void)H; size_t off[T_NFIELDS]; return temp_offsets(R, off); }
-// backward scratch: the per-Gaussian records; in the bit-reproducible mode (csplat_debug_flags bit 8) also one 9-float record
-// per (list entry, quadrant)
-static size_t acc_bytes(int P) { return align256((size_t)(P > 0 ? P : 1) * ACC_STRIDE * 4); }
-static size_t det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 9 * 4); }
-size_t csplat_backward_scratch_bytes(int P, int64_t R) { return acc_bytes(P) + ((g_debug_flags & 256u) ? det_bytes(R) : 0); }
-// the depth-gradient path: the per-Gaussian records, in the bit-reproducible mode the (entry, block) records of 10 floats, then the
-// per-(segment, pixel) depth partials of the prepass
-static size_t depth_det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 10 * 4); }
-static size_t depth_dpart_offset(int P, int64_t R) { return acc_bytes(P) + ((g_debug_flags & 256u) ? depth_det_bytes(R) : 0); }
-size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H) {
-    return depth_dpart_offset(P, R) + align256((size_t)max_slots(R, tiles_of(W, H)) * 256 * 4);
+// backward scratch of the four paths (scratch_offsets)
+static size_t scratch_bytes(ScratchPath path, int P, int64_t R, int W, int H) {
+    size_t off[S_NFIELDS];
+    return scratch_offsets(path, P, R, W, H, dbg(CSPLAT_DEBUG_BIT_REPRODUCIBLE), off);
 }
-// the camera path's slabs live behind everything the depth path lays out: the K8 slab (at most one row per 32 Gaussians: the batched K8's
-// workgroup), then the background slab
-static size_t cam_slab_offset(int P, int64_t R, int W, int H) { return csplat_backward_depth_scratch_bytes(P, R, W, H); }
-static size_t cam_bg_offset(int P, int64_t R, int W, int H) {
-    return cam_slab_offset(P, R, W, H) + align256((size_t)cdiv(P > 0 ? P : 1, 32) * CAM_NC * 4);
-}
-size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H) {
-    return cam_bg_offset(P, R, W, H) + align256((size_t)BG_BLOCKS * 3 * 4);
-}
-// the feature / alpha path (ABI 9) lays out everything the camera path does, then the feature partials of the prepass (one float per
-// (segment, pixel)) and, in the bit-reproducible mode, its own 16-float (entry, block) records (the depth layout's 10-float ones go unused)
-static size_t feat_wpart_offset(int P, int64_t R, int W, int H) { return csplat_backward_camera_scratch_bytes(P, R, W, H); }
-static size_t feat_det_offset(int P, int64_t R, int W, int H) {
-    return feat_wpart_offset(P, R, W, H) + align256((size_t)max_slots(R, tiles_of(W, H)) * 256 * 4);
-}
-static size_t feat_det_bytes(int64_t R) { return align256((size_t)(R > 0 ? R : 1) * 16 * 16 * 4); }
-size_t csplat_backward_feature_scratch_bytes(int P, int64_t R, int W, int H) {
-    return feat_det_offset(P, R, W, H) + ((g_debug_flags & 256u) ? feat_det_bytes(R) : 0);
-}
+size_t csplat_backward_scratch_bytes(int P, int64_t R) { return scratch_bytes(SP_COLOUR, P, R, 0, 0); }
+size_t csplat_backward_depth_scratch_bytes(int P, int64_t R, int W, int H) { return scratch_bytes(SP_DEPTH, P, R, W, H); }
+size_t csplat_backward_camera_scratch_bytes(int P, int64_t R, int W, int H) { return scratch_bytes(SP_CAMERA, P, R, W, H); }
+size_t csplat_backward_feature_scratch_bytes(int P, int64_t R, int W, int H) { return scratch_bytes(SP_FEATURE, P, R, W, H); }
 int csplat_geom_layout(int P, size_t *o8) { size_t off[G_NFIELDS]; geom_offsets(P, off); for (int k = 0; k < 8; k++) o8[k] = off[k]; return 0; }
 // every sub-buffer of the BINNING chunk (csplat.h: csplat_binning_fields): 0 keys 1 ids 2 seg_offset + blk_hi 3 slot_tile 4 checkpoints
 // 5 masks 6-8 records A / B / C 9 bbits 10 bmask; o11[11] = byte offsets for a chunk laid out for R list entries (diagnostics: tools/,
@@ -923,7 +933,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
     CSPLAT_REQUIRE(gbase && ibase, "allocator returned NULL");
     const ImageView im = image_view(ibase, W, H);
     const int tiles = cam.gx * cam.gy;
-    const bool can_bucket = tiles <= BUCKET_TILES && !(g_debug_flags & 2u);
+    const bool can_bucket = tiles <= BUCKET_TILES && !dbg(CSPLAT_DEBUG_GLOBAL_SORT);
     uint32_t *table = nullptr;
     if (can_bucket) {
         table = (uint32_t *)alloc(alloc_ctx, CSPLAT_CHUNK_TABLE, bucket_table_bytes(P, tiles));
@@ -940,7 +950,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
     FwdTicket &t = g_tickets[tk];
     t.s = s; t.P = P; t.W = W; t.H = H; t.tiles = tiles; t.nb = cdiv(P > 0 ? P : 1, BUCKET_G); t.can_bucket = can_bucket;
     t.use_mail = false; t.tag = 0; t.mb_host = nullptr; t.mb_dev = nullptr;
-    if (can_bucket && !(g_debug_flags & 4u) && mail_init()) {
+    if (can_bucket && !dbg(CSPLAT_DEBUG_NO_MAILBOX) && mail_init()) {
         t.use_mail = true;
         t.tag = g_mail.next.fetch_add(1);
         if (t.tag == 0) t.tag = g_mail.next.fetch_add(1);
@@ -958,7 +968,7 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
     return 0;
 }
 
-static int nocull_mode() { return (int)((g_debug_flags & 1u) ? 1 : ((g_debug_flags & 16u) ? 2 : 0)); }
+static int nocull_mode() { return dbg(CSPLAT_DEBUG_NO_CULLING) ? 1 : dbg(CSPLAT_DEBUG_CULL_RADIUS_X4) ? 2 : 0; }
 
 // K1 + the counting half of the binning of ONE view, on its stream
 static int begin_launch(const FwdTicket &t) {
@@ -1004,7 +1014,7 @@ static int begin_launch(const FwdTicket &t) {
 static bool begin_views_compatible(int V, const int *tk) {
     // (V == 1 qualifies too since round 5: a camera-by-camera caller -- the reference's own loop, train_utils.py:259-272 -- then gets the
     //  speculative second phase as well instead of a blocking read of its counts per camera)
-    if (V < 1 || V > RASTER_MAX_VIEWS || (g_debug_flags & 512u)) return false;
+    if (V < 1 || V > RASTER_MAX_VIEWS || dbg(CSPLAT_DEBUG_PER_VIEW_LAUNCHES)) return false;
     const FwdTicket &a = g_tickets[tk[0]];
     if (a.P <= 0 || !a.can_bucket || !a.shs || a.colors_precomp || a.cov3D_precomp || !a.scales || !a.rotations) return false;
     for (int i = 1; i < V; i++) {
@@ -1233,7 +1243,7 @@ static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, con
         }
         {
             ProfScope ps(PROF_K5, join);
-            const int exact = (g_debug_flags & (1u | 16u | 32u)) ? 0 : 1, nbm = cdiv((int64_t)maxR + 1, 256);
+            const int exact = dbg(DBG_NO_ELLIPSE_STAGE) ? 0 : 1, nbm = cdiv((int64_t)maxR + 1, 256);
             if (V == 1 || V == 2 || V == 4 || V == 8)         // one view per XCD (see k_block_masks_views)
                 k_block_masks_views<<<dim3((unsigned)(((int64_t)nbm * V + 7) / 8 * 8)), 256, 0, join>>>(tab, exact, V);
             else
@@ -1250,7 +1260,7 @@ static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, con
             // waves per slot to place): 158 -> 137 us for four views, step 0.685 -> 0.665 ms (same box, three alternations).  Bit 15 of
             // csplat_debug_flags selects the row form.
             const int total = cdiv(tiles, 8) * 128, bg_ = cdiv((int)Bcap, 8) * 128, busy_grid = bg_ < total ? bg_ : total;
-            if (!(g_debug_flags & 32768u))
+            if (!dbg(CSPLAT_DEBUG_K6_ROWS))
                 k_composite_fwd_views<false><<<dim3(busy_grid + K6_EXTRA, V), 64, 0, join>>>(tiles, W, H, tab, busy_grid);
             else
                 k_composite_fwd_views<true><<<dim3(busy_grid + K6_EXTRA, V), 64, 0, join>>>(tiles, W, H, tab, busy_grid);
@@ -1266,7 +1276,7 @@ static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, con
 static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_t join, bool *done, int mode = 0,
                                 PendingViews *pend = nullptr, int *relaunched = nullptr) {
     *done = false;
-    if (V < 1 || V > RASTER_MAX_VIEWS || (g_debug_flags & 512u)) return 0;
+    if (V < 1 || V > RASTER_MAX_VIEWS || dbg(CSPLAT_DEBUG_PER_VIEW_LAUNCHES)) return 0;
     const FwdTicket &a = g_tickets[tk[0]];
     for (int i = 0; i < V; i++) {
         const FwdTicket &t = g_tickets[tk[i]];
@@ -1314,7 +1324,7 @@ static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_
                 hist.busy = e.busy > hist.busy ? e.busy : hist.busy;
             }
     }
-    if (mode == 2 || (!(g_debug_flags & 1024u) && hist.R > 0)) {
+    if (mode == 2 || (!dbg(CSPLAT_DEBUG_NO_SPECULATION) && hist.R > 0)) {
         uint32_t Rcap[RASTER_MAX_VIEWS];
         uint32_t Lcap, Bcap;
         if (mode == 2) {        // the capacities the pending call was launched with
@@ -1441,12 +1451,12 @@ int csplat_forward_finish(int ticket, float *out_color, float *out_depth, int *n
     {
         ProfScope ps(PROF_K5, s);
         k_block_masks<<<cdiv((int64_t)R + 1, 256), 256, 0, s>>>((int64_t)R, cam.gx, b.keys_sorted, b.ids_sorted, g.pack, b.mask16, b.recA, b.recB,
-                                                                 b.recC, (g_debug_flags & (1u | 16u | 32u)) ? 0 : 1, b.bmask);
+                                                                 b.recC, dbg(DBG_NO_ELLIPSE_STAGE) ? 0 : 1, b.bmask);
         LAUNCH_CHECK();
     }
     {
         ProfScope ps(PROF_K6, s);
-        if (g_debug_flags & 32768u)       // (bit 15: the row form, four survivors a step; default: the survivor-column form, 74 -> 67 us alone)
+        if (dbg(CSPLAT_DEBUG_K6_ROWS))       // (bit 15: the row form, four survivors a step; default: the survivor-column form, 74 -> 67 us alone)
             k_composite_fwd<true><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, bg, b.seg_offset,
                                                                       b.ckpt, final_T, n_contrib, out_color, out_depth, b.bbits, b.bmask);
         else
@@ -1517,21 +1527,22 @@ static int launch_k8(hipStream_t k8s, const csplat_view &w, bool depth, float *c
 }
 
 // One view's backward: K7 on `s` (with_k7; false = the caller launched K7 of all views as one batch), K8 on `k8s` (with_k8; after an
-// event wait when the streams differ; false = the caller runs one K8 over all views afterwards).  accmask see k_preprocess_bwd.
-static int backward_impl(const csplat_view &w, hipStream_t s, hipStream_t k8s, bool with_k7, bool with_k8, bool depth_k8 = false,
-                         float *cam_slab = nullptr, int *cam_rows = nullptr) {
+// event wait when the streams differ; false = the caller runs one K8 over all views afterwards).  depth_k8 / cam_k8: K8's form (launch_k8).
+// A view without Gaussians has nothing to do, whatever else it lacks.  accmask see k_preprocess_bwd.
+static int backward_one(const csplat_view &w, ScratchPath path, hipStream_t s, hipStream_t k8s, bool with_k7, bool with_k8, bool depth_k8,
+                        bool cam_k8, int *cam_rows) {
+    if (w.P <= 0) return 0;
     CSPLAT_REQUIRE(w.geom && w.binning && w.image && w.out_color, "csplat_backward: missing saved state");
     CSPLAT_REQUIRE(w.dL_dmean2D && w.dL_dconic && w.dL_dopacity && w.dL_dcolor && w.dL_dmean3D && w.dL_dcov3D, "missing gradient outputs");
     CSPLAT_REQUIRE(w.scratch != nullptr, "csplat_backward: scratch (csplat_backward_scratch_bytes) missing");
     const int P = w.P, R = layout_R(w), tiles = tiles_of(w.W, w.H);
-    if (P <= 0) return 0;
+    const ScratchView sv = (with_k7 || cam_k8) ? scratch_view(w, path) : ScratchView{};
     if (with_k7) {
-        const bool det_mode = (g_debug_flags & 256u) != 0;
-        const BinView b = binning_view(w.binning, R, tiles);
         B2View k;
-        fill_b2_view(w, b, image_view(w.image, w.W, w.H), det_mode ? (float *)((char *)w.scratch + acc_bytes(P)) : nullptr, k);
-        if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, (size_t)(R > 0 ? R : 1) * 16 * 9 * 4, s));
-        else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(k.acc, 0, (size_t)P * ACC_STRIDE * 4, s));
+        DetView e;
+        fill_k7_view(w, sv, tiles, k, e);
+        if (sv.det) HIP_TRY(hipMemsetAsync(sv.det, 0, sv.det_bytes, s));
+        else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(sv.acc, 0, (size_t)P * ACC_STRIDE * 4, s));
         ProfScope ps(PROF_K7, s);
         if (R > 0) {
             const unsigned grid = (unsigned)cdiv(max_slots(R, tiles), 8) * 32u;
@@ -1539,13 +1550,11 @@ static int backward_impl(const csplat_view &w, hipStream_t s, hipStream_t k8s, b
                 kernel<<<grid, 256, 0, s>>>(tiles, w.W, w.H, cdiv(w.W, CSPLAT_TILE), k.ranges, k.ids_sorted, k.bbits, k.recA, k.recB, k.recC, k.R,
                                             k.seg_offset, k.slot_tile, k.ckpt, k.final_T, k.n_contrib, k.out_color, k.dL_dpix, k.acc, k.det);
             };
-            if (det_mode) go(k_composite_bwd_rows<true>);
+            if (sv.det) go(k_composite_bwd_rows<true>);
             else go(k_composite_bwd_rows<false>);
             LAUNCH_CHECK();
         }
-        if (det_mode) {   // fixed-order sum of every Gaussian's instance records (writes all of acc)
-            DetView e;
-            fill_det_view(w, b, k, e);
+        if (sv.det) {   // fixed-order sum of every Gaussian's instance records (writes all of acc)
             k_det_reduce<<<cdiv(P, 256), 256, 0, s>>>(P, e.cam, e.xy, e.depth, e.radii, e.ranges, e.keys_sorted, e.ids_sorted, e.det, e.acc);
             LAUNCH_CHECK();
         }
@@ -1557,45 +1566,7 @@ static int backward_impl(const csplat_view &w, hipStream_t s, hipStream_t k8s, b
         HIP_TRY(hipEventRecord(ev, s));
         HIP_TRY(hipStreamWaitEvent(k8s, ev, 0));
     }
-    return launch_k8(k8s, w, depth_k8, cam_slab, cam_rows);
-}
-
-// the arguments of the single-view C entry points as a csplat_view (everything else zero: no accumulation, no antialiasing, no extras)
-static csplat_view pack_view(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
-                             const float *colors_precomp, const float *scales, float scale_modifier, const float *rotations,
-                             const float *cov3D_precomp, const float *view, const float *proj, const float *campos, float tanfovx,
-                             float tanfovy, const int32_t *radii, const void *geom, const void *binning, const void *image,
-                             const float *out_color, const float *dL_dpix, void *scratch, float *dL_dmean2D, float *dL_dconic,
-                             float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
-                             float *dL_drot) {
-    csplat_view w;
-    memset(&w, 0, sizeof(w));
-    w.stream = stream;
-    w.P = P; w.D = D; w.M = M; w.W = W; w.H = H;
-    w.scale_modifier = scale_modifier; w.tanfovx = tanfovx; w.tanfovy = tanfovy;
-    w.bg = bg; w.means3D = means3D; w.shs = shs; w.colors_precomp = colors_precomp; w.scales = scales; w.rotations = rotations;
-    w.cov3D_precomp = cov3D_precomp; w.view = view; w.proj = proj; w.campos = campos;
-    w.out_color = const_cast<float *>(out_color); w.radii = const_cast<int32_t *>(radii);
-    w.num_rendered = R; w.layout_rendered = R;
-    w.geom = const_cast<void *>(geom); w.binning = const_cast<void *>(binning); w.image = const_cast<void *>(image);
-    w.dL_dpix = dL_dpix; w.scratch = scratch;
-    w.dL_dmean2D = dL_dmean2D; w.dL_dconic = dL_dconic; w.dL_dopacity = dL_dopacity; w.dL_dcolor = dL_dcolor; w.dL_dmean3D = dL_dmean3D;
-    w.dL_dcov3D = dL_dcov3D; w.dL_dsh = dL_dsh; w.dL_dscale = dL_dscale; w.dL_drot = dL_drot;
-    return w;
-}
-
-int csplat_backward(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
-                    const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
-                    const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
-                    const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
-                    const void *binning, const void *image, const float *out_color, const float *dL_dpix, void *scratch,
-                    float *dL_dmean2D,
-                    float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
-                    float *dL_dsh, float *dL_dscale, float *dL_drot) {
-    const csplat_view w = pack_view(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                    view, proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, scratch, dL_dmean2D,
-                                    dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
-    return backward_impl(w, (hipStream_t)stream, (hipStream_t)stream, true, true);
+    return launch_k8(k8s, w, depth_k8, cam_k8 ? sv.cam_slab : nullptr, cam_rows);
 }
 
 // ---- batched entry points: V independent views, one stream each, fenced against `join_stream`
@@ -1917,7 +1888,7 @@ static int forward_views_settle_impl(int V, csplat_view *v, void *join_stream, i
 // gradient output either the SAME buffer in all views (then views after the first must have been asked to add into it) or
 // a DIFFERENT buffer in every view.  Fills the table and returns true; anything else keeps the per-view launches.
 static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
-    if (V < 2 || V > RASTER_MAX_VIEWS || (g_debug_flags & 128u)) return false;
+    if (V < 2 || V > RASTER_MAX_VIEWS || dbg(CSPLAT_DEBUG_PER_VIEW_K8)) return false;
     const csplat_view &a = v[0];
     if (a.P <= 0 || a.cov3D_precomp || !a.shs || !a.dL_dsh || a.M != 16 || !a.scales || !a.rotations || !a.dL_dscale || !a.dL_drot ||
         ((((uintptr_t)a.shs | (uintptr_t)a.dL_dsh) & 15u) != 0))
@@ -1975,35 +1946,26 @@ static bool k8_views_table(int V, const csplat_view *v, K8Table &tab) {
     return true;
 }
 
-// csplat_backward_views cut into parts (round 6: the gradient exchange of a view-parallel step starts before the backward has ended).
-// parts bit 0: the compositing backward (K7) of all views; bit 1: the per-Gaussian backward (K8) for SLICE `slice` of `nslices` equal
-// ranges of Gaussians (boundaries at multiples of 32: csplat_backward_slice_rows) -- a caller launches K7 once, then the K8 slices one by
-// one, and may hand the gradient rows of slice g to its collective while slice g + 1 computes.  Only the one-launch-per-stage path can be
-// cut (the views share P, SH, scales and the image size, as csplat_forward_views_faith requires); parts == 3 with one slice is
-// csplat_backward_views.  The sum of the parts is the whole call bit for bit: every Gaussian's arithmetic is the same in any slicing.
-// The depth-gradient path (some view has dL_ddepth): every stage runs on the join stream -- clearing, the depth prepass, the depth K7 of
-// all views in one launch (views without a depth gradient take it with zero depth terms), the depth K8.  Every view's scratch is laid out
-// by csplat_backward_depth_scratch_bytes.  The default path (backward_views_impl below) is not entered.
 // ---- the camera-gradient path (ABI 8: csplat_view.dL_dview / dL_dproj / dL_dcampos / dL_dbg).  The compositing backward is the call's
 // own (default or depth); only K8 changes, to its CAM variant (when a view / projection / centre gradient is asked for), and two small
 // launches follow on the join stream, behind every view's K8: k_bg_partials (when a background gradient is asked for) and k_cam_sum.
 static bool cam_k8_wanted(const csplat_view &w) { return w.dL_dview || w.dL_dproj || w.dL_dcampos; }
-static float *cam_slab_of(const csplat_view &w) { return (float *)((char *)w.scratch + cam_slab_offset(w.P, layout_R(w), w.W, w.H)); }
-static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *rows) {
+static int cam_tail(int V, const csplat_view *v, ScratchPath path, hipStream_t join, const int *rows) {
     BgTable bt;
     CamSumTable ct;
     bool any_bg = false;
     for (int i = 0; i < V; i++) {
         const csplat_view &w = v[i];
+        const ScratchView sv = scratch_view(w, path);
         BgView &b = bt.v[i];
         b.slab = nullptr; b.final_T = nullptr; b.dL_dpix = w.dL_dpix; b.npix = w.W * w.H;
         if (w.dL_dbg && w.dL_dpix && w.scratch) {
             b.final_T = w.image ? image_view(w.image, w.W, w.H).final_T : nullptr;
-            b.slab = (float *)((char *)w.scratch + cam_bg_offset(w.P, layout_R(w), w.W, w.H));
+            b.slab = sv.bg_slab;
             any_bg = true;
         }
         CamSumView &c = ct.v[i];
-        c.slab = w.scratch ? cam_slab_of(w) : nullptr; c.rows = w.scratch ? rows[i] : 0;
+        c.slab = sv.cam_slab; c.rows = w.scratch ? rows[i] : 0;
         c.bg_slab = b.slab; c.bg_rows = b.slab ? BG_BLOCKS : 0;
         c.dL_dview = w.dL_dview; c.dL_dproj = w.dL_dproj; c.dL_dcampos = w.dL_dcampos; c.dL_dbg = w.dL_dbg;
     }
@@ -2020,14 +1982,14 @@ static int cam_tail(int V, const csplat_view *v, hipStream_t join, const int *ro
 // The batched K8 (k8_views_table filled `tab`) on the join stream: k_preprocess_bwd_views / _depth / _cam<DEPTH> / _aa<DEPTH, CAM>.  depth:
 // the call takes the depth / feature path; cam_k8: the camera form, one slab row per workgroup and view (cam_rows[i] = their number), whole
 // calls only; every other form runs the workgroups of slice `slice` of `nslices`.
-static int launch_k8_views(int V, const csplat_view *v, const K8Table &tab, bool depth, bool cam_k8, int slice, int nslices, hipStream_t join,
-                           int *cam_rows) {
+static int launch_k8_views(int V, const csplat_view *v, ScratchPath path, const K8Table &tab, bool depth, bool cam_k8, int slice, int nslices,
+                           hipStream_t join, int *cam_rows) {
     ProfScope ps(cam_k8 ? PROF_K8_CAM : depth ? PROF_K8_DEPTH : PROF_K8, join);
     const csplat_view &a = v[0];
     const int nb = cdiv(a.P, 32);
     const int b_lo = cam_k8 ? 0 : (int)((int64_t)nb * slice / nslices), b_hi = cam_k8 ? nb : (int)((int64_t)nb * (slice + 1) / nslices);
     CamSlabs sl{};       // (stays empty without cam_k8: the antialiased kernel takes the argument on every path)
-    for (int i = 0; i < V && cam_k8; i++) { sl.p[i] = cam_slab_of(v[i]); cam_rows[i] = nb; }
+    for (int i = 0; i < V && cam_k8; i++) { sl.p[i] = scratch_view(v[i], path).cam_slab; cam_rows[i] = nb; }
     if (b_hi <= b_lo) return 0;
     auto go = [&](auto kernel, auto... extra) {
         kernel<<<b_hi - b_lo, 128, 0, join>>>(a.P, a.D, a.M, a.shs, a.scales, a.scale_modifier, 0, a.dL_dsh, tab, b_lo, extra...);
@@ -2051,25 +2013,51 @@ static int launch_k8_views(int V, const csplat_view *v, const K8Table &tab, bool
     return 0;
 }
 
+// What the launches of a group of views depend on.  backward_views_impl sets, once per call, which gradients the CALL takes (cam: camera /
+// background at all, cam_k8: K8 in its camera form, feat: feature / alpha) and the scratch layout that follows (path); plan_group sets,
+// once per group, the rest: the parts wanted; `shared` = some view adds into another view's buffers, so every K8 runs on the join stream,
+// in view order; one_k8 = ONE K8 serves all views (tab).
+struct GroupPlan {
+    bool want_k7, want_k8, whole, shared, one_k8, det_mode, cam, cam_k8, feat;
+    ScratchPath path;
+    K8Table tab;
+};
+static void plan_group(int V, const csplat_view *v, unsigned parts, int nslices, GroupPlan &g) {
+    g.want_k7 = (parts & 1u) != 0; g.want_k8 = (parts & 2u) != 0; g.whole = parts == 3u && nslices == 1;
+    g.shared = false;
+    for (int i = 0; i < V; i++) g.shared |= (v[i].accmask & ~(unsigned)(CSPLAT_SCRATCH_ZEROED | CSPLAT_K8_OUTPUTS_UNREAD)) != 0u;
+    g.one_k8 = g.shared && k8_views_table(V, v, g.tab);
+    g.det_mode = dbg(CSPLAT_DEBUG_BIT_REPRODUCIBLE);
+}
+// the fixed-order sum of every Gaussian's (entry, block) records (bit-reproducible mode): one launch of `kernel` per view, in view order
+static int det_reduce_each(int V, const csplat_view *v, const DetTable &dt, void (*kernel)(int, DetTable), hipStream_t join) {
+    for (int i = 0; i < V; i++) {
+        if (v[i].P <= 0) continue;
+        DetTable one;
+        one.valid = nullptr;
+        one.v[0] = dt.v[i];
+        kernel<<<dim3((unsigned)cdiv(v[i].P, 256), 1), 256, 0, join>>>(v[i].P, one);
+        LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 static bool feat_wanted(const csplat_view &w) { return w.dL_dfeatures || w.dL_dalpha; }
-// earlier[0 .. n_earlier): the views of the call's earlier groups (backward_views_impl), whose dL_dfeat_in this group adds to
-static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigned parts, int slice, int nslices, bool cam = false,
-                                bool cam_k8 = false, bool feat = false, const csplat_view *earlier = nullptr, int n_earlier = 0) {
+// The depth-gradient path (some view has dL_ddepth) and the feature path (g.feat): every stage runs on the join stream -- clearing, the
+// prepass of depth / feature partials, the depth (feature) K7 of all views in one launch (views without a depth gradient take it with zero
+// depth terms), the depth K8.  earlier[0 .. n_earlier): the views of the call's earlier groups, whose dL_dfeat_in this group adds to.
+static int backward_views_depth(int V, csplat_view *v, hipStream_t join, GroupPlan &g, int slice, int nslices, const csplat_view *earlier,
+                                int n_earlier) {
     CSPLAT_REQUIRE(V <= RASTER_MAX_VIEWS, "csplat_backward_views: a depth, feature or alpha gradient is taken for at most 8 views per group");
     CSPLAT_REQUIRE(!v[0].valid, "csplat_backward_views: views launched on faith take no depth, feature or alpha gradient");
-    const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
-    CSPLAT_REQUIRE(!feat || whole, "csplat_backward_views_parts: feature / alpha gradients are taken by the whole call only");
-    bool shared = false;
-    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)(CSPLAT_SCRATCH_ZEROED | CSPLAT_K8_OUTPUTS_UNREAD)) != 0u;
-    K8Table tab;
-    const bool one_k8 = shared && k8_views_table(V, v, tab);
-    CSPLAT_REQUIRE(whole || one_k8, "csplat_backward_views_parts: only the one-launch-per-stage path can be cut into parts");
-    const bool det_mode = (g_debug_flags & 256u) != 0;
-    if (want_k7) {
+    CSPLAT_REQUIRE(!g.feat || g.whole, "csplat_backward_views_parts: feature / alpha gradients are taken by the whole call only");
+    CSPLAT_REQUIRE(g.whole || g.one_k8, "csplat_backward_views_parts: only the one-launch-per-stage path can be cut into parts");
+    const bool feat = g.feat, det_mode = g.det_mode;
+    if (g.want_k7) {
         DepthTable dtab;
         FeatTable ftab;
         ftab.n = V;
-        bool any_fgrad = false;
+        bool any_fgrad = false, any_depth = false;
         DetTable dt;
         dt.valid = nullptr;
         int64_t slots = 0;
@@ -2080,15 +2068,14 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             CSPLAT_REQUIRE(w.P <= 0 || (w.geom && w.binning && w.image && w.out_color && w.scratch && w.dL_dpix && w.radii),
                            "csplat_backward_views: missing saved state, scratch or dL_dpix");
             DepthView &d = dtab.v[i];
-            const int gx = cdiv(w.W, CSPLAT_TILE), tiles = tiles_of(w.W, w.H), Rl = layout_R(w);
-            const BinView b = binning_view(w.binning, Rl, tiles);
-            B2View &k = d.b;
-            fill_b2_view(w, b, image_view(w.image, w.W, w.H),
-                         !det_mode ? nullptr : (float *)((char *)w.scratch + (feat ? feat_det_offset(w.P, Rl, w.W, w.H) : acc_bytes(w.P))), k);
+            const int tiles = tiles_of(w.W, w.H);
+            const ScratchView sv = scratch_view(w, g.path);
+            fill_k7_view(w, sv, tiles, d.b, dt.v[i]);
             d.dL_ddepth = w.dL_ddepth;
-            d.dpart = (float *)((char *)w.scratch + depth_dpart_offset(w.P, Rl));
-            d.W = w.W; d.H = w.H; d.gx = gx;
+            d.dpart = sv.dpart;
+            d.W = w.W; d.H = w.H; d.gx = cdiv(w.W, CSPLAT_TILE);
             d.tiles = (w.P > 0 && w.num_rendered > 0) ? tiles : 0;
+            any_depth = any_depth || w.dL_ddepth;
             if (feat) {
                 CSPLAT_REQUIRE(w.n_features >= 0 && w.n_features <= CSPLAT_MAX_FEATURES &&
                                ((w.n_features == 0) == (w.features == nullptr) || (w.P <= 0 && w.features == nullptr)),
@@ -2097,7 +2084,7 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
                 FeatView &f = ftab.v[i];
                 f.d = d;
                 f.radii = w.radii; f.features = w.features; f.nf = w.n_features; f.dL_dfeat = w.dL_dfeatures; f.dL_dalpha = w.dL_dalpha;
-                f.wpart = (float *)((char *)w.scratch + feat_wpart_offset(w.P, Rl, w.W, w.H));
+                f.wpart = sv.wpart;
                 f.dL_dfeat_in = w.n_features > 0 ? w.dL_dfeat_in : nullptr; f.P = w.P; f.accmask = w.accmask;
                 for (int j = 0; j < n_earlier && f.dL_dfeat_in; j++)
                     if (earlier[j].n_features > 0 && earlier[j].dL_dfeat_in == f.dL_dfeat_in) f.accmask |= FEAT_ADD_IN;
@@ -2106,143 +2093,65 @@ static int backward_views_depth(int V, csplat_view *v, hipStream_t join, unsigne
             if (w.P <= 0) continue;
             Pmax = w.P > Pmax ? w.P : Pmax;
             // (the records start at zero: the bit-reproducible mode writes every one of them, CSPLAT_SCRATCH_ZEROED promises them)
-            if (det_mode) HIP_TRY(hipMemsetAsync(k.det, 0, feat ? feat_det_bytes(Rl) : depth_det_bytes(Rl), join));
-            else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(k.acc, 0, (size_t)w.P * ACC_STRIDE * 4, join));
-            if (det_mode) fill_det_view(w, b, k, dt.v[i]);
+            if (det_mode) HIP_TRY(hipMemsetAsync(sv.det, 0, sv.det_bytes, join));
+            else if (!(w.accmask & CSPLAT_SCRATCH_ZEROED)) HIP_TRY(hipMemsetAsync(sv.acc, 0, (size_t)w.P * ACC_STRIDE * 4, join));
             const int64_t sl = k7_slots(w, tiles);
             slots = sl > slots ? sl : slots;
         }
+        const unsigned items = (unsigned)cdiv(slots, 8) * 32u;
+        if (slots > 0 && (any_depth || !feat)) {
+            ProfScope ps(PROF_K7_DEPTH_PARTIALS, join);
+            k_depth_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(dtab);
+            LAUNCH_CHECK();
+        }
         if (feat) {
-            for (int i = 0; i < V; i++) ftab.v[i].d = dtab.v[i];
-            bool any_depth = false;
-            for (int i = 0; i < V; i++) any_depth = any_depth || v[i].dL_ddepth;
             if (slots > 0) {
-                if (any_depth) {
-                    ProfScope ps(PROF_K7_DEPTH_PARTIALS, join);
-                    k_depth_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(dtab);
-                    LAUNCH_CHECK();
-                }
                 if (any_fgrad) {
                     ProfScope ps(PROF_K7_FEAT_PARTIALS, join);
                     k_feature_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(ftab);
                     LAUNCH_CHECK();
                 }
                 ProfScope ps(PROF_K7_FEAT, join);
-                const unsigned items = (unsigned)cdiv(slots, 8) * 32u;
-                if (det_mode)
-                    k_feature_composite_bwd_views<true><<<dim3(items, V), 256, 0, join>>>(ftab);
-                else
-                    k_feature_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(ftab);
+                if (det_mode) k_feature_composite_bwd_views<true><<<dim3(items, V), 256, 0, join>>>(ftab);
+                else k_feature_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(ftab);
                 LAUNCH_CHECK();
             }
-            if (det_mode && Pmax > 0) {
-                for (int i = 0; i < V; i++) {
-                    if (v[i].P <= 0) continue;
-                    DetTable one;
-                    one.valid = nullptr;
-                    one.v[0] = dt.v[i];
-                    k_feature_det_reduce_views<<<dim3((unsigned)cdiv(v[i].P, 256), 1), 256, 0, join>>>(v[i].P, one);
-                    LAUNCH_CHECK();
-                }
-            }
+            if (det_mode)
+                if (int rc = det_reduce_each(V, v, dt, k_feature_det_reduce_views, join)) return rc;
             if (Pmax > 0) {     // the feature gradients leave the records before K8 reads (and may clear) them
                 ProfScope ps(PROF_FEAT_GRADS, join);
                 k_feature_grads<<<dim3((unsigned)cdiv(Pmax, 256), 1), 256, 0, join>>>(ftab);
                 LAUNCH_CHECK();
             }
-        } else if (slots > 0) {
-            {
-                ProfScope ps(PROF_K7_DEPTH_PARTIALS, join);
-                k_depth_bwd_partials<<<dim3((unsigned)slots, V), 256, 0, join>>>(dtab);
+        } else {
+            if (slots > 0) {
+                ProfScope ps(PROF_K7_DEPTH, join);
+                if (det_mode) k_depth_composite_bwd_views<true><<<dim3(items, V), 256, 0, join>>>(dtab);
+                else k_depth_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(dtab);
                 LAUNCH_CHECK();
             }
-            ProfScope ps(PROF_K7_DEPTH, join);
-            const unsigned items = (unsigned)cdiv(slots, 8) * 32u;
             if (det_mode)
-                k_depth_composite_bwd_views<true><<<dim3(items, V), 256, 0, join>>>(dtab);
-            else
-                k_depth_composite_bwd_views<false><<<dim3(items, V), 256, 0, join>>>(dtab);
-            LAUNCH_CHECK();
-        }
-        if (det_mode && Pmax > 0 && !feat) {
-            // (a view with fewer Gaussians: its rows past P are not visited -- the launch is sized for the largest view and guarded per view)
-            for (int i = 0; i < V; i++) {
-                if (v[i].P <= 0) continue;
-                DetTable one;
-                one.valid = nullptr;
-                one.v[0] = dt.v[i];
-                k_depth_det_reduce_views<<<dim3((unsigned)cdiv(v[i].P, 256), 1), 256, 0, join>>>(v[i].P, one);
-                LAUNCH_CHECK();
-            }
+                if (int rc = det_reduce_each(V, v, dt, k_depth_det_reduce_views, join)) return rc;
         }
     }
-    if (!want_k8) return 0;
+    if (!g.want_k8) return 0;
     int cam_rows[RASTER_MAX_VIEWS] = {0};
-    if (one_k8) {
-        if (int rc = launch_k8_views(V, v, tab, true, cam_k8, slice, nslices, join, cam_rows)) return rc;
+    if (g.one_k8) {
+        if (int rc = launch_k8_views(V, v, g.path, g.tab, true, g.cam_k8, slice, nslices, join, cam_rows)) return rc;
     } else {
         for (int i = 0; i < V; i++)       // per-view K8 on the join stream, in view order (views may add into one another's buffers)
-            if (int rc = backward_impl(v[i], join, join, false, true, v[i].dL_ddepth != nullptr, cam_k8 ? cam_slab_of(v[i]) : nullptr, &cam_rows[i]))
-                return rc;
+            if (int rc = backward_one(v[i], g.path, join, join, false, true, v[i].dL_ddepth != nullptr, g.cam_k8, &cam_rows[i])) return rc;
     }
-    return cam ? cam_tail(V, v, join, cam_rows) : 0;
+    return g.cam ? cam_tail(V, v, g.path, join, cam_rows) : 0;
 }
 
-static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices, bool cam, bool cam_k8);
-// The path (default, depth, feature; camera or not) is the call's.  A call of more than 8 views that takes the depth, feature or camera
-// path runs in groups of at most 8 views (view_group), one after the other on the join stream, each as a call of its own views would run:
-// every group writes or adds into the call's gradient buffers as the views' accmask says (an accumulating view of a later group adds to
-// what an earlier group wrote), dL_dfeat_in included.  A call of up to 8 views is one group: its launches are those of the ungrouped call.
-static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
-    CSPLAT_REQUIRE(V >= 0 && (V == 0 || v != nullptr), "csplat_backward_views: bad view count");
-    CSPLAT_REQUIRE(parts >= 1 && parts <= 3 && nslices >= 1 && slice >= 0 && slice < nslices, "csplat_backward_views_parts: bad parts / slice");
-    bool cam = false, cam_k8 = false;
-    for (int i = 0; i < V; i++) {
-        cam_k8 = cam_k8 || cam_k8_wanted(v[i]);
-        cam = cam || cam_k8_wanted(v[i]) || v[i].dL_dbg != nullptr;
-    }
-    if (cam) {
-        CSPLAT_REQUIRE(parts == 3u && nslices == 1, "csplat_backward_views_parts: camera / background gradients are taken by the whole call only");
-        CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no camera / background gradient");
-        for (int i = 0; i < V; i++)
-            CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: camera gradients need scratch of csplat_backward_camera_scratch_bytes");
-    }
-    for (int i = 0; i < V; i++)
-        CSPLAT_REQUIRE(!aa_of(v[i]) || v[i].opacities || v[i].P <= 0, "csplat_backward_views: CSPLAT_ANTIALIAS needs the view's opacities");
-    bool feat = false, depth = false;
-    for (int i = 0; i < V; i++) {
-        feat = feat || feat_wanted(v[i]);
-        depth = depth || v[i].dL_ddepth != nullptr;
-    }
-    if (feat) {
-        CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no feature or alpha gradient");
-        for (int i = 0; i < V; i++)
-            CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: feature / alpha gradients need scratch of csplat_backward_feature_scratch_bytes");
-    }
-    if (!feat && !depth && !cam) return backward_views_colour(V, v, join_stream, parts, slice, nslices, false, false);
-    for (int g = 0, ng = view_groups(V); g < ng; g++) {
-        int lo, hi;
-        view_group(V, g, &lo, &hi);
-        const int rc = (feat || depth) ? backward_views_depth(hi - lo, v + lo, (hipStream_t)join_stream, parts, slice, nslices, cam, cam_k8, feat,
-                                                              v, lo)
-                                       : backward_views_colour(hi - lo, v + lo, join_stream, parts, slice, nslices, cam, cam_k8);
-        if (rc) return rc;
-    }
-    return 0;
-}
-// the colour path (no view has a depth, feature or alpha gradient); cam / cam_k8: the call takes camera / background gradients
-static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices, bool cam, bool cam_k8) {
-    CSPLAT_REQUIRE(!cam || V <= RASTER_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per group");
+// the colour path (no view has a depth, feature or alpha gradient)
+static int backward_views_colour(int V, csplat_view *v, hipStream_t join, GroupPlan &g, int slice, int nslices) {
+    CSPLAT_REQUIRE(!g.cam || V <= RASTER_MAX_VIEWS, "csplat_backward_views: camera / background gradients are taken for at most 8 views per group");
     int cam_rows[RASTER_MAX_VIEWS] = {0};
-    const bool want_k7 = (parts & 1u) != 0, want_k8 = (parts & 2u) != 0, whole = parts == 3u && nslices == 1;
-    hipStream_t join = (hipStream_t)join_stream;
-    bool shared = false;   // any view adding into another view's buffers: all K8 run on the join stream, in view order
-    for (int i = 0; i < V; i++) shared |= (v[i].accmask & ~(unsigned)(CSPLAT_SCRATCH_ZEROED | CSPLAT_K8_OUTPUTS_UNREAD)) != 0u;
-    K8Table tab;
-    const bool one_k8 = shared && k8_views_table(V, v, tab);
+    const bool shared = g.shared, one_k8 = g.one_k8, det_mode = g.det_mode;
     // K7 of all views in ONE launch on the join stream (plus one launch clearing the records) when the views are alike
-    const bool det_mode = (g_debug_flags & 256u) != 0;
-    bool batch_k7 = V >= 2 && V <= RASTER_MAX_VIEWS && !(g_debug_flags & 512u);
+    bool batch_k7 = V >= 2 && V <= RASTER_MAX_VIEWS && !dbg(CSPLAT_DEBUG_PER_VIEW_LAUNCHES);
     for (int i = 0; i < V && batch_k7; i++)
         batch_k7 = v[i].P == v[0].P && v[i].P > 0 && v[i].W == v[0].W && v[i].H == v[0].H && v[i].num_rendered > 0 && v[i].geom &&
                    v[i].binning && v[i].image && v[i].out_color && v[i].scratch && v[i].dL_dpix;
@@ -2250,24 +2159,21 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
     // neither the entry nor the exit fence (six event / wait calls, ~25 us of host time per step)
     const bool lone = V == 1 && (hipStream_t)v[0].stream == join;      // one view on the caller's stream: nothing to fence
     const bool side_streams = !(batch_k7 && one_k8) && !lone;
-    CSPLAT_REQUIRE(whole || (batch_k7 && one_k8), "csplat_backward_views_parts: only the one-launch-per-stage path can be cut into parts");
+    CSPLAT_REQUIRE(g.whole || (batch_k7 && one_k8), "csplat_backward_views_parts: only the one-launch-per-stage path can be cut into parts");
     CSPLAT_REQUIRE(!(V > 0 && v[0].valid) || !side_streams, "csplat_backward_views: views launched on faith need the one-launch-per-stage path");
     if (side_streams)
         if (int rc = fence_in(V, v, join)) return rc;
     // from here on side streams may hold work on caller-owned buffers: whatever fails, the exit fence is still issued
     auto body = [&]() -> int {
-        if (batch_k7 && want_k7) {
+        if (batch_k7 && g.want_k7) {
             const int W = v[0].W, H = v[0].H, P = v[0].P, gx = cdiv(W, CSPLAT_TILE), tiles = tiles_of(W, H);
             B2Table bt;
             DetTable dt;
             dt.valid = v[0].valid;
             int64_t slots = 0;
             for (int i = 0; i < V; i++) {
-                const csplat_view &w = v[i];
-                const BinView b = binning_view(w.binning, layout_R(w), tiles);
-                fill_b2_view(w, b, image_view(w.image, W, H), det_mode ? (float *)((char *)w.scratch + acc_bytes(P)) : nullptr, bt.v[i]);
-                if (det_mode) fill_det_view(w, b, bt.v[i], dt.v[i]);
-                const int64_t sl = k7_slots(w, tiles);
+                fill_k7_view(v[i], scratch_view(v[i], g.path), tiles, bt.v[i], dt.v[i]);
+                const int64_t sl = k7_slots(v[i], tiles);
                 slots = sl > slots ? sl : slots;
             }
             {   // (measurement hook, off unless csplat_debug_stamps handed over a buffer large enough for this launch)
@@ -2297,11 +2203,11 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
         }
         for (int i = 0; i < V && !(batch_k7 && one_k8); i++) {
             const csplat_view &w = v[i];
-            if (int rc = backward_impl(w, (hipStream_t)w.stream, (shared || batch_k7) ? join : (hipStream_t)w.stream, !batch_k7, !one_k8, false,
-                                       cam_k8 ? cam_slab_of(w) : nullptr, &cam_rows[i]))
+            if (int rc = backward_one(w, g.path, (hipStream_t)w.stream, (shared || batch_k7) ? join : (hipStream_t)w.stream, !batch_k7, !one_k8,
+                                      false, g.cam_k8, &cam_rows[i]))
                 return rc;
         }
-        if (one_k8 && want_k8) {   // every view's K7 is queued on its own stream: the join stream waits for all of them, then ONE K8
+        if (one_k8 && g.want_k8) {   // every view's K7 is queued on its own stream: the join stream waits for all of them, then ONE K8
             for (int i = 0; i < V && !batch_k7; i++) {
                 if ((hipStream_t)v[i].stream == join) continue;
                 hipEvent_t ev = pooled_event();
@@ -2309,38 +2215,66 @@ static int backward_views_colour(int V, csplat_view *v, void *join_stream, unsig
                 HIP_TRY(hipEventRecord(ev, (hipStream_t)v[i].stream));
                 HIP_TRY(hipStreamWaitEvent(join, ev, 0));
             }
-            return launch_k8_views(V, v, tab, false, cam_k8, slice, nslices, join, cam_rows);
+            return launch_k8_views(V, v, g.path, g.tab, false, g.cam_k8, slice, nslices, join, cam_rows);
         }
         return 0;
     };
     const int rc = body();
     const int r2 = side_streams ? fence_out(V, v, join) : 0;
-    if (!rc && !r2 && cam) return cam_tail(V, v, join, cam_rows);     // (behind every view's K8: the exit fence has joined their streams)
+    if (!rc && !r2 && g.cam) return cam_tail(V, v, g.path, join, cam_rows);     // (behind every view's K8: the exit fence has joined their streams)
     return rc ? rc : r2;
 }
-int csplat_backward_views(int V, csplat_view *v, void *join_stream) { return backward_views_impl(V, v, join_stream, 3u, 0, 1); }
-// csplat_backward with the depth image's gradient: the one view goes through the depth path of the batched entry (NULL dL_ddepth = the
-// call is csplat_backward's)
-int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
-                          const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
-                          const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
-                          const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
-                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, const float *dL_ddepth,
-                          void *scratch, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot) {
-    if (!dL_ddepth)
-        return csplat_backward(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                               view, proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, scratch, dL_dmean2D,
-                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
-    CSPLAT_REQUIRE(scratch != nullptr, "csplat_backward_depth: scratch (csplat_backward_depth_scratch_bytes) missing");
-    CSPLAT_REQUIRE(dL_dmean2D && dL_dconic && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dcov3D, "missing gradient outputs");
-    if (P <= 0) return 0;
-    csplat_view w = pack_view(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, view,
-                              proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, scratch, dL_dmean2D, dL_dconic,
-                              dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
-    w.dL_ddepth = dL_ddepth;
-    return backward_views_depth(1, &w, (hipStream_t)stream, 3u, 0, 1);
+
+// The only way into the backward.  The path (colour, depth, feature; camera or not) is the call's.  A call of more than 8 views that takes
+// the depth, feature or camera path runs in groups of at most 8 views (view_group), one after the other on the join stream, each as a call
+// of its own views would run: every group writes or adds into the call's gradient buffers as the views' accmask says (an accumulating view
+// of a later group adds to what an earlier group wrote), dL_dfeat_in included.  A call of up to 8 views is one group: its launches are those
+// of the ungrouped call.  The colour path without camera gradients takes any number of views as one group.
+static int backward_views_impl(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
+    CSPLAT_REQUIRE(V >= 0 && (V == 0 || v != nullptr), "csplat_backward_views: bad view count");
+    CSPLAT_REQUIRE(parts >= 1 && parts <= 3 && nslices >= 1 && slice >= 0 && slice < nslices, "csplat_backward_views_parts: bad parts / slice");
+    GroupPlan g;
+    bool depth = false;
+    g.cam = g.cam_k8 = g.feat = false;
+    for (int i = 0; i < V; i++) {
+        g.cam_k8 = g.cam_k8 || cam_k8_wanted(v[i]);
+        g.cam = g.cam || cam_k8_wanted(v[i]) || v[i].dL_dbg != nullptr;
+        g.feat = g.feat || feat_wanted(v[i]);
+        depth = depth || v[i].dL_ddepth != nullptr;
+    }
+    if (g.cam) {
+        CSPLAT_REQUIRE(parts == 3u && nslices == 1, "csplat_backward_views_parts: camera / background gradients are taken by the whole call only");
+        CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no camera / background gradient");
+        for (int i = 0; i < V; i++)
+            CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: camera gradients need scratch of csplat_backward_camera_scratch_bytes");
+    }
+    for (int i = 0; i < V; i++)
+        CSPLAT_REQUIRE(!aa_of(v[i]) || v[i].opacities || v[i].P <= 0, "csplat_backward_views: CSPLAT_ANTIALIAS needs the view's opacities");
+    if (g.feat) {
+        CSPLAT_REQUIRE(!(V > 0 && v[0].valid), "csplat_backward_views: views launched on faith take no feature or alpha gradient");
+        for (int i = 0; i < V; i++)
+            CSPLAT_REQUIRE(v[i].scratch, "csplat_backward_views: feature / alpha gradients need scratch of csplat_backward_feature_scratch_bytes");
+    }
+    g.path = g.feat ? SP_FEATURE : g.cam ? SP_CAMERA : depth ? SP_DEPTH : SP_COLOUR;
+    hipStream_t join = (hipStream_t)join_stream;
+    for (int k = 0, ng = g.path == SP_COLOUR ? 1 : view_groups(V); k < ng; k++) {
+        int lo = 0, hi = V;
+        if (ng > 1) view_group(V, k, &lo, &hi);
+        plan_group(hi - lo, v + lo, parts, nslices, g);
+        const int rc = (g.feat || depth) ? backward_views_depth(hi - lo, v + lo, join, g, slice, nslices, v, lo)
+                                         : backward_views_colour(hi - lo, v + lo, join, g, slice, nslices);
+        if (rc) return rc;
+    }
+    return 0;
 }
+
+int csplat_backward_views(int V, csplat_view *v, void *join_stream) { return backward_views_impl(V, v, join_stream, 3u, 0, 1); }
+// csplat_backward_views cut into parts (round 6: the gradient exchange of a view-parallel step starts before the backward has ended).
+// parts bit 0: the compositing backward (K7) of all views; bit 1: the per-Gaussian backward (K8) for SLICE `slice` of `nslices` equal
+// ranges of Gaussians (boundaries at multiples of 32: csplat_backward_slice_rows) -- a caller launches K7 once, then the K8 slices one by
+// one, and may hand the gradient rows of slice g to its collective while slice g + 1 computes.  Only the one-launch-per-stage path can be
+// cut (the views share P, SH, scales and the image size, as csplat_forward_views_faith requires); parts == 3 with one slice is
+// csplat_backward_views.  The sum of the parts is the whole call bit for bit: every Gaussian's arithmetic is the same in any slicing.
 int csplat_backward_views_parts(int V, csplat_view *v, void *join_stream, unsigned parts, int slice, int nslices) {
     return backward_views_impl(V, v, join_stream, parts, slice, nslices);
 }
@@ -2351,6 +2285,56 @@ int csplat_backward_slice_rows(int P, int slice, int nslices, int64_t *row_lo, i
     const int64_t lo = nb * slice / nslices * 32, hi = nb * (slice + 1) / nslices * 32;
     *row_lo = lo < P ? lo : P; *row_hi = hi < P ? hi : P;
     return 0;
+}
+
+// ---- the single-view C entry points: their arguments as a csplat_view (everything else zero: no accumulation, no antialiasing, no extras),
+// then a call of one view on its own stream
+static csplat_view pack_view(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
+                             const float *colors_precomp, const float *scales, float scale_modifier, const float *rotations,
+                             const float *cov3D_precomp, const float *view, const float *proj, const float *campos, float tanfovx,
+                             float tanfovy, const int32_t *radii, const void *geom, const void *binning, const void *image,
+                             const float *out_color, const float *dL_dpix, const float *dL_ddepth, void *scratch, float *dL_dmean2D,
+                             float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
+                             float *dL_dscale, float *dL_drot) {
+    csplat_view w;
+    memset(&w, 0, sizeof(w));
+    w.stream = stream;
+    w.P = P; w.D = D; w.M = M; w.W = W; w.H = H;
+    w.scale_modifier = scale_modifier; w.tanfovx = tanfovx; w.tanfovy = tanfovy;
+    w.bg = bg; w.means3D = means3D; w.shs = shs; w.colors_precomp = colors_precomp; w.scales = scales; w.rotations = rotations;
+    w.cov3D_precomp = cov3D_precomp; w.view = view; w.proj = proj; w.campos = campos;
+    w.out_color = const_cast<float *>(out_color); w.radii = const_cast<int32_t *>(radii);
+    w.num_rendered = R; w.layout_rendered = R;
+    w.geom = const_cast<void *>(geom); w.binning = const_cast<void *>(binning); w.image = const_cast<void *>(image);
+    w.dL_dpix = dL_dpix; w.dL_ddepth = dL_ddepth; w.scratch = scratch;
+    w.dL_dmean2D = dL_dmean2D; w.dL_dconic = dL_dconic; w.dL_dopacity = dL_dopacity; w.dL_dcolor = dL_dcolor; w.dL_dmean3D = dL_dmean3D;
+    w.dL_dcov3D = dL_dcov3D; w.dL_dsh = dL_dsh; w.dL_dscale = dL_dscale; w.dL_drot = dL_drot;
+    return w;
+}
+int csplat_backward(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                    const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                    const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
+                    const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
+                    const void *binning, const void *image, const float *out_color, const float *dL_dpix, void *scratch,
+                    float *dL_dmean2D,
+                    float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                    float *dL_dsh, float *dL_dscale, float *dL_drot) {
+    return csplat_backward_depth(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                 view, proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, nullptr, scratch,
+                                 dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+}
+// csplat_backward with the depth image's gradient (NULL dL_ddepth = the call is csplat_backward's: the colour path)
+int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                          const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                          const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
+                          const float *campos, float tanfovx, float tanfovy, const int32_t *radii, const void *geom,
+                          const void *binning, const void *image, const float *out_color, const float *dL_dpix, const float *dL_ddepth,
+                          void *scratch, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot) {
+    csplat_view w = pack_view(stream, P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, view,
+                              proj, campos, tanfovx, tanfovy, radii, geom, binning, image, out_color, dL_dpix, dL_ddepth, scratch, dL_dmean2D,
+                              dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+    return backward_views_impl(1, &w, stream, 3u, 0, 1);
 }
 
 }  // extern "C"

@@ -397,15 +397,15 @@ class _View:
         self.alloc = None
 
     def backward(self, grad_color, saved, grad_depth=None, cam_need=None):
-        """K7 + K8 on the CURRENT stream; returns the per-input gradients in the Function's argument order.  grad_depth None: the
-        colour-only call (csplat_backward); else the depth path (csplat_backward_depth), where a missing grad_color counts as zero.
-        cam_need: which of (viewmatrix, projmatrix, campos, bg) want a gradient -- any does: the camera path, csplat_backward_views with
-        this one view (it takes the chunks csplat_forward_finish leaves), and a second tuple of the four camera gradients is returned."""
+        """K7 + K8 on the CURRENT stream: csplat_backward_views with this one view (it takes the chunks csplat_forward_finish leaves).
+        Returns the per-input gradients in the Function's argument order.  grad_depth None: the colour path; else the depth path, where
+        a missing grad_color counts as zero.  cam_need: which of (viewmatrix, projmatrix, campos, bg) want a gradient -- any does: the
+        camera path, and a second tuple of the four camera gradients is returned."""
         means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = saved
-        rs, dev, P, M = self.rs, self.dev, self.P, self.M
+        dev, P, M = self.dev, self.P, self.M
         if grad_color is None:
             grad_color = torch.zeros(3, self.H, self.W, dtype=torch.float32, device=dev)
-        grad_color = _f32c_grad(grad_color, dev)
+        grad_color, grad_depth = _f32c_grad(grad_color, dev), _f32c_grad(grad_depth, dev)
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         d_mean2D, d_conic, d_opac, d_color = new(P, 3), new(P, 4), new(P, 1), new(P, 3)
         d_mean3D, d_cov3D = new(P, 3), new(P, 6)
@@ -414,39 +414,27 @@ class _View:
         d_rot = new(P, 4) if rotations is not None else None
         grads = (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
                  d_cov3D if cov3Ds_precomp is not None else None)
-        if cam_need is not None and any(cam_need):
-            grad_depth = _f32c_grad(grad_depth, dev)
-            scratch = new(max(int(_n.lib.csplat_backward_camera_scratch_bytes(P, self.num_rendered, self.W, self.H)), 256) // 4 + 1)
-            cam_out = _cam_outputs(cam_need, dev)
-            w = _n.CsplatView()
-            self.fill(w, _n.stream_handle(dev), (means3D, sh, colors_precomp, None, scales, rotations, cov3Ds_precomp, color, radii))
-            w.dL_dpix, w.dL_ddepth, w.scratch = _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch)
-            w.dL_dmean2D, w.dL_dconic, w.dL_dopacity, w.dL_dcolor = _n.ptr(d_mean2D), _n.ptr(d_conic), _n.ptr(d_opac), _n.ptr(d_color)
-            w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh = _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh)
-            w.dL_dscale, w.dL_drot = _n.ptr(d_scale), _n.ptr(d_rot)
-            for f, g in zip(_CAM_FIELDS, cam_out):
-                setattr(w, f, _n.ptr(g))
-            with _n.on_device(dev):
-                rc = _n.lib.csplat_backward_views(1, C.addressof(w), w.stream)
-            _n.check(rc, "csplat_backward_views")
-            return grads, cam_out
-        # csplat_backward and csplat_backward_depth: one argument list, the depth entry takes dL_ddepth in front of the scratch
-        head = [_n.stream_handle(dev), P, int(rs.sh_degree), M, self.num_rendered, _n.ptr(self.bg), self.W, self.H,
-                _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp), _n.ptr(scales), float(rs.scale_modifier),
-                _n.ptr(rotations), _n.ptr(cov3Ds_precomp), _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos),
-                float(rs.tanfovx), float(rs.tanfovy), _n.ptr(radii), *(_n.ptr(c) for c in self.chunks), _n.ptr(color), _n.ptr(grad_color)]
-        outs = [_n.ptr(g) for g in (d_mean2D, d_conic, d_opac, d_color, d_mean3D, d_cov3D, d_sh, d_scale, d_rot)]
-        if grad_depth is not None:
-            entry, grad_depth = "csplat_backward_depth", _f32c_grad(grad_depth, dev)
+        cam = cam_need is not None and any(cam_need)
+        if cam:
+            nbytes = _n.lib.csplat_backward_camera_scratch_bytes(P, self.num_rendered, self.W, self.H)
+        elif grad_depth is not None:
             nbytes = _n.lib.csplat_backward_depth_scratch_bytes(P, self.num_rendered, self.W, self.H)
-            head.append(_n.ptr(grad_depth))
         else:
-            entry, nbytes = "csplat_backward", _n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)
+            nbytes = _n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)
         scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        w = _n.CsplatView()
+        self.fill(w, _n.stream_handle(dev), (means3D, sh, colors_precomp, None, scales, rotations, cov3Ds_precomp, color, radii))
+        w.dL_dpix, w.dL_ddepth, w.scratch = _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch)
+        w.dL_dmean2D, w.dL_dconic, w.dL_dopacity, w.dL_dcolor = _n.ptr(d_mean2D), _n.ptr(d_conic), _n.ptr(d_opac), _n.ptr(d_color)
+        w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh = _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh)
+        w.dL_dscale, w.dL_drot = _n.ptr(d_scale), _n.ptr(d_rot)
+        cam_out = _cam_outputs(cam_need, dev) if cam else ()
+        for f, g in zip(_CAM_FIELDS, cam_out):
+            setattr(w, f, _n.ptr(g))
         with _n.on_device(dev):
-            rc = getattr(_n.lib, entry)(*head, _n.ptr(scratch), *outs)
-        _n.check(rc, entry)
-        return grads
+            rc = _n.lib.csplat_backward_views(1, C.addressof(w), w.stream)
+        _n.check(rc, "csplat_backward_views")
+        return (grads, cam_out) if cam else grads
 
     def saved(self):
         return _SAVED_OF(self)
@@ -498,7 +486,7 @@ K8_OUTPUTS_UNREAD = 512    # csplat.h: CSPLAT_K8_OUTPUTS_UNREAD
 
 def _acc_scratch(dev, P, slot):
     """(tensor, True) = the persistent zeroed records of `slot`; (None, False) in the bit-reproducible mode (its scratch is laid out per call)"""
-    if int(_n.lib.csplat_debug_flags_query()) & 256:
+    if int(_n.lib.csplat_debug_flags_query()) & _n.DEBUG_BIT_REPRODUCIBLE:
         return None, False
     key = (dev.index, _n.scratch_stream(dev), int(P), int(slot))
     buf = _ACC_SCRATCH.get(key)
@@ -931,7 +919,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             if arrived[what] and where[place]:
                 raise RuntimeError(message)
         plan, ctx.plan = ctx.plan, None                         # (one use: the buffers are handed to autograd)
-        if plan is not None and plan["acc"] and (int(_n.lib.csplat_debug_flags_query()) & 256):
+        if plan is not None and plan["acc"] and (int(_n.lib.csplat_debug_flags_query()) & _n.DEBUG_BIT_REPRODUCIBLE):
             _n.grad_release(plan["sinks"])                      # (the bit-reproducible mode was switched on after the forward: its scratch
             plan = None                                         #  has another layout -- plan again)
         if plan is None or plan["active"] != active:            # a view's image went unused, or a second backward pass

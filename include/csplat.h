@@ -69,6 +69,18 @@ int csplat_abi_version(void);
  * Bits 13, 14, 16-21 selected the shelved kernel forms of round 3 (K7 survivor columns, retire-waves flush, K6 items per wave / tile order,
  * block masks by blockIdx.y); those forms left the library in round 4 (history: commit 809fd4b) and the bits are
  * ignored.  The word is process-global and meant to be set between calls, not concurrently with them. */
+#define CSPLAT_DEBUG_NO_CULLING 1u             /* bit 0 */
+#define CSPLAT_DEBUG_GLOBAL_SORT 2u            /* bit 1 */
+#define CSPLAT_DEBUG_NO_MAILBOX 4u             /* bit 2 */
+#define CSPLAT_DEBUG_CULL_RADIUS_X4 16u        /* bit 4 */
+#define CSPLAT_DEBUG_CIRCLE_ONLY 32u           /* bit 5 */
+#define CSPLAT_DEBUG_PER_VIEW_K8 128u          /* bit 7 */
+#define CSPLAT_DEBUG_BIT_REPRODUCIBLE 256u     /* bit 8 */
+#define CSPLAT_DEBUG_PER_VIEW_LAUNCHES 512u    /* bit 9 */
+#define CSPLAT_DEBUG_NO_SPECULATION 1024u      /* bit 10 */
+#define CSPLAT_DEBUG_SORT_RADIX_ONLY 2048u     /* bit 11 */
+#define CSPLAT_DEBUG_SORT_RADIX_FALLBACK 4096u /* bit 12 */
+#define CSPLAT_DEBUG_K6_ROWS 32768u            /* bit 15 */
 int csplat_debug_flags(unsigned flags);
 unsigned csplat_debug_flags_query(void);
 /* measurement hook (not part of the operator interface): a device buffer the batched compositing backward fills with s_memtime stamps,
