@@ -897,3 +897,47 @@ def test_captured_train_step_rerecords_after_a_scratch_eviction():
     m = captured_atomic_metrics(eager, cap)
     for k, v in m.items():
         assert v <= cal["bars"][k], (k, v, cal["bars"][k], m)
+
+
+def _all_terms_step(on):
+    """step 1 from `_captured_fixture()` with the opacity logits lowered by 1 (off the targets) and cameras that carry `depth` and
+    `silhouette` (from a render of the unperturbed model: Z = D / A where A > 0.5, else a hole; S = A > 0.5) and `points` (500 of the
+    camera's deformed centres + noise), in the bit-reproducible mode; every optional term on, or all of them off"""
+    from types import SimpleNamespace
+    from csplat import train as tr
+    from gaussian_renderer import render_views
+    weights = dict(lambda_depth=0.2, lambda_silhouette=0.5, lambda_chamfer=0.7, lambda_isometric=1.0, lambda_spring=0.5, lambda_rigidity=0.3)
+    with _reproducible_k7():
+        pc, sim, mopt, cams, bg = _captured_fixture()
+        gen = torch.Generator().manual_seed(5)
+        with torch.no_grad():
+            res, alphas = render_views(cams, pc, sim, tr.DEFAULT_PIPE, bg, return_alpha=True)
+            for cam, r, a in zip(cams, res, alphas):
+                cam.depth = torch.where(a > 0.5, r.depth / a.clamp_min(1e-6), torch.zeros_like(a))
+                cam.silhouette = (a > 0.5).float()
+                m = r.means3D_deform.detach().cpu()
+                pick = torch.randperm(m.shape[0], generator=gen)[:500]
+                cam.points = (m[pick] + 0.02 * torch.randn(500, 3, generator=gen)).cuda().contiguous()
+            pc._opacity.sub_(1.0)
+        opt = SimpleNamespace(**vars(tr.DEFAULT_OPT), **(dict(weights, k_nearest=5) if on else {}))
+        _ps, loss, stats = tr.train_step(1, cams, pc, sim, mopt, opt=opt, background=bg)
+        torch.cuda.synchronize()
+    return weights, float(loss), {k: float(v) for k, v in stats.items() if k.endswith("_loss")}
+
+
+def test_train_step_with_every_optional_term_adds_their_weighted_parts():
+    """Depth, silhouette, Chamfer and the three kNN-graph regularisers in ONE step (P = 4000, 160 x 128, three cameras): the loss equals
+    the loss of the same step with every term off plus sum weight * part, formed in float64 from the reported float32 parts, within
+    8 float32 ulps of the largest magnitude among the plain loss and the weighted parts -- at most seven float32 roundings of half an ulp
+    on the way (a product and a sum per part, the fused kernels' sums with `add`), doubled.  Every term's stats key is present.
+    Seen on an MI355X: plain 6.92e-3, with the terms 1.178e-2, difference 1.6e-10 against a bar of 3.7e-9."""
+    _w, plain, none = _all_terms_step(on=False)
+    weights, loss, parts = _all_terms_step(on=True)
+    assert none == {}
+    assert sorted(parts) == ["chamfer_loss", "depth_loss", "isometric_loss", "rigidity_loss", "silhouette_loss", "spring_loss"]
+    weighted = {k: weights["lambda_" + k[:-5]] * v for k, v in parts.items()}
+    expect = plain + sum(weighted.values())
+    bar = 8 * float(np.spacing(np.float32(max([abs(plain)] + [abs(v) for v in weighted.values()]))))
+    print(f"plain {plain!r} with the terms {loss!r} expected {expect!r} difference {loss - expect:.3e} bar {bar:.3e} parts {parts}")
+    assert all(v >= 0.0 and np.isfinite(v) for v in parts.values()) and parts["depth_loss"] > 0 and parts["chamfer_loss"] > 0
+    assert abs(loss - expect) <= bar, (loss, expect, bar)
