@@ -1,7 +1,7 @@
 // Body of the batched per-Gaussian backward (K8 of csplat_backward_views), included by csplat_raster.hip into k_preprocess_bwd_views
 // (DEPTH = false), k_preprocess_bwd_views_depth (DEPTH = true), k_preprocess_bwd_views_cam (CAM = true) and k_preprocess_bwd_views_aa
 // (AA = true: antialiasing, see preprocess_bwd_body).  Not a standalone header: it expects the kernels' parameters, constexpr bools DEPTH,
-// CAM, AA and UNREAD (the caller reads no dL_dconic / dL_dcolor / dL_dcov3D, known at compile time: the default kernel's second
+// CAM, AA, STAMP (with an `unsigned long long *stamp_buf`) and UNREAD (the caller reads no dL_dconic / dL_dcolor / dL_dcov3D, known at compile time: the default kernel's second
 // instantiation, which then drops their nine running sums from the view loop), a `const CamSlabs *cam_slabs` and a `const float *aa_opacities` (the raw opacities when AA) in scope.
     constexpr bool STAGE = true;
     if (tab.valid && *tab.valid == 0u) return;
@@ -25,11 +25,45 @@
     const int gi = threadIdx.x / VL, vl = threadIdx.x % VL;
     const int i = bx * NG + gi;
     const int rows = min(NG, P - bx * NG);
-    if (STAGE) {
-        stage_sh_rows<NT>(shs + (size_t)bx * NG * 48, rows, s_in);
-        __syncthreads();
-    }
-    if (i < P) {
+    if (tab.n <= 0) return;
+    // (STAMP: k_preprocess_bwd_views_stamps, see StampMark -- words 0..5 of the workgroup's 8 = entry, behind the staging barrier, the record
+    //  arrived, the conic arrived, the last of the visible branch's inputs arrived, the last store issued; the last four where thread 0 got there)
+    auto mark = [&](int k, float dep) {
+        if constexpr (STAMP) StampMark{stamp_buf + (size_t)bx * 8}(k, dep);
+    };
+    mark(0, 0.f);
+    // ---- Every global load of the lane's first view is issued here, unconditionally and in front of the SH staging loads: all of a wave's
+    // loads travel in ONE memory round trip.  (Read where they are used -- the staging barrier, then the radius and the record, then the conic
+    // behind the radius, then the visible branch's means3D / cov3D / clamped / rotations / scales -- they were four dependent round trips.)
+    // Visibility only SELECTS among what arrived: a culled Gaussian's values are never used, so its gradients stay exactly 0 whatever was
+    // loaded.  A lane past P requests the last Gaussian's values, a lane without a view (V < 4) the last view's: valid addresses, dropped.
+    struct ViewIn {
+        float4 co;      // g.conic_opacity[i]
+        float c6[6];    // g.cov3D[6 i ..]
+        float p[3];     // means3D[3 i ..]
+        uint32_t cl;    // g.clamped[i]                 (read only when the SH gradient is wanted)
+        float q[4];     // rotations[4 i ..]            (read only when the view's pointer is set and cov3D is not precomputed)
+    };
+    const bool want_sh = shs && dL_dsh;
+    // (the view's pointers are read from the table first, all of them, and no load below is conditional: a pointer fetched or a branch taken
+    //  between two of these loads would make the later one wait for the earlier.  Where the rotations are not read -- no pointer, or a
+    //  precomputed cov3D -- the four words come from the start of the conic array, which is always there, and are never used.)
+    auto load_view_inputs = [&](const K8View &w_, int i_, ViewIn &o) {
+        const float4 *co_ = w_.g.conic_opacity;
+        const float *c6_ = w_.g.cov3D, *m3_ = w_.means3D, *rot_ = w_.rotations;
+        const uint32_t *cl_ = w_.g.clamped;
+        const bool rot_ok = !use_precomp_cov && rot_;
+        const float *rp_ = rot_ok ? rot_ : reinterpret_cast<const float *>(co_);
+        const int ri_ = rot_ok ? 4 * i_ : 0;
+        o.co = co_[i_];
+#pragma unroll
+        for (int k = 0; k < 6; k++) o.c6[k] = c6_[6 * i_ + k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) o.p[k] = m3_[3 * i_ + k];
+        o.cl = cl_[i_];
+#pragma unroll
+        for (int k = 0; k < 4; k++) o.q[k] = rp_[ri_ + k];
+    };
     float L_op = 0.f, L_col[3] = {0.f, 0.f, 0.f}, L_m3[3] = {0.f, 0.f, 0.f}, L_c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float L_sc[3] = {0.f, 0.f, 0.f}, L_rt[4] = {0.f, 0.f, 0.f, 0.f};
     // the per-view record (radius, the nine accumulated pixel-level gradients) of view vi+1 is requested while view vi is
@@ -47,17 +81,41 @@
     // what the SH gradient of this lane's FIRST view (views 0..3) is formed from after the loop: direction, dRGB (0 where clamped); all
     // zero for a view that is culled or absent.  A second view's (4..7) six values go to the quad's own row of s_in: see below.
     float e0[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (vl < tab.n) {
-        vis_n = tab.v[vl].radii[i] > 0;
-        load_record(tab.v[vl].acc, i, a9_n, dz_n);
-        if (vis_n && (tab.v[vl].accmask & CSPLAT_SCRATCH_ZEROED)) clear_record(tab.v[vl].acc, i);
+    ViewIn in;                                           // the other inputs of the view in hand
+    const int il = min(i, P - 1);
+    const int v0 = min(vl, tab.n - 1);
+    const int32_t *radii0 = tab.v[v0].radii;
+    const float *acc0 = tab.v[v0].acc;
+    const unsigned accmask0 = tab.v[v0].accmask;
+    load_view_inputs(tab.v[v0], il, in);
+    vis_n = radii0[il] > 0;
+    load_record(acc0, il, a9_n, dz_n);
+    // the scales (and the raw opacity when AA) are the same in every view
+    float sc3[3];
+    {
+        const bool sc_ok = !use_precomp_cov && scales;
+        const float *sp = sc_ok ? scales : reinterpret_cast<const float *>(tab.v[v0].g.conic_opacity);
+        const int si = sc_ok ? 3 * il : 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) sc3[k] = sp[si + k];
     }
+    float aa_o = 0.f;
+    if constexpr (AA) aa_o = aa_opacities[il];
+    (void)aa_o;
+    if (STAGE) {
+        // (the barrier cannot sit inside the divergent visible branch where s_in is first read: it stands here, behind every request)
+        stage_sh_rows_batched<NT, NG>(shs + (size_t)bx * NG * 48, rows, s_in);
+        __syncthreads();
+    }
+    mark(1, 0.f);
+    if (i < P) {
+    vis_n = vis_n && vl < tab.n;
+    if (vis_n && (accmask0 & CSPLAT_SCRATCH_ZEROED)) clear_record(acc0, i);
     for (int vi = vl; vi < tab.n; vi += VL) {
     const K8View &w = tab.v[vi];
     const Cam cam = w.cam;
-    const Geom g = w.g;
     const int32_t *radii = w.radii;
-    const float *acc = w.acc, *means3D = w.means3D, *rotations = w.rotations;
+    const float *acc = w.acc;
     float *dL_dmean2D = w.dL_dmean2D, *dL_dconic = w.dL_dconic, *dL_dopacity = w.dL_dopacity, *dL_dcolor = w.dL_dcolor;
     float *dL_dmean3D = w.dL_dmean3D, *dL_dcov3D = w.dL_dcov3D, *dL_dscale = w.dL_dscale, *dL_drot = w.dL_drot;
     const unsigned accmask = w.accmask;
@@ -68,8 +126,9 @@
 #pragma unroll
     for (int k = 0; k < 9; k++) a9[k] = vis ? a9_n[k] : 0.f;
     const float dz = vis ? dz_n : 0.f;
-    // (the view's conic + opacity are not requested ahead: four registers across the body that the one-round case, V <= 4, would pay too)
-    moments_to_gradients(a9, vis ? g.conic_opacity[i] : make_float4(0.f, 0.f, 0.f, 0.f));
+    mark(2, a9_n[8]);
+    mark(3, in.co.w);
+    moments_to_gradients(a9, vis ? in.co : make_float4(0.f, 0.f, 0.f, 0.f));
     a9[0] *= (float)cam.W; a9[1] *= (float)cam.H;      // (see k_preprocess_bwd)
     if (vi + VL < tab.n) {
         const K8View &wn = tab.v[vi + VL];
@@ -103,7 +162,7 @@
             for (int k = 0; k < 4; k++) PUTL(L_rt[k], dL_drot, 4 * i + k, 0.f, CSPLAT_ACC_ROT);
         if constexpr (CAM) cam_partials_zero(crow);
     } else {
-    const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
+    const float p[3] = {in.p[0], in.p[1], in.p[2]};
     const float *view = cam.view, *proj = cam.proj;
 
     // ---- conic -> cov2D -> cov3D and view-space mean
@@ -114,14 +173,14 @@
         proj_jacobian(pv, cam, pj);
         float c6[6];
 #pragma unroll
-        for (int k = 0; k < 6; k++) c6[k] = g.cov3D[6 * i + k];
+        for (int k = 0; k < 6; k++) c6[k] = in.c6[k];
         float a, b, c;
         float aa_ga = 0.f, aa_gb = 0.f, aa_gc = 0.f;     // (AA) o dL/do' dh/d(a0, b, c0)
         if constexpr (AA) {
             float a0, c0;
             cov2d_undilated(c6, pj, a0, b, c0);
             a = a0 + AA_DILATE; c = c0 + AA_DILATE;
-            const float h = aa_backward(a0, b, c0, aa_opacities[i] * a9[5], aa_ga, aa_gb, aa_gc);
+            const float h = aa_backward(a0, b, c0, aa_o * a9[5], aa_ga, aa_gb, aa_gc);
             PUTL(L_op, dL_dopacity, i, h * a9[5], CSPLAT_ACC_OPACITY);
         } else {
             cov2d_from_cov3d(c6, pj, a, b, c);
@@ -184,9 +243,9 @@
     }
     if constexpr (CAM) { crow[32] = 0.f; crow[33] = 0.f; crow[34] = 0.f; }
     // ---- colour -> SH (+ view direction -> mean3D)
-    if (shs && dL_dsh) {
+    if (want_sh) {
         const float *sh = (const float *)(s_in + gi * SH_ROW);
-        const uint32_t cl = g.clamped[i];
+        const uint32_t cl = in.cl;
         const float vx = p[0] - cam.campos[0], vy = p[1] - cam.campos[1], vz = p[2] - cam.campos[2];
         const float sum2 = vx * vx + vy * vy + vz * vz;
         const float len = sqrtf(sum2);
@@ -241,10 +300,11 @@
 
     // ---- cov3D -> scale, quaternion
     if (!use_precomp_cov && dL_dscale && dL_drot) {
-        const float q[4] = {rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]};
+        const float q[4] = {in.q[0], in.q[1], in.q[2], in.q[3]};
         float R[3][3];
         quat_to_rot(q, R);
-        const float s[3] = {scale_mod * scales[3 * i], scale_mod * scales[3 * i + 1], scale_mod * scales[3 * i + 2]};
+        const float s[3] = {scale_mod * sc3[0], scale_mod * sc3[1], scale_mod * sc3[2]};
+        mark(4, s[2]);
         const float dS[3][3] = {{g6[0], 0.5f * g6[1], 0.5f * g6[2]},
                                 {0.5f * g6[1], g6[3], 0.5f * g6[4]},
                                 {0.5f * g6[2], 0.5f * g6[4], g6[5]}};
@@ -282,6 +342,8 @@
 #pragma unroll
         for (int k = 0; k < 6; k++) s_in[gi * SH_ROW + vl * 6 + k] = e[k];
     }
+    // (V > 4) the lane's next view: its record was requested above; its other inputs go out here in one batch, behind this view's stores
+    if (vi + VL < tab.n) load_view_inputs(tab.v[vi + VL], i, in);
     }   // views
     __builtin_amdgcn_wave_barrier();
     if (VL == 4) {   // the four lanes' sums over their views: ((v0 + v1) + (v2 + v3)) in every lane
@@ -378,6 +440,7 @@
 #undef PUTS
     }
     }   // i < P
+    mark(5, 0.f);
     if constexpr (CAM)   // (every view of the call: each lane with i < P has written its rows of all the views it holds)
         for (int vi = 0; vi < tab.n; vi++) cam_block_sum<NT>(s_cam + vi * NG * CAM_NC, rows, s_cpart, cam_slabs->p[vi] + (size_t)bx * CAM_NC);
 #undef PUTL

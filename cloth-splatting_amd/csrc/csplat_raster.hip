@@ -807,6 +807,11 @@ bool mail_init() {
 
 unsigned long long *g_stamp_buf = nullptr;     // csplat_debug_stamps: 12 u64 per K7 workgroup (rows form, batched launch)
 size_t g_stamp_words = 0;
+// ... or, when the buffer holds EXACTLY 8 u64 per workgroup of the batched K1 (P / 64) and, behind them, of the batched K8 (P / 32): those
+// two kernels' stamps (k_preprocess_views_stamps, k_preprocess_bwd_views_stamps; tools/per_gaussian_stamps.py) and not K7's
+unsigned long long *per_gaussian_stamps(int P) {
+    return (g_stamp_buf && g_stamp_words == 8u * ((size_t)cdiv(P, 64) + (size_t)cdiv(P, 32))) ? g_stamp_buf : nullptr;
+}
 
 // `mode` argument of the tile sort kernels: bit 0 ids < 2^24, bit 1 radix only, bit 2 fallback limit 1
 int tsort_mode(int P) { return (P < (1 << 24) ? 1 : 0) | (dbg(CSPLAT_DEBUG_SORT_RADIX_ONLY) ? 2 : 0) | (dbg(CSPLAT_DEBUG_SORT_RADIX_FALLBACK) ? 4 : 0); }
@@ -1046,6 +1051,9 @@ static int begin_launch_views(int V, const int *tk, hipStream_t join) {
         else if (a.aa)
             k_preprocess_views_aa<false><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
                                                                          nocull_mode());
+        else if (stage && per_gaussian_stamps(P))
+            k_preprocess_views_stamps<<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
+                                                                      nocull_mode(), per_gaussian_stamps(P));
         else if (stage)
             k_preprocess_views<true><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
                                                                      nocull_mode());
@@ -2006,7 +2014,8 @@ static int launch_k8_views(int V, const csplat_view *v, ScratchPath path, const 
         go(k_preprocess_bwd_views_depth<128, 4>);
     } else {
         // (the flagship form: with every view's CSPLAT_K8_OUTPUTS_UNREAD the three outputs' running sums leave the registers as well)
-        if (tab.unread) go(k_preprocess_bwd_views<128, 4, true>);
+        if (tab.unread && per_gaussian_stamps(a.P)) go(k_preprocess_bwd_views_stamps<128, 4>, per_gaussian_stamps(a.P) + (size_t)cdiv(a.P, 64) * 8);
+        else if (tab.unread) go(k_preprocess_bwd_views<128, 4, true>);
         else go(k_preprocess_bwd_views<128, 4, false>);
     }
     LAUNCH_CHECK();

@@ -408,10 +408,24 @@ struct CamSlabs {
     float *p[RASTER_MAX_VIEWS];   // per view: the slab (rows of CAM_NC floats, one per workgroup)
 };
 template <int NT, int VL, bool UNREAD>
-__global__ __launch_bounds__(NT) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
+__global__ __launch_bounds__(NT, UNREAD ? 4 : 3) void k_preprocess_bwd_views(int P, int D, int M, const float *__restrict__ shs,
                                                                const float *__restrict__ scales, float scale_mod,
                                                                int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = false, CAM = false, AA = false;
+    constexpr bool DEPTH = false, CAM = false, AA = false, STAMP = false;
+    unsigned long long *const stamp_buf = nullptr;
+    (void)stamp_buf;
+    const CamSlabs *const cam_slabs = nullptr;
+    const float *const aa_opacities = nullptr;
+    (void)aa_opacities;
+#include "csplat_k8_views_body.h"
+}
+// (the flagship form, k_preprocess_bwd_views<NT, VL, true>, with s_memtime stamps: the measurement hook of csplat_debug_stamps)
+template <int NT, int VL>
+__global__ __launch_bounds__(NT, 4) void k_preprocess_bwd_views_stamps(int P, int D, int M, const float *__restrict__ shs,
+                                                                        const float *__restrict__ scales, float scale_mod,
+                                                                        int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
+                                                                        unsigned long long *stamp_buf) {
+    constexpr bool DEPTH = false, CAM = false, AA = false, UNREAD = true, STAMP = true;
     const CamSlabs *const cam_slabs = nullptr;
     const float *const aa_opacities = nullptr;
     (void)aa_opacities;
@@ -421,7 +435,9 @@ template <int NT, int VL>
 __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_depth(int P, int D, int M, const float *__restrict__ shs,
                                                                      const float *__restrict__ scales, float scale_mod,
                                                                      int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0) {
-    constexpr bool DEPTH = true, CAM = false, AA = false, UNREAD = false;
+    constexpr bool DEPTH = true, CAM = false, AA = false, UNREAD = false, STAMP = false;
+    unsigned long long *const stamp_buf = nullptr;
+    (void)stamp_buf;
     const CamSlabs *const cam_slabs = nullptr;
     const float *const aa_opacities = nullptr;
     (void)aa_opacities;
@@ -432,7 +448,9 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_cam(int P, int D, i
                                                                    const float *__restrict__ scales, float scale_mod,
                                                                    int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
                                                                    CamSlabs slabs) {
-    constexpr bool CAM = true, AA = false, UNREAD = false;
+    constexpr bool CAM = true, AA = false, UNREAD = false, STAMP = false;
+    unsigned long long *const stamp_buf = nullptr;
+    (void)stamp_buf;
     const CamSlabs *const cam_slabs = &slabs;
     const float *const aa_opacities = nullptr;
     (void)aa_opacities;
@@ -444,7 +462,9 @@ __global__ __launch_bounds__(NT) void k_preprocess_bwd_views_aa(int P, int D, in
                                                                   const float *__restrict__ scales, float scale_mod,
                                                                   int use_precomp_cov, float *__restrict__ dL_dsh, K8Table tab, int block0,
                                                                   CamSlabs slabs, const float *__restrict__ opacities) {
-    constexpr bool AA = true, UNREAD = false;
+    constexpr bool AA = true, UNREAD = false, STAMP = false;
+    unsigned long long *const stamp_buf = nullptr;
+    (void)stamp_buf;
     const CamSlabs *const cam_slabs = &slabs;
     const float *const aa_opacities = opacities;
     (void)cam_slabs;

@@ -84,7 +84,9 @@ int csplat_abi_version(void);
 int csplat_debug_flags(unsigned flags);
 unsigned csplat_debug_flags_query(void);
 /* measurement hook (not part of the operator interface): a device buffer the batched compositing backward fills with s_memtime stamps,
- * 12 uint64 per workgroup in launch order [view][workgroup] (tools/k7_stamps.py); NULL / 0 switches it off */
+ * 12 uint64 per workgroup in launch order [view][workgroup] (tools/k7_stamps.py); NULL / 0 switches it off.  A buffer of exactly
+ * 8 * (ceil(P / 64) + ceil(P / 32)) uint64 is filled by the batched K1 and K8 of a P-Gaussian step instead, 8 per workgroup, K1's first
+ * (tools/per_gaussian_stamps.py) */
 int csplat_debug_stamps(void *device_buffer, size_t bytes);
 const char *csplat_last_error(void);
 
