@@ -195,6 +195,12 @@ _K7_OUT = tuple(r for r in _INPUTS if r.acc is None)        # gradients K7 write
 _K8_OUT = tuple(r for r in _INPUTS if r.acc is not None)    # gradients K8 writes, into a buffer of their view or a shared one
 
 
+def _sh_staged(M, sh):
+    """does the library stage this SH tensor's rows through LDS (include/csplat.h, at `M`)?  Only then may views share one dL_dsh
+    (CSPLAT_ACC_SH) -- a [P, 16, 3] tensor that is a view into a flat buffer may start off a 16-byte boundary"""
+    return M == 16 and sh.data_ptr() % 16 == 0
+
+
 class _CallLayout:
     """How one call of _RasterizeGaussiansBatch is laid out: the order of its tensor arguments, the order of its outputs and the tuple
     its backward returns.  Beside the settings it holds no tensor, and it calls nothing; `_call_layout` builds it once per call and it
@@ -845,7 +851,10 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                     continue
                 unread = unread and not (row.temp and present)
                 j = first_of[i][slot]
-                if present and j != i and j in active and (row.name != "sh" or M == 16):
+                # (dL_dsh: only the SH-staging K8 can add into a buffer -- the library's own predicate, include/csplat.h at `M`: M == 16 and
+                # a 16-byte aligned SH tensor; the buffers reserved here are 256-byte aligned.  Otherwise every view gets a dL_dsh of its
+                # own, the per-view unstaged K8 writes it and autograd sums them.)
+                if present and j != i and j in active and (row.name != "sh" or _sh_staged(M, saved[i * k + row.saved])):
                     ent[field] = owner[(j, slot)]
                     ent["mask"] |= row.acc
                 else:

@@ -139,6 +139,12 @@ int csplat_image_layout(int W, int H, size_t *offsets3);
  *   view/proj: the reference's transposed 4x4 matrices (flat index 4*row+col of world_view_transform /
  *   full_proj_transform, scene_reconstruction/cameras.py:63-67), campos[3], bg[3]  -- all device, fp32.
  *   D = active SH degree (0..3), M = SH coefficients per channel stored (16 for max degree 3).
+ *   The rule for M and the SH pointers, for every entry point that takes them (csplat_forward*, csplat_backward*, csplat_view):
+ *     - any M >= (D+1)^2 is accepted, at any 4-byte alignment of shs / dL_dsh; coefficient rows past (D+1)^2 are not read, and their
+ *       gradient rows are written as zeros;
+ *     - staging the SH rows through LDS (K1, K8), the one K8 launch for all views of csplat_backward_views and CSPLAT_ACC_SH need
+ *       M == 16 and 16-byte aligned shs and (K8) dL_dsh.  Anything else is served by the unstaged kernels, per view, each view writing a
+ *       dL_dsh of its own; a view that asks for CSPLAT_ACC_SH there is an error.
  * Outputs (device): out_color[3][H][W], out_depth[1][H][W], radii[P] (int32).
  * *num_rendered (host) receives R = number of (Gaussian, tile) instances.
  * The three kept chunks are returned through geom/binning/image (device pointers from `alloc`). */
