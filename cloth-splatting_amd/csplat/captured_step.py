@@ -30,9 +30,9 @@ class CapturedStep:
     pipe.antialiasing).
     Falls back to the eager train_step for what it does not cover: masks, a static stage, view-parallel runs, densification steps and
     every optional term that is on (train._optional_terms_on: opt.lambda_depth / opt.lambda_silhouette, opt.lambda_chamfer,
-    opt.lambda_isometric / opt.lambda_spring / opt.lambda_rigidity > 0) -- the rasterizer refuses the geometry terms' gradients on a
-    forward launched on faith, the observed clouds' sizes are per camera and not part of a step's shape, and the kNN graph is refreshed
-    on the host's schedule."""
+    opt.lambda_isometric / opt.lambda_spring / opt.lambda_rigidity, opt.lambda_flow > 0) -- the rasterizer refuses the geometry terms'
+    gradients on a forward launched on faith, the observed clouds' sizes are per camera and not part of a step's shape, the kNN graph
+    is refreshed on the host's schedule, and the flow images belong to the cameras of a step, not to its shape."""
 
     def __init__(self, gaussians, simulator, meshnet_optimizer, pipe=None, opt=None, background=None):
         from . import train as tr       # (at call time: csplat.train imports this module)

@@ -8,7 +8,8 @@ Quirks reproduced, not fixed (the golden fixture tests/golden/scene_io.npz holds
   * the alpha-composited image is quantised by TRUNCATION (`np.array(arr * 255.0, dtype=np.byte)`, :371), not rounding;
   * frames whose file name is not r_<view>_<time> get their ids from the sorted unique transform matrices / times (:331-333);
   * `mapper` (read_timeline) is accepted and unused: the raw `time` of the frame is kept (:347-348);
-  * the optic-flow side-car is never read upstream (`if False`, :273) and is not read here.
+  * the optic-flow side-car is never read upstream (`if False`, :273) and is not read here: a caller who trains with
+    `opt.lambda_flow` (csplat/flow_loss.py) sets `camera.flow` itself.
 Host-side I/O: no GPU work, Pillow for the PNG decode."""
 import json
 import os

@@ -2,10 +2,10 @@
 /root/reference/scene_reconstruction/train_utils.py:240-321 around the hot path -- for the cameras of the mini-batch
 (3 consecutive timesteps of one view, scene_reconstruction/dataset.py:75-87) simulator -> mesh->Gaussian transform -> HIP rasterizer,
 all cameras in one call; L1 + lambda_dssim*(1-SSIM) (train_utils.py:50-74); regularisation (train_utils.py:77-100); the optional
-depth / silhouette, Chamfer and kNN-graph terms; ONE backward; the summed screen-space gradient / radii / visibility (:276-292); with
+depth / silhouette, Chamfer, kNN-graph and optical-flow terms; ONE backward; the summed screen-space gradient / radii / visibility (:276-292); with
 `densify_opt` the reference's densification / pruning / opacity-reset schedule (:295-307, csplat/densify.py); two Adam steps
 (:310-319).  The step also runs view-parallel (csplat/dist.py) and recorded into a hipGraph (captured_step.py).  Host-side torch only.
-This module is the way in: image_loss.py, geometry_loss.py, cloth_regs.py and captured_step.py are re-exported here; train_step and
+This module is the way in: image_loss.py, geometry_loss.py, flow_loss.py, cloth_regs.py and captured_step.py are re-exported here; train_step and
 its stages stay here because tests replace `render_views`, `render`, `geometry_losses` and `cd` as globals of THIS module."""
 from types import SimpleNamespace
 
@@ -20,6 +20,7 @@ from .densify import densification
 from .image_loss import (_mask_layout, l1_loss, _taps, _L1_SCRATCH, _IMG_SCRATCH, FusedL1, GaussianBlur11, FusedSSIM,  # noqa: F401
                          FusedImageLoss, _image_loss_fusable, ssim, psnr, image_losses)
 from .geometry_loss import _GEOM_SCRATCH, GeometryLoss, geometry_losses  # noqa: F401
+from .flow_loss import _FLOW_SCRATCH, FlowLoss, flow_losses  # noqa: F401
 from .cloth_regs import (FusedClothRegs, SimulatorStep, simulator_step, _DEFERRED, launch_deferred, edge_csr,  # noqa: F401
                          regularization)
 from .captured_step import CapturedStep
@@ -201,6 +202,48 @@ def _neighbour_graph(gaussians, iteration, o):
     return cached[1]
 
 
+def _flow_options(opt):
+    """(lambda_flow, flow_max_error or None) of an options namespace; absent or 0 = off, no cap.  The term is on when the weight is > 0."""
+    lam = float(getattr(opt, "lambda_flow", 0.0) or 0.0)
+    if not (lam >= 0.0 and lam <= 3.0e38):
+        raise ValueError(f"train_step: lambda_flow is a finite number >= 0, got {lam}")
+    cap = getattr(opt, "flow_max_error", None)
+    if cap is not None:
+        cap = float(cap)
+        if not (cap > 0.0 and cap <= 3.0e38):
+            raise ValueError(f"train_step: flow_max_error is a finite number of pixels > 0 (or None), got {cap}")
+    return lam, cap
+
+
+def _flow_targets(cams):
+    """the flow images of the step's pairs: `camera.flow` of every camera but the last (float32 [2,H,W] or [1,2,H,W], tensor or numpy
+    array; pair t is camera t -> camera t+1, the flow defined at camera t's pixels); ValueError for fewer than 2 cameras, a camera that
+    lacks the field or carries another shape or dtype, cameras of different image sizes and cameras of different views (where they carry
+    a `view_id`) -- all from the host-side attributes, before anything is launched"""
+    if len(cams) < 2:
+        raise ValueError(f"train_step: the optical-flow term needs at least 2 cameras (consecutive frames of one view), got {len(cams)}")
+    sizes = {(int(c.image_height), int(c.image_width)) for c in cams}
+    if len(sizes) > 1:
+        raise ValueError(f"train_step: the optical-flow term needs cameras of one image size, got {sorted(sizes)}")
+    views = {getattr(c, "view_id", None) for c in cams} - {None}
+    if len(views) > 1:
+        raise ValueError(f"train_step: the optical-flow term needs the frames of ONE view, got view_id {sorted(views)}")
+    (H, W), out = next(iter(sizes)), []
+    for cam in cams[:-1]:
+        f = getattr(cam, "flow", None)
+        if f is None or not hasattr(f, "shape") or not hasattr(f, "dtype"):
+            raise ValueError(f"train_step: lambda_flow > 0 needs `flow` (float32 [2,{H},{W}] or [1,2,{H},{W}]) on every camera but the last, "
+                             f"got {type(f).__name__}")
+        if str(f.dtype).split(".")[-1] != "float32" or tuple(f.shape) not in ((2, H, W), (1, 2, H, W)):
+            raise ValueError(f"train_step: camera.flow is {f.dtype} {tuple(f.shape)}, expected float32 [2,{H},{W}] or [1,2,{H},{W}]")
+        out.append(f)
+        m = getattr(cam, "mask", None)
+        if m is not None and (not torch.is_tensor(m) or m.dtype != torch.float32 or tuple(m.shape) not in ((1, H, W), (H, W))):
+            raise ValueError(f"train_step: a masked optical-flow term needs camera.mask as float32 [1,{H},{W}] or [{H},{W}], got "
+                             f"{(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else type(m).__name__}")
+    return out
+
+
 def _refuse_view_parallel(term, plural, view_parallel):
     """an optional term on the view-parallel step (csplat.dist.is_dist()): NotImplementedError"""
     if view_parallel and cd.is_dist():
@@ -215,18 +258,19 @@ def _refuse_camera_by_camera(term, plural, batched_views):
 
 def _optional_terms_on(opt):
     """whether some optional term's weight is > 0 (ValueError for a bad value) -- from the options alone, nothing of the model is read"""
-    return max(_geometry_weights(opt)) > 0.0 or _chamfer_weight(opt)[0] > 0.0 or _neighbour_options(opt)["on"]
+    return (max(_geometry_weights(opt)) > 0.0 or _chamfer_weight(opt)[0] > 0.0 or _neighbour_options(opt)["on"] or
+            _flow_options(opt)[0] > 0.0)
 
 
 def _plan_optional_terms(opt, cams, gaussians, iteration, static, view_parallel, batched_views):
     """What each optional term needs, None when it is off: geometry = (lambda_depth, lambda_silhouette, depths | None, silhouettes | None),
-    chamfer = (lambda_chamfer, squared cap | None, clouds), neighbours = the _neighbour_options dict.  Every refusal is raised here, in
-    this order: geometry, Chamfer, kNN; within a term the option value, view-parallel, batched_views=False, the cameras / Gaussian count.
-    Nothing of the model but num_gaussians is read."""
+    chamfer = (lambda_chamfer, squared cap | None, clouds), neighbours = the _neighbour_options dict, flow = (lambda_flow, cap | None,
+    the pairs' flow images).  Every refusal is raised here, in this order: geometry, Chamfer, kNN, flow; within a term the option value,
+    view-parallel, batched_views=False, the cameras / Gaussian count.  Nothing of the model but num_gaussians is read."""
     def carried(term, plural):
         _refuse_view_parallel(term, plural, view_parallel)
         _refuse_camera_by_camera(term, plural, batched_views)
-    plan = SimpleNamespace(geometry=None, chamfer=None, neighbours=None)
+    plan = SimpleNamespace(geometry=None, chamfer=None, neighbours=None, flow=None)
     lam_d, lam_s = _geometry_weights(opt)
     if (lam_d > 0.0 or lam_s > 0.0) and cams:
         carried("the depth and silhouette terms", True)
@@ -241,12 +285,17 @@ def _plan_optional_terms(opt, cams, gaussians, iteration, static, view_parallel,
         if int(gaussians.num_gaussians) <= nbr["k"]:
             raise ValueError(f"train_step: {int(gaussians.num_gaussians)} Gaussians have no k_nearest = {nbr['k']} neighbours each")
         plan.neighbours = nbr
+    lam_f, cap_f = _flow_options(opt)
+    if lam_f > 0.0 and cams:
+        carried("the optical-flow term", False)
+        plan.flow = (lam_f, cap_f, _flow_targets(cams))
     return plan
 
 
-def _add_optional_terms(plan, reg, pkgs, alphas, masks, gaussians, iteration):
-    """(reg + the terms of `plan` that are on, their stats): geometry, then Chamfer, then the kNN regularisers -- the sum rides into the
-    image loss where the regularisers alone would"""
+def _add_optional_terms(plan, reg, pkgs, alphas, masks, gaussians, iteration, cams=()):
+    """(reg + the terms of `plan` that are on, their stats): geometry, then Chamfer, then the kNN regularisers, then the optical flow
+    (which reads the cameras' full_proj_transform and image size from `cams`) -- the sum rides into the image loss where the
+    regularisers alone would"""
     stats = {}
     if plan.geometry is not None:
         # the two terms and their sum with the regularisers: two launches (and one in backward)
@@ -280,7 +329,25 @@ def _add_optional_terms(plan, reg, pkgs, alphas, masks, gaussians, iteration):
                                                      graph, *nbr["lams"], isometric_abs=nbr["iso_abs"])
         reg = reg + nb_loss
         stats["isometric_loss"], stats["spring_loss"], stats["rigidity_loss"] = nb_parts.unbind(0)
+    if plan.flow is not None:
+        # the motion of every Gaussian between consecutive frames against the flow images, and the sum with what came before: two
+        # launches (and one in backward); nothing is read back
+        lam_f, cap_f, flows = plan.flow
+        fdev = pkgs[0].means3D_deform.device
+        reg, fl, fn = flow_losses([pkg.means3D_deform for pkg in pkgs], [cam.full_proj_transform.to(fdev).contiguous() for cam in cams],
+                                  [_flow_image(f, fdev) for f in flows], (int(cams[0].image_height), int(cams[0].image_width)),
+                                  visible=[pkg.radii.reshape(-1) for pkg in pkgs], masks=None if masks is None else [m[0] for m in masks[:-1]],
+                                  lambda_flow=lam_f, max_error=cap_f, add=reg)
+        stats["flow_loss"], stats["flow_valid"] = fl.detach(), fn.detach()
     return reg, stats
+
+
+def _flow_image(f, dev):
+    """a camera's flow (tensor or numpy array, [2,H,W] or [1,2,H,W]) as a contiguous [2,H,W] tensor on `dev`: the camera's own tensor
+    when it is there already"""
+    if not torch.is_tensor(f):
+        f = torch.from_numpy(f)
+    return f.reshape(f.shape[-3:]).to(dev).contiguous()
 
 
 def _bind_flat_grads(gaussians, simulator, P, world, static, n_total):
@@ -432,7 +499,14 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
         num_gaussians must exceed it), `opt.lambda_w` (absent: 2000; w = exp(-lambda_w d^2)), rebuilt every `opt.knn_update_iter`
         iterations (absent: 1000) and after the number of Gaussians changed; `opt.isometric_abs` (absent: the reference's signed term).
         On when some weight is > 0, the step is not static and iteration > `opt.reg_iter` (absent: 0).  stats: "isometric_loss",
-        "spring_loss", "rigidity_loss" (unweighted; 0 for rigidity without its weight)."""
+        "spring_loss", "rigidity_loss" (unweighted; 0 for rigidity without its weight).
+      * `opt.lambda_flow` adds lambda_flow * L_flow of csplat.flow_loss.flow_losses(): the motion of every Gaussian's projection between
+        consecutive cameras of the step (the views' means3D_deform and full_proj_transform, in camera order) against `camera.flow` of
+        every camera but the last -- float32 [2,H,W] or [1,2,H,W], tensor or numpy array, dx / dy in pixels defined at that camera's
+        pixels towards the NEXT camera of the step, NaN = no flow there; the last camera's flow is not read.  Needs >= 2 cameras of one
+        image size and (where they carry `view_id`) of one view; visibility is the views' radii > 0, weighted by `camera.mask` when
+        the cameras carry one; `opt.flow_max_error` (absent / None: no cap; <= 0 is a ValueError) drops pairs whose error in pixels
+        exceeds it.  stats: "flow_loss" (L_flow, unweighted), "flow_valid" (the number of valid pairs, int32)."""
     if captured and _cap is None:     # the step as a replayed hipGraph (CapturedStep); falls back to this function when it must
         cs = gaussians.__dict__.get("_captured_step")
         if cs is None or not cs.matches(simulator, meshnet_optimizer, pipe, opt, background):
@@ -464,7 +538,7 @@ def train_step(iteration, viewpoint_cams, gaussians, simulator, meshnet_optimize
     if reg is None:
         verts = [pkg.vertice_deform[None] for pkg in pkgs]
         reg = regularization(torch.cat(verts, 0), gaussians, opt, static) if verts else torch.zeros((), device=dev)
-    reg, term_stats = _add_optional_terms(plan, reg, pkgs, alphas, masks, gaussians, iteration)
+    reg, term_stats = _add_optional_terms(plan, reg, pkgs, alphas, masks, gaussians, iteration, cams)
     loss, psnr_ = _image_term(cams, n_total, world, dist_mode, stacked, pkgs, masks, reg, opt, gaussians, _cap)
     if loss.requires_grad:
         try:

@@ -659,6 +659,42 @@ int csplat_geom_loss_fwd(void *stream, int n_views, int64_t hw, const float *con
 int csplat_geom_loss_bwd(void *stream, int n_views, int64_t hw, const unsigned char *sign8, const float *const *gt_depth,
                          const float *const *mask, float lambda_depth, float lambda_silhouette, float weight, const float *g_scalar,
                          float *d_depth, float *d_alpha);
+/* Optical-flow supervision of the Gaussians' motion between the frames of a training step, two launches forward and one backward
+ * (csplat_flow_loss.hip).  Added exports: CSPLAT_ABI_VERSION is unchanged.  The reference carries flow images as far as an unfinished
+ * `flow_loss` that prints (train.py:52-90); this is that term.
+ * FRAMES, PAIRS, PROJECTION.  T = n_frames frames, 2 <= T <= 16, of P Gaussians.  Frame t has centres X_t [P][3] and full_t [16], row-major
+ * in the reference's transposed convention, hom = [X, 1] @ full, as csplat_project_points takes it; all frames share one image size W x H.
+ * Pair t = 0..T-2 is (frame t -> frame t+1) with the flow image F_t [2][H][W]: channel 0 is dx in pixels (+x to the right), channel 1 dy,
+ * defined at the pixels of frame t (RAFT's convention).  Projection as gaussian_renderer._project: x = ((hom_x / w + 1) W - 1) / 2,
+ * y likewise with H; pixel centres sit at the integers.
+ * PER PAIR t AND GAUSSIAN i.  p_a = projection of X_t[i] with full_t, p_b = projection of X_{t+1}[i] with full_{t+1}.
+ *   g = bilinear(F_t, p_a): x0 = floor(x), x1 = min(x0 + 1, W - 1), fx = x - x0, the same in y (at x = W - 1 the clamped tap weighs 0)
+ *   m = M_t[floor(y + 0.5)][floor(x + 0.5)] clamped to the image; M_t [H][W] the optional camera mask of frame t, m = 1 without a table
+ *   r = (p_b - p_a) - g          e = |r_x| + |r_y|
+ * The pair is VALID iff visible_t[i] > 0 and visible_{t+1}[i] > 0 (int32 [P] per frame, the rasterizer's radii; the table or an entry
+ * may be NULL: visible), w_a > 0 and w_b > 0, p_a and p_b finite, 0 <= x_a <= W - 1 and 0 <= y_a <= H - 1, all four taps of both
+ * channels finite (a NaN / Inf flow pixel means "no flow here"), m finite and > 0, and -- when max_error > 0 -- e <= max_error.
+ *   L_flow   = (1/n) sum_valid m e,  n = (T - 1) P: ALL pairs, the convention of csplat_geom_loss_fwd
+ *   out[0]   = weight lambda L_flow + add_weight add[0]   (add may be NULL)        out[1] = L_flow        count[0] = valid pairs (int32)
+ * SELECTION, not multiplication: an invalid pair adds exactly 0 and gets exactly 0 gradient whatever its inputs hold.  sign(0) = 0.
+ * GRADIENT: the full analytic one, the sample's dependence on p_a included.  With s = m (sign r_x, sign r_y): dL/dp_b = s,
+ * dL/dp_a = -(I + J_g)^T s, J_g the 2 x 2 Jacobian of the bilinear sample in its cell (floor convention); then through the projection,
+ * dx/dX_k = (W/2) (full[k][0] - ndc_x full[k][3]) / w and likewise y.  The mask lookup and every validity decision are constants.  A
+ * middle frame receives the sum of its role as b of pair t-1 and as a of pair t.
+ * Tables are host arrays of device pointers: points and full_proj T entries, flow T-1, visible T or NULL, mask T-1 or NULL.
+ * unit [T][P][3]: dL_flow/dX_t[i] (divided by n), each element written once, no atomics; NULL = no gradient wanted, nothing is stored.
+ * csplat_flow_loss_bwd: d_points[t][i][c] = g_scalar[0] weight lambda unit[t][i][c] (g_scalar on the device; a unit of 0 gives 0).
+ * scratch: csplat_flow_loss_scratch_bytes bytes, no initial state, not shared between concurrent calls.  Bit-reproducible: workgroup
+ * partials summed in index order by a one-workgroup second launch, no float atomics.  Argument errors, before any launch: n_frames
+ * outside 2..16, P < 1, W < 1 or H < 1, lambda < 0, max_error NaN, a NULL required table, entry or output, an operand that is not
+ * 4-byte aligned, (T - 1) P >= 2^31. */
+size_t csplat_flow_loss_scratch_bytes(int n_frames, int64_t P);
+int csplat_flow_loss_fwd(void *stream, int n_frames, int64_t P, int W, int H, const float *const *points,
+                         const float *const *full_proj, const float *const *flow, const int *const *visible, const float *const *mask,
+                         float max_error, float lambda, float weight, const float *add, float add_weight, float *unit, void *scratch,
+                         float *out, int *count);
+int csplat_flow_loss_bwd(void *stream, int n_frames, int64_t P, const float *unit, float lambda, float weight, const float *g_scalar,
+                         float *d_points);
 
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
