@@ -3,6 +3,7 @@ launch (FusedClothRegs), fused with the time-conditioned simulator into one auto
 step issue that launch behind the rasterizer's forward (launch_deferred).  Re-exported by csplat.train."""
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import native as _n
 from .image_loss import _IMG_SCRATCH
@@ -52,6 +53,7 @@ class FusedClothRegs(torch.autograd.Function):
         return loss
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, g_through=None):
         _issue(ctx.pending)
         (grad,) = ctx.saved_tensors
@@ -82,6 +84,7 @@ class SimulatorStep(torch.autograd.Function):
         return D, loss
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_D, g_loss):
         from meshnet import graph_ops as go
         _issue(ctx.pending)

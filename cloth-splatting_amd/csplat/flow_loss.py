@@ -4,6 +4,7 @@ between them.  Re-exported by csplat.train, whose train_step adds the term when 
 import ctypes as C
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import native as _n
 
@@ -70,6 +71,7 @@ class FlowLoss(torch.autograd.Function):
         return loss, lf, nv
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _gl, _gn):
         T, P, lam, weight, w_add, has_add, n_in = ctx.dims
         if g is None:

@@ -7,6 +7,7 @@ csplat/densify.py (DensifyMixin), point_cloud.ply I/O from cs
 from types import SimpleNamespace
 
 import torch
+from torch.autograd.function import once_differentiable
 from torch import nn
 
 from . import native as _n
@@ -37,6 +38,7 @@ class MeshTransform(torch.autograd.Function):
         return xyz, quat
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_xyz, g_quat):
         vertices, bary, rotation, vid, rest, rowptr, corners = ctx.saved_tensors
         T, P, V = ctx.dims
@@ -97,6 +99,7 @@ class MeshTransformViews(torch.autograd.Function):
         return tuple(xyz.unbind(0)) + tuple(quat.unbind(0))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *grads):
         T, P, V = ctx.dims
         dev = ctx.saved_tensors[0].device
@@ -160,6 +163,7 @@ class _GaussianActivations(torch.autograd.Function):
         return opacity, scales, shs
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_op, g_sc, g_shs):
         return _act_bwd(*ctx.saved_tensors, g_op, g_sc, g_shs, sinks=ctx.sinks)
 
@@ -188,6 +192,7 @@ class GaussianStepInputs(torch.autograd.Function):
         return tuple(xyz.unbind(0)) + tuple(quat.unbind(0)) + (opacity, scales, shs)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *grads):
         T, P, V = ctx.dims
         saved = ctx.saved_tensors
@@ -224,6 +229,7 @@ class UnbindViews(torch.autograd.Function):
         return tuple(x.detach().unbind(0))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *grads):
         return _join_views(grads, ctx.shape[1:], *ctx.meta)
 

@@ -4,6 +4,7 @@ csplat.train, whose train_step adds the term when opt.lambda_depth / opt.lambda_
 import ctypes as C
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import native as _n
 
@@ -64,6 +65,7 @@ class GeometryLoss(torch.autograd.Function):
         return loss, ld, ls
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _gd, _gs):
         V, hw, lam_d, lam_s, weight, w_add, nz, nm, has_add, shapes, n_views_in = ctx.dims
         if g is None:

@@ -8,6 +8,7 @@ import ctypes as C
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import native as _n
 
@@ -82,9 +83,10 @@ class FusedL1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, mask=None):
         _n.require_cuda(a)
+        # (asked of the ARGUMENTS: grad mode is off in here, so the copy .contiguous() makes of a strided image requires no gradient)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         a, b = a.contiguous(), b.contiguous()
         mask = None if mask is None else mask.contiguous()
-        need = a.requires_grad or b.requires_grad
         scratch = _l1_scratch(a.device)
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         if mask is not None:
@@ -103,6 +105,7 @@ class FusedL1(torch.autograd.Function):
         return loss
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         sign8, mask = ctx.saved_tensors
         B, Cc, hw, mc, shape = ctx.layout
@@ -193,6 +196,7 @@ class FusedSSIM(torch.autograd.Function):
         return partial.sum() / float(x.numel())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, y, p = ctx.saved_tensors
         n_img, H, W = ctx.dims
@@ -261,6 +265,7 @@ class FusedImageLoss(torch.autograd.Function):
         return loss, ps, il
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _gp, _gi):
         x, y, p, sign, mask = ctx.saved_tensors
         B, Cc, H, W, mc, lam, w_img, w_add, has_add, shape = ctx.dims

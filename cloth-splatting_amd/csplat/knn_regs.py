@@ -6,6 +6,7 @@ be run, so there is no reference-run fixture and parity is against tests/knn_reg
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 import simple_knn
 
@@ -109,6 +110,7 @@ class _FusedRegs(torch.autograd.Function):
         return loss, parts
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _g_parts):
         want_m, want_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if g is None or not (want_m or want_q):

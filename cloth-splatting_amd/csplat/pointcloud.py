@@ -2,6 +2,7 @@
 its one-sided form, the 3-D companion of the depth / silhouette terms -- a loss that pulls the deformed Gaussian centres onto an
 observed point cloud."""
 import torch
+from torch.autograd.function import once_differentiable
 
 import simple_knn
 
@@ -32,6 +33,7 @@ class ChamferDirection(torch.autograd.Function):
         return loss.view(())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         if g is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return None, None, None

@@ -34,6 +34,7 @@ from operator import attrgetter as _attrgetter
 from typing import NamedTuple
 
 import torch
+from torch.autograd.function import once_differentiable
 import torch.nn as nn
 
 from csplat import native as _n
@@ -469,6 +470,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         return color, radii, depth
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_color, _grad_radii, grad_depth):
         if grad_color is None and grad_depth is None:
             return (None,) * (9 + ctx.ncam)
@@ -903,8 +905,12 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 "acc": [e["scratch"] for e in plan if torch.is_tensor(e["scratch"])]}      # (kept alive with the plan)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *grads):
         layout, views, k, arr = ctx.layout, ctx.views, ctx.nsaved, ctx.arr
+        # unpacked on EVERY path: the plan made in forward() holds raw pointers into the inputs, so the usual pass would never touch the saved
+        # tensors -- and autograd's version check, which refuses an input edited in place since the forward, runs when they are unpacked
+        saved = ctx.saved_tensors
         V = layout.V
         dev = views[0].dev
         main = torch.cuda.current_stream(dev)
@@ -934,7 +940,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         if plan is None or plan["active"] != active:            # a view's image went unused, or a second backward pass
             if plan is not None:
                 _n.grad_release(plan["sinks"])
-            plan = _RasterizeGaussiansBatch._plan_backward(views, ctx.saved_tensors, k, arr, ctx.first_of, active, dev)
+            plan = _RasterizeGaussiansBatch._plan_backward(views, saved, k, arr, ctx.first_of, active, dev)
         gs = [_f32c_grad(gcol[i], dev) if gcol[i] is not None else torch.zeros(3, views[i].H, views[i].W, dtype=torch.float32, device=dev)
               for i in active]
         for a, g in enumerate(gs):
@@ -951,7 +957,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         if want_feat:
             # the feature path (csplat_view.dL_dfeatures / dL_dalpha): one dL_dfeat_in buffer per feature tensor OBJECT that wants a
             # gradient, shared by the views it was passed to (the library adds their sums in view order)
-            fsaved = ctx.saved_tensors[len(ctx.saved_tensors) - ctx.nfeat_saved:]
+            fsaved = saved[len(saved) - ctx.nfeat_saved:]
             fout, owner = [None] * V, {}
             for a, i in enumerate(active):
                 w, F = plan["sub"][a], fspec[i][0]
@@ -989,7 +995,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             # (kept alive: the MEMORY the K8 slices write -- never the gradient tensor objects themselves: AccumulateGrad adopts a
             #  gradient only when nobody else holds it, and would otherwise snapshot the still unwritten buffer into a copy)
             outs, plan["out"] = plan["out"], None
-            _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, ctx.saved_tensors,
+            _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, saved,
                                                                                           ctx.aa_opacities)))
             return layout.grads(outs)
         with _n.on_device(dev):

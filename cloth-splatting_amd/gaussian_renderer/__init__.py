@@ -8,6 +8,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, rasterize_views
 
 
@@ -75,6 +76,7 @@ class _ProjectPoints(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         points, full = ctx.saved_tensors
         with torch.enable_grad():
