@@ -22,6 +22,9 @@
  *   csplat_knn, csplat_knn_ws, csplat_fps
  *       the host neighbour queries of the reference: cKDTree in compute_edges_index (meshnet/data_utils.py:406-412), the Open3D
  *       KD-tree of o3d_knn (utils/external.py:5-16), the numpy loop of farthest_point_sampling (meshnet/data_utils.py:134-160).
+ *   csplat_track_visibility, csplat_track_mte
+ *       the host-side tracking evaluation: `project` and `get_mask` of render.py:77-121 for all view-frames at once, and the
+ *       align_traj + compute_mte loop of scripts/align_eval_trajs.py for all ground-truth tracks at once.
  *   csplat_gnn_*
  *       the torch_geometric MessagePassing gather / scatter-add inside InteractionNetwork.propagate,
  *       meshnet/graph_network.py:173-174 (gather x_i, x_j: PyG __lift__), :197 (concat), :136 (aggr='add').
@@ -695,6 +698,44 @@ int csplat_flow_loss_fwd(void *stream, int n_frames, int64_t P, int W, int H, co
                          float *out, int *count);
 int csplat_flow_loss_bwd(void *stream, int n_frames, int64_t P, const float *unit, float lambda, float weight, const float *g_scalar,
                          float *d_points);
+/* Point tracking, the evaluation end of the pipeline (csplat_tracking.hip).  Added exports: CSPLAT_ABI_VERSION is unchanged.  They restate
+ * the reference's `project` and `get_mask` (render.py:77-121) for all view-frames of a tracking run in one launch, and the `align_traj` +
+ * `compute_mte` loop of scripts/align_eval_trajs.py for all ground-truth tracks in one launch (plus a one-workgroup mean).  No gradients.
+ *
+ * csplat_track_visibility: F view-frames (1 <= F <= 65535) of N points; every array is stacked and contiguous.  Per frame f and point i,
+ * with X = points[f][i], full = full_proj[f] (row-major, the reference's transposed convention: hom = [X, 1] @ full), c = cam_center[f]:
+ *   PIXEL     pixels_in == NULL: the arithmetic of csplat_project_points, x = ((hom_x / w + 1) W - 1) / 2, y likewise with H;
+ *             pixels_in given: (x, y) = pixels_in[f][i], nothing is projected (the get_mask form, which receives projections)
+ *   in_image  0 <= x < W and 0 <= y < H, both finite -- and, when projecting, w > 0.  The reference has no test of w: a point behind
+ *             the camera is mirrored into the image there and can count as visible.  A deliberate divergence, as csplat_flow_loss_fwd's
+ *   d         depth[f][(int)y][(int)x], C truncation (the reference's astype(int)); then d < min_depth gives d = far_value (render.py:
+ *             171, 206: `depth[depth < 1.0] = 10e3`).  min_depth <= 0 (or NaN) switches that rule off
+ *   visible   in_image and (||X - c||_2 - depth_threshold) <= d: a EUCLIDEAN distance against the rendered (alpha-weighted z) depth,
+ *             as the reference compares them.  A NaN depth or a NaN point gives not visible.  depth == NULL: visible = in_image
+ *   counts    counts[f] = (points in the image, points visible), int32.  Of the two forms the design allowed, the finishing launch was
+ *             chosen over integer atomics: a second launch, one workgroup per frame, sums the frame's in_image and visible bytes.
+ *             INTEGER sums, the same in any order; no atomics of any kind (atomics of all workgroups into the one cache line that
+ *             holds counts cost 88 us of a 97 us call at 100 000 points x 12 frames)
+ * Every load is unconditional with its index clamped into the arrays; an invalid point is selected out.  pixels_out [F][N][2] (NULL:
+ * not stored), in_image / visible [F][N] bytes 0 / 1, counts [F][2] (NULL: not formed).  Bit-reproducible.  N == 0 returns at once.
+ * Argument errors, before any launch: F outside 1..65535, N < 0 or >= 2^31, W < 1 or H < 1, W * H >= 2^31, a NULL points, full_proj,
+ * cam_center, in_image or visible, depth_threshold or far_value NaN, a float operand that is not 4-byte aligned.
+ *
+ * csplat_track_mte: T >= 1 frames, N tracked points, G ground-truth tracks; track g is associated with point j = assoc[g] (int32; the
+ * caller guarantees 0 <= j < N, the kernel clamps j so that no load can leave the arrays).  With R_k = the rotation matrix of the
+ * quaternion rotations[k][j], r first, normalised inside (build_rotation, scripts/align_eval_trajs.py:9-27):
+ *   t0 = gt[0][g] - traj[0][j]        aligned[0][g] = traj[0][j] + t0        aligned[k][g] = traj[k][j] + (R_k R_0^T) t0   (k >= 1)
+ *   err[k][g] = ||gt[k][g] - aligned[k][g]||_2        mte[g] = (sum_k err[k][g]) / T, summed in increasing k
+ *   mean[0] = (sum_g mte[g]) / G, formed by a second, one-workgroup launch in a fixed order
+ * rotations == NULL: no alignment, aligned[k][g] = traj[k][j] (render.py's own `deform[gt_idxs]`).  A ZERO quaternion normalises to NaN
+ * and makes its track's aligned positions, errors and the mean NaN, as in the reference; it is not guarded.  aligned [T][G][3], err
+ * [T][G], mte [G], mean [1]; aligned and err may be NULL.  Bit-reproducible, no atomics.  N == 0 or G == 0 returns at once.  Argument
+ * errors: T < 1, N or G < 0 or >= 2^31, a NULL traj, gt, assoc, mte or mean, an operand that is not 4-byte aligned. */
+int csplat_track_visibility(void *stream, int F, int64_t N, int W, int H, const float *points, const float *pixels_in,
+                            const float *full_proj, const float *cam_center, const float *depth, float depth_threshold, float min_depth,
+                            float far_value, float *pixels_out, uint8_t *in_image, uint8_t *visible, int *counts);
+int csplat_track_mte(void *stream, int T, int64_t N, int64_t G, const float *traj, const float *rotations, const float *gt,
+                     const int *assoc, float *aligned, float *err, float *mte, float *mean);
 
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
