@@ -113,6 +113,10 @@ EXPORTS = {
     "csplat_flow_loss_bwd": (_i, [_vp, _i, _i64, _vp, _f, _f, _vp, _vp]),
     "csplat_track_visibility": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "csplat_track_mte": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_plan_integrate": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_plan_cost": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp]),
+    "csplat_plan_select": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "csplat_plan_refit_sample": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f]),
     "csplat_psnr_scratch_bytes": (_sz, [_i64]),
     "csplat_psnr": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "csplat_sim_hidden_fwd": (_i, [_vp, _i, _i] + [_vp] * 7),

@@ -737,6 +737,53 @@ int csplat_track_visibility(void *stream, int F, int64_t N, int W, int H, const 
 int csplat_track_mte(void *stream, int T, int64_t N, int64_t G, const float *traj, const float *rotations, const float *gt,
                      const int *assoc, float *aligned, float *err, float *mte, float *mean);
 
+/* Planning, the control end of the pipeline (csplat_plan.hip).  Added exports: CSPLAT_ABI_VERSION is unchanged.  What a model-predictive
+ * planner needs around the batched MeshNet rollout: the reference rolls the GNN out for A candidate action sequences as one
+ * block-diagonal graph (meshnet/dataloader_sim.py:248-288), takes (pos - goal).pow(2).mean() per candidate (manipulation/planning.py:425)
+ * and executes the cheapest (:311).  Its MPC class is not shipped; these entries restate the cost and supply a cross-entropy-method update.
+ *
+ * Batched state, PyG's Batch layout: node n of candidate b is row b * N + n.  pos [B*N][3], hist [H][B*N][3] (oldest first), actions
+ * [B][T][3], goal [N][3] shared by all candidates, node_w [N] or NULL (all ones), cost [B].  Plain loads and vector stores, NO atomics:
+ * every output is bit-reproducible.  Every entry validates its arguments before any launch (a bad one returns non-zero and
+ * csplat_last_error() names the entry) and does nothing, returning 0, for an empty problem.  Operands are 4-byte aligned.
+ *
+ * csplat_plan_integrate: the tail of rollout step k (0 <= k < T, by value) for all candidates, the batched twin of
+ * csplat_rollout_integrate: v[b*N + grasped] = actions[b][k] (a grasped index outside [0, N) pins NOTHING); pos += v;
+ * hist <- (hist[1:], v); preds[k][b*N + n] = v when preds != NULL (preds [steps][B*N][3], steps > k).  With goal != NULL also
+ *   cost[b] += step_w[k] * (1 / 3N) * sum_{n,c} node_w[n] * (pos_new[b][n][c] - goal[n][c])^2
+ * step_w [T], or NULL = 1 at k == T-1 and 0 before it -- an earlier step then forms no term and leaves cost untouched; with node_w == NULL
+ * this is planning.py:425 on the final state.  cost is zeroed by the caller before step 0.  ONE workgroup owns a candidate's cost word and
+ * sums its 3N terms in an order fixed by N alone (thread t its elements t, t + 256, .. in increasing index; a xor tree over each wave;
+ * the waves in order; / 3N; * the weight; added to cost[b]): a candidate's cost is a function of its own positions, bit for bit,
+ * independent of B and of b.  Elementwise arithmetic without contraction, in torch's order.  B * N < 2^29, H >= 1, T >= 1.
+ *
+ * csplat_plan_cost: the same term on stored positions pos [B][N][3]: cost[b] = (accumulate ? cost[b] : 0) + w * (1 / 3N) * sum ...
+ * It shares the device function with csplat_plan_integrate: for equal positions and an equal weight the two give bit-equal terms, so a
+ * cost formed after the rollout (w = 1, accumulate = 0) EQUALS the one accumulated under the default step_w.
+ *
+ * csplat_plan_select: B <= 65536 costs, K <= B: order[r] (int32) = the index of the r-th smallest cost, best[r] = that cost as stored.
+ * A total order: numbers ascending with -0.0 == 0.0, +inf before every NaN, NaN last; equal costs (and all NaN) by ascending index --
+ * torch.sort(cost, stable=True) truncated to K.  Each candidate's rank is counted against LDS tiles of the cost vector (B^2 compares:
+ * no global sort); the ranks are a permutation, so every output slot is written once.
+ *
+ * csplat_plan_refit_sample: one cross-entropy-method update.  actions [B][T][3] (in/out), order [K] (the elite rows; an index outside
+ * [0, B) is clamped), mu / sigma [T][3] (in/out), noise [B][T][3] (standard normal, drawn by the caller; row 0 is not read).  Per (t, c),
+ * sums over the elites in the order r = 0 .. K-1:
+ *   m = (sum_r a_r) / K          s = sqrt((sum_r (a_r - m)^2) / K)          a_r = actions[order[r]][t][c]
+ *   mu <- alpha * mu + (1 - alpha) * m          sigma <- max(sigma_min, alpha * sigma + (1 - alpha) * s)   (a NaN stays a NaN)
+ * then the new candidates: row 0 = clamp(mu, +-a_max) (the incumbent is always a candidate), row b > 0 = clamp(mu + sigma * noise[b],
+ * +-a_max); a_max <= 0: no clamp.  alpha = 1 is an identity refit (of finite elites); K = 0 skips the refit altogether (order may be
+ * NULL).  Two launches on the stream, refit then sample: every elite row is read before any row is overwritten.  0 <= alpha <= 1,
+ * sigma_min >= 0, B * T < 2^29. */
+int csplat_plan_integrate(void *stream, int B, int N, int H, int T, int k, float *v, const float *actions, int64_t grasped, float *pos,
+                          float *hist, float *preds /* or NULL */, const float *goal /* or NULL: no cost */, const float *node_w /* or NULL */,
+                          const float *step_w /* or NULL */, float *cost /* NULL only without a goal */);
+int csplat_plan_cost(void *stream, int B, int N, const float *pos, const float *goal, const float *node_w /* or NULL */, float w,
+                     int accumulate, float *cost);
+int csplat_plan_select(void *stream, int B, int K, const float *cost, int32_t *order, float *best);
+int csplat_plan_refit_sample(void *stream, int B, int T, int K, float *actions, const int32_t *order, float *mu, float *sigma,
+                             const float *noise, float alpha, float sigma_min, float a_max);
+
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
  *   csplat_mesh_rest       per-Gaussian constants of the REST face (in-plane basis, normal, in-plane coordinates) into
