@@ -117,6 +117,11 @@ EXPORTS = {
     "csplat_plan_cost": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp]),
     "csplat_plan_select": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "csplat_plan_refit_sample": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f]),
+    "csplat_obs_unproject_temp_bytes": (_sz, [_i, _i, _i]),
+    "csplat_obs_unproject": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i64, _vp, _vp, _vp, _vp]),
+    "csplat_obs_voxel_temp_bytes": (_sz, [_i64]),
+    "csplat_obs_voxel": (_i, [_vp, _i64, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csplat_obs_mark": (_i, [_vp, _i64, _i, _i, _vp, _vp, _f, _vp]),
     "csplat_psnr_scratch_bytes": (_sz, [_i64]),
     "csplat_psnr": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "csplat_sim_hidden_fwd": (_i, [_vp, _i, _i] + [_vp] * 7),

@@ -25,6 +25,9 @@
  *   csplat_track_visibility, csplat_track_mte
  *       the host-side tracking evaluation: `project` and `get_mask` of render.py:77-121 for all view-frames at once, and the
  *       align_traj + compute_mte loop of scripts/align_eval_trajs.py for all ground-truth tracks at once.
+ *   csplat_obs_unproject, csplat_obs_voxel, csplat_obs_mark
+ *       the host-side observation code: get_world_coords (manipulation/envs/camera_utils.py:106-133, manipulation/deform_mesh.py:168-195)
+ *       and get_observable_particle_index (camera_utils.py:136-162); the voxel grid thins the cloud before node sampling.
  *   csplat_gnn_*
  *       the torch_geometric MessagePassing gather / scatter-add inside InteractionNetwork.propagate,
  *       meshnet/graph_network.py:173-174 (gather x_i, x_j: PyG __lift__), :197 (concat), :136 (aggr='add').
@@ -783,6 +786,56 @@ int csplat_plan_cost(void *stream, int B, int N, const float *pos, const float *
 int csplat_plan_select(void *stream, int B, int K, const float *cost, int32_t *order, float *best);
 int csplat_plan_refit_sample(void *stream, int B, int T, int K, float *actions, const int32_t *order, float *mu, float *sigma,
                              const float *noise, float alpha, float sigma_min, float a_max);
+
+/* Observation clouds, the sensing end of the pipeline (csplat_observation.hip): what turns depth images, silhouettes and cameras into the
+ * 3-D data the Chamfer term (camera.points), the cloth-graph builders and the planner's node weights read.  They restate the reference's
+ * host code: get_world_coords (manipulation/envs/camera_utils.py:106-133, manipulation/deform_mesh.py:168-195) and
+ * get_observable_particle_index / _old (camera_utils.py:136-162, a full cdist matrix).  No gradients.  NO atomics of any kind: every
+ * output is bit-reproducible run to run.  Float arithmetic without contraction, every operation one float32 rounding; the library is built
+ * without fast-math, so `/` is the correctly rounded IEEE division and the cell below can be restated exactly in numpy float32.  Every
+ * entry validates its arguments before any launch (a bad one returns non-zero and csplat_last_error() names the entry): NULL operands,
+ * an output or `temp` that shares a byte with another operand, sizes out of range, operands that are not 4-byte aligned (temp: 16).
+ *
+ * csplat_obs_unproject: V views (1 <= V <= 65535) of H x W, V * H * W < 2^31; depth [V][H][W]; mask [V][H][W] or NULL (all ones);
+ * intrinsics [V][4] = (fx, fy, cx, cy) in pixel units, pixel centres at the integers; cam_to_world [V][3][4] row-major, column-vector
+ * form (p_world = R p_cam + t, t the fourth column).  Pixel (v, y, x) is SELECTED when x % stride == 0 and y % stride == 0 (stride >= 1),
+ * its depth d is finite and > 0 (a hole is 0, negative, NaN or Inf: the rule of csplat_geom_loss_fwd), d <= max_depth when max_depth > 0
+ * (<= 0: no maximum), and mask > 0.5 when a mask is given (a NaN mask value selects nothing).  Its point, with a = x - cx, b = y - cy:
+ *   kind 0 (d is the view-space z)             p_cam = (a * d / fx, b * d / fy, d)
+ *   kind 1 (d is the distance along the ray)   u = a / fx, w = b / fy, s = d / sqrt(u u + w w + 1), p_cam = (u s, w s, s)
+ *   p_world[r] = R[r][0] p_cam.x + R[r][1] p_cam.y + R[r][2] p_cam.z + t[r], summed left to right
+ * Selected pixels land in ascending order of their flat index (v H + y) W + x: points [cap][3], source [cap] (int32, that flat index),
+ * *count_dev (device int32) = the number of selected pixels -- the FULL count, also when it exceeds cap; rows beyond cap are not written.
+ * A stable compaction: selection bytes, csplat_mask_to_map, then a second pass that computes a selected pixel's point into its row.  Both
+ * passes read a view's pixels row-wise, 16 bytes a lane where the view's plane allows it and scalar before and behind (odd H * W); the
+ * view's 4 + 12 camera floats are uniform per workgroup.  temp: csplat_obs_unproject_temp_bytes(V, H, W) bytes of device memory.
+ * Errors besides the common ones: stride < 1, kind not 0 or 1, a NaN max_depth, cap < 0 or >= 2^31, NULL points / source with cap > 0.
+ *
+ * csplat_obs_voxel: M points [M][3] (0 <= M < 2^31) on a grid of cubic cells of edge voxel (finite, > 0) from `origin` (DEVICE float [3];
+ * NULL: the per-axis minimum over the finite points, found on the device).  A point with a non-finite coordinate is left out:
+ * inverse = -1.  Per axis the cell is c = floorf((p - o) / voxel), the subtraction and the division each rounded to float32 (no reciprocal,
+ * no fused form).  Cells lie in [0, 2^21) per axis; a finite point outside (or a non-finite origin) is counted in *n_outside (device int32)
+ * and gets inverse = -1.  Voxels are the occupied cells in ascending order of the key cz << 42 | cy << 21 | cx:
+ *   centroid[q] = corner + (sum of (p - corner) over the voxel's points) / count[q],  corner = o + (float)c * voxel per axis;
+ *                 the points of a voxel are taken in ascending index: lane l of one wave sums the l-th, (l + 64)-th, .. in that order
+ *                 and a xor tree joins the 64 lanes -- an order fixed by the voxel's own points
+ *   count[q] (int32), inverse[i] (int32) = the voxel of point i, *n_voxels (device int32) = K
+ * centroid and count have M rows of capacity (K <= M is not known to the host); rows from K on are not written.  Built on
+ * csplat_sort_pairs_u64 (stable, the point index as value), a head-flag csplat_scan_u32 and a segment reduction.  M == 0 zeroes the two
+ * counters and returns.  temp: csplat_obs_voxel_temp_bytes(M) bytes of device memory.
+ *
+ * csplat_obs_mark: idx [Q][K] (int32), d2 [Q][K] as csplat_knn_query returns them (K >= 1, Q * K < 2^31): flags[n] = 1 (uint8, N of them)
+ * iff some entry has idx == n and (max_sq_dist < 0 or d2 <= max_sq_dist), else 0.  The entry zeroes flags on the stream, then every
+ * writer stores the same byte: plain stores, no atomics.  Entries with idx outside [0, N) (the -1 of an unfilled slot) mark nothing.
+ * A NaN max_sq_dist is an error.  Added exports: CSPLAT_ABI_VERSION is unchanged. */
+size_t csplat_obs_unproject_temp_bytes(int V, int H, int W);
+int csplat_obs_unproject(void *stream, int V, int H, int W, const float *depth, const float *mask /* or NULL */, const float *intrinsics,
+                         const float *cam_to_world, int stride, float max_depth, int kind, int64_t cap, float *points, int32_t *source,
+                         int32_t *count_dev, void *temp);
+size_t csplat_obs_voxel_temp_bytes(int64_t M);
+int csplat_obs_voxel(void *stream, int64_t M, const float *points, float voxel, const float *origin /* device, or NULL */, float *centroid,
+                     int32_t *count, int32_t *inverse, int32_t *n_voxels, int32_t *n_outside, void *temp);
+int csplat_obs_mark(void *stream, int64_t Q, int K, int N, const int32_t *idx, const float *d2, float max_sq_dist, uint8_t *flags);
 
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
