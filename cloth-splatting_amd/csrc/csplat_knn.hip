@@ -880,3 +880,113 @@ extern "C" int csplat_chamfer_bwd(void *stream, int Q, int N, const float *queri
     }
     return 0;
 }
+
+// ================================================================================================================================
+// Trajectory smoothing (csplat_traj_smooth; include/csplat.h "Trajectory preprocessing" states the semantics): the reference's
+// gaussian_smoothing (meshnet/data_utils.py:267-278, one KD-tree query per point per frame in Python) for all T frames of a tracked
+// cloud in ONE launch.  Nothing above is touched: this is k_knn_query_brute with the frame on the grid's second axis (queries and
+// points are the same frame; a wave never reads another frame) and an epilogue that forms the weighted mean straight from the K-best
+// registers -- K gathers from the frame, which the slab loop has just pulled through the cache -- so no index array leaves the kernel
+// unless the caller asks for it.  A candidate whose squared distance is not finite is offered as knn_offer's `self` case: it changes
+// nothing.  The sum runs over the list in its ascending (d2, index) order, one float32 rounding per operation: bit-reproducible, no
+// atomics.  Brute force only, O(T N^2): tracked clouds are hundreds to a few thousand points (profiles/trajectory_cost.txt shows
+// where that stops being the right tool).
+namespace {
+__device__ __forceinline__ bool traj_finite(float v) { return fabsf(v) < __builtin_inff(); }   // (false for a NaN)
+
+template <int CAP>
+__global__ __launch_bounds__(KNN_THREADS) void k_traj_smooth(int T, int N, int K, const float *__restrict__ pts, float neg_scale,
+                                                             float *__restrict__ out, float *__restrict__ out_d2, int32_t *__restrict__ out_idx) {
+#pragma clang fp contract(off)
+    __shared__ float s_p[KNN_SLAB * 3];
+    const int i = blockIdx.x * KNN_THREADS + threadIdx.x;
+    const bool live = i < N;
+    for (int t = blockIdx.y; t < T; t += gridDim.y) {            // uniform per workgroup: the barriers below stay together
+        const float *__restrict__ frame = pts + (size_t)t * N * 3;
+        const float x = live ? frame[3 * (size_t)i] : 0.f, y = live ? frame[3 * (size_t)i + 1] : 0.f, z = live ? frame[3 * (size_t)i + 2] : 0.f;
+        KBest<CAP> b;
+        b.init(live ? K : 0);
+        for (int base = 0; base < N; base += KNN_SLAB) {
+            const int cnt = min(KNN_SLAB, N - base);
+            __syncthreads();
+            for (int k = threadIdx.x; k < cnt * 3; k += KNN_THREADS) s_p[k] = frame[(size_t)base * 3 + k];
+            __syncthreads();
+            int j = 0;
+            for (; j + 4 <= cnt; j += 4) {
+                float d[4];
+                int ci[4];
+                bool none[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const float dx = s_p[3 * (j + u)] - x, dy = s_p[3 * (j + u) + 1] - y, dz = s_p[3 * (j + u) + 2] - z;
+                    d[u] = dx * dx + dy * dy + dz * dz;
+                    ci[u] = base + j + u;
+                    none[u] = !traj_finite(d[u]);
+                }
+                knn_offer4(b, d, ci, none);
+            }
+            for (; j < cnt; j++) {
+                const float dx = s_p[3 * j] - x, dy = s_p[3 * j + 1] - y, dz = s_p[3 * j + 2] - z;
+                const float d = dx * dx + dy * dy + dz * dz;
+                knn_offer(b, d, base + j, !traj_finite(d));
+            }
+        }
+        if (live) {
+            const size_t row = (size_t)t * N + i;
+            float ax = -0.f, ay = -0.f, az = -0.f, sw = 0.f;      // -0 is the identity of +: the sum is that of its terms alone (K = 1 returns a -0 as -0)
+#pragma unroll
+            for (int s = 0; s < CAP; s++) {
+                const int r = s - (CAP - K);
+                if (r < 0) continue;
+                const bool filled = b.id[s] != KNN_IDX_NONE;
+                if (out_d2) out_d2[row * K + r] = b.d[s];                 // an empty slot still holds +inf
+                if (out_idx) out_idx[row * K + r] = filled ? b.id[s] : -1;
+                if (filled) {
+                    const float w = expf(b.d[s] * neg_scale);
+                    const float *__restrict__ q = frame + 3 * (size_t)b.id[s];
+                    ax = ax + w * q[0]; ay = ay + w * q[1]; az = az + w * q[2];
+                    sw = sw + w;
+                }
+            }
+            // a non-finite coordinate: every distance was a NaN or Inf, the list is empty and the point goes through as it is
+            const bool whole = traj_finite(x) && traj_finite(y) && traj_finite(z);
+            out[3 * row] = whole ? ax / sw : x;
+            out[3 * row + 1] = whole ? ay / sw : y;
+            out[3 * row + 2] = whole ? az / sw : z;
+        }
+    }
+}
+
+bool traj_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b || na == 0 || nb == 0) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+}  // namespace
+
+extern "C" int csplat_traj_smooth(void *stream, int T, int N, int K, const float *points, float sigma, float *out, float *out_d2,
+                                  int32_t *out_idx) {
+    CSPLAT_REQUIRE(T >= 0 && N >= 0, "csplat_traj_smooth: bad T or N");
+    CSPLAT_REQUIRE(K >= 1 && K <= CSPLAT_KNN_MAX_K, "csplat_traj_smooth: K outside 1 .. CSPLAT_KNN_MAX_K");
+    CSPLAT_REQUIRE(sigma > 0.f && sigma < __builtin_inff(), "csplat_traj_smooth: sigma is a finite number > 0");
+    CSPLAT_REQUIRE((int64_t)T * N * K < ((int64_t)1 << 31), "csplat_traj_smooth: T * N * K must stay below 2^31");
+    if (T == 0 || N == 0) return 0;
+    CSPLAT_REQUIRE(points && out, "csplat_traj_smooth: NULL points or out");
+    CSPLAT_REQUIRE((((uintptr_t)points | (uintptr_t)out | (uintptr_t)out_d2 | (uintptr_t)out_idx) & 3u) == 0,
+                   "csplat_traj_smooth: operands must be 4-byte aligned");
+    const size_t rows = (size_t)T * N, nb = rows * 3 * 4, kb = rows * K * 4;
+    CSPLAT_REQUIRE(!traj_overlap(out, nb, points, nb) && !traj_overlap(out_d2, kb, points, nb) && !traj_overlap(out_idx, kb, points, nb) &&
+                       !traj_overlap(out, nb, out_d2, kb) && !traj_overlap(out, nb, out_idx, kb) && !traj_overlap(out_d2, kb, out_idx, kb),
+                   "csplat_traj_smooth: an output overlaps another operand");
+    // the weight's scale: 1 / (2 sigma^2) in double from the float32 sigma, rounded once to float32, at most FLT_MAX (0 * scale stays 0)
+    const double inv = 1.0 / (2.0 * (double)sigma * (double)sigma);
+    const float neg_scale = -(inv < (double)__FLT_MAX__ ? (float)inv : __FLT_MAX__);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_KNN, s);
+    const dim3 grid(cdiv(N, KNN_THREADS), T < 65535 ? T : 65535);
+#define LAUNCH(CAP) k_traj_smooth<CAP><<<grid, KNN_THREADS, 0, s>>>(T, N, K, points, neg_scale, out, out_d2, out_idx)
+    KNN_BY_CAPACITY(K, LAUNCH);
+#undef LAUNCH
+    LAUNCH_CHECK();
+    return 0;
+}

@@ -15,7 +15,8 @@ from csplat import native as _n
 
 
 def edge_features(pos, edge_index):
-    """[E, 4] = (pos[row] - pos[col], norm), row / col = edge_index[0] / [1] (PyG Cartesian + Distance, norm=False)"""
+    """[E, 4] = (pos[row] - pos[col], norm), row / col = edge_index[0] / [1] (PyG Cartesian + Distance, norm=False).  The sign is the
+    opposite of meshnet.data_utils.compute_edge_features (the reference's own: pos[edge_index[1]] - pos[edge_index[0]])."""
     if pos.is_cuda and pos.dtype == torch.float32 and edge_index.dtype == torch.int64:
         pos, edge_index = pos.contiguous(), edge_index.contiguous()
         E = int(edge_index.shape[1])

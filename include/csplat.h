@@ -837,6 +837,45 @@ int csplat_obs_voxel(void *stream, int64_t M, const float *points, float voxel, 
                      int32_t *count, int32_t *inverse, int32_t *n_voxels, int32_t *n_outside, void *temp);
 int csplat_obs_mark(void *stream, int64_t Q, int K, int N, const int32_t *idx, const float *d2, float max_sq_dist, uint8_t *flags);
 
+/* Trajectory preprocessing, the step between the sensing end and the planner (csplat_traj_smooth in csplat_knn.hip, csplat_traj_features in
+ * csplat_trajectory.hip): what turns a tracked cloud [T][N][3] into the smoothed positions, velocities and per-frame edge features the GNN and
+ * the planner read.  They restate the reference's host code: gaussian_smoothing (meshnet/data_utils.py:267-278, one KD-tree query per point
+ * per frame), the loop of process_traj (:307-348) and compute_edge_features (:443-448).  No gradients.  No atomics: every output element is
+ * written by one thread in a fixed order of operations, so every output is bit-reproducible run to run.  Float arithmetic without
+ * contraction, every operation one float32 rounding.  Every entry validates its arguments before any launch (a bad one returns non-zero
+ * and csplat_last_error() names the entry): sizes out of range, NULL operands, operands that are not 4-byte aligned (edge_index: 8), an
+ * output that shares a byte with another operand.
+ *
+ * csplat_traj_smooth: points [T][N][3], 1 <= K <= CSPLAT_KNN_MAX_K, sigma finite and > 0, T * N * K < 2^31.  For every frame t and point i:
+ * the K nearest points of frame t to point i -- the point itself included, at distance 0 -- ordered exactly as csplat_knn_query orders them:
+ * ascending in (d2, index), d2 = dx*dx + dy*dy + dz*dz with d = candidate - point, FP contraction off, ties to the smaller index.  No
+ * other frame is ever read.  A candidate whose d2 is not finite (a NaN or Inf coordinate, an overflow) is nobody's neighbour; with fewer
+ * than K neighbours (N < K among them) the remaining slots are (+inf, -1) as in csplat_knn_query and contribute nothing.  Weights:
+ *   c = 1 / (2 sigma^2), evaluated in double from the float32 sigma, rounded once to float32 and limited to FLT_MAX;
+ *   w_j = expf(-(d2_j * c)), the product rounded once to float32 (so w = 1 at d2 = 0 for every sigma; expf is the device library's);
+ *   out_i = (sum_j w_j p_j) / (sum_j w_j), per axis: each product w_j p_j rounded, added in the list's ascending order beginning with its
+ *   first term, one IEEE division at the end.  K = 1 returns the input bits.
+ * sum_j w_j >= 1 always (a point at distance 0 is in the list), so no division is by zero.  A point with a non-finite coordinate has an
+ * empty list and is written through unchanged.  out [T][N][3]; out_d2 [T][N][K] and out_idx [T][N][K] (int32) are optional (NULL: not
+ * wanted), each on its own.  T = 0 or N = 0 is a no-op without a launch.  One launch: the brute-force search of csplat_knn_query with the
+ * frame on the grid's second axis (frames beyond the axis limit are looped over) and the weighted mean formed from the K-best registers, K
+ * gathers from the frame.  Only the brute-force form exists, O(T N^2): tracked clouds are hundreds to a few thousand points.
+ *
+ * csplat_traj_features: pos [T][N][3], edge_index [2][E] (int64, entries in 0 .. N-1), T * N < 2^31, T * E < 2^31, inv_dt finite; ONE launch for
+ * all frames:
+ *   vel[0][i] = 0;  vel[t][i] = (pos[t][i] - pos[t-1][i]) * inv_dt, the difference and the product each rounded once
+ *   disp[t][e] = pos[t][edge_index[1][e]] - pos[t][edge_index[0][e]]  (receiver minus sender: the sign of the reference's
+ *                compute_edge_features, the OPPOSITE of csplat_gnn_edge_features / rollout.edge_features)
+ *   norm[t][e] = sqrtf(dx*dx + dy*dy + dz*dz), contraction off
+ * vel [T][N][3] is optional (NULL: not wanted); disp [T][E][3] and norm [T][E] are wanted together or not at all.  An edge_index entry
+ * outside 0 .. N-1 gives a NaN row and reads nothing (the Python surface checks the range).  T = 0 or N = 0 is a no-op without a launch, and
+ * so is a call that has nothing to write (E = 0 without vel); E = 0 with vel writes the velocities alone.
+ * Added exports: CSPLAT_ABI_VERSION is unchanged. */
+int csplat_traj_smooth(void *stream, int T, int N, int K, const float *points, float sigma, float *out, float *out_d2 /* or NULL */,
+                       int32_t *out_idx /* or NULL */);
+int csplat_traj_features(void *stream, int T, int N, int64_t E, const float *pos, const int64_t *edge_index, float inv_dt, float *vel /* or NULL */,
+                         float *disp, float *norm);
+
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
  *   csplat_mesh_rest       per-Gaussian constants of the REST face (in-plane basis, normal, in-plane coordinates) into
