@@ -76,7 +76,7 @@ class SimulatorStep(torch.autograd.Function):
         from meshnet import graph_ops as go
         ctx.sinks = tuple(_n.grad_sink(t) for t in (W1, b1, W2, b2, Wo, bo))       # (csplat.dist.FlatGrads: gradients written in place)
         e, W2s, h1, h2 = go._sim_hidden_fwd(e, W1, b1, W2, b2)
-        y, Wo = go._rows_dot_fwd(h2, Wo, bo, base)
+        y, h2, Wo = go._rows_dot_fwd(h2, Wo, bo, base)
         D = y.view(int(e.shape[0]), -1, 3)
         loss, grad = _cloth_regs_for(ctx, D, edge_index, rest_len, (lam_deform, lam_rigid, lam_mom), csr, defer)
         ctx.save_for_backward(e, W2s, h1, h2, Wo, grad)

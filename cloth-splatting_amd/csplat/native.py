@@ -267,6 +267,22 @@ def check(rc, what):
         raise CsplatError(f"{what} failed (rc={rc}): {lib.csplat_last_error().decode(errors='replace')}")
 
 
+def launch(name, device, *args):
+    """lib.<name>(current stream of `device`, *args) with `device` made current for the call when it is not already; a non-zero return
+    takes check()'s failure path (scratch caches evicted, CsplatError naming the entry).  `args` are what the C-ABI takes: plain integers,
+    floats and pointers (ptr(t)) -- nothing is converted here, the step is bound by the host.  For entries that take the stream they run on
+    as their first argument and are called when they are to run; a launch queued for later with a stream fixed earlier stays on check()."""
+    idx = device.index if isinstance(device, torch.device) else device
+    cur = torch.cuda.current_device()
+    if idx is None or idx == cur:
+        rc = getattr(lib, name)(stream_handle(cur), *args)
+    else:
+        with torch.cuda.device(idx):
+            rc = getattr(lib, name)(stream_handle(idx), *args)
+    if rc != 0:
+        check(rc, name)
+
+
 def ptr(t):
     """device pointer of a tensor (None -> NULL).  The tensor must be contiguous."""
     if t is None:
@@ -421,8 +437,7 @@ def group_by_key(keys, n_keys):
     rowptr = torch.empty(n_keys + 1, dtype=torch.int32, device=dev)
     perm = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
     tmp = torch.empty(max(int(lib.csplat_gnn_csr_temp_bytes(n_keys, E)), 256), dtype=torch.uint8, device=dev)
-    with on_device(dev):
-        check(lib.csplat_gnn_build_csr(stream_handle(dev), n_keys, E, ptr(keys), ptr(rowptr), ptr(perm), ptr(tmp)), "csplat_gnn_build_csr")
+    launch("csplat_gnn_build_csr", dev, n_keys, E, ptr(keys), ptr(rowptr), ptr(perm), ptr(tmp))
     return rowptr, perm[:E]
 
 

@@ -202,9 +202,7 @@ def smooth_clouds(points, k=20, sigma=0.1, return_neighbours=False):
             out = torch.empty_like(P)
             d2 = torch.empty(T, N, k, dtype=torch.float32, device=dev) if return_neighbours else None
             idx = torch.empty(T, N, k, dtype=torch.int32, device=dev) if return_neighbours else None
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_traj_smooth(_n.stream_handle(dev), T, N, k, _n.ptr(P), sg, _n.ptr(out), _n.ptr(d2), _n.ptr(idx)),
-                         "csplat_traj_smooth")
+            _n.launch("csplat_traj_smooth", dev, T, N, k, _n.ptr(P), sg, _n.ptr(out), _n.ptr(d2), _n.ptr(idx))
             res = (out, d2, None if idx is None else idx.to(torch.int64))
         else:
             _n.composed_fallback("data_utils.smooth_clouds", why, P)
@@ -253,9 +251,7 @@ def _features(P, ei, inv_dt, want_vel, want_edges):
             vel = torch.zeros(T, N, 3, dtype=dt, device=dev) if want_vel else None
             disp = torch.empty(T, E, 3, dtype=dt, device=dev) if want_edges else None
             norm = torch.empty(T, E, 1, dtype=dt, device=dev) if want_edges else None
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_traj_features(_n.stream_handle(dev), T, N, E, _n.ptr(P), _n.ptr(ei), inv_dt, _n.ptr(vel), _n.ptr(disp),
-                                                     _n.ptr(norm)), "csplat_traj_features")
+            _n.launch("csplat_traj_features", dev, T, N, E, _n.ptr(P), _n.ptr(ei), inv_dt, _n.ptr(vel), _n.ptr(disp), _n.ptr(norm))
             return vel, disp, norm
         _n.composed_fallback("data_utils.trajectory_features", why, P)
     vel = disp = norm = None

@@ -21,7 +21,18 @@ import torch
 import torch.nn as nn
 
 from .graph_ops import (EdgeCombine, EdgeFirstLayer, GraphCSR, SegmentSum, absmax, rows_chain, rows_chain_pack, edge_latent_linear, edge_mlp3, edge_mlp3_mode, edge_mlp3_pack, edge_tail_aggregate, gather_rows, mlp3_rows, node_update_pack, node_update_packed, segment_sum_rows, edge_tail_ok, linear_narrow128,
-                        layer_norm_rows, report_missed_edge_tail, linear128, linear_rows, node_update)
+                        layer_norm_rows, report_missed_edge_tail, linear128, linear_rows, node_update, _linears, is_mlp3_128)
+
+
+def _cached(owner, slot, key, build):
+    """owner.<slot>: what build() returned for `key` -- built again (under no_grad) only when `key` differs from the one it was built
+    for, which stays readable as owner.<slot>_key (a layer's node image is keyed on the next layer's `_wsplit_key`).  "Pack once per
+    weight version": keys hold the `_version` / `data_ptr()` of the weights and, for register images, edge_mlp3_mode()."""
+    if getattr(owner, slot + "_key", None) != key:
+        with torch.no_grad():
+            setattr(owner, slot, build())
+        setattr(owner, slot + "_key", key)
+    return getattr(owner, slot)
 
 
 def build_mlp(input_size: int, hidden_layer_sizes: List[int], output_size: int = None,
@@ -98,7 +109,7 @@ def _fusable(seq: nn.Sequential, width: int = 128) -> bool:
 
 def _fused_tail(seq: nn.Sequential, h: torch.Tensor, add_post: torch.Tensor = None) -> torch.Tensor:
     """layers 1.. of a _fusable MLP + its LayerNorm (+ a residual), in place on h (h = activated output of layer 0)."""
-    lins = list(seq[0].children())[0::2]
+    lins = _linears(seq[0])
     for i, lin in enumerate(lins[1:], start=1):
         last = i == len(lins) - 1
         h = linear128(h, lin.weight, lin.bias, relu=not last, layer_norm=seq[1] if last else None,
@@ -108,21 +119,19 @@ def _fused_tail(seq: nn.Sequential, h: torch.Tensor, add_post: torch.Tensor = No
 
 def _encode_inference(seq: nn.Sequential, x: torch.Tensor, x_absmax=None):
     """[build_mlp(K -> 128 -> ... -> 128), LayerNorm(128)] of an encoder under no_grad, or None when the shapes are not these"""
-    lins = list(seq[0].children())[0::2]
+    lins = _linears(seq[0])
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and 1 <= x.shape[1] <= 32 and len(lins) >= 2 and _fusable(seq)
             and tuple(lins[0].weight.shape) == (128, x.shape[1]) and lins[0].weight.dtype == torch.float32):
         return None
     if ENCODER_FUSED and len(lins) == 3 and x.shape[1] % 4 == 0 and x.shape[0] > 0 and edge_mlp3_mode() == 0:
         # the whole MLP + LayerNorm in ONE launch (csplat_gnn_mlp3_rows: the one-launch edge MLP's kernel on narrow rows, no gathers); the
         # first weight zero-padded to 128 columns, image packed once per weight version
-        key = tuple((l.weight._version, l.weight.data_ptr()) for l in lins)
-        if getattr(seq, "_mlp3_key", None) != key:
-            with torch.no_grad():
-                w0 = torch.zeros(128, 128, dtype=torch.float32, device=x.device)
-                w0[:, :x.shape[1]] = lins[0].weight
-                seq._mlp3_img = edge_mlp3_pack(w0, lins[1].weight, lins[2].weight)
-            seq._mlp3_key = key
-        return mlp3_rows(x, seq._mlp3_img, lins[0].bias, lins[1].bias, lins[2].bias, seq[1], x_absmax=x_absmax)
+        def pack():
+            w0 = torch.zeros(128, 128, dtype=torch.float32, device=x.device)
+            w0[:, :x.shape[1]] = lins[0].weight
+            return edge_mlp3_pack(w0, lins[1].weight, lins[2].weight)
+        image = _cached(seq, "_mlp3_img", tuple((l.weight._version, l.weight.data_ptr()) for l in lins), pack)
+        return mlp3_rows(x, image, lins[0].bias, lins[1].bias, lins[2].bias, seq[1], x_absmax=x_absmax)
     h = linear_narrow128(x, lins[0].weight, lins[0].bias, relu=True)
     return _fused_tail(seq, h)
 
@@ -241,33 +250,27 @@ class InteractionNetwork(nn.Module):
     def _split_weights(self):
         """contiguous column blocks of the two first-layer weights, re-cut only when an optimizer step changed them"""
         we, wn = self.edge_fn[0][0].weight, self.node_fn[0][0].weight
-        key = (we._version, wn._version, we.data_ptr(), wn.data_ptr())
-        if getattr(self, "_wsplit_key", None) != key:
-            n, a = self._nnode_in, wn.shape[1] - self._nnode_in
-            with torch.no_grad():
-                self._wsplit = tuple(t.contiguous() for t in (we[:, :n], we[:, n:2 * n], we[:, 2 * n:], wn[:, :a], wn[:, a:]))
-            self._wsplit_key = key
-        return self._wsplit
+        n, a = self._nnode_in, wn.shape[1] - self._nnode_in
+        return _cached(self, "_wsplit", (we._version, wn._version, we.data_ptr(), wn.data_ptr()),
+                       lambda: tuple(t.contiguous() for t in (we[:, :n], we[:, n:2 * n], we[:, 2 * n:], wn[:, :a], wn[:, a:])))
 
     def _node_image(self, w_agg, w_x, lins, next_layer, nw):
         """the packed register image of the node update's weights (+ the next layer's x_i / x_j blocks), re-packed only when one changed"""
         key = (self._wsplit_key, lins[1].weight._version, lins[2].weight._version, lins[1].weight.data_ptr(), lins[2].weight.data_ptr(),
                None if next_layer is None else next_layer._wsplit_key, edge_mlp3_mode())
-        if getattr(self, "_nimg_key", None) != key:
-            with torch.no_grad():
-                self._nimg = node_update_pack(w_agg, w_x, lins[1].weight, lins[2].weight, nw[0], nw[1])
-            self._nimg_key = key
-        return self._nimg
+        return _cached(self, "_nimg", key, lambda: node_update_pack(w_agg, w_x, lins[1].weight, lins[2].weight, nw[0], nw[1]))
 
     def _edge_image(self, w_e, elins):
         """the packed LDS image of the edge MLP's three weights, re-packed only when a weight changed"""
         key = (self._wsplit_key, elins[1].weight._version, elins[2].weight._version, elins[1].weight.data_ptr(), elins[2].weight.data_ptr(),
                edge_mlp3_mode())
-        if getattr(self, "_eimg_key", None) != key:
-            with torch.no_grad():
-                self._eimg = edge_mlp3_pack(w_e, elins[1].weight, elins[2].weight)
-            self._eimg_key = key
-        return self._eimg
+        return _cached(self, "_eimg", key, lambda: edge_mlp3_pack(w_e, elins[1].weight, elins[2].weight))
+
+    def first_products_image(self):
+        """the packed register image csplat_gnn_rows_chain (mode 0) forms both node-level products x W_i^T, x W_j^T of the first edge
+        Linear from, re-packed only when the weight or the arithmetic mode changed"""
+        w_i, w_j = self._split_weights()[:2]
+        return _cached(self, "_pair_img", (self._wsplit_key, edge_mlp3_mode()), lambda: rows_chain_pack(0, w_i, w_j))
 
     def forward_inference(self, x, edge_index, e0, scale: float, xa=None, xb=None, next_layer=None, e0_absmax=None, plan=None):
         """Same arithmetic as forward() for edge features scale * e0 (scale = 2^l after l layers), no autograd.
@@ -280,16 +283,11 @@ class InteractionNetwork(nn.Module):
         if xa is None and NODE_UPDATE_PACKED and x.shape[0] > 0:
             # both node-level products of the first layer in ONE launch on pre-packed 16-bit pieces (csplat_gnn_rows_chain, round 6: 8 us
             # against two exact-fp32 launches of 16 us at N = 10^4); later layers get theirs from the previous layer's node update
-            key = (self._wsplit_key, edge_mlp3_mode())
-            if getattr(self, "_pair_key", None) != key:
-                with torch.no_grad():
-                    self._pair_img = rows_chain_pack(0, w_i, w_j)
-                self._pair_key = key
-            xa, xb = rows_chain(x, self._pair_img, 0)
+            xa, xb = rows_chain(x, self.first_products_image(), 0)
         elif xa is None:
             xa = linear128(x, w_i)                               # contribution of x_i = x[edge_index[1]]
             xb = linear128(x, w_j)                               # contribution of x_j = x[edge_index[0]]
-        elins = list(self.edge_fn[0].children())[0::2]
+        elins = _linears(self.edge_fn[0])
         if len(elins) == 3 and EDGE_MLP_FUSED and _is_pow2(scale):
             # the whole message MLP + LayerNorm in ONE launch: the two inner [E,128] activations never leave the registers
             # (csplat_gnn_edge_mlp3; the weights' LDS image is packed once per weight version)
@@ -299,7 +297,7 @@ class InteractionNetwork(nn.Module):
                 edge_mlp3(e0, scale, xa, plan["dst"], xb, plan["src"], self._edge_image(w_e, elins), elins[0].bias, elins[1].bias,
                           elins[2].bias, self.edge_fn[1], e0_absmax=e0_absmax, agg=(plan["gp0"], pieces))
                 msg = None
-                lins_n = list(self.node_fn[0].children())[0::2]
+                lins_n = _linears(self.node_fn[0])
                 if NODE_UPDATE_PACKED and len(lins_n) == 3:
                     # ... added up by the node update's own row loader
                     nw = next_layer._split_weights() if next_layer is not None else (None, None)
@@ -314,7 +312,7 @@ class InteractionNetwork(nn.Module):
             msg = _fused_tail(self.edge_fn, h)
         if msg is not None:
             agg = SegmentSum.apply(msg, csr)
-        lins = list(self.node_fn[0].children())[0::2]
+        lins = _linears(self.node_fn[0])
         if len(lins) == 3:
             nw = next_layer._split_weights() if next_layer is not None else (None, None)
             if NODE_UPDATE_PACKED:
@@ -345,7 +343,7 @@ class Processor(nn.Module):
         return bool(len(self.gnn_stacks)) and all(g.inference_ok(x, edge_features) for g in self.gnn_stacks) and EDGE_MLP_FUSED and \
             EDGE_AGG_FUSED and edge_mlp3_mode() == 0 and edge_features.numel() > 0 and \
             edge_features.shape[0] // 8 + x.shape[0] + 8 < (1 << 22) and \
-            all(len(list(g.edge_fn[0].children())[0::2]) == 3 for g in self.gnn_stacks)
+            all(len(_linears(g.edge_fn[0])) == 3 for g in self.gnn_stacks)
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_features: torch.Tensor, edges_out: bool = True, dst_order=None,
                 first_products=None):
@@ -401,23 +399,21 @@ class Decoder(nn.Module):
         self.node_fn = build_mlp(nnode_in, [mlp_hidden_dim for _ in range(nmlp_layers)], nnode_out)
 
     def forward(self, x: torch.Tensor):
-        lins = list(self.node_fn.children())[0::2]
-        acts = list(self.node_fn.children())[1::2]
         if (not torch.is_grad_enabled()) and NODE_UPDATE_PACKED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and \
-                x.shape[0] > 0 and x.shape[1] == 128 and len(lins) == 3 and tuple(lins[0].weight.shape) == (128, 128) and \
-                tuple(lins[1].weight.shape) == (128, 128) and lins[2].in_features == 128 and \
-                isinstance(acts[0], nn.ReLU) and isinstance(acts[1], nn.ReLU) and isinstance(acts[2], nn.Identity) and \
-                lins[0].weight.dtype == torch.float32:
+                x.shape[0] > 0 and x.shape[1] == 128 and is_mlp3_128(self.node_fn, k_in=128):
             # rollout: the two hidden layers in ONE launch on pre-packed 16-bit pieces (csplat_gnn_rows_chain, round 6) instead of two
             # library GEMMs + two ReLU launches; the narrow last Linear stays the library's
-            key = tuple((l.weight._version, l.weight.data_ptr()) for l in lins[:2]) + (edge_mlp3_mode(),)
-            if getattr(self, "_chain_key", None) != key:
-                with torch.no_grad():
-                    self._chain_img = rows_chain_pack(1, lins[0].weight, lins[1].weight)
-                self._chain_key = key
-            h = rows_chain(x, self._chain_img, 1, lins[0].bias, lins[1].bias)
+            lins = _linears(self.node_fn)
+            h = rows_chain(x, self.hidden_image(), 1, lins[0].bias, lins[1].bias)
             return torch.nn.functional.linear(h, lins[2].weight, lins[2].bias)
         return self.node_fn(x)
+
+    def hidden_image(self):
+        """the packed register image csplat_gnn_rows_chain (mode 1) runs the two hidden layers from (an is_mlp3_128 decoder), re-packed
+        only when a weight or the arithmetic mode changed"""
+        lins = _linears(self.node_fn)
+        key = tuple((l.weight._version, l.weight.data_ptr()) for l in lins[:2]) + (edge_mlp3_mode(),)
+        return _cached(self, "_chain_img", key, lambda: rows_chain_pack(1, lins[0].weight, lins[1].weight))
 
 
 class EncodeProcessDecode(nn.Module):
@@ -440,12 +436,8 @@ class EncodeProcessDecode(nn.Module):
         sqrt(127) in magnitude, so max|gamma| * sqrt(127) + max|beta| bounds them -- what the one-launch edge MLP takes its fp16 scale from
         without a pass over the [E,128] latents (re-derived when the LayerNorm's parameters change)"""
         ln = self._encoder.edge_fn[1]
-        key = (ln.weight._version, ln.bias._version, ln.weight.data_ptr(), ln.weight.device)
-        if getattr(self, "_elb_key", None) != key:
-            with torch.no_grad():
-                self._elb = (ln.weight.abs().max() * (127.0 ** 0.5) + ln.bias.abs().max()).reshape(1).float().contiguous()
-            self._elb_key = key
-        return self._elb
+        return _cached(self, "_elb", (ln.weight._version, ln.bias._version, ln.weight.data_ptr(), ln.weight.device),
+                       lambda: (ln.weight.abs().max() * (127.0 ** 0.5) + ln.bias.abs().max()).reshape(1).float().contiguous())
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_features: torch.Tensor):
         """The rollout's default arithmetic multiplies with two fp16 pieces per operand (edge_mlp3_mode 0), whose exponent range a trained

@@ -25,13 +25,11 @@ class GraphCSR:
         dev = edge_index.device
         self.rowptr, self.perm = {}, {}
         tmp = torch.empty(max(int(_n.lib.csplat_gnn_csr_temp_bytes(self.N, self.E)), 256), dtype=torch.uint8, device=dev)
-        with _n.on_device(dev):
-            for name, row in (("src", 0), ("dst", 1)):
-                rp = torch.empty(self.N + 1, dtype=torch.int32, device=dev)
-                pm = torch.empty(max(self.E, 1), dtype=torch.int32, device=dev)
-                _n.check(_n.lib.csplat_gnn_build_csr(_n.stream_handle(dev), self.N, self.E, self.ei[row].data_ptr(),
-                                                     _n.ptr(rp), _n.ptr(pm), _n.ptr(tmp)), "csplat_gnn_build_csr")
-                self.rowptr[name], self.perm[name] = rp, pm
+        for name, row in (("src", 0), ("dst", 1)):
+            rp = torch.empty(self.N + 1, dtype=torch.int32, device=dev)
+            pm = torch.empty(max(self.E, 1), dtype=torch.int32, device=dev)      # (never an empty tensor: its pointer would be NULL)
+            _n.launch("csplat_gnn_build_csr", dev, self.N, self.E, self.ei[row].data_ptr(), _n.ptr(rp), _n.ptr(pm), _n.ptr(tmp))
+            self.rowptr[name], self.perm[name] = rp, pm
         self._deg_dst = None
 
     @property
@@ -92,6 +90,23 @@ def _i32_on(t, device, what):
     assert t.dtype == torch.int32 and t.is_contiguous() and t.device == device, f"{what}: a contiguous int32 tensor on {device}"
 
 
+def _linears(mlp):
+    """the Linear layers of a graph_network.build_mlp Sequential (Linear "NN-i" and activation "Act-i" alternate)"""
+    return list(mlp.children())[0::2]
+
+
+def is_mlp3_128(mlp, k_in=None, n_out=None):
+    """a build_mlp of three fp32 Linears k_in -> 128 -> 128 -> n_out (None: any width) with ReLU, ReLU, Identity behind them: the form
+    the one-launch kernels (csplat_gnn_mlp3_rows, csplat_gnn_rows_chain, csplat_gnn_edge_mlp3) are packed for"""
+    mods = list(mlp.children())
+    lins, acts = mods[0::2], mods[1::2]
+    return len(lins) == 3 and len(acts) == 3 and all(isinstance(m, torch.nn.Linear) for m in lins) and \
+        lins[0].out_features == 128 and tuple(lins[1].weight.shape) == (128, 128) and lins[2].in_features == 128 and \
+        (k_in is None or lins[0].in_features == k_in) and (n_out is None or lins[2].out_features == n_out) and \
+        isinstance(acts[0], torch.nn.ReLU) and isinstance(acts[1], torch.nn.ReLU) and isinstance(acts[2], torch.nn.Identity) and \
+        lins[0].weight.dtype == torch.float32
+
+
 def piece_numbering(dst_sorted, rowptr, group=8):
     """The numbering of the "pieces" the one-launch edge MLP leaves instead of messages (csplat_gnn_edge_mlp3 with `pieces`): rows are edges in
     destination order; a piece = a maximal run of rows with one destination, cut additionally at every multiple of `group` rows (a wave
@@ -121,10 +136,8 @@ class EdgeCombine(torch.autograd.Function):
         xa, xb, ec = _f32a(xa), _f32a(xb), _f32a(ec)
         E, L = ec.shape
         out = torch.empty_like(ec)
-        with _n.on_device(ec.device):
-            _n.check(_n.lib.csplat_gnn_edge_combine_fwd(_n.stream_handle(ec.device), csr.N, E, L, _n.ptr(csr.ei), _n.ptr(xa),
-                                                        _n.ptr(xb), _n.ptr(ec), int(relu), _n.ptr(out)),
-                     "csplat_gnn_edge_combine_fwd")
+        _n.launch("csplat_gnn_edge_combine_fwd", ec.device, csr.N, E, L, _n.ptr(csr.ei), _n.ptr(xa), _n.ptr(xb), _n.ptr(ec), int(relu),
+                  _n.ptr(out))
         ctx.csr, ctx.relu = csr, bool(relu) and not grad_premasked
         ctx.save_for_backward(out)
         return out
@@ -132,18 +145,21 @@ class EdgeCombine(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
-        csr = ctx.csr
         g = _f32a(g)
-        E, L = out.shape
         gm = torch.empty_like(g) if ctx.relu else g
-        dxa = torch.empty(csr.N, L, dtype=torch.float32, device=g.device)
-        dxb = torch.empty_like(dxa)
-        with _n.on_device(g.device):
-            _n.check(_n.lib.csplat_gnn_edge_combine_bwd(
-                _n.stream_handle(g.device), csr.N, E, L, _n.ptr(g), _n.ptr(out), int(ctx.relu), _n.ptr(csr.rowptr["dst"]),
-                _n.ptr(csr.perm["dst"]), _n.ptr(csr.rowptr["src"]), _n.ptr(csr.perm["src"]), _n.ptr(gm), _n.ptr(dxa),
-                _n.ptr(dxb)), "csplat_gnn_edge_combine_bwd")
+        dxa, dxb = _edge_combine_bwd(ctx.csr, g, out, ctx.relu, gm)
         return dxa, dxb, gm, None, None, None
+
+
+def _edge_combine_bwd(csr, g, out, relu, gm):
+    """(dxa, dxb) [N, L]: the gradient g [E, L] of an edge combine summed per destination / per source node (csplat_gnn_edge_combine_bwd).
+    relu: g is first masked by out > 0 and the masked rows are written to gm; without it out and gm may be None"""
+    E, L = g.shape
+    dxa = torch.empty(csr.N, L, dtype=torch.float32, device=g.device)
+    dxb = torch.empty_like(dxa)
+    _n.launch("csplat_gnn_edge_combine_bwd", g.device, csr.N, E, L, _n.ptr(g), _n.ptr(out), int(relu), _n.ptr(csr.rowptr["dst"]),
+              _n.ptr(csr.perm["dst"]), _n.ptr(csr.rowptr["src"]), _n.ptr(csr.perm["src"]), _n.ptr(gm), _n.ptr(dxa), _n.ptr(dxb))
+    return dxa, dxb
 
 
 class SegmentSum(torch.autograd.Function):
@@ -151,72 +167,27 @@ class SegmentSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, msg, csr):
-        msg = _f32a(msg)
-        E, L = msg.shape
-        agg = torch.empty(csr.N, L, dtype=torch.float32, device=msg.device)
-        with _n.on_device(msg.device):
-            _n.check(_n.lib.csplat_gnn_segment_sum(_n.stream_handle(msg.device), csr.N, E, L, _n.ptr(msg),
-                                                   _n.ptr(csr.rowptr["dst"]), _n.ptr(csr.perm["dst"]), _n.ptr(agg)),
-                     "csplat_gnn_segment_sum")
         ctx.csr = csr
-        return agg
+        return segment_sum_rows(msg, csr.rowptr["dst"], csr.perm["dst"], csr.N)
 
     @staticmethod
     def backward(ctx, g):
-        csr = ctx.csr
-        g = _f32a(g)
-        L = g.shape[1]
-        out = torch.empty(csr.E, L, dtype=torch.float32, device=g.device)
-        with _n.on_device(g.device):
-            _n.check(_n.lib.csplat_gnn_gather_rows(_n.stream_handle(g.device), csr.E, L, _n.ptr(g), csr.ei[1].data_ptr(),
-                                                   _n.ptr(out)), "csplat_gnn_gather_rows")
-        return out, None
-
-
-class RowsDot(torch.autograd.Function):
-    """y[T, R] = h[T, 256] @ W[R, 256]^T + b -- the simulator's 256 -> 3V output layer for the T time values of a step at once
-    (csplat_rows_dot_fwd / _bwd: the weight is streamed once per direction; deterministic)."""
-
-    @staticmethod
-    def forward(ctx, h, weight, bias, add=None):
-        h, weight, bias = _f32a(h), _f32a(weight), _f32(bias)
-        T, K = h.shape
-        R = weight.shape[0]
-        y = torch.empty(T, R, dtype=torch.float32, device=h.device)
-        add = None if add is None else _f32(add.reshape(T, R))
-        with _n.on_device(h.device):
-            _n.check(_n.lib.csplat_rows_dot_fwd(_n.stream_handle(h.device), T, R, K, _n.ptr(weight), _n.ptr(bias), _n.ptr(h),
-                                                _n.ptr(y), None if add is None else _n.ptr(add)), "csplat_rows_dot_fwd")
-        ctx.add_shape = None if add is None else add.shape
-        ctx.save_for_backward(h, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        h, weight = ctx.saved_tensors
-        g = _f32(g)
-        T, K = h.shape
-        R = weight.shape[0]
-        dW, db, dh = torch.empty_like(weight), torch.empty(R, dtype=torch.float32, device=g.device), torch.empty_like(h)
-        scratch = torch.empty(_n.lib.csplat_rows_dot_scratch_bytes(T), dtype=torch.uint8, device=g.device)
-        with _n.on_device(g.device):
-            _n.check(_n.lib.csplat_rows_dot_bwd(_n.stream_handle(g.device), T, R, K, _n.ptr(weight), _n.ptr(h), _n.ptr(g),
-                                                _n.ptr(dW), _n.ptr(db), _n.ptr(dh), _n.ptr(scratch)), "csplat_rows_dot_bwd")
-        return dh, dW, db, (g if ctx.add_shape is not None and ctx.needs_input_grad[3] else None)
+        return gather_rows(g, ctx.csr.ei[1]), None
 
 
 _SIMH_SCRATCH = {}
 _n.TICKET_CACHES.append(_SIMH_SCRATCH)
 
 
+# ---- the simulator's residual MLP: one forward / backward pair per kernel pair; RowsDot, SimHidden, SimResidual and
+# csplat.cloth_regs.SimulatorStep are autograd shells over them
 def _sim_hidden_fwd(e, W1, b1, W2, b2):
+    """csplat_sim_hidden_fwd -> (e, W2 as the kernels read them, h1, h2 [T, 256]): what _sim_hidden_bwd takes back"""
     e, W1, b1, W2, b2 = _f32(e), _f32(W1), _f32(b1), _f32a(W2), _f32(b2)
     T, K0 = int(e.shape[0]), int(e.shape[1])
     h1 = torch.empty(T, 256, dtype=torch.float32, device=e.device)
     h2 = torch.empty(T, 256, dtype=torch.float32, device=e.device)
-    with _n.on_device(e.device):
-        _n.check(_n.lib.csplat_sim_hidden_fwd(_n.stream_handle(e.device), T, K0, _n.ptr(e), _n.ptr(W1), _n.ptr(b1), _n.ptr(W2), _n.ptr(b2),
-                                              _n.ptr(h1), _n.ptr(h2)), "csplat_sim_hidden_fwd")
+    _n.launch("csplat_sim_hidden_fwd", e.device, T, K0, _n.ptr(e), _n.ptr(W1), _n.ptr(b1), _n.ptr(W2), _n.ptr(b2), _n.ptr(h1), _n.ptr(h2))
     return e, W2, h1, h2
 
 
@@ -228,15 +199,54 @@ def _sim_hidden_bwd(e, W2, h1, h2, g, sinks=(None, None, None, None)):
     dW1 = _n.grad_out(sinks[0], (256, K0), dev)
     dW2 = _n.grad_out(sinks[2], (256, 256), dev)
     db = [_n.grad_out(sinks[1], (256,), dev), _n.grad_out(sinks[3], (256,), dev)]
-    with _n.on_device(dev):
-        key = (str(dev), _n.scratch_stream(dev))
-        scratch = _SIMH_SCRATCH.get(key)        # zeroed once per stream: the kernel leaves its ticket word at zero
-        if scratch is None:
+    key = (str(dev), _n.scratch_stream(dev))
+    scratch = _SIMH_SCRATCH.get(key)        # zeroed once per stream: the kernel leaves its ticket word at zero
+    if scratch is None:
+        with _n.on_device(dev):       # (the zero fill runs on dev's current stream)
             scratch = _SIMH_SCRATCH[key] = torch.zeros(int(_n.lib.csplat_sim_hidden_scratch_bytes(8)) // 4, dtype=torch.int32, device=dev)
-        _n.check(_n.lib.csplat_sim_hidden_bwd(_n.stream_handle(dev), T, K0, _n.ptr(e), _n.ptr(W2), _n.ptr(h1), _n.ptr(h2), _n.ptr(g),
-                                                       _n.ptr(dW1), _n.ptr(db[0]), _n.ptr(dW2), _n.ptr(db[1]), _n.ptr(scratch)),
-                 "csplat_sim_hidden_bwd")
+    _n.launch("csplat_sim_hidden_bwd", dev, T, K0, _n.ptr(e), _n.ptr(W2), _n.ptr(h1), _n.ptr(h2), _n.ptr(g), _n.ptr(dW1), _n.ptr(db[0]),
+              _n.ptr(dW2), _n.ptr(db[1]), _n.ptr(scratch))
     return dW1, db[0], dW2, db[1]
+
+
+def _rows_dot_fwd(h, W, b, base=None):
+    """csplat_rows_dot_fwd: y [T, R] = h [T, K] @ W [R, K]^T + b [+ base, T * R elements] -> (y, h and W as the kernels read them)"""
+    h, W, b = _f32a(h), _f32a(W), _f32(b)
+    T, K, R = int(h.shape[0]), int(h.shape[1]), int(W.shape[0])
+    y = torch.empty(T, R, dtype=torch.float32, device=h.device)
+    add = None if base is None else _f32(base.reshape(T, R))
+    _n.launch("csplat_rows_dot_fwd", h.device, T, R, K, _n.ptr(W), _n.ptr(b), _n.ptr(h), _n.ptr(y), _n.ptr(add))
+    return y, h, W
+
+
+def _rows_dot_bwd(W, h, g, sinks=(None, None)):
+    """csplat_rows_dot_bwd for the gradient g (T * R elements) of _rows_dot_fwd's y -> (dW, db, dh); sinks: grad_sink keys of (W, b)"""
+    g, W, h = _f32(g), _f32a(W), _f32a(h)
+    T, K, R = int(h.shape[0]), int(h.shape[1]), int(W.shape[0])
+    dW, db, dh = _n.grad_out(sinks[0], W.shape, g.device), _n.grad_out(sinks[1], (R,), g.device), torch.empty_like(h)
+    scratch = torch.empty(_n.lib.csplat_rows_dot_scratch_bytes(T), dtype=torch.uint8, device=g.device)
+    _n.launch("csplat_rows_dot_bwd", g.device, T, R, K, _n.ptr(W), _n.ptr(h), _n.ptr(g.reshape(T, R)), _n.ptr(dW), _n.ptr(db), _n.ptr(dh),
+              _n.ptr(scratch))
+    return dW, db, dh
+
+
+class RowsDot(torch.autograd.Function):
+    """y[T, R] = h[T, 256] @ W[R, 256]^T + b -- the simulator's 256 -> 3V output layer for the T time values of a step at once
+    (csplat_rows_dot_fwd / _bwd: the weight is streamed once per direction; deterministic)."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, add=None):
+        y, h, weight = _rows_dot_fwd(h, weight, bias, add)
+        ctx.has_add = add is not None
+        ctx.save_for_backward(h, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        h, weight = ctx.saved_tensors
+        g = _f32(g)
+        dW, db, dh = _rows_dot_bwd(weight, h, g)
+        return dh, dW, db, (g if ctx.has_add and ctx.needs_input_grad[3] else None)
 
 
 class SimHidden(torch.autograd.Function):
@@ -254,35 +264,6 @@ class SimHidden(torch.autograd.Function):
         return (None,) + _sim_hidden_bwd(*ctx.saved_tensors, g)
 
 
-def _rows_dot_fwd(h2, Wo, bo, base=None):
-    h2, Wo, bo = _f32a(h2), _f32a(Wo), _f32(bo)
-    T, R = int(h2.shape[0]), int(Wo.shape[0])
-    y = torch.empty(T, R, dtype=torch.float32, device=h2.device)
-    add = None if base is None else _f32(base.reshape(T, R))
-    with _n.on_device(h2.device):
-        _n.check(_n.lib.csplat_rows_dot_fwd(_n.stream_handle(h2.device), T, R, 256, _n.ptr(Wo), _n.ptr(bo), _n.ptr(h2), _n.ptr(y),
-                                            None if add is None else _n.ptr(add)), "csplat_rows_dot_fwd")
-    return y, Wo
-
-
-def _rows_dot_bwd(Wo, h2, g, sinks=(None, None)):
-    g, Wo, h2 = _f32(g), _f32a(Wo), _f32a(h2)
-    T, R = int(h2.shape[0]), int(Wo.shape[0])
-    dWo, dbo, dh = _n.grad_out(sinks[0], Wo.shape, g.device), _n.grad_out(sinks[1], (R,), g.device), torch.empty_like(h2)
-    scratch = torch.empty(_n.lib.csplat_rows_dot_scratch_bytes(T), dtype=torch.uint8, device=g.device)
-    with _n.on_device(g.device):
-        _n.check(_n.lib.csplat_rows_dot_bwd(_n.stream_handle(g.device), T, R, 256, _n.ptr(Wo), _n.ptr(h2), _n.ptr(g.reshape(T, R)),
-                                            _n.ptr(dWo), _n.ptr(dbo), _n.ptr(dh), _n.ptr(scratch)), "csplat_rows_dot_bwd")
-    return dWo, dbo, dh
-
-
-def sim_residual_applies(e, lin1, lin2, lin_out, base=None):
-    return bool(e.is_cuda and e.dim() == 2 and 0 < e.shape[0] <= 8 and e.shape[1] <= 16 and tuple(lin1.weight.shape) == (256, e.shape[1]) and
-                tuple(lin2.weight.shape) == (256, 256) and lin1.bias is not None and lin2.bias is not None and not e.requires_grad and
-                lin_out.weight.shape[1] == 256 and lin_out.bias is not None and
-                (base is None or (base.is_cuda and base.numel() == e.shape[0] * lin_out.weight.shape[0])))
-
-
 class SimResidual(torch.autograd.Function):
     """the simulator's whole residual MLP for the T time rows of a step as ONE autograd node:
         y = Linear(256, 3V)(relu(Linear(256, 256)(relu(Linear(K0, 256)(e))))) [+ base]          (meshnet_network.py:337-339,364-371)
@@ -292,13 +273,7 @@ class SimResidual(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, W1, b1, W2, b2, Wo, bo, base=None):
         e, W2, h1, h2 = _sim_hidden_fwd(e, W1, b1, W2, b2)
-        Wo, bo = _f32a(Wo), _f32(bo)
-        T, R = int(h2.shape[0]), int(Wo.shape[0])
-        y = torch.empty(T, R, dtype=torch.float32, device=h2.device)
-        add = None if base is None else _f32(base.reshape(T, R))
-        with _n.on_device(h2.device):
-            _n.check(_n.lib.csplat_rows_dot_fwd(_n.stream_handle(h2.device), T, R, 256, _n.ptr(Wo), _n.ptr(bo), _n.ptr(h2), _n.ptr(y),
-                                                None if add is None else _n.ptr(add)), "csplat_rows_dot_fwd")
+        y, h2, Wo = _rows_dot_fwd(h2, Wo, bo, base)
         ctx.save_for_backward(e, W2, h1, h2, Wo)
         ctx.has_base = base is not None
         return y
@@ -307,22 +282,29 @@ class SimResidual(torch.autograd.Function):
     def backward(ctx, g):
         e, W2, h1, h2, Wo = ctx.saved_tensors
         g = _f32(g)
-        T, R = int(h2.shape[0]), int(Wo.shape[0])
-        dWo, dbo, dh = torch.empty_like(Wo), torch.empty(R, dtype=torch.float32, device=g.device), torch.empty_like(h2)
-        scratch = torch.empty(_n.lib.csplat_rows_dot_scratch_bytes(T), dtype=torch.uint8, device=g.device)
-        with _n.on_device(g.device):
-            _n.check(_n.lib.csplat_rows_dot_bwd(_n.stream_handle(g.device), T, R, 256, _n.ptr(Wo), _n.ptr(h2), _n.ptr(g),
-                                                _n.ptr(dWo), _n.ptr(dbo), _n.ptr(dh), _n.ptr(scratch)), "csplat_rows_dot_bwd")
+        dWo, dbo, dh = _rows_dot_bwd(Wo, h2, g)
         dW1, db1, dW2, db2 = _sim_hidden_bwd(e, W2, h1, h2, dh)
         return None, dW1, db1, dW2, db2, dWo, dbo, (g if ctx.has_base and ctx.needs_input_grad[7] else None)
 
 
+def sim_hidden_applies(e, lin1, lin2):
+    """csplat_sim_hidden_fwd / _bwd cover these: T <= 8 GPU rows of a code of K0 <= 16 values that takes no gradient, through
+    Linear(K0, 256) and Linear(256, 256) with biases"""
+    return bool(e.is_cuda and e.dim() == 2 and 0 < e.shape[0] <= 8 and e.shape[1] <= 16 and tuple(lin1.weight.shape) == (256, e.shape[1]) and
+                tuple(lin2.weight.shape) == (256, 256) and lin1.bias is not None and lin2.bias is not None and not e.requires_grad)
+
+
+def sim_residual_applies(e, lin1, lin2, lin_out, base=None):
+    """... and csplat_rows_dot_fwd / _bwd behind them: an output layer of 256 columns with a bias, `base` (if any) on the GPU with one
+    value per output"""
+    return sim_hidden_applies(e, lin1, lin2) and bool(
+        lin_out.weight.shape[1] == 256 and lin_out.bias is not None and
+        (base is None or (base.is_cuda and base.numel() == e.shape[0] * lin_out.weight.shape[0])))
+
+
 def sim_residual(e, lin1, lin2, lin_out, base=None):
     """rows_dot(sim_hidden(e, lin1, lin2), lin_out.weight, lin_out.bias, base) as one autograd node when both fused forms apply"""
-    if e.is_cuda and e.dim() == 2 and 0 < e.shape[0] <= 8 and e.shape[1] <= 16 and tuple(lin1.weight.shape) == (256, e.shape[1]) and \
-            tuple(lin2.weight.shape) == (256, 256) and lin1.bias is not None and lin2.bias is not None and not e.requires_grad and \
-            lin_out.weight.shape[1] == 256 and lin_out.bias is not None and \
-            (base is None or (base.is_cuda and base.numel() == e.shape[0] * lin_out.weight.shape[0])):
+    if sim_residual_applies(e, lin1, lin2, lin_out, base):
         return SimResidual.apply(e, lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin_out.weight, lin_out.bias, base)
     return rows_dot(sim_hidden(e, lin1, lin2), lin_out.weight, lin_out.bias, base)
 
@@ -330,8 +312,7 @@ def sim_residual(e, lin1, lin2, lin_out, base=None):
 def sim_hidden(e, lin1, lin2):
     """relu(lin2(relu(lin1(e)))) for the simulator's two hidden layers; the fused HIP form for T <= 8 fp32 GPU rows of the reference's
     shape (K0 <= 16 -> 256 -> 256), composed torch otherwise"""
-    if e.is_cuda and e.dim() == 2 and 0 < e.shape[0] <= 8 and e.shape[1] <= 16 and tuple(lin1.weight.shape) == (256, e.shape[1]) and \
-            tuple(lin2.weight.shape) == (256, 256) and lin1.bias is not None and lin2.bias is not None and not e.requires_grad:
+    if sim_hidden_applies(e, lin1, lin2):
         return SimHidden.apply(e, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
     _n.composed_fallback("graph_ops.sim_hidden", "shape", e)
     return torch.relu(lin2(torch.relu(lin1(e))))
@@ -404,11 +385,9 @@ def linear128(A, weight, bias=None, alpha=1.0, relu=False, gather=None, layer_no
     stats_out = ln_stats
     if ln_stats is not None and (not ln_stats.is_contiguous() or ln_stats.data_ptr() % 8):      # (written as float2: through a temporary)
         stats_out = torch.empty(ln_stats.shape, dtype=torch.float32, device=ln_stats.device)
-    with _n.on_device(A.device):
-        _n.check(_n.lib.csplat_linear128_ex(_n.stream_handle(A.device), M, _n.ptr(A), weight.data_ptr(), ldw, wt, _n.ptr(bias), float(alpha),
-                                            int(relu), _n.ptr(ga), _n.ptr(ia), _n.ptr(gb), _n.ptr(ib), _n.ptr(g), _n.ptr(b), eps,
-                                            _n.ptr(add_pre), _n.ptr(add_post), _n.ptr(mask), _n.ptr(stats_out), _n.ptr(out)),
-                 "csplat_linear128_ex")
+    _n.launch("csplat_linear128_ex", A.device, M, _n.ptr(A), weight.data_ptr(), ldw, wt, _n.ptr(bias), float(alpha), int(relu), _n.ptr(ga),
+              _n.ptr(ia), _n.ptr(gb), _n.ptr(ib), _n.ptr(g), _n.ptr(b), eps, _n.ptr(add_pre), _n.ptr(add_post), _n.ptr(mask),
+              _n.ptr(stats_out), _n.ptr(out))
     if stats_out is not ln_stats:
         ln_stats.copy_(stats_out)
     return out
@@ -424,10 +403,8 @@ def linear_narrow128(x, weight, bias=None, relu=False):
     w = w if w.stride(1) == 1 else w.contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     out = torch.empty(x.shape[0], 128, dtype=torch.float32, device=x.device)
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_linear_narrow128(_n.stream_handle(x.device), x.shape[0], x.shape[1], _n.ptr(x), int(x.stride(0)) if x.shape[0] > 1 else x.shape[1],
-                                                w.data_ptr(), int(w.stride(0)), _n.ptr(bias), int(relu), _n.ptr(out)),
-                 "csplat_linear_narrow128")
+    _n.launch("csplat_linear_narrow128", x.device, x.shape[0], x.shape[1], _n.ptr(x), int(x.stride(0)) if x.shape[0] > 1 else x.shape[1],
+              w.data_ptr(), int(w.stride(0)), _n.ptr(bias), int(relu), _n.ptr(out))
     return out
 
 
@@ -438,14 +415,11 @@ def gather_rows(rows, keys, with_absmax=False):
     rows, keys = _f32a(rows), keys.contiguous()
     assert keys.dtype == torch.int64
     out = torch.empty(keys.numel(), rows.shape[1], dtype=torch.float32, device=rows.device)
-    with _n.on_device(rows.device):
-        if with_absmax:
-            am = torch.empty(1, dtype=torch.float32, device=rows.device)
-            _n.check(_n.lib.csplat_gnn_gather_rows_absmax(_n.stream_handle(rows.device), keys.numel(), rows.shape[1], _n.ptr(rows), _n.ptr(keys),
-                                                          _n.ptr(out), _n.ptr(am)), "csplat_gnn_gather_rows_absmax")
-            return out, am
-        _n.check(_n.lib.csplat_gnn_gather_rows(_n.stream_handle(rows.device), keys.numel(), rows.shape[1], _n.ptr(rows), _n.ptr(keys), _n.ptr(out)),
-                 "csplat_gnn_gather_rows")
+    if with_absmax:
+        am = torch.empty(1, dtype=torch.float32, device=rows.device)
+        _n.launch("csplat_gnn_gather_rows_absmax", rows.device, keys.numel(), rows.shape[1], _n.ptr(rows), _n.ptr(keys), _n.ptr(out), _n.ptr(am))
+        return out, am
+    _n.launch("csplat_gnn_gather_rows", rows.device, keys.numel(), rows.shape[1], _n.ptr(rows), _n.ptr(keys), _n.ptr(out))
     return out
 
 
@@ -453,9 +427,7 @@ def segment_sum_rows(rows, rowptr, perm, N):
     """out[v] = sum of rows[perm[rowptr[v] .. rowptr[v + 1] - 1]] in that order (csplat_gnn_segment_sum), no autograd"""
     rows = _f32a(rows)
     out = torch.empty(N, rows.shape[1], dtype=torch.float32, device=rows.device)
-    with _n.on_device(rows.device):
-        _n.check(_n.lib.csplat_gnn_segment_sum(_n.stream_handle(rows.device), N, rows.shape[0], rows.shape[1], _n.ptr(rows), _n.ptr(rowptr), _n.ptr(perm),
-                                               _n.ptr(out)), "csplat_gnn_segment_sum")
+    _n.launch("csplat_gnn_segment_sum", rows.device, N, rows.shape[0], rows.shape[1], _n.ptr(rows), _n.ptr(rowptr), _n.ptr(perm), _n.ptr(out))
     return out
 
 
@@ -473,8 +445,7 @@ def absmax(x):
     x = _f32a(x)
     assert x.numel() % 4 == 0
     out = torch.empty(1, dtype=torch.float32, device=x.device)
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_absmax(_n.stream_handle(x.device), x.numel(), _n.ptr(x), _n.ptr(out)), "csplat_absmax")
+    _n.launch("csplat_absmax", x.device, x.numel(), _n.ptr(x), _n.ptr(out))
     return out
 
 
@@ -490,10 +461,8 @@ def edge_mlp3_pack(w0, w1, w2):
         if not (w.stride(1) == 1 and w.stride(0) >= 128):
             w = w.contiguous()
         ws.append(w)
-    with _n.on_device(w0.device):
-        _n.check(_n.lib.csplat_gnn_edge_mlp3_pack(_n.stream_handle(w0.device), ws[0].data_ptr(), int(ws[0].stride(0)), ws[1].data_ptr(),
-                                                  int(ws[1].stride(0)), ws[2].data_ptr(), int(ws[2].stride(0)), _n.ptr(img)),
-                 "csplat_gnn_edge_mlp3_pack")
+    _n.launch("csplat_gnn_edge_mlp3_pack", w0.device, ws[0].data_ptr(), int(ws[0].stride(0)), ws[1].data_ptr(), int(ws[1].stride(0)),
+              ws[2].data_ptr(), int(ws[2].stride(0)), _n.ptr(img))
     return img
 
 
@@ -524,11 +493,8 @@ def edge_mlp3(e0, alpha, xa, ia, xb, ib, image, b0, b1, b2, layer_norm, out=None
     if e0_absmax is None and E > 0 and edge_mlp3_mode() == 0:
         e0_absmax = absmax(e0)
     vs = [_vec(t) for t in (b0, b1, b2, layer_norm.weight, layer_norm.bias)]       # (a copy must outlive the launch call: held here)
-    with _n.on_device(e0.device):
-        _n.check(_n.lib.csplat_gnn_edge_mlp3(_n.stream_handle(e0.device), E, _n.ptr(e0), float(alpha), _n.ptr(e0_absmax), _n.ptr(xa), _n.ptr(ia),
-                                             _n.ptr(xb), _n.ptr(ib), _n.ptr(image), *[_n.ptr(t) for t in vs], float(layer_norm.eps), _n.ptr(out),
-                                             _n.ptr(gp0), _n.ptr(pieces)),
-                 "csplat_gnn_edge_mlp3")
+    _n.launch("csplat_gnn_edge_mlp3", e0.device, E, _n.ptr(e0), float(alpha), _n.ptr(e0_absmax), _n.ptr(xa), _n.ptr(ia), _n.ptr(xb), _n.ptr(ib),
+              _n.ptr(image), *[_n.ptr(t) for t in vs], float(layer_norm.eps), _n.ptr(out), _n.ptr(gp0), _n.ptr(pieces))
     return out if agg is None else pieces
 
 
@@ -548,10 +514,8 @@ def node_update(agg, x, w_agg, w_x, b0, lin2, lin3, layer_norm, w_i_next=None, w
     ops = [c(w_agg), c(w_x), c(b0), c(lin2.weight), c(lin2.bias), c(lin3.weight), c(lin3.bias), c(layer_norm.weight),
            c(layer_norm.bias)]
     nxt = [c(w_i_next), c(w_j_next)] if have_next else [None, None]
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_node_update(_n.stream_handle(x.device), N, _n.ptr(agg), _n.ptr(x), *[_n.ptr(t) for t in ops],
-                                               float(layer_norm.eps), _n.ptr(nxt[0]), _n.ptr(nxt[1]), _n.ptr(x_new), _n.ptr(xa),
-                                               _n.ptr(xb)), "csplat_gnn_node_update")
+    _n.launch("csplat_gnn_node_update", x.device, N, _n.ptr(agg), _n.ptr(x), *[_n.ptr(t) for t in ops], float(layer_norm.eps), _n.ptr(nxt[0]),
+              _n.ptr(nxt[1]), _n.ptr(x_new), _n.ptr(xa), _n.ptr(xb))
     return x_new, xa, xb
 
 
@@ -567,10 +531,8 @@ def mlp3_rows(x, image, b0, b1, b2, layer_norm, x_absmax=None):
     if x_absmax is None and M > 0:
         x_absmax = absmax(x)
     vs = [_vec(t) for t in (b0, b1, b2, layer_norm.weight, layer_norm.bias)]       # (a copy must outlive the launch call: held here)
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_mlp3_rows(_n.stream_handle(x.device), M, _n.ptr(x), K, _n.ptr(x_absmax), _n.ptr(image), *[_n.ptr(t) for t in vs],
-                                             float(layer_norm.eps), _n.ptr(out)),
-                 "csplat_gnn_mlp3_rows")
+    _n.launch("csplat_gnn_mlp3_rows", x.device, M, _n.ptr(x), K, _n.ptr(x_absmax), _n.ptr(image), *[_n.ptr(t) for t in vs],
+              float(layer_norm.eps), _n.ptr(out))
     return out
 
 
@@ -582,8 +544,7 @@ def node_update_pack(w_agg, w_x, w2, w3, w_i_next=None, w_j_next=None):
     ws = [c(t) for t in (w_agg, w_x, w2, w3, w_i_next, w_j_next)]
     for t in ws[:4]:
         assert tuple(t.shape) == (128, 128) and t.dtype == torch.float32 and t.is_cuda
-    with _n.on_device(w_agg.device):
-        _n.check(_n.lib.csplat_gnn_node_update_pack(_n.stream_handle(w_agg.device), *[_n.ptr(t) for t in ws], _n.ptr(img)), "csplat_gnn_node_update_pack")
+    _n.launch("csplat_gnn_node_update_pack", w_agg.device, *[_n.ptr(t) for t in ws], _n.ptr(img))
     return img
 
 
@@ -593,8 +554,7 @@ def rows_chain_pack(mode, w_first, w_second):
     img = torch.empty(int(_n.lib.csplat_gnn_node_update_image_bytes()), dtype=torch.uint8, device=w_first.device)
     a, b = w_first.detach().contiguous(), w_second.detach().contiguous()
     assert tuple(a.shape) == (128, 128) and tuple(b.shape) == (128, 128) and a.dtype == torch.float32 and a.is_cuda
-    with _n.on_device(a.device):
-        _n.check(_n.lib.csplat_gnn_rows_chain_pack(_n.stream_handle(a.device), int(mode), _n.ptr(a), _n.ptr(b), _n.ptr(img)), "csplat_gnn_rows_chain_pack")
+    _n.launch("csplat_gnn_rows_chain_pack", a.device, int(mode), _n.ptr(a), _n.ptr(b), _n.ptr(img))
     return img
 
 
@@ -607,9 +567,8 @@ def rows_chain(x, image, mode, b0=None, b1=None):
     out_a = torch.empty_like(x)
     out_b = torch.empty_like(x) if mode == 0 else None
     vs = [_vec(b0), _vec(b1)]       # (a copy must outlive the launch call: held here)
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_rows_chain(_n.stream_handle(x.device), N, int(mode), _n.ptr(x), _n.ptr(image), _n.ptr(vs[0]), _n.ptr(vs[1]),
-                                              _n.ptr(out_a), _n.ptr(out_b)), "csplat_gnn_rows_chain")
+    _n.launch("csplat_gnn_rows_chain", x.device, N, int(mode), _n.ptr(x), _n.ptr(image), _n.ptr(vs[0]), _n.ptr(vs[1]), _n.ptr(out_a),
+              _n.ptr(out_b))
     return (out_a, out_b) if mode == 0 else out_a
 
 
@@ -627,9 +586,8 @@ def node_update_packed(agg, x, image, b0, b2, b3, layer_norm, has_next, piece_pt
     x_new = torch.empty_like(x)
     xa = torch.empty_like(x) if has_next else None
     xb = torch.empty_like(x) if has_next else None
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_gnn_node_update_packed(_n.stream_handle(x.device), N, _n.ptr(agg), _n.ptr(x), _n.ptr(image), *[_n.ptr(t) for t in vs], float(layer_norm.eps),
-                                                      int(bool(has_next)), _n.ptr(x_new), _n.ptr(xa), _n.ptr(xb), _n.ptr(piece_ptr)), "csplat_gnn_node_update_packed")
+    _n.launch("csplat_gnn_node_update_packed", x.device, N, _n.ptr(agg), _n.ptr(x), _n.ptr(image), *[_n.ptr(t) for t in vs],
+              float(layer_norm.eps), int(bool(has_next)), _n.ptr(x_new), _n.ptr(xa), _n.ptr(xb), _n.ptr(piece_ptr))
     return x_new, xa, xb
 
 
@@ -638,9 +596,7 @@ def ln128_fwd(x, gamma, beta, eps):
     M = x.shape[0]
     y = torch.empty_like(x)
     stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_ln128_fwd(_n.stream_handle(x.device), M, _n.ptr(x), _n.ptr(gamma), _n.ptr(beta), float(eps), _n.ptr(y),
-                                         _n.ptr(stats)), "csplat_ln128_fwd")
+    _n.launch("csplat_ln128_fwd", x.device, M, _n.ptr(x), _n.ptr(gamma), _n.ptr(beta), float(eps), _n.ptr(y), _n.ptr(stats))
     return y, stats
 
 
@@ -656,10 +612,8 @@ def ln128_bwd(g, x, stats, gamma, want_dxsum=False, g_rows=None, x_normalized=Fa
     dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
     dxsum = torch.empty_like(gamma) if want_dxsum else None
     part = torch.empty(3 * int(_n.lib.csplat_ln128_partial_floats(M)), dtype=torch.float32, device=x.device)
-    with _n.on_device(x.device):
-        _n.check(_n.lib.csplat_ln128_bwd(_n.stream_handle(x.device), M, _n.ptr(g), _n.ptr(x), _n.ptr(stats), _n.ptr(gamma), _n.ptr(dx),
-                                         _n.ptr(dgamma), _n.ptr(dbeta), _n.ptr(dxsum), _n.ptr(g_rows), int(x_normalized), _n.ptr(part)),
-                 "csplat_ln128_bwd")
+    _n.launch("csplat_ln128_bwd", x.device, M, _n.ptr(g), _n.ptr(x), _n.ptr(stats), _n.ptr(gamma), _n.ptr(dx), _n.ptr(dgamma), _n.ptr(dbeta),
+              _n.ptr(dxsum), _n.ptr(g_rows), int(x_normalized), _n.ptr(part))
     return dx, dgamma, dbeta, dxsum
 
 
@@ -698,9 +652,7 @@ def relu_mask_bias128(g, out):
     gm = torch.empty_like(g) if out is not None else None
     db = torch.empty(128, dtype=torch.float32, device=g.device)
     part = torch.empty(int(_n.lib.csplat_ln128_partial_floats(M)), dtype=torch.float32, device=g.device)
-    with _n.on_device(g.device):
-        _n.check(_n.lib.csplat_relu_mask_bias128(_n.stream_handle(g.device), M, _n.ptr(g), _n.ptr(out), _n.ptr(gm), _n.ptr(db), _n.ptr(part)),
-                 "csplat_relu_mask_bias128")
+    _n.launch("csplat_relu_mask_bias128", g.device, M, _n.ptr(g), _n.ptr(out), _n.ptr(gm), _n.ptr(db), _n.ptr(part))
     return (gm if gm is not None else g), db
 
 
@@ -712,9 +664,7 @@ def dw128(g, x, bias=False, x_relu=False):
     dW = torch.empty(128, 128, dtype=torch.float32, device=g.device)
     db = torch.empty(128, dtype=torch.float32, device=g.device) if bias else None
     ws = torch.empty(max(int(_n.lib.csplat_dw128_workspace_bytes(M)), 256), dtype=torch.uint8, device=g.device)
-    with _n.on_device(g.device):
-        _n.check(_n.lib.csplat_dw128_bias(_n.stream_handle(g.device), M, _n.ptr(g), _n.ptr(x), int(x_relu), _n.ptr(dW), _n.ptr(db), _n.ptr(ws)),
-                 "csplat_dw128_bias")
+    _n.launch("csplat_dw128_bias", g.device, M, _n.ptr(g), _n.ptr(x), int(x_relu), _n.ptr(dW), _n.ptr(db), _n.ptr(ws))
     return (dW, db) if bias else dW
 
 
@@ -808,11 +758,7 @@ class EdgeTailAggregate(torch.autograd.Function):
         stats = torch.empty(E, 2, dtype=torch.float32, device=a0.device)
         unit = _unit_ln(a0.device, eps)
         xhat = linear128(acts[-1], wb[2 * k - 2], wb[2 * k - 1], layer_norm=unit, ln_stats=stats)
-        S = torch.empty(csr.N, 128, dtype=torch.float32, device=a0.device)
-        with _n.on_device(a0.device):
-            _n.check(_n.lib.csplat_gnn_segment_sum(_n.stream_handle(a0.device), csr.N, E, 128, _n.ptr(xhat),
-                                                   _n.ptr(csr.rowptr["dst"]), _n.ptr(csr.perm["dst"]), _n.ptr(S)),
-                     "csplat_gnn_segment_sum")
+        S = segment_sum_rows(xhat, csr.rowptr["dst"], csr.perm["dst"], csr.N)
         ctx.csr, ctx.k, ctx.a0_relu, ctx.unit = csr, k, bool(a0_relu), unit
         ctx.save_for_backward(stats, xhat, *acts, *wb[0::2])
         return S
@@ -836,6 +782,23 @@ class EdgeTailAggregate(torch.autograd.Function):
         return (d if ctx.needs_input_grad[0] else None, None, None, None, *grads)
 
 
+def _edge_latent_bwd(ctx, e, weight, g, g_next):
+    """(de, dw) of ec = ctx.scale * e @ weight^T with e chained through: the backward tail EdgeFirstLayer and EdgeLatentLinear share.
+    g: gradient of ec (None: the product was not used), g_next: the running gradient of e from the layers behind (joins de inside the
+    input-gradient GEMM)"""
+    de = dw = None
+    if g is not None:
+        if ctx.needs_input_grad[0]:
+            de = linear128(g, weight.t(), alpha=ctx.scale, add_post=g_next)
+        if ctx.needs_input_grad[1]:
+            dw = dw128(g, e)
+            if ctx.scale != 1.0:
+                dw = dw * ctx.scale
+    elif ctx.needs_input_grad[0]:
+        de = g_next
+    return de, dw
+
+
 class EdgeFirstLayer(torch.autograd.Function):
     """(a0, e_next) = (relu(scale * e @ weight^T + xa[dst] + xb[src]), e): the first edge Linear of an InteractionNetwork with the
     [x_i, x_j, e] concat folded away (xa / xb: the node-level products of the x_i / x_j column blocks, bias included) -- gathers, sum and
@@ -853,26 +816,11 @@ class EdgeFirstLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, g_next):
         e, weight = ctx.saved_tensors
-        csr = ctx.csr
-        de = dw = dxa = dxb = None
+        dxa = dxb = None
         if g is not None:
             g = _f32a(g)
-            E = g.shape[0]
-            dxa = torch.empty(csr.N, 128, dtype=torch.float32, device=g.device)
-            dxb = torch.empty_like(dxa)
-            with _n.on_device(g.device):
-                _n.check(_n.lib.csplat_gnn_edge_combine_bwd(
-                    _n.stream_handle(g.device), csr.N, E, 128, _n.ptr(g), None, 0, _n.ptr(csr.rowptr["dst"]),
-                    _n.ptr(csr.perm["dst"]), _n.ptr(csr.rowptr["src"]), _n.ptr(csr.perm["src"]), None, _n.ptr(dxa),
-                    _n.ptr(dxb)), "csplat_gnn_edge_combine_bwd")
-            if ctx.needs_input_grad[0]:
-                de = linear128(g, weight.t(), alpha=ctx.scale, add_post=g_next)
-            if ctx.needs_input_grad[1]:
-                dw = dw128(g, e)
-                if ctx.scale != 1.0:
-                    dw = dw * ctx.scale
-        elif ctx.needs_input_grad[0]:
-            de = g_next
+            dxa, dxb = _edge_combine_bwd(ctx.csr, g, None, False, None)
+        de, dw = _edge_latent_bwd(ctx, e, weight, g, g_next)
         return de, dw, None, dxa, dxb, None
 
 
@@ -900,7 +848,7 @@ def report_missed_edge_tail(a0):
 def edge_tail_aggregate(a0, csr, seq, a0_relu=True):
     """sum over destination nodes of seq's output, seq = [build_mlp, LayerNorm] entered behind its first Linear (+ ReLU):
     EdgeTailAggregate for the [E, 128] work, the LayerNorm's affine part on the [N, 128] sums"""
-    lins = list(seq[0].children())[2::2]
+    lins = _linears(seq[0])[1:]
     wb = [t for m in lins for t in (m.weight, m.bias)]
     S = EdgeTailAggregate.apply(a0, csr, float(seq[1].eps), a0_relu, *wb)
     return S * seq[1].weight + csr.deg_dst[:, None] * seq[1].bias
@@ -922,18 +870,7 @@ class EdgeLatentLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, g_next):
         e, weight = ctx.saved_tensors
-        de = dw = None
-        if g is not None:
-            g = g.contiguous()
-            if ctx.needs_input_grad[0]:
-                de = linear128(g, weight.t(), alpha=ctx.scale, add_post=g_next)
-            if ctx.needs_input_grad[1]:
-                dw = dw128(g, e)
-                if ctx.scale != 1.0:
-                    dw = dw * ctx.scale
-        elif ctx.needs_input_grad[0]:
-            de = g_next
-        return de, dw, None
+        return (*_edge_latent_bwd(ctx, e, weight, None if g is None else g.contiguous(), g_next), None)
 
 
 def edge_latent_linear(e, weight, scale: float = 1.0):

@@ -87,9 +87,7 @@ def candidate_costs(final_positions, goal, node_weights=None):
         p, g = final_positions.contiguous(), goal.contiguous()
         w = None if node_weights is None else node_weights.reshape(-1).contiguous()
         cost = torch.empty(B, dtype=torch.float32, device=dev)
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_plan_cost(_n.stream_handle(dev), B, N, _n.ptr(p), _n.ptr(g), _n.ptr(w), 1.0, 0, _n.ptr(cost)),
-                     "csplat_plan_cost")
+        _n.launch("csplat_plan_cost", dev, B, N, _n.ptr(p), _n.ptr(g), _n.ptr(w), 1.0, 0, _n.ptr(cost))
         return cost
     _n.composed_fallback("mpc.candidate_costs", "dtype", final_positions, goal)
     return _cost_composed(final_positions, goal, node_weights)
@@ -106,8 +104,7 @@ def select_candidates(costs, k=1):
         c = costs.contiguous()
         order = torch.empty(k, dtype=torch.int32, device=dev)
         best = torch.empty(k, dtype=torch.float32, device=dev)
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_plan_select(_n.stream_handle(dev), B, k, _n.ptr(c), _n.ptr(order), _n.ptr(best)), "csplat_plan_select")
+        _n.launch("csplat_plan_select", dev, B, k, _n.ptr(c), _n.ptr(order), _n.ptr(best))
         return order, best
     _n.composed_fallback("mpc.select_candidates", "dtype" if costs.dtype != torch.float32 else "shape", costs)
     val, idx = torch.sort(costs, stable=True)
@@ -122,10 +119,8 @@ def refit_sample(actions, order, mu, sigma, noise, alpha, sigma_min, a_max):
     if _on_kernels(0, actions, mu, sigma, noise) and order.is_cuda and order.dtype == torch.int32 and \
             all(t.is_contiguous() for t in (actions, mu, sigma)):
         dev = actions.device
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_plan_refit_sample(_n.stream_handle(dev), B, T, K, _n.ptr(actions), _n.ptr(order.contiguous()), _n.ptr(mu),
-                                                     _n.ptr(sigma), _n.ptr(noise.contiguous()), float(alpha), float(sigma_min), float(a_max)),
-                     "csplat_plan_refit_sample")
+        _n.launch("csplat_plan_refit_sample", dev, B, T, K, _n.ptr(actions), _n.ptr(order.contiguous()), _n.ptr(mu), _n.ptr(sigma),
+                  _n.ptr(noise.contiguous()), float(alpha), float(sigma_min), float(a_max))
         return actions, mu, sigma
     _n.composed_fallback("mpc.refit_sample", "dtype", actions, mu, sigma, noise, order)
     if K > 0:
@@ -181,7 +176,6 @@ def rollout_candidates(simulator, positions, velocity_history, node_type, edge_i
         edge_index.dtype == torch.int64
     if not kernels:
         _n.composed_fallback("mpc.rollout_candidates", "dtype", positions, velocity_history, candidate_actions)
-    st = _n.stream_handle(dev) if kernels else None
     if nsteps == 0:
         cost = None if goal is None else torch.zeros(B, dtype=dt, device=dev)
         preds = torch.empty(0, B, N, 3, dtype=dt, device=dev) if return_trajectories else None
@@ -197,10 +191,8 @@ def rollout_candidates(simulator, positions, velocity_history, node_type, edge_i
                 v = simulator.predict_velocity(velocities=vel, node_type=batch.node_type, edge_index=batch.edge_index,
                                                edge_features=ef).contiguous()
                 if kernels:
-                    with _n.on_device(dev):
-                        _n.check(_n.lib.csplat_plan_integrate(st, B, N, H, nsteps, k, _n.ptr(v), _n.ptr(acts), grasped_particle, _n.ptr(pos),
-                                                              _n.ptr(hist), _n.ptr(preds), _n.ptr(goal if goal is None else goal.contiguous()),
-                                                              _n.ptr(node_w), _n.ptr(step_w), _n.ptr(cost)), "csplat_plan_integrate")
+                    _n.launch("csplat_plan_integrate", dev, B, N, H, nsteps, k, _n.ptr(v), _n.ptr(acts), grasped_particle, _n.ptr(pos), _n.ptr(hist),
+                              _n.ptr(preds), _n.ptr(goal if goal is None else goal.contiguous()), _n.ptr(node_w), _n.ptr(step_w), _n.ptr(cost))
                     continue
                 # the composed step: the same rule for an int as the kernel's (outside [0, N) pins nothing); an index tensor as torch takes it
                 vb = v.view(B, N, 3)

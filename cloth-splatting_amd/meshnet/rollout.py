@@ -21,9 +21,7 @@ def edge_features(pos, edge_index):
         pos, edge_index = pos.contiguous(), edge_index.contiguous()
         E = int(edge_index.shape[1])
         out = torch.empty(E, 4, dtype=torch.float32, device=pos.device)
-        with _n.on_device(pos.device):
-            _n.check(_n.lib.csplat_gnn_edge_features(_n.stream_handle(pos.device), E, _n.ptr(pos), _n.ptr(edge_index), _n.ptr(out)),
-                     "csplat_gnn_edge_features")
+        _n.launch("csplat_gnn_edge_features", pos.device, E, _n.ptr(pos), _n.ptr(edge_index), _n.ptr(out))
         return out
     _n.composed_fallback("rollout.edge_features", "dtype", pos)
     d = pos[edge_index[0]] - pos[edge_index[1]]
@@ -51,11 +49,9 @@ def refine_edge_lengths(pos, v, edge_index, rest_len, grasped_particle=None, ite
         scratch = torch.empty(9 * max(N, 1), dtype=torch.float32, device=dev)
         rl = rest_len.to(device=dev, dtype=torch.float32).contiguous()
         p_ = pos.contiguous()
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_gnn_edge_length_refine(
-                _n.stream_handle(dev), N, E, _n.ptr(p_), _n.ptr(out), _n.ptr(csr.ei), _n.ptr(rl), _n.ptr(w), _n.ptr(csr.rowptr["dst"]),
-                _n.ptr(csr.perm["dst"]), _n.ptr(csr.rowptr["src"]), _n.ptr(csr.perm["src"]), int(iters), float(lr), 0.9, 0.999, 1e-8,
-                _n.ptr(scratch)), "csplat_gnn_edge_length_refine")
+        _n.launch("csplat_gnn_edge_length_refine", dev, N, E, _n.ptr(p_), _n.ptr(out), _n.ptr(csr.ei), _n.ptr(rl), _n.ptr(w),
+                  _n.ptr(csr.rowptr["dst"]), _n.ptr(csr.perm["dst"]), _n.ptr(csr.rowptr["src"]), _n.ptr(csr.perm["src"]), int(iters), float(lr),
+                  0.9, 0.999, 1e-8, _n.ptr(scratch))
         return out
     _n.composed_fallback("rollout.refine_edge_lengths", "dtype", v)
     with torch.enable_grad():
@@ -85,21 +81,96 @@ FUSED_STEP = _os.environ.get("CSPLAT_ROLLOUT_FUSED", "1") not in ("", "0")
 ROLLOUT_STATS = {"eager_steps": 0, "replayed_steps": 0, "recorded": 0, "record_failed": 0, "repeated_bf16": 0}
 
 
-def _step_body(simulator, pos, hist, act, node_type, edge_index, grasped_particle, real_world, original_edge_lengths, edge_w, out):
-    """one rollout step on the state tensors `pos` [N,3] / `hist` [H,N,3] (both updated IN PLACE), grasped node velocity `act` [3];
-    the predicted velocity is written to `out` [N,3]"""
-    H = hist.shape[0]
-    ef = edge_features(pos, edge_index)
-    vel = torch.cat([hist[h] for h in range(H)], 1)                       # [N, 3H], oldest first (:145)
-    v_next = simulator.predict_velocity(velocities=vel, node_type=node_type, edge_index=edge_index, edge_features=ef)
-    if real_world:
-        v_next = refine_edge_lengths(pos, v_next, edge_index, original_edge_lengths, grasped_particle, edge_w=edge_w)
-    v_next[grasped_particle] = act
-    out.copy_(v_next)
-    pos += v_next
-    if H > 1:
-        hist[:H - 1] = hist[1:].clone()
-    hist[-1] = v_next
+# ---- the two steppers.  Each owns the state buffers of a rollout and offers: begin(...) -- a new rollout into the buffers; before(step) /
+# after(step) -- what the host does around a step; step(recording) -- the step launch by launch, safe to capture; finish(...) -- the
+# results, or None when the step left fp16's range; references() -- what a kept recording must keep alive.  _run() drives either.
+class _GenericStep:
+    """One rollout step through simulator.predict_velocity and stock tensor operations, on state tensors `pos` [N,3] / `hist` [H,N,3]
+    (updated in place), the step's grasped-node velocity `act` [3] and the step's output `out` [N,3]: the host copies the action in before
+    a step and the output row out behind it.  Works on CPU tensors too (never recorded there)."""
+
+    def __init__(self, simulator, positions, velocity_history, node_type, edge_index, grasped_particle, real_world, original_edge_lengths):
+        dev = positions.device
+        self.sim, self.node_type, self.edge_index, self.grasped, self.real_world = simulator, node_type, edge_index, grasped_particle, real_world
+        self.pos, self.hist = torch.empty_like(positions), torch.empty_like(velocity_history)
+        self.act = None
+        self.out = torch.empty_like(self.pos)
+        self.L0 = torch.empty(original_edge_lengths.shape, dtype=torch.float32, device=dev) if real_world else None
+        self.edge_w = None
+        if real_world and positions.is_cuda and int(edge_index.shape[1]) > 0:
+            self.edge_w = torch.ones(int(edge_index.shape[1]), dtype=torch.float32, device=dev)
+            self.edge_w[grasped_particle] = 0.0          # (`length_deviation[grasped_particle] *= 0`, train_meshnet_sim.py:234)
+        self.graph, self.kept = None, False
+        # the fp16-piece arithmetic of the one-launch kernels reports an overflow as a device word per predict_velocity call: the words of
+        # eager steps are collected in `items` and read ONCE behind the loop (no host read per step); a recorded step ANDs its words into
+        # `fine`, which lives across the replays (they overwrite the step's own words)
+        self.items, self.fine, self.mods = [], None, []
+        self.actions = self.preds = None
+
+    def references(self):
+        """strong references: whatever the recording's raw pointers point into stays alive (and its addresses un-reusable) as long as the
+        recording can be replayed"""
+        from .graph_ops import GraphCSR
+        return (self.sim, self.edge_index, self.node_type, GraphCSR.get(self.edge_index, self.pos.shape[0]))
+
+    def begin(self, positions, velocity_history, actions, original_edge_lengths, nsteps, will_record):
+        self.pos.copy_(positions); self.hist.copy_(velocity_history)
+        if self.L0 is not None:
+            self.L0.copy_(original_edge_lengths)
+        if nsteps and self.act is None:
+            self.act = torch.empty(actions.shape[1:], dtype=actions.dtype, device=self.pos.device)
+        self.actions = actions
+        self.preds = torch.empty(nsteps, positions.shape[0], positions.shape[1], dtype=positions.dtype, device=self.pos.device)
+        self.items = []
+        if self.fine is not None:
+            self.fine.fill_(True)
+        elif will_record:
+            self.fine = torch.ones((), dtype=torch.bool, device=self.pos.device)      # (set here, OUTSIDE the recording: replays only AND into it)
+
+    def before(self, step):
+        self.act.copy_(self.actions[step])
+
+    def after(self, step):
+        self.preds[step].copy_(self.out)
+
+    def step(self, recording=False):
+        from .graph_network import _OVERFLOW_COLLECT
+        pos, hist, grasped = self.pos, self.hist, self.grasped
+        H = hist.shape[0]
+        words = [] if recording else self.items
+        _OVERFLOW_COLLECT.append(words)
+        try:
+            ef = edge_features(pos, self.edge_index)
+            vel = torch.cat([hist[h] for h in range(H)], 1)                       # [N, 3H], oldest first (:145)
+            v_next = self.sim.predict_velocity(velocities=vel, node_type=self.node_type, edge_index=self.edge_index, edge_features=ef)
+            if self.real_world:
+                # (ADVICE: the reference pins the grasped node BEFORE the refinement too, train_meshnet_sim.py:176 -- a change of its own)
+                v_next = refine_edge_lengths(pos, v_next, self.edge_index, self.L0, grasped, edge_w=self.edge_w)
+            v_next[grasped] = self.act
+            self.out.copy_(v_next)
+            pos += v_next
+            if H > 1:
+                hist[:H - 1] = hist[1:].clone()
+            hist[-1] = v_next
+        finally:
+            _OVERFLOW_COLLECT.pop()
+        if recording:
+            # (inside the recording; `words` holds tensors of the capture's private pool and is dropped here, with every other local)
+            for _m, ok in words:
+                self.fine.logical_and_(ok)
+            self.mods = list({id(m): m for m, _ok in words}.values())
+
+    def finish(self, nsteps, check_overflow=True):
+        from .graph_network import deferred_overflow_check
+        preds, self.actions, self.preds = self.preds, None, None
+        if check_overflow:
+            chk = deferred_overflow_check()
+            chk.items = self.items + ([(m, self.fine) for m in self.mods] if self.graph is not None else [])
+            self.items = []
+            if chk.overflowed():         # (the one host read of the rollout; the modules concerned now run with bf16 pieces)
+                return None
+        # (the state buffers belong to a kept recording: hand back a copy)
+        return preds, (self.pos.clone() if self.kept else self.pos)
 
 
 class _FusedClothStep:
@@ -114,7 +185,7 @@ class _FusedClothStep:
     def applicable(sim, positions, velocity_history, node_type, edge_index, actions, grasped_particle):
         from .cloth_network import ClothMeshSimulator
         from .graph_network import ENCODER_FUSED
-        from .graph_ops import edge_mlp3_mode
+        from .graph_ops import edge_mlp3_mode, is_mlp3_128, _linears
         if not (isinstance(sim, ClothMeshSimulator) and not sim.training and isinstance(grasped_particle, int) and positions.is_cuda):
             return False
         epd = sim._encode_process_decode
@@ -128,13 +199,9 @@ class _FusedClothStep:
         if not 0 <= grasped_particle < N:        # (k_rollout_integrate pins nothing outside [0, N); `v_next[-1] = act` of the generic step does)
             return False
         F = 3 * H + T
-        lins_n = list(epd._encoder.node_fn[0].children())[0::2]
-        lins_e = list(epd._encoder.edge_fn[0].children())[0::2]
-        dec = list(epd._decoder.node_fn.children())[0::2]
-        if not (F % 4 == 0 and F <= 32 and len(lins_n) == 3 and len(lins_e) == 3 and tuple(lins_n[0].weight.shape) == (128, F) and
-                tuple(lins_e[0].weight.shape) == (128, 4) and len(dec) == 3 and tuple(dec[0].weight.shape) == (128, 128) and
-                tuple(dec[1].weight.shape) == (128, 128) and tuple(dec[2].weight.shape) == (3, 128) and dec[2].weight.is_contiguous() and
-                all(isinstance(a, torch.nn.ReLU) for a in list(epd._decoder.node_fn.children())[1:4:2]) and node_type.numel() == N):
+        if not (F % 4 == 0 and F <= 32 and is_mlp3_128(epd._encoder.node_fn[0], k_in=F) and is_mlp3_128(epd._encoder.edge_fn[0], k_in=4) and
+                is_mlp3_128(epd._decoder.node_fn, k_in=128, n_out=3) and _linears(epd._decoder.node_fn)[2].weight.is_contiguous() and
+                node_type.numel() == N):
             return False
         # (the processor's one-launch kernels in destination order: asked on tensors of the right shape)
         probe_x = torch.empty(N, 128, dtype=torch.float32, device=positions.device)
@@ -145,7 +212,7 @@ class _FusedClothStep:
     def __init__(self, sim, positions, velocity_history, node_type, edge_index, cap, grasped_particle, real_world):
         from .graph_ops import GraphCSR
         dev = positions.device
-        self.sim, self.epd = sim, sim._encode_process_decode
+        self.sim, self.epd, self.node_type = sim, sim._encode_process_decode, node_type
         self.N, self.H, self.T = int(positions.shape[0]), int(velocity_history.shape[0]), int(sim._node_type_embedding_size)
         self.F, self.E, self.cap = 3 * self.H + self.T, int(edge_index.shape[1]), int(cap)
         self.edge_index, self.grasped, self.real_world = edge_index, int(grasped_particle), bool(real_world)
@@ -170,13 +237,16 @@ class _FusedClothStep:
         if real_world:
             self.edge_w = torch.ones(self.E, **f32)
             self.edge_w[self.grasped] = 0.0          # (`length_deviation[grasped_particle] *= 0`, train_meshnet_sim.py:234)
-        self.graph = None
-        self.chain = None
+        self.graph, self.kept = None, False
 
-    def begin(self, positions, velocity_history, actions, original_edge_lengths):
+    def references(self):
+        return (self.sim, self.edge_index, self.node_type)
+
+    def begin(self, positions, velocity_history, actions, original_edge_lengths, nsteps, will_record):
         """the state of a new rollout -> the buffers (stock copies, once per rollout); the normalisers' statistics as plain vectors"""
         from .model_utils import Normalizer
         self.pos.copy_(positions); self.hist.copy_(velocity_history)
+        # (ADVICE: sized by cap, not by what is used -- more rows than cap raise, fewer than nsteps are padded with zeros; a change of its own)
         self.actions[:actions.shape[0]].copy_(actions)
         self.counter.zero_(); self.fine.fill_(1); self.am.zero_()
         if self.L0 is not None:
@@ -188,92 +258,48 @@ class _FusedClothStep:
         if self.has_out_norm:
             self.norm["om"].copy_(on_._mean().reshape(-1)); self.norm["os"].copy_(on_._std_with_epsilon().reshape(-1))
 
-    def step(self):
+    def before(self, step):         # (the step number lives on the device: nothing for the host to do around a step)
+        pass
+
+    after = before
+
+    def step(self, recording=False):
         from .graph_network import _encode_inference
-        from .graph_ops import rows_chain, rows_chain_pack
+        from .graph_ops import rows_chain, _linears
         dev = self.pos.device
-        st = _n.stream_handle(dev)
         epd, N, H, T = self.epd, self.N, self.H, self.T
         nm, ns = (self.norm["nm"], self.norm["ns"]) if self.has_node_norm else (None, None)
         om, os_ = (self.norm["om"], self.norm["os"]) if self.has_out_norm else (None, None)
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_rollout_head(st, N, H, T, _n.ptr(self.hist), _n.ptr(self.nt), _n.ptr(nm), _n.ptr(ns), _n.ptr(self.feats),
-                                                _n.ptr(self.counter), self.am.data_ptr()), "csplat_rollout_head")
-            _n.check(_n.lib.csplat_gnn_edge_features_ordered(st, self.E, _n.ptr(self.pos), _n.ptr(self.csr.ei), _n.ptr(self.plan["perm"]),
-                                                             _n.ptr(self.ef), self.am.data_ptr() + 4), "csplat_gnn_edge_features_ordered")
+        _n.launch("csplat_rollout_head", dev, N, H, T, _n.ptr(self.hist), _n.ptr(self.nt), _n.ptr(nm), _n.ptr(ns), _n.ptr(self.feats),
+                  _n.ptr(self.counter), self.am.data_ptr())
+        _n.launch("csplat_gnn_edge_features_ordered", dev, self.E, _n.ptr(self.pos), _n.ptr(self.csr.ei), _n.ptr(self.plan["perm"]),
+                  _n.ptr(self.ef), self.am.data_ptr() + 4)
         # the encoders (one launch each) with the absmax words the two launches above left: no absmax pass of their own
         xe = _encode_inference(epd._encoder.node_fn, self.feats, self.am[0:1])
         ee = _encode_inference(epd._encoder.edge_fn, self.ef, self.am[1:2])
         if xe is None or ee is None:         # (an encoder the one-launch form does not cover: the module's own path)
             xe, ee = epd._encoder(self.feats, self.ef)
-        dec = list(epd._decoder.node_fn.children())[0::2]
-        if self.chain is None:          # (packed once per object: the object is keyed on the weights' versions)
-            w_i, w_j = epd._processor.gnn_stacks[0]._split_weights()[:2]
-            self.chain = (rows_chain_pack(0, w_i, w_j), rows_chain_pack(1, dec[0].weight, dec[1].weight))
         # the first layer's x_i / x_j products and the decoder's two hidden layers: ONE launch each on pre-packed 16-bit pieces
-        # (csplat_gnn_rows_chain) instead of four exact-fp32 launches of 16 us
+        # (csplat_gnn_rows_chain) instead of four exact-fp32 launches of 16 us; the images are the modules' own, packed per weight version
         xp, _e = epd._processor(xe, self.edge_index, ee, edges_out=False, dst_order=(self.plan, epd._edge_latent_bound()),
-                                first_products=rows_chain(xe, self.chain[0], 0))
-        h = rows_chain(xp, self.chain[1], 1, dec[0].bias, dec[1].bias)
+                                first_products=rows_chain(xe, epd._processor.gnn_stacks[0].first_products_image(), 0))
+        dec = _linears(epd._decoder.node_fn)
+        h = rows_chain(xp, epd._decoder.hidden_image(), 1, dec[0].bias, dec[1].bias)
         last = self.hist[H - 1]
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_rollout_decode(st, N, 3, _n.ptr(h), _n.ptr(dec[2].weight.detach()), _n.ptr(dec[2].bias.detach().contiguous()),
-                                                  _n.ptr(om), _n.ptr(os_), _n.ptr(last), _n.ptr(self.v), _n.ptr(self.fine)), "csplat_rollout_decode")
+        _n.launch("csplat_rollout_decode", dev, N, 3, _n.ptr(h), _n.ptr(dec[2].weight.detach()), _n.ptr(dec[2].bias.detach().contiguous()),
+                  _n.ptr(om), _n.ptr(os_), _n.ptr(last), _n.ptr(self.v), _n.ptr(self.fine))
         if self.real_world:
+            # (ADVICE: the reference pins the grasped node BEFORE the refinement too, train_meshnet_sim.py:176 -- a change of its own)
             refine_edge_lengths(self.pos, self.v, self.edge_index, self.L0, self.grasped, edge_w=self.edge_w, in_place=True)
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_rollout_integrate(st, N, H, 3, _n.ptr(self.v), _n.ptr(self.actions), _n.ptr(self.counter), self.grasped,
-                                                     _n.ptr(self.pos), _n.ptr(self.hist), _n.ptr(self.preds), _n.ptr(self.am)), "csplat_rollout_integrate")
+        _n.launch("csplat_rollout_integrate", dev, N, H, 3, _n.ptr(self.v), _n.ptr(self.actions), _n.ptr(self.counter), self.grasped,
+                  _n.ptr(self.pos), _n.ptr(self.hist), _n.ptr(self.preds), _n.ptr(self.am))
 
-
-def _rollout_fused(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle, nsteps, real_world,
-                   original_edge_lengths, use_graph):
-    """rollout() on _FusedClothStep: every step a replay of ONE recorded step that holds library kernels only (the first rollout of a
-    combination runs its step 0 launch by launch and records its step 1); None when an overflow made the module switch arithmetic"""
-    dev = positions.device
-    cap = max(64, 1 << max(int(nsteps) - 1, 0).bit_length())
-    base = _rollout_key(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle, real_world)
-    key = None if base is None else base + ("fused", cap)
-    ent = _ROLLOUT_CACHE.get(key) if key is not None else None
-    if ent is None:
-        fs = _FusedClothStep(simulator, positions, velocity_history, node_type, edge_index, cap, grasped_particle, real_world)
-        ent = {"fused": fs, "keep": (simulator, edge_index, node_type)}
-        if key is not None:
-            while len(_ROLLOUT_CACHE) >= _ROLLOUT_CACHE_MAX:
-                _ROLLOUT_CACHE.pop(next(iter(_ROLLOUT_CACHE)))
-            _ROLLOUT_CACHE[key] = ent
-    fs = ent["fused"]
-    fs.begin(positions, velocity_history, actions, original_edge_lengths)
-    for step in range(nsteps):
-        if use_graph and fs.graph is not None:
-            fs.graph.replay()
-            ROLLOUT_STATS["replayed_steps"] += 1
-        elif use_graph and key is not None and step == 1:
-            try:
-                from csplat.graphs import capture
-                torch.cuda.synchronize(dev)
-                g = torch.cuda.CUDAGraph()
-                with capture(g):
-                    fs.step()
-                fs.graph = g
-                ROLLOUT_STATS["recorded"] += 1
-                g.replay()
-                ROLLOUT_STATS["replayed_steps"] += 1
-            except Exception:
-                fs.graph, use_graph = None, False
-                ROLLOUT_STATS["record_failed"] += 1
-                torch.cuda.synchronize(dev)
-                fs.step()
-                ROLLOUT_STATS["eager_steps"] += 1
-        else:
-            fs.step()
-            ROLLOUT_STATS["eager_steps"] += 1
-    preds, pos = fs.preds[:nsteps].clone(), fs.pos.clone()
-    if int(fs.fine.item()) == 0:          # (the one host read of the rollout)
-        simulator._encode_process_decode.latch_bf16()
-        _ROLLOUT_CACHE.pop(key, None)
-        return None
-    return preds, pos
+    def finish(self, nsteps, check_overflow=True):
+        preds, pos = self.preds[:nsteps].clone(), self.pos.clone()
+        if int(self.fine.item()) == 0:          # (the one host read of the rollout)
+            self.epd.latch_bf16()
+            return None
+        return preds, pos
 
 
 # recorded steps are kept across rollout() calls (recording costs ~40 ms: a collection pass, the capture, the instantiation -- two steps'
@@ -302,6 +328,56 @@ def _rollout_key(simulator, positions, velocity_history, node_type, edge_index, 
             bool(simulator.training), _n.SCRATCH_EPOCH[0], positions.device.index)
 
 
+def _run(make, key, use_graph, nsteps, state, check_overflow=True):
+    """One rollout on the stepper kept under `key` (made by make() and kept, first in first out, when there is none; key None: made for
+    this rollout only).  With use_graph the first rollout of a stepper runs step 0 launch by launch (weight images packed, caches
+    filled) and RECORDS step 1 into a hipGraph; every later step -- of this and of later rollouts on the stepper -- is one replay.  A
+    capture that fails leaves the launch-by-launch loop.  -> (predictions, final positions), or None when a step left fp16's range."""
+    ent = _ROLLOUT_CACHE.get(key) if key is not None else None
+    if ent is None:
+        st = make()
+        if key is not None:
+            st.kept = True
+            while len(_ROLLOUT_CACHE) >= _ROLLOUT_CACHE_MAX:
+                _ROLLOUT_CACHE.pop(next(iter(_ROLLOUT_CACHE)))
+            _ROLLOUT_CACHE[key] = {"step": st, "keep": st.references()}
+    else:
+        st = ent["step"]
+    dev = st.pos.device
+    st.begin(*state, nsteps, use_graph)
+    for step in range(nsteps):
+        st.before(step)
+        if use_graph and st.graph is not None:
+            st.graph.replay()
+            ROLLOUT_STATS["replayed_steps"] += 1
+        elif use_graph and step == 1:
+            try:
+                from csplat.graphs import capture
+                torch.cuda.synchronize(dev)
+                g = torch.cuda.CUDAGraph()
+                with capture(g):
+                    st.step(recording=True)
+                st.graph = g
+                ROLLOUT_STATS["recorded"] += 1
+                g.replay()          # (the capture itself executed nothing)
+                ROLLOUT_STATS["replayed_steps"] += 1
+            except Exception:
+                # (a capture that failed half way leaves the state buffers as they were: nothing of a capture executes)
+                st.graph, use_graph = None, False
+                ROLLOUT_STATS["record_failed"] += 1
+                torch.cuda.synchronize(dev)
+                st.step()
+                ROLLOUT_STATS["eager_steps"] += 1
+        else:
+            st.step()
+            ROLLOUT_STATS["eager_steps"] += 1
+        st.after(step)
+    res = st.finish(nsteps, check_overflow)
+    if res is None:
+        _ROLLOUT_CACHE.pop(key, None)           # (recorded with the fp16 pieces: not to be replayed for the latched module)
+    return res
+
+
 @torch.no_grad()
 def rollout(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle, nsteps, real_world=False,
             original_edge_lengths=None, graph=None):
@@ -315,98 +391,25 @@ def rollout(simulator, positions, velocity_history, node_type, edge_index, actio
     row); every later step -- and every step of later rollouts with the same combination -- is one replay: the same launches in the same
     order on the same buffers, so the result equals the eager loop bit for bit; the host issues one graph launch and two small copies
     per step instead of ~35 launches."""
-    from .graph_network import deferred_overflow_check
-    from .graph_ops import GraphCSR
     if real_world and original_edge_lengths is None:
         original_edge_lengths = torch.norm(positions[edge_index[1]] - positions[edge_index[0]], dim=1)
-    dev = positions.device
     use_graph = (ROLLOUT_GRAPH if graph is None else bool(graph)) and positions.is_cuda and nsteps >= 4
-    N = positions.shape[0]
+    state = (positions, velocity_history, actions, original_edge_lengths)
+
+    def key():
+        return _rollout_key(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle, real_world)
     if nsteps > 0 and FUSED_STEP and _FusedClothStep.applicable(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle):
-        res = _rollout_fused(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle, nsteps, real_world,
-                             original_edge_lengths, use_graph)
+        cap = max(64, 1 << max(int(nsteps) - 1, 0).bit_length())
+        res = _run(lambda: _FusedClothStep(simulator, positions, velocity_history, node_type, edge_index, cap, grasped_particle, real_world),
+                   key() + ("fused", cap), use_graph, nsteps, state)
         if res is not None:
             return res
-        ROLLOUT_STATS["repeated_bf16"] += 1          # (a step left fp16's range: the module now runs bf16 pieces -- the generic loop below)
+        ROLLOUT_STATS["repeated_bf16"] += 1          # (a step left fp16's range: the module now runs bf16 pieces -- the generic step below)
     for attempt in range(2):
-        key = _rollout_key(simulator, positions, velocity_history, node_type, edge_index, actions, grasped_particle, real_world) if use_graph else None
-        ent = _ROLLOUT_CACHE.get(key) if key is not None else None
-        preds = torch.empty(nsteps, N, positions.shape[1], dtype=positions.dtype, device=dev)
-        if ent is not None:
-            # ---- every step a replay of the recording made by an earlier rollout
-            ent["pos"].copy_(positions); ent["hist"].copy_(velocity_history); ent["fine"].fill_(True)
-            if real_world:
-                ent["L0"].copy_(original_edge_lengths)
-            for step in range(nsteps):
-                ent["act"].copy_(actions[step])
-                ent["graph"].replay()
-                preds[step].copy_(ent["out"])
-            ROLLOUT_STATS["replayed_steps"] += nsteps
-            if attempt == 0 and ent["mods"] and not bool(ent["fine"]):
-                for m in ent["mods"]:
-                    m.latch_bf16()
-                ROLLOUT_STATS["repeated_bf16"] += 1
-                continue
-            return preds, ent["pos"].clone()
-        pos = positions.clone()
-        hist = velocity_history.clone()
-        act = torch.empty(actions.shape[1:], dtype=actions.dtype, device=dev) if nsteps else None
-        out = torch.empty_like(pos)
-        L0 = original_edge_lengths.to(device=dev, dtype=torch.float32).clone() if real_world else None
-        edge_w = None
-        if real_world and positions.is_cuda and int(edge_index.shape[1]) > 0:
-            edge_w = torch.ones(int(edge_index.shape[1]), dtype=torch.float32, device=dev)
-            edge_w[grasped_particle] = 0.0          # (`length_deviation[grasped_particle] *= 0`, train_meshnet_sim.py:234)
-        # (the fp16-piece arithmetic of the one-launch kernels reports an overflow as a device word per predict_velocity call: collected
-        #  here, read ONCE behind the loop -- no host read per step)
-        with deferred_overflow_check() as chk:
-            g = None
-            for step in range(nsteps):
-                act.copy_(actions[step])
-                if g is not None:
-                    g.replay()
-                    ROLLOUT_STATS["replayed_steps"] += 1
-                elif use_graph and step == 1:
-                    try:
-                        from csplat.graphs import capture
-                        n_before = len(chk.items)
-                        fine_all = torch.ones((), dtype=torch.bool, device=dev)      # (set here, OUTSIDE the recording: replays only AND into it)
-                        torch.cuda.synchronize(dev)
-                        g = torch.cuda.CUDAGraph()
-                        with capture(g):
-                            _step_body(simulator, pos, hist, act, node_type, edge_index, grasped_particle, real_world, L0, edge_w, out)
-                            # the replays overwrite the step's overflow word: AND it into one that lives across the replays
-                            for _m, ok in chk.items[n_before:]:
-                                fine_all.logical_and_(ok)
-                        mods = list({id(m): m for m, _ok in chk.items[n_before:]}.values())
-                        del chk.items[n_before:]
-                        chk.items.extend((m, fine_all) for m in mods[:1])
-                        ROLLOUT_STATS["recorded"] += 1
-                        g.replay()          # (the capture itself executed nothing)
-                        ROLLOUT_STATS["replayed_steps"] += 1
-                        if key is not None:
-                            while len(_ROLLOUT_CACHE) >= _ROLLOUT_CACHE_MAX:
-                                _ROLLOUT_CACHE.pop(next(iter(_ROLLOUT_CACHE)))
-                            _ROLLOUT_CACHE[key] = {"graph": g, "pos": pos, "hist": hist, "act": act, "out": out, "L0": L0, "edge_w": edge_w,
-                                                   "fine": fine_all, "mods": mods,
-                                                   # strong references: whatever the recording's raw pointers point into stays alive (and its
-                                                   # addresses un-reusable) as long as the recording can be replayed
-                                                   "keep": (simulator, edge_index, node_type, GraphCSR.get(edge_index, N))}
-                    except Exception:
-                        # (a capture that failed half way leaves the state buffers as they were: nothing of a capture executes)
-                        g, use_graph = None, False
-                        ROLLOUT_STATS["record_failed"] += 1
-                        torch.cuda.synchronize(dev)
-                        _step_body(simulator, pos, hist, act, node_type, edge_index, grasped_particle, real_world, L0, edge_w, out)
-                        ROLLOUT_STATS["eager_steps"] += 1
-                else:
-                    _step_body(simulator, pos, hist, act, node_type, edge_index, grasped_particle, real_world, L0, edge_w, out)
-                    ROLLOUT_STATS["eager_steps"] += 1
-                preds[step].copy_(out)
-            if attempt == 0 and chk.overflowed():
-                ROLLOUT_STATS["repeated_bf16"] += 1
-                _ROLLOUT_CACHE.pop(key, None)           # (recorded with the fp16 pieces: not to be replayed for the latched module)
-                continue        # a step left fp16's range: the modules concerned now run with bf16 pieces -- the rollout again, from its start
-        # (the state buffers belong to the cached recording from here on: hand back a copy)
-        return preds, (pos.clone() if (key is not None and key in _ROLLOUT_CACHE) else pos)
+        res = _run(lambda: _GenericStep(simulator, positions, velocity_history, node_type, edge_index, grasped_particle, real_world,
+                                        original_edge_lengths),
+                   key() if use_graph else None, use_graph, nsteps, state, check_overflow=attempt == 0)
+        if res is not None:
+            return res
+        ROLLOUT_STATS["repeated_bf16"] += 1      # a step left fp16's range: the modules concerned now run bf16 pieces -- once more, from the start
     raise AssertionError("unreachable")

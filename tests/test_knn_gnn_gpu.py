@@ -1230,6 +1230,105 @@ def test_recorded_rollout_equals_the_launch_by_launch_loop(real_world):
     assert torch.equal(e_pred, f_pred) and not torch.equal(e_pred, a_pred)
 
 
+def _small_rollout_case(seed=51, n_graphs=1, n_actions=6):
+    """N = 300, E = 3000, latent 128, 3 message-passing steps: (simulator, positions, history, node types, edge lists, actions)"""
+    from meshnet.cloth_network import ClothMeshSimulator
+    dev = "cuda"
+    g = torch.Generator().manual_seed(seed)
+    N, E = 300, 3000
+    pos = torch.randn(N, 3, generator=g).to(dev)
+    eis = [torch.stack([torch.randint(0, N, (E,), generator=g), torch.randint(0, N, (E,), generator=g)]).to(dev) for _ in range(n_graphs)]
+    torch.manual_seed(seed)
+    sim = ClothMeshSimulator(3, 8, 4, 128, 3, 2, 128, 2, 2, normalize=False, device=dev).eval()
+    hist = (torch.randn(2, N, 3, generator=g) * 0.01).to(dev)
+    ntype = torch.randint(0, 2, (N, 1), generator=g).to(dev)
+    actions = (torch.randn(n_actions, 3, generator=g) * 0.01).to(dev)
+    return sim, pos, hist, ntype, eis, actions
+
+
+@pytest.mark.parametrize("real_world", [False, True])
+def test_generic_recorded_rollout_equals_the_launch_by_launch_loop(real_world):
+    """the GENERIC rollout step (rollout.FUSED_STEP = False: ClothMeshSimulator.predict_velocity and stock tensor operations on state
+    buffers) recorded into a hipGraph against the same loop launch by launch: bit-equal predictions and positions; step 0 eager, step 1
+    recorded, the rest replays; a second rollout of the combination from another state replays every step of the kept recording; an
+    in-place weight change records again.  Reference loop: train_meshnet_sim.py:126-265."""
+    from meshnet import rollout as ro
+    sim, pos, hist, ntype, (ei,), actions = _small_rollout_case(seed=52, n_actions=5)
+    was = ro.FUSED_STEP
+    ro.FUSED_STEP = False
+    try:
+        before = dict(ro.ROLLOUT_STATS)
+        a_pred, a_pos = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, real_world=real_world, graph=True)
+        after = dict(ro.ROLLOUT_STATS)
+        assert after["recorded"] == before["recorded"] + 1 and after["replayed_steps"] == before["replayed_steps"] + 4 and \
+            after["record_failed"] == before["record_failed"] and after["eager_steps"] == before["eager_steps"] + 1, (before, after)
+        b_pred, b_pos = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, real_world=real_world, graph=False)
+        assert torch.isfinite(a_pred).all()
+        assert torch.equal(a_pred, b_pred) and torch.equal(a_pos, b_pos)
+        assert torch.equal(a_pred[:, 11], actions)
+        pos2, hist2 = pos + 0.01, hist * 0.5
+        mid = dict(ro.ROLLOUT_STATS)
+        c_pred, c_pos = ro.rollout(sim, pos2, hist2, ntype, ei, actions, 11, 5, real_world=real_world, graph=True)
+        again = dict(ro.ROLLOUT_STATS)
+        assert again["recorded"] == mid["recorded"] and again["replayed_steps"] == mid["replayed_steps"] + 5 and \
+            again["eager_steps"] == mid["eager_steps"], (mid, again)
+        d_pred, d_pos = ro.rollout(sim, pos2, hist2, ntype, ei, actions, 11, 5, real_world=real_world, graph=False)
+        assert torch.equal(c_pred, d_pred) and torch.equal(c_pos, d_pos) and not torch.equal(c_pred, a_pred)
+        # the recording owns its state buffers: what a replayed rollout hands back is a copy, untouched by the next rollout
+        c_pos_kept = c_pos.clone()
+        ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, real_world=real_world, graph=True)
+        assert torch.equal(c_pos, c_pos_kept)
+        with torch.no_grad():
+            sim._encode_process_decode._decoder.node_fn[0].weight.mul_(1.01)
+        mid = dict(ro.ROLLOUT_STATS)
+        e_pred, _ = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, real_world=real_world, graph=True)
+        assert ro.ROLLOUT_STATS["recorded"] == mid["recorded"] + 1
+        f_pred, _ = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, real_world=real_world, graph=False)
+        assert torch.equal(e_pred, f_pred) and not torch.equal(e_pred, a_pred)
+    finally:
+        ro.FUSED_STEP = was
+
+
+def test_a_recording_is_kept_across_rollouts_of_another_length():
+    """the fused step's recording is keyed on the capacity of its action / prediction buffers (64 rows at least), not on nsteps: a
+    6-step rollout records, a 5-step rollout of the same combination replays every step; both bit-equal to the eager loop"""
+    from meshnet import rollout as ro
+    sim, pos, hist, ntype, (ei,), actions = _small_rollout_case(seed=53)
+    assert ro.FUSED_STEP and ro._FusedClothStep.applicable(sim, pos, hist, ntype, ei, actions, 11)
+    before = dict(ro.ROLLOUT_STATS)
+    a_pred, a_pos = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 6, graph=True)
+    after = dict(ro.ROLLOUT_STATS)
+    assert after["recorded"] == before["recorded"] + 1 and after["replayed_steps"] == before["replayed_steps"] + 5, (before, after)
+    b_pred, b_pos = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, graph=True)
+    again = dict(ro.ROLLOUT_STATS)
+    assert again["recorded"] == after["recorded"] and again["replayed_steps"] == after["replayed_steps"] + 5 and \
+        again["eager_steps"] == after["eager_steps"], (after, again)
+    c_pred, c_pos = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 6, graph=False)
+    d_pred, d_pos = ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, graph=False)
+    assert torch.isfinite(a_pred).all() and a_pred.shape[0] == 6 and b_pred.shape[0] == 5
+    assert torch.equal(a_pred, c_pred) and torch.equal(a_pos, c_pos)
+    assert torch.equal(b_pred, d_pred) and torch.equal(b_pos, d_pos)
+
+
+def test_rollout_recordings_are_evicted_first_in_first_out_at_two():
+    """three graphs in turn: never more than _ROLLOUT_CACHE_MAX = 2 recordings are kept, and the first combination -- evicted by the
+    third -- records again when it returns"""
+    from meshnet import rollout as ro
+    sim, pos, hist, ntype, eis, actions = _small_rollout_case(seed=54, n_graphs=3)
+    assert ro._ROLLOUT_CACHE_MAX == 2
+    preds = []
+    for ei in eis:
+        before = ro.ROLLOUT_STATS["recorded"]
+        preds.append(ro.rollout(sim, pos, hist, ntype, ei, actions, 11, 5, graph=True)[0])
+        assert ro.ROLLOUT_STATS["recorded"] == before + 1 and len(ro._ROLLOUT_CACHE) <= 2
+    before = dict(ro.ROLLOUT_STATS)
+    ro.rollout(sim, pos, hist, ntype, eis[2], actions, 11, 5, graph=True)             # the newest is still there: replays only
+    assert ro.ROLLOUT_STATS["recorded"] == before["recorded"] and ro.ROLLOUT_STATS["replayed_steps"] == before["replayed_steps"] + 5
+    again, _ = ro.rollout(sim, pos, hist, ntype, eis[0], actions, 11, 5, graph=True)
+    assert ro.ROLLOUT_STATS["recorded"] == before["recorded"] + 1 and len(ro._ROLLOUT_CACHE) <= 2
+    assert torch.equal(again, preds[0])
+
+
 def test_rollout_repeats_with_bf16_pieces_after_an_overflow():
     """a rollout whose network leaves fp16's range at some step: the per-call overflow words are collected without a host read, read once
     behind the loop, and the rollout is repeated from its start with three bf16 pieces -- finite results equal to the launch-by-launch

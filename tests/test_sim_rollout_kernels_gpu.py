@@ -227,6 +227,40 @@ def test_rows_dot_misaligned_operands_are_copied_by_the_wrappers_and_refused_by_
             assert same_bits(a, c)
 
 
+def test_native_launch_takes_the_failure_path_of_check_and_the_next_launch_succeeds():
+    """csplat.native.launch(name, device, *args) on an entry that refuses its arguments BEFORE launching anything (csplat_rows_dot_fwd
+    with h off a 16-byte boundary): CsplatError naming the entry, every registered ticket cache emptied, SCRATCH_EPOCH moved by one,
+    nothing written; the same call with the aligned operand then succeeds and gives the bits of the plain check() call"""
+    from csplat import native as n
+    Rr, T = 771, 3
+    h8, W, b, _add, _dy = R.rows_dot_case(Rr)
+    hc, Wc, bc = cuda(h8[:T]), cuda(W), cuda(b)
+    buf = torch.zeros(hc.numel() + 1, device="cuda")
+    moved = buf[1:].view(hc.shape)
+    moved.copy_(hc)
+    assert moved.data_ptr() % 16 == 4
+    dev = torch.device("cuda", torch.cuda.current_device())
+    y = filled(T, Rr)
+    cache = {"ticket": object()}
+    n.TICKET_CACHES.append(cache)
+    try:
+        epoch = n.SCRATCH_EPOCH[0]
+        with pytest.raises(n.CsplatError, match="csplat_rows_dot_fwd"):
+            n.launch("csplat_rows_dot_fwd", dev, T, Rr, 256, P(Wc), P(bc), P(moved), P(y), None)
+        assert not cache and n.SCRATCH_EPOCH[0] == epoch + 1
+        assert bool((y == SENT).all())
+        cache["ticket"] = object()
+        assert n.launch("csplat_rows_dot_fwd", dev, T, Rr, 256, P(Wc), P(bc), P(hc), P(y), None) is None
+        assert cache and n.SCRATCH_EPOCH[0] == epoch + 1
+    finally:
+        n.TICKET_CACHES[:] = [c for c in n.TICKET_CACHES if c is not cache]
+    assert same_bits(y, _rows_dot_fwd(T, Rr, Wc, bc, hc, None))
+    # device None: the current device
+    y2 = filled(T, Rr)
+    n.launch("csplat_rows_dot_fwd", None, T, Rr, 256, P(Wc), P(bc), P(hc), P(y2), None)
+    assert same_bits(y2, y)
+
+
 # ================================================================================================ sim_hidden
 def _sim_fwd(T, K0, e, W1, b1, W2, b2):
     h1, h2 = filled(T, 256), filled(T, 256)
