@@ -886,62 +886,60 @@ int csplat_image_layout(int W, int H, size_t *o3) {
 // finish: reads num_rendered (mailbox poll), allocates the R-sized chunks, K3..K6.  A caller with several independent
 // views issues every begin (each on its own stream) before the first finish, so the one host round trip per view and
 // the under-filled compositing kernels of different views overlap.  csplat_forward = begin + finish.
+// antialiasing (csplat_view.prefiltered & CSPLAT_ANTIALIAS; bit 0, upstream's prefiltered, is ignored): K1 stores o' = o h
+// (k_preprocess_aa / k_preprocess_views_aa); K8 takes its AA variant and reads the raw opacities
+static bool aa_of(const csplat_view &w) { return (w.prefiltered & CSPLAT_ANTIALIAS) != 0; }
+
+// A forward between its two phases: the call's arguments as a csplat_view, and what begin_prepare derived from them.  The outputs that
+// arrive late are NOT read from `w`: the flat finish receives out_color / out_depth itself, the batched second phase takes them from
+// the caller's array (p2_launch).
 struct FwdTicket {
-    bool used = false;
-    hipStream_t s = nullptr;
-    int P = 0, W = 0, H = 0, tiles = 0, nb = 0;
-    bool can_bucket = false, use_mail = false;
-    uint32_t tag = 0;
-    volatile uint32_t *mb_host = nullptr;
+    bool used;              // (static storage: starts false; claimed in begin_prepare, given back by release_ticket)
+    csplat_view w;
+    csplat_alloc_fn alloc;
+    hipStream_t s;
     Cam cam;
     Geom g;
-    void *gbase = nullptr, *ibase = nullptr;
-    int2 *ranges = nullptr;
-    uint32_t *n_contrib = nullptr, *info = nullptr, *table = nullptr;
-    float *final_T = nullptr;
-    const float *bg = nullptr;
-    int32_t *radii = nullptr;
-    csplat_alloc_fn alloc = nullptr;
-    void *alloc_ctx = nullptr;
-    uint32_t *mb_dev = nullptr;
-    int D = 0, M = 0;
-    bool aa = false;        // prefiltered & CSPLAT_ANTIALIAS: K1 stores o' = o h (k_preprocess_aa / k_preprocess_views_aa)
-    float scale_modifier = 1.f;
-    const float *means3D = nullptr, *shs = nullptr, *colors_precomp = nullptr, *opacities = nullptr, *scales = nullptr, *rotations = nullptr,
-                *cov3D_precomp = nullptr;
+    ImageView im;
+    void *gbase, *ibase;
+    uint32_t *table;
+    int tiles, nb;
+    bool can_bucket, use_mail;
+    uint32_t tag;           // the mailbox triple: tag, host and device address of the slot
+    volatile uint32_t *mb_host;
+    uint32_t *mb_dev;
 };
 constexpr int MAX_TICKETS = 64;
 static FwdTicket g_tickets[MAX_TICKETS];
 static std::mutex g_ticket_mu;
+// the ONE place a ticket is given back
+static void release_ticket(int tk) {
+    std::lock_guard<std::mutex> lk(g_ticket_mu);
+    g_tickets[tk].used = false;
+}
 
 // allocation + bookkeeping of a forward: nothing is launched
-static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int W, int H, const float *means3D,
-                         const float *shs, const float *colors_precomp, const float *opacities, const float *scales,
-                         float scale_modifier, const float *rotations, const float *cov3D_precomp, const float *view,
-                         const float *proj, const float *campos, float tanfovx, float tanfovy, int prefiltered,
-                         csplat_alloc_fn alloc, void *alloc_ctx, int32_t *radii, int *ticket_out) {
-    hipStream_t s = (hipStream_t)stream;
-    // (bit 0, upstream's prefiltered, is ignored; bit 1 is CSPLAT_ANTIALIAS)
+static int begin_prepare(const csplat_view &w, csplat_alloc_fn alloc, int *ticket_out) {
+    const int P = w.P, W = w.W, H = w.H;
     CSPLAT_REQUIRE(P >= 0 && W > 0 && H > 0, "csplat_forward: bad sizes");
     CSPLAT_REQUIRE(ticket_out != nullptr, "csplat_forward_begin: ticket_out missing");
     // (an empty input, P == 0, legitimately arrives with NULL data pointers)
-    CSPLAT_REQUIRE(P == 0 || (shs != nullptr) != (colors_precomp != nullptr), "provide exactly one of shs / colors_precomp");
-    CSPLAT_REQUIRE(P == 0 || (cov3D_precomp != nullptr) != (scales != nullptr && rotations != nullptr),
+    CSPLAT_REQUIRE(P == 0 || (w.shs != nullptr) != (w.colors_precomp != nullptr), "provide exactly one of shs / colors_precomp");
+    CSPLAT_REQUIRE(P == 0 || (w.cov3D_precomp != nullptr) != (w.scales != nullptr && w.rotations != nullptr),
                    "provide exactly one of (scales, rotations) / cov3D_precomp");
-    CSPLAT_REQUIRE(shs == nullptr || (D >= 0 && D <= 3 && M >= (D + 1) * (D + 1)), "SH degree / coefficient count mismatch");
+    CSPLAT_REQUIRE(w.shs == nullptr || (w.D >= 0 && w.D <= 3 && w.M >= (w.D + 1) * (w.D + 1)), "SH degree / coefficient count mismatch");
     CSPLAT_REQUIRE(alloc != nullptr, "allocator callback missing");
     Cam cam;
-    make_cam(cam, view, proj, campos, tanfovx, tanfovy, W, H);
+    make_cam(cam, w);
 
-    void *gbase = alloc(alloc_ctx, CSPLAT_CHUNK_GEOM, csplat_geom_bytes(P));
-    void *ibase = alloc(alloc_ctx, CSPLAT_CHUNK_IMAGE, csplat_image_bytes(W, H));
+    void *gbase = alloc(w.alloc_ctx, CSPLAT_CHUNK_GEOM, csplat_geom_bytes(P));
+    void *ibase = alloc(w.alloc_ctx, CSPLAT_CHUNK_IMAGE, csplat_image_bytes(W, H));
     CSPLAT_REQUIRE(gbase && ibase, "allocator returned NULL");
-    const ImageView im = image_view(ibase, W, H);
     const int tiles = cam.gx * cam.gy;
     const bool can_bucket = tiles <= BUCKET_TILES && !dbg(CSPLAT_DEBUG_GLOBAL_SORT);
     uint32_t *table = nullptr;
     if (can_bucket) {
-        table = (uint32_t *)alloc(alloc_ctx, CSPLAT_CHUNK_TABLE, bucket_table_bytes(P, tiles));
+        table = (uint32_t *)alloc(w.alloc_ctx, CSPLAT_CHUNK_TABLE, bucket_table_bytes(P, tiles));
         CSPLAT_REQUIRE(table, "allocator returned NULL");
     }
     int tk = -1;
@@ -953,7 +951,9 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
     }
     CSPLAT_REQUIRE(tk >= 0, "csplat_forward_begin: more than 64 forwards begun and not finished");
     FwdTicket &t = g_tickets[tk];
-    t.s = s; t.P = P; t.W = W; t.H = H; t.tiles = tiles; t.nb = cdiv(P > 0 ? P : 1, BUCKET_G); t.can_bucket = can_bucket;
+    t.w = w; t.alloc = alloc; t.s = (hipStream_t)w.stream;
+    t.cam = cam; t.g = geom_view(gbase, P); t.im = image_view(ibase, W, H); t.gbase = gbase; t.ibase = ibase; t.table = table;
+    t.tiles = tiles; t.nb = cdiv(P > 0 ? P : 1, BUCKET_G); t.can_bucket = can_bucket;
     t.use_mail = false; t.tag = 0; t.mb_host = nullptr; t.mb_dev = nullptr;
     if (can_bucket && !dbg(CSPLAT_DEBUG_NO_MAILBOX) && mail_init()) {
         t.use_mail = true;
@@ -963,12 +963,6 @@ static int begin_prepare(void *stream, int P, int D, int M, const float *bg, int
         t.mb_host = g_mail.host + slot * MAIL_WORDS;
         t.mb_dev = g_mail.dev + slot * MAIL_WORDS;
     }
-    t.cam = cam; t.g = geom_view(gbase, P); t.gbase = gbase; t.ibase = ibase;
-    t.ranges = im.ranges; t.n_contrib = im.n_contrib; t.final_T = im.final_T; t.info = im.info;
-    t.table = table; t.bg = bg; t.radii = radii; t.alloc = alloc; t.alloc_ctx = alloc_ctx;
-    t.D = D; t.M = M; t.means3D = means3D; t.shs = shs; t.colors_precomp = colors_precomp; t.opacities = opacities; t.scales = scales;
-    t.scale_modifier = scale_modifier; t.rotations = rotations; t.cov3D_precomp = cov3D_precomp;
-    t.aa = (prefiltered & CSPLAT_ANTIALIAS) != 0;
     *ticket_out = tk;
     return 0;
 }
@@ -978,29 +972,28 @@ static int nocull_mode() { return dbg(CSPLAT_DEBUG_NO_CULLING) ? 1 : dbg(CSPLAT_
 // K1 + the counting half of the binning of ONE view, on its stream
 static int begin_launch(const FwdTicket &t) {
     hipStream_t s = t.s;
-    const int P = t.P, tiles = t.tiles, nb = t.nb;
-    if (!t.can_bucket) HIP_TRY(hipMemsetAsync(t.ranges, 0, (size_t)tiles * 8, s));
+    const csplat_view &w = t.w;
+    const int P = w.P, tiles = t.tiles, nb = t.nb;
+    if (!t.can_bucket) HIP_TRY(hipMemsetAsync(t.im.ranges, 0, (size_t)tiles * 8, s));
     if (P > 0) {
         ProfScope ps(PROF_K1, s);
-        const bool stage = t.shs != nullptr && t.M == 16 && ((uintptr_t)t.shs & 15u) == 0;
-        if (t.aa && stage)
-            k_preprocess_aa<true><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
-                                                                t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
-        else if (t.aa)
-            k_preprocess_aa<false><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
-                                                                 t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
-        else if (stage)
-            k_preprocess<true><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
-                                                             t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
-        else
-            k_preprocess<false><<<cdiv(P, 256), 256, 0, s>>>(P, t.D, t.M, t.means3D, t.shs, t.colors_precomp, t.opacities, t.scales,
-                                                              t.scale_modifier, t.rotations, t.cov3D_precomp, t.cam, t.g, t.radii, nocull_mode());
+        auto form = [&](auto staged) {        // staged: the SH rows go through LDS
+            constexpr bool STAGE = decltype(staged)::value;
+            auto go = [&](auto kernel) {
+                kernel<<<cdiv(P, 256), 256, 0, s>>>(P, w.D, w.M, w.means3D, w.shs, w.colors_precomp, w.opacities, w.scales, w.scale_modifier,
+                                                    w.rotations, w.cov3D_precomp, t.cam, t.g, w.radii, nocull_mode());
+            };
+            if (aa_of(w)) go(k_preprocess_aa<STAGE>);
+            else go(k_preprocess<STAGE>);
+        };
+        if (w.shs != nullptr && w.M == 16 && ((uintptr_t)w.shs & 15u) == 0) form(std::true_type{});
+        else form(std::false_type{});
         LAUNCH_CHECK();
     }
     if (t.can_bucket) {
         ProfScope ps(PROF_K2, s);
         if (P > 0) {
-            k_tile_count<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, t.g.xy, t.radii, t.cam, t.table);
+            k_tile_count<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, t.g.xy, w.radii, t.cam, t.table);
             LAUNCH_CHECK();
         } else {
             HIP_TRY(hipMemsetAsync(t.table, 0, (size_t)nb * tiles * 4, s));
@@ -1008,7 +1001,7 @@ static int begin_launch(const FwdTicket &t) {
         uint32_t *tile_cnt = t.table + (size_t)nb * tiles;   // last row of the chunk: per-tile totals
         k_tile_colscan<<<cdiv(tiles, 256), 256, 0, s>>>(tiles, nb, t.table, tile_cnt);
         LAUNCH_CHECK();
-        k_tile_scan<<<1, 1024, 0, s>>>(tiles, tile_cnt, t.ranges, t.info, t.mb_dev, t.tag);
+        k_tile_scan<<<1, 1024, 0, s>>>(tiles, tile_cnt, t.im.ranges, t.im.info, t.mb_dev, t.tag);
         LAUNCH_CHECK();
     }
     return 0;
@@ -1020,46 +1013,43 @@ static bool begin_views_compatible(int V, const int *tk) {
     // (V == 1 qualifies too since round 5: a camera-by-camera caller -- the reference's own loop, train_utils.py:259-272 -- then gets the
     //  speculative second phase as well instead of a blocking read of its counts per camera)
     if (V < 1 || V > RASTER_MAX_VIEWS || dbg(CSPLAT_DEBUG_PER_VIEW_LAUNCHES)) return false;
-    const FwdTicket &a = g_tickets[tk[0]];
-    if (a.P <= 0 || !a.can_bucket || !a.shs || a.colors_precomp || a.cov3D_precomp || !a.scales || !a.rotations) return false;
+    const FwdTicket &ta = g_tickets[tk[0]];
+    const csplat_view &a = ta.w;
+    if (a.P <= 0 || !ta.can_bucket || !a.shs || a.colors_precomp || a.cov3D_precomp || !a.scales || !a.rotations) return false;
     for (int i = 1; i < V; i++) {
-        const FwdTicket &w = g_tickets[tk[i]];
+        const csplat_view &w = g_tickets[tk[i]].w;
         if (w.P != a.P || w.D != a.D || w.M != a.M || w.W != a.W || w.H != a.H || w.shs != a.shs || w.opacities != a.opacities ||
             w.scales != a.scales || w.scale_modifier != a.scale_modifier || w.colors_precomp || w.cov3D_precomp || !w.rotations ||
-            !w.can_bucket || w.aa != a.aa)
+            !g_tickets[tk[i]].can_bucket || aa_of(w) != aa_of(a))
             return false;
     }
     return true;
 }
 static int begin_launch_views(int V, const int *tk, hipStream_t join) {
-    const FwdTicket &a = g_tickets[tk[0]];
-    const int P = a.P, tiles = a.tiles, nb = a.nb;
+    const FwdTicket &ta = g_tickets[tk[0]];
+    const csplat_view &a = ta.w;
+    const int P = a.P, tiles = ta.tiles, nb = ta.nb;
     K1Table tab;
     tab.n = V;
     for (int i = 0; i < V; i++) {
         const FwdTicket &t = g_tickets[tk[i]];
         K1View &k = tab.v[i];
-        k.means3D = t.means3D; k.rotations = t.rotations; k.cam = t.cam; k.g = t.g; k.radii = t.radii; k.table = t.table;
-        k.info = t.info; k.mailbox = t.mb_dev; k.ranges = t.ranges; k.tag = t.tag;
+        k.means3D = t.w.means3D; k.rotations = t.w.rotations; k.cam = t.cam; k.g = t.g; k.radii = t.w.radii; k.table = t.table;
+        k.info = t.im.info; k.mailbox = t.mb_dev; k.ranges = t.im.ranges; k.tag = t.tag;
     }
     {
         ProfScope ps(PROF_K1, join);
-        const bool stage = a.M == 16 && ((uintptr_t)a.shs & 15u) == 0;
-        if (a.aa && stage)
-            k_preprocess_views_aa<true><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
-                                                                        nocull_mode());
-        else if (a.aa)
-            k_preprocess_views_aa<false><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
-                                                                         nocull_mode());
-        else if (stage && per_gaussian_stamps(P))
-            k_preprocess_views_stamps<<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
-                                                                      nocull_mode(), per_gaussian_stamps(P));
-        else if (stage)
-            k_preprocess_views<true><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
-                                                                     nocull_mode());
-        else
-            k_preprocess_views<false><<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab,
-                                                                      nocull_mode());
+        auto form = [&](auto staged) {
+            constexpr bool STAGE = decltype(staged)::value;
+            auto go = [&](auto kernel, auto... extra) {
+                kernel<<<cdiv(P, K1V_G), 256, 0, join>>>(P, a.D, a.M, a.shs, a.opacities, a.scales, a.scale_modifier, tab, nocull_mode(), extra...);
+            };
+            if (aa_of(a)) go(k_preprocess_views_aa<STAGE>);
+            else if (STAGE && per_gaussian_stamps(P)) go(k_preprocess_views_stamps, per_gaussian_stamps(P));   // (staged rows, no AA only)
+            else go(k_preprocess_views<STAGE>);
+        };
+        if (a.M == 16 && ((uintptr_t)a.shs & 15u) == 0) form(std::true_type{});
+        else form(std::false_type{});
         LAUNCH_CHECK();
     }
     {
@@ -1074,6 +1064,7 @@ static int begin_launch_views(int V, const int *tk, hipStream_t join) {
     return 0;
 }
 
+// the flat begin: its arguments as a csplat_view (everything else zero; the outputs arrive with csplat_forward_finish)
 int csplat_forward_begin(void *stream, int P, int D, int M, const float *bg, int W, int H, const float *means3D,
                          const float *shs, const float *colors_precomp, const float *opacities, const float *scales,
                          float scale_modifier, const float *rotations, const float *cov3D_precomp, const float *view,
@@ -1081,14 +1072,17 @@ int csplat_forward_begin(void *stream, int P, int D, int M, const float *bg, int
                          csplat_alloc_fn alloc, void *alloc_ctx, int32_t *radii, int *ticket_out) {
     CSPLAT_REQUIRE(!(prefiltered & CSPLAT_ANTIALIAS), "csplat_forward / csplat_forward_begin: CSPLAT_ANTIALIAS needs a csplat_view entry point "
                                                       "(csplat_forward_views*), whose backward knows the bit");
-    if (int rc = begin_prepare(stream, P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                               cov3D_precomp, view, proj, campos, tanfovx, tanfovy, prefiltered, alloc, alloc_ctx, radii, ticket_out))
-        return rc;
+    csplat_view w;
+    memset(&w, 0, sizeof(w));
+    w.stream = stream;
+    w.P = P; w.D = D; w.M = M; w.W = W; w.H = H; w.prefiltered = prefiltered;
+    w.scale_modifier = scale_modifier; w.tanfovx = tanfovx; w.tanfovy = tanfovy;
+    w.bg = bg; w.means3D = means3D; w.shs = shs; w.colors_precomp = colors_precomp; w.opacities = opacities; w.scales = scales;
+    w.rotations = rotations; w.cov3D_precomp = cov3D_precomp; w.view = view; w.proj = proj; w.campos = campos;
+    w.alloc_ctx = alloc_ctx; w.radii = radii;
+    if (int rc = begin_prepare(w, alloc, ticket_out)) return rc;
     const int rc = begin_launch(g_tickets[*ticket_out]);
-    if (rc) {
-        std::lock_guard<std::mutex> lk(g_ticket_mu);
-        g_tickets[*ticket_out].used = false;
-    }
+    if (rc) release_ticket(*ticket_out);
     return rc;
 }
 
@@ -1108,13 +1102,13 @@ static int finish_read(const FwdTicket &t, uint32_t host_info[3], hipStream_t la
             if (got) { host_info[0] = t.mb_host[0]; host_info[1] = t.mb_host[1]; host_info[2] = t.mb_host[3]; }
         }
         if (!got) {
-            HIP_TRY(hipMemcpyAsync(host_info, t.info, 12, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(host_info, t.im.info, 12, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
-    } else if (t.P > 0) {
+    } else if (t.w.P > 0) {
         ProfScope ps(PROF_K2, s);
-        if (int rc = csplat_inclusive_scan_u32(s, t.g.tiles_touched, t.g.offsets, t.P, t.g.scan_tmp)) return rc;
-        HIP_TRY(hipMemcpyAsync(host_info, t.g.offsets + (t.P - 1), 4, hipMemcpyDeviceToHost, s));
+        if (int rc = csplat_inclusive_scan_u32(s, t.g.tiles_touched, t.g.offsets, t.w.P, t.g.scan_tmp)) return rc;
+        HIP_TRY(hipMemcpyAsync(host_info, t.g.offsets + (t.w.P - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         host_info[1] = 0xFFFFFFFFu;
         host_info[2] = 0xFFFFFFFFu;
@@ -1159,15 +1153,15 @@ static uint32_t tile_sort_cap() {
     return s_lds_big ? (uint32_t)BUCKET_CAP : 5120u;
 }
 // `longest`: no tile list of the launch is longer (LDS and the keys per lane are sized from it); `busy`: its non-empty tiles
-static void tile_sort_launch(hipStream_t s, int tiles, uint32_t longest, uint32_t busy, const int2 *ranges, const uint64_t *comp,
-                             uint64_t *keys_sorted, uint32_t *ids_sorted, const uint32_t *info, int mode) {
+static void tile_sort_launch(hipStream_t s, int tiles, uint32_t longest, uint32_t busy, const ImageView &im, const uint64_t *comp,
+                             const BinView &b, int mode) {
     const size_t lds = tsort_lds_bytes((int)longest);
     const int grid = tiles < TSORT_GRID ? tiles : TSORT_GRID, items = tsort_items(longest);
     const bool dense = tsort_dense(items, busy);
     switch (items) {
 #define X(I) case I:                                                                                                                        \
-        if (dense) k_tile_sort<I, I <= 6><<<grid, TSORT_THREADS, lds, s>>>(ranges, comp, keys_sorted, ids_sorted, info, tiles, mode);       \
-        else k_tile_sort<I, false><<<grid, TSORT_THREADS, lds, s>>>(ranges, comp, keys_sorted, ids_sorted, info, tiles, mode);              \
+        if (dense) k_tile_sort<I, I <= 6><<<grid, TSORT_THREADS, lds, s>>>(im.ranges, comp, b.keys_sorted, b.ids_sorted, im.info, tiles, mode); \
+        else k_tile_sort<I, false><<<grid, TSORT_THREADS, lds, s>>>(im.ranges, comp, b.keys_sorted, b.ids_sorted, im.info, tiles, mode);    \
         break;
         TSORT_FOR_ITEMS(X)
 #undef X
@@ -1188,9 +1182,11 @@ static void tile_sort_views_launch(hipStream_t s, int tiles, int V, uint32_t Lca
     }
 }
 
-// Second phase of ALL views in one launch per stage on `join` (see P2Table).  *done = false (and nothing launched or
-// allocated) when the views do not qualify -- a tile list too long for the LDS sort, different sizes -- and the caller
-// finishes view by view.
+// ---- second phase of ALL views in one launch per stage on `join` (see P2Table), as named steps: p2_qualifies, caps_from_history,
+// p2_launch, p2_settle.  The entries further down compose them.
+// Capacities of a batched second phase: list entries per view, longest tile list, non-empty tiles (per view)
+struct Caps { uint32_t R[RASTER_MAX_VIEWS], longest, busy; };
+
 // What the last batched call saw, per image size: the capacities the next one is launched with BEFORE its counts are read.
 // (a short ring: a process that alternates between scenes of different density -- bench.py --mode scenes -- is served by the largest
 // of its recent calls with the same shape instead of failing the speculation at every switch)
@@ -1199,187 +1195,204 @@ constexpr int SPEC_RING = 8;
 static SpecHist g_spec_ring[SPEC_RING];
 static int g_spec_next = 0;
 static std::mutex g_spec_mu;
-
-// A call whose speculative second phase has been launched but whose counts have not been read yet (csplat_forward_views_deferred):
-// what csplat_forward_views_settle needs to finish it.  Keyed by the caller's view array.
-struct PendingViews {
-    bool used = false;
-    const csplat_view *key = nullptr;
-    int V = 0, tk[RASTER_MAX_VIEWS];
-    uint32_t Rcap[RASTER_MAX_VIEWS], Lcap = 0, Bcap = 0;
-};
-constexpr int MAX_PENDING = 8;
-static PendingViews g_pending[MAX_PENDING];
-static std::mutex g_pending_mu;
-
-// lays the chunks of every view out for `Rcap[i]` list entries and launches the five stages of the second phase on `join`
-// (valid != nullptr: K6's first wave leaves 1 there when every view's counts fitted the capacities, else 0 -- csplat_forward_views_faith)
-static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, const uint32_t *Rcap, uint32_t Lcap, int spec, uint32_t Bcap,
-                     uint32_t *valid = nullptr) {
-    const FwdTicket &a = g_tickets[tk[0]];
-    const int P = a.P, W = a.W, H = a.H, tiles = a.tiles, nb = a.nb;
-    {
-        P2Table tab;
-        tab.valid = valid; tab.nviews = V;
-        uint32_t maxR = 0;
-        for (int i = 0; i < V; i++) {
-            const FwdTicket &t = g_tickets[tk[i]];
-            const uint32_t R = Rcap[i];
-            maxR = R > maxR ? R : maxR;
-            void *bbase = t.alloc(t.alloc_ctx, CSPLAT_CHUNK_BINNING, csplat_binning_bytes(R, W, H));
-            void *tbase = t.alloc(t.alloc_ctx, CSPLAT_CHUNK_TEMP, csplat_temp_bytes(P, R, W, H));
-            CSPLAT_REQUIRE(bbase && tbase, "allocator returned NULL");
-            const BinView b = binning_view(bbase, R, tiles);
-            P2View &k = tab.v[i];
-            k.g = t.g; k.cam = t.cam; k.radii = t.radii; k.table = t.table; k.ranges = t.ranges;
-            k.keys_u = temp_view(tbase, R).keys_u;
-            k.keys_sorted = b.keys_sorted; k.ids_sorted = b.ids_sorted; k.seg_offset = b.seg_offset; k.slot_tile = b.slot_tile;
-            k.ckpt = b.ckpt; k.mask16 = b.mask16; k.bbits = b.bbits; k.bmask = b.bmask; k.recA = b.recA; k.recB = b.recB; k.recC = b.recC;
-            k.bg = t.bg; k.final_T = t.final_T; k.n_contrib = t.n_contrib; k.out_color = v[i].out_color; k.out_depth = v[i].out_depth;
-            k.R = R; k.info = t.info; k.Lcap = Lcap; k.Bcap = Bcap; k.spec = spec;
-            v[i].layout_rendered = (int)R; v[i].geom = t.gbase; v[i].binning = bbase; v[i].image = t.ibase;
-        }
-        {
-            ProfScope ps(PROF_K3, join);
-            k_emit_bucket_views<<<dim3(nb + 1, V), BUCKET_G, (size_t)tiles * 4, join>>>(P, tiles, tab);
-            LAUNCH_CHECK();
-        }
-        {
-            ProfScope ps(PROF_K4, join);
-            tile_sort_views_launch(join, tiles, V, Lcap, Bcap, tab, tsort_mode(P));
-            LAUNCH_CHECK();
-        }
-        {
-            ProfScope ps(PROF_K5, join);
-            const int exact = dbg(DBG_NO_ELLIPSE_STAGE) ? 0 : 1, nbm = cdiv((int64_t)maxR + 1, 256);
-            if (V == 1 || V == 2 || V == 4 || V == 8)         // one view per XCD (see k_block_masks_views)
-                k_block_masks_views<<<dim3((unsigned)(((int64_t)nbm * V + 7) / 8 * 8)), 256, 0, join>>>(tab, exact, V);
-            else
-                k_block_masks_views<<<dim3(nbm, V), 256, 0, join>>>(tab, exact, 0);
-            LAUNCH_CHECK();
-        }
-        {
-            ProfScope ps(PROF_K6, join);
-            // Waves for the NON-EMPTY tiles only (Bcap of them, longest list first) + K6_EXTRA waves that paint the empty tiles' pixels: on
-            // scene_1 nine tiles in ten are empty, and launching 16 waves for each of them cost ~50 us of the launch (the same launch on a
-            // scene of 500 Gaussians: 51 us).  What is left is ~17 k waves with work for 8192 wave slots, 40-75 us each in the row form
-            // (four survivors a step): the launch is as long as a few of those in a row on the unluckiest slot.  Hence the SURVIVOR-COLUMN
-            // form by default (sixteen survivors a step: a quarter of the steps, each longer; 96 VGPRs, which no longer matters with two
-            // waves per slot to place): 158 -> 137 us for four views, step 0.685 -> 0.665 ms (same box, three alternations).  Bit 15 of
-            // csplat_debug_flags selects the row form.
-            const int total = cdiv(tiles, 8) * 128, bg_ = cdiv((int)Bcap, 8) * 128, busy_grid = bg_ < total ? bg_ : total;
-            if (!dbg(CSPLAT_DEBUG_K6_ROWS))
-                k_composite_fwd_views<false><<<dim3(busy_grid + K6_EXTRA, V), 64, 0, join>>>(tiles, W, H, tab, busy_grid);
-            else
-                k_composite_fwd_views<true><<<dim3(busy_grid + K6_EXTRA, V), 64, 0, join>>>(tiles, W, H, tab, busy_grid);
-            LAUNCH_CHECK();
-        }
-        return 0;
+// info[i]: the three counts view i's first phase left (finish_read)
+static void remember(int P, int W, int H, int V, const uint32_t (*info)[3]) {
+    std::lock_guard<std::mutex> lk(g_spec_mu);
+    SpecHist &e = g_spec_ring[g_spec_next];
+    g_spec_next = (g_spec_next + 1) % SPEC_RING;
+    e.W = W; e.H = H; e.P = P; e.R = 0; e.longest = 0; e.busy = 0;
+    for (int i = 0; i < V; i++) {
+        e.R = info[i][0] > e.R ? info[i][0] : e.R;
+        e.longest = info[i][1] > e.longest ? info[i][1] : e.longest;
+        e.busy = info[i][2] > e.busy ? info[i][2] : e.busy;
     }
 }
-
-// mode 0: the whole second phase (launch, read the counts, repeat with exact sizes if the speculation missed);
-// mode 1: as 0, but when the speculative launch is possible return right after it with *pend filled (pend->used) -- nothing is read;
-// mode 2: finish a mode-1 call: read the counts, accept or repeat (*relaunched)
-static int finish_views_batched(int V, const int *tk, csplat_view *v, hipStream_t join, bool *done, int mode = 0,
-                                PendingViews *pend = nullptr, int *relaunched = nullptr) {
-    *done = false;
-    if (V < 1 || V > RASTER_MAX_VIEWS || dbg(CSPLAT_DEBUG_PER_VIEW_LAUNCHES)) return 0;
-    const FwdTicket &a = g_tickets[tk[0]];
-    for (int i = 0; i < V; i++) {
-        const FwdTicket &t = g_tickets[tk[i]];
-        if (!t.can_bucket || t.P != a.P || t.W != a.W || t.H != a.H || t.P <= 0) return 0;
-    }
-    const int P = a.P, W = a.W, H = a.H, tiles = a.tiles;
-    const uint32_t cap = tile_sort_cap();
-    uint32_t info[RASTER_MAX_VIEWS][3];
-    bool have_info = false;
-    auto read_counts = [&]() -> int {   // the one host read of the call: instances and longest tile list of every view
-        for (int i = 0; i < V && !have_info; i++)
-            if (int rc = finish_read(g_tickets[tk[i]], info[i], join)) return rc;
-        have_info = true;
-        return 0;
-    };
-    auto launch = [&](const uint32_t *Rcap, uint32_t Lcap, int spec, uint32_t Bcap) -> int { return p2_launch(V, tk, v, join, Rcap, Lcap, spec, Bcap); };
-    auto remember = [&]() {
-        std::lock_guard<std::mutex> lk(g_spec_mu);
-        SpecHist &e = g_spec_ring[g_spec_next];
-        g_spec_next = (g_spec_next + 1) % SPEC_RING;
-        e.W = W; e.H = H; e.P = P; e.R = 0; e.longest = 0; e.busy = 0;
-        for (int i = 0; i < V; i++) {
-            e.R = info[i][0] > e.R ? info[i][0] : e.R;
-            e.longest = info[i][1] > e.longest ? info[i][1] : e.longest;
-            e.busy = info[i][2] > e.busy ? info[i][2] : e.busy;
-        }
-    };
-    auto release = [&]() {
-        std::lock_guard<std::mutex> lk(g_ticket_mu);
-        for (int i = 0; i < V; i++) g_tickets[tk[i]].used = false;
-    };
-    // ---- speculative launch: in a training loop the counts of consecutive steps differ by a few per cent, and waiting for them
-    // leaves the GPU idle for a host round trip (~40 us of a 1 ms step).  With the previous call's counts + 1/8 as capacities the
-    // second phase is queued straight behind the first; the counts are read AFTER that (the GPU is busy with the phase by then),
-    // and a view whose counts do not fit was left untouched by the kernels (p2_live) -- the phase is then repeated with exact
-    // sizes.  csplat_debug_flags bit 10 switches the speculation off.
+// Speculative capacities: in a training loop the counts of consecutive steps differ by a few per cent, and waiting for them leaves the
+// GPU idle for a host round trip (~40 us of a 1 ms step).  With the largest recent counts of the shape + 1/8 as capacities the second
+// phase is queued straight behind the first; the counts are read AFTER that (the GPU is busy with the phase by then), and a view whose
+// counts do not fit was left untouched by the kernels (p2_live) -- the phase is then repeated with exact sizes (p2_settle).
+// false = the ring has no entry of the shape.
+static bool caps_from_history(int P, int W, int H, int tiles, int V, Caps &c) {
     SpecHist hist;
     {
         std::lock_guard<std::mutex> lk(g_spec_mu);
         for (const SpecHist &e : g_spec_ring)
             if (e.R > 0 && e.W == W && e.H == H && e.P == P) {
-                hist.W = W; hist.H = H; hist.P = P;
                 hist.R = e.R > hist.R ? e.R : hist.R;
                 hist.longest = e.longest > hist.longest ? e.longest : hist.longest;
                 hist.busy = e.busy > hist.busy ? e.busy : hist.busy;
             }
     }
-    if (mode == 2 || (!dbg(CSPLAT_DEBUG_NO_SPECULATION) && hist.R > 0)) {
-        uint32_t Rcap[RASTER_MAX_VIEWS];
-        uint32_t Lcap, Bcap;
-        if (mode == 2) {        // the capacities the pending call was launched with
-            for (int i = 0; i < V; i++) Rcap[i] = pend->Rcap[i];
-            Lcap = pend->Lcap;
-            Bcap = pend->Bcap;
-        } else {
-            const uint64_t want = (uint64_t)hist.R + hist.R / 8 + 4096;
-            const uint32_t rc32 = (uint32_t)(want > 0x7FFFFF00ull ? 0x7FFFFF00ull : want);
-            for (int i = 0; i < V; i++) Rcap[i] = rc32;
-            Lcap = hist.longest + hist.longest / 4 + 64;
-            Lcap = Lcap > cap ? cap : Lcap;
-            Bcap = hist.busy + hist.busy / 8 + 16;          // non-empty tiles: sizes the compositing forward's grid
-            Bcap = Bcap > (uint32_t)tiles ? (uint32_t)tiles : Bcap;
-            if (int rc = launch(Rcap, Lcap, 1, Bcap)) return rc;
-            if (mode == 1) {    // deferred: the caller reads the counts later (csplat_forward_views_settle), the GPU has its work
-                pend->used = true; pend->key = v; pend->V = V; pend->Lcap = Lcap; pend->Bcap = Bcap;
-                for (int i = 0; i < V; i++) { pend->tk[i] = tk[i]; pend->Rcap[i] = Rcap[i]; v[i].num_rendered = -1; v[i].busy_tiles = 0; }
-                *done = true;
-                return 0;
-            }
-        }
-        if (int rc = read_counts()) return rc;
-        bool fits = true;
-        for (int i = 0; i < V; i++) fits = fits && info[i][0] - 1u < Rcap[i] && info[i][1] <= Lcap && info[i][2] <= Bcap;
-        remember();
-        if (fits) {
-            for (int i = 0; i < V; i++) { v[i].num_rendered = (int)info[i][0]; v[i].busy_tiles = (int)info[i][2]; }
-            release();
-            *done = true;
-            return 0;
-        }
+    if (hist.R == 0) return false;
+    const uint64_t want = (uint64_t)hist.R + hist.R / 8 + 4096;
+    const uint32_t rc32 = (uint32_t)(want > 0x7FFFFF00ull ? 0x7FFFFF00ull : want), cap = tile_sort_cap();
+    for (int i = 0; i < V; i++) c.R[i] = rc32;
+    c.longest = hist.longest + hist.longest / 4 + 64;
+    c.longest = c.longest > cap ? cap : c.longest;
+    c.busy = hist.busy + hist.busy / 8 + 16;          // non-empty tiles: sizes the compositing forward's grid
+    c.busy = c.busy > (uint32_t)tiles ? (uint32_t)tiles : c.busy;
+    return true;
+}
+
+// A call whose speculative second phase has been launched but whose counts have not been read yet (csplat_forward_views_deferred):
+// what csplat_forward_views_settle needs to finish it.  Keyed by the caller's view array.
+struct PendingViews {
+    bool parked = false;
+    const csplat_view *key = nullptr;
+    int V = 0, tk[RASTER_MAX_VIEWS];
+    Caps caps;
+};
+constexpr int MAX_PENDING = 8;
+static PendingViews g_pending[MAX_PENDING];
+static std::mutex g_pending_mu;
+
+// The tickets a call has opened.  Whatever way the call ends, the destructor gives back those it still owns: a ticket leaves the set
+// only into a pending slot (park; settle takes them back with adopt) or into csplat_forward_finish, which releases its own (hand_over).
+namespace {     // (its member functions stay out of the library's exports)
+struct TicketSet {
+    int tk[MAX_TICKETS], n = 0, handed = 0;         // tk[handed..n) are this call's to release
+    TicketSet() = default;
+    TicketSet(const TicketSet &) = delete;
+    TicketSet &operator=(const TicketSet &) = delete;
+    ~TicketSet() {
+        for (int i = handed; i < n; i++) release_ticket(tk[i]);
     }
-    if (int rc = read_counts()) return rc;
-    uint32_t longest = 0, busiest = 0, Rex[RASTER_MAX_VIEWS];
+    // begin_prepare for views[0..V), up to the first refusal
+    int prepare(int V, const csplat_view *v, csplat_alloc_fn alloc) {
+        for (; n < V; n++)
+            if (int rc = begin_prepare(v[n], alloc, &tk[n])) return rc;
+        return 0;
+    }
+    int hand_over() { return tk[handed++]; }
+    // false = no free pending slot (the set keeps its tickets)
+    bool park(const csplat_view *key, const Caps &caps) {
+        std::lock_guard<std::mutex> lk(g_pending_mu);
+        for (PendingViews &p : g_pending)
+            if (!p.parked) {
+                p.parked = true; p.key = key; p.V = n; p.caps = caps;
+                for (int i = 0; i < n; i++) p.tk[i] = tk[i];
+                n = handed = 0;
+                return true;
+            }
+        return false;
+    }
+    void adopt(const PendingViews &p) {
+        for (n = 0; n < p.V; n++) tk[n] = p.tk[n];
+    }
+};
+}  // namespace
+
+// the checks a call passes before its second phase can be one launch per stage; false: the caller finishes view by view
+static bool p2_qualifies(int V, const int *tk) {
+    if (V < 1 || V > RASTER_MAX_VIEWS || dbg(CSPLAT_DEBUG_PER_VIEW_LAUNCHES)) return false;
+    const FwdTicket &a = g_tickets[tk[0]];
+    for (int i = 0; i < V; i++) {
+        const FwdTicket &t = g_tickets[tk[i]];
+        if (!t.can_bucket || t.w.P != a.w.P || t.w.W != a.w.W || t.w.H != a.w.H || t.w.P <= 0) return false;
+    }
+    return true;
+}
+
+// lays the chunks of every view out for `caps.R[i]` list entries and launches the five stages of the second phase on `join`, writing
+// the images v[i].out_color / out_depth name NOW.  spec: the capacities are a guess, the kernels check the counts against them;
+// valid != nullptr: K6's first wave leaves 1 there when every view's counts fitted the capacities, else 0 (csplat_forward_views_faith)
+static int p2_launch(int V, const int *tk, csplat_view *v, hipStream_t join, const Caps &caps, int spec, uint32_t *valid) {
+    const FwdTicket &a = g_tickets[tk[0]];
+    const int P = a.w.P, W = a.w.W, H = a.w.H, tiles = a.tiles, nb = a.nb;
+    const uint32_t Lcap = caps.longest, Bcap = caps.busy;
+    P2Table tab;
+    tab.valid = valid; tab.nviews = V;
+    uint32_t maxR = 0;
+    for (int i = 0; i < V; i++) {
+        const FwdTicket &t = g_tickets[tk[i]];
+        const uint32_t R = caps.R[i];
+        maxR = R > maxR ? R : maxR;
+        void *bbase = t.alloc(t.w.alloc_ctx, CSPLAT_CHUNK_BINNING, csplat_binning_bytes(R, W, H));
+        void *tbase = t.alloc(t.w.alloc_ctx, CSPLAT_CHUNK_TEMP, csplat_temp_bytes(P, R, W, H));
+        CSPLAT_REQUIRE(bbase && tbase, "allocator returned NULL");
+        const BinView b = binning_view(bbase, R, tiles);
+        P2View &k = tab.v[i];
+        k.g = t.g; k.cam = t.cam; k.radii = t.w.radii; k.table = t.table; k.ranges = t.im.ranges;
+        k.keys_u = temp_view(tbase, R).keys_u;
+        k.keys_sorted = b.keys_sorted; k.ids_sorted = b.ids_sorted; k.seg_offset = b.seg_offset; k.slot_tile = b.slot_tile;
+        k.ckpt = b.ckpt; k.mask16 = b.mask16; k.bbits = b.bbits; k.bmask = b.bmask; k.recA = b.recA; k.recB = b.recB; k.recC = b.recC;
+        k.bg = t.w.bg; k.final_T = t.im.final_T; k.n_contrib = t.im.n_contrib; k.out_color = v[i].out_color; k.out_depth = v[i].out_depth;
+        k.R = R; k.info = t.im.info; k.Lcap = Lcap; k.Bcap = Bcap; k.spec = spec;
+        v[i].layout_rendered = (int)R; v[i].geom = t.gbase; v[i].binning = bbase; v[i].image = t.ibase;
+    }
+    {
+        ProfScope ps(PROF_K3, join);
+        k_emit_bucket_views<<<dim3(nb + 1, V), BUCKET_G, (size_t)tiles * 4, join>>>(P, tiles, tab);
+        LAUNCH_CHECK();
+    }
+    {
+        ProfScope ps(PROF_K4, join);
+        tile_sort_views_launch(join, tiles, V, Lcap, Bcap, tab, tsort_mode(P));
+        LAUNCH_CHECK();
+    }
+    {
+        ProfScope ps(PROF_K5, join);
+        const int exact = dbg(DBG_NO_ELLIPSE_STAGE) ? 0 : 1, nbm = cdiv((int64_t)maxR + 1, 256);
+        if (V == 1 || V == 2 || V == 4 || V == 8)         // one view per XCD (see k_block_masks_views)
+            k_block_masks_views<<<dim3((unsigned)(((int64_t)nbm * V + 7) / 8 * 8)), 256, 0, join>>>(tab, exact, V);
+        else
+            k_block_masks_views<<<dim3(nbm, V), 256, 0, join>>>(tab, exact, 0);
+        LAUNCH_CHECK();
+    }
+    {
+        ProfScope ps(PROF_K6, join);
+        // Waves for the NON-EMPTY tiles only (Bcap of them, longest list first) + K6_EXTRA waves that paint the empty tiles' pixels: on
+        // scene_1 nine tiles in ten are empty, and launching 16 waves for each of them cost ~50 us of the launch (the same launch on a
+        // scene of 500 Gaussians: 51 us).  What is left is ~17 k waves with work for 8192 wave slots, 40-75 us each in the row form
+        // (four survivors a step): the launch is as long as a few of those in a row on the unluckiest slot.  Hence the SURVIVOR-COLUMN
+        // form by default (sixteen survivors a step: a quarter of the steps, each longer; 96 VGPRs, which no longer matters with two
+        // waves per slot to place): 158 -> 137 us for four views, step 0.685 -> 0.665 ms (same box, three alternations).  Bit 15 of
+        // csplat_debug_flags selects the row form.
+        const int total = cdiv(tiles, 8) * 128, bg_ = cdiv((int)Bcap, 8) * 128, busy_grid = bg_ < total ? bg_ : total;
+        if (!dbg(CSPLAT_DEBUG_K6_ROWS))
+            k_composite_fwd_views<false><<<dim3(busy_grid + K6_EXTRA, V), 64, 0, join>>>(tiles, W, H, tab, busy_grid);
+        else
+            k_composite_fwd_views<true><<<dim3(busy_grid + K6_EXTRA, V), 64, 0, join>>>(tiles, W, H, tab, busy_grid);
+        LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// The one host read of a batched call: the counts of every view, behind the speculative launch when there was one (`speculated`: its
+// capacities).  They fit: accepted as launched.  They do not, or nothing was launched yet: the phase is launched with exact sizes
+// (*relaunched = 1 when given) -- unless a list is too long for the in-LDS sort or a view is empty: P2_PER_VIEW, the caller goes view
+// by view.  The ring learns the counts (remember) whenever they were compared with capacities, and before every exact launch.
+enum P2Result { P2_DONE, P2_PER_VIEW };
+static int p2_settle(int V, const int *tk, csplat_view *v, hipStream_t join, const Caps *speculated, int *relaunched, P2Result *how) {
+    const csplat_view &a = g_tickets[tk[0]].w;
+    *how = P2_PER_VIEW;
+    uint32_t info[RASTER_MAX_VIEWS][3];
+    for (int i = 0; i < V; i++)
+        if (int rc = finish_read(g_tickets[tk[i]], info[i], join)) return rc;
+    auto accept = [&]() {
+        for (int i = 0; i < V; i++) { v[i].num_rendered = (int)info[i][0]; v[i].busy_tiles = (int)info[i][2]; }
+        *how = P2_DONE;
+    };
+    if (speculated) {
+        bool fits = true;
+        for (int i = 0; i < V; i++)
+            fits = fits && info[i][0] - 1u < speculated->R[i] && info[i][1] <= speculated->longest && info[i][2] <= speculated->busy;
+        remember(a.P, a.W, a.H, V, info);
+        if (fits) { accept(); return 0; }
+    }
+    const uint32_t cap = tile_sort_cap();
+    Caps exact;
+    exact.longest = exact.busy = 0;
     for (int i = 0; i < V; i++) {
         if (info[i][1] > cap || info[i][0] == 0) return 0;      // a list too long for the in-LDS sort, an empty view: view by view
-        longest = info[i][1] > longest ? info[i][1] : longest;
-        busiest = info[i][2] > busiest ? info[i][2] : busiest;
-        Rex[i] = info[i][0];
+        exact.longest = info[i][1] > exact.longest ? info[i][1] : exact.longest;
+        exact.busy = info[i][2] > exact.busy ? info[i][2] : exact.busy;
+        exact.R[i] = info[i][0];
     }
-    remember();
-    if (int rc = launch(Rex, longest, 0, busiest)) return rc;
+    remember(a.P, a.W, a.H, V, info);
+    if (int rc = p2_launch(V, tk, v, join, exact, 0, nullptr)) return rc;
     if (relaunched) *relaunched = 1;
-    for (int i = 0; i < V; i++) { v[i].num_rendered = (int)info[i][0]; v[i].busy_tiles = (int)info[i][2]; }
-    release();
-    *done = true;
+    accept();
     return 0;
 }
 
@@ -1387,48 +1400,38 @@ int csplat_forward_finish(int ticket, float *out_color, float *out_depth, int *n
                           void **binning_out, void **image_out) {
     CSPLAT_REQUIRE(ticket >= 0 && ticket < MAX_TICKETS && g_tickets[ticket].used, "csplat_forward_finish: unknown ticket");
     const FwdTicket t = g_tickets[ticket];
-    {
-        std::lock_guard<std::mutex> lk(g_ticket_mu);
-        g_tickets[ticket].used = false;   // released whatever happens below
-    }
+    release_ticket(ticket);     // released whatever happens below: the slot is free before the first launch
     hipStream_t s = t.s;
-    const int P = t.P, W = t.W, H = t.H, tiles = t.tiles, nb = t.nb;
-    const bool can_bucket = t.can_bucket;
-    const Cam cam = t.cam;
-    const Geom g = t.g;
-    void *gbase = t.gbase, *ibase = t.ibase;
-    int2 *ranges = t.ranges;
-    uint32_t *n_contrib = t.n_contrib, *table = t.table;
-    float *final_T = t.final_T;
-    const float *bg = t.bg;
-    int32_t *radii = t.radii;
-    csplat_alloc_fn alloc = t.alloc;
-    void *alloc_ctx = t.alloc_ctx;
+    const int P = t.w.P, W = t.w.W, H = t.w.H, tiles = t.tiles, nb = t.nb;
+    const Cam &cam = t.cam;
+    const Geom &g = t.g;
+    int2 *ranges = t.im.ranges;
+    const int32_t *radii = t.w.radii;
     uint32_t host_info[3] = {0, 0, 0};   // R, longest tile list, non-empty tiles
     if (int rc = finish_read(t, host_info)) return rc;
     const uint32_t R = host_info[0];
     const uint32_t cap = tile_sort_cap();
-    const bool bucketed = can_bucket && host_info[1] <= cap;
+    const bool bucketed = t.can_bucket && host_info[1] <= cap;
     *num_rendered = (int)R;
-    void *bbase = alloc(alloc_ctx, CSPLAT_CHUNK_BINNING, csplat_binning_bytes(R, W, H));
+    void *bbase = t.alloc(t.w.alloc_ctx, CSPLAT_CHUNK_BINNING, csplat_binning_bytes(R, W, H));
     CSPLAT_REQUIRE(bbase, "allocator returned NULL");
     const BinView b = binning_view(bbase, R, tiles);
     if (R > 0) {
-        void *tbase = alloc(alloc_ctx, CSPLAT_CHUNK_TEMP, csplat_temp_bytes(P, R, W, H));
+        void *tbase = t.alloc(t.w.alloc_ctx, CSPLAT_CHUNK_TEMP, csplat_temp_bytes(P, R, W, H));
         CSPLAT_REQUIRE(tbase, "allocator returned NULL");
         const TempView tmp = temp_view(tbase, R);
         if (bucketed) {
             {
                 ProfScope ps(PROF_K3, s);
-                k_emit_bucket<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, g.xy, g.depth, radii, cam, table, ranges, tmp.keys_u);
+                k_emit_bucket<<<nb, BUCKET_G, (size_t)tiles * 4, s>>>(P, tiles, g.xy, g.depth, radii, cam, t.table, ranges, tmp.keys_u);
                 LAUNCH_CHECK();
             }
             ProfScope ps(PROF_K4, s);
-            tile_sort_launch(s, tiles, host_info[1], host_info[2], ranges, tmp.keys_u, b.keys_sorted, b.ids_sorted, t.info, tsort_mode(P));
+            tile_sort_launch(s, tiles, host_info[1], host_info[2], t.im, tmp.keys_u, b, tsort_mode(P));
             LAUNCH_CHECK();
         } else {
             // a tile list longer than the LDS sort takes: the global stable radix sort (upstream's pipeline shape)
-            if (can_bucket) {   // (the bucket path was attempted: the P-scan has not run yet)
+            if (t.can_bucket) {   // (the bucket path was attempted: the P-scan has not run yet)
                 ProfScope ps(PROF_K2, s);
                 if (int rc = csplat_inclusive_scan_u32(s, g.tiles_touched, g.offsets, P, g.scan_tmp)) return rc;
             }
@@ -1465,14 +1468,14 @@ int csplat_forward_finish(int ticket, float *out_color, float *out_depth, int *n
     {
         ProfScope ps(PROF_K6, s);
         if (dbg(CSPLAT_DEBUG_K6_ROWS))       // (bit 15: the row form, four survivors a step; default: the survivor-column form, 74 -> 67 us alone)
-            k_composite_fwd<true><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, bg, b.seg_offset,
-                                                                      b.ckpt, final_T, n_contrib, out_color, out_depth, b.bbits, b.bmask);
+            k_composite_fwd<true><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, t.w.bg, b.seg_offset,
+                                                                      b.ckpt, t.im.final_T, t.im.n_contrib, out_color, out_depth, b.bbits, b.bmask);
         else
-            k_composite_fwd<false><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, bg, b.seg_offset,
-                                                                       b.ckpt, final_T, n_contrib, out_color, out_depth, b.bbits, b.bmask);
+            k_composite_fwd<false><<<cdiv(tiles, 8) * 128, 64, 0, s>>>(tiles, W, H, cam.gx, ranges, b.mask16, b.recA, b.recB, b.recC, R, t.w.bg, b.seg_offset,
+                                                                       b.ckpt, t.im.final_T, t.im.n_contrib, out_color, out_depth, b.bbits, b.bmask);
         LAUNCH_CHECK();
     }
-    *geom_out = gbase; *binning_out = bbase; *image_out = ibase;
+    *geom_out = t.gbase; *binning_out = bbase; *image_out = t.ibase;
     return 0;
 }
 
@@ -1489,9 +1492,6 @@ int csplat_forward(void *stream, int P, int D, int M, const float *bg, int W, in
         return rc;
     return csplat_forward_finish(ticket, out_color, out_depth, num_rendered, geom_out, binning_out, image_out);
 }
-
-// antialiasing (csplat_view.prefiltered & CSPLAT_ANTIALIAS): K1 stored o' = o h; K8 takes its AA variant and reads the raw opacities
-static bool aa_of(const csplat_view &w) { return (w.prefiltered & CSPLAT_ANTIALIAS) != 0; }
 
 // The single-view K8 of `w` on `k8s`: one of k_preprocess_bwd / _depth / _cam<DEPTH> / _aa<DEPTH, CAM>, each with the SH rows staged in
 // LDS (128 threads) or not (256).  depth: record slot 9 -> dL/dmean3D (csplat_view.dL_ddepth); cam_slab != NULL: the camera-gradient
@@ -1602,17 +1602,13 @@ static int fence_out(int V, const csplat_view *v, hipStream_t join) {
     return 0;
 }
 
-// the per-view tail of a forward call: every prepared ticket is finished (= released) even after an error
-static int finish_views_one_by_one(int V, csplat_view *v, const int *tickets, int begun, hipStream_t join, bool fenced, int rc) {
-    for (int i = 0; i < begun; i++) {
+// the per-view tail of a forward call: every ticket of the set is finished (csplat_forward_finish releases its own) or, after an
+// error, left to the set to release
+static int finish_views_one_by_one(int V, csplat_view *v, TicketSet &ts, hipStream_t join, bool fenced, int rc) {
+    for (int i = 0; i < ts.n && rc == 0; i++) {
         csplat_view &w = v[i];
-        if (rc == 0) {
-            rc = csplat_forward_finish(tickets[i], w.out_color, w.out_depth, &w.num_rendered, &w.geom, &w.binning, &w.image);
-            w.layout_rendered = w.num_rendered;
-        } else {
-            std::lock_guard<std::mutex> lk(g_ticket_mu);
-            g_tickets[tickets[i]].used = false;
-        }
+        rc = csplat_forward_finish(ts.hand_over(), w.out_color, w.out_depth, &w.num_rendered, &w.geom, &w.binning, &w.image);
+        w.layout_rendered = w.num_rendered;
     }
     // (also on the error path: the side streams may hold work on torch-owned chunks that the caller frees on its own stream as
     // soon as the error propagates)
@@ -1620,59 +1616,46 @@ static int finish_views_one_by_one(int V, csplat_view *v, const int *tickets, in
     return rc;
 }
 
+// csplat_forward_views (pending == nullptr) and csplat_forward_views_deferred: prepare; then, for views that share their Gaussians, K1
+// of all views and the second phase -- speculate and settle, or settle alone (no history of the shape, speculation switched off by
+// csplat_debug_flags bit 10); the deferred call parks itself behind the speculative launch instead of settling.  Everything else, and
+// a call whose counts p2_settle hands back, goes view by view on the views' own streams.
 static int forward_views_impl(int V, csplat_view *v, csplat_alloc_fn alloc, void *join_stream, int *pending) {
     CSPLAT_REQUIRE(V >= 0 && V <= MAX_TICKETS && (V == 0 || v != nullptr), "csplat_forward_views: bad view count");
     hipStream_t join = (hipStream_t)join_stream;
-    int tickets[MAX_TICKETS];
-    int rc = 0, begun = 0;
+    TicketSet ts;
     if (pending) *pending = 0;
-    for (; begun < V; begun++) {
-        csplat_view &w = v[begun];
-        rc = begin_prepare(w.stream, w.P, w.D, w.M, w.bg, w.W, w.H, w.means3D, w.shs, w.colors_precomp, w.opacities, w.scales,
-                           w.scale_modifier, w.rotations, w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy,
-                           w.prefiltered, alloc, w.alloc_ctx, w.radii, &tickets[begun]);
-        if (rc) break;
-    }
+    int rc = ts.prepare(V, v, alloc);
     bool fenced = false;
-    if (rc == 0 && begin_views_compatible(V, tickets)) {
+    if (rc == 0 && begin_views_compatible(V, ts.tk)) {
         // first phase of all views in four launches on the join stream ...
-        rc = begin_launch_views(V, tickets, join);
+        rc = begin_launch_views(V, ts.tk, join);
         // ... and, when every tile list fits the in-LDS sort, the second phase in five more, also on the join stream: no
         // side stream is involved at all
-        bool done = false;
-        PendingViews pend;
-        if (rc == 0) rc = finish_views_batched(V, tickets, v, join, &done, pending ? 1 : 0, &pend);
-        if (rc == 0 && done && pend.used) {      // deferred: park the call until csplat_forward_views_settle
-            std::lock_guard<std::mutex> lk(g_pending_mu);
-            int slot = -1;
-            for (int i = 0; i < MAX_PENDING && slot < 0; i++)
-                if (!g_pending[i].used) slot = i;
-            if (slot >= 0) {
-                g_pending[slot] = pend;
-                *pending = 1;
-                return 0;
+        P2Result how = P2_PER_VIEW;
+        if (rc == 0 && p2_qualifies(V, ts.tk)) {
+            const FwdTicket &a = g_tickets[ts.tk[0]];
+            Caps caps;
+            const bool spec = caps_from_history(a.w.P, a.w.W, a.w.H, a.tiles, V, caps) && !dbg(CSPLAT_DEBUG_NO_SPECULATION);
+            if (spec) rc = p2_launch(V, ts.tk, v, join, caps, 1, nullptr);
+            if (rc == 0 && spec && pending) {   // deferred: the caller reads the counts later (settle), the GPU has its work
+                for (int i = 0; i < V; i++) { v[i].num_rendered = -1; v[i].busy_tiles = 0; }
+                if (ts.park(v, caps)) {
+                    *pending = 1;
+                    return 0;
+                }                               // (no free slot: settle right here)
             }
+            if (rc == 0) rc = p2_settle(V, ts.tk, v, join, spec ? &caps : nullptr, nullptr, &how);
         }
-        if (rc == 0 && done && pend.used) {      // (no free slot: settle right here)
-            int rl = 0;
-            done = false;
-            rc = finish_views_batched(V, tickets, v, join, &done, 2, &pend, &rl);
-        }
-        if (done || rc) {
-            if (rc) {
-                std::lock_guard<std::mutex> lk(g_ticket_mu);
-                for (int i = 0; i < begun; i++) g_tickets[tickets[i]].used = false;
-            }
-            return rc;
-        }
+        if (rc || how == P2_DONE) return rc;
         rc = fence_in(V, v, join);     // otherwise the views' streams branch off here
         fenced = rc == 0;
     } else if (rc == 0) {
         rc = fence_in(V, v, join);
         fenced = rc == 0;
-        for (int i = 0; i < V && rc == 0; i++) rc = begin_launch(g_tickets[tickets[i]]);
+        for (int i = 0; i < V && rc == 0; i++) rc = begin_launch(g_tickets[ts.tk[i]]);
     }
-    return finish_views_one_by_one(V, v, tickets, begun, join, fenced, rc);
+    return finish_views_one_by_one(V, v, ts, join, fenced, rc);
 }
 
 // ABI 9: the feature / alpha images of a finished forward (csplat_view.out_features / out_alpha), on the join stream behind every view's
@@ -1813,33 +1796,18 @@ int csplat_forward_views_faith(int V, csplat_view *v, csplat_alloc_fn alloc, voi
     CSPLAT_REQUIRE(caps[0] > 0 && caps[0] <= 0x7FFFFF00u && caps[1] > 0 && caps[1] <= tile_sort_cap() && caps[2] > 0,
                    "csplat_forward_views_faith: capacities out of range");
     hipStream_t join = (hipStream_t)join_stream;
-    int tickets[RASTER_MAX_VIEWS];
-    int rc = 0, begun = 0;
-    for (; begun < V; begun++) {
-        csplat_view &w = v[begun];
-        rc = begin_prepare(w.stream, w.P, w.D, w.M, w.bg, w.W, w.H, w.means3D, w.shs, w.colors_precomp, w.opacities, w.scales,
-                           w.scale_modifier, w.rotations, w.cov3D_precomp, w.view, w.proj, w.campos, w.tanfovx, w.tanfovy,
-                           w.prefiltered, alloc, w.alloc_ctx, w.radii, &tickets[begun]);
-        if (rc) break;
-    }
-    auto release = [&]() {
-        std::lock_guard<std::mutex> lk(g_ticket_mu);
-        for (int i = 0; i < begun; i++) g_tickets[tickets[i]].used = false;
-    };
-    if (rc == 0 && !begin_views_compatible(V, tickets)) {
-        release();
-        CSPLAT_REQUIRE(false, "csplat_forward_views_faith: the views do not qualify for the one-launch-per-stage path");
-    }
-    if (rc == 0) rc = begin_launch_views(V, tickets, join);
-    if (rc == 0) {
-        uint32_t Rcap[RASTER_MAX_VIEWS];
-        for (int i = 0; i < V; i++) Rcap[i] = caps[0];
-        const uint32_t tiles = (uint32_t)g_tickets[tickets[0]].tiles;
-        rc = p2_launch(V, tickets, v, join, Rcap, caps[1], 1, caps[2] > tiles ? tiles : caps[2], valid);
-    }
-    for (int i = 0; i < V && rc == 0; i++) { v[i].num_rendered = (int)caps[0]; v[i].busy_tiles = 0; v[i].valid = valid; }
-    release();
-    return rc;
+    TicketSet ts;
+    if (int rc = ts.prepare(V, v, alloc)) return rc;
+    CSPLAT_REQUIRE(begin_views_compatible(V, ts.tk), "csplat_forward_views_faith: the views do not qualify for the one-launch-per-stage path");
+    if (int rc = begin_launch_views(V, ts.tk, join)) return rc;
+    Caps c;
+    for (int i = 0; i < V; i++) c.R[i] = caps[0];
+    const uint32_t tiles = (uint32_t)g_tickets[ts.tk[0]].tiles;
+    c.longest = caps[1];
+    c.busy = caps[2] > tiles ? tiles : caps[2];
+    if (int rc = p2_launch(V, ts.tk, v, join, c, 1, valid)) return rc;
+    for (int i = 0; i < V; i++) { v[i].num_rendered = (int)caps[0]; v[i].busy_tiles = 0; v[i].valid = valid; }
+    return 0;
 }
 // byte offset, inside the IMAGE chunk, of the three counts a view's first phase leaves (u32: tile instances, longest tile list, non-empty
 // tiles) -- what a caller that launched on faith reads, at a time of its choosing, to size the next launch
@@ -1871,25 +1839,21 @@ static int forward_views_settle_impl(int V, csplat_view *v, void *join_stream, i
         std::lock_guard<std::mutex> lk(g_pending_mu);
         int slot = -1;
         for (int i = 0; i < MAX_PENDING && slot < 0; i++)
-            if (g_pending[i].used && g_pending[i].key == v && g_pending[i].V == V) slot = i;
+            if (g_pending[i].parked && g_pending[i].key == v && g_pending[i].V == V) slot = i;
         CSPLAT_REQUIRE(slot >= 0, "csplat_forward_views_settle: no pending call for this view array");
         pend = g_pending[slot];
-        g_pending[slot].used = false;
+        g_pending[slot].parked = false;
     }
     hipStream_t join = (hipStream_t)join_stream;
-    bool done = false;
-    int rc = finish_views_batched(V, pend.tk, v, join, &done, 2, &pend, relaunched);
-    if (done || rc) {
-        if (rc) {
-            std::lock_guard<std::mutex> lk(g_ticket_mu);
-            for (int i = 0; i < V; i++) g_tickets[pend.tk[i]].used = false;
-        }
-        return rc;
-    }
+    TicketSet ts;
+    ts.adopt(pend);
+    P2Result how;
+    int rc = p2_settle(V, ts.tk, v, join, &pend.caps, relaunched, &how);
+    if (rc || how == P2_DONE) return rc;
     // the exact counts do not qualify for the batched phase (a list too long for the in-LDS sort, an empty view): view by view
     *relaunched = 1;
     rc = fence_in(V, v, join);
-    return finish_views_one_by_one(V, v, pend.tk, V, join, rc == 0, rc);
+    return finish_views_one_by_one(V, v, ts, join, rc == 0, rc);
 }
 
 // Can ONE K8 serve all views?  Same Gaussians (P, D, M, scale modifier, SH and scale tensors), SH staging applicable, and every

@@ -12,7 +12,8 @@ the reference pins: a loss on it reaches means3D, means2D, opacities, scales / r
 a depth gradient the backward is exactly the colour-only one).  The camera tensors of the settings (viewmatrix, projmatrix, campos, bg)
 receive gradients when they require grad (camera refinement, a learnable background; include/csplat.h csplat_view.dL_dview .. dL_dbg):
 only then are they inputs of the autograd Functions, so without them the call is exactly the one without camera gradients.  All compute
-is in libcsplat.so (csplat_forward_begin / _finish / csplat_backward).
+is in libcsplat.so: csplat_forward_views_deferred / _settle / _faith and csplat_backward_views, which take their arguments as csplat_view
+records; the flat csplat_forward_begin / _finish serve the single-view Function when PER_CALL_SPECULATION is off.
 `rasterize_views` renders several independent views in one call, one HIP stream per view.
 Beyond upstream, `features=` ([P, F] float32, 1 <= F <= 6) composites per-Gaussian feature channels with the colour's weights and
 `return_alpha=True` returns the alpha image 1 - T_final, both differentiable (include/csplat.h, csplat_view.features .. dL_dfeat_in);
@@ -332,7 +333,9 @@ PER_CALL_SPECULATION = True      # False: every call waits for its own counts (c
 
 
 class _View:
-    """Everything one view's forward produces and its backward needs (host side of csplat_forward_begin / _finish)."""
+    """Everything one view's forward produces and its backward needs.  `fill` writes it into a csplat_view, the record every library entry
+    keeps a view's arguments in; `begin` / `finish` are the flat two-phase entries (csplat_forward_begin / _finish), which pack the same
+    record themselves."""
 
     def __init__(self, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs):
         _n.require_cuda(means3D)
