@@ -124,6 +124,8 @@ EXPORTS = {
     "csplat_obs_mark": (_i, [_vp, _i64, _i, _i, _vp, _vp, _f, _vp]),
     "csplat_traj_smooth": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "csplat_traj_features": (_i, [_vp, _i, _i, _i64, _vp, _vp, _f, _vp, _vp, _vp]),
+    "csplat_train_update_fwd": (_i, [_vp, _i, _i64, _i] + [_vp] * 12),
+    "csplat_train_update_bwd": (_i, [_vp, _i, _i64] + [_vp] * 12),
     "csplat_psnr_scratch_bytes": (_sz, [_i64]),
     "csplat_psnr": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "csplat_sim_hidden_fwd": (_i, [_vp, _i, _i] + [_vp] * 7),

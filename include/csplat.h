@@ -876,6 +876,47 @@ int csplat_traj_smooth(void *stream, int T, int N, int K, const float *points, f
 int csplat_traj_features(void *stream, int T, int N, int64_t E, const float *pos, const int64_t *edge_index, float inv_dt, float *vel /* or NULL */,
                          float *disp, float *norm);
 
+/* MeshNet training transition (csplat_train_sim.hip): the state update between the predictions of one unrolled training step, the
+ * reference's update_prediction (train_meshnet_sim.py:322-359), forward and backward, one launch each.  H = input_sequence_length, c a
+ * component 0..2; every operation is float32 and rounded once, no contraction:
+ *   pa[n][c]      = pred_acc[n][c] * ostd[c] + omean[c]   (Normalizer.inverse folded in: one multiply, one add, each rounded; pred_acc[n][c]
+ *                   itself when omean / ostd are NULL -- they are given together or not at all)
+ *   vn[n]         = velocity[n] + velocity_noise[n]       (velocity[n] itself when the noise is NULL)
+ *   nv[n][c]      = old_actions[n][c] != 0 ? old_actions[n][c] : vn[n][3(H-1)+c] + pa[n][c]
+ *   new_pos[n][c] = (actions[n][c] == 0 ? init_position[n][c] + nv[n][c] : init_position[n][c]) + actions[n][c]
+ *   hist[n][0 : 3(H-1)] = vn[n][3 : 3H]                    (a shift; H = 1 shifts nothing)
+ *   hist[n][3(H-1)+c]   = actions[n][c] != 0 ? actions[n][c] : vn[n][3(H-1)+c]
+ *   edge_feat[e]  = (d, |d|), d = new_pos[row] - new_pos[col], row / col = edge_index[0 / 1][e]: bit-equal to csplat_gnn_edge_features on
+ *                   new_pos (|d| = sqrtf(fma(dz, dz, fma(dx, dx, dy * dy))), the form that kernel's object code has)
+ * The quirks are the reference's: the masks are per component (a grasped node whose action has one component exactly 0 integrates the
+ * predicted velocity in that component), and the last history slot receives the OLD last velocity with the next action's non-zero
+ * components written over it, not nv.  velocity, velocity_noise, hist [N][3H]; pred_acc, init_position, old_actions, actions, new_pos [N][3];
+ * omean, ostd [3]; edge_index [2][E] int64 with entries in 0 .. N-1 (an entry outside gives a NaN row and reads nothing; the Python surface
+ * checks the range); edge_feat [E][4], 16-byte aligned.  Each of hist, edge_feat, new_pos may be NULL: not wanted.  Edge threads recompute
+ * their two endpoint positions from the node inputs with the same rounded operations, so the forward is ONE launch.
+ *
+ * csplat_train_update_bwd, ONE launch, one thread per node, gathers
+ *   gp[n] = g_new_pos[n] + sum_{e: row = n} (g_d[e] + g_len[e] d[e] / |d[e]|) - sum_{e: col = n} (the same)
+ * with (d[e], |d[e]|) = edge_feat[e] as the forward left it and (g_d[e], g_len[e]) = g_edge_feat[e]; the length term is 0 for a zero-length
+ * edge, as with torch.norm.  The sums run over the CSR by source, then the CSR by destination (csplat_gnn_build_csr's rowptr [N+1] / perm [E],
+ * ascending edge id inside a row), in that fixed order.  g_init_position = gp;
+ * g_pred_acc[n][c] = (actions[n][c] == 0 && old_actions[n][c] == 0) ? gp[n][c] (times ostd[c] when folded) : 0.  Nothing flows to velocity,
+ * the noise or the actions, and hist carries no gradient.  g_edge_feat or g_new_pos may be NULL (no such gradient arrived), and so may
+ * either output.  No atomics: two runs give equal bits.
+ *
+ * Both entries refuse, before any launch, with return 2 and csplat_last_error() naming the entry: negative sizes, H outside 1 .. 16, NULL
+ * or misaligned operands, omean without ostd, an output that shares a byte with an input or with another output, N * 3H or 4E beyond 2^31.
+ * N = 0 or nothing wanted is a no-op that returns 0.
+ * Added exports: CSPLAT_ABI_VERSION is unchanged. */
+int csplat_train_update_fwd(void *stream, int N, int64_t E, int H, const float *velocity, const float *velocity_noise /* or NULL */,
+                            const float *pred_acc, const float *omean /* or NULL */, const float *ostd /* or NULL */, const float *init_position,
+                            const float *old_actions, const float *actions, const int64_t *edge_index, float *hist /* or NULL */,
+                            float *edge_feat /* or NULL */, float *new_pos /* or NULL */);
+int csplat_train_update_bwd(void *stream, int N, int64_t E, const float *edge_feat, const float *g_edge_feat /* or NULL */,
+                            const float *g_new_pos /* or NULL */, const float *old_actions, const float *actions, const float *ostd /* or NULL */,
+                            const int32_t *src_rowptr, const int32_t *src_perm, const int32_t *dst_rowptr, const int32_t *dst_perm,
+                            float *g_pred_acc /* or NULL */, float *g_init_position /* or NULL */);
+
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
  *   csplat_mesh_rest       per-Gaussian constants of the REST face (in-plane basis, normal, in-plane coordinates) into
