@@ -19,7 +19,8 @@ torch operations in the input's dtype (reported through csplat.native.composed_f
 CPU path).  A numpy array goes to the GPU as float32 when there is one, else the composed CPU path runs in its own dtype; the result comes
 back as numpy in the input's dtype, like farthest_point_sampling.  Everything here is an observation: detached, no gradients.
 
-The Delaunay branch, the PyG `Data` builders and the file loaders of that module are host-side plumbing and stay out of scope."""
+The samples a training step reads are assembled from these dictionaries by meshnet.dataloader_sim (SamplesClothSimDataset), which stands
+in for the PyG `Data` builders.  The Delaunay branch and the file loaders of that module are host-side plumbing and stay out of scope."""
 import math
 
 import numpy as np

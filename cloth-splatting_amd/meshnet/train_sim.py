@@ -17,7 +17,8 @@ Dispatch as in meshnet.data_utils: float32 contiguous GPU tensors take the kerne
 operations in the dtype of `velocity` (reported through csplat.native.composed_fallback for GPU tensors: raises under STRICT; it is the
 CPU path).  `edge_index` is validated once per tensor object (dtype, shape [2,E], range: one blocking read), never per step.
 
-Data sets and loaders, validation, logging, checkpoints and the Delaunay branch are host-side plumbing and stay out of scope."""
+The sample data set, its batches and the validation rollout's errors are meshnet.dataloader_sim (SamplesClothSimDataset; train_step takes
+its Batch as it is).  Loading trajectory files, logging, checkpoints and the Delaunay branch are host-side plumbing and stay out of scope."""
 import types
 import weakref
 
@@ -26,6 +27,7 @@ import torch
 from csplat import native as _n
 from .model_utils import Normalizer, get_velocity_noise
 
+BATCH_FIELDS = ("velocity", "node_types", "edge_index", "edge_features", "target_velocities", "particle_actions", "positions")
 _EDGES = {}       # id(edge_index) -> (weak reference, in-place version, N, device, the checked copy or None when the tensor itself fits)
 
 
@@ -205,7 +207,9 @@ def train_step(simulator, optimizer, batch, future_sequence_length=1, noise_std=
     """One optimizer step on `batch` = (velocity, node_types, edge_index, edge_features, target_velocities, particle_actions, positions),
     the 7-tuple of the reference's `_graph_to_data` (a collate() of several is one too).  The noise is get_velocity_noise's: normal(0,
     noise_std) of the velocity's shape, drawn where the reference draws it.  Order as the reference's: zero_grad, backward, step.
-    -> (loss, per-step losses), detached."""
+    -> (loss, per-step losses), detached.  A meshnet.dataloader_sim.Batch is taken as it is: its first seven fields are this tuple."""
+    if getattr(batch, "_fields", ())[:7] == BATCH_FIELDS:
+        batch = batch[:7]
     try:
         velocity, node_types, edge_index, edge_features, target_velocities, particle_actions, positions = batch
     except (TypeError, ValueError):

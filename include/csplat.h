@@ -917,6 +917,61 @@ int csplat_train_update_bwd(void *stream, int N, int64_t E, const float *edge_fe
                             const int32_t *src_rowptr, const int32_t *src_perm, const int32_t *dst_rowptr, const int32_t *dst_perm,
                             float *g_pred_acc /* or NULL */, float *g_init_position /* or NULL */);
 
+/* MeshNet sample data set (csplat_dataset.hip): the samples of the reference's SamplesClothSimDataset (meshnet/dataloader_sim.py: __getitem__
+ * :148-182, _data_to_graph :352-412, followed by FaceToEdge / Cartesian / Distance and PyG's collate) assembled on the device, a whole
+ * block-diagonal batch in ONE launch, and the arithmetic of its validate (train_meshnet_sim.py:303-308) in one launch.
+ *
+ * The store: all trajectories packed back to back in device buffers.  Trajectory j has T_j frames of N_j nodes and E_j edges:
+ *   pos, velocity [sum T_j N_j][3], node_type [sum T_j N_j]  frame-major inside a trajectory: node i of frame t is row NODE_BASE + t N_j + i
+ *   actions [sum T_j][3]                                     frame t is row FRAME_BASE + t
+ *   edges (int64)                                            trajectory j's [2][E_j] block begins at word 2 * EDGE_BASE: stored once, not
+ *                                                            per frame; entries in 0 .. N_j - 1
+ *   table (int64) [n_traj][CSPLAT_DATASET_TABLE_WORDS]       NODE_BASE (node rows in front), FRAME_BASE (frames in front), EDGE_BASE (edges
+ *                                                            in front), N, E, T, GRASPED (the grasped node g_j; outside 0 .. N-1: none)
+ * store_rows, store_frames, store_edges are the three sums (what the buffers hold).
+ *
+ * desc (int32) [B][4] = (trajectory j, time index t, first output node row r, first output edge row e0) of every sample, 16-byte aligned;
+ * action_override [B][F][3] or NULL.  n_rows / n_edges are the batch's totals (sum N_j / sum E_j over the samples), max_items the largest
+ * N_j (3H + 4 + 9F) + E_j of a sample (it sizes the grid; a larger sample is still written whole).  H = input sequence length, F = future
+ * sequence length, a[f] = action_override[b][f] when given, else actions_j[t - 1 + f].  Sample b writes, bit for bit (i a node, g = g_j):
+ *   out_velocity[r + i][3h : 3h + 3]   = vel_j[t - H + h][i], h = 0 .. H-1 (oldest first); the grasped row's last three columns are
+ *                                        vel_j[t][g] (_data_to_graph:363-365: the grasped node already carries its target velocity)
+ *   out_node_types[r + i]              = node_type_j[t - 1][i]
+ *   out_positions[r + i]               = pos_j[t - 1][i]; the grasped row is pos_j[t - 1][g] + a[0], one float32 add per component
+ *   out_target_velocities[r + i][f]    = vel_j[t + f][i],  out_pos_target[r + i][f] = pos_j[t + f][i],  f = 0 .. F-1
+ *   out_particle_actions[r + i][f]     = 0; the grasped row is a[f]
+ *   out_edge_index[0 / 1][e0 + e]      = edges_j[0 / 1][e] + r          (out_edge_index is [2][n_edges])
+ *   out_edge_features[e0 + e]          = (d, |d|), d = p[row] - p[col] on the OUTPUT positions p (the moved grasped node included), bit-equal
+ *                                        to csplat_gnn_edge_features on out_positions (|d| = sqrtf(fma(dz, dz, fma(dx, dx, dy * dy))), the
+ *                                        form that kernel's object code has); [n_edges][4], 16-byte aligned
+ * Float arithmetic without contraction.  Plain loads and stores, every output element written by exactly one thread, no atomics: two runs
+ * give equal bits.  An edges entry outside 0 .. N_j - 1 gives that edge a NaN feature row and reads nothing out of range.  A window that
+ * leaves its trajectory (t < H or t + F > T_j) is the caller's error -- the Python surface refuses it; here every float of that sample is
+ * NaN and nothing is read.  A sample whose rows would leave the outputs (r + N_j > n_rows, e0 + E_j > n_edges), whose j is not a
+ * trajectory or whose trajectory leaves the store is skipped: nothing outside the operands is ever touched.
+ *
+ * csplat_dataset_rollout_error: pos0 [N][3], pred [S][N][3] (the predicted displacement of every step), gt [S][N][3] (the true positions of
+ * steps 1 .. S) -> err [S]:
+ *   at_s[i] = ((pos0[i] + pred[0][i]) + pred[1][i]) + ... + pred[s][i]   added in this order, each sum rounded
+ *   err[s]  = (sum_i (at_s[i] - gt[s][i])^2) / (float)(3 N)              i over the 3 N components
+ * The sum has a fixed order: thread q of 256 adds its components q, q + 256, ... in ascending order beginning from 0, then the 256 partial
+ * sums are joined by a halving tree (slot q += slot q + 128, then + 64, ... + 1).  One workgroup per step, no atomics: two runs give
+ * equal bits.  S = 0 is a no-op; N = 0 with S > 0 is refused.  S * N * 3 < 2^31.
+ *
+ * Both entries refuse, before any launch, with return 2 and csplat_last_error() naming the entry: negative sizes, H outside 1 .. 16,
+ * F < 1, NULL or misaligned operands, an output that shares a byte with another operand, row counts beyond 2^31 (n_rows * 3H, n_rows * 3F,
+ * 4 * n_edges, the store's sums).  B = 0 or an empty batch is a no-op that returns 0.
+ * Added exports: CSPLAT_ABI_VERSION is unchanged. */
+#define CSPLAT_DATASET_TABLE_WORDS 8
+enum { CSPLAT_DATASET_NODE_BASE = 0, CSPLAT_DATASET_FRAME_BASE, CSPLAT_DATASET_EDGE_BASE, CSPLAT_DATASET_N, CSPLAT_DATASET_E, CSPLAT_DATASET_T,
+       CSPLAT_DATASET_GRASPED };
+int csplat_dataset_batch(void *stream, int B, int H, int F, int n_traj, int64_t store_rows, int64_t store_frames, int64_t store_edges,
+                         const float *pos, const float *velocity, const float *node_type, const float *actions, const int64_t *edges,
+                         const int64_t *table, const int32_t *desc, const float *action_override /* or NULL */, int64_t n_rows, int64_t n_edges,
+                         int64_t max_items, float *out_velocity, float *out_node_types, float *out_positions, float *out_target_velocities,
+                         float *out_pos_target, float *out_particle_actions, int64_t *out_edge_index, float *out_edge_features);
+int csplat_dataset_rollout_error(void *stream, int S, int N, const float *pos0, const float *pred, const float *gt, float *err);
+
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
  *   csplat_mesh_rest       per-Gaussian constants of the REST face (in-plane basis, normal, in-plane coordinates) into
