@@ -128,6 +128,7 @@ EXPORTS = {
     "csplat_train_update_bwd": (_i, [_vp, _i, _i64] + [_vp] * 12),
     "csplat_dataset_batch": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _i64] + [_vp] * 8 + [_i64, _i64, _i64] + [_vp] * 8),
     "csplat_dataset_rollout_error": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "csplat_camera_batch": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
     "csplat_psnr_scratch_bytes": (_sz, [_i64]),
     "csplat_psnr": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "csplat_sim_hidden_fwd": (_i, [_vp, _i, _i] + [_vp] * 7),

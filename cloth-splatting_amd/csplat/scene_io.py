@@ -3,6 +3,8 @@ reference's Scene builds its Cameras from.  Restates /root/reference/scene_recon
   read_timeline                 :386-401
   read_cameras_from_transforms  :268-385   (readCamerasFromTransforms)
   camera_from_info              scene_reconstruction/cameras.py:57-68 through csplat.synthetic.camera_matrices
+  nerf_normalization            :58-79     (getNerfppNorm)
+  read_cloth_scene_info         scene_reconstruction/scene.py:39-87, the meshes (meshnet/data_utils.py:450-457) through csplat.hdf5min
 Quirks reproduced, not fixed (the golden fixture tests/golden/scene_io.npz holds what the reference returns):
   * CameraInfo.width / .height are image.shape[1] / image.shape[2] of the [3,H,W] tensor, i.e. H and W swapped (:382);
   * the alpha-composited image is quantised by TRUNCATION (`np.array(arr * 255.0, dtype=np.byte)`, :371), not rounding;
@@ -116,6 +118,43 @@ def read_blender_scene(path, white_background, extension=".png", time_skip=None,
     if os.path.exists(os.path.join(path, "video.json")):
         video = read_cameras_from_transforms(path, "video.json", white_background, extension, mapper, 1, 1)
     return train, test, video, mapper, max_time
+
+
+def nerf_normalization(cam_infos):
+    """getNerfppNorm (:58-79): {"translate": minus the mean camera centre, "radius": 1.1 x the largest distance of a camera centre
+    from that mean} -- the radius is the `cameras_extent` of densification"""
+    from .synthetic import world_to_view
+    centers = np.hstack([np.linalg.inv(world_to_view(np.asarray(c.R), np.asarray(c.T)))[:3, 3:4] for c in cam_infos])
+    center = np.mean(centers, axis=1, keepdims=True)
+    diagonal = np.max(np.linalg.norm(centers - center, axis=0, keepdims=True))
+    return {"translate": -center.flatten(), "radius": diagonal * 1.1}
+
+
+def load_mesh(path, device="cpu"):
+    """meshnet/data_utils.py:450-457 (load_mesh_from_h5py) through csplat.hdf5min: pos, norm, face, edge_index as tensors"""
+    from . import hdf5min
+    d = hdf5min.load(path)
+    return SimpleNamespace(**{k: torch.as_tensor(np.ascontiguousarray(d[k]), device=device) for k in ("pos", "norm", "face", "edge_index")})
+
+
+def read_cloth_scene_info(path, white_background, eval=True, extension=".png", time_skip=None, view_skip=None, device="cpu"):
+    """scene_reconstruction/scene.py:39-87 -> (scene_info, initial_mesh, mesh_predictions): the Blender cameras (train, test and
+    `video.json` when there is one; with eval=False the test cameras are merged into the training set), nerf_normalization of the
+    training cameras, `init_mesh.hdf5` and the sorted `mesh_predictions/mesh_*.hdf5` (every time_skip-th).  Without a `video.json` the
+    reference generates a spiral of video cameras; here `video_cameras` is None."""
+    import glob
+    if not os.path.exists(path):
+        raise FileNotFoundError("Path does not exist: {}".format(path))
+    train, test, video, _mapper, max_time = read_blender_scene(path, white_background, extension, time_skip, view_skip)
+    if not eval:
+        train, test = train + test, []
+    initial_mesh = load_mesh(os.path.join(path, "init_mesh.hdf5"), device)
+    paths = sorted(glob.glob(os.path.join(path, "mesh_predictions", "mesh_*.hdf5")))
+    paths = paths[::time_skip] if time_skip is not None else paths
+    mesh_predictions = [load_mesh(p, device) for p in paths]
+    scene_info = SimpleNamespace(train_cameras=train, test_cameras=test, video_cameras=video, nerf_normalization=nerf_normalization(train),
+                                 maxtime=max_time, initial_mesh=initial_mesh, mesh_predictions=mesh_predictions)
+    return scene_info, initial_mesh, mesh_predictions
 
 
 def camera_from_info(info, device="cuda"):

@@ -37,13 +37,32 @@ _GT_STACKS = {}          # insertion-ordered: least recently used first
 _GT_STACKS_MAX = 8
 
 
+def _batch_stack(cams, name, field, device):
+    """the tensor `name` ("gt_stack" / "mask_stack") that ALL cameras carry and whose rows their `field` ("original_image" / "mask") still
+    are, in order (camera i: gt_index == i; the batches of csplat.camera_dataset), when it lies on `device`; None for any other camera list"""
+    stack = getattr(cams[0], name, None) if cams else None
+    if not torch.is_tensor(stack) or stack.shape[0] != len(cams) or stack.device != device or not stack.is_contiguous():
+        return None
+    row = stack.stride(0) * stack.element_size()
+    for i, cam in enumerate(cams):
+        t = getattr(cam, field, None)
+        if getattr(cam, name, None) is not stack or getattr(cam, "gt_index", None) != i or not torch.is_tensor(t) or \
+                t.data_ptr() != stack.data_ptr() + i * row or t.shape != stack.shape[1:] or not t.is_contiguous():
+            return None
+    return stack
+
+
 def _gt_stack(cams, device):
     """torch.cat of the cameras' ground-truth images (train_utils.py:262-270 builds it every step).  A caller that cycles through a few
     camera OBJECTS whose images never change (bench_train, the parity runs) gets the stack of a camera set built once: a small LRU
     (8 sets) keyed on the image tensors' identities and in-place versions.  The entry holds WEAK references to the source images -- an id
     recycled by a new tensor cannot alias (the dead reference no longer matches) and nothing of the caller's is pinned.  The
     reference's dataset builds a fresh Camera per item (scene_reconstruction/dataset.py:89-): such a caller never hits, and then the
-    cache costs eight stale stacks at most (it used to hold up to 512 entries with strong references to the sources)."""
+    cache costs eight stale stacks at most (it used to hold up to 512 entries with strong references to the sources).
+    The cameras of a csplat.camera_dataset step ARE slices of one stack: it is handed through (_batch_stack)."""
+    stack = _batch_stack(cams, "gt_stack", "original_image", device)
+    if stack is not None:
+        return stack
     import weakref
     imgs = [cam.original_image for cam in cams]
     key = tuple((id(t), t._version) for t in imgs) + (str(device),)
@@ -402,7 +421,10 @@ def _image_term(cams, n_total, world, dist_mode, stacked, pkgs, masks, reg, opt,
     if cams:
         image_tensor = stacked if stacked is not None else torch.cat([pkg.render.unsqueeze(0) for pkg in pkgs], 0)
         gt_image_tensor = _gt_stack(cams, image_tensor.device) if _cap is None else _cap["gt"]
-        mask_tensor = torch.cat(masks, 0) if masks is not None else None
+        mask_tensor = None
+        if masks is not None:         # (the masks of a csplat.camera_dataset step are the rows of one tensor already)
+            mask_tensor = _batch_stack(cams, "mask_stack", "mask", image_tensor.device)
+            mask_tensor = torch.cat(masks, 0) if mask_tensor is None else mask_tensor
         w_img = 1.0 if len(cams) == n_total else len(cams) / n_total
         if _image_loss_fusable(image_tensor, gt_image_tensor, opt, mask_tensor) and reg.dtype == torch.float32:
             # image loss + PSNR + the sum with the regularisers: one launch (and one in backward)

@@ -972,6 +972,35 @@ int csplat_dataset_batch(void *stream, int B, int H, int F, int n_traj, int64_t 
                          float *out_pos_target, float *out_particle_actions, int64_t *out_edge_index, float *out_edge_features);
 int csplat_dataset_rollout_error(void *stream, int S, int N, const float *pos0, const float *pred, const float *gt, float *err);
 
+/* Camera data set (csplat_camera_dataset.hip): the ground-truth images and masks of a training step's cameras -- the reference's MDNerfDataset
+ * (scene_reconstruction/dataset.py:46-123), whose items carry float images from the host -- gathered out of a device-resident store in ONE
+ * launch.
+ *
+ * The store: one 16-byte aligned device buffer of n_slots slots.  A slot holds 3 image planes, then 1 mask plane when has_mask = 1; plane p
+ * of slot s begins at byte (s * (3 + has_mask) + p) * pitch.  pitch is a multiple of 16 bytes and at least H * W elements long, so every
+ * plane begins 16-byte aligned; the bytes behind the H * W elements of a plane are never read.  storage:
+ *   CSPLAT_CAMERA_UINT8    an element is one byte, the 8-bit level u of an image or m of a mask (the loader's own quantisation,
+ *                          csplat/scene_io.py: image = uint8 / 255.0, mask = 1.0 - uint8 / 255.0)
+ *   CSPLAT_CAMERA_FLOAT32  an element is one float32 word
+ * slots (int32, device) [n] names the slot of every camera of the step.  Camera i writes, bit for bit:
+ *   gt[i][c][y][x]   = (float)u / 255.0f, one correctly rounded division (torch's uint8_tensor / 255.0; a multiply by the reciprocal
+ *                      differs at 126 of the 256 levels)                                         | the stored word (float32 storage)
+ *   mask[i][0][y][x] = 1.0f - (float)m / 255.0f, two roundings (torch's 1.0 - uint8_tensor / 255.0) | the stored word
+ * gt is [n][3][H][W], mask [n][1][H][W] (NULL exactly when has_mask = 0).  float32 storage copies words: NaN payloads, -0.0 and denormals
+ * arrive as stored.  Float arithmetic without contraction.  Plain loads and stores, every output element written by exactly one thread,
+ * no atomics: two runs give equal bits.  A slots entry outside 0 .. n_slots - 1 is the caller's error -- the Python surface refuses it;
+ * here every float of that camera is NaN and nothing is read.
+ *
+ * Refused before any launch, with return 2 and csplat_last_error() naming the entry: negative sizes, another storage or has_mask value, a
+ * pitch that is not a multiple of 16 or shorter than a plane, H * W or n_slots beyond 2^31, NULL slots / gt / store (with n_slots > 0), a
+ * mask output that does not go with has_mask, a store that is not 16-byte aligned or slots / gt / mask that are not 4-byte aligned, an
+ * output that shares a byte with another operand.  n = 0 or H * W = 0 is a no-op that returns 0.
+ * Added exports: CSPLAT_ABI_VERSION is unchanged. */
+#define CSPLAT_CAMERA_UINT8 0
+#define CSPLAT_CAMERA_FLOAT32 1
+int csplat_camera_batch(void *stream, int n, int H, int W, int storage, int has_mask, int64_t n_slots, int64_t pitch, const void *store,
+                        const int32_t *slots, float *gt, float *mask /* or NULL */);
+
 /* Fused mesh -> Gaussian transform (SURVEY.md 8(f) "next" row N1): MultiGaussianMesh.get_xyz + get_rotation,
  * scene_reconstruction/gaussian_mesh.py:151-188.  face_vertex_ids[P][3] (int64, device) = mesh.face[:, face_ids].T.
  *   csplat_mesh_rest       per-Gaussian constants of the REST face (in-plane basis, normal, in-plane coordinates) into
