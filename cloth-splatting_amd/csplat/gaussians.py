@@ -59,7 +59,7 @@ class MeshTransform(torch.autograd.Function):
 
 def _join_views(grads, rest, dtype, dev):
     """the [T, *rest] gradient of T unbound rows: a VIEW when the T incoming gradients sit back to back in one buffer (the batched
-    rasterizer's backward lays the per-view gradients of means3D / rotations out that way, diff_gaussian_rasterization._plan_backward),
+    rasterizer's backward lays the per-view gradients of means3D / rotations out that way, diff_gaussian_rasterization._GradLayout),
     their stack otherwise (None rows = zeros); None when every row is None"""
     if all(g is None for g in grads):
         return None

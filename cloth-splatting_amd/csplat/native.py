@@ -415,18 +415,24 @@ class CsplatVisibility(C.Structure):
 ACC_OPACITY, ACC_COLOR, ACC_MEAN3D, ACC_COV3D, ACC_SH, ACC_SCALE, ACC_ROT = 1, 2, 4, 8, 16, 32, 64
 
 
-class ChunkAllocator:
-    """Answers csplat_alloc_fn with torch-owned byte buffers and keeps them alive."""
+GEOM, BINNING, IMAGE = 0, 1, 2      # csplat.h: the chunks a forward leaves for its backward (the others are temporaries)
 
-    def __init__(self, device):
+
+class ChunkAllocator:
+    """Answers csplat_alloc_fn with torch-owned byte buffers and keeps them alive: `views[alloc_ctx]` = {chunk: buffer} of the view whose
+    csplat_view.alloc_ctx the library hands back (`chunks` = views[0], the one view of a call that passes no alloc_ctx).  `cb` and the
+    allocator refer to each other: set `cb = None` after the call, so that the temporaries die there and not at the next cyclic GC."""
+
+    def __init__(self, device, nviews=1):
         self.device = device
-        self.chunks = {}
+        self.views = [{} for _ in range(nviews)]
+        self.chunks = self.views[0]
         self.cb = ALLOC_FN(self._alloc)
 
-    def _alloc(self, _ctx, chunk, nbytes):
+    def _alloc(self, ctx, chunk, nbytes):
         try:
             buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
-            self.chunks[int(chunk)] = buf
+            self.views[int(ctx or 0)][int(chunk)] = buf
             return buf.data_ptr()
         except Exception:  # never let an exception cross the C boundary
             return None

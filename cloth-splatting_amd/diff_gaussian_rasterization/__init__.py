@@ -26,7 +26,10 @@ weight T alpha and the number of pixels it blended into, per pixel the id of the
 csplat_visibility_views) -- forward only, bit-reproducible.  Without it the call is unchanged.
 Which tensor argument, output and returned gradient of the batched Function belongs to which view is the business of one object,
 `_CallLayout`, built once per call by `rasterize_gaussians` / `rasterize_views`; what a per-Gaussian input is called, where it is saved
-and which gradient field and shape it has is one table, `_INPUTS` (tests/test_raster_call_layout_cpu.py needs no GPU).
+and which gradient field and shape it has is one table, `_INPUTS`; the layout also knows the order of the saved tensors
+(tests/test_raster_call_layout_cpu.py needs no GPU).  Where a backward's gradients land -- shared buffers, accumulate bits, every offset in
+the step's one allocation -- is decided by a second pure object, `_GradLayout` (tests/test_raster_grad_layout_cpu.py, no GPU), from
+which `_plan_backward` fills the csplat_view array.  What one view's forward leaves and its backward needs is one record, `_View`.
 """
 import contextlib as _contextlib
 import ctypes as C
@@ -152,27 +155,24 @@ def _check_visibility_flag(flag):
     return flag
 
 
-def _visibility_mode_check():
-    """visibility is computed by eager steps only"""
-    if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-        raise RuntimeError("diff_gaussian_rasterization: visibility is not computed by a forward launched on faith or a captured / "
-                           "replayed step -- compute it in an eager step")
+_EAGER_ONLY = "diff_gaussian_rasterization: %s by a forward launched on faith or a captured / replayed step -- %s in an eager step"
+_EAGER_ONLY_VIS = _EAGER_ONLY % ("visibility is not computed", "compute it")
+_EAGER_ONLY_FEAT = _EAGER_ONLY % ("feature / alpha images are not rendered", "render them")
 
 
-def _feature_mode_check():
-    """feature / alpha images are rendered by eager steps only"""
+def _eager_mode_check(message):
+    """visibility, feature and alpha images are computed by eager steps only: RuntimeError(message) anywhere else"""
     if _FAITH is not None or _n.REPLAY_STREAM or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-        raise RuntimeError("diff_gaussian_rasterization: feature / alpha images are not rendered by a forward launched on faith or a "
-                           "captured / replayed step -- render them in an eager step")
+        raise RuntimeError(message)
 
 
 class _Input(NamedTuple):
     """one per-Gaussian input of a view"""
     name: str           # the _View attribute (rasterize_gaussians' parameter)
     slot: int           # position among a view's NIN tensor arguments
-    saved: object       # position in _View.saved(); None: not saved for the backward
+    saved: object       # position among the saved tensors; None: not saved for the backward
     field: str          # the csplat_view gradient field
-    acc: object         # the accumulate bit of a gradient buffer shared between views; None: K7's own output, one buffer per view
+    acc: object         # the accumulate bit of a gradient buffer shared between views; None: formed from one view's K7 records, one buffer per view
     shape: object       # (P, M) -> shape of the gradient
     optional: bool      # may be None: present when its saved tensor is; else always present
     temp: bool = False  # K8 writes the buffer even when the input is absent (it is never handed back then)
@@ -180,7 +180,7 @@ class _Input(NamedTuple):
 
 _INPUTS = (
     _Input("means3D", 0, 0, "dL_dmean3D", _n.ACC_MEAN3D, lambda P, M: (P, 3), False),
-    _Input("means2D", 1, None, "dL_dmean2D", None, lambda P, M: (P, 3), False),      # (K7's own output, one per view)
+    _Input("means2D", 1, None, "dL_dmean2D", None, lambda P, M: (P, 3), False),      # (from this view's K7 moments: one per view)
     _Input("sh", 2, 1, "dL_dsh", _n.ACC_SH, lambda P, M: (P, M, 3), True),
     _Input("colors_precomp", 3, 2, "dL_dcolor", _n.ACC_COLOR, lambda P, M: (P, 3), True, True),
     _Input("opacities", 4, None, "dL_dopacity", _n.ACC_OPACITY, lambda P, M: (P, 1), False),
@@ -191,16 +191,81 @@ _INPUTS = (
 NIN = len(_INPUTS)
 _IN = {r.name: r for r in _INPUTS}
 _SAVED = sorted((r for r in _INPUTS if r.saved is not None), key=lambda r: r.saved)
-_SAVED_OF = _attrgetter(*(r.name for r in _SAVED), "radii", "color")      # what _View.saved() saves, in that order
+_SAVED_NAMES = tuple(r.name for r in _SAVED) + ("radii", "color")          # what _View.take_saved() returns, in that order
+_SAVED_OF = _attrgetter(*_SAVED_NAMES)
 _GRAD_FIELDS = ("dL_dconic",) + tuple(r.field for r in _INPUTS)     # every gradient pointer of a csplat_view the plan sets
-_K7_OUT = tuple(r for r in _INPUTS if r.acc is None)        # gradients K7 writes itself
+_K7_OUT = tuple(r for r in _INPUTS if r.acc is None)        # gradients of one view's K7 records, never shared
 _K8_OUT = tuple(r for r in _INPUTS if r.acc is not None)    # gradients K8 writes, into a buffer of their view or a shared one
+_BACK_TO_BACK = (_IN["means3D"], _IN["rotations"])          # per-view gradients csplat.gaussians.UnbindViews stacks as a view
+SCRATCH_ZEROED, K8_OUTPUTS_UNREAD = 256, 512      # csplat.h: CSPLAT_SCRATCH_ZEROED, CSPLAT_K8_OUTPUTS_UNREAD
 
 
 def _sh_staged(M, sh):
     """does the library stage this SH tensor's rows through LDS (include/csplat.h, at `M`)?  Only then may views share one dL_dsh
     (CSPLAT_ACC_SH) -- a [P, 16, 3] tensor that is a view into a flat buffer may start off a 16-byte boundary"""
     return M == 16 and sh.data_ptr() % 16 == 0
+
+
+class _GradLayout:
+    """Where every gradient of one batched backward lands, in one pass over the `active` views.  It holds no tensor and calls nothing but
+    `sunk` (tests/test_raster_grad_layout_cpu.py needs no GPU); _RasterizeGaussiansBatch._plan_backward fills the csplat_view array from it.
+    specs[i] = (P, M, present[slot], first_of[slot]: the first view that got the same tensor object, staged: _sh_staged, scratch: floats of
+    per-call scratch or None for the persistent zeroed records).  sunk(view, slot, numel) -> does this owner's gradient go to a gradient
+    sink?  Asked in the order the sinks must be claimed (grad_out claims on asking); None: no sinks.
+    Per position a in `active`: owner[a][slot] = the view whose buffer the field points at -- itself, or an earlier active view that got the
+    same tensor object: mask[a] then carries the row's CSPLAT_ACC_* bit (a dL_dsh only when staged: the unstaged K8 cannot add) -- or None:
+    the input is absent, the field NULL.  The `temp` rows own a buffer even when absent (K8 writes it) unless CSPLAT_K8_OUTPUTS_UNREAD says
+    that neither is present.  scratch[a] and fields[a] (in the order of _GRAD_FIELDS) are float offsets into the step's ONE allocation of
+    `total` floats, None, or the (view, slot) of a sink; ret[a] = the returned (slot, offset or sink, shape).  Buffers lie in 256-byte granules,
+    but the _BACK_TO_BACK gradients of DISTINCT, equally sized inputs (the rows of one [T, P, .] tensor upstream) back to back: their stack is a view."""
+    __slots__ = ("active", "owner", "mask", "scratch", "fields", "ret", "total")
+
+    def __init__(self, specs, active, sunk=None):
+        total, block, at = 0, {}, {}
+
+        def reserve(numel):
+            nonlocal total
+            off = total
+            total += (int(numel) + 63) & ~63          # 256-byte granules
+            return off
+        equal = len(active) > 1 and len({specs[i][0] for i in active}) == 1
+        for row in _BACK_TO_BACK:
+            if equal and all(specs[i][3][row.slot] == i and specs[i][2][row.slot] for i in active):
+                size = _prod(row.shape(specs[active[0]][0], 0))
+                block[row.slot] = (reserve(len(active) * size), size)
+        self.active, self.owner, self.mask, self.scratch, self.fields, self.ret = active, [], [], [], [], []
+        for a, i in enumerate(active):
+            P, M, present, first_of, staged, scratch = specs[i]
+            mask = (SCRATCH_ZEROED if scratch is None else 0) | K8_OUTPUTS_UNREAD
+            self.scratch.append(None if scratch is None else reserve(scratch))
+            own, loc, ret = [None] * NIN, [None] * (1 + NIN), []
+            for row in _K7_OUT:
+                shape = row.shape(P, M)
+                own[row.slot], loc[1 + row.slot] = i, reserve(_prod(shape))
+                ret.append((row.slot, loc[1 + row.slot], shape))
+            loc[0] = reserve(4 * P)                     # dL_dconic, never handed back
+            for row in _K8_OUT:
+                slot, there = row.slot, present[row.slot]
+                if not there and not row.temp:
+                    continue
+                if there and row.temp:
+                    mask &= ~K8_OUTPUTS_UNREAD
+                j = first_of[slot]
+                if there and j != i and j in at and (staged or row.name != "sh"):
+                    own[slot], loc[1 + slot] = j, self.fields[at[j]][1 + slot]
+                    mask |= row.acc
+                    continue
+                own[slot], shape = i, row.shape(P, M)
+                if slot in block:
+                    loc[1 + slot] = block[slot][0] + a * block[slot][1]
+                else:
+                    sink = there and sunk is not None and sunk(i, slot, _prod(shape))
+                    loc[1 + slot] = (i, slot) if sink else reserve(_prod(shape))
+                if there:
+                    ret.append((slot, loc[1 + slot], shape))
+            at[i] = a
+            self.owner.append(own); self.mask.append(mask); self.fields.append(loc); self.ret.append(ret)
+        self.total = total
 
 
 class _CallLayout:
@@ -226,6 +291,8 @@ class _CallLayout:
         self._feat0 = self._cam0 + (4 * V if self.cam else 0)
         self.n_tensors = self._feat0 + (V if self.has_feat else 0)
         self.stacked_output = 0 if self.stacked else None
+        self._nsaved = len(_SAVED_NAMES) - (1 if self.stacked else 0)      # per view
+        self.n_saved = V * self._nsaved + (1 if self.stacked else 0) + (V if self.has_feat else 0)
         self.outputs, at = [], 1 if self.stacked else 0       # per view {output name: index}, in output order
         for (F, alpha), v in zip(self.feat, self.vis):
             names = [n for n, w in zip(self.OUTPUTS, (not self.stacked, True, True, F > 0, alpha) + (v,) * NVIS) if w]
@@ -279,6 +346,24 @@ class _CallLayout:
             views.append(tuple(t))
         return (colors, views) if self.stacked else views
 
+    # ---- what is saved for the backward
+    def pack_saved(self, per_view, colors=None, feats=()):
+        """per view what _View.take_saved() returns, the stacked colours, per view the feature tensor (or None) -> the saved list: per view
+        the _SAVED_NAMES (its colour only unless `stacked`); the stacked colours when `stacked`; the feature tensors when `has_feat`"""
+        saved = [t for s in per_view for t in s[:self._nsaved]]
+        if self.stacked:
+            saved.append(colors)
+        return saved + list(feats) if self.has_feat else saved
+
+    def saved_input(self, saved, i, name):
+        """view i's `name` of _SAVED_NAMES (its colour in a `stacked` call: the stacked colours, view i = row i)"""
+        at = _SAVED_NAMES.index(name)
+        return saved[i * self._nsaved + at if at < self._nsaved else self.V * self._nsaved]
+
+    def saved_features(self, saved):
+        """per view its feature tensor (None where it has none); () without `has_feat`"""
+        return saved[self.n_saved - self.V:self.n_saved] if self.has_feat else ()
+
     # ---- what backward returns
     def grads(self, per_gaussian=None, cam=None, feat=None):
         """backward's return value: per_gaussian[i] = view i's NIN gradients, cam[i] = the 4 of its camera group, feat[i] = its feature
@@ -301,10 +386,19 @@ def _call_layout(settings, stacked, antialias, feat, vis):
         if len({f for f, _a in layout.feat}) > 1:
             raise ValueError("rasterize_views: every view must have the same number of feature channels, got "
                              f"{[f for f, _a in layout.feat]}")
-        _feature_mode_check()
+        _eager_mode_check(_EAGER_ONLY_FEAT)
     if layout.has_vis:
-        _visibility_mode_check()
+        _eager_mode_check(_EAGER_ONLY_VIS)
     return layout
+
+
+def _check_one_of_each(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """upstream's checks of a view's arguments, with upstream's messages"""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -337,27 +431,52 @@ class _View:
     keeps a view's arguments in; `begin` / `finish` are the flat two-phase entries (csplat_forward_begin / _finish), which pack the same
     record themselves."""
 
-    def __init__(self, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs):
+    def __init__(self, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, features=None):
         _n.require_cuda(means3D)
         dev = self.dev = means3D.device
-        self.rs = rs
-        self.P = int(means3D.shape[0])
+        self.rs, self.P = rs, int(means3D.shape[0])
         self.H, self.W = int(rs.image_height), int(rs.image_width)
         self.means3D = _f32c(means3D, dev, "means3D"); self.opacities = _f32c(opacities, dev, "opacities")
-        self.sh = _f32c(sh, dev, "shs")
-        self.colors_precomp = _f32c(colors_precomp, dev, "colors_precomp")
-        self.scales = _f32c(scales, dev, "scales")
-        self.rotations = _f32c(rotations, dev, "rotations")
+        self.sh = _f32c(sh, dev, "shs"); self.colors_precomp = _f32c(colors_precomp, dev, "colors_precomp")
+        self.scales = _f32c(scales, dev, "scales"); self.rotations = _f32c(rotations, dev, "rotations")
         self.cov3Ds_precomp = _f32c(cov3Ds_precomp, dev, "cov3D_precomp")
         self.bg = _f32c(rs.bg, dev, "bg", False); self.view = _f32c(rs.viewmatrix, dev, "viewmatrix", False)
-        self.proj = _f32c(rs.projmatrix, dev, "projmatrix", False)
-        self.campos = _f32c(rs.campos, dev, "campos", False)
+        self.proj = _f32c(rs.projmatrix, dev, "projmatrix", False); self.campos = _f32c(rs.campos, dev, "campos", False)
         self.M = int(self.sh.shape[1]) if self.sh is not None else 0
-        self.ticket = self.chunks = None
+        self.present = [not r.optional or getattr(self, r.name) is not None for r in _INPUTS]      # per slot: the input is there
+        self.staged = self.sh is not None and _sh_staged(self.M, self.sh)
+        self.features = features                                # [P, F], contiguous: the feature channels the batched forward renders
+        self.color = self.radii = self.depth = self.feat = self.alpha = self.vis = None      # the outputs: outputs()
+        self.ticket = self.chunks = self.num_rendered = self.layout_rendered = None          # what a forward leaves: adopt()
+
+    def outputs(self, F=0, alpha=False, vis=False, color=None):
+        """allocates the view's outputs -- the feature image for F > 0 channels, the alpha image, the tensors of a Visibility; `color`: a
+        slice to render into instead of a tensor of its own -> {their names in _CallLayout.OUTPUTS: tensor}"""
+        P, H, W = self.P, self.H, self.W
+        new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=self.dev)  # noqa: E731
+        f32, i32 = torch.float32, torch.int32
+        self.color, self.depth, self.radii = new(f32, 3, H, W) if color is None else color, new(f32, 1, H, W), new(i32, P)
+        self.feat, self.alpha = new(f32, F, H, W) if F else None, new(f32, 1, H, W) if alpha else None
+        made = {"color": self.color, "radii": self.radii, "depth": self.depth, "feat": self.feat, "alpha": self.alpha}
+        if vis:
+            self.vis = [new(f32, P), new(f32, P), new(i32, P), new(i32, 1, H, W)]
+            made.update(zip(Visibility._fields, self.vis))
+        return made
+
+    def adopt(self, chunks, num_rendered, layout_rendered):
+        """what a forward leaves for the backward: its GEOM, BINNING and IMAGE chunks out of {chunk: buffer} and its counts (num_rendered
+        -1: the call is still pending; layout_rendered >= num_rendered: what the binning chunk was laid out for)"""
+        self.chunks = (chunks[_n.GEOM], chunks[_n.BINNING], chunks[_n.IMAGE])
+        self.num_rendered, self.layout_rendered = int(num_rendered), int(layout_rendered)
+
+    def info_words(self):
+        """the int32 [3] view of the device words (tile instances, longest tile list, non-empty tiles) in the IMAGE chunk"""
+        off = int(_n.lib.csplat_image_info_offset(self.W, self.H))
+        return self.chunks[_n.IMAGE][off:off + 12].view(torch.int32)
 
     def fill(self, w, stream, tensors=None):
-        """the csplat_view fields a forward and a backward call share: sizes, scalars, the input and camera pointers, out_color, radii and,
-        once a forward has left them, the chunks and their counts.  tensors: (means3D, sh, colors_precomp, opacities, scales, rotations,
+        """the csplat_view fields a forward and a backward call share: sizes, scalars, the input and camera pointers, the output pointers
+        and, once a forward has left them, the chunks and their counts.  tensors: (means3D, sh, colors_precomp, opacities, scales, rotations,
         cov3Ds_precomp, color, radii) where the view no longer holds them (a backward: they come out of ctx.saved_tensors)"""
         rs = self.rs
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, color, radii = tensors or (
@@ -368,19 +487,19 @@ class _View:
         w.bg, w.means3D, w.shs, w.colors_precomp = _n.ptr(self.bg), _n.ptr(means3D), _n.ptr(sh), _n.ptr(colors_precomp)
         w.opacities, w.scales, w.rotations = _n.ptr(opacities), _n.ptr(scales), _n.ptr(rotations)
         w.cov3D_precomp, w.view, w.proj, w.campos = _n.ptr(cov3Ds_precomp), _n.ptr(self.view), _n.ptr(self.proj), _n.ptr(self.campos)
-        w.out_color, w.radii = _n.ptr(color), _n.ptr(radii)
+        w.out_color, w.radii, w.out_depth = _n.ptr(color), _n.ptr(radii), _n.ptr(self.depth)
+        if self.features is not None:
+            w.features, w.n_features = _n.ptr(self.features), int(self.features.shape[1])
+        w.out_features, w.out_alpha = _n.ptr(self.feat), _n.ptr(self.alpha)
         if self.chunks is not None:
-            w.num_rendered = w.layout_rendered = self.num_rendered
+            w.num_rendered, w.layout_rendered = self.num_rendered, self.layout_rendered
             w.geom, w.binning, w.image = (_n.ptr(c) for c in self.chunks)
 
     def begin(self):
         """K1 + the counting half of the binning on the CURRENT stream; nothing here waits for the GPU."""
         dev, rs = self.dev, self.rs
-        self.color = torch.empty(3, self.H, self.W, dtype=torch.float32, device=dev)
-        self.depth = torch.empty(1, self.H, self.W, dtype=torch.float32, device=dev)
-        self.radii = torch.empty(self.P, dtype=torch.int32, device=dev)
-        self.alloc = _n.ChunkAllocator(dev)
-        tk = C.c_int(-1)
+        self.outputs()
+        self.alloc, tk = _n.ChunkAllocator(dev), C.c_int(-1)
         with _n.on_device(dev):
             rc = _n.lib.csplat_forward_begin(
                 _n.stream_handle(dev), self.P, int(rs.sh_degree), self.M, _n.ptr(self.bg), self.W, self.H,
@@ -400,44 +519,34 @@ class _View:
                                               C.byref(geom), C.byref(binning), C.byref(image))
         self.ticket = None
         _n.check(rc, "csplat_forward_finish")
-        self.num_rendered = int(R.value)
-        ch = self.alloc.chunks
-        self.chunks = (ch[_n_GEOM], ch[_n_BINNING], ch[_n_IMAGE])
-        self.alloc.cb = None  # break the allocator <-> callback cycle: TEMP / TABLE die here, not at the next cyclic GC
-        self.alloc = None
+        self.adopt(self.alloc.chunks, R.value, R.value)
+        self.alloc.cb = self.alloc = None  # break the allocator <-> callback cycle: TEMP / TABLE die here, not at the next cyclic GC
 
     def backward(self, grad_color, saved, grad_depth=None, cam_need=None):
         """K7 + K8 on the CURRENT stream: csplat_backward_views with this one view (it takes the chunks csplat_forward_finish leaves).
         Returns the per-input gradients in the Function's argument order.  grad_depth None: the colour path; else the depth path, where
         a missing grad_color counts as zero.  cam_need: which of (viewmatrix, projmatrix, campos, bg) want a gradient -- any does: the
         camera path, and a second tuple of the four camera gradients is returned."""
-        means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = saved
+        t = dict(zip(_SAVED_NAMES, saved))
         dev, P, M = self.dev, self.P, self.M
         if grad_color is None:
             grad_color = torch.zeros(3, self.H, self.W, dtype=torch.float32, device=dev)
         grad_color, grad_depth = _f32c_grad(grad_color, dev), _f32c_grad(grad_depth, dev)
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-        d_mean2D, d_conic, d_opac, d_color = new(P, 3), new(P, 4), new(P, 1), new(P, 3)
-        d_mean3D, d_cov3D = new(P, 3), new(P, 6)
-        d_sh = new(P, M, 3) if sh is not None else None
-        d_scale = new(P, 3) if scales is not None else None
-        d_rot = new(P, 4) if rotations is not None else None
-        grads = (d_mean3D, d_mean2D, d_sh, d_color if colors_precomp is not None else None, d_opac, d_scale, d_rot,
-                 d_cov3D if cov3Ds_precomp is not None else None)
+        # a buffer per gradient field: the `temp` rows and dL_dconic always (K8 writes them), an optional input's only when it is there
+        rows = list(zip(_INPUTS, self.present))
+        bufs = {r.field: torch.empty(r.shape(P, M), dtype=torch.float32, device=dev) for r, there in rows if there or r.temp}
+        bufs["dL_dconic"] = torch.empty(P, 4, dtype=torch.float32, device=dev)
+        grads = tuple(bufs[r.field] if there else None for r, there in rows)
         cam = cam_need is not None and any(cam_need)
-        if cam:
-            nbytes = _n.lib.csplat_backward_camera_scratch_bytes(P, self.num_rendered, self.W, self.H)
-        elif grad_depth is not None:
-            nbytes = _n.lib.csplat_backward_depth_scratch_bytes(P, self.num_rendered, self.W, self.H)
-        else:
-            nbytes = _n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)
+        sized = _n.lib.csplat_backward_camera_scratch_bytes if cam else _n.lib.csplat_backward_depth_scratch_bytes
+        nbytes = sized(P, self.num_rendered, self.W, self.H) if cam or grad_depth is not None else _n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)
         scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
         w = _n.CsplatView()
-        self.fill(w, _n.stream_handle(dev), (means3D, sh, colors_precomp, None, scales, rotations, cov3Ds_precomp, color, radii))
+        self.fill(w, _n.stream_handle(dev), (t["means3D"], t["sh"], t["colors_precomp"], None, t["scales"], t["rotations"], t["cov3Ds_precomp"],
+                                            t["color"], t["radii"]))
         w.dL_dpix, w.dL_ddepth, w.scratch = _n.ptr(grad_color), _n.ptr(grad_depth), _n.ptr(scratch)
-        w.dL_dmean2D, w.dL_dconic, w.dL_dopacity, w.dL_dcolor = _n.ptr(d_mean2D), _n.ptr(d_conic), _n.ptr(d_opac), _n.ptr(d_color)
-        w.dL_dmean3D, w.dL_dcov3D, w.dL_dsh = _n.ptr(d_mean3D), _n.ptr(d_cov3D), _n.ptr(d_sh)
-        w.dL_dscale, w.dL_drot = _n.ptr(d_scale), _n.ptr(d_rot)
+        for f in _GRAD_FIELDS:
+            setattr(w, f, _n.ptr(bufs.get(f)))
         cam_out = _cam_outputs(cam_need, dev) if cam else ()
         for f, g in zip(_CAM_FIELDS, cam_out):
             setattr(w, f, _n.ptr(g))
@@ -446,13 +555,12 @@ class _View:
         _n.check(rc, "csplat_backward_views")
         return (grads, cam_out) if cam else grads
 
-    def saved(self):
-        return _SAVED_OF(self)
-
-    def drop_inputs(self):
-        """the tensors travel through ctx.save_for_backward; keep only constants and chunks here"""
+    def take_saved(self):
+        """-> the tensors of _SAVED_NAMES: they travel through ctx.save_for_backward, only constants and chunks are kept here"""
+        saved = _SAVED_OF(self)
         self.means3D = self.sh = self.colors_precomp = self.opacities = self.scales = self.rotations = None
-        self.cov3Ds_precomp = self.radii = self.color = self.depth = None
+        self.cov3Ds_precomp = self.radii = self.color = self.depth = self.features = self.feat = self.alpha = None
+        return saved
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -464,8 +572,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         v.begin()
         v.finish()
         color, radii, depth = v.color, v.radii, v.depth
-        ctx.save_for_backward(*v.saved())
-        v.drop_inputs()
+        ctx.save_for_backward(*v.take_saved())
         ctx.view_state = v
         ctx.mark_non_differentiable(radii)
         if hasattr(ctx, "set_materialize_grads"):      # (an unused depth image arrives as None: the colour-only call)
@@ -491,8 +598,6 @@ _side_streams = {}
 # entry point may leave records behind: the cache is a ticket cache (csplat.native.check drops it, recordings are invalidated).
 _ACC_SCRATCH = {}
 _n.TICKET_CACHES.append(_ACC_SCRATCH)
-SCRATCH_ZEROED = 256       # csplat.h: CSPLAT_SCRATCH_ZEROED
-K8_OUTPUTS_UNREAD = 512    # csplat.h: CSPLAT_K8_OUTPUTS_UNREAD
 
 
 def _acc_scratch(dev, P, slot):
@@ -625,6 +730,55 @@ _REFUSALS = (
 )
 
 
+class _Plan:
+    """what _plan_backward leaves: the active views, the one allocation, their csplat_view array, per view the NIN gradients to return, the
+    gradient sinks it claimed, per view its persistent records or None; `keep`: what backward() attaches (alive as long as the plan)"""
+    __slots__ = ("active", "big", "sub", "out", "sinks", "acc", "keep")
+
+    def __init__(self, active, big, sub, out, sinks, acc):
+        self.active, self.big, self.sub, self.out, self.sinks, self.acc, self.keep = active, big, sub, out, sinks, acc, []
+
+    def attach_camera(self, cam_need):
+        """the camera path (csplat_view.dL_dview .. dL_dbg): the gradient buffers of the views that want them -> {view: its four}"""
+        cam_out = {}
+        for a, i in enumerate(self.active):
+            cam_out[i] = _cam_outputs(cam_need[i], self.big.device)
+            for f, g in zip(_CAM_FIELDS, cam_out[i]):
+                setattr(self.sub[a], f, _n.ptr(g))
+            self.keep += [g for g in cam_out[i] if g is not None]
+        return cam_out
+
+    def attach_features(self, ctx, gfeat, galpha, fsaved, need):
+        """the feature path (csplat_view.dL_dfeatures / dL_dalpha): one dL_dfeat_in buffer per feature tensor OBJECT that wants a
+        gradient, shared by the views it was passed to (the library adds their sums in view order) -> per view its buffer or None"""
+        layout, dev = ctx.layout, self.big.device
+        fout, owner = [None] * layout.V, {}
+        for a, i in enumerate(self.active):
+            w, F = self.sub[a], layout.feat[i][0]
+            gf, ga = _f32c_grad(gfeat[i], dev), _f32c_grad(galpha[i], dev)
+            w.features, w.n_features = _n.ptr(fsaved[i]), F
+            w.dL_dfeatures, w.dL_dalpha = _n.ptr(gf), _n.ptr(ga)
+            buf = None
+            if F and layout.features(need, i):
+                key = ctx.feat_first[i]
+                if key not in owner:
+                    owner[key] = fout[i] = torch.empty(ctx.views[i].P, F, dtype=torch.float32, device=dev)
+                buf = owner[key]
+            w.dL_dfeat_in = _n.ptr(buf)
+            self.keep += [gf, ga]
+        return fout
+
+    def attach_depth_scratch(self, views, gdep, scratch_bytes):
+        """the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth (camera, feature) layout, allocated
+        here (never on the colour-only path) and cleared by the library -- the persistent zeroed records are not used by this call"""
+        for a, i in enumerate(self.active):
+            v, w = views[i], self.sub[a]
+            gd = _f32c_grad(gdep[i], v.dev)
+            buf = torch.empty(max(int(scratch_bytes(v.P, v.layout_rendered, v.W, v.H)), 256), dtype=torch.uint8, device=v.dev)
+            w.dL_ddepth, w.scratch, w.accmask = _n.ptr(gd), buf.data_ptr(), w.accmask & ~SCRATCH_ZEROED
+            self.keep += [gd, buf]
+
+
 class _RasterizeGaussiansBatch(torch.autograd.Function):
     """V independent views in one autograd node and ONE library call each way (csplat_forward_views /
     csplat_backward_views).  Every view runs on its own HIP stream (the caller's + V-1 side streams, fenced inside the
@@ -641,71 +795,92 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         assert len(tensors) == layout.n_tensors
         ctx.layout = layout
         if layout.has_vis:
-            _visibility_mode_check()
+            _eager_mode_check(_EAGER_ONLY_VIS)
         if layout.has_feat:
-            _feature_mode_check()
+            _eager_mode_check(_EAGER_ONLY_FEAT)
         groups = [layout.view_inputs(tensors, i) for i in range(V)]
         feats = [layout.features(tensors, i) for i in range(V)]
         ctx.feat_first = [next(j for j in range(i + 1) if feats[j] is feats[i]) for i in range(V)]     # (one gradient per tensor object)
-        views = []
-        for group, rs in zip(groups, layout.settings):
-            means3D, _means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = group
-            views.append(_View(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, rs))
+        views = [_View(g[0], *g[2:], rs, f.contiguous() if F else None)      # (means2D only receives a gradient)
+                 for g, rs, f, (F, _alpha) in zip(groups, layout.settings, feats, layout.feat)]
         dev = views[0].dev
-        main = torch.cuda.current_stream(dev)
-        streams = _view_streams(dev, V, main)
-        arr = (_n.CsplatView * V)()
-        chunks = [dict() for _ in range(V)]
+        main, arr = torch.cuda.current_stream(dev), (_n.CsplatView * V)()
         # stacked: the V images land in ONE [V, 3, H, W] tensor (what the reference builds with torch.cat before the loss,
         # scene_reconstruction/train_utils.py:262-270) and that tensor is the node's first output
+        colors = None
         if stacked:
             assert all((v.H, v.W) == (views[0].H, views[0].W) for v in views), "stacked output needs equal image sizes"
             colors = torch.empty(V, 3, views[0].H, views[0].W, dtype=torch.float32, device=dev)
-
-        def _alloc(ctx_, chunk, nbytes):     # all on the caller's stream: the library fences the view streams around it
-            try:
-                buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-                chunks[int(ctx_ or 0)][int(chunk)] = buf
-                return buf.data_ptr()
-            except Exception:
-                return None
-        cb = _n.ALLOC_FN(_alloc)
-        for i, (v, st) in enumerate(zip(views, streams)):
-            w = arr[i]
-            v.color = colors[i] if stacked else torch.empty(3, v.H, v.W, dtype=torch.float32, device=dev)
-            v.depth = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
-            v.radii = torch.empty(v.P, dtype=torch.int32, device=dev)
-            v.fill(w, st.cuda_stream)
-            w.prefiltered = int(bool(v.rs.prefiltered)) | (CSPLAT_ANTIALIAS if layout.aa else 0)
-            w.alloc_ctx, w.out_depth = i, _n.ptr(v.depth)
-            v.feat = v.alpha = v.features = None
-            F, want_alpha = layout.feat[i]
-            if F:
-                v.features = feats[i].contiguous()
-                v.feat = torch.empty(F, v.H, v.W, dtype=torch.float32, device=dev)
-                w.features, w.n_features, w.out_features = _n.ptr(v.features), F, _n.ptr(v.feat)
-            if want_alpha:
-                v.alpha = torch.empty(1, v.H, v.W, dtype=torch.float32, device=dev)
-                w.out_alpha = _n.ptr(v.alpha)
+        alloc = _n.ChunkAllocator(dev, V)     # (all on the caller's stream: the library fences the view streams around it)
+        made = []
+        for i, (v, st) in enumerate(zip(views, _view_streams(dev, V, main))):
+            made.append(v.outputs(layout.feat[i][0], layout.feat[i][1], layout.vis[i], colors[i] if stacked else None))
+            v.fill(arr[i], st.cuda_stream)
+            arr[i].prefiltered = int(bool(v.rs.prefiltered)) | (CSPLAT_ANTIALIAS if layout.aa else 0)
+            arr[i].alloc_ctx = i
         # the one host read of the call (its counts) is DEFERRED when the library can launch the second phase on the previous call's
         # capacities: everything below that does not need the counts -- the output lists, the backward plan -- is host work done
         # while the GPU runs K1..K6, instead of after a ~45 us wait for K1 / K2
         pending = C.c_int(0)
-        faith = _FAITH
-        if faith is not None:
-            caps = (C.c_uint32 * 3)(*[int(c) for c in faith["caps"]])
-            with _n.on_device(dev):
-                rc = _n.lib.csplat_forward_views_faith(V, C.cast(arr, C.c_void_p), cb, main.cuda_stream, C.cast(caps, C.c_void_p),
-                                                       _n.ptr(faith["valid"]))
-            _n.check(rc, "csplat_forward_views_faith")
-            off = int(_n.lib.csplat_image_info_offset(views[0].W, views[0].H))
-            faith["info"] = [chunks[i][_n_IMAGE][off:off + 12].view(torch.int32) for i in range(V)]
-        else:
-            with _n.on_device(dev):
-                rc = _n.lib.csplat_forward_views_deferred(V, C.cast(arr, C.c_void_p), cb, main.cuda_stream, C.byref(pending))
-            _n.check(rc, "csplat_forward_views_deferred")
         try:
-            return _RasterizeGaussiansBatch._finish_forward(ctx, views, arr, chunks, groups, colors if stacked else None, dev, main, pending, cb)
+            faith = _FAITH
+            if faith is not None:
+                caps = (C.c_uint32 * 3)(*[int(c) for c in faith["caps"]])
+                with _n.on_device(dev):
+                    rc = _n.lib.csplat_forward_views_faith(V, C.cast(arr, C.c_void_p), alloc.cb, main.cuda_stream, C.cast(caps, C.c_void_p),
+                                                           _n.ptr(faith["valid"]))
+                _n.check(rc, "csplat_forward_views_faith")
+            else:
+                with _n.on_device(dev):
+                    rc = _n.lib.csplat_forward_views_deferred(V, C.cast(arr, C.c_void_p), alloc.cb, main.cuda_stream, C.byref(pending))
+                _n.check(rc, "csplat_forward_views_deferred")
+            outs = [None] * layout.n_outputs
+            for i, v in enumerate(views):
+                v.adopt(alloc.views[i], arr[i].num_rendered, arr[i].layout_rendered)
+                for name, j in layout.outputs[i].items():
+                    outs[j] = made[i][name]
+            if _FAITH is not None:
+                _FAITH["info"] = [v.info_words() for v in views]
+            # (mark_non_differentiable keeps its last call's tensors only: all of them in one call)
+            ctx.mark_non_differentiable(*[v.radii for v in views], *[t for v in views if v.vis is not None for t in v.vis])
+            if stacked:
+                outs[layout.stacked_output] = colors
+            # (antialiasing: K8 reads the raw opacities through the views' `opacities` pointers -- those tensors live as long as the node)
+            ctx.aa_opacities = [v.opacities for v in views] if layout.aa else None
+            features = [v.features for v in views]
+            ctx.save_for_backward(*layout.pack_saved([v.take_saved() for v in views], colors, features))
+            # which view first received each input tensor OBJECT (shared parameters get one gradient buffer)
+            ctx.first_of = [[next(j for j in range(i + 1) if groups[j][k] is groups[i][k]) for k in range(NIN)] for i in range(V)]
+            ctx.views, ctx.arr, ctx.on_faith = views, arr, _FAITH is not None
+            ctx.set_materialize_grads(False)     # an unused view arrives as None in backward() and costs nothing
+
+            def plan():
+                return _RasterizeGaussiansBatch._plan_backward(views, arr, ctx.first_of, list(range(V)), groups if _n.GRAD_SINK else None)
+            # the GPU is busy with K1..K6 of the views right now: prepare the backward call in its shadow
+            ctx.plan = plan() if any(ctx.needs_input_grad) else None
+            if not pending.value and _FAITH is None:
+                SPEC_STATS["wait"] += 1
+            if pending.value:
+                relaunched = C.c_int(0)
+                with _n.on_device(dev):
+                    rc = _n.lib.csplat_forward_views_settle(V, C.cast(arr, C.c_void_p), main.cuda_stream, C.byref(relaunched))
+                _n.check(rc, "csplat_forward_views_settle")
+                for i, v in enumerate(views):       # the counts; after a miss, new binning chunks and a new layout
+                    v.adopt(alloc.views[i], arr[i].num_rendered, arr[i].layout_rendered)
+                pending.value = 0
+                SPEC_STATS["miss" if relaunched.value else "hit"] += 1
+                if relaunched.value and ctx.plan is not None:     # the speculation missed: the plan is rebuilt (rare)
+                    _n.grad_release(ctx.plan.sinks)
+                    ctx.plan = plan()
+                elif ctx.plan is not None:
+                    for a, i in enumerate(ctx.plan.active):
+                        ctx.plan.sub[a].num_rendered = arr[i].num_rendered
+                        ctx.plan.sub[a].busy_tiles = arr[i].busy_tiles
+            if layout.has_vis:
+                _RasterizeGaussiansBatch._visibility(views, arr, dev, main)
+            if _KEEP_INFO and _FAITH is None and len({(v.W, v.H) for v in views}) == 1:
+                LAST_INFO[:] = [v.info_words() for v in views]
+            return tuple(outs)
         except BaseException:
             if pending.value:        # never leave a call pending in the library (its tickets stay reserved otherwise)
                 dummy = C.c_int(0)
@@ -715,95 +890,20 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 except Exception:
                     pass
             raise
-
-    @staticmethod
-    def _finish_forward(ctx, views, arr, chunks, groups, colors, dev, main, pending, cb):
-        layout = ctx.layout
-        V, stacked = layout.V, layout.stacked
-        outs, saved = [None] * layout.n_outputs, []
-        for i, v in enumerate(views):
-            v.num_rendered = int(arr[i].num_rendered)            # (-1 while the call is pending)
-            v.layout_rendered = int(arr[i].layout_rendered)      # >= num_rendered: what the binning chunk was laid out for
-            v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
-            made = {"color": v.color, "radii": v.radii, "depth": v.depth, "feat": v.feat, "alpha": v.alpha}
-            v.vis = None
-            if layout.vis[i]:
-                v.vis = [torch.empty(v.P, dtype=torch.float32, device=dev), torch.empty(v.P, dtype=torch.float32, device=dev),
-                         torch.empty(v.P, dtype=torch.int32, device=dev), torch.empty(1, v.H, v.W, dtype=torch.int32, device=dev)]
-                made.update(zip(Visibility._fields, v.vis))
-            for name, j in layout.outputs[i].items():
-                outs[j] = made[name]
-            saved += list(v.saved()[:-1]) + ([] if stacked else [v.color])
-            ctx.mark_non_differentiable(v.radii)
-        if layout.has_vis:        # (mark_non_differentiable keeps its last call's tensors only: all of them in one call)
-            ctx.mark_non_differentiable(*[v.radii for v in views], *[t for v in views if v.vis is not None for t in v.vis])
-        if stacked:
-            outs[layout.stacked_output] = colors
-            saved.append(colors)
-        ctx.nsaved = len(views[0].saved()) - (1 if stacked else 0)
-        ctx.nfeat_saved = 0
-        if layout.has_feat:       # (behind everything the colour path saves: the views' feature tensors, None where a view has none)
-            saved += [v.features for v in views]
-            ctx.nfeat_saved = V
-        ctx.save_for_backward(*saved)
-        # which view first received each input tensor OBJECT (shared parameters get one gradient buffer)
-        ctx.first_of = [[next(j for j in range(i + 1) if groups[j][k] is groups[i][k]) for k in range(NIN)] for i in range(V)]
-        # (antialiasing: K8 reads the raw opacities through the views' `opacities` pointers -- those tensors live as long as the node)
-        ctx.aa_opacities = [v.opacities for v in views] if layout.aa else None
-        for v in views:
-            v.drop_inputs()
-            v.features = v.feat = v.alpha = None
-        ctx.views, ctx.arr = views, arr
-        ctx.on_faith = _FAITH is not None
-        ctx.set_materialize_grads(False)     # an unused view arrives as None in backward() and costs nothing
-        ctx.plan = None
-        if any(ctx.needs_input_grad):
-            # the GPU is busy with K1..K6 of the views right now: prepare the backward call in its shadow
-            ctx.plan = _RasterizeGaussiansBatch._plan_backward(views, saved, ctx.nsaved, arr, ctx.first_of, list(range(V)), dev, groups if _n.GRAD_SINK else None)
-        if not pending.value and _FAITH is None:
-            SPEC_STATS["wait"] += 1
-        if pending.value:
-            relaunched = C.c_int(0)
-            with _n.on_device(dev):
-                rc = _n.lib.csplat_forward_views_settle(V, C.cast(arr, C.c_void_p), main.cuda_stream, C.byref(relaunched))
-            _n.check(rc, "csplat_forward_views_settle")
-            for i, v in enumerate(views):
-                v.num_rendered = int(arr[i].num_rendered)
-            pending.value = 0
-            SPEC_STATS["miss" if relaunched.value else "hit"] += 1
-            if relaunched.value:     # the speculation missed: new binning chunks, new layout -> the plan is rebuilt (rare)
-                for i, v in enumerate(views):
-                    v.layout_rendered = int(arr[i].layout_rendered)
-                    v.chunks = (chunks[i][_n_GEOM], chunks[i][_n_BINNING], chunks[i][_n_IMAGE])
-                if ctx.plan is not None:
-                    _n.grad_release(ctx.plan["sinks"])
-                    ctx.plan = _RasterizeGaussiansBatch._plan_backward(views, saved, ctx.nsaved, arr, ctx.first_of, list(range(V)), dev, groups if _n.GRAD_SINK else None)
-            elif ctx.plan is not None:
-                for a, i in enumerate(ctx.plan["active"]):
-                    ctx.plan["sub"][a].num_rendered = arr[i].num_rendered
-                    ctx.plan["sub"][a].busy_tiles = arr[i].busy_tiles
-        if layout.has_vis:
-            _RasterizeGaussiansBatch._visibility(views, arr, dev, main)
-        if _KEEP_INFO and _FAITH is None and len({(v.W, v.H) for v in views}) == 1 and all(_n_IMAGE in c for c in chunks):
-            off = int(_n.lib.csplat_image_info_offset(views[0].W, views[0].H))
-            LAST_INFO[:] = [chunks[i][_n_IMAGE][off:off + 12].view(torch.int32) for i in range(V)]
-        return tuple(outs)
+        finally:
+            alloc.cb = None          # (the allocator <-> callback cycle: the temporaries die here, not at the next cyclic GC)
 
     @staticmethod
     def _visibility(views, arr, dev, main):
         """csplat_visibility_views on the views that asked for it (the forward is settled: counts and chunks are final); the scratch is
         freed on the caller's stream, behind the launch"""
-        outs = (_n.CsplatVisibility * len(views))()
-        keep = []
-        for i, v in enumerate(views):
-            if v.vis is None:
-                continue
-            scratch = torch.empty(max(int(_n.lib.csplat_visibility_scratch_bytes(v.P, max(v.layout_rendered, v.num_rendered, 0), v.W, v.H)), 256),
-                                  dtype=torch.uint8, device=dev)
-            keep.append(scratch)
-            o = outs[i]
-            o.weight_max, o.weight_sum, o.pixel_count, o.top_id = (_n.ptr(t) for t in v.vis)
-            o.scratch = scratch.data_ptr()
+        outs, keep = (_n.CsplatVisibility * len(views))(), []
+        for o, v in zip(outs, views):
+            if v.vis is not None:
+                keep.append(torch.empty(max(int(_n.lib.csplat_visibility_scratch_bytes(v.P, max(v.layout_rendered, v.num_rendered, 0), v.W, v.H)), 256),
+                                        dtype=torch.uint8, device=dev))
+                o.weight_max, o.weight_sum, o.pixel_count, o.top_id = (_n.ptr(t) for t in v.vis)
+                o.scratch = keep[-1].data_ptr()
         with _n.on_device(dev):
             rc = _n.lib.csplat_visibility_views(len(views), C.cast(arr, C.c_void_p), C.cast(outs, C.c_void_p), main.cuda_stream)
         _n.check(rc, "csplat_visibility_views")
@@ -811,115 +911,60 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             v.vis = None
 
     @staticmethod
-    def _plan_backward(views, saved, k, arr, first_of, active, dev, inputs=None):
-        """Everything of the backward call that does not depend on the incoming gradient values: ONE allocation for every
-        gradient, temporary and K7 record of the step (returned gradients are views of it), the csplat_view array with all
-        pointers but dL_dpix, the accumulate masks of shared parameters.  Built at the end of forward(), while the
-        compositing kernels run, so that backward() is left with pointer patching and one library call.
-        inputs: the call's input tensors -- one with a registered gradient SINK (csplat.native.GRAD_SINK: a view-parallel step's flat
-        buffer) gets its gradient written there by K8 and handed to autograd as a fresh view of the sink."""
-        plan, owner, total = [], {}, 0
-        sink_of = {}        # (view, slot) -> a fresh view of the input's gradient sink
-        used_sinks = []
+    def _plan_backward(views, arr, first_of, active, inputs=None):
+        """Everything of the backward call that does not depend on the incoming gradient values: ONE allocation for every gradient,
+        temporary and K7 record of the step and the csplat_view array with all pointers but dL_dpix, as a _GradLayout says.  Built at the
+        end of forward(), while the compositing kernels run: backward() is left with pointer patching and one library call.  inputs: the
+        call's input tensors -- one with a registered gradient SINK (csplat.native.GRAD_SINK: a view-parallel step's flat buffer) gets its
+        gradient written there by K8 and handed to autograd as a fresh view of the sink."""
+        dev = views[0].dev
+        specs, acc = [None] * len(views), []        # acc: per active view its persistent zeroed records, None in the bit-reproducible mode
+        for a, i in enumerate(active):
+            v = views[i]
+            acc.append(_acc_scratch(dev, v.P, a)[0])
+            specs[i] = (v.P, v.M, v.present, first_of[i], v.staged,
+                        int(_n.lib.csplat_backward_scratch_bytes(v.P, v.layout_rendered)) // 4 + 64 if acc[a] is None else None)
+        sink_of, claimed = {}, []        # (view, slot) -> a fresh view of the input's gradient sink; the sinks this plan claimed
 
-        def reserve(numel):
-            nonlocal total
-            off = total
-            total += (int(numel) + 63) & ~63          # 256-byte granules
-            return off
-        # per-view gradients of means3D / rotations that belong to DISTINCT input tensors of equal size -- the rows of one [T, P, .]
-        # tensor upstream (csplat.gaussians.UnbindViews) -- are laid out back to back, so that their stack is a view
-        pre = {}
-        for row in (_IN["means3D"], _IN["rotations"]):
-            slot = row.slot
-            if len(active) > 1 and all(first_of[i][slot] == i for i in active) and len({views[i].P for i in active}) == 1 and \
-                    all(not row.optional or saved[i * k + row.saved] is not None for i in active):
-                size = _prod(row.shape(views[active[0]].P, 0))
-                blk = reserve(len(active) * size)
-                for a, i in enumerate(active):
-                    pre[(i, slot)] = blk + a * size
-        for i in active:
-            P, M = views[i].P, views[i].M
-            acc_buf, zeroed = _acc_scratch(dev, P, len(plan))
-            ent = {"scratch": acc_buf if zeroed else reserve(int(_n.lib.csplat_backward_scratch_bytes(P, views[i].layout_rendered)) // 4 + 64),
-                   "mask": SCRATCH_ZEROED if zeroed else 0, "ret": {}}
-            for row in _K7_OUT:
-                ent[row.field] = reserve(_prod(row.shape(P, M)))
-                ent["ret"][row.slot] = (ent[row.field], row.shape(P, M))
-            ent["dL_dconic"] = reserve(4 * P)
-            unread = True
-            for row in _K8_OUT:
-                slot, field = row.slot, row.field
-                present = not row.optional or saved[i * k + row.saved] is not None
-                if not present and not row.temp:
-                    ent[field] = None
-                    continue
-                unread = unread and not (row.temp and present)
-                j = first_of[i][slot]
-                # (dL_dsh: only the SH-staging K8 can add into a buffer -- the library's own predicate, include/csplat.h at `M`: M == 16 and
-                # a 16-byte aligned SH tensor; the buffers reserved here are 256-byte aligned.  Otherwise every view gets a dL_dsh of its
-                # own, the per-view unstaged K8 writes it and autograd sums them.)
-                if present and j != i and j in active and (row.name != "sh" or _sh_staged(M, saved[i * k + row.saved])):
-                    ent[field] = owner[(j, slot)]
-                    ent["mask"] |= row.acc
-                else:
-                    shape = row.shape(P, M)
-                    numel = _prod(shape)
-                    t = inputs[i][slot] if inputs is not None and present and (i, slot) not in pre else None
-                    sk = _n.grad_sink(t) if t is not None else None
-                    sv = _n.grad_out(sk, t.shape, dev) if sk is not None else None
-                    if sv is not None and sv.numel() == numel and sv.data_ptr() % 16 == 0:
-                        sink_of[(i, slot)] = sv
-                        # (only a sink this plan really CLAIMED is given back when the plan is rebuilt: grad_out() hands out fresh memory
-                        # when another node holds the slice, and releasing that node's claim would let a third writer alias it -- ADVICE r5)
-                        if sv.data_ptr() == sk[0].data_ptr() + 4 * int(sk[1]):
-                            used_sinks.append(sk)
-                        ent[field] = owner[(i, slot)] = ("sink", i, slot)
-                        ent["ret"][slot] = (ent[field], shape)
-                        continue
-                    ent[field] = owner[(i, slot)] = pre[(i, slot)] if (i, slot) in pre else reserve(numel)
-                    if present:
-                        ent["ret"][slot] = (ent[field], shape)
-            # dL_dconic is never handed back; dL_dcolor / dL_dcov3D (the `temp` rows) only to a precomputed colour / covariance input:
-            # without those the batched K8 may leave the three unwritten (they keep their place in the allocation: address space, no traffic)
-            if unread:
-                ent["mask"] |= K8_OUTPUTS_UNREAD
-            plan.append(ent)
-        big = torch.empty(max(total, 64), dtype=torch.float32, device=dev)
-        base = big.data_ptr()
-        sub = (_n.CsplatView * len(active))()
+        def sunk(i, slot, numel):
+            t = inputs[i][slot]
+            sk = _n.grad_sink(t)
+            sv = _n.grad_out(sk, t.shape, dev) if sk is not None else None
+            if sv is None or sv.numel() != numel or sv.data_ptr() % 16:
+                return False
+            sink_of[(i, slot)] = sv
+            # (only a sink this plan really CLAIMED is given back when the plan is rebuilt: grad_out() hands out fresh memory
+            # when another node holds the slice, and releasing that node's claim would let a third writer alias it -- ADVICE r5)
+            if sv.data_ptr() == sk[0].data_ptr() + 4 * int(sk[1]):
+                claimed.append(sk)
+            return True
+        lay = _GradLayout(specs, active, sunk if inputs is not None else None)
+        big = torch.empty(max(lay.total, 64), dtype=torch.float32, device=dev)
+        base, sub = big.data_ptr(), (_n.CsplatView * len(active))()
         out = [None] * len(views)       # per active view its NIN gradients, in slot order
         for a, i in enumerate(active):
-            ent = plan[a]
-            C.memmove(C.byref(sub[a]), C.byref(arr[i]), C.sizeof(_n.CsplatView))
             w = sub[a]
-            w.scratch = ent["scratch"].data_ptr() if torch.is_tensor(ent["scratch"]) else base + 4 * ent["scratch"]
-            w.accmask = ent["mask"]
-            for field in _GRAD_FIELDS:
-                off = ent.get(field)
-                if isinstance(off, tuple):
-                    setattr(w, field, sink_of[off[1:]].data_ptr())
-                else:
-                    setattr(w, field, None if off is None else base + 4 * off)
+            C.memmove(C.byref(w), C.byref(arr[i]), C.sizeof(_n.CsplatView))
+            w.scratch = acc[a].data_ptr() if lay.scratch[a] is None else base + 4 * lay.scratch[a]
+            w.accmask = lay.mask[a]
+            for field, loc in zip(_GRAD_FIELDS, lay.fields[a]):
+                setattr(w, field, None if loc is None else sink_of[loc].data_ptr() if loc.__class__ is tuple else base + 4 * loc)
             out[i] = [None] * NIN
-            for slot, (off, shape) in ent["ret"].items():
-                out[i][slot] = sink_of[off[1:]] if isinstance(off, tuple) else big[off:off + _prod(shape)].view(shape)
-        return {"active": list(active), "big": big, "sub": sub, "out": out, "sinks": used_sinks,
-                "acc": [e["scratch"] for e in plan if torch.is_tensor(e["scratch"])]}      # (kept alive with the plan)
+            for slot, loc, shape in lay.ret[a]:
+                out[i][slot] = sink_of[loc] if loc.__class__ is tuple else big[loc:loc + _prod(shape)].view(shape)
+        return _Plan(list(active), big, sub, out, claimed, acc)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        layout, views, k, arr = ctx.layout, ctx.views, ctx.nsaved, ctx.arr
+        layout, views, arr = ctx.layout, ctx.views, ctx.arr
         # unpacked on EVERY path: the plan made in forward() holds raw pointers into the inputs, so the usual pass would never touch the saved
         # tensors -- and autograd's version check, which refuses an input edited in place since the forward, runs when they are unpacked
         saved = ctx.saved_tensors
-        V = layout.V
-        dev = views[0].dev
+        V, dev = layout.V, views[0].dev
         main = torch.cuda.current_stream(dev)
         need = ctx.needs_input_grad[1:]
         cam_need = [tuple(layout.cam_group(need, i)) for i in range(V)]
-        fspec = layout.feat
         if layout.stacked:
             gstack = grads[layout.stacked_output]
             gcol = [None] * V if gstack is None else [gstack[i] for i in range(V)]
@@ -931,81 +976,45 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             return layout.grads()
         want_feat = any(gfeat[i] is not None or galpha[i] is not None for i in active)
         want_cam = any(any(cam_need[i]) for i in active)
-        arrived = {"depth": any(gdep[i] is not None for i in active), "feat": want_feat, "cam": want_cam}
+        want_depth = any(gdep[i] is not None for i in active)
+        arrived = {"depth": want_depth, "feat": want_feat, "cam": want_cam}
         where = {"faith": ctx.on_faith, "deferred_k8": _K8_DEFER is not None}
         for what, place, message in _REFUSALS:
             if arrived[what] and where[place]:
                 raise RuntimeError(message)
         plan, ctx.plan = ctx.plan, None                         # (one use: the buffers are handed to autograd)
-        if plan is not None and plan["acc"] and (int(_n.lib.csplat_debug_flags_query()) & _n.DEBUG_BIT_REPRODUCIBLE):
-            _n.grad_release(plan["sinks"])                      # (the bit-reproducible mode was switched on after the forward: its scratch
-            plan = None                                         #  has another layout -- plan again)
-        if plan is None or plan["active"] != active:            # a view's image went unused, or a second backward pass
-            if plan is not None:
-                _n.grad_release(plan["sinks"])
-            plan = _RasterizeGaussiansBatch._plan_backward(views, saved, k, arr, ctx.first_of, active, dev)
-        gs = [_f32c_grad(gcol[i], dev) if gcol[i] is not None else torch.zeros(3, views[i].H, views[i].W, dtype=torch.float32, device=dev)
-              for i in active]
-        for a, g in enumerate(gs):
-            plan["sub"][a].dL_dpix = _n.ptr(g)
-        cam_out = {}
-        if want_cam:
-            # the camera path (csplat_view.dL_dview .. dL_dbg): the gradient buffers of the views that want them; the scratch follows below
-            for a, i in enumerate(active):
-                cam_out[i] = _cam_outputs(cam_need[i], dev)
-                for f, g in zip(_CAM_FIELDS, cam_out[i]):
-                    setattr(plan["sub"][a], f, _n.ptr(g))
-                gs += [g for g in cam_out[i] if g is not None]
-        fout = None
-        if want_feat:
-            # the feature path (csplat_view.dL_dfeatures / dL_dalpha): one dL_dfeat_in buffer per feature tensor OBJECT that wants a
-            # gradient, shared by the views it was passed to (the library adds their sums in view order)
-            fsaved = saved[len(saved) - ctx.nfeat_saved:]
-            fout, owner = [None] * V, {}
-            for a, i in enumerate(active):
-                w, F = plan["sub"][a], fspec[i][0]
-                gf = _f32c_grad(gfeat[i], dev) if gfeat[i] is not None else None
-                ga = _f32c_grad(galpha[i], dev) if galpha[i] is not None else None
-                w.features, w.n_features = _n.ptr(fsaved[i]), F
-                w.dL_dfeatures, w.dL_dalpha = _n.ptr(gf), _n.ptr(ga)
-                buf = None
-                if F and layout.features(need, i):
-                    key = ctx.feat_first[i]
-                    if key not in owner:
-                        owner[key] = fout[i] = torch.empty(views[i].P, F, dtype=torch.float32, device=dev)
-                    buf = owner[key]
-                w.dL_dfeat_in = _n.ptr(buf)
-                gs += [gf, ga]
-        if want_feat or want_cam or any(gdep[i] is not None for i in active):
-            # the depth path (csplat_view.dL_ddepth): every view of the call gets scratch of the depth layout (the camera path: of the
-            # camera layout; the feature path: of the feature layout), allocated here (never on the colour-only path) and cleared by the
-            # library -- the persistent zeroed records are not used by this call
-            scratch_bytes = _n.lib.csplat_backward_feature_scratch_bytes if want_feat else \
-                _n.lib.csplat_backward_camera_scratch_bytes if want_cam else _n.lib.csplat_backward_depth_scratch_bytes
-            for a, i in enumerate(active):
-                v = views[i]
-                gd = _f32c_grad(gdep[i], dev) if gdep[i] is not None else None
-                buf = torch.empty(max(int(scratch_bytes(v.P, v.layout_rendered, v.W, v.H)), 256), dtype=torch.uint8, device=dev)
-                plan["sub"][a].dL_ddepth = _n.ptr(gd)
-                plan["sub"][a].scratch = buf.data_ptr()
-                plan["sub"][a].accmask &= ~SCRATCH_ZEROED
-                gs += [gd, buf]
+        # plan again: a view's image went unused, a second backward pass, or the bit-reproducible mode was switched on after the forward
+        # (its scratch has another layout)
+        if plan is not None and (plan.active != active or (plan.acc[0] is not None and int(_n.lib.csplat_debug_flags_query()) & _n.DEBUG_BIT_REPRODUCIBLE)):
+            _n.grad_release(plan.sinks)
+            plan = None
+        if plan is None:
+            plan = _RasterizeGaussiansBatch._plan_backward(views, arr, ctx.first_of, active)
+        sub = plan.sub
+        plan.keep += [_f32c_grad(gcol[i], dev) if gcol[i] is not None else torch.zeros(3, views[i].H, views[i].W, dtype=torch.float32, device=dev)
+                      for i in active]
+        for a, g in enumerate(plan.keep):
+            sub[a].dL_dpix = _n.ptr(g)
+        cam_out = plan.attach_camera(cam_need) if want_cam else {}
+        fout = plan.attach_features(ctx, gfeat, galpha, layout.saved_features(saved), need) if want_feat else None
+        if want_feat or want_cam or want_depth:
+            plan.attach_depth_scratch(views, gdep, _n.lib.csplat_backward_feature_scratch_bytes if want_feat else
+                                      _n.lib.csplat_backward_camera_scratch_bytes if want_cam else _n.lib.csplat_backward_depth_scratch_bytes)
         if _K8_DEFER is not None:
             # K7 now, K8 in slices later (DeferredK8.launch): the plan -- the view array and every buffer it points into -- stays alive
             with _n.on_device(dev):
-                rc = _n.lib.csplat_backward_views_parts(len(active), C.cast(plan["sub"], C.c_void_p), main.cuda_stream, 1, 0, 1)
+                rc = _n.lib.csplat_backward_views_parts(len(active), C.cast(sub, C.c_void_p), main.cuda_stream, 1, 0, 1)
             _n.check(rc, "csplat_backward_views_parts")
             # (kept alive: the MEMORY the K8 slices write -- never the gradient tensor objects themselves: AccumulateGrad adopts a
             #  gradient only when nobody else holds it, and would otherwise snapshot the still unwritten buffer into a copy)
-            outs, plan["out"] = plan["out"], None
-            _K8_DEFER.entries.append((plan["sub"], len(active), dev, views[active[0]].P, (plan["big"], plan["acc"], gs, saved,
-                                                                                          ctx.aa_opacities)))
+            outs, plan.out = plan.out, None
+            _K8_DEFER.entries.append((sub, len(active), dev, views[active[0]].P, (plan.big, plan.acc, plan.keep, saved, ctx.aa_opacities)))
             return layout.grads(outs)
         with _n.on_device(dev):
-            rc = _n.lib.csplat_backward_views(len(active), C.cast(plan["sub"], C.c_void_p), main.cuda_stream)
+            rc = _n.lib.csplat_backward_views(len(active), C.cast(sub, C.c_void_p), main.cuda_stream)
         _n.check(rc, "csplat_backward_views")
         cam = [_cam_returns(cam_out[i], _cam_tensors(views[i].rs)) if i in cam_out else None for i in range(V)]
-        return layout.grads(plan["out"], cam, fout)
+        return layout.grads(plan.out, cam, fout)
 
 
 def rasterize_views(settings, inputs, stacked=False):
@@ -1022,26 +1031,18 @@ def rasterize_views(settings, inputs, stacked=False):
     call of more than 8 views in groups of at most 8 (include/csplat.h, "More than 8 views"), adding every group into the same gradients."""
     groups, fspec, feats = [], [], []
     vis = [_check_visibility_flag(kw.get("return_visibility", False)) for kw in inputs]
-    aa = {bool(kw.get("antialiasing", False)) for kw in inputs}
-    if len(aa) > 1:
-        raise ValueError("rasterize_views: antialiasing must be the same in every view of a call, got "
-                         f"{[bool(kw.get('antialiasing', False)) for kw in inputs]}")
+    aa = [bool(kw.get("antialiasing", False)) for kw in inputs]
+    if len(set(aa)) > 1:
+        raise ValueError(f"rasterize_views: antialiasing must be the same in every view of a call, got {aa}")
     for kw in inputs:
         f, want_alpha = kw.get("features"), bool(kw.get("return_alpha", False))
         fspec.append((_check_features(f, kw["means3D"]) if f is not None else 0, want_alpha))
         feats.append(f)
-        shs, cp = kw.get("shs"), kw.get("colors_precomp")
-        sc, ro, cov = kw.get("scales"), kw.get("rotations"), kw.get("cov3D_precomp")
-        if (shs is None) == (cp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((sc is None or ro is None) and cov is None) or ((sc is not None or ro is not None) and cov is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        shs, cp, sc, ro, cov = (kw.get(k) for k in ("shs", "colors_precomp", "scales", "rotations", "cov3D_precomp"))
+        _check_one_of_each(shs, cp, sc, ro, cov)
         groups.append((kw["means3D"], kw["means2D"], shs, cp, kw["opacities"], sc, ro, cov))
     layout = _call_layout(settings, stacked, True in aa, fspec, vis)
     return layout.split(_RasterizeGaussiansBatch.apply(layout, *layout.pack(groups, feats)))
-
-
-_n_GEOM, _n_BINNING, _n_IMAGE = 0, 1, 2
 
 
 class GaussianRasterizer(nn.Module):
@@ -1069,11 +1070,7 @@ class GaussianRasterizer(nn.Module):
         return_visibility=True: one more element at the very end, a Visibility(weight_max, weight_sum, pixel_count, top_id) of this view
         (non-differentiable, bit-reproducible; not for a forward launched on faith or a captured step: RuntimeError).  It composes with
         everything above."""
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _check_one_of_each(shs, colors_precomp, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings, features, bool(return_alpha), bool(antialiasing),
                                    _check_visibility_flag(return_visibility))

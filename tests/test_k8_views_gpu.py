@@ -9,7 +9,8 @@ backward in its bit-reproducible mode (csplat_debug_flags 256), so that what dif
   - cut into three Gaussian ranges (csplat_backward_views_parts) == the whole call, torch.equal;
   - CSPLAT_K8_OUTPUTS_UNREAD (include/csplat.h) by direct calls of csplat_backward_views on a csplat_view array: the bit changes no
     gradient the caller reads, and dL_dconic / dL_dcolor / dL_dcov3D are each written in full or left untouched;
-  - a gradient buffer at a 4-byte-aligned address that is not 16-byte aligned: same result as the aligned buffer."""
+  - a gradient buffer at a 4-byte-aligned address that is not 16-byte aligned: same result as the aligned buffer;
+  - in the default mode, the csplat_view array of a real deferred backward against the plan tests/test_raster_grad_layout_cpu.py pins."""
 import ctypes as C
 
 import numpy as np
@@ -305,3 +306,39 @@ def test_misaligned_gradient_buffers(V, own):
     for k in res[0]:
         assert torch.isfinite(res[0][k]).all(), k
         assert torch.equal(res[0][k], res[1][k]), k
+
+
+def test_deferred_plan_lies_where_the_pinned_layout_says():
+    """the csplat_view array a real backward hands the library -- default mode, persistent zeroed records -- against the default-mode entry
+    of the table tests/test_raster_grad_layout_cpu.py pins without a GPU: every gradient pointer as an offset from the one allocation,
+    and the accumulate masks.  V = 2, P = 33, a 16 x 16 image, every parameter shared -- but means2D: K8 turns a view's K7 moments into its dL_dmean2D
+    (csrc/csplat_k8_views_body.h: `dL_dmean2D[3 * i] = a9[0]`), one buffer per view, and inside deferred_k8() a leaf must get its gradient from one buffer alone (a shared means2D would have autograd add two
+    buffers K8 has not written yet); the layout never shares that row, so the pinned plan is the same."""
+    import diff_gaussian_rasterization as dgr
+    import test_raster_grad_layout_cpu as L
+    case = make_case(P=33, W=16, H=16, seed=3, grid=4, scale_mul=3.0)
+    inp = util.gpu_inputs(case)
+    m2d = [inp["means2D"], torch.zeros(33, 3, device="cuda", requires_grad=True)]
+    kws = [dict(means3D=inp["means3D"], means2D=m, opacities=inp["opacities"], shs=inp["shs"], scales=inp["scales"],
+                rotations=inp["rotations"]) for m in m2d]
+    assert inp["shs"].shape[1] == 16 and inp["shs"].data_ptr() % 16 == 0
+    outs = dgr.rasterize_views([util.gpu_settings(case)] * 2, kws)
+    with dgr.deferred_k8() as h:
+        (outs[0][0].sum() + 2.0 * outs[1][0].sum()).backward()
+    assert len(h.entries) == 1
+    sub, n, _dev, P, keep = h.entries[0]
+    want = L.expected()["0"]["V2_P33_M16_all"]
+    assert (n, P) == (2, 33) and keep[0].numel() == want["total"]
+    base = keep[0].data_ptr()
+    for a in range(n):
+        got = [int(sub[a].accmask)] + [None if not getattr(sub[a], f) else (getattr(sub[a], f) - base) // 4 for f in L.FIELDS]
+        assert got == want["views"][a][:1] + want["views"][a][2:], (a, got)
+        assert all((getattr(sub[a], f) - base) % 4 == 0 for f in L.FIELDS if getattr(sub[a], f))
+        assert sub[a].scratch and not base <= sub[a].scratch < base + 4 * keep[0].numel()      # (the persistent records: outside)
+    leaves = [t for k, t in kws[0].items() if k != "means2D"] + m2d
+    for t in leaves:      # the gradients autograd adopted ARE the plan's buffers: K8 has yet to write them
+        assert base <= t.grad.data_ptr() < base + 4 * keep[0].numel()
+        t.grad.fill_(float("nan"))
+    h.launch(0, 1)
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(t.grad).all() for t in leaves)

@@ -164,3 +164,35 @@ def test_builder_passes_the_camera_groups_only_for_a_wanted_gradient():
         assert not _call_layout(mixed, False, False, none, vis).cam
     with pytest.raises(ValueError, match="same number of feature channels"):
         _call_layout(_settings(2), False, False, [(2, False), (3, False)], vis)
+
+
+def test_saved_tensors_round_trip_and_indices_are_a_bijection():
+    """the saved order: per view means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii and -- unless stacked -- its colour;
+    then the stacked colours; then, when a view asks for features or alpha, the views' feature tensors"""
+    names = ("means3D", "sh", "colors_precomp", "scales", "rotations", "cov3Ds_precomp", "radii", "color")
+    for case in _cases():
+        L = _layout(*case)
+        V = L.V
+        per_view = [tuple(object() for _ in names) for _ in range(V)]
+        colors = [v[-1] for v in per_view] if L.stacked else None        # (the stacked colours: row i is view i's colour)
+        feats = [object() if L.feat[i][0] else None for i in range(V)]
+        saved = L.pack_saved(per_view, colors, feats)
+        assert len(saved) == L.n_saved == V * (7 if L.stacked else 8) + (1 if L.stacked else 0) + (V if L.has_feat else 0), case
+        seen = []           # positions of the saved list the accessors reach: together every one, each once
+        where = lambda t: next(j for j, u in enumerate(saved) if u is t)      # noqa: E731
+        for i in range(V):
+            for name, want in zip(names, per_view[i]):
+                got = L.saved_input(saved, i, name)
+                if name == "color" and L.stacked:
+                    assert got is colors and got[i] is want and where(got) == V * 7, case
+                    seen += [where(got)] if i == 0 else []
+                else:
+                    assert got is want, (case, i, name)
+                    seen.append(where(got))
+        got = L.saved_features(saved)
+        if L.has_feat:
+            assert len(got) == V and all(a is b for a, b in zip(got, feats)), case
+            seen += range(L.n_saved - V, L.n_saved)
+        else:
+            assert len(got) == 0, case
+        assert sorted(seen) == list(range(L.n_saved)), case
