@@ -57,12 +57,10 @@ class FlowLoss(torch.autograd.Function):
         count = torch.empty(1, dtype=torch.int32, device=dev)
         unit = torch.empty(T, P, 3, dtype=torch.float32, device=dev) if need else None
         addc = None if add is None else add.reshape(1).float()
-        with _n.on_device(dev):
-            scratch = _flow_scratch(dev, T, P)
-            _n.check(_n.lib.csplat_flow_loss_fwd(_n.stream_handle(dev), T, P, W, H, _ptr_table(X), _ptr_table(full), _ptr_table(F),
-                                                 _ptr_table(vis), _ptr_table(M), float(cap), float(lam), float(weight),
-                                                 None if addc is None else _n.ptr(addc), float(add_weight), _n.ptr(unit), _n.ptr(scratch),
-                                                 _n.ptr(out), _n.ptr(count)), "csplat_flow_loss_fwd")
+        scratch = _flow_scratch(dev, T, P)
+        _n.launch("csplat_flow_loss_fwd", dev, T, P, W, H, _ptr_table(X), _ptr_table(full), _ptr_table(F), _ptr_table(vis), _ptr_table(M),
+                  float(cap), float(lam), float(weight), _n.ptr(addc), float(add_weight), _n.ptr(unit), _n.ptr(scratch), _n.ptr(out),
+                  _n.ptr(count))
         ctx.save_for_backward(unit)
         ctx.dims = (T, P, float(lam), float(weight), float(add_weight), add is not None, len(tensors))
         loss, lf, nv = out[0], out[1], count[0]
@@ -82,9 +80,7 @@ class FlowLoss(torch.autograd.Function):
         if unit is not None:
             dev = unit.device
             d = torch.empty(T, P, 3, dtype=torch.float32, device=dev)
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_flow_loss_bwd(_n.stream_handle(dev), T, P, _n.ptr(unit), lam, weight, _n.ptr(g), _n.ptr(d)),
-                         "csplat_flow_loss_bwd")
+            _n.launch("csplat_flow_loss_bwd", dev, T, P, _n.ptr(unit), lam, weight, _n.ptr(g), _n.ptr(d))
             grads = [d[t] if ctx.needs_input_grad[2 + t] else None for t in range(T)]      # slices of the one buffer the launch wrote
         gadd = None
         if has_add and ctx.needs_input_grad[1]:

@@ -50,12 +50,9 @@ class GeometryLoss(torch.autograd.Function):
         out = torch.empty(3, dtype=torch.float32, device=dev)
         sign = torch.empty(V * hw, dtype=torch.uint8, device=dev) if need else None
         addc = None if add is None else add.reshape(1).float()
-        with _n.on_device(dev):
-            scratch = _geom_scratch(dev, V, hw)
-            _n.check(_n.lib.csplat_geom_loss_fwd(_n.stream_handle(dev), V, hw, _ptr_table(D if Z else []), _ptr_table(A), _ptr_table(Z),
-                                                 _ptr_table(S), _ptr_table(M), float(lam_d), float(lam_s), float(weight),
-                                                 None if addc is None else _n.ptr(addc), float(add_weight), _n.ptr(sign), _n.ptr(scratch),
-                                                 _n.ptr(out)), "csplat_geom_loss_fwd")
+        scratch = _geom_scratch(dev, V, hw)
+        _n.launch("csplat_geom_loss_fwd", dev, V, hw, _ptr_table(D if Z else []), _ptr_table(A), _ptr_table(Z), _ptr_table(S), _ptr_table(M),
+                  float(lam_d), float(lam_s), float(weight), _n.ptr(addc), float(add_weight), _n.ptr(sign), _n.ptr(scratch), _n.ptr(out))
         ctx.save_for_backward(sign, *Z, *M)
         ctx.dims = (V, hw, float(lam_d) if Z else 0.0, float(lam_s) if S else 0.0, float(weight), float(add_weight), len(Z), len(M),
                     add is not None, [tuple(t.shape) for t in views[:2 * V]], len(views))
@@ -80,9 +77,8 @@ class GeometryLoss(torch.autograd.Function):
             dev = sign.device
             gD = torch.empty(V, hw, dtype=torch.float32, device=dev) if want_d else None
             gA = torch.empty(V, hw, dtype=torch.float32, device=dev) if want_a else None
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_geom_loss_bwd(_n.stream_handle(dev), V, hw, _n.ptr(sign), _ptr_table(Z), _ptr_table(M), lam_d, lam_s,
-                                                     weight, _n.ptr(g), _n.ptr(gD), _n.ptr(gA)), "csplat_geom_loss_bwd")
+            _n.launch("csplat_geom_loss_bwd", dev, V, hw, _n.ptr(sign), _ptr_table(Z), _ptr_table(M), lam_d, lam_s, weight, _n.ptr(g),
+                      _n.ptr(gD), _n.ptr(gA))
         grads = []
         for k, buf in enumerate((gD, gA)):      # every view's gradient is a slice of the one buffer the launch wrote
             for v in range(V):

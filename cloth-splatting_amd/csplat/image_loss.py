@@ -65,16 +65,6 @@ def _l1_scratch(device):
     return buf
 
 
-def _launch_l1(x, y, mask, scratch, loss, grad):
-    st = _n.stream_handle(x.device)
-    if mask is None:
-        _n.check(_n.lib.csplat_l1(st, x.numel(), _n.ptr(x), _n.ptr(y), _n.ptr(scratch), _n.ptr(loss), _n.ptr(grad)), "csplat_l1")
-    else:
-        B, Cc, hw, mc = _mask_layout(x, mask)
-        _n.check(_n.lib.csplat_l1_masked(st, B, Cc, hw, _n.ptr(x), _n.ptr(y), _n.ptr(mask), mc, _n.ptr(scratch), _n.ptr(loss),
-                                         _n.ptr(grad)), "csplat_l1_masked")
-
-
 class FusedL1(torch.autograd.Function):
     """mean |a - b| (mean |(a - b) * mask| with a mask).  Forward: csplat_l1_signs -- the loss and ONE BYTE per element
     (sign((a - b) m)); backward: csplat_l1_signs_bwd writes g * sign * m / n in one pass (g = the incoming gradient, read on the
@@ -93,15 +83,15 @@ class FusedL1(torch.autograd.Function):
             B, Cc, hw, mc = _mask_layout(a, mask)
         else:
             B, Cc, hw, mc = 1, 1, a.numel(), 1
-        with _n.on_device(a.device):
-            if need:
-                sign8 = torch.empty(a.numel(), dtype=torch.int8, device=a.device)
-                _n.check(_n.lib.csplat_l1_signs(_n.stream_handle(a.device), B, Cc, hw, _n.ptr(a), _n.ptr(b), _n.ptr(mask), mc, _n.ptr(scratch),
-                                                _n.ptr(loss), _n.ptr(sign8)), "csplat_l1_signs")
-                ctx.save_for_backward(sign8, mask)
-                ctx.layout = (B, Cc, hw, mc, tuple(a.shape))
-            else:
-                _launch_l1(a, b, mask, scratch, loss, None)
+        if need:
+            sign8 = torch.empty(a.numel(), dtype=torch.int8, device=a.device)
+            _n.launch("csplat_l1_signs", a.device, B, Cc, hw, _n.ptr(a), _n.ptr(b), _n.ptr(mask), mc, _n.ptr(scratch), _n.ptr(loss), _n.ptr(sign8))
+            ctx.save_for_backward(sign8, mask)
+            ctx.layout = (B, Cc, hw, mc, tuple(a.shape))
+        elif mask is None:
+            _n.launch("csplat_l1", a.device, a.numel(), _n.ptr(a), _n.ptr(b), _n.ptr(scratch), _n.ptr(loss), None)
+        else:
+            _n.launch("csplat_l1_masked", a.device, B, Cc, hw, _n.ptr(a), _n.ptr(b), _n.ptr(mask), mc, _n.ptr(scratch), _n.ptr(loss), None)
         return loss
 
     @staticmethod
@@ -111,9 +101,7 @@ class FusedL1(torch.autograd.Function):
         B, Cc, hw, mc, shape = ctx.layout
         g = g.reshape(1).float().contiguous()
         out = torch.empty(shape, dtype=torch.float32, device=sign8.device)
-        with _n.on_device(sign8.device):
-            _n.check(_n.lib.csplat_l1_signs_bwd(_n.stream_handle(sign8.device), B, Cc, hw, _n.ptr(sign8), _n.ptr(mask), mc, _n.ptr(g), _n.ptr(out)),
-                     "csplat_l1_signs_bwd")
+        _n.launch("csplat_l1_signs_bwd", sign8.device, B, Cc, hw, _n.ptr(sign8), _n.ptr(mask), mc, _n.ptr(g), _n.ptr(out))
         ga = out if ctx.needs_input_grad[0] else None
         gb = -out if ctx.needs_input_grad[1] else None
         return ga, gb, None
@@ -128,6 +116,13 @@ def _plane_chunks(n_planes):
     return [(s, min(s + _MAX_PLANES, n_planes)) for s in range(0, n_planes, _MAX_PLANES)]
 
 
+def _launch_per_chunk(name, device, n_planes, H, W, *args):
+    """lib.<name>(stream, planes of the range, H, W, taps, *args) once per _plane_chunks range.  A tensor among `args` holds one row
+    per plane and passes as the pointer of the range's rows; anything else (None, a number, a pointer) passes as it is."""
+    for s, e in _plane_chunks(n_planes):
+        _n.launch(name, device, e - s, H, W, _taps(), *[_n.ptr(a[s:e]) if torch.is_tensor(a) else a for a in args])
+
+
 class GaussianBlur11(torch.autograd.Function):
     """zero-padded 11x11 Gaussian window (sigma 1.5) on every [H, W] plane, HIP kernel csplat_blur11; self-adjoint."""
 
@@ -139,11 +134,8 @@ class GaussianBlur11(torch.autograd.Function):
         out = torch.empty_like(x)
         if x.numel() == 0:
             return out
-        xp, op = x.view(-1, H, W), out.view(-1, H, W)
-        with _n.on_device(x.device):
-            for s, e in _plane_chunks(xp.shape[0]):
-                _n.check(_n.lib.csplat_blur11(_n.stream_handle(x.device), e - s, H, W, _taps(), _n.ptr(xp[s:e]), _n.ptr(op[s:e])),
-                         "csplat_blur11")
+        xp = x.view(-1, H, W)
+        _launch_per_chunk("csplat_blur11", x.device, xp.shape[0], H, W, xp, out.view(-1, H, W))
         return out
 
     @staticmethod
@@ -184,13 +176,9 @@ class FusedSSIM(torch.autograd.Function):
         p = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=x.device) if need else None
         per_plane = int(_n.lib.csplat_ssim_partial_count(1, H, W))
         partial = torch.empty(n_img * per_plane, dtype=torch.float32, device=x.device)
-        xp, yp, pp = x.view(-1, H, W), y.view(-1, H, W), (p.view(3, -1, H, W) if need else None)
-        with _n.on_device(x.device):
-            for s, e in _plane_chunks(n_img):
-                _n.check(_n.lib.csplat_ssim_fwd(_n.stream_handle(x.device), e - s, H, W, _taps(), _n.ptr(xp[s:e]), _n.ptr(yp[s:e]),
-                                                _n.ptr(pp[0, s:e]) if need else None, _n.ptr(pp[1, s:e]) if need else None,
-                                                _n.ptr(pp[2, s:e]) if need else None, None, _n.ptr(partial[s * per_plane:e * per_plane])),
-                         "csplat_ssim_fwd")
+        pp = p.view(3, -1, H, W) if need else (None,) * 3
+        _launch_per_chunk("csplat_ssim_fwd", x.device, n_img, H, W, x.view(-1, H, W), y.view(-1, H, W), pp[0], pp[1], pp[2], None,
+                          partial.view(n_img, per_plane))
         ctx.save_for_backward(x, y, p)
         ctx.dims = (n_img, H, W)
         return partial.sum() / float(x.numel())
@@ -202,12 +190,9 @@ class FusedSSIM(torch.autograd.Function):
         n_img, H, W = ctx.dims
         g = g.reshape(1).float().contiguous()
         dx = torch.empty_like(x)
-        xp, yp, pp, dp = x.view(-1, H, W), y.view(-1, H, W), p.view(3, -1, H, W), dx.view(-1, H, W)
-        with _n.on_device(x.device):
-            for s, e in _plane_chunks(n_img):
-                _n.check(_n.lib.csplat_ssim_bwd(_n.stream_handle(x.device), e - s, H, W, _taps(), _n.ptr(xp[s:e]), _n.ptr(yp[s:e]),
-                                                _n.ptr(pp[0, s:e]), _n.ptr(pp[1, s:e]), _n.ptr(pp[2, s:e]), _n.ptr(g), 1.0 / float(x.numel()),
-                                                None, None, _n.ptr(dp[s:e])), "csplat_ssim_bwd")
+        pp = p.view(3, -1, H, W)
+        _launch_per_chunk("csplat_ssim_bwd", x.device, n_img, H, W, x.view(-1, H, W), y.view(-1, H, W), pp[0], pp[1], pp[2], _n.ptr(g),
+                          1.0 / float(x.numel()), None, None, dx.view(-1, H, W))
         return dx, None
 
 
@@ -250,13 +235,10 @@ class FusedImageLoss(torch.autograd.Function):
         p = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=dev) if need else None
         sign = torch.empty(x.shape, dtype=torch.int8, device=dev) if need else None
         addc = None if add is None else add.reshape(1).float()
-        with _n.on_device(dev):
-            scratch = _image_loss_scratch(dev, (B, Cc, H, W))
-            _n.check(_n.lib.csplat_image_loss_fwd(_n.stream_handle(dev), B, Cc, H, W, _taps(), _n.ptr(x), _n.ptr(y),
-                                                  None if mask is None else _n.ptr(mask), mc, float(lam), float(img_weight),
-                                                  None if addc is None else _n.ptr(addc), float(add_weight), float(psnr_scale),
-                                                  *([_n.ptr(p[k]) for k in range(3)] if need else [None] * 3),
-                                                  _n.ptr(sign) if need else None, _n.ptr(scratch), _n.ptr(out)), "csplat_image_loss_fwd")
+        scratch = _image_loss_scratch(dev, (B, Cc, H, W))
+        _n.launch("csplat_image_loss_fwd", dev, B, Cc, H, W, _taps(), _n.ptr(x), _n.ptr(y), _n.ptr(mask), mc, float(lam), float(img_weight),
+                  _n.ptr(addc), float(add_weight), float(psnr_scale), *([_n.ptr(p[k]) for k in range(3)] if need else [None] * 3),
+                  _n.ptr(sign), _n.ptr(scratch), _n.ptr(out))
         ctx.save_for_backward(x, y, p, sign, mask)
         ctx.dims = (B, Cc, H, W, mc, float(lam), float(img_weight), float(add_weight), add is not None, image.shape)
         loss, ps, il = out[0], out[1], out[2]
@@ -275,10 +257,8 @@ class FusedImageLoss(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            with _n.on_device(x.device):
-                _n.check(_n.lib.csplat_image_loss_bwd(_n.stream_handle(x.device), B, Cc, H, W, _taps(), _n.ptr(x), _n.ptr(y), _n.ptr(p[0]),
-                                                      _n.ptr(p[1]), _n.ptr(p[2]), _n.ptr(sign), None if mask is None else _n.ptr(mask), mc,
-                                                      lam, w_img, _n.ptr(g), _n.ptr(dx)), "csplat_image_loss_bwd")
+            _n.launch("csplat_image_loss_bwd", x.device, B, Cc, H, W, _taps(), _n.ptr(x), _n.ptr(y), _n.ptr(p[0]), _n.ptr(p[1]), _n.ptr(p[2]),
+                      _n.ptr(sign), _n.ptr(mask), mc, lam, w_img, _n.ptr(g), _n.ptr(dx))
             dx = dx.reshape(shape)
         gadd = None
         if has_add and ctx.needs_input_grad[4]:
@@ -332,9 +312,7 @@ def psnr(img1, img2):
         B = int(a.shape[0])
         out = torch.empty(B, 1, dtype=torch.float32, device=a.device)
         scratch = torch.empty(_n.lib.csplat_psnr_scratch_bytes(B), dtype=torch.uint8, device=a.device)
-        with _n.on_device(a.device):
-            _n.check(_n.lib.csplat_psnr(_n.stream_handle(a.device), B, a.numel() // B, _n.ptr(a), _n.ptr(b), _n.ptr(scratch),
-                                        _n.ptr(out)), "csplat_psnr")
+        _n.launch("csplat_psnr", a.device, B, a.numel() // B, _n.ptr(a), _n.ptr(b), _n.ptr(scratch), _n.ptr(out))
         return out
     _n.composed_fallback("train.psnr", "dtype" if img1.shape == img2.shape and img1.numel() else "shape", img1)
     mse = ((img1 - img2) ** 2).view(img1.shape[0], -1).mean(1, keepdim=True)

@@ -248,10 +248,12 @@ def why_not_f32c(*tensors):
     return None
 
 
-# caches of scratch buffers that are "zeroed once: the kernel leaves its ticket word at zero" (csplat_l1, the image loss, the cloth
-# regularisers, csplat_sim_hidden_bwd ...) register here.  An entry point that FAILS may have left a ticket anywhere -- every later launch
-# would then take the wrong "last workgroup" branch and return wrong sums silently -- so any error drops every cached buffer:
-# the next call allocates and zeroes a fresh one.
+# caches of scratch buffers that are "zeroed once: the kernel leaves its ticket word at zero" (the cloth regularisers,
+# csplat_sim_hidden_bwd ...) register here.  An entry point that FAILS may have left a ticket anywhere -- every later launch would then
+# take the wrong "last workgroup" branch and return wrong sums silently -- so any error drops every cached buffer: the next call
+# allocates and zeroes a fresh one.  (csplat_l1, the image, geometry and flow losses register their per-stream partial-sum buffers here
+# too, for the eviction: since round 5 a second launch sums their partials and they leave no ticket.  Of the image kernels only
+# csplat_psnr has one, which it clears itself in every call.)
 TICKET_CACHES = []
 # Recorded hipGraphs (csplat.train.CapturedStep, bench.py's GraphedSteps) hold RAW POINTERS into these buffers: whenever a cache is
 # emptied the freed memory may be handed to another tensor while the graphs stay replayable.  Every eviction therefore bumps

@@ -5,195 +5,41 @@
 // HBM-bound, 4 B read + 4 B written per pixel (the grouped-conv path measured 1.2-1.8 ms per call on 5x3x3x800x800;
 // this is a 46 MB round trip).  The window is symmetric and the padding is zero, so the operator is self-adjoint: the
 // backward of blur is the same kernel applied to the incoming gradient.
+// Sums: the L1, the image loss and the geometry loss leave one partial per workgroup, added in index order by a second, one-workgroup
+// launch (no ticket, no float atomics); the standalone SSIM hands its partials to the caller.  Only k_psnr still has a ticket.
 #include "csplat_common.h"
 #include <math.h>
 #include <stdlib.h>
 
 namespace {
+// ---- the tile the blur, the SSIM and the image loss share: IL_T threads per 64 x 16 tile of one plane (blockIdx.z).  il_load puts N maps
+// with their 5-pixel halo into LDS; a thread then owns a STRIP: il_hrow makes 4 consecutive outputs of a halo row from 14 loaded values,
+// il_vcol 2 consecutive rows of a column from 12 -- the sums of one output per thread and pass, tap order k = 0 .. 10, at half the
+// instructions (round 5: 80.2 / 54.9 us at [3,3,800,800] -> 76.1 / 48.1 us; 256 threads with 8 x 1 / 1 x 4 strips were slower than either).
 constexpr int BW = 64, BH = 16, R5 = 5;
 struct Taps { float w[11]; };
+constexpr int IL_T = 512, IL_HR = BH + 2 * R5, IL_XP = BW + 2 * R5 + 2, IL_HP = BW + 4;      // 26 halo rows; pitches 76 / 68 floats
+constexpr int IL_HS = 4, IL_VS = 2;            // outputs per horizontal / vertical strip: 26 x 16 = 416 and 64 x 8 = 512 strips for 512 threads
+constexpr int IL_NS = BW / IL_HS, IL_NV = IL_HS + 10;      // strips per halo row; values a horizontal strip loads per map
+static_assert(IL_NS * IL_HR <= IL_T && BW * (BH / IL_VS) == IL_T, "one strip per thread");
+static_assert(BW == 64 && BH == 16, "the strip assignment below is written for 64 x 16 tiles");
 
-__global__ __launch_bounds__(256) void k_blur11(int H, int W, Taps taps, const float *__restrict__ in, float *__restrict__ out) {
-    __shared__ float s_in[(BH + 2 * R5)][BW + 2 * R5 + 1];
-    __shared__ float s_h[(BH + 2 * R5)][BW + 1];
-    const size_t img = (size_t)blockIdx.z * H * W;
-    const int x0 = blockIdx.x * BW, y0 = blockIdx.y * BH;
-    for (int t = threadIdx.x; t < (BH + 2 * R5) * (BW + 2 * R5); t += 256) {
-        const int ry = t / (BW + 2 * R5), rx = t - ry * (BW + 2 * R5);
-        const int y = y0 + ry - R5, x = x0 + rx - R5;
-        s_in[ry][rx] = (y >= 0 && y < H && x >= 0 && x < W) ? in[img + (size_t)y * W + x] : 0.f;   // zero padding
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < (BH + 2 * R5) * BW; t += 256) {
-        const int ry = t / BW, rx = t - ry * BW;
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) a += taps.w[k] * s_in[ry][rx + k];
-        s_h[ry][rx] = a;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < BH * BW; t += 256) {
-        const int ry = t / BW, rx = t - ry * BW;
-        const int y = y0 + ry, x = x0 + rx;
-        if (y < H && x < W) {
-            float a = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) a += taps.w[k] * s_h[ry + k][rx];
-            out[img + (size_t)y * W + x] = a;
-        }
-    }
-}
-
-// ---- fused SSIM (utils/loss_utils.py:40-70, size_average form).  Forward: ONE kernel loads an x / y tile with its 5-pixel
-// halo, forms x^2, y^2, xy in LDS, runs the five separable 11x11 windows, evaluates the SSIM map and its three partial
-// derivatives (w.r.t. mu1 = blur(x), s11 = blur(x^2), s12 = blur(xy)) and a per-workgroup sum of the map.  Backward: ONE
-// kernel blurs the three partials (the window is self-adjoint) and combines g * (b1 + 2x b2 + y b3).  The composed form
-// is a cat, a blur launch and ~25 elementwise launches forward, ~50 backward, each a full-image HBM round trip.
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
-
-constexpr int SSIM_THREADS = 512;   // 8 waves share one tile's LDS: the load / horizontal / vertical phases of the 3 resident workgroups overlap better
-__global__ __launch_bounds__(SSIM_THREADS) void k_ssim_fwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
-                                                   float *__restrict__ P1, float *__restrict__ P2, float *__restrict__ P3,
-                                                   float *__restrict__ map_out, float *__restrict__ partial,
-                                                   const float *__restrict__ mask, int mask_channels, int channels) {
-    __shared__ float s_x[(BH + 2 * R5)][BW + 2 * R5 + 1];
-    __shared__ float s_y[(BH + 2 * R5)][BW + 2 * R5 + 1];
-    __shared__ float s_h[5][(BH + 2 * R5)][BW + 1];
-    __shared__ float s_red[SSIM_THREADS / 64];
-    const size_t img = (size_t)blockIdx.z * H * W;
-    const int x0 = blockIdx.x * BW, y0 = blockIdx.y * BH;
-    for (int t = threadIdx.x; t < (BH + 2 * R5) * (BW + 2 * R5); t += SSIM_THREADS) {
-        const int ry = t / (BW + 2 * R5), rx = t - ry * (BW + 2 * R5);
-        const int y = y0 + ry - R5, x = x0 + rx - R5;
-        const bool in = y >= 0 && y < H && x >= 0 && x < W;       // zero padding (of the images AND of their products)
-        s_x[ry][rx] = in ? X[img + (size_t)y * W + x] : 0.f;
-        s_y[ry][rx] = in ? Y[img + (size_t)y * W + x] : 0.f;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < (BH + 2 * R5) * BW; t += SSIM_THREADS) {
-        const int ry = t / BW, rx = t - ry * BW;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float w = taps.w[k], xv = s_x[ry][rx + k], yv = s_y[ry][rx + k];
-            a0 += w * xv; a1 += w * yv; a2 += w * (xv * xv); a3 += w * (yv * yv); a4 += w * (xv * yv);
-        }
-        s_h[0][ry][rx] = a0; s_h[1][ry][rx] = a1; s_h[2][ry][rx] = a2; s_h[3][ry][rx] = a3; s_h[4][ry][rx] = a4;
-    }
-    __syncthreads();
-    float acc = 0.f;
-    for (int t = threadIdx.x; t < BH * BW; t += SSIM_THREADS) {
-        const int ry = t / BW, rx = t - ry * BW;
-        const int y = y0 + ry, x = x0 + rx;
-        if (y < H && x < W) {
-            float mu1 = 0.f, mu2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-                const float w = taps.w[k];
-                mu1 += w * s_h[0][ry + k][rx]; mu2 += w * s_h[1][ry + k][rx]; s11 += w * s_h[2][ry + k][rx];
-                s22 += w * s_h[3][ry + k][rx]; s12 += w * s_h[4][ry + k][rx];
-            }
-            const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float A1 = 2.f * mu12 + SSIM_C1, A2 = 2.f * (s12 - mu12) + SSIM_C2;
-            const float B1 = mu1_sq + mu2_sq + SSIM_C1, B2 = (s11 - mu1_sq) + (s22 - mu2_sq) + SSIM_C2;
-            const float inv = 1.f / (B1 * B2);
-            const float S = A1 * A2 * inv;
-            const size_t o = img + (size_t)y * W + x;
-            if (map_out) map_out[o] = S;
-            // masked form (train_utils.py:64-67): the reduced quantity is sum((1 - S) * m) and the partials carry the weight m
-            float m = 1.f;
-            if (mask) {
-                const size_t plane = mask_channels == 1 ? blockIdx.z / channels : blockIdx.z;
-                m = mask[(plane * H + y) * W + x];
-                acc += (1.f - S) * m;
-            } else acc += S;
-            if (P1) {
-                P1[o] = m * (2.f * mu2 * (A2 - A1) * inv - S * 2.f * mu1 * (B2 - B1) * inv);   // dS/dmu1
-                P2[o] = m * (-S / B2);                                                         // dS/ds11
-                P3[o] = m * (2.f * A1 * inv);                                                  // dS/ds12
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t_ = 0.f;
-        for (int k = 0; k < SSIM_THREADS / 64; k++) t_ += s_red[k];
-        partial[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t_;
-    }
-}
-
-__global__ __launch_bounds__(SSIM_THREADS) void k_ssim_bwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
-                                                   const float *__restrict__ P1, const float *__restrict__ P2,
-                                                   const float *__restrict__ P3, const float *__restrict__ gscalar, float inv_n,
-                                                   const float *__restrict__ addend, const float *__restrict__ add_scale,
-                                                   float *__restrict__ dX) {
-    __shared__ float s_p[3][(BH + 2 * R5)][BW + 2 * R5 + 1];
-    __shared__ float s_h[3][(BH + 2 * R5)][BW + 1];
-    const size_t img = (size_t)blockIdx.z * H * W;
-    const int x0 = blockIdx.x * BW, y0 = blockIdx.y * BH;
-    for (int t = threadIdx.x; t < (BH + 2 * R5) * (BW + 2 * R5); t += SSIM_THREADS) {
+// the tile at (x0, y0) of plane `img` of N maps with its halo, zero outside the image; ends with the barrier
+template <int N, class... Src>
+__device__ __forceinline__ void il_load(int H, int W, size_t img, int x0, int y0, float (&dst)[N][IL_HR][IL_XP], const Src *__restrict__... src) {
+    static_assert(sizeof...(Src) == N, "one source per map");
+    for (int t = threadIdx.x; t < IL_HR * (BW + 2 * R5); t += IL_T) {
         const int ry = t / (BW + 2 * R5), rx = t - ry * (BW + 2 * R5);
         const int y = y0 + ry - R5, x = x0 + rx - R5;
         const bool in = y >= 0 && y < H && x >= 0 && x < W;
         const size_t o = img + (size_t)y * W + x;
-        s_p[0][ry][rx] = in ? P1[o] : 0.f; s_p[1][ry][rx] = in ? P2[o] : 0.f; s_p[2][ry][rx] = in ? P3[o] : 0.f;
+        int q = 0;
+        ((dst[q++][ry][rx] = in ? src[o] : 0.f), ...);
     }
     __syncthreads();
-    for (int t = threadIdx.x; t < (BH + 2 * R5) * BW; t += SSIM_THREADS) {
-        const int ry = t / BW, rx = t - ry * BW;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float w = taps.w[k];
-            a0 += w * s_p[0][ry][rx + k]; a1 += w * s_p[1][ry][rx + k]; a2 += w * s_p[2][ry][rx + k];
-        }
-        s_h[0][ry][rx] = a0; s_h[1][ry][rx] = a1; s_h[2][ry][rx] = a2;
-    }
-    __syncthreads();
-    const float g = gscalar[0] * inv_n;
-    const float ga = addend ? add_scale[0] : 0.f;
-    for (int t = threadIdx.x; t < BH * BW; t += SSIM_THREADS) {
-        const int ry = t / BW, rx = t - ry * BW;
-        const int y = y0 + ry, x = x0 + rx;
-        if (y < H && x < W) {
-            float b1 = 0.f, b2 = 0.f, b3 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-                const float w = taps.w[k];
-                b1 += w * s_h[0][ry + k][rx]; b2 += w * s_h[1][ry + k][rx]; b3 += w * s_h[2][ry + k][rx];
-            }
-            const size_t o = img + (size_t)y * W + x;
-            const float d = g * (b1 + 2.f * X[o] * b2 + Y[o] * b3);
-            dX[o] = addend ? d + ga * addend[o] : d;
-        }
-    }
 }
-
-// ---- the WHOLE image loss of a train step in one launch each way (train_utils.py:50-74 + the PSNR the reference logs every step,
-// :262-283): Ll1 + lambda (1 - SSIM) [masked: mean|(x - y) m| + lambda mean((1 - S) m)], the per-camera PSNR, and -- optionally -- the
-// sum with another device scalar (the regularisers), so that the loss the step differentiates leaves the library finished.  k_ssim_fwd's
-// tile already holds x and y: the L1 term, the sign byte of its gradient and the squared error ride on the third phase.  Workgroup
-// partials (3 floats) are summed in index order by k_image_loss_finish: bit-reproducible, no float atomics.
-// Replaces k_l1 + k_psnr + k_ssim_fwd and eight stock reductions / elementwise launches.
-// k_image_loss_fwd / _bwd, REGISTER-BLOCKED since round 5.  The round-4 forms (one output per thread and pass: every output re-read its
-// eleven taps from LDS, re-formed x^2 / y^2 / xy per tap; counters: 428 lane-instructions and 79 LDS instructions per pixel, vector pipe
-// ~45 % busy, 53 % of the wave-cycles waiting) measured 80.2 / 54.9 us at [3,3,800,800].  Here a thread owns a strip: the horizontal pass
-// makes 4 consecutive outputs of a row from 14 loaded values per map (products formed once per loaded value), the vertical pass 2
-// consecutive rows of a column from 12 values per map -- half the instructions -- for 76.1 / 48.1 us (same box, rocprofv3).  Not more,
-// because what the kernel waits for is a tile's LIFE (load, barrier, pass, barrier, pass, stores) with three tiles resident per CU (51 KB of
-// LDS each): the same scheme on 256 threads per tile (8 x 1 / 1 x 4 strips) was SLOWER than the round-4 kernels (97.6 / 61.3 us), and at 84
-// VGPRs (5 waves per SIMD: two tiles per CU) the forward took 92.6 us -- hence __launch_bounds__(512, 6).  Same tile (64 x 16), same
-// partial-sum layout, same arithmetic per output (tap order k = 0 .. 10): the finish kernel and the parity tests are unchanged.
-constexpr int IL_T = 512, IL_HR = BH + 2 * R5, IL_XP = BW + 2 * R5 + 2, IL_HP = BW + 4;      // 26 halo rows; pitches 76 / 68 floats
-constexpr int IL_HS = 4, IL_VS = 2;            // outputs per horizontal / vertical strip: 26 x 16 = 416 and 64 x 8 = 512 strips for 512 threads
-static_assert((BW / IL_HS) * IL_HR <= IL_T && BW * (BH / IL_VS) == IL_T, "one strip per thread");
-static_assert(BW == 64 && BH == 16, "the strip assignment below is written for 64 x 16 tiles");
-
 // horizontal 11-tap pass of one row strip: out[o] = sum_k w[k] v[o + k], o = 0 .. IL_HS - 1
-__device__ __forceinline__ void il_hrow(const Taps &taps, const float (&v)[IL_HS + 10], float *dst) {
+__device__ __forceinline__ void il_hrow(const Taps &taps, const float (&v)[IL_NV], float *dst) {
     float a[IL_HS];
 #pragma unroll
     for (int o = 0; o < IL_HS; o++) {
@@ -204,6 +50,13 @@ __device__ __forceinline__ void il_hrow(const Taps &taps, const float (&v)[IL_HS
     }
     static_assert(IL_HS == 4, "one 16-byte store per strip");
     reinterpret_cast<float4 *>(dst)[0] = make_float4(a[0], a[1], a[2], a[3]);
+}
+// the same for a map as it was loaded: the strip's IL_NV values from LDS, its IL_HS sums back
+__device__ __forceinline__ void il_hmap(const Taps &taps, const float *src, float *dst) {
+    float v[IL_NV];
+#pragma unroll
+    for (int k = 0; k < IL_NV; k++) v[k] = src[k];
+    il_hrow(taps, v, dst);
 }
 // vertical 11-tap pass of one column strip: out[r] = sum_k w[k] s[(row0 + r + k) * IL_HP], r = 0 .. IL_VS - 1
 __device__ __forceinline__ void il_vcol(const Taps &taps, const float *s, float (&out)[IL_VS]) {
@@ -218,41 +71,84 @@ __device__ __forceinline__ void il_vcol(const Taps &taps, const float *s, float 
         out[r] = t;
     }
 }
+// the mask plane of image plane blockIdx.z: one per image (mask_channels == 1) or one per channel
+__device__ __forceinline__ size_t il_mask_plane(const float *mask, int mask_channels, int channels) {
+    return mask ? (mask_channels == 1 ? blockIdx.z / channels : blockIdx.z) : 0;
+}
 
-__global__ __launch_bounds__(IL_T, 6) void k_image_loss_fwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
-                                                           float *__restrict__ P1, float *__restrict__ P2, float *__restrict__ P3,
-                                                           signed char *__restrict__ sign8, const float *__restrict__ mask, int mask_channels,
-                                                           int channels, float *__restrict__ partial) {
+__global__ __launch_bounds__(IL_T) void k_blur11(int H, int W, Taps taps, const float *__restrict__ in, float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float s_in[1][IL_HR][IL_XP];
+    __shared__ __attribute__((aligned(16))) float s_h[1][IL_HR][IL_HP];
+    const size_t img = (size_t)blockIdx.z * H * W;
+    const int x0 = blockIdx.x * BW, y0 = blockIdx.y * BH;
+    il_load(H, W, img, x0, y0, s_in, in);
+    if (threadIdx.x < IL_HR * IL_NS) {
+        const int ry = threadIdx.x / IL_NS, c0 = (threadIdx.x % IL_NS) * IL_HS;
+        il_hmap(taps, &s_in[0][ry][c0], &s_h[0][ry][c0]);
+    }
+    __syncthreads();
+    const int rx = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * IL_VS, x = x0 + rx;
+    float a[IL_VS];
+    il_vcol(taps, &s_h[0][r0][rx], a);
+#pragma unroll
+    for (int r = 0; r < IL_VS; r++) {
+        const int y = y0 + r0 + r;
+        if (y < H && x < W) out[img + (size_t)y * W + x] = a[r];
+    }
+}
+
+// ---- fused SSIM (utils/loss_utils.py:40-70, size_average form) and the WHOLE image loss of a train step (train_utils.py:50-74 + the PSNR
+// the reference logs every step, :262-283): Ll1 + lambda (1 - SSIM) [masked: mean|(x - y) m| + lambda mean((1 - S) m)].  ONE tile body each
+// way, instantiated twice.  Forward: loads an x / y tile with its halo, runs the five separable 11x11 windows (x^2, y^2, xy formed once
+// per loaded value), evaluates the SSIM map, its three partial derivatives (w.r.t. mu1 = blur(x), s11 = blur(x^2), s12 = blur(xy)) and the
+// workgroup's sum of the map.  Backward: blurs the three partials (the window is self-adjoint) and combines g (b1 + 2x b2 + y b3).  The
+// composed form is a cat, a blur launch and ~25 elementwise launches forward, ~50 backward, each a full-image HBM round trip.
+//   L1 = false (k_ssim_fwd / k_ssim_bwd, the standalone SSIM): one partial sum per workgroup, the optional map, the optional addend.
+//   L1 = true  (k_image_loss_fwd / _bwd, what every train step runs): the tile already holds x and y, so the L1 term, the sign byte of
+//              its gradient and the squared error of the PSNR ride on the last phase; three partial sums per workgroup, summed in index
+//              order by k_image_loss_finish: bit-reproducible, no float atomics.
+// What these kernels wait for is a tile's LIFE (load, barrier, pass, barrier, pass, stores) with three tiles resident per CU (51 KB of LDS
+// each): at 84 VGPRs (5 waves per SIMD: two tiles per CU) the forward took 92.6 us against 76.1 -- hence __launch_bounds__(IL_T, 6).
+constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
+
+// partial [L1 ? 3 : 1][workgroups]: sum S (masked: sum (1 - S) m), then sum |(x - y) m| and sum (x - y)^2
+template <bool L1>
+__device__ __forceinline__ void ssim_tile_fwd(int H, int W, const Taps &taps, const float *__restrict__ X, const float *__restrict__ Y,
+                                              float *__restrict__ P1, float *__restrict__ P2, float *__restrict__ P3,
+                                              signed char *__restrict__ sign8, float *__restrict__ map_out, const float *__restrict__ mask,
+                                              int mask_channels, int channels, float *__restrict__ partial) {
+    constexpr int NQ = L1 ? 3 : 1;
     __shared__ __attribute__((aligned(16))) float s_x[IL_HR][IL_XP];
     __shared__ __attribute__((aligned(16))) float s_y[IL_HR][IL_XP];
     __shared__ __attribute__((aligned(16))) float s_h[5][IL_HR][IL_HP];
-    __shared__ float s_red[3][IL_T / 64];
+    __shared__ float s_red[NQ][IL_T / 64];
     const size_t img = (size_t)blockIdx.z * H * W;
     const int x0 = blockIdx.x * BW, y0 = blockIdx.y * BH;
+    // (this body's own halo loop, not il_load: with the one index il_load forms for all its maps the compiler arranges the address
+    //  arithmetic of the two loads differently -- three instructions fewer, but not the listing every train step has run since round 5)
     for (int t = threadIdx.x; t < IL_HR * (BW + 2 * R5); t += IL_T) {
         const int ry = t / (BW + 2 * R5), rx = t - ry * (BW + 2 * R5);
         const int y = y0 + ry - R5, x = x0 + rx - R5;
-        const bool in = y >= 0 && y < H && x >= 0 && x < W;
+        const bool in = y >= 0 && y < H && x >= 0 && x < W;       // zero padding (of the images AND of their products)
         s_x[ry][rx] = in ? X[img + (size_t)y * W + x] : 0.f;
         s_y[ry][rx] = in ? Y[img + (size_t)y * W + x] : 0.f;
     }
     __syncthreads();
-    constexpr int NS = BW / IL_HS, NV = IL_HS + 10;
-    if (threadIdx.x < IL_HR * NS) {                    // strip = (halo row, IL_HS columns)
-        const int ry = threadIdx.x / NS, c0 = (threadIdx.x % NS) * IL_HS;
-        float xv[NV], yv[NV], v[NV];
+    if (threadIdx.x < IL_HR * IL_NS) {                    // strip = (halo row, IL_HS columns)
+        const int ry = threadIdx.x / IL_NS, c0 = (threadIdx.x % IL_NS) * IL_HS;
+        float xv[IL_NV], yv[IL_NV], v[IL_NV];
 #pragma unroll
-        for (int k = 0; k < NV; k++) { xv[k] = s_x[ry][c0 + k]; yv[k] = s_y[ry][c0 + k]; }
+        for (int k = 0; k < IL_NV; k++) { xv[k] = s_x[ry][c0 + k]; yv[k] = s_y[ry][c0 + k]; }
         il_hrow(taps, xv, &s_h[0][ry][c0]);
         il_hrow(taps, yv, &s_h[1][ry][c0]);
 #pragma unroll
-        for (int k = 0; k < NV; k++) v[k] = xv[k] * xv[k];
+        for (int k = 0; k < IL_NV; k++) v[k] = xv[k] * xv[k];
         il_hrow(taps, v, &s_h[2][ry][c0]);
 #pragma unroll
-        for (int k = 0; k < NV; k++) v[k] = yv[k] * yv[k];
+        for (int k = 0; k < IL_NV; k++) v[k] = yv[k] * yv[k];
         il_hrow(taps, v, &s_h[3][ry][c0]);
 #pragma unroll
-        for (int k = 0; k < NV; k++) v[k] = xv[k] * yv[k];
+        for (int k = 0; k < IL_NV; k++) v[k] = xv[k] * yv[k];
         il_hrow(taps, v, &s_h[4][ry][c0]);
     }
     __syncthreads();
@@ -266,7 +162,7 @@ __global__ __launch_bounds__(IL_T, 6) void k_image_loss_fwd(int H, int W, Taps t
         il_vcol(taps, &s_h[3][r0][rx], q22);
         il_vcol(taps, &s_h[4][r0][rx], q12);
         const int x = x0 + rx;
-        const size_t plane = mask ? (mask_channels == 1 ? blockIdx.z / channels : blockIdx.z) : 0;
+        const size_t plane = il_mask_plane(mask, mask_channels, channels);
 #pragma unroll
         for (int r = 0; r < IL_VS; r++) {
             const int y = y0 + r0 + r;
@@ -278,32 +174,42 @@ __global__ __launch_bounds__(IL_T, 6) void k_image_loss_fwd(int H, int W, Taps t
                 const float inv = 1.f / (B1 * B2);
                 const float S = A1 * A2 * inv;
                 const size_t o = img + (size_t)y * W + x;
+                if constexpr (!L1) { if (map_out) map_out[o] = S; }
+                // masked form (train_utils.py:64-67): the reduced quantity is sum((1 - S) * m) and the partials carry the weight m
                 float m = 1.f;
                 if (mask) {
                     m = mask[(plane * H + y) * W + x];
                     acc_s += (1.f - S) * m;
                 } else acc_s += S;
-                const float d0 = s_x[r0 + r + R5][rx + R5] - s_y[r0 + r + R5][rx + R5];
-                const float d = d0 * m;                               // (utils/loss_utils.py:21-22: |(x - y) m|; the PSNR is unmasked)
-                acc_l += fabsf(d);
-                acc_q += d0 * d0;
-                if (sign8) sign8[o] = (signed char)(d > 0.f ? 1 : (d < 0.f ? -1 : 0));
+                if constexpr (L1) {
+                    const float d0 = s_x[r0 + r + R5][rx + R5] - s_y[r0 + r + R5][rx + R5];
+                    const float d = d0 * m;                               // (utils/loss_utils.py:21-22: |(x - y) m|; the PSNR is unmasked)
+                    acc_l += fabsf(d);
+                    acc_q += d0 * d0;
+                    if (sign8) sign8[o] = (signed char)(d > 0.f ? 1 : (d < 0.f ? -1 : 0));
+                }
                 if (P1) {
-                    P1[o] = m * (2.f * mu2 * (A2 - A1) * inv - S * 2.f * mu1 * (B2 - B1) * inv);
-                    P2[o] = m * (-S / B2);
-                    P3[o] = m * (2.f * A1 * inv);
+                    P1[o] = m * (2.f * mu2 * (A2 - A1) * inv - S * 2.f * mu1 * (B2 - B1) * inv);   // dS/dmu1
+                    P2[o] = m * (-S / B2);                                                         // dS/ds11
+                    P3[o] = m * (2.f * A1 * inv);                                                  // dS/ds12
                 }
             }
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc_s += __shfl_xor(acc_s, o, 64); acc_l += __shfl_xor(acc_l, o, 64); acc_q += __shfl_xor(acc_q, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = acc_s; s_red[1][threadIdx.x >> 6] = acc_l; s_red[2][threadIdx.x >> 6] = acc_q; }
+    for (int o = 32; o > 0; o >>= 1) {
+        acc_s += __shfl_xor(acc_s, o, 64);
+        if constexpr (L1) { acc_l += __shfl_xor(acc_l, o, 64); acc_q += __shfl_xor(acc_q, o, 64); }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_red[0][threadIdx.x >> 6] = acc_s;
+        if constexpr (L1) { s_red[1][threadIdx.x >> 6] = acc_l; s_red[2][threadIdx.x >> 6] = acc_q; }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         const size_t nwg = (size_t)gridDim.y * gridDim.x * gridDim.z;
         const size_t me = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        for (int q = 0; q < 3; q++) {
+        for (int q = 0; q < NQ; q++) {
             float t_ = 0.f;
             for (int k = 0; k < IL_T / 64; k++) t_ += s_red[q][k];
             partial[q * nwg + me] = t_;
@@ -311,61 +217,83 @@ __global__ __launch_bounds__(IL_T, 6) void k_image_loss_fwd(int H, int W, Taps t
     }
 }
 
-__global__ __launch_bounds__(IL_T, 6) void k_image_loss_bwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
-                                                           const float *__restrict__ P1, const float *__restrict__ P2,
-                                                           const float *__restrict__ P3, const signed char *__restrict__ sign8,
-                                                           const float *__restrict__ mask, int mask_channels, int channels,
-                                                           const float *__restrict__ gscalar, float g_l1, float g_ssim, float *__restrict__ dX) {
+// dX = gscalar[0] g_ssim (b1 + 2 x b2 + y b3), plus gscalar[0] g_l1 sign m (L1) or add_scale[0] addend (the standalone SSIM, optional)
+template <bool L1>
+__device__ __forceinline__ void ssim_tile_bwd(int H, int W, const Taps &taps, const float *__restrict__ X, const float *__restrict__ Y,
+                                              const float *__restrict__ P1, const float *__restrict__ P2, const float *__restrict__ P3,
+                                              const signed char *__restrict__ sign8, const float *__restrict__ mask, int mask_channels,
+                                              int channels, const float *__restrict__ gscalar, float g_l1, float g_ssim,
+                                              const float *__restrict__ addend, const float *__restrict__ add_scale, float *__restrict__ dX) {
     __shared__ __attribute__((aligned(16))) float s_p[3][IL_HR][IL_XP];
     __shared__ __attribute__((aligned(16))) float s_h[3][IL_HR][IL_HP];
     const size_t img = (size_t)blockIdx.z * H * W;
     const int x0 = blockIdx.x * BW, y0 = blockIdx.y * BH;
-    for (int t = threadIdx.x; t < IL_HR * (BW + 2 * R5); t += IL_T) {
-        const int ry = t / (BW + 2 * R5), rx = t - ry * (BW + 2 * R5);
-        const int y = y0 + ry - R5, x = x0 + rx - R5;
-        const bool in = y >= 0 && y < H && x >= 0 && x < W;
-        const size_t o = img + (size_t)y * W + x;
-        s_p[0][ry][rx] = in ? P1[o] : 0.f; s_p[1][ry][rx] = in ? P2[o] : 0.f; s_p[2][ry][rx] = in ? P3[o] : 0.f;
+    il_load(H, W, img, x0, y0, s_p, P1, P2, P3);
+    if (threadIdx.x < IL_HR * IL_NS) {
+        const int ry = threadIdx.x / IL_NS, c0 = (threadIdx.x % IL_NS) * IL_HS;
+#pragma unroll
+        for (int q = 0; q < 3; q++) il_hmap(taps, &s_p[q][ry][c0], &s_h[q][ry][c0]);
     }
     __syncthreads();
-    constexpr int NS = BW / IL_HS, NV = IL_HS + 10;
-    if (threadIdx.x < IL_HR * NS) {
-        const int ry = threadIdx.x / NS, c0 = (threadIdx.x % NS) * IL_HS;
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            float v[NV];
-#pragma unroll
-            for (int k = 0; k < NV; k++) v[k] = s_p[q][ry][c0 + k];
-            il_hrow(taps, v, &s_h[q][ry][c0]);
-        }
-    }
-    __syncthreads();
-    const float gs = gscalar[0] * g_ssim, gl = gscalar[0] * g_l1;
+    const float gs = gscalar[0] * g_ssim, gl = L1 ? gscalar[0] * g_l1 : 0.f;
+    const float ga = !L1 && addend ? add_scale[0] : 0.f;
     const int rx = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * IL_VS;
     float b1[IL_VS], b2[IL_VS], b3[IL_VS];
     il_vcol(taps, &s_h[0][r0][rx], b1);
     il_vcol(taps, &s_h[1][r0][rx], b2);
     il_vcol(taps, &s_h[2][r0][rx], b3);
     const int x = x0 + rx;
-    const size_t plane = mask ? (mask_channels == 1 ? blockIdx.z / channels : blockIdx.z) : 0;
+    const size_t plane = il_mask_plane(mask, mask_channels, channels);
 #pragma unroll
     for (int r = 0; r < IL_VS; r++) {
         const int y = y0 + r0 + r;
         if (y < H && x < W) {
             const size_t o = img + (size_t)y * W + x;
-            const float m = mask ? mask[(plane * H + y) * W + x] : 1.f;
-            dX[o] = gs * (b1[r] + 2.f * X[o] * b2[r] + Y[o] * b3[r]) + gl * (float)sign8[o] * m;
+            if constexpr (L1) {
+                const float m = mask ? mask[(plane * H + y) * W + x] : 1.f;
+                dX[o] = gs * (b1[r] + 2.f * X[o] * b2[r] + Y[o] * b3[r]) + gl * (float)sign8[o] * m;
+            } else {
+                const float d = gs * (b1[r] + 2.f * X[o] * b2[r] + Y[o] * b3[r]);
+                dX[o] = addend ? d + ga * addend[o] : d;
+            }
         }
     }
+}
+
+__global__ __launch_bounds__(IL_T, 6) void k_ssim_fwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
+                                                     float *__restrict__ P1, float *__restrict__ P2, float *__restrict__ P3,
+                                                     float *__restrict__ map_out, float *__restrict__ partial,
+                                                     const float *__restrict__ mask, int mask_channels, int channels) {
+    ssim_tile_fwd<false>(H, W, taps, X, Y, P1, P2, P3, nullptr, map_out, mask, mask_channels, channels, partial);
+}
+__global__ __launch_bounds__(IL_T, 6) void k_ssim_bwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
+                                                     const float *__restrict__ P1, const float *__restrict__ P2,
+                                                     const float *__restrict__ P3, const float *__restrict__ gscalar, float inv_n,
+                                                     const float *__restrict__ addend, const float *__restrict__ add_scale,
+                                                     float *__restrict__ dX) {
+    ssim_tile_bwd<false>(H, W, taps, X, Y, P1, P2, P3, nullptr, nullptr, 1, 1, gscalar, 0.f, inv_n, addend, add_scale, dX);
+}
+__global__ __launch_bounds__(IL_T, 6) void k_image_loss_fwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
+                                                           float *__restrict__ P1, float *__restrict__ P2, float *__restrict__ P3,
+                                                           signed char *__restrict__ sign8, const float *__restrict__ mask, int mask_channels,
+                                                           int channels, float *__restrict__ partial) {
+    ssim_tile_fwd<true>(H, W, taps, X, Y, P1, P2, P3, sign8, nullptr, mask, mask_channels, channels, partial);
+}
+__global__ __launch_bounds__(IL_T, 6) void k_image_loss_bwd(int H, int W, Taps taps, const float *__restrict__ X, const float *__restrict__ Y,
+                                                           const float *__restrict__ P1, const float *__restrict__ P2,
+                                                           const float *__restrict__ P3, const signed char *__restrict__ sign8,
+                                                           const float *__restrict__ mask, int mask_channels, int channels,
+                                                           const float *__restrict__ gscalar, float g_l1, float g_ssim, float *__restrict__ dX) {
+    ssim_tile_bwd<true>(H, W, taps, X, Y, P1, P2, P3, sign8, mask, mask_channels, channels, gscalar, g_l1, g_ssim, nullptr, nullptr, dX);
 }
 
 // the second (one-workgroup) launch of the image loss: sums the workgroup partials in index order.  NOT a ticket in the kernel above:
 // a device-scope release on gfx950 writes the XCD's dirty L2 lines back, and ~6000 workgroups each fencing while all of them stream the
 // three partial-derivative images out cost 4x the kernel itself (measured 268-351 us against 75 + 4 for the two launches).
-__global__ __launch_bounds__(SSIM_THREADS) void k_image_loss_finish(size_t per_plane, int planes, int channels, int H, int W, int masked, float lam,
+__global__ __launch_bounds__(IL_T) void k_image_loss_finish(size_t per_plane, int planes, int channels, int H, int W, int masked, float lam,
                                                             float img_weight, const float *__restrict__ add, float add_weight,
                                                             float psnr_scale, const float *__restrict__ partial, float *__restrict__ out) {
-    __shared__ float s_red[SSIM_THREADS / 64];
+    __shared__ float s_red[IL_T / 64];
     const size_t nwg = per_plane * planes;
     // (ONE workgroup pulls ~135 KB of partials: 16-byte loads, four of them in flight per thread -- with 4-byte loads in a dependent
     //  `t += p[i]` loop the five sums of a 3-camera step took 12.8 us)
@@ -376,21 +304,21 @@ __global__ __launch_bounds__(SSIM_THREADS) void k_image_loss_finish(size_t per_p
         const size_t n4 = (hi - a0) >> 2;
         const float4 *p4 = reinterpret_cast<const float4 *>(p + a0);
         size_t i = threadIdx.x;
-        for (; i + 3 * SSIM_THREADS < n4; i += 4 * SSIM_THREADS) {
-            const float4 u0 = p4[i], u1 = p4[i + SSIM_THREADS], u2 = p4[i + 2 * SSIM_THREADS], u3 = p4[i + 3 * SSIM_THREADS];
+        for (; i + 3 * IL_T < n4; i += 4 * IL_T) {
+            const float4 u0 = p4[i], u1 = p4[i + IL_T], u2 = p4[i + 2 * IL_T], u3 = p4[i + 3 * IL_T];
             t += ((u0.x + u0.y) + (u0.z + u0.w)) + ((u1.x + u1.y) + (u1.z + u1.w));
             t += ((u2.x + u2.y) + (u2.z + u2.w)) + ((u3.x + u3.y) + (u3.z + u3.w));
         }
-        for (; i < n4; i += SSIM_THREADS) { const float4 u = p4[i]; t += (u.x + u.y) + (u.z + u.w); }
-        for (size_t j = lo + threadIdx.x; j < a0; j += SSIM_THREADS) t += p[j];                    // <= 3 elements in front ...
-        for (size_t j = a0 + (n4 << 2) + threadIdx.x; j < hi; j += SSIM_THREADS) t += p[j];        // ... and behind the float4 body
+        for (; i < n4; i += IL_T) { const float4 u = p4[i]; t += (u.x + u.y) + (u.z + u.w); }
+        for (size_t j = lo + threadIdx.x; j < a0; j += IL_T) t += p[j];                    // <= 3 elements in front ...
+        for (size_t j = a0 + (n4 << 2) + threadIdx.x; j < hi; j += IL_T) t += p[j];        // ... and behind the float4 body
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
         __syncthreads();
         if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = t;
         __syncthreads();
         float r = 0.f;
-        for (int k = 0; k < SSIM_THREADS / 64; k++) r += s_red[k];
+        for (int k = 0; k < IL_T / 64; k++) r += s_red[k];
         return r;
     };
     const float ssim_sum = block_sum(partial, 0, nwg);
@@ -414,8 +342,8 @@ __global__ __launch_bounds__(SSIM_THREADS) void k_image_loss_finish(size_t per_p
 }
 
 // ---- fused L1 loss: mean |a - b| and its gradient sign(a - b) / n in ONE pass (utils/loss_utils.py:20-23 is three
-// elementwise launches forward and three backward).  Deterministic: workgroup partials are summed in index order by
-// whichever workgroup finishes last (ticket counter), not with float atomics.
+// elementwise launches forward and three backward).  Deterministic: one partial per workgroup, summed in index order by
+// k_l1_finish, a second one-workgroup launch -- no ticket, no float atomics.
 constexpr int L1_BLOCKS = 256, L1_THREADS = 1024;  // one fat workgroup per CU; their partials are summed by k_l1_finish
 __global__ __launch_bounds__(L1_THREADS) void k_l1(int64_t n, const float *__restrict__ a, const float *__restrict__ b,
                                                     float inv_n, float *__restrict__ partial, float *__restrict__ grad,
@@ -705,14 +633,27 @@ __global__ __launch_bounds__(1024) void k_psnr(int64_t n, const float *__restric
 }
 }  // namespace
 
+// ---- what every launch of a tile kernel starts from: one workgroup per 64 x 16 tile and plane (the plane rides in blockIdx.z, hence
+// fewer than 65536 of them per launch) and the window's taps by value
+static dim3 tile_grid(int64_t planes, int H, int W) { return dim3(cdiv(W, BW), cdiv(H, BH), (unsigned)planes); }
+struct TileLaunch { Taps taps; dim3 grid; };
+static int tile_launch(const char *who, const float *taps11, int64_t planes, int H, int W, TileLaunch *tl) {
+    if (!(taps11 && planes >= 0 && planes < 65536 && H > 0 && W > 0)) {
+        snprintf(g_csplat_err, sizeof(g_csplat_err), "%s: bad arguments (the taps, H, W > 0, fewer than 65536 planes per launch) (%s:%d)", who,
+                 __FILE__, __LINE__);
+        return 2;
+    }
+    memcpy(tl->taps.w, taps11, sizeof(tl->taps.w));
+    tl->grid = tile_grid(planes, H, W);
+    return 0;
+}
+
 extern "C" int csplat_blur11(void *stream, int64_t n_images, int H, int W, const float *taps11, const float *in, float *out) {
-    CSPLAT_REQUIRE(n_images >= 0 && H > 0 && W > 0 && taps11 && in && out && in != out, "csplat_blur11: bad arguments");
-    CSPLAT_REQUIRE(n_images < 65536, "csplat_blur11: too many images for one launch");
+    CSPLAT_REQUIRE(in && out && in != out, "csplat_blur11: bad arguments");
+    TileLaunch tl;
+    if (int rc = tile_launch("csplat_blur11", taps11, n_images, H, W, &tl)) return rc;
     if (n_images == 0) return 0;
-    Taps t;
-    memcpy(t.w, taps11, sizeof(t.w));
-    dim3 grid(cdiv(W, BW), cdiv(H, BH), (unsigned)n_images);
-    k_blur11<<<grid, 256, 0, (hipStream_t)stream>>>(H, W, t, in, out);
+    k_blur11<<<tl.grid, IL_T, 0, (hipStream_t)stream>>>(H, W, tl.taps, in, out);
     LAUNCH_CHECK();
     return 0;
 }
@@ -746,7 +687,7 @@ __global__ __launch_bounds__(256) void k_l1_bwd(int64_t n, const signed char *__
 }
 
 static int l1_launch(void *stream, int64_t n, const float *a, const float *b, void *scratch, float *loss, float *grad,
-                     const float *mask, int64_t hw, int channels, int mask_channels, const char *who, signed char *sign8 = nullptr) {
+                     const float *mask, int64_t hw, int channels, int mask_channels, signed char *sign8 = nullptr) {
     CSPLAT_REQUIRE(n > 0 && a && b && scratch && loss, "csplat_l1: bad arguments");
     CSPLAT_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad | (uintptr_t)mask) & 3u) == 0, "csplat_l1: operands must be 4-byte aligned");
     const bool al = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad | (uintptr_t)mask) & 15u) == 0);      // else k_l1 takes its scalar form
@@ -759,26 +700,25 @@ static int l1_launch(void *stream, int64_t n, const float *a, const float *b, vo
     LAUNCH_CHECK();
     k_l1_finish<<<1, L1_BLOCKS, 0, (hipStream_t)stream>>>(grid, partial, 1.0f / (float)n, loss);
     LAUNCH_CHECK();
-    (void)who;
     return 0;
 }
 
 extern "C" int csplat_l1(void *stream, int64_t n, const float *a, const float *b, void *scratch, float *loss, float *grad) {
-    return l1_launch(stream, n, a, b, scratch, loss, grad, nullptr, 1, 1, 1, "csplat_l1");
+    return l1_launch(stream, n, a, b, scratch, loss, grad, nullptr, 1, 1, 1);
 }
 
 extern "C" int csplat_l1_masked(void *stream, int64_t n_batch, int channels, int64_t hw, const float *a, const float *b,
                                 const float *mask, int mask_channels, void *scratch, float *loss, float *grad) {
     CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && hw > 0 && mask, "csplat_l1_masked: bad arguments");
     CSPLAT_REQUIRE(mask_channels == 1 || mask_channels == channels, "csplat_l1_masked: the mask has 1 plane per image or one per channel");
-    return l1_launch(stream, n_batch * channels * hw, a, b, scratch, loss, grad, mask, hw, channels, mask_channels, "csplat_l1_masked");
+    return l1_launch(stream, n_batch * channels * hw, a, b, scratch, loss, grad, mask, hw, channels, mask_channels);
 }
 
 extern "C" int csplat_l1_signs(void *stream, int64_t n_batch, int channels, int64_t hw, const float *a, const float *b, const float *mask,
                                int mask_channels, void *scratch, float *loss, signed char *sign8) {
     CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && hw > 0 && sign8, "csplat_l1_signs: bad arguments");
     CSPLAT_REQUIRE(!mask || mask_channels == 1 || mask_channels == channels, "csplat_l1_signs: the mask has 1 plane per image or one per channel");
-    return l1_launch(stream, n_batch * channels * hw, a, b, scratch, loss, nullptr, mask, hw, channels, mask ? mask_channels : 1, "csplat_l1_signs", sign8);
+    return l1_launch(stream, n_batch * channels * hw, a, b, scratch, loss, nullptr, mask, hw, channels, mask ? mask_channels : 1, sign8);
 }
 extern "C" int csplat_l1_signs_bwd(void *stream, int64_t n_batch, int channels, int64_t hw, const signed char *sign8, const float *mask,
                                    int mask_channels, const float *g_scalar, float *out) {
@@ -902,18 +842,18 @@ extern "C" int csplat_geom_loss_bwd(void *stream, int n_views, int64_t hw, const
     return 0;
 }
 
-extern "C" size_t csplat_ssim_partial_count(int64_t n_images, int H, int W) { return (size_t)n_images * cdiv(H, BH) * cdiv(W, BW); }
+static size_t tiles_per_plane(int H, int W) { const dim3 g = tile_grid(1, H, W); return (size_t)g.x * g.y; }
+extern "C" size_t csplat_ssim_partial_count(int64_t n_images, int H, int W) { return (size_t)n_images * tiles_per_plane(H, W); }
 
 static int ssim_fwd_launch(void *stream, int64_t n_images, int H, int W, const float *taps11, const float *x, const float *y,
                            float *p1, float *p2, float *p3, float *map_out, float *partial, const float *mask, int mask_channels,
                            int channels) {
-    CSPLAT_REQUIRE(n_images >= 0 && n_images < 65536 && H > 0 && W > 0 && taps11 && x && y && partial, "csplat_ssim_fwd: bad arguments");
+    CSPLAT_REQUIRE(x && y && partial, "csplat_ssim_fwd: bad arguments");
+    TileLaunch tl;
+    if (int rc = tile_launch("csplat_ssim_fwd", taps11, n_images, H, W, &tl)) return rc;
     CSPLAT_REQUIRE((p1 != nullptr) == (p2 != nullptr) && (p1 != nullptr) == (p3 != nullptr), "csplat_ssim_fwd: all three partials or none");
     if (n_images == 0) return 0;
-    Taps t;
-    memcpy(t.w, taps11, sizeof(t.w));
-    dim3 grid(cdiv(W, BW), cdiv(H, BH), (unsigned)n_images);
-    k_ssim_fwd<<<grid, SSIM_THREADS, 0, (hipStream_t)stream>>>(H, W, t, x, y, p1, p2, p3, map_out, partial, mask, mask_channels, channels);
+    k_ssim_fwd<<<tl.grid, IL_T, 0, (hipStream_t)stream>>>(H, W, tl.taps, x, y, p1, p2, p3, map_out, partial, mask, mask_channels, channels);
     LAUNCH_CHECK();
     return 0;
 }
@@ -936,14 +876,12 @@ extern "C" int csplat_ssim_fwd_masked(void *stream, int64_t n_batch, int channel
 extern "C" int csplat_ssim_bwd(void *stream, int64_t n_images, int H, int W, const float *taps11, const float *x, const float *y,
                                const float *p1, const float *p2, const float *p3, const float *g_scalar, float inv_n,
                                const float *addend, const float *add_scale, float *dx) {
-    CSPLAT_REQUIRE(n_images >= 0 && n_images < 65536 && H > 0 && W > 0 && taps11 && x && y && p1 && p2 && p3 && g_scalar && dx,
-                   "csplat_ssim_bwd: bad arguments");
+    CSPLAT_REQUIRE(x && y && p1 && p2 && p3 && g_scalar && dx, "csplat_ssim_bwd: bad arguments");
+    TileLaunch tl;
+    if (int rc = tile_launch("csplat_ssim_bwd", taps11, n_images, H, W, &tl)) return rc;
     if (n_images == 0) return 0;
-    Taps t;
-    memcpy(t.w, taps11, sizeof(t.w));
-    dim3 grid(cdiv(W, BW), cdiv(H, BH), (unsigned)n_images);
     CSPLAT_REQUIRE((addend == nullptr) == (add_scale == nullptr), "csplat_ssim_bwd: addend and add_scale go together");
-    k_ssim_bwd<<<grid, SSIM_THREADS, 0, (hipStream_t)stream>>>(H, W, t, x, y, p1, p2, p3, g_scalar, inv_n, addend, add_scale, dx);
+    k_ssim_bwd<<<tl.grid, IL_T, 0, (hipStream_t)stream>>>(H, W, tl.taps, x, y, p1, p2, p3, g_scalar, inv_n, addend, add_scale, dx);
     LAUNCH_CHECK();
     return 0;
 }
@@ -953,39 +891,35 @@ extern "C" int csplat_ssim_bwd(void *stream, int64_t n_images, int H, int W, con
 // p1..p3 / sign8 may be NULL when no gradient will be asked for.
 extern "C" size_t csplat_image_loss_scratch_bytes(int64_t n_batch, int channels, int H, int W) {
     const size_t planes = (size_t)(n_batch > 0 ? n_batch : 1) * channels;
-    return align256(3 * planes * cdiv(H, BH) * cdiv(W, BW) * 4);      // [3][workgroups] partial sums
+    return align256(3 * planes * tiles_per_plane(H, W) * 4);      // [3][workgroups] partial sums
 }
 extern "C" int csplat_image_loss_fwd(void *stream, int64_t n_batch, int channels, int H, int W, const float *taps11, const float *x,
                                      const float *y, const float *mask, int mask_channels, float lam, float img_weight, const float *add,
                                      float add_weight, float psnr_scale, float *p1, float *p2, float *p3, signed char *sign8, void *scratch,
                                      float *out) {
-    CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && n_batch * channels < 65536 && H > 0 && W > 0 && taps11 && x && y && scratch && out,
-                   "csplat_image_loss_fwd: bad arguments");
+    CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && x && y && scratch && out, "csplat_image_loss_fwd: bad arguments");
+    TileLaunch tl;
+    if (int rc = tile_launch("csplat_image_loss_fwd", taps11, n_batch * channels, H, W, &tl)) return rc;
     CSPLAT_REQUIRE((p1 != nullptr) == (p2 != nullptr) && (p1 != nullptr) == (p3 != nullptr) && (p1 != nullptr) == (sign8 != nullptr),
                    "csplat_image_loss_fwd: the three partials and the sign bytes go together");
     CSPLAT_REQUIRE(!mask || mask_channels == 1 || mask_channels == channels, "csplat_image_loss_fwd: the mask has 1 plane per image or one per channel");
-    Taps t;
-    memcpy(t.w, taps11, sizeof(t.w));
-    dim3 grid(cdiv(W, BW), cdiv(H, BH), (unsigned)(n_batch * channels));
     float *partial = (float *)scratch;
-    k_image_loss_fwd<<<grid, IL_T, 0, (hipStream_t)stream>>>(H, W, t, x, y, p1, p2, p3, sign8, mask, mask ? mask_channels : 1, channels, partial);
+    k_image_loss_fwd<<<tl.grid, IL_T, 0, (hipStream_t)stream>>>(H, W, tl.taps, x, y, p1, p2, p3, sign8, mask, mask ? mask_channels : 1, channels, partial);
     LAUNCH_CHECK();
-    k_image_loss_finish<<<1, SSIM_THREADS, 0, (hipStream_t)stream>>>((size_t)grid.x * grid.y, (int)grid.z, channels, H, W, mask ? 1 : 0, lam, img_weight,
-                                                                     add, add_weight, psnr_scale, partial, out);
+    k_image_loss_finish<<<1, IL_T, 0, (hipStream_t)stream>>>((size_t)tl.grid.x * tl.grid.y, (int)tl.grid.z, channels, H, W, mask ? 1 : 0, lam, img_weight,
+                                                             add, add_weight, psnr_scale, partial, out);
     LAUNCH_CHECK();
     return 0;
 }
 extern "C" int csplat_image_loss_bwd(void *stream, int64_t n_batch, int channels, int H, int W, const float *taps11, const float *x,
                                      const float *y, const float *p1, const float *p2, const float *p3, const signed char *sign8,
                                      const float *mask, int mask_channels, float lam, float img_weight, const float *g_scalar, float *dx) {
-    CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && n_batch * channels < 65536 && H > 0 && W > 0 && taps11 && x && y && p1 && p2 && p3 &&
-                   sign8 && g_scalar && dx, "csplat_image_loss_bwd: bad arguments");
-    Taps t;
-    memcpy(t.w, taps11, sizeof(t.w));
-    dim3 grid(cdiv(W, BW), cdiv(H, BH), (unsigned)(n_batch * channels));
+    CSPLAT_REQUIRE(n_batch > 0 && channels > 0 && x && y && p1 && p2 && p3 && sign8 && g_scalar && dx, "csplat_image_loss_bwd: bad arguments");
+    TileLaunch tl;
+    if (int rc = tile_launch("csplat_image_loss_bwd", taps11, n_batch * channels, H, W, &tl)) return rc;
     const float inv_n = 1.0f / ((float)(n_batch * channels) * (float)H * (float)W);
-    k_image_loss_bwd<<<grid, IL_T, 0, (hipStream_t)stream>>>(H, W, t, x, y, p1, p2, p3, sign8, mask, mask ? mask_channels : 1, channels, g_scalar,
-                                                             img_weight * inv_n, -lam * img_weight * inv_n, dx);
+    k_image_loss_bwd<<<tl.grid, IL_T, 0, (hipStream_t)stream>>>(H, W, tl.taps, x, y, p1, p2, p3, sign8, mask, mask ? mask_channels : 1, channels,
+                                                                g_scalar, img_weight * inv_n, -lam * img_weight * inv_n, dx);
     LAUNCH_CHECK();
     return 0;
 }

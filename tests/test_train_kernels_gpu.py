@@ -291,6 +291,108 @@ def test_image_losses_reports_too_many_planes_as_a_miss_on_shape():
     check("image_losses 65536 planes", "d/dx", a.grad, res[0][1], res[1][1], UP / x.numel())
 
 
+# ---- the SSIM's C-ABI surface that no Python wrapper reaches: csplat_ssim_fwd_masked, map_out of csplat_ssim_fwd, addend / add_scale
+# of csplat_ssim_bwd (include/csplat.h states them), called through native.lib
+def _taps11():
+    return (C.c_float * 11)(*[float(v) for v in R.window(F32)])
+
+
+def _ssim_fwd_abi(x, y, mask=None, want_p=True, want_map=False):
+    """csplat_ssim_fwd (mask None) / csplat_ssim_fwd_masked -> (p [3,B,C,H,W] or None, map [B,C,H,W] or None, partial); every output
+    starts as NaN, so an element the kernel leaves out fails whatever looks at it"""
+    n_, dev = _lib()
+    B, Cc, H, W = x.shape
+    xc, yc, mk = cuda(x), cuda(y), cuda(mask)
+    p = torch.full((3,) + tuple(x.shape), float("nan"), device=dev) if want_p else None
+    mp = torch.full(tuple(x.shape), float("nan"), device=dev) if want_map else None
+    partial = torch.full((int(n_.lib.csplat_ssim_partial_count(B * Cc, H, W)),), float("nan"), device=dev)
+    pp = [n_.ptr(p[k]) if want_p else None for k in range(3)]
+    if mask is None:
+        n_.check(n_.lib.csplat_ssim_fwd(n_.stream_handle(dev), B * Cc, H, W, _taps11(), n_.ptr(xc), n_.ptr(yc), *pp, n_.ptr(mp),
+                                        n_.ptr(partial)), "csplat_ssim_fwd")
+    else:
+        n_.check(n_.lib.csplat_ssim_fwd_masked(n_.stream_handle(dev), B, Cc, H, W, _taps11(), n_.ptr(xc), n_.ptr(yc), n_.ptr(mk),
+                                               int(mask.shape[1]), *pp, n_.ptr(mp), n_.ptr(partial)), "csplat_ssim_fwd_masked")
+    return p, mp, partial
+
+
+def _ssim_bwd_abi(x, y, p, g, addend=None, add_scale=None):
+    """csplat_ssim_bwd with inv_n = 1 / numel -> (rc, dx)"""
+    n_, dev = _lib()
+    B, Cc, H, W = x.shape
+    xc, yc = cuda(x), cuda(y)
+    gs = torch.tensor([g], dtype=F32, device=dev)
+    dx = torch.full(tuple(x.shape), float("nan"), device=dev)
+    rc = n_.lib.csplat_ssim_bwd(n_.stream_handle(dev), B * Cc, H, W, _taps11(), n_.ptr(xc), n_.ptr(yc), n_.ptr(p[0]), n_.ptr(p[1]),
+                                n_.ptr(p[2]), n_.ptr(gs), 1.0 / x.numel(), n_.ptr(addend), n_.ptr(add_scale), n_.ptr(dx))
+    torch.cuda.synchronize()
+    return rc, dx
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("shape", R.SSIM_ABI_SHAPES)
+def test_ssim_fwd_masked_with_one_mask_plane_and_with_one_per_channel(shape):
+    """csplat_ssim_fwd_masked: sum(partial) / n is mean((1 - S) m); p1..p3 are the mask times the unmasked call's p1..p3 (one float32
+    product, so equal); csplat_ssim_bwd on them with g = -1 writes the gradient of the masked term"""
+    x, y, _ = R.image_case("uniform", shape, 0, seed=sum(shape))
+    n = x.numel()
+    p_plain, _, _ = _ssim_fwd_abi(x, y)
+    for mc in sorted({1, shape[1]}):
+        mask = R.make_mask(shape, mc, 3)
+        if shape[2] * shape[3] == 1:
+            mask.fill_(0.5)                      # (make_mask leaves the only pixel of a 1 x 1 image at 1)
+        p, _, partial = _ssim_fwd_abi(x, y, mask)
+        res = []
+        for dt in (F64, F32):
+            a = leaf(x, dt)
+            v = ((1.0 - R.ssim_map(a, y, dt)) * mask.to(dt)).mean()
+            v.backward()
+            res.append((v.detach(), a.grad))
+        where = f"{tuple(shape)} mask planes {mc}"
+        check("ssim abi masked", f"{where} value", partial.double().sum() / n, res[0][0], res[1][0], 1.0)
+        assert torch.equal(p, p_plain * cuda(mask).unsqueeze(0)), f"{where}: p1..p3 are not mask * the unmasked partials"
+        rc, dx = _ssim_bwd_abi(x, y, p, -1.0)
+        assert rc == 0
+        check("ssim abi masked d/dx", f"{where} d/dx", dx, res[0][1], res[1][1], 1.0 / n)
+
+
+@pytest.mark.parametrize("shape", R.SSIM_ABI_SHAPES)
+def test_ssim_map_out_with_and_without_the_partial_derivatives(shape):
+    """map_out of csplat_ssim_fwd is the SSIM map, the same bits whether p1..p3 are asked for or NULL; the masked entry writes the same
+    (unweighted) map"""
+    x, y, _ = R.image_case("uniform", shape, 0, seed=sum(shape))
+    _, m_with, part_with = _ssim_fwd_abi(x, y, want_p=True, want_map=True)
+    _, m_without, part_without = _ssim_fwd_abi(x, y, want_p=False, want_map=True)
+    assert torch.equal(_bits(m_with), _bits(m_without)) and torch.equal(_bits(part_with), _bits(part_without))
+    check("ssim abi map", f"{tuple(shape)} map", m_with, R.ssim_map(x, y, F64), R.ssim_map(x, y, F32), 1.0)
+    check("ssim abi map", f"{tuple(shape)} mean", part_with.double().sum() / x.numel(), R.ssim(x, y, F64), R.ssim(x, y, F32), 1.0)
+    if shape[2] * shape[3] > 1:
+        _, m_masked, _ = _ssim_fwd_abi(x, y, R.make_mask(shape, 1, 3), want_p=False, want_map=True)
+        assert torch.equal(_bits(m_masked), _bits(m_with))
+
+
+@pytest.mark.parametrize("shape", R.SSIM_ABI_SHAPES)
+def test_ssim_bwd_addend_and_add_scale_go_together(shape):
+    """csplat_ssim_bwd with addend / add_scale: dx = dx_without + add_scale[0] * addend; one of the pair without the other is refused"""
+    n_, dev = _lib()
+    x, y, _ = R.image_case("uniform", shape, 0, seed=sum(shape))
+    p, _, _ = _ssim_fwd_abi(x, y)
+    rc, dx0 = _ssim_bwd_abi(x, y, p, UP)
+    assert rc == 0
+    addend = (torch.rand(x.shape, generator=torch.Generator().manual_seed(7)) - 0.5) * (4.0 / x.numel())
+    ac, sc = cuda(addend), torch.tensor([-0.3], dtype=F32, device=dev)
+    rc, dx = _ssim_bwd_abi(x, y, p, UP, ac, sc)
+    assert rc == 0
+    want = [dx0.cpu().to(dt) + sc.cpu().to(dt) * addend.to(dt) for dt in (F64, F32)]
+    check("ssim abi addend", f"{tuple(shape)} d/dx", dx, want[0], want[1], 1e-30)
+    for a_, s_ in ((ac, None), (None, sc)):
+        rc, _ = _ssim_bwd_abi(x, y, p, UP, a_, s_)
+        assert rc == 2 and b"addend and add_scale go together" in n_.lib.csplat_last_error()
+
+
 @pytest.mark.parametrize("n", R.L1_SIZES)
 def test_l1_sizes_around_the_four_in_flight_loop(n):
     x, y, _ = R.image_case("saturated" if n > 100 else "uniform", (1, 1, 1, n), 0, seed=n % 97)

@@ -297,6 +297,9 @@ IMAGE_LOSS_CASES = [("uniform", (3, 3, 33, 129), 0, False), ("uniform", (4, 3, 8
                     ("equal", (1, 3, 5, 64), 0, False), ("equal", (3, 3, 15, 65), 3, True), ("equal", (1, 3, 1600, 1300), 0, False),
                     ("dark", (1, 1, 33, 65), 1, False), ("dark", (3, 1, 5, 3), 0, True), ("dark", (4, 3, 801, 803), 3, False),
                     ("quantised", (3, 3, 33, 129), 1, True), ("quantised", (1, 3, 1600, 1300), 1, False), ("quantised", (4, 3, 801, 803), 0, False)]
+# the C-ABI surface of the SSIM that no Python wrapper calls (csplat_ssim_fwd_masked, map_out, addend): a single pixel, narrower and shorter
+# than the window, one tile minus a column, a second tile row of one line, 3 x 2 ragged tiles on 9 planes
+SSIM_ABI_SHAPES = [(1, 1, 1, 1), (3, 1, 5, 3), (1, 3, 16, 63), (1, 1, 17, 64), (3, 3, 17, 129)]
 L1_SIZES = [1, 3, 4, 5, 4097, 3_145_728, 3_145_732, 7_680_000, 7_680_003]
 L1_MASKED = [((4, 3, 800, 800), 1), ((4, 3, 800, 800), 3), ((4, 3, 801, 803), 1), ((4, 3, 801, 803), 3), ((3, 3, 37, 53), 1)]
 L1_SLICE = ((3, 3, 37, 53), 1)                  # l1_loss(img[i], gt[i]): 3 * 37 * 53 = 5883 floats per image, not a multiple of 4
