@@ -1,9 +1,12 @@
 """Autograd wrappers around the csplat_gnn_* C-ABI entry points (include/csplat.h): the gather / concat /
 scatter-add that torch_geometric's MessagePassing.propagate performs for InteractionNetwork
-(/root/reference/meshnet/graph_network.py:136,173-174,197).  GPU only; no fallback."""
+(/root/reference/meshnet/graph_network.py:136,173-174,197).  GPU only; no fallback.  Every node is once_differentiable: a backward
+pass writes kernel results into fresh buffers, so differentiating it again raises (SplitKLinear in its torch branch too: one node, one
+behaviour).  Operands an entry point reads as 16-byte vectors go through _f32a."""
 import weakref
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from csplat import native as _n
 
@@ -143,6 +146,7 @@ class EdgeCombine(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
         g = _f32a(g)
@@ -171,6 +175,7 @@ class SegmentSum(torch.autograd.Function):
         return segment_sum_rows(msg, csr.rowptr["dst"], csr.perm["dst"], csr.N)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         return gather_rows(g, ctx.csr.ei[1]), None
 
@@ -242,6 +247,7 @@ class RowsDot(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         h, weight = ctx.saved_tensors
         g = _f32(g)
@@ -260,6 +266,7 @@ class SimHidden(torch.autograd.Function):
         return saved[3]
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         return (None,) + _sim_hidden_bwd(*ctx.saved_tensors, g)
 
@@ -279,6 +286,7 @@ class SimResidual(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         e, W2, h1, h2, Wo = ctx.saved_tensors
         g = _f32(g)
@@ -337,7 +345,7 @@ def _weight_layout(weight):
         return w, int(w.stride(0)), 0
     if w.stride(0) == 1 and w.stride(1) >= 128 and w.data_ptr() % 16 == 0:
         return w, int(w.stride(1)), 1
-    return w.contiguous(), 128, 0
+    return _f32a(w), 128, 0          # (contiguous and misaligned included: the kernel reads W as 16-byte vectors)
 
 
 _UNIT_LN = {}
@@ -364,7 +372,7 @@ def linear128(A, weight, bias=None, alpha=1.0, relu=False, gather=None, layer_no
     is recorded: callers use it under torch.no_grad() or inside an autograd Function."""
     _n.require_cuda(A)
     assert A.dtype == torch.float32 and A.dim() == 2 and A.shape[1] == 128 and tuple(weight.shape) == (128, 128)
-    A = A.contiguous()
+    A = _f32a(A)
     weight, ldw, wt = _weight_layout(weight)
     M = A.shape[0]
     out = torch.empty_like(A) if out is None else out
@@ -377,7 +385,7 @@ def linear128(A, weight, bias=None, alpha=1.0, relu=False, gather=None, layer_no
     eps = 0.0
     if layer_norm is not None:
         assert tuple(layer_norm.normalized_shape) == (128,) and layer_norm.elementwise_affine
-        g, b, eps = layer_norm.weight.detach().contiguous(), layer_norm.bias.detach().contiguous(), float(layer_norm.eps)
+        g, b, eps = _vec(layer_norm.weight), _vec(layer_norm.bias), float(layer_norm.eps)
     bias = None if bias is None else _f32a(bias.detach())
     add_pre = None if add_pre is None else _f32a(add_pre)
     add_post = None if add_post is None else _f32a(add_post)
@@ -623,12 +631,13 @@ class LayerNorm128(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        x, gamma, beta = _f32(x), _f32(gamma), _f32(beta)
+        x, gamma, beta = _f32a(x), _f32a(gamma), _f32a(beta)       # (csplat_ln128_fwd takes 16-byte rows, as csplat_ln128_bwd does)
         y, stats = ln128_fwd(x, gamma, beta, eps)
         ctx.save_for_backward(x, stats, gamma)
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, stats, gamma = ctx.saved_tensors
         dx, dgamma, dbeta, _ = ln128_bwd(_f32(g), x, stats, gamma)
@@ -659,7 +668,7 @@ def relu_mask_bias128(g, out):
 def dw128(g, x, bias=False, x_relu=False):
     """g^T @ x for [M, 128] fp32 rows -> [128, 128] (csplat_dw128: fp32 MFMA on the row-major operands, deterministic split over rows);
     bias=True: (dW, column sums of g); x_relu=True: max(x, 0) in place of x"""
-    g, x = _f32(g), _f32(x)
+    g, x = _f32a(g), _f32a(x)
     M = g.shape[0]
     dW = torch.empty(128, 128, dtype=torch.float32, device=g.device)
     db = torch.empty(128, dtype=torch.float32, device=g.device) if bias else None
@@ -700,6 +709,7 @@ class SplitKLinear(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, weight, out = ctx.saved_tensors
         g = g.contiguous()
@@ -751,7 +761,7 @@ class EdgeTailAggregate(torch.autograd.Function):
     def forward(ctx, a0, csr, eps, a0_relu, *wb):
         ctx.set_materialize_grads(False)
         k = len(wb) // 2
-        acts = [_f32(a0)]
+        acts = [_f32a(a0)]
         for i in range(k - 1):
             acts.append(linear128(acts[-1], wb[2 * i], wb[2 * i + 1], relu=True))
         E = acts[0].shape[0]
@@ -764,6 +774,7 @@ class EdgeTailAggregate(torch.autograd.Function):
         return S
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_S):
         k, csr = ctx.k, ctx.csr
         saved = ctx.saved_tensors
@@ -814,6 +825,7 @@ class EdgeFirstLayer(torch.autograd.Function):
         return a0, e.view_as(e)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, g_next):
         e, weight = ctx.saved_tensors
         dxa = dxb = None
@@ -868,6 +880,7 @@ class EdgeLatentLinear(torch.autograd.Function):
         return linear128(e, weight, alpha=ctx.scale), e.view_as(e)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, g_next):
         e, weight = ctx.saved_tensors
         return (*_edge_latent_bwd(ctx, e, weight, None if g is None else g.contiguous(), g_next), None)

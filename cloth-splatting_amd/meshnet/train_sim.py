@@ -23,6 +23,7 @@ import types
 import weakref
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from csplat import native as _n
 from .model_utils import Normalizer, get_velocity_noise
@@ -95,6 +96,7 @@ class UpdatePrediction(torch.autograd.Function):
         return hist, edge_feat, new_pos
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, _g_hist, g_edge, g_pos):
         edge_feat, old_actions, actions = ctx.saved_tensors
         want_pred, want_init = ctx.needs_input_grad[2], ctx.needs_input_grad[3]

@@ -10,8 +10,10 @@ gradient, every differentiable output weighted with fixed dense random weights, 
 into +0).  A clause that cannot be bit-equal for a stated reason (a strided input that leaves the HIP path through a
 counted "layout" fallback) is compared through `Case.bar`, the node's own fp64 bar rule, which returns error / bar.  A clause returns
 what it observed -- "equal bits", "within bar (ratio)", "raises", "refuses" -- and raises ContractViolation otherwise; `Case.na` holds
-the clauses that do not apply to a node, with the reason.  tests/test_autograd_contract_cpu.py runs the harness on toy nodes that each
-break one clause; tests/test_autograd_contract_gpu.py runs it on the HIP nodes."""
+the clauses that do not apply to a node, with the reason.  C1 hands every input as a column slice and as a transpose; `Case.kinds` may
+add "offset", a CONTIGUOUS view that starts one float past a 16-byte boundary (what a kernel's 16-byte accesses cannot read: the node
+copies it or refuses it in forward, never in backward).  tests/test_autograd_contract_cpu.py runs the harness on toy nodes that each
+break one clause; tests/test_autograd_contract_gpu.py and tests/test_autograd_contract_meshnet_gpu.py run it on the HIP nodes."""
 import contextlib
 import itertools
 from dataclasses import dataclass, field
@@ -54,6 +56,8 @@ class Case:
     #                                                   node takes other kernels for a subset of its outputs (C5; None: bits must be equal)
     reorder: Optional[Callable] = None                # reorder(got, plain) -> error / bound, for a composed torch branch whose reduction
     #                                                   runs over the strided memory in another order (C1; None: bits must be equal)
+    kinds: tuple = ("columns", "transposed")          # the forms C1 hands every input in; "offset" (opt-in): a CONTIGUOUS view that starts
+    #                                                   one float past a 16-byte boundary -- what a kernel's float4 access cannot read
 
 
 @dataclass
@@ -173,7 +177,11 @@ def plain(case):
 def _strided(values, kind):
     """(base leaf, view of it with `values`, mask of the viewed elements in the base)"""
     v = values.detach()
-    if v.dim() == 0:                                   # (a scalar has no stride: an element inside a larger buffer)
+    if kind == "offset":                               # contiguous, and 4 bytes past a 16-byte boundary: a slice of a flat buffer
+        n = v.numel()
+        base = torch.zeros(n + 1, dtype=v.dtype, device=v.device)
+        pick = lambda b: b[1:1 + n].view(v.shape)  # noqa: E731
+    elif v.dim() == 0:                                 # (a scalar has no stride: an element inside a larger buffer)
         base = torch.zeros(3, dtype=v.dtype, device=v.device)
         pick = lambda b: b[1]  # noqa: E731
     elif v.dim() == 1:                                 # a column of a [n, 2] buffer
@@ -188,6 +196,8 @@ def _strided(values, kind):
     pick(base).copy_(v)
     base = base.clone().requires_grad_()
     view = pick(base)
+    if kind == "offset":
+        assert view.is_contiguous() and view.data_ptr() % 16 == 4, (view.is_contiguous(), view.data_ptr() % 16)
     mask = torch.zeros_like(base, dtype=torch.bool)
     pick(mask).fill_(True)
     return base, view, mask, pick
@@ -195,7 +205,7 @@ def _strided(values, kind):
 
 def c1(case, ref):
     verdicts = []
-    for name, kind in itertools.product(case.diff, ("columns", "transposed")):
+    for name, kind in itertools.product(case.diff, case.kinds):
         leaves = leaves_of(case)
         base, view, mask, pick = _strided(case.diff[name], kind)
         leaves[name] = view
@@ -219,7 +229,8 @@ def c1(case, ref):
         _require(base.grad is not None, "C1", case, f"{name} as a {kind} view: its base leaf received no gradient")
         _require(not bool(base.grad[~mask].ne(0).any()), "C1", case, f"{name} as a {kind} view: a gradient outside the viewed elements")
         got.grads[name] = pick(base.grad).detach().clone().contiguous()
-        if not moved and case.reorder is not None and not all(same(a, b) for a, b in zip(got.outs, ref.outs)):
+        # (reorder speaks of strided memory: a contiguous view, the "offset" kind, stays held to the plain form's bits)
+        if not moved and case.reorder is not None and not view.is_contiguous() and not all(same(a, b) for a, b in zip(got.outs, ref.outs)):
             verdicts.append(f"within bar ({case.reorder(got, ref):.2f})")
         elif not moved:
             _same_all("C1", case, f"{name} as a {kind} view", got, ref)

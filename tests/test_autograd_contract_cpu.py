@@ -41,7 +41,9 @@ def toy(flaw=None, twice=False):
          constant    needs_input_grad is ignored and the constant m gets a gradient
          stride0     the upstream gradient is read through its pointer as if it were dense (in bounds: the values of other elements)
          stash       the inputs are kept on ctx, not through save_for_backward
-         detached    not once_differentiable, and the result carries no graph"""
+         detached    not once_differentiable, and the result carries no graph
+         misaligned  `a` is read as 16-byte vectors whatever its address: a contiguous view that starts one float past a 16-byte
+                     boundary gets another gradient (seen by C1 only under the opt-in kind "offset": it is not in FLAWS)"""
     def backward(ctx, gy, gz):
         if flaw == "stash":
             a, b, m = ctx.stash
@@ -63,6 +65,8 @@ def toy(flaw=None, twice=False):
             ga, gb = (gz if ga is None else ga + gz), (-gz if gb is None else gb - gz)
         if flaw == "detached":
             ga, gb = ga.detach(), gb.detach()
+        if flaw == "misaligned" and ctx.misaligned:
+            ga = ga.roll(1, -1)       # (the elements a vector load at the boundary below the address would pair up)
         if flaw != "constant":
             ga, gb = (ga if ctx.needs_input_grad[0] else None), (gb if ctx.needs_input_grad[1] else None)
         return ga, gb, gm
@@ -72,6 +76,7 @@ def toy(flaw=None, twice=False):
         def forward(ctx, a, b, m):
             ctx.set_materialize_grads(False)
             y, z = a * b * m, a - b
+            ctx.misaligned = a.contiguous().data_ptr() % 16 != 0      # (a strided view is copied, as a wrapper's .contiguous() does)
             if flaw == "contiguous":
                 a, b = a.contiguous(), b.contiguous()
                 if a.requires_grad or b.requires_grad:
@@ -111,14 +116,17 @@ GEN = torch.Generator().manual_seed(5)
 MASK = (torch.rand(6, 5, generator=GEN) > 0.3).float()
 
 
-def toy_case(flaw=None, twice=False):
+OFFSET = ("columns", "transposed", "offset")
+
+
+def toy_case(flaw=None, twice=False, kinds=None):
     gen = torch.Generator().manual_seed(11)
     fn = toy(flaw, twice)
     diff, const = dict(a=torch.randn(6, 5, generator=gen), b=torch.randn(6, 5, generator=gen)), dict(m=MASK)
     if flaw == "contiguous":          # (as l1_loss(render, gt): the second operand is a constant)
         const["b"] = diff.pop("b")
     return ac.Case(name=f"toy {flaw}", call=lambda t: fn.apply(t["a"], t["b"], t["m"]), diff=diff, const=const, outputs=(0, 1),
-                   second=_second if twice else None)
+                   second=_second if twice else None, **({} if kinds is None else dict(kinds=kinds)))
 
 
 def outcome(case, clause):
@@ -155,6 +163,30 @@ def test_the_violations_say_what_was_seen():
             ac.run_clause(toy_case(flaw), FLAWS[flaw])
     with pytest.raises(ValueError, match="not enough values to unpack"):        # the crash the issue reports for l1_loss of a cropped render
         ac.run_clause(toy_case("contiguous"), "C1")
+
+
+@pytest.mark.parametrize("clause", ac.CLAUSES)
+def test_the_misaligned_node_fails_c1_under_the_offset_kind_only(clause):
+    """kinds = (..., "offset") hands every input as a contiguous view 4 bytes past a 16-byte boundary: the toy that reads `a` as 16-byte
+    vectors fails C1 there and nowhere else, and passes C1 under the default kinds; a correct node passes with the kind switched on"""
+    verdict, what = outcome(toy_case("misaligned", kinds=OFFSET), clause)
+    assert verdict == ("fails" if clause == "C1" else "passes"), f"toy misaligned, {clause}: {what}"
+    if clause == "C1":
+        assert "a as a offset view: d/da differs from the plain form" in what, what
+        assert toy_case("misaligned").kinds == ("columns", "transposed")          # (the default: today's two forms)
+        assert outcome(toy_case("misaligned"), "C1") == ("passes", ac.EQUAL)
+        for twice in (False, True):
+            assert outcome(toy_case(None, twice, kinds=OFFSET), "C1") == ("passes", ac.EQUAL)
+
+
+def test_the_offset_kind_is_a_contiguous_view_four_bytes_past_a_16_byte_boundary():
+    """every rank the harness takes (a scalar, a vector, rows): the view, its base leaf and the mask of the viewed elements"""
+    for shape in ((), (7,), (6, 5), (2, 3, 4)):
+        v = torch.arange(1, 1 + max(1, int(torch.tensor(shape).prod())) if shape else 2, dtype=torch.float32).reshape(shape)
+        base, view, mask, pick = ac._strided(v, "offset")
+        assert base.is_leaf and base.requires_grad and base.dim() == 1 and base.data_ptr() % 16 == 0
+        assert view.is_contiguous() and view.data_ptr() % 16 == 4 and view.shape == v.shape and torch.equal(view.detach(), v)
+        assert int(mask.sum()) == v.numel() and not bool(mask[0]) and torch.equal(pick(base).detach(), v)
 
 
 def test_a_refusal_is_held_to_its_inputs_and_its_message():

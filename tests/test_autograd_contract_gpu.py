@@ -5,6 +5,7 @@ leaves, every differentiable output weighted, one backward), and test_plain_form
 fp64 restatement under the bar rule of the node's own test file (imported, not restated).  Nodes whose backward sums with float atomics
 run in their reproducible form: the rasterizer under debug flag 256, the cloth regularisers with the edge CSR, the mesh transform with
 its incidence CSR.  The rasterizer's per-Gaussian inputs keep their refusal of strided tensors under STRICT ("refuses").
+The nodes of meshnet/graph_ops.py, UpdatePrediction and _Length: tests/test_autograd_contract_meshnet_gpu.py (C1 with the "offset" kind too).
 
 What the table showed on an MI355X when this file was written ("equal bits" = eq; wall time of the 225 tests: 7 s; the slowest
 pairs 0.7 s and 0.6 s -- C5 of gaussian_step_inputs, 510 subsets of its 9 outputs, and of raster batch V=2 features, 254 of its 8):
