@@ -15,6 +15,12 @@ from . import rotations as rot
 from .native import require_cuda
 
 
+def corner_scratch_floats(T, P):
+    """floats of the corner scratch of csplat_mesh_transform_bwd_views.  include/csplat.h, at csplat_mesh_transform_fwd_views: "with
+    vertex_rowptr [V+1] / vertex_corners [3P] ... and corner_scratch (T*P*9 floats, contents irrelevant) they are gathered in that fixed order"."""
+    return T * P * 9
+
+
 class MeshTransform(torch.autograd.Function):
     """(deformed vertices, face_bary, _rotation) -> (means3D, rotations): one HIP kernel each way
     (csplat_mesh_transform_fwd_views / _bwd_views, include/csplat.h).  vertices [V,3] -> ([P,3], [P,4]), or the cameras of a
@@ -45,7 +51,7 @@ class MeshTransform(torch.autograd.Function):
         sinks = getattr(ctx, "sinks", (None, None))
         d_v = torch.empty_like(vertices)
         d_b, d_r = _n.grad_out(sinks[0], bary.shape, bary.device), _n.grad_out(sinks[1], rotation.shape, rotation.device)
-        scratch = None if rowptr is None else torch.empty(max(T * P * 9, 1), dtype=torch.float32, device=vertices.device)
+        scratch = None if rowptr is None else torch.empty(max(corner_scratch_floats(T, P), 1), dtype=torch.float32, device=vertices.device)
         g_xyz = None if g_xyz is None else g_xyz.contiguous().float()
         g_quat = None if g_quat is None else g_quat.contiguous().float()
         with _n.on_device(vertices.device):

@@ -14,6 +14,12 @@ import torch
 from csplat import native as _n
 
 
+def refine_scratch_floats(N):
+    """floats of the scratch of csplat_gnn_edge_length_refine.  include/csplat.h, at csplat_gnn_edge_length_refine: "scratch = 9 N floats,
+    contents irrelevant" (the second velocity buffer and the two Adam moments of the double-buffered iteration)."""
+    return 9 * N
+
+
 def edge_features(pos, edge_index):
     """[E, 4] = (pos[row] - pos[col], norm), row / col = edge_index[0] / [1] (PyG Cartesian + Distance, norm=False).  The sign is the
     opposite of meshnet.data_utils.compute_edge_features (the reference's own: pos[edge_index[1]] - pos[edge_index[0]])."""
@@ -46,7 +52,7 @@ def refine_edge_lengths(pos, v, edge_index, rest_len, grasped_particle=None, ite
         if w is None and grasped_particle is not None and E > 0:
             w = torch.ones(E, dtype=torch.float32, device=dev)
             w[grasped_particle] = 0.0
-        scratch = torch.empty(9 * max(N, 1), dtype=torch.float32, device=dev)
+        scratch = torch.empty(refine_scratch_floats(max(N, 1)), dtype=torch.float32, device=dev)
         rl = rest_len.to(device=dev, dtype=torch.float32).contiguous()
         p_ = pos.contiguous()
         _n.launch("csplat_gnn_edge_length_refine", dev, N, E, _n.ptr(p_), _n.ptr(out), _n.ptr(csr.ei), _n.ptr(rl), _n.ptr(w),

@@ -342,7 +342,7 @@ int csplat_visibility_views(int V, const csplat_view *views, const csplat_visibi
 /* Backward: K7 compositing backward, K8 per-Gaussian backward.
  * out_color is the forward's colour image; dL_dpix[3][H][W] its gradient.  The depth image's gradient is taken by
  * csplat_backward_depth below.
- * scratch: device buffer of csplat_backward_scratch_bytes(P, R) bytes: one 64-byte-aligned accumulation record per Gaussian (9 floats
+ * scratch: device buffer of csplat_backward_scratch_bytes(P, R) bytes, no initial state: one 64-byte-aligned accumulation record per Gaussian (9 floats
  * used).  ABI 3: K7 adds one 36-byte partial per (list entry, 4x4 pixel BLOCK that blended it) -- the nine lanes that hold the row sums
  * issue one float-atomic request to the Gaussian's record; K8 consumes the records.  In the bit-reproducible mode (csplat_debug_flags
  * bit 8) the buffer also holds one stored 9-float record per (list entry, block), summed per Gaussian in emission order.
@@ -362,7 +362,7 @@ int csplat_backward(void *stream, int P, int D, int M, int R, const float *bg, i
  * rasterizer that the reference pins).  Its adjoint adds g (T_i z_i - D_behind_i / (1 - alpha_i)) to dL/dalpha_i (reaching means2D,
  * conic / cov3D / scale / rotation and opacity as the colour term does) and sum_pix g T_i alpha_i (view[2], view[6], view[10]) to
  * dL/dmean3D_i.  Launches: a prepass of per-(segment, pixel) depth partials, the depth variant of K7, the depth variant of K8.
- * scratch: csplat_backward_depth_scratch_bytes(P, R, W, H) bytes. */
+ * scratch: csplat_backward_depth_scratch_bytes(P, R, W, H) bytes, no initial state. */
 int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
                           const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
                           const float *rotations, const float *cov3D_precomp, const float *view, const float *proj,
@@ -374,7 +374,7 @@ int csplat_backward_depth(void *stream, int P, int D, int M, int R, const float 
 /* distCUDA2: out[i] = mean of squared distances from point i to its 3 nearest other points. */
 int csplat_dist2(void *stream, int P, const float *xyz, float *out);
 /* the same result (bit for bit) in O(P * pruned candidates): Morton order + bounding-box pruning as the upstream extension
- * does; temp: csplat_dist2_temp_bytes(P) bytes of device memory. */
+ * does; temp: csplat_dist2_temp_bytes(P) bytes of device memory, no initial state. */
 size_t csplat_dist2_temp_bytes(int P);
 int csplat_dist2_ws(void *stream, int P, const float *xyz, float *out, void *temp);
 
@@ -384,7 +384,7 @@ int csplat_dist2_ws(void *stream, int P, const float *xyz, float *out, void *tem
  * idx = -1.  d2 = dx*dx + dy*dy + dz*dz with d = candidate - query, FP contraction off (the arithmetic of csplat_dist2: for
  * K = 3, (d2[0] + d2[1] + d2[2]) / 3.0f is bit-identical to it).  1 <= K <= CSPLAT_KNN_MAX_K; P = 0 is a no-op.  Indices are
  * the caller's.  csplat_knn is the brute-force form, csplat_knn_ws the Morton-order + bounding-box form (the same bits and the
- * same indices; temp: csplat_knn_temp_bytes(P, K) bytes of device memory).  Added exports: CSPLAT_ABI_VERSION is unchanged. */
+ * same indices; temp: csplat_knn_temp_bytes(P, K) bytes of device memory, no initial state).  Added exports: CSPLAT_ABI_VERSION is unchanged. */
 #define CSPLAT_KNN_MAX_K 32
 int csplat_knn(void *stream, int P, int K, const float *xyz, float *out_d2, int32_t *out_idx);
 size_t csplat_knn_temp_bytes(int P, int K);
@@ -403,7 +403,7 @@ int csplat_fps(void *stream, int N, int S, const float *xyz, int start, float *m
  * NULL).  Negative sizes, a K outside the range and NULL with non-zero sizes are errors whose text names the entry point.
  * csplat_knn_query is the brute-force form; csplat_knn_query_ws orders the points along a Morton curve, prunes by the bounding
  * boxes of 1024-point runs and orders the queries along the same curve (clamped to the points' bounding box), temp:
- * csplat_knn_query_temp_bytes(Q, N, K) bytes of device memory.  Both forms return the same bits and the same indices for
+ * csplat_knn_query_temp_bytes(Q, N, K) bytes of device memory, no initial state.  Both forms return the same bits and the same indices for
  * every input.  Added exports: CSPLAT_ABI_VERSION is unchanged. */
 int csplat_knn_query(void *stream, int Q, int N, int K, const float *queries, const float *points, float *out_d2, int32_t *out_idx);
 size_t csplat_knn_query_temp_bytes(int Q, int N, int K);
@@ -418,7 +418,7 @@ int csplat_knn_query_ws(void *stream, int Q, int N, int K, const float *queries,
  * hipGraph).  dL_dqueries[i] = g (2/Q) w_i (q_i - p_idx[i]); dL_dpoints[j] = - the sum of the same terms over the queries with
  * idx[i] = j, in ascending i (stable sort of (idx, i), one lane sums a run: no float atomics, the result is reproducible bit
  * for bit); every row of dL_dpoints is written, exact zeros for a point nobody selected.  Either output may be NULL.
- * temp: csplat_chamfer_bwd_temp_bytes(Q, N) bytes of device memory (needed for dL_dpoints only).  Q >= 1, N >= 1. */
+ * temp: csplat_chamfer_bwd_temp_bytes(Q, N) bytes of device memory, no initial state (needed for dL_dpoints only).  Q >= 1, N >= 1. */
 int csplat_chamfer_fwd(void *stream, int Q, const float *d2, float max_sq_dist, float *loss);
 size_t csplat_chamfer_bwd_temp_bytes(int Q, int N);
 int csplat_chamfer_bwd(void *stream, int Q, int N, const float *queries, const float *points, const float *d2, const int32_t *idx,
@@ -440,7 +440,7 @@ int csplat_chamfer_bwd(void *stream, int Q, int N, const float *queries, const f
  * d0 = sqrt(d2) and w = exp(-lambda_w d2) (exponent and exp in fp64, rounded once); with d2 == NULL d0 / w are the caller's.
  * Always: the REVERSE lists -- rev_offsets [N+1], rev_entries [N K]: rev_entries[rev_offsets[j] .. rev_offsets[j+1]) are the
  * pair numbers i K + k with idx[i,k] == j in ascending order (integer counts + csplat_scan, stable csplat_sort_pairs).
- * temp: csplat_knn_regs_graph_temp_bytes(N, K) bytes, 16-byte aligned, as rev_offsets.
+ * temp: csplat_knn_regs_graph_temp_bytes(N, K) bytes, no initial state, 16-byte aligned, as rev_offsets.
  *
  * csplat_knn_regs_fwd: ONE kernel launch; out4 = (L_iso, L_spring, L_rigid, L) on the device.  rotations == NULL: L_rigid = 0
  * and w is not read.  The sums run in fp64 in a fixed order (per-workgroup partials over contiguous pair ranges, joined by
@@ -493,7 +493,7 @@ int csplat_gather_words(void *stream, int n, const void *const *src, const int *
 /* Capacity-based densify / prune: replaces the boolean-mask indexing / torch.cat re-creation of every
  * parameter and Adam moment in /root/reference/scene_reconstruction/gaussian_model.py:266-341 and gaussian_mesh.py:336-431.
  *   csplat_mask_to_map: map[i] = base + (number of set mask bytes before i) where mask[i] != 0, else -1; *count_dev = number of
- *                       set bytes (device int32).  Stable.  temp: csplat_mask_to_map_temp_bytes(n) bytes.
+ *                       set bytes (device int32).  Stable.  temp: csplat_mask_to_map_temp_bytes(n) bytes, no initial state.
  *   csplat_rows_scatter: for every tensor t and source row i with map[i] >= 0: dst[t][map[i]] = src[t][i] (row_bytes[t] bytes,
  *                       a multiple of 4); src[t] == NULL writes zeros (fresh Adam moments of appended rows).  ONE launch for up
  *                       to CSPLAT_ROWS_MAX_TENSORS tensors.  Source and destination rows must not overlap (ping-pong buffers
@@ -557,7 +557,7 @@ int csplat_project_points(void *stream, int64_t n, const float *full_proj, int W
 
 /* psnr of /root/reference/utils/image_utils.py:19-21 per image: out[i] = 20 log10(1 / sqrt(mean((a_i - b_i)^2))) over the
  * n_per_image values (channels x pixels) of image i; a, b [n_images][n_per_image].  One launch; fixed summation order.
- * scratch: csplat_psnr_scratch_bytes(n_images) bytes, not shared between concurrent calls. */
+ * scratch: csplat_psnr_scratch_bytes(n_images) bytes, no initial state (the entry clears its tickets on the stream), not shared between concurrent calls. */
 size_t csplat_psnr_scratch_bytes(int64_t n_images);
 int csplat_psnr(void *stream, int64_t n_images, int64_t n_per_image, const float *a, const float *b, void *scratch, float *out);
 
@@ -808,7 +808,7 @@ int csplat_plan_refit_sample(void *stream, int B, int T, int K, float *actions, 
  * *count_dev (device int32) = the number of selected pixels -- the FULL count, also when it exceeds cap; rows beyond cap are not written.
  * A stable compaction: selection bytes, csplat_mask_to_map, then a second pass that computes a selected pixel's point into its row.  Both
  * passes read a view's pixels row-wise, 16 bytes a lane where the view's plane allows it and scalar before and behind (odd H * W); the
- * view's 4 + 12 camera floats are uniform per workgroup.  temp: csplat_obs_unproject_temp_bytes(V, H, W) bytes of device memory.
+ * view's 4 + 12 camera floats are uniform per workgroup.  temp: csplat_obs_unproject_temp_bytes(V, H, W) bytes of device memory, no initial state.
  * Errors besides the common ones: stride < 1, kind not 0 or 1, a NaN max_depth, cap < 0 or >= 2^31, NULL points / source with cap > 0.
  *
  * csplat_obs_voxel: M points [M][3] (0 <= M < 2^31) on a grid of cubic cells of edge voxel (finite, > 0) from `origin` (DEVICE float [3];
@@ -822,7 +822,7 @@ int csplat_plan_refit_sample(void *stream, int B, int T, int K, float *actions, 
  *   count[q] (int32), inverse[i] (int32) = the voxel of point i, *n_voxels (device int32) = K
  * centroid and count have M rows of capacity (K <= M is not known to the host); rows from K on are not written.  Built on
  * csplat_sort_pairs_u64 (stable, the point index as value), a head-flag csplat_scan_u32 and a segment reduction.  M == 0 zeroes the two
- * counters and returns.  temp: csplat_obs_voxel_temp_bytes(M) bytes of device memory.
+ * counters and returns.  temp: csplat_obs_voxel_temp_bytes(M) bytes of device memory, no initial state.
  *
  * csplat_obs_mark: idx [Q][K] (int32), d2 [Q][K] as csplat_knn_query returns them (K >= 1, Q * K < 2^31): flags[n] = 1 (uint8, N of them)
  * iff some entry has idx == n and (max_sq_dist < 0 or d2 <= max_sq_dist), else 0.  The entry zeroes flags on the stream, then every
@@ -1020,7 +1020,7 @@ int csplat_mesh_transform_bwd(void *stream, int P, int V, const int64_t *face_ve
  * [T][P][3] / g_quat [T][P][4] (either may be NULL) and returns d_vertices [T][V][3] and d_bary / d_rotation summed over the
  * cameras in camera order.  Vertex gradients: with vertex_rowptr [V+1] / vertex_corners [3P] (int32; the (Gaussian, corner)
  * pairs incident to each vertex as 3 * gaussian + corner, grouped by vertex: a stable sort of face_vertex_ids) and
- * corner_scratch (T*P*9 floats) they are gathered in that fixed order -- deterministic, no atomics; with NULLs they are
+ * corner_scratch (T*P*9 floats, contents irrelevant) they are gathered in that fixed order -- deterministic, no atomics; with NULLs they are
  * scattered with float atomics. */
 int csplat_mesh_transform_fwd_views(void *stream, int T, int P, int V, const int64_t *face_vertex_ids, const float *vertices,
                                     const float *bary, const float *rotation, const void *rest, float *out_xyz, float *out_quat);
@@ -1051,7 +1051,7 @@ int csplat_prof_read(int kernel_class, double *ms_total, int64_t *launches);
  * Rows of L floats move as float4 (16 B per lane) when L % 4 == 0, as scalars otherwise: with such an L every float operand of
  * csplat_gnn_edge_combine_fwd / _bwd, csplat_gnn_segment_sum and csplat_gnn_gather_rows must be 16-byte aligned (refused otherwise,
  * before anything is launched). */
-size_t csplat_gnn_csr_temp_bytes(int N, int64_t E);
+size_t csplat_gnn_csr_temp_bytes(int N, int64_t E); /* temp of csplat_gnn_build_csr: no initial state */
 int csplat_gnn_build_csr(void *stream, int N, int64_t E, const int64_t *keys /* device, [E] */, int32_t *rowptr,
                          int32_t *perm, void *temp);
 
@@ -1175,7 +1175,7 @@ int csplat_relu_mask_bias128(void *stream, int64_t M, const float *g, const floa
 
 /* Weight gradient of a 128 -> 128 Linear layer under autograd: dW[o][i] = sum_e g[e][o] * x[e][i], g and x [M][128] row-major,
  * dW [128][128] (torch Linear.weight layout).  Exact-fp32 MFMA, split over row slices, partial results summed in slice order
- * (deterministic).  workspace: csplat_dw128_workspace_bytes(M) bytes. */
+ * (deterministic).  workspace: csplat_dw128_workspace_bytes(M) bytes, no initial state. */
 size_t csplat_dw128_workspace_bytes(int64_t M);
 int csplat_dw128(void *stream, int64_t M, const float *g, const float *x, float *dW, void *workspace);
 /* the same with dbias[128] = column sums of g (the bias gradient, from the g rows the product reads anyway) and, when x_relu != 0,

@@ -5,6 +5,7 @@ flat C entries csplat_backward / csplat_backward_depth, which nothing else in th
 Shape: P = 70 (no multiple of 32 or 128: more than one K8 workgroup in the single-view and the batched kernels, each with a ragged tail),
 a 33 x 17 image (partial tiles on both edges), SH degree 3; and P = 0, a view without Gaussians."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -102,30 +103,54 @@ def _outputs(P, M, dev):
 OUT_FIELDS = ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
 
 
+def forward_state(case, W=W, H=H):
+    """ONE forward of the single-view path on `case` (a W x H image) -> what the flat C entries read: the view state with its chunks, the
+    saved tensors, the settings"""
+    import diff_gaussian_rasterization as dgr
+    inp = util.gpu_inputs(case, requires_grad=False)
+    rs = util.gpu_settings(case)
+
+    class Ctx:
+        def save_for_backward(self, *a): self.saved_tensors = a
+        def mark_non_differentiable(self, *a): pass
+    ctx = Ctx()
+    with torch.no_grad():
+        dgr._RasterizeGaussians.forward(ctx, inp["means3D"], inp["means2D"], inp["shs"], None, inp["opacities"], inp["scales"],
+                                        inp["rotations"], None, rs)
+    return SimpleNamespace(vs=ctx.view_state, saved=ctx.saved_tensors, rs=rs, P=case["P"], W=W, H=H)
+
+
+def flat_call(st, entry, dpix, depth_arg, scratch_ptr, out_ptrs):
+    """csplat_backward (depth_arg = []) or csplat_backward_depth (depth_arg = [pointer or None]) on the chunks of forward_state(), with
+    the caller's scratch and the addresses of its nine outputs (the order of OUT_FIELDS); synchronised on return"""
+    from csplat import native as n
+    vs, rs = st.vs, st.rs
+    means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = st.saved
+    dev = means3D.device
+    head = [n.stream_handle(dev), st.P, int(rs.sh_degree), vs.M, vs.num_rendered, n.ptr(vs.bg), st.W, st.H, n.ptr(means3D), n.ptr(sh),
+            n.ptr(colors_precomp), n.ptr(scales), float(rs.scale_modifier), n.ptr(rotations), n.ptr(cov3Ds_precomp), n.ptr(vs.view),
+            n.ptr(vs.proj), n.ptr(vs.campos), float(rs.tanfovx), float(rs.tanfovy), n.ptr(radii), *(n.ptr(c) for c in vs.chunks),
+            n.ptr(color), n.ptr(dpix)]
+    with n.on_device(dev):
+        rc = getattr(n.lib, entry)(*head, *depth_arg, scratch_ptr, *out_ptrs)
+    n.check(rc, entry)
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("P", [70, 0])
 @pytest.mark.parametrize("with_depth", [False, True])
 def test_flat_entries_equal_the_views_entry_bit_for_bit(with_depth, P):
     """csplat_backward and csplat_backward_depth (with and without a depth gradient) against csplat_backward_views(1, ...), all on the
     chunks of ONE forward of the single-view path"""
-    import diff_gaussian_rasterization as dgr
     from csplat import native as n
     case = _case(P)
     dev = torch.device("cuda")
     old_flags = int(n.lib.csplat_debug_flags_query())
     try:
         n.lib.csplat_debug_flags(BIT_REPRODUCIBLE)
-        inp = util.gpu_inputs(case, requires_grad=False)
-        rs = util.gpu_settings(case)
-
-        class Ctx:
-            def save_for_backward(self, *a): self.saved_tensors = a
-            def mark_non_differentiable(self, *a): pass
-        ctx = Ctx()
-        with torch.no_grad():
-            dgr._RasterizeGaussians.forward(ctx, inp["means3D"], inp["means2D"], inp["shs"], None, inp["opacities"], inp["scales"],
-                                            inp["rotations"], None, rs)
-        vs = ctx.view_state
-        means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = ctx.saved_tensors
+        st = forward_state(case)
+        vs = st.vs
+        means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp, radii, color = st.saved
         R, M = vs.num_rendered, vs.M
         dpix, ddepth = _images()
         if not with_depth:
@@ -137,13 +162,7 @@ def test_flat_entries_equal_the_views_entry_bit_for_bit(with_depth, P):
 
         def flat(entry, depth_arg):
             outs, buf = _outputs(P, M, dev), scratch()
-            head = [stream, P, int(rs.sh_degree), M, R, n.ptr(vs.bg), W, H, n.ptr(means3D), n.ptr(sh), n.ptr(colors_precomp), n.ptr(scales),
-                    float(rs.scale_modifier), n.ptr(rotations), n.ptr(cov3Ds_precomp), n.ptr(vs.view), n.ptr(vs.proj), n.ptr(vs.campos),
-                    float(rs.tanfovx), float(rs.tanfovy), n.ptr(radii), *(n.ptr(c) for c in vs.chunks), n.ptr(color), n.ptr(dpix)]
-            with n.on_device(dev):
-                rc = getattr(n.lib, entry)(*head, *depth_arg, n.ptr(buf), *(n.ptr(o) for o in outs))
-            n.check(rc, entry)
-            torch.cuda.synchronize()
+            flat_call(st, entry, dpix, depth_arg, n.ptr(buf), [n.ptr(o) for o in outs])
             return outs
 
         def views():
