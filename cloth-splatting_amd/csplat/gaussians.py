@@ -240,6 +240,15 @@ class UnbindViews(torch.autograd.Function):
         return _join_views(grads, ctx.shape[1:], *ctx.meta)
 
 
+def mesh_vertex_normals(vertices, face):
+    """unit vertex normals of the mesh (vertices [V,3], face [3,M]) as torch_geometric.transforms.GenerateMeshNormals defines them: unit
+    face normals (v1 - v0) x (v2 - v0), summed onto the face's three vertices, normalised"""
+    v0, v1, v2 = vertices[face[0]], vertices[face[1]], vertices[face[2]]
+    fn = torch.nn.functional.normalize(torch.cross(v1 - v0, v2 - v0, dim=1), p=2, dim=-1)
+    vn = torch.zeros_like(vertices).index_add_(0, torch.cat([face[0], face[1], face[2]]), fn.repeat(3, 1))
+    return torch.nn.functional.normalize(vn, p=2, dim=-1)
+
+
 class MeshGaussians(DensifyMixin):
     def __init__(self, sh_degree: int):
         self.active_sh_degree = 0
@@ -284,6 +293,17 @@ class MeshGaussians(DensifyMixin):
         self._scaling = nn.Parameter(scales.requires_grad_(True))
         self._rotation = nn.Parameter(rots.requires_grad_(True))
         self._opacity = nn.Parameter(opac.requires_grad_(True))
+        return self
+
+    def from_vertices(self, vertices, gaussian_init_factor=2, generator=None):
+        """gaussian_mesh.py:204-205 (make_mesh :52): the mesh of a cloud [N,3] is the Delaunay triangulation of its x and y coordinates
+        (meshnet.data_utils.compute_mesh, on the device), then from_mesh.  The mesh keeps compute_mesh's rest-pose vertex normals as
+        `mesh.norm`, which get_vertice_rotation reads."""
+        from meshnet.data_utils import compute_mesh
+        require_cuda(vertices)
+        mesh = compute_mesh(vertices)
+        self.from_mesh(mesh.pos, mesh.face, mesh.edge_index, gaussian_init_factor=gaussian_init_factor, generator=generator)
+        self.mesh.norm = mesh.norm
         return self
 
     def from_arrays(self, pos, face, edge_index, face_ids, bary, log_scales, quats, opacity_logits, sh):
@@ -446,11 +466,7 @@ class MeshGaussians(DensifyMixin):
     def vertex_normals(self, vertices):
         """unit vertex normals as torch_geometric.transforms.GenerateMeshNormals defines them (the transform the reference applies,
         gaussian_mesh.py:199-200): unit face normals (v1 - v0) x (v2 - v0), summed onto the face's three vertices, normalised."""
-        face = self.mesh.face
-        v0, v1, v2 = vertices[face[0]], vertices[face[1]], vertices[face[2]]
-        fn = torch.nn.functional.normalize(torch.cross(v1 - v0, v2 - v0, dim=1), p=2, dim=-1)
-        vn = torch.zeros_like(vertices).index_add_(0, torch.cat([face[0], face[1], face[2]]), fn.repeat(3, 1))
-        return torch.nn.functional.normalize(vn, p=2, dim=-1)
+        return mesh_vertex_normals(vertices, self.mesh.face)
 
     def get_vertice_rotation(self, deformed_vertices):
         """gaussian_mesh.py:190-201: per-vertex rotation (quaternion, XYZW) from the rest-pose vertex normal to the deformed one --

@@ -124,7 +124,9 @@ EXPORTS = {
     "csplat_obs_mark": (_i, [_vp, _i64, _i, _i, _vp, _vp, _f, _vp]),
     "csplat_traj_smooth": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "csplat_traj_features": (_i, [_vp, _i, _i, _i64, _vp, _vp, _f, _vp, _vp, _vp]),
-    "csplat_train_update_fwd": (_i, [_vp, _i, _i64, _i] + [_vp] * 12),
+    "csplat_delaunay_temp_bytes": (_i, [_i, C.POINTER(_sz)]),
+    "csplat_delaunay": (_i, [_vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "csplat_train_update_fwd":(_i, [_vp, _i, _i64, _i] + [_vp] * 12),
     "csplat_train_update_bwd": (_i, [_vp, _i, _i64] + [_vp] * 12),
     "csplat_dataset_batch": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _i64] + [_vp] * 8 + [_i64, _i64, _i64] + [_vp] * 8),
     "csplat_dataset_rollout_error": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1,6 +1,8 @@
 """Drop-in for the reference's `meshnet/data_utils.py`, on the GPU kernels of this library.
 
-Graph builders: the kNN graph of `compute_edges_index` (:371-414) and `farthest_point_sampling` (:134-160), on `simple_knn`.
+Graph builders: the kNN graph of `compute_edges_index` (:371-414) and `farthest_point_sampling` (:134-160), on `simple_knn`; its
+`delaunay=True` branch (:372-405, the default of every MeshNet script) and `compute_mesh` (:419-440) on csplat.triangulate, the Delaunay
+triangulation on the device (include/csplat.h, "Delaunay triangulation": cocircular points are resolved by its tie rule, not by Qhull).
 
 Trajectory preprocessing, the step between an observed / tracked cloud and the planner (include/csplat.h, "Trajectory preprocessing"):
   smooth_clouds / gaussian_smoothing   the reference's gaussian_smoothing (:267-278) for one cloud [N,3] or all frames [T,N,3] of a tracked
@@ -20,7 +22,8 @@ CPU path).  A numpy array goes to the GPU as float32 when there is one, else the
 back as numpy in the input's dtype, like farthest_point_sampling.  Everything here is an observation: detached, no gradients.
 
 The samples a training step reads are assembled from these dictionaries by meshnet.dataloader_sim (SamplesClothSimDataset), which stands
-in for the PyG `Data` builders.  The Delaunay branch and the file loaders of that module are host-side plumbing and stay out of scope."""
+in for the PyG `Data` builders.  The file loaders of that module are host-side plumbing and stay out of scope.  There is no CPU Delaunay:
+a CPU tensor with delaunay=True raises NotImplementedError (use SciPy there); a numpy array goes to the GPU when there is one."""
 import math
 
 import numpy as np
@@ -56,19 +59,56 @@ def edges_from_knn(indices):
     return torch.stack((torch.div(key, max(P, 1), rounding_mode="floor"), key % max(P, 1))).contiguous()
 
 
+def _delaunay_points(points, what):
+    """numpy array or tensor [N,3] for the Delaunay branch -> float32 tensor on the GPU.  Shape errors come first; a CPU tensor, and a
+    numpy array on a machine without a GPU, raise NotImplementedError: there is no CPU Delaunay here"""
+    t = points.detach() if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{what}: points must be [N, 3], got {tuple(t.shape)}")
+    if not t.is_cuda and (torch.is_tensor(points) or not torch.cuda.is_available()):
+        raise NotImplementedError(f"{what}(delaunay=True) triangulates on the GPU (csplat.triangulate.delaunay) and has no CPU form; for "
+                                  "points that live on the host build the edges and faces with SciPy (scipy.spatial.Delaunay, as the "
+                                  "reference does) and pass them in")
+    return t.to(torch.float32).cuda() if not t.is_cuda else t.to(torch.float32)
+
+
 def compute_edges_index(points, k=3, delaunay=False, sim_data=False, norm_threshold=0.01):
-    """the kNN graph of the reference's function: every point joined to its k nearest other points, each undirected edge
-    once.  points: numpy array or tensor [N,3].  Returns torch.long [2,E], sorted by (i, j), on the GPU (on the input's
-    device for a GPU tensor).  `sim_data` and `norm_threshold` belong to the Delaunay branch."""
+    """delaunay=False: the kNN graph of the reference's function: every point joined to its k nearest other points, each undirected edge
+    once.  points: numpy array or tensor [N,3].  Returns torch.long [2,E], sorted by (i, j), on the GPU (on the input's device for a GPU
+    tensor).
+    delaunay=True: (edge_index, faces) as the reference's -- the Delaunay triangulation of the points projected on [:, [0, 2]] with
+    sim_data, else on [:, :2]; an edge of a face longer than norm_threshold (None: no limit) is left out and spoils its face.  edge_index
+    [2,E] each edge once, i < j, sorted by (i, j); faces [3,M], lowest index first, counter-clockwise in the projection, sorted.  Both
+    torch.long on the GPU, straight from csplat.triangulate.delaunay (which states the rule for cocircular points).  A GPU tensor that is
+    not float32 is converted; a numpy array goes to the GPU; a CPU tensor raises NotImplementedError."""
     if delaunay:
-        raise NotImplementedError("compute_edges_index(delaunay=True) is host geometry (scipy.spatial.Delaunay in the reference) "
-                                  "and is not provided here; build those edges with SciPy")
+        from csplat import triangulate
+        what = "compute_edges_index"
+        thr = triangulate.checked_threshold(norm_threshold, what)
+        pts = _delaunay_points(points, what)
+        tri = triangulate.delaunay(pts[:, [0, 2]] if sim_data else pts[:, :2].contiguous(), thr)
+        return tri.edge_index, tri.faces
     if isinstance(k, np.integer):
         k = int(k)
     if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= simple_knn.MAX_K:
         raise ValueError(f"compute_edges_index: k must be an integer in 1 .. {simple_knn.MAX_K}, got {k!r}")
     _d2, idx = simple_knn.knn(_gpu_points(points, "compute_edges_index"), k)
     return edges_from_knn(idx)
+
+
+def compute_mesh(points):
+    """the reference's compute_mesh (:419-440): the Delaunay triangulation of the x and y coordinates of points [N,3] as a
+    SimpleNamespace(pos, face [3,M], edge_index, norm) -- edge_index = face_to_edge(face, N) (PyG's FaceToEdge), norm the unit vertex
+    normals of GenerateMeshNormals as csplat.gaussians.mesh_vertex_normals forms them.  The reference joggles the input (Qhull's QJ) so
+    that cocircular points give some triangulation; here the tie rule of csplat_delaunay gives one, the same on every run.  pos is the
+    input as given when it is a float32 GPU tensor."""
+    import types
+    from csplat import triangulate
+    from csplat.gaussians import mesh_vertex_normals
+    from meshnet.dataloader_sim import face_to_edge
+    pts = _delaunay_points(points, "compute_mesh")
+    face = triangulate.delaunay(pts[:, :2].contiguous()).faces
+    return types.SimpleNamespace(pos=pts, face=face, edge_index=face_to_edge(face, int(pts.shape[0])), norm=mesh_vertex_normals(pts, face))
 
 
 def farthest_point_sampling(points, num_samples, start=None):
@@ -326,11 +366,11 @@ def process_traj(traj, dt, k=3, delaunay=False, subsample=False, num_samples=300
     order.  Deliberately different: that prune mask is applied ONCE (the reference applies it twice and raises IndexError whenever an
     edge is actually pruned; once is the same result whenever it does not crash), and faces=None gives edge_faces None (the reference
     cannot stack None).  Subsampling is farthest_point_sampling, a missing edge_index comes from compute_edges_index (both need the GPU);
-    delaunay=True raises NotImplementedError.  The displacement's sign is the reference's: see compute_edge_features."""
+    with delaunay=True a missing edge_index comes with its faces from the triangulation of frame 0's sampled nodes
+    (compute_edges_index(delaunay=True, sim_data, norm_threshold)), and edge_faces is those faces [T,3,M]; an explicit edge_index wins,
+    as in the reference.  There is no CPU Delaunay: a CPU tensor that needs one raises NotImplementedError.  The displacement's sign is
+    the reference's: see compute_edge_features."""
     what = "process_traj"
-    if delaunay:
-        raise NotImplementedError("process_traj(delaunay=True) is host geometry (scipy.spatial.Delaunay in the reference) and is not provided "
-                                  "here; pass `edge_index` (and `faces`) built with SciPy")
     kind = _Kind(traj, "traj", what)
     if kind.raw.dim() != 3 or kind.raw.shape[2] != 3 or kind.raw.shape[0] < 1:
         raise ValueError(f"{what}: `traj` is [T,N,3] with T >= 1, got {tuple(kind.raw.shape)}")
@@ -355,6 +395,9 @@ def process_traj(traj, dt, k=3, delaunay=False, subsample=False, num_samples=300
             raise ValueError(f"{what}: `sampled_points_indeces` entries must lie in 0 .. N-1 = {N - 1}")
     elif subsample and (not isinstance(num_samples, (int, np.integer)) or isinstance(num_samples, bool) or int(num_samples) < 1):
         raise ValueError(f"{what}: num_samples is an integer >= 1, got {num_samples!r}")
+    if delaunay and edge_index is None and not kind.raw.is_cuda and not (kind.numpy and torch.cuda.is_available()):
+        raise NotImplementedError("process_traj(delaunay=True) triangulates on the GPU and has no CPU form; for a trajectory that lives on "
+                                  "the host pass `edge_index` (and `faces`) built with SciPy (scipy.spatial.Delaunay, as the reference does)")
     P = kind.work()
     dev = P.device
     if sel is None:
@@ -363,7 +406,10 @@ def process_traj(traj, dt, k=3, delaunay=False, subsample=False, num_samples=300
     pos = P[:, sel].contiguous()
     S = int(sel.shape[0])
     if edge_index is None:
-        edge_index = compute_edges_index(pos[0], k=k)
+        if delaunay:
+            edge_index, faces = compute_edges_index(pos[0], k=k, delaunay=True, sim_data=sim_data, norm_threshold=thr)
+        else:
+            edge_index = compute_edges_index(pos[0], k=k)
     ei = _checked_edges(edge_index, S, dev, what)
     vel, disp, norm = _features(pos, ei, inv, True, True)
     first = min(1, T - 1)                                   # the frame whose edge features stand for frame 0 as well

@@ -19,7 +19,9 @@ Dispatch as in meshnet.data_utils: a store of float32 data on the GPU takes the 
 from torch operations in its own dtype; a GPU store of another dtype reports through csplat.native.composed_fallback (raises under STRICT)
 and composes.  Everything here is data: detached, no gradients.
 
-Loading trajectory files (`data_path`) and the Delaunay branch are host-side plumbing and stay out of scope."""
+delaunay=True, the reference's default: collect_observation's trajectory then carries the faces of the Delaunay triangulation of its
+sampled nodes (meshnet.data_utils.process_traj, on the device), and the network's edges are face_to_edge(faces).  Loading trajectory
+files (`data_path`) is host-side plumbing and stays out of scope."""
 import collections
 
 import numpy as np

@@ -18,7 +18,7 @@ operations in the dtype of `velocity` (reported through csplat.native.composed_f
 CPU path).  `edge_index` is validated once per tensor object (dtype, shape [2,E], range: one blocking read), never per step.
 
 The sample data set, its batches and the validation rollout's errors are meshnet.dataloader_sim (SamplesClothSimDataset; train_step takes
-its Batch as it is).  Loading trajectory files, logging, checkpoints and the Delaunay branch are host-side plumbing and stay out of scope."""
+its Batch as it is).  Loading trajectory files, logging and checkpoints are host-side plumbing and stay out of scope."""
 import types
 import weakref
 

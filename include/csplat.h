@@ -876,6 +876,52 @@ int csplat_traj_smooth(void *stream, int T, int N, int K, const float *points, f
 int csplat_traj_features(void *stream, int T, int N, int64_t E, const float *pos, const int64_t *edge_index, float inv_dt, float *vel /* or NULL */,
                          float *disp, float *norm);
 
+/* Delaunay triangulation of a planar cloud, the mesh between the sampled nodes and the network's edges (csplat_delaunay.hip, predicates in
+ * csplat_delaunay_predicates.h).  It restates what the reference does on the host: scipy.spatial.Delaunay followed by the loop over simplices
+ * with the length filter (meshnet/data_utils.py:371-405, compute_edges_index with delaunay=True, the default of every MeshNet script), and
+ * compute_mesh (:419-440), from which scene_reconstruction/gaussian_mesh.py:52,204 builds the Gaussians' mesh.  No gradients.
+ *
+ * points [N][2] float32 (the projected coordinates), 0 <= N < 2^24.  A point with a non-finite coordinate is skipped; so is a point whose
+ * two coordinates equal those of a lower-indexed point (-0.0 == 0.0).  Skipped points are in no face and are counted.  Among the rest the
+ * output is the triangulation of their convex hull in which no point is strictly inside a face's circumcircle.  Ties are broken by raising
+ * the lifted height x^2 + y^2 of point p by a symbolic eps_p, eps_0 >> eps_1 >> ... > 0: when the exact in-circle determinant of (a, b, c, d)
+ * is zero, its sign is that of the first non-zero cofactor, taken in ascending point index over the four; the cofactors are +orient(b,c,d),
+ * -orient(a,c,d), +orient(a,b,d), -orient(a,b,c) for a, b, c, d.  Orientation is not perturbed: a collinear triple is never a face.  The
+ * result is therefore a pure function of the coordinates and the index order, unique also on a regular grid where every quad is
+ * cocircular (this rule replaces Qhull's joggle and its arbitrary choice among cocircular points).  All points collinear, or fewer than
+ * three usable: zero faces, no error.
+ *
+ * Brute force, one wave per point i and no dependence between points: from the exact nearest other point j0 (ties to the lower index; that
+ * edge is in every Delaunay triangulation) the walk takes, among the points strictly left of i -> j, the one that no other beats under the
+ * perturbed in-circle test, emits the face and goes on with the edge (i, k), until it closes on j0 or nothing is left of the edge (the
+ * hull); then it walks the other way from j0.  Each face is found by its three vertices; only the walk of its lowest index writes it.
+ * The walk counts what each point owns and keeps the first sixteen faces and edges per point; one scan lays the output out; only points
+ * that own more walk a second time to write; one ordering pass.  O(N^2) per walk, made for hundreds to a few thousand points.  Every
+ * decision of the walk -- nearest neighbour, orientation, in-circle -- is an exact predicate on the float32 inputs over the whole finite
+ * float32 range, denormals and 60-binade exponent gaps included: an fp64 evaluation with a forward error bound as filter, then an exact
+ * stage in fp64 expansion arithmetic (two-sum; two-product by explicit fma; nothing else contracts).  No float atomics: every output is
+ * bit-reproducible.
+ *
+ * The length filter of the reference's loop is part of the entry: len = sqrtf(du*du + dv*dv) in float32 without contraction; an edge of a
+ * simplex is dropped when len > (float)norm_threshold; a face is kept when none of its three edges is dropped; kept edges come back once
+ * each.  has_threshold = 0 keeps everything (norm_threshold is not read); a NaN threshold is an error.
+ *
+ * Outputs on the device: faces [2N][3] int32, the first counters[0] rows written: each face rotated so that its lowest index is first,
+ * counter-clockwise in the input plane, the rows in lexicographic order.  edges [3N][2] int32, the first counters[1] rows written: i < j,
+ * sorted by (i, j).  counters [5] int64: kept faces, kept edges, skipped points, exact decisions (how many decisions of the counting walk
+ * the exact stage took: per-point partials summed in a fixed order), status.  status bit 0: a walk exceeded N steps; bit 1: the two walks
+ * disagreed or an output would leave its capacity (nothing is written outside).  A non-zero status means the outputs are not to be used.
+ * temp: what csplat_delaunay_temp_bytes reports, 256-byte aligned, no initial state.  csplat_delaunay_temp_bytes returns 0 and stores the
+ * size, or refuses N like the entry does.  N = 0 zeroes the counters without a launch.
+ *
+ * Refused before any launch, with return 2 and csplat_last_error() naming the entry: N outside 0 .. 2^24 - 1, has_threshold other than 0 or
+ * 1, a NaN threshold, NULL operands, points not 8-byte aligned, faces / edges not 4-byte aligned, counters not 8-byte aligned, temp not
+ * 256-byte aligned, an output or temp that shares a byte with another operand.
+ * Added exports: CSPLAT_ABI_VERSION is unchanged. */
+int csplat_delaunay_temp_bytes(int N, size_t *bytes);
+int csplat_delaunay(void *stream, int N, const float *points, int has_threshold, double norm_threshold, int32_t *faces, int32_t *edges,
+                    int64_t *counters, void *temp);
+
 /* MeshNet training transition (csplat_train_sim.hip): the state update between the predictions of one unrolled training step, the
  * reference's update_prediction (train_meshnet_sim.py:322-359), forward and backward, one launch each.  H = input_sequence_length, c a
  * component 0..2; every operation is float32 and rounded once, no contraction:
