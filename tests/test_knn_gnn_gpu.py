@@ -25,6 +25,19 @@ def test_dist2_bit_exact_vs_oracle():
     assert distCUDA2(torch.zeros(0, 3, device="cuda")).numel() == 0
 
 
+@pytest.mark.parametrize("P", [1025, 2051])
+def test_dist2_brute_force_over_several_slabs_vs_oracle(P):
+    """csplat_dist2 called directly (distCUDA2 takes it below 4096 points only): two and three 1024-point slabs, the last one ragged
+    and with a tail that the four-wide loop leaves; every row, so a point that is the first or the last candidate of a slab too"""
+    from csplat import native as n
+    pts = np.random.default_rng(P).normal(size=(P, 3)).astype(np.float32)
+    pts[1023] = pts[1024]                          # coincident points either side of the slab edge
+    t = torch.tensor(pts, device="cuda")
+    out = torch.full((P,), -7.0, dtype=torch.float32, device="cuda")
+    n.check(n.lib.csplat_dist2(n.stream_handle(t.device), P, n.ptr(t), n.ptr(out)), "csplat_dist2")
+    np.testing.assert_array_equal(out.cpu().numpy(), ro.dist2(pts))
+
+
 def test_dist2_boxed_path_equals_brute_force_bit_for_bit():
     """csplat_dist2_ws (Morton order + bounding-box pruning, the upstream extension's scheme) against the brute-force
     kernel: identical bits on clustered, planar, duplicated and ragged inputs, and the timing that motivates it."""

@@ -97,6 +97,29 @@ def test_small_clouds_agree_in_the_pruned_form_too():
                     assert np.array_equal(d2.cpu().numpy().view(np.uint32), rd.view(np.uint32)), (kind, P, K)
 
 
+@pytest.mark.parametrize("K", [5, 8])
+def test_the_eight_slot_list_in_both_forms_through_the_c_interface(K):
+    """K in 5 .. 8 takes KBest<8>, which no K of the two tests above reaches.  Called directly, so that the form does not depend on
+    the Python threshold: the brute-force form at P = 1025 and 2051 (two and three slabs, the last one ragged, a tail the four-wide
+    loop leaves), the pruned form at P = 1025 and 4099 (two and five boxes, the same tails).  Every row is compared, so the query
+    whose own point is the first or the last candidate of a slab or a box is among them."""
+    from csplat import native as n
+    for P in (1025, 2051, 4099):
+        pts = cloud("duplicated" if P == 2051 else "uniform", P, seed=P + K)
+        rd, ri = knn_ref.knn(pts, K)
+        t = gpu(pts)
+        for form in (("brute", "pruned") if P == 1025 else ("brute",) if P == 2051 else ("pruned",)):
+            d2 = torch.full((P, K), -7.0, dtype=torch.float32, device="cuda")
+            idx = torch.full((P, K), -7, dtype=torch.int32, device="cuda")
+            if form == "brute":
+                n.check(n.lib.csplat_knn(n.stream_handle(t.device), P, K, n.ptr(t), n.ptr(d2), n.ptr(idx)), "csplat_knn")
+            else:
+                temp = torch.empty(int(n.lib.csplat_knn_temp_bytes(P, K)), dtype=torch.uint8, device="cuda")
+                n.check(n.lib.csplat_knn_ws(n.stream_handle(t.device), P, K, n.ptr(t), n.ptr(d2), n.ptr(idx), n.ptr(temp)), "csplat_knn_ws")
+            assert np.array_equal(idx.cpu().numpy(), ri), (form, P, K)
+            assert np.array_equal(d2.cpu().numpy().view(np.uint32), rd.view(np.uint32)), (form, P, K)
+
+
 def test_pruned_form_equals_brute_form_bit_for_bit():
     import simple_knn
     for P in (4096, 20_000, 200_000):

@@ -416,10 +416,15 @@ def test_header_exports_and_bindings():
     src = open(os.path.join(ROOT, "cloth-splatting_amd", "csrc", "csplat_trajectory.hip")).read()
     code = re.sub(r"//.*", "", src)
     assert "atomic" not in code.lower() and "#pragma clang fp contract(off)" in code and "__fmul_rn(__fsub_rn(" in code and "k_traj_features" in code
-    knn = open(os.path.join(ROOT, "cloth-splatting_amd", "csrc", "csplat_knn.hip")).read()
-    smooth = knn[knn.index("void k_traj_smooth("):knn.index('extern "C" int csplat_traj_smooth(')]
-    assert "KBest<CAP>" in smooth and "knn_offer4(" in smooth and "KNN_SLAB" in smooth and "atomic" not in re.sub(r"//.*", "", smooth).lower()
-    assert knn.count("struct KBest") == 1 and knn.count("void knn_offer4(") == 1               # used, not copied
+    csrc = os.path.join(ROOT, "cloth-splatting_amd", "csrc")
+    knn = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.startswith("csplat_knn"))   # the knn sources
+    smooth = re.sub(r"//.*", "", knn[knn.index("void k_traj_smooth("):knn.index('extern "C" int csplat_traj_smooth(')])
+    assert "KBest<CAP>" in smooth and "knn_scan_slabs(" in smooth and "atomic" not in smooth.lower()
+    assert "s_p[" not in smooth and "offer" not in smooth                                      # the kernel holds no candidate loop of its own
+    for once in ("struct KBest", "void offer(", "void offer4("):                              # used, not copied: one definition of each,
+        assert knn.count(once) == 1, once                                                      # whatever its parameters are called
+    for fn in ("knn_scan_slabs", "knn_d2", "knn_box_d2"):                                      # (a definition starts its line with __device__)
+        assert len(re.findall(r"^__device__[^\n;]*\b" + fn + r"\(", knn, flags=re.M)) == 1, fn
     assert du.FLT_MAX == R.FLT_MAX and du.GRIPPER_OFFSET == (0.0, -0.03, 0.02)
 
 

@@ -12,7 +12,7 @@ float64 selections themselves agree for every point and frame (asserted), so tha
 Shapes.  One lane per point, 256 lanes a workgroup, the frame through a 1024-point LDS slab four candidates at a time: N = 1; 5 with
 k = 20 (fewer points than k); 256 and 257 (the workgroup edge); 1024 and 1029 (the slab edge, and a tail the four-wide loop leaves).
 k in {1, 4, 5, 20, 32} at every N: the capacities 4, 8 and 32 of KBest, full (4, 32) and with dead slots (1, 5, 20); k in {8, 9, 16, 17} at
-N = 257: the capacity 16 and both of its borders.  T in {1, 3}, and 65538 frames of 3 points: more than the grid's second axis holds."""
+N = 257: the capacity 16 and both of its borders; k in {9, 16} at N = 1025: that capacity over two slabs.  T in {1, 3}, and 65538 frames of 3 points: more than the grid's second axis holds."""
 import numpy as np
 import pytest
 
@@ -93,6 +93,11 @@ def test_smoothing_at_the_launch_edges_and_every_capacity(N, k):
 @pytest.mark.parametrize("k", [8, 9, 16, 17])
 def test_smoothing_at_the_borders_of_the_sixteen_slot_list(k):
     smooth_case(3, 257, k, seed=257)
+
+
+@pytest.mark.parametrize("k", [9, 16])
+def test_the_sixteen_slot_list_over_two_slabs(k):
+    smooth_case(1, 1025, k, seed=1025)
 
 
 @pytest.mark.parametrize("T", [1, 3])
