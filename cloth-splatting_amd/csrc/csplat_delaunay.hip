@@ -14,6 +14,7 @@
 // Every decision is an exact predicate (csplat_delaunay_predicates.h), so the three walks that find a face agree on it.  No float
 // atomics, no atomics on data at all (one integer atomicOr raises the status word): every output is bit-reproducible.
 #include "csplat_common.h"
+#include "csplat_device.h"
 #include "csplat_delaunay_predicates.h"
 
 #pragma clang fp contract(off)
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(DL_THREADS) void k_dl_walk(int N, const float *__re
             if (steps > 0) dl_edge(o, j0, f0);                                        // (i, j0) is an edge of a face unless every point is collinear
         }
     }
-    for (int off = CSPLAT_WAVE / 2; off > 0; off >>= 1) exact += __shfl_xor(exact, off, CSPLAT_WAVE);
+    exact = wave_sum(exact);
     if (lane == 0) {
         if (o.write) {
             if (o.nf != o.f_end - o.f_at || o.ne != o.e_end - o.e_at) o.bad |= DL_STATUS_LAYOUT;

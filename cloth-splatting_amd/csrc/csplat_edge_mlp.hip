@@ -54,6 +54,7 @@
 // beat the three launches; the bare MFMA pipeline of THIS design runs at 1,736 cycles per 48-MFMA phase (floor 1,536), the chip's clock
 // under it at ~1.7 GHz.
 #include "csplat_common.h"
+#include "csplat_device.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -63,7 +64,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
@@ -121,10 +121,9 @@ __global__ __launch_bounds__(64) void k_edge_mlp3r_pack(const float *__restrict_
         img[((size_t)j * ErCfg<F16>::NW + (l * NP + q) * 8 + st) * 64 + lane] = *reinterpret_cast<const i32x4 *>(p[q]);
 }
 
-// ReLU that lets a NaN through.  fmaxf(x, 0) (v_max_f32) returns 0 for a NaN -- and a value that left fp16's range turns into NaN one layer
-// later (pieces Inf and -Inf), which the NEXT ReLU would then launder into finite garbage: measured, a first-layer weight of 3e4 gave
-// finite rows with a relative error of 1.2.  With this form an overflow anywhere reaches the output as NaN rows: visible, never silent.
-__device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
+// Every ReLU here is relu_keep_nan (csplat_common.h: `x < 0.f ? 0.f : x`, a NaN passes).  A value that left fp16's range turns into NaN one layer later (pieces Inf and -Inf),
+// which a fmaxf ReLU would then launder into finite garbage: measured, a first-layer weight of 3e4 gave finite rows with a relative error
+// of 1.2.  With this form an overflow anywhere reaches the output as NaN rows: visible, never silent.
 
 __device__ __forceinline__ float pair_sum(float v) {      // v of lane (n, 0) + v of lane (n, 1), in both lanes
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
@@ -138,10 +137,8 @@ __global__ __launch_bounds__(256) void k_absmax(int64_t n4, const float4 *__rest
         const float4 v = x[i];
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     __shared__ float sm[4];
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    block_stash(sm, wave_max(m));
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned b = __float_as_uint(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(256) void k_edge_mlp3r(int64_t M, const float *__re
         const int half = m / RELU_HALF, mm = m % RELU_HALF;
         if (mm < 4 * RELU_PAIR) {
             const int jj = mm / RELU_PAIR, j = 4 * half + jj, o = mm % RELU_PAIR;
-            if (o == 0) { rx0 = relu_nan(acc[2 * j]); rx1 = relu_nan(acc[2 * j + 1]); rq = pk(rx0, rx1); opaque(rq); P[0][jj] = rq; }
+            if (o == 0) { rx0 = relu_keep_nan(acc[2 * j]); rx1 = relu_keep_nan(acc[2 * j + 1]); rq = pk(rx0, rx1); opaque(rq); P[0][jj] = rq; }
             else if (o % 3 == 1) rx0 -= lo_f(rq);
             else if (o % 3 == 2) rx1 -= hi_f(rq);
             else { rq = pk(rx0, rx1); if (o != RELU_PAIR - 1) opaque(rq); P[o / 3][jj] = rq; }
@@ -848,14 +845,14 @@ __global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const floa
     product(B0, acc, 1);
     product(B1, acc, 2);
 #pragma unroll
-    for (int r = 0; r < 16; r++) v[r] = relu_nan(acc[r]);
+    for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]);
     to_pieces(v, B2, 1.f);
     __syncthreads();
     // ---- layer 2
     start_from(b2, acc);
     product(B2, acc, 3);
 #pragma unroll
-    for (int r = 0; r < 16; r++) v[r] = relu_nan(acc[r]);
+    for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]);
     to_pieces(v, B0, 1.f);
     __syncthreads();
     // ---- layer 3, LayerNorm (the four waves' partials combined by the parallel-variance formula), residual
@@ -1051,13 +1048,13 @@ __global__ __launch_bounds__(256, 2) void k_rows_chain(int64_t N, const float *_
         start_from(b0, acc);
         product(B0, acc, 2);
 #pragma unroll
-        for (int r = 0; r < 16; r++) v[r] = relu_nan(acc[r]);
+        for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]);
         to_pieces(v, B1, 1.f);
         __syncthreads();
         start_from(b1, acc);
         product(B1, acc, -1);
 #pragma unroll
-        for (int r = 0; r < 16; r++) v[r] = relu_nan(acc[r]) * ISC;
+        for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]) * ISC;
         store_rows(v, out_a);
     }
     (void)B2; (void)sS;

@@ -4,10 +4,11 @@
 //   k_flow_loss_fwd      one thread per (frame t, Gaussian i): both pairs frame t takes part in -- as b of pair t-1, as a of pair t --
 //                        through flow_cell() / flow_pair(), so that a pair is judged by the same code in both roles; writes the
 //                        unit gradient dL_flow/dX_t[i] once (no atomics) and one (sum, count) partial per workgroup
-//   k_flow_loss_finish   one workgroup sums the partials in index order: bit-reproducible, no float atomics (the twin of k_geom_loss_finish)
+//   k_flow_loss_finish   one workgroup sums the partials in index order: bit-reproducible, no float atomics
 //   k_flow_loss_bwd      d_points = g weight lambda unit
 // Algorithmic bytes per (t, i): <= 3 points (36) + 3 visibility words (12) + 16 flow taps + 2 mask taps (72) read, 12 written.
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 
@@ -19,28 +20,11 @@ struct FlowTable {
     const int *vis[FL_FRAMES];
 };
 
-struct FlowProj { float x, y, w, ndx, ndy; };
-
-// gaussian_renderer._project: [X, 1] @ full, /w, ndc -> pixel (pixel centres at the integers).  `full` is wave-uniform
-__device__ __forceinline__ FlowProj flow_project(float px, float py, float pz, const float *__restrict__ full, float W, float H) {
-    FlowProj p;
-    const float hx = px * full[0] + py * full[4] + pz * full[8] + full[12];
-    const float hy = px * full[1] + py * full[5] + pz * full[9] + full[13];
-    p.w = px * full[3] + py * full[7] + pz * full[11] + full[15];
-    p.ndx = hx / p.w;
-    p.ndy = hy / p.w;
-    p.x = ((p.ndx + 1.f) * W - 1.f) * 0.5f;
-    p.y = ((p.ndy + 1.f) * H - 1.f) * 0.5f;
-    return p;
-}
-
-__device__ __forceinline__ bool flow_finite(float v) { return fabsf(v) < __builtin_inff(); }      // (false for a NaN)
-
 // where pair's `a` end samples the flow image and the mask: the four taps of its cell (floor convention, the upper tap clamped to the
 // image so that its weight is 0 at x = W-1) and the nearest pixel.  Outside the image (or not a number) every index is 0: the loads
 // stay inside the image whatever the point holds, and flow_pair() selects the pair out
 struct FlowCell { int64_t i00, i01, i10, i11, im; float fx, fy; bool inside; };
-__device__ __forceinline__ FlowCell flow_cell(const FlowProj &a, int W, int H) {
+__device__ __forceinline__ FlowCell flow_cell(const PixelProj &a, int W, int H) {
     FlowCell c;
     c.inside = a.x >= 0.f && a.x <= (float)(W - 1) && a.y >= 0.f && a.y <= (float)(H - 1);
     const float xs = c.inside ? a.x : 0.f, ys = c.inside ? a.y : 0.f;
@@ -72,7 +56,7 @@ __device__ __forceinline__ FlowTaps flow_gather(const float *__restrict__ F, con
 // ONE pair (a -> b) from its two projections, visibilities, taps and mask weight.  SELECTION: an invalid pair returns value 0 and both
 // gradients exactly 0, whatever its inputs hold.  ga = dL/dp_a = -(I + J_g)^T s, gb = dL/dp_b = s, s = m (sign r_x, sign r_y)
 struct FlowPair { bool valid; float value, gax, gay, gbx, gby; };
-__device__ __forceinline__ FlowPair flow_pair(const FlowProj &a, const FlowProj &b, int vis_a, int vis_b, const FlowCell &c, const FlowTaps &t,
+__device__ __forceinline__ FlowPair flow_pair(const PixelProj &a, const PixelProj &b, int vis_a, int vis_b, const FlowCell &c, const FlowTaps &t,
                                               float max_error) {
     const float fx = c.fx, fy = c.fy, ex = 1.f - fx, ey = 1.f - fy;
     const float gu = ey * (ex * t.u00 + fx * t.u01) + fy * (ex * t.u10 + fx * t.u11);
@@ -80,10 +64,10 @@ __device__ __forceinline__ FlowPair flow_pair(const FlowProj &a, const FlowProj 
     const float rx = (b.x - a.x) - gu, ry = (b.y - a.y) - gv;
     const float e = fabsf(rx) + fabsf(ry);
     bool ok = vis_a > 0 && vis_b > 0 && a.w > 0.f && b.w > 0.f;
-    ok = ok && flow_finite(a.x) && flow_finite(a.y) && flow_finite(b.x) && flow_finite(b.y) && c.inside;
-    ok = ok && flow_finite(t.u00) && flow_finite(t.u01) && flow_finite(t.u10) && flow_finite(t.u11);
-    ok = ok && flow_finite(t.v00) && flow_finite(t.v01) && flow_finite(t.v10) && flow_finite(t.v11);
-    ok = ok && flow_finite(t.m) && t.m > 0.f;
+    ok = ok && finite_f32(a.x) && finite_f32(a.y) && finite_f32(b.x) && finite_f32(b.y) && c.inside;
+    ok = ok && finite_f32(t.u00) && finite_f32(t.u01) && finite_f32(t.u10) && finite_f32(t.u11);
+    ok = ok && finite_f32(t.v00) && finite_f32(t.v01) && finite_f32(t.v10) && finite_f32(t.v11);
+    ok = ok && finite_f32(t.m) && t.m > 0.f;
     ok = ok && !(max_error > 0.f && !(e <= max_error));
     const float sx = t.m * (float)((rx > 0.f) - (rx < 0.f)), sy = t.m * (float)((ry > 0.f) - (ry < 0.f));
     // J_g in the cell: d(gu, gv) / d(x, y)
@@ -127,9 +111,9 @@ __global__ __launch_bounds__(FL_THREADS) void k_flow_loss_fwd(int T, int64_t P, 
     const int lp = (Vp ? Vp : reinterpret_cast<const int *>(Xp))[i], lc = (Vc ? Vc : reinterpret_cast<const int *>(Xc))[i],
               ln = (Vn ? Vn : reinterpret_cast<const int *>(Xn))[i];
     const int vp = Vp ? lp : 1, vc = Vc ? lc : 1, vn = Vn ? ln : 1;
-    const FlowProj pp = flow_project(px, py, pz, tab.full[tp], Wf, Hf);
-    const FlowProj pc = flow_project(cx, cy, cz, tab.full[t], Wf, Hf);
-    const FlowProj pn = flow_project(nx, ny, nz, tab.full[tn], Wf, Hf);
+    const PixelProj pp = project_pixel(px, py, pz, tab.full[tp], Wf, Hf);
+    const PixelProj pc = project_pixel(cx, cy, cz, tab.full[t], Wf, Hf);
+    const PixelProj pn = project_pixel(nx, ny, nz, tab.full[tn], Wf, Hf);
 
     // round 2: every tap of both pairs before the first one is used
     const FlowCell cell_a = flow_cell(pc, W, H), cell_b = flow_cell(pp, W, H);
@@ -158,14 +142,12 @@ __global__ __launch_bounds__(FL_THREADS) void k_flow_loss_fwd(int T, int64_t P, 
 
     float acc = on_a ? as_a.value : 0.f;
     int cnt = (on_a && as_a.valid) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = acc; s_cnt[threadIdx.x >> 6] = cnt; }
+    wave_sum_each(acc, cnt);
+    block_stash(s_sum, acc, s_cnt, cnt);
     __syncthreads();
     if (threadIdx.x == 0) {
-        float ts = 0.f;
-        int tc = 0;
-        for (int k = 0; k < FL_THREADS / 64; k++) { ts += s_sum[k]; tc += s_cnt[k]; }
+        const float ts = block_join<FL_THREADS>(s_sum, 0.f, OpSum{});
+        const int tc = block_join<FL_THREADS>(s_cnt, 0, OpSum{});
         const int64_t at = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
         partial[at] = ts;
         reinterpret_cast<int *>(partial + n_parts)[at] = tc;
@@ -183,14 +165,12 @@ __global__ __launch_bounds__(FL_THREADS) void k_flow_loss_finish(int64_t n_parts
     float ts = 0.f;
     int tc = 0;
     for (int64_t i = threadIdx.x; i < n_parts; i += FL_THREADS) { ts += partial[i]; tc += counts[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { ts += __shfl_xor(ts, o, 64); tc += __shfl_xor(tc, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = ts; s_cnt[threadIdx.x >> 6] = tc; }
+    wave_sum_each(ts, tc);
+    block_stash(s_sum, ts, s_cnt, tc);
     __syncthreads();
     if (threadIdx.x == 0) {
-        float ss = 0.f;
-        int sc = 0;
-        for (int k = 0; k < FL_THREADS / 64; k++) { ss += s_sum[k]; sc += s_cnt[k]; }
+        const float ss = block_join<FL_THREADS>(s_sum, 0.f, OpSum{});
+        const int sc = block_join<FL_THREADS>(s_cnt, 0, OpSum{});
         const float l = ss / n_pairs;
         out[0] = scale * l + (add ? add_weight * add[0] : 0.f);
         out[1] = l;

@@ -13,10 +13,9 @@
 // of step s is one conflict-free ds_read_b32 per column tile (32 consecutive columns at row k of W^T).  Bias + ReLU are
 // applied to the accumulators; each (register, lane-half) stores 32 consecutive floats of one output row.
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // sum over the 32 lanes of a half wave (lanes 0..31 / 32..63), result in every lane of the half: four DPP adds inside each
 // 16-lane row, then the gfx950 row swap folds rows 0|1 and 2|3 (cheaper than five ds_bpermute round trips)
@@ -24,7 +23,7 @@ template <int CTRL>
 __device__ __forceinline__ float l128_dpp_add(float v) {
     return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
 }
-__device__ __forceinline__ float half_sum(float v) {
+__device__ __forceinline__ float l128_half_sum(float v) {
     v = l128_dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
     v = l128_dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
     v = l128_dpp_add<0x141>(v);   // row_half_mirror
@@ -342,12 +341,12 @@ __global__ __launch_bounds__(B3 ? 512 : 256, 2) void k_linear128(int64_t M, cons
             }
             if (LN) {
                 float sum = (v[0] + v[1]) + (v[2] + v[3]);
-                sum = half_sum(sum);
+                sum = l128_half_sum(sum);
                 const float mean = sum * (1.f / GN);
                 float d[4], sq = 0.f;
 #pragma unroll
                 for (int c = 0; c < 4; c++) { d[c] = v[c] - mean; sq += d[c] * d[c]; }
-                sq = half_sum(sq);
+                sq = l128_half_sum(sq);
                 const float rstd = rsqrtf(sq * (1.f / GN) + eps);
                 if (ln_stats && r32 == 0 && orow < M) ln_stats[orow] = make_float2(mean, rstd);
 #pragma unroll
@@ -439,7 +438,7 @@ __global__ __launch_bounds__(256) void k_linear128_rows32(int64_t M, const float
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             float sum = v[r];
-            sum = half_sum(sum);
+            sum = l128_half_sum(sum);
             if (r32 == 0) s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sum;
         }
         __syncthreads();
@@ -449,7 +448,7 @@ __global__ __launch_bounds__(256) void k_linear128_rows32(int64_t M, const float
             mean[r] = ((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN);
             const float d = v[r] - mean[r];
             float sq = d * d;
-            sq = half_sum(sq);
+            sq = l128_half_sum(sq);
             if (r32 == 0) s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sq;
         }
         __syncthreads();
@@ -590,7 +589,7 @@ __global__ __launch_bounds__(256) void k_node_update(int64_t N, const float *__r
         for (int r = 0; r < 16; r++) {
             v[r] = acc[r] + bv;
             float sum = v[r];
-            sum = half_sum(sum);
+            sum = l128_half_sum(sum);
             if (r32 == 0) s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sum;
         }
     }
@@ -601,7 +600,7 @@ __global__ __launch_bounds__(256) void k_node_update(int64_t N, const float *__r
         mean[r] = ((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN);
         const float d = v[r] - mean[r];
         float sq = d * d;
-        sq = half_sum(sq);
+        sq = l128_half_sum(sq);
         if (r32 == 0) s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sq;
     }
     __syncthreads();                          // (also: every wave is done reading s_act)

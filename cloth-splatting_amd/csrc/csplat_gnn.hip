@@ -8,6 +8,7 @@
 // (ascending edge id) order, i.e. deterministic and without float atomics.  All kernels are HBM-bound row
 // movers: 16 B per lane, a row of L floats is read by L/4 consecutive lanes (full 128-B lines at L >= 32).
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 
@@ -71,8 +72,7 @@ __global__ __launch_bounds__(256) void k_edge_features_ordered(int64_t E, const 
         m = fmaxf(m, fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fmaxf(fabsf(dz), len)));
     }
     if (absmax) {
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+        block_stash(s_m, wave_max(m));
         __syncthreads();
         if (threadIdx.x == 0) {
             m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256) void k_rollout_head(int N, int H, int T, const
     }
     if (absmax) {       // (max |feature| as float bits: what the encoder's fp16 pieces are scaled by; zeroed by k_rollout_integrate / the caller)
         __shared__ float s_m[4];
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+        block_stash(s_m, wave_max(m));
         __syncthreads();
         if (threadIdx.x == 0) {
             m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
@@ -140,8 +139,7 @@ __global__ __launch_bounds__(256) void k_rollout_decode(int N, int D, const floa
         if (d < D) {
             const float4 w = reinterpret_cast<const float4 *>(W + (size_t)d * 128)[q];
             float t = a.x * w.x; t = t + a.y * w.y; t = t + a.z * w.z; t = t + a.w * w.w;
-            for (int o = 16; o > 0; o >>= 1) t = t + __shfl_xor(t, o, 32);
-            y[d] = t;
+            y[d] = wave_sum<32>(t);
         }
     bool ok = true;
     for (int d = 0; d < D; d++) {
@@ -271,8 +269,7 @@ __global__ __launch_bounds__(256) void k_gather_rows_absmax(int64_t E, int LV, c
         out[t] = v;
         m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > *reinterpret_cast<volatile unsigned *>(amax)) atomicMax(amax, __float_as_uint(m));
 }
 
@@ -528,11 +525,6 @@ int csplat_gnn_gather_rows_absmax(void *stream, int64_t E, int L, const float *r
 // A row = 32 lanes x float4; a wave holds two rows; row statistics by 5 xor-shuffles inside the 32-lane half.
 namespace {
 constexpr int LN_THREADS = 256, LN_ROWS_PER_BLOCK_ITER = LN_THREADS / 32;
-__device__ __forceinline__ float half_sum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __global__ __launch_bounds__(LN_THREADS) void k_ln128_fwd(int64_t M, const float4 *__restrict__ x, const float4 *__restrict__ gamma,
                                                            const float4 *__restrict__ beta, float eps, float4 *__restrict__ y,
                                                            float2 *__restrict__ stats) {
@@ -540,9 +532,9 @@ __global__ __launch_bounds__(LN_THREADS) void k_ln128_fwd(int64_t M, const float
     const float4 ga = gamma[sub], be = beta[sub];
     for (int64_t row = (int64_t)blockIdx.x * LN_ROWS_PER_BLOCK_ITER + (threadIdx.x >> 5); row < M; row += (int64_t)gridDim.x * LN_ROWS_PER_BLOCK_ITER) {
         const float4 v = x[row * 32 + sub];
-        const float mean = half_sum((v.x + v.y) + (v.z + v.w)) * (1.f / 128.f);
+        const float mean = wave_sum<32>((v.x + v.y) + (v.z + v.w)) * (1.f / 128.f);
         const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-        const float var = half_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) * (1.f / 128.f);
+        const float var = wave_sum<32>((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) * (1.f / 128.f);
         const float rstd = rsqrtf(var + eps);
         y[row * 32 + sub] = make_float4(d0 * rstd * ga.x + be.x, d1 * rstd * ga.y + be.y, d2 * rstd * ga.z + be.z, d3 * rstd * ga.w + be.w);
         if (sub == 0) stats[row] = make_float2(mean, rstd);
@@ -563,8 +555,8 @@ __global__ __launch_bounds__(LN_THREADS) void k_ln128_bwd(int64_t M, const float
         const float sub_mean = x_normalized ? 0.f : st.x, mul = x_normalized ? 1.f : st.y;   // x_normalized: x already is xhat
         const float h0 = (xv.x - sub_mean) * mul, h1 = (xv.y - sub_mean) * mul, h2 = (xv.z - sub_mean) * mul, h3 = (xv.w - sub_mean) * mul;
         const float w0 = gv.x * ga.x, w1 = gv.y * ga.y, w2 = gv.z * ga.z, w3 = gv.w * ga.w;
-        const float m1 = half_sum((w0 + w1) + (w2 + w3)) * (1.f / 128.f);
-        const float m2 = half_sum((w0 * h0 + w1 * h1) + (w2 * h2 + w3 * h3)) * (1.f / 128.f);
+        const float m1 = wave_sum<32>((w0 + w1) + (w2 + w3)) * (1.f / 128.f);
+        const float m2 = wave_sum<32>((w0 * h0 + w1 * h1) + (w2 * h2 + w3 * h3)) * (1.f / 128.f);
         const float4 dv = make_float4(st.y * (w0 - m1 - h0 * m2), st.y * (w1 - m1 - h1 * m2), st.y * (w2 - m1 - h2 * m2), st.y * (w3 - m1 - h3 * m2));
         dx[row * 32 + sub] = dv;
         ax.x += dv.x; ax.y += dv.y; ax.z += dv.z; ax.w += dv.w;

@@ -8,6 +8,7 @@
 // Sums: the L1, the image loss and the geometry loss leave one partial per workgroup, added in index order by a second, one-workgroup
 // launch (no ticket, no float atomics); the standalone SSIM hands its partials to the caller.  Only k_psnr still has a ticket.
 #include "csplat_common.h"
+#include "csplat_device.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -196,24 +197,13 @@ __device__ __forceinline__ void ssim_tile_fwd(int H, int W, const Taps &taps, co
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc_s += __shfl_xor(acc_s, o, 64);
-        if constexpr (L1) { acc_l += __shfl_xor(acc_l, o, 64); acc_q += __shfl_xor(acc_q, o, 64); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = acc_s;
-        if constexpr (L1) { s_red[1][threadIdx.x >> 6] = acc_l; s_red[2][threadIdx.x >> 6] = acc_q; }
-    }
+    if constexpr (L1) wave_sum_each(acc_s, acc_l, acc_q); else wave_sum_each(acc_s);
+    if constexpr (L1) block_stash(s_red[0], acc_s, s_red[1], acc_l, s_red[2], acc_q); else block_stash(s_red[0], acc_s);
     __syncthreads();
     if (threadIdx.x == 0) {
         const size_t nwg = (size_t)gridDim.y * gridDim.x * gridDim.z;
         const size_t me = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        for (int q = 0; q < NQ; q++) {
-            float t_ = 0.f;
-            for (int k = 0; k < IL_T / 64; k++) t_ += s_red[q][k];
-            partial[q * nwg + me] = t_;
-        }
+        for (int q = 0; q < NQ; q++) partial[q * nwg + me] = block_join<IL_T>(s_red[q], 0.f, OpSum{});
     }
 }
 
@@ -297,7 +287,7 @@ __global__ __launch_bounds__(IL_T) void k_image_loss_finish(size_t per_plane, in
     const size_t nwg = per_plane * planes;
     // (ONE workgroup pulls ~135 KB of partials: 16-byte loads, four of them in flight per thread -- with 4-byte loads in a dependent
     //  `t += p[i]` loop the five sums of a 3-camera step took 12.8 us)
-    auto block_sum = [&](const float *p, size_t lo, size_t hi) -> float {     // fixed-order sum of p[lo, hi)
+    auto range_sum = [&](const float *p, size_t lo, size_t hi) -> float {     // fixed-order sum of p[lo, hi)
         float t = 0.f;
         size_t a0 = lo + (((16u - (unsigned)((uintptr_t)(p + lo) & 15u)) & 15u) >> 2);      // first 16-byte-aligned element of p[lo ..
         if (a0 > hi) a0 = hi;
@@ -312,21 +302,16 @@ __global__ __launch_bounds__(IL_T) void k_image_loss_finish(size_t per_plane, in
         for (; i < n4; i += IL_T) { const float4 u = p4[i]; t += (u.x + u.y) + (u.z + u.w); }
         for (size_t j = lo + threadIdx.x; j < a0; j += IL_T) t += p[j];                    // <= 3 elements in front ...
         for (size_t j = a0 + (n4 << 2) + threadIdx.x; j < hi; j += IL_T) t += p[j];        // ... and behind the float4 body
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = t;
-        __syncthreads();
-        float r = 0.f;
-        for (int k = 0; k < IL_T / 64; k++) r += s_red[k];
-        return r;
+        __syncthreads();                                      // (s_red still holds the call before this one)
+        block_sum<IL_T, true>(s_red, t);
+        return t;
     };
-    const float ssim_sum = block_sum(partial, 0, nwg);
-    const float l1_sum = block_sum(partial + nwg, 0, nwg);
+    const float ssim_sum = range_sum(partial, 0, nwg);
+    const float l1_sum = range_sum(partial + nwg, 0, nwg);
     const int n_batch = planes / channels;
     double psnr_sum = 0.0;         // (a float sum of 21 845 images' PSNR, added one by one, is off by 1e-6 of its value)
     for (int b = 0; b < n_batch; b++) {
-        const float q = block_sum(partial + 2 * nwg, (size_t)b * channels * per_plane, (size_t)(b + 1) * channels * per_plane);
+        const float q = range_sum(partial + 2 * nwg, (size_t)b * channels * per_plane, (size_t)(b + 1) * channels * per_plane);
         const float mse = q / ((float)channels * (float)H * (float)W);
         psnr_sum += (double)(20.f * log10f(1.f / sqrtf(mse)));
     }
@@ -403,15 +388,12 @@ __global__ __launch_bounds__(L1_THREADS) void k_l1(int64_t n, const float *__res
         if (grad) grad[i] = sg(d) * m;
         if (sign8) sign8[i] = s8(d);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    block_sum<L1_THREADS>(s_red, acc);
     // one partial per workgroup; k_l1_finish (a second, one-workgroup launch) sums them in index order.  Rounds 1-4 had the LAST workgroup
     // to arrive do that behind a ticket: a device-scope release per workgroup, and on gfx950 a release writes the XCD's dirty L2 lines back
     // -- here the sign bytes this kernel has just stored and the image the compositing kernel wrote in front of it -- which made ~10 us of
     // fixed cost on a kernel that streams its 69 MB in ~14 us (24.8 us for four views, 15 us for ONE view: profiles/r04g, r05g).
-    if (threadIdx.x == 0) { float t_ = 0.f; for (int k_ = 0; k_ < L1_THREADS / 64; k_++) t_ += s_red[k_]; partial[blockIdx.x] = t_; }
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(L1_BLOCKS) void k_l1_finish(int nparts, const float *__restrict__ partial, float inv_n, float *__restrict__ loss) {
     __shared__ float s[L1_BLOCKS];
@@ -503,16 +485,11 @@ __global__ __launch_bounds__(GL_THREADS) void k_geom_loss_fwd(int64_t hw, GeomTa
             if (sg) sg[i] = (unsigned char)c;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc_d += __shfl_xor(acc_d, o, 64); acc_s += __shfl_xor(acc_s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = acc_d; s_red[1][threadIdx.x >> 6] = acc_s; }
-    __syncthreads();
+    block_sum<GL_THREADS>(s_red, acc_d, acc_s);
     if (threadIdx.x == 0) {
-        float td = 0.f, ts = 0.f;
-        for (int k = 0; k < GL_THREADS / 64; k++) { td += s_red[0][k]; ts += s_red[1][k]; }
         const int64_t at = (int64_t)(view0 + v) * gridDim.x + blockIdx.x;
-        partial[at] = td;
-        partial[n_parts + at] = ts;
+        partial[at] = acc_d;
+        partial[n_parts + at] = acc_s;
     }
 }
 
@@ -524,14 +501,9 @@ __global__ __launch_bounds__(GL_THREADS) void k_geom_loss_finish(int64_t n_parts
     __shared__ float s_red[2][GL_THREADS / 64];
     float td = 0.f, ts = 0.f;
     for (int64_t i = threadIdx.x; i < n_parts; i += GL_THREADS) { td += partial[i]; ts += partial[n_parts + i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { td += __shfl_xor(td, o, 64); ts += __shfl_xor(ts, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = td; s_red[1][threadIdx.x >> 6] = ts; }
-    __syncthreads();
+    block_sum<GL_THREADS>(s_red, td, ts);
     if (threadIdx.x == 0) {
-        float sd = 0.f, ss = 0.f;
-        for (int k = 0; k < GL_THREADS / 64; k++) { sd += s_red[0][k]; ss += s_red[1][k]; }
-        const float ld = sd / n_pixels, ls = ss / n_pixels;
+        const float ld = td / n_pixels, ls = ts / n_pixels;
         out[0] = weight * (lam_d * ld + lam_s * ls) + (add ? add_weight * add[0] : 0.f);
         out[1] = ld;
         out[2] = ls;
@@ -610,14 +582,9 @@ __global__ __launch_bounds__(1024) void k_psnr(int64_t n, const float *__restric
             acc += d * d;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    block_sum<1024>(s_red, acc);
     if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int k = 0; k < 16; k++) t += s_red[k];
-        partial[blockIdx.y * PSNR_BLOCKS + blockIdx.x] = t;
+        partial[blockIdx.y * PSNR_BLOCKS + blockIdx.x] = acc;
         __threadfence();
         s_last = atomicAdd(ticket + blockIdx.y, 1u) == gridDim.x - 1;
     }

@@ -26,6 +26,7 @@
 //   csplat_traj_smooth      k_traj_smooth      KBest, knn_scan_slabs(ExclNonFinite) per frame, then the weighted mean from the list
 //   csplat_fps, csplat_chamfer_fwd / _bwd      kernels of their own (k_fps, k_chamfer_*); the Chamfer backward sorts through a PairSortWs
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 constexpr int KNN_THREADS = 256;
@@ -122,10 +123,9 @@ template <int CAP> struct KBest {
 
 // ---- which candidates a scan leaves out, from the candidate's position in the array the scan walks and its squared distance.  A
 // left-out candidate is offered as (+inf, KNN_IDX_NONE): it changes nothing.
-__device__ __forceinline__ bool traj_finite(float v) { return fabsf(v) < __builtin_inff(); }   // (false for a NaN)
 struct ExclSelf { int self; __device__ __forceinline__ bool operator()(int pos, float) const { return pos == self; } };   // the query's own point
 struct ExclNone { __device__ __forceinline__ bool operator()(int, float) const { return false; } };
-struct ExclNonFinite { __device__ __forceinline__ bool operator()(int, float d) const { return !traj_finite(d); } };
+struct ExclNonFinite { __device__ __forceinline__ bool operator()(int, float d) const { return !finite_f32(d); } };
 
 // ---- the scans.  Each takes the lane's list BY VALUE and returns it (`b = knn_scan_...(b, ...)`).  With a `List &` parameter the
 // compiler keeps a second copy of the whole list live across the inner loop, `__restrict__` or not: measured, KBest<32> +24 VGPRs and
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_dist2(int P, const float *__res
 __device__ __forceinline__ void block_minmax6_store(const float (&mn)[3], const float (&mx)[3], float *__restrict__ dst) {
     __shared__ float s[6][4];
     for (int a = 0; a < 3; a++) {
-        float lo = mn[a], hi = mx[a];
+        float lo = mn[a], hi = mx[a];      // (its own loop: minimum and maximum in step; one after the other, wave_min then wave_max, timed above the parent)
         for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, 64)); hi = fmaxf(hi, __shfl_xor(hi, o, 64)); }
         if ((threadIdx.x & 63) == 0) { s[a][threadIdx.x >> 6] = lo; s[3 + a][threadIdx.x >> 6] = hi; }
     }
@@ -703,14 +703,8 @@ __global__ __launch_bounds__(CHAMFER_THREADS) void k_chamfer_fwd(int Q, const fl
         const float d = d2[i];
         acc += chamfer_weight(d, cap) != 0.f ? (double)d : 0.0;
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < CHAMFER_WAVES; w++) t += s_w[w];
-        loss[0] = (float)(t / (double)Q);
-    }
+    block_sum<CHAMFER_THREADS>(s_w, acc);
+    if (threadIdx.x == 0) loss[0] = (float)(acc / (double)Q);
 }
 
 // the term both gradients are made of: t_i = g (2/Q) w_i (q_i - p_idx[i])
@@ -896,7 +890,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_traj_smooth(int T, int N, int K
                 }
             }
             // a non-finite coordinate: every distance was a NaN or Inf, the list is empty and the point goes through as it is
-            const bool whole = traj_finite(x) && traj_finite(y) && traj_finite(z);
+            const bool whole = finite_f32(x) && finite_f32(y) && finite_f32(z);
             out[3 * row] = whole ? ax / sw : x;
             out[3 * row + 1] = whole ? ay / sw : y;
             out[3 * row + 2] = whole ? az / sw : z;

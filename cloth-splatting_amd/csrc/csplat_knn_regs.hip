@@ -34,6 +34,7 @@ __global__ __launch_bounds__(KR_THREADS) void k_knn_regs_keys(int64_t NK, int N,
 // ---- forward: one thread per pair, the T rows in order; three fp64 sums per workgroup, joined by the workgroup that arrives last
 // (ticket) in a fixed order: thread k takes partials k, k + 256, ... ascending, then the lanes' and waves' fixed tree.  The geometry of
 // the launch depends on N * K alone, so neither scheduling nor stream nor replay can change a bit.
+// (its own loops, not block_sum of csplat_device.h: with the three sums in step the forward timed 1-2 us above the parent's runs)
 __device__ __forceinline__ void kr_block_sum3(double (&acc)[3], double (*s_red)[KR_WAVES]) {
     for (int m = 0; m < 3; m++) {
         double v = acc[m];
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(KR_THREADS) void k_knn_regs_bwd(int T, int N, int K
             }
         }
     }
-    for (int o = G / 2; o > 0; o >>= 1) {
+    for (int o = G / 2; o > 0; o >>= 1) {      // (its own loop, not wave_sum<G> of csplat_device.h: one row of the cost table timed above the parent)
         for (int a = 0; a < 3; a++) am[a] += __shfl_xor(am[a], o, 64);
         if (dQ)
             for (int a = 0; a < 4; a++) aq[a] += __shfl_xor(aq[a], o, 64);

@@ -14,6 +14,7 @@
 // inputs it replaced (7800 -> ~550 per Gaussian) and a third of its registers.  Vertex gradients are scattered with float
 // atomics.  Both directions take the T cameras of a training step in one launch (vertices [T][V][3]).
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 
@@ -378,10 +379,7 @@ __global__ __launch_bounds__(256) void k_vertex_gather(int P, int V, const int *
             s0 += g[0]; s1 += g[1]; s2 += g[2];
         }
     }
-#pragma unroll
-    for (int m = 4; m >= 1; m >>= 1) {
-        s0 += __shfl_xor(s0, m, 64); s1 += __shfl_xor(s1, m, 64); s2 += __shfl_xor(s2, m, 64);
-    }
+    wave_sum_each<8>(s0, s1, s2);
     if (v < V && sub == 0) {
         float *o = d_verts + ((size_t)blockIdx.y * V + v) * 3;
         o[0] = s0; o[1] = s1; o[2] = s2;
@@ -395,11 +393,9 @@ __global__ __launch_bounds__(256) void k_project_points(int64_t n, const float *
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    const float hx = x * full[0] + y * full[4] + z * full[8] + full[12];
-    const float hy = x * full[1] + y * full[5] + z * full[9] + full[13];
-    const float hw = x * full[3] + y * full[7] + z * full[11] + full[15];
-    out[2 * i] = ((hx / hw + 1.f) * W - 1.f) * 0.5f;
-    out[2 * i + 1] = ((hy / hw + 1.f) * H - 1.f) * 0.5f;
+    const PixelProj p = project_pixel(x, y, z, full, W, H);
+    out[2 * i] = p.x;
+    out[2 * i + 1] = p.y;
 }
 
 }  // namespace

@@ -18,6 +18,7 @@
 // Algorithmic bytes: unproject, per pixel: 4 (depth) [+ 4 mask] read and 1 written, then 4 + 4 (depth, row) read and, per selected pixel,
 // 16 written; voxel, per point: 12 read and 12 written around an 8-pass sort of 12-byte pairs, 12 gathered; mark, per entry: 8 read.
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 #pragma clang fp contract(off)
 
@@ -26,8 +27,6 @@ namespace {
 constexpr int OB_THREADS = 256, OB_MIN_BLOCKS = 256;
 constexpr int OB_CELL_BITS = 21;
 constexpr uint64_t OB_KEY_RANGE = (uint64_t)1 << 63, OB_KEY_NONFINITE = OB_KEY_RANGE | 1u;      // above every cell's key, in this order
-
-__device__ __forceinline__ bool obs_finite(float v) { return fabsf(v) < __builtin_inff(); }      // (false for a NaN)
 
 template <typename T> struct ObsQuad { T v[4]; };
 
@@ -136,13 +135,9 @@ __global__ __launch_bounds__(OB_THREADS) void k_obs_points(int W, int64_t HW, co
 __device__ __forceinline__ void obs_block_min3(float m[3], float *__restrict__ out) {
     __shared__ float s_min[3][OB_THREADS / 64];
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m[a] = fminf(m[a], __shfl_xor(m[a], o, 64));
-        if ((threadIdx.x & 63) == 0) s_min[a][threadIdx.x >> 6] = m[a];
-    }
+    for (int a = 0; a < 3; a++) block_stash(s_min[a], wave_min(m[a]));
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 3) {                              // thread a joins axis a, from slot 0 on
         float r = s_min[threadIdx.x][0];
         for (int k = 1; k < OB_THREADS / 64; k++) r = fminf(r, s_min[threadIdx.x][k]);
         out[threadIdx.x] = r;
@@ -154,7 +149,7 @@ __global__ __launch_bounds__(OB_THREADS) void k_obs_min_part(int64_t M, const fl
     float m[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
     for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < M; i += (int64_t)gridDim.x * OB_THREADS) {
         const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
-        if (obs_finite(x) && obs_finite(y) && obs_finite(z)) { m[0] = fminf(m[0], x); m[1] = fminf(m[1], y); m[2] = fminf(m[2], z); }
+        if (finite_f32(x) && finite_f32(y) && finite_f32(z)) { m[0] = fminf(m[0], x); m[1] = fminf(m[1], y); m[2] = fminf(m[2], z); }
     }
     obs_block_min3(m, part + 3 * blockIdx.x);
 }
@@ -180,7 +175,7 @@ __global__ __launch_bounds__(OB_THREADS) void k_obs_keys(int64_t M, const float 
     if (i >= M) return;
     const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
     uint64_t key = OB_KEY_NONFINITE;
-    if (obs_finite(x) && obs_finite(y) && obs_finite(z)) {
+    if (finite_f32(x) && finite_f32(y) && finite_f32(z)) {
         const int64_t cx = obs_cell(x, origin[0], voxel), cy = obs_cell(y, origin[1], voxel), cz = obs_cell(z, origin[2], voxel);
         key = (cx < 0 || cy < 0 || cz < 0) ? OB_KEY_RANGE
                                            : ((uint64_t)cz << (2 * OB_CELL_BITS)) | ((uint64_t)cy << OB_CELL_BITS) | (uint64_t)cx;
@@ -234,8 +229,7 @@ __global__ __launch_bounds__(OB_THREADS) void k_obs_centroids(int64_t M, const f
         s[1] += points[3 * i + 1] - corner[1];
         s[2] += points[3 * i + 2] - corner[2];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s[0] += __shfl_xor(s[0], o, 64); s[1] += __shfl_xor(s[1], o, 64); s[2] += __shfl_xor(s[2], o, 64); }
+    wave_sum_each(s[0], s[1], s[2]);
     if (lane < 3) {
         const float n = (float)(hi - lo);
         const float sum = lane == 0 ? s[0] : (lane == 1 ? s[1] : s[2]);

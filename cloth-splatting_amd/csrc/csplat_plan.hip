@@ -18,6 +18,7 @@
 #include <initializer_list>
 
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 
@@ -32,25 +33,12 @@ __device__ __forceinline__ float plan_term(float p, float g, float w) {
     return w * (d * d);
 }
 
-// the workgroup's sum of the threads' partial sums, valid in thread 0: xor tree over the wave (every lane ends with the wave's sum), the
-// waves' sums added in wave order
-__device__ __forceinline__ float plan_block_sum(float acc) {
-    __shared__ float s_sum[PL_THREADS / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < PL_THREADS / 64; k++) t = t + s_sum[k];
-    return t;
-}
-
 // cost[b] = (keep ? cost[b] : 0) + w * (sum / 3N), by thread 0 of the candidate's workgroup
 __device__ __forceinline__ void plan_cost_store(float acc, int n3, float w, bool keep, float *__restrict__ cost_b) {
-    const float total = plan_block_sum(acc);
+    __shared__ float s_sum[PL_THREADS / 64];
+    block_sum<PL_THREADS>(s_sum, acc);
     if (threadIdx.x == 0) {
-        const float mean = total / (float)n3;
+        const float mean = acc / (float)n3;
         const float term = w * mean;
         *cost_b = keep ? *cost_b + term : term;
     }

@@ -11,17 +11,15 @@
 // Both are HBM-bound streams; a wavefront owns a row (64 lanes x float4 = the 256 inputs).  dh is reduced deterministically:
 // per-workgroup partials, then a fixed-order sum.
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 constexpr int SIM_K = 256;        // inputs of the layer (hidden width of the simulator MLP)
 constexpr int SIM_TMAX = 8;       // time rows per call
 constexpr int SIM_BLOCKS = 512;   // 2 workgroups per CU, 4 waves each, 4 rows in flight per wave: 32 KB of loads per CU
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
+// the four waves' slots joined pairwise: this file's own order (block_join of csplat_device.h goes in wave order from 0)
+__device__ __forceinline__ float sim_join4(const float *s) { return (s[0] + s[1]) + (s[2] + s[3]); }
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 
 template <int T>
@@ -199,11 +197,10 @@ __global__ __launch_bounds__(256) void k_cloth_regs(int T, int V, long long E, c
         atomicAdd(gt + b * 3, k_ * dx); atomicAdd(gt + b * 3 + 1, k_ * dy); atomicAdd(gt + b * 3 + 2, k_ * dz);
         atomicAdd(gt + a * 3, -k_ * dx); atomicAdd(gt + a * 3 + 1, -k_ * dy); atomicAdd(gt + a * 3 + 2, -k_ * dz);
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
+    block_stash(s_red, wave_sum(acc));
     __syncthreads();
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+        partial[blockIdx.x] = sim_join4(s_red);
         __threadfence();
         s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
     }
@@ -212,11 +209,10 @@ __global__ __launch_bounds__(256) void k_cloth_regs(int T, int V, long long E, c
     __threadfence();
     float s = 0.f;
     for (unsigned j = threadIdx.x; j < gridDim.x; j += 256) s += __builtin_nontemporal_load(partial + j);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+    block_stash(s_red, wave_sum(s));
     __syncthreads();
     if (threadIdx.x == 0) {
-        *loss = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+        *loss = sim_join4(s_red);
         *ticket = 0u;   // ready for the next call
     }
 }
@@ -291,12 +287,11 @@ __global__ __launch_bounds__(256) void k_cloth_regs_csr(int T, int V, long long 
         float *o = grad + ((size_t)t * V + v) * 3;
         o[0] = gx; o[1] = gy; o[2] = gz;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
+    block_stash(s_red, wave_sum(acc));
     __syncthreads();
     const unsigned nblocks = gridDim.x * gridDim.y, me = blockIdx.y * gridDim.x + blockIdx.x;
     if (threadIdx.x == 0) {
-        partial[me] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+        partial[me] = sim_join4(s_red);
         __threadfence();
         s_last = atomicAdd(ticket, 1u) == nblocks - 1;
     }
@@ -305,11 +300,10 @@ __global__ __launch_bounds__(256) void k_cloth_regs_csr(int T, int V, long long 
     __threadfence();
     float s = 0.f;
     for (unsigned j = threadIdx.x; j < nblocks; j += 256) s += __builtin_nontemporal_load(partial + j);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+    block_stash(s_red, wave_sum(s));
     __syncthreads();
     if (threadIdx.x == 0) {
-        *loss = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+        *loss = sim_join4(s_red);
         *ticket = 0u;
     }
 }

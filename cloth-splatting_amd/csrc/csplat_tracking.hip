@@ -7,36 +7,21 @@
 //                        counts: 88 us of a 97 us launch at 100 000 points x 12 frames; this launch replaced them)
 //   k_track_mte          one thread per ground-truth track g: its associated point's trajectory aligned by the reference's rule, the
 //                        per-frame errors and their mean over the frames, summed in increasing k
-//   k_track_mean         one workgroup: the mean of mte[G] in a fixed order (the twin of k_flow_loss_finish)
+//   k_track_mean         one workgroup: the mean of mte[G] in a fixed order
 // Every load is unconditional with its index clamped into the arrays; an invalid point is selected out, never branched around.  No float
 // atomics, no atomics at all: every output is bit-reproducible.
 // Algorithmic bytes: visibility, per (f, i): 12 (point) [+ 8 pixels_in] + 4 (depth tap) read, 8 (pixel) + 2 (bytes) written;
 // mte, per (k, g): 12 (gt) + 12 (traj row) + 16 (quaternion) read, 12 (aligned) + 4 (err) written.
 #include "csplat_common.h"
+#include "csplat_device.h"
 
 namespace {
 
 constexpr int TK_THREADS = 256, TK_BATCH = 8, TK_COUNT_THREADS = 1024;
 
-__device__ __forceinline__ bool track_finite(float v) { return fabsf(v) < __builtin_inff(); }      // (false for a NaN)
-
-struct TrackPixel { float x, y, w; };
-
-// k_project_points / flow_project: [X, 1] @ full, /w, ndc -> pixel (pixel centres at the integers).  `full` is wave-uniform
-__device__ __forceinline__ TrackPixel track_project(float x, float y, float z, const float *__restrict__ full, float W, float H) {
-    TrackPixel p;
-    const float hx = x * full[0] + y * full[4] + z * full[8] + full[12];
-    const float hy = x * full[1] + y * full[5] + z * full[9] + full[13];
-    const float hw = x * full[3] + y * full[7] + z * full[11] + full[15];
-    p.x = ((hx / hw + 1.f) * W - 1.f) * 0.5f;
-    p.y = ((hy / hw + 1.f) * H - 1.f) * 0.5f;
-    p.w = hw;
-    return p;
-}
-
 // 0 <= x < W, 0 <= y < H, both finite; `front` carries w > 0 when the pixel was projected here
 __device__ __forceinline__ bool track_in_image(float x, float y, bool front, float W, float H) {
-    return front && track_finite(x) && track_finite(y) && x >= 0.f && x < W && y >= 0.f && y < H;
+    return front && finite_f32(x) && finite_f32(y) && x >= 0.f && x < W && y >= 0.f && y < H;
 }
 
 // the depth tap of a pixel: C truncation, as the reference's astype(int).  A point that is not in the image reads pixel (0, 0); the
@@ -72,9 +57,9 @@ __global__ __launch_bounds__(TK_THREADS) void k_track_visibility(int64_t N, int 
 
     // round 1: the point (and its given pixel)
     const float px = points[3 * row], py = points[3 * row + 1], pz = points[3 * row + 2];
-    TrackPixel p;
+    PixelProj p;
     if (PROJECT) {
-        p = track_project(px, py, pz, full, Wf, Hf);
+        p = project_pixel(px, py, pz, full, Wf, Hf);
     } else {
         p.x = pixels_in[2 * row];
         p.y = pixels_in[2 * row + 1];
@@ -120,18 +105,13 @@ __device__ __forceinline__ int track_count_ones(const uint8_t *__restrict__ p, i
 // grid F, 1024 threads (a frame has one workgroup: the more loads it keeps in flight the better): counts[f] = (points in the image, points visible) of frame f -- integer sums, the same whatever the order
 __global__ __launch_bounds__(TK_COUNT_THREADS) void k_track_counts(int64_t N, const uint8_t *__restrict__ in_image,
                                                              const uint8_t *__restrict__ visible, int *__restrict__ counts) {
-    __shared__ int s_in[TK_COUNT_THREADS / 64], s_vis[TK_COUNT_THREADS / 64];
+    __shared__ int s_cnt[2][TK_COUNT_THREADS / 64];
     const int f = blockIdx.x;
     int ci = track_count_ones(in_image + (int64_t)f * N, N), cv = track_count_ones(visible + (int64_t)f * N, N);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { ci += __shfl_xor(ci, o, 64); cv += __shfl_xor(cv, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_in[threadIdx.x >> 6] = ci; s_vis[threadIdx.x >> 6] = cv; }
-    __syncthreads();
+    block_sum<TK_COUNT_THREADS>(s_cnt, ci, cv);
     if (threadIdx.x == 0) {
-        int ti = 0, tv = 0;
-        for (int k = 0; k < TK_COUNT_THREADS / 64; k++) { ti += s_in[k]; tv += s_vis[k]; }
-        counts[2 * f] = ti;
-        counts[2 * f + 1] = tv;
+        counts[2 * f] = ci;
+        counts[2 * f + 1] = cv;
     }
 }
 
@@ -220,15 +200,8 @@ __global__ __launch_bounds__(TK_THREADS) void k_track_mean(int64_t G, const floa
     __shared__ float s_sum[TK_THREADS / 64];
     float ts = 0.f;
     for (int64_t i = threadIdx.x; i < G; i += TK_THREADS) ts += mte[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ts += __shfl_xor(ts, o, 64);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = ts;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ss = 0.f;
-        for (int k = 0; k < TK_THREADS / 64; k++) ss += s_sum[k];
-        mean[0] = ss / (float)G;
-    }
+    block_sum<TK_THREADS>(s_sum, ts);
+    if (threadIdx.x == 0) mean[0] = ts / (float)G;
 }
 
 }  // namespace

@@ -89,7 +89,9 @@ def test_constants_of_the_hip_file_are_the_ones_the_reference_assumes(src):
     assert _one(src, r"if \(m > 0\.f && m < ([0-9.e]+)f\)") == "3.0e38"
     assert int(_one(src, r"nb < (\d+) \? nb : \d+\), (\d+), 0, s>>>")[0]) == R.ABSMAX_GRID_CAP
     assert int(_one(src, r"nb < (\d+) \? nb : \d+\), (\d+), 0, s>>>")[1]) == R.ABSMAX_LANES
-    assert "x < 0.f ? 0.f : x" in src                                    # relu_nan: a NaN passes
+    common = open(os.path.join(os.path.dirname(HIP), "csplat_common.h")).read()
+    assert "float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }" in common      # a NaN passes; the one ReLU of this file:
+    assert src.count("relu_keep_nan(acc[") == 6 and "float relu" not in src and "fmaxf(acc[" not in src
     assert R.GROUP == 8 and "((M + 7) / 8)" in src and "r0 / 8" in src
 
 

@@ -227,6 +227,19 @@ def test_kernels_against_restatement_every_shape(shape, variant):
     compare("flow_loss " + variant, c, run_kernel(c))
 
 
+# k_flow_loss_finish: 256 threads walk T * ceil(P / 256) partials.  One short of a full pass, a full pass, and a second pass of two
+# (257 is prime and T >= 2: 258 = 6 * 43 is the first count beyond 256 that frames x workgroups reach)
+FINISH_SHAPES = [(4099, 15, (37, 23)), (4096, 16, (37, 23)), (10753, 6, (37, 23))]
+
+
+@pytest.mark.parametrize("shape", FINISH_SHAPES, ids=str)
+def test_finish_kernel_at_255_256_and_258_partials(shape):
+    P, T, _ = shape
+    assert T * -(-P // 256) == {4099: 255, 4096: 256, 10753: 258}[P]
+    c = make_case(*shape, "plain")
+    compare("flow_loss plain", c, run_kernel(c))
+
+
 @pytest.mark.parametrize("variant", [v for v in VARIANTS if v not in ("plain", "mask_cap")])
 @pytest.mark.parametrize("shape", [(1, 2, (37, 23)), (257, 3, (37, 23)), (65, 16, (64, 48)), (4099, 3, (128, 96))], ids=str)
 def test_kernels_against_restatement_every_variant(shape, variant):

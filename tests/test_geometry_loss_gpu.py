@@ -193,6 +193,16 @@ def test_kernels_against_restatement(shape, variant):
     compare("geometry_loss " + variant, c, run_kernel(c))
 
 
+@pytest.mark.parametrize("shape", [(1, 255, 255), (1, 255, 257), (1, 59, 1111)], ids=str)
+def test_finish_kernel_at_255_256_and_257_partials(shape):
+    """one view, a pixel count that is no multiple of 4 (the elementwise path: a workgroup per 256 pixels): k_geom_loss_finish's 256 threads
+    walk one partial short of a pass, a full pass, and one partial of a second pass"""
+    V, H, W = shape
+    assert V == 1 and (H * W) % 4 != 0 and -(-(H * W) // 256) == {255: 255, 257: 256, 1111: 257}[W]
+    c = make_case(shape, "both")
+    compare("geometry_loss both", c, run_kernel(c))
+
+
 @pytest.mark.parametrize("variant", ["both", "mask_frac", "z_holes"])
 @pytest.mark.parametrize("shape", LARGE, ids=str)
 def test_kernels_beyond_the_workgroup_cap(shape, variant):

@@ -67,7 +67,9 @@ def test_the_size_tables_cross_the_launch_constants_of_the_source():
     src = open(os.path.join(ROOT, "cloth-splatting_amd", "csrc", "csplat_plan.hip")).read()
     m = re.search(r"constexpr int PL_THREADS = (\d+), PL_SEL_TILE = (\d+), PL_BATCH = (\d+);", src)
     assert m and tuple(int(x) for x in m.groups()) == (R.PL_THREADS, R.PL_SEL_TILE, R.PL_BATCH) == (256, 1024, 8)
-    assert "atomic" not in re.sub(r"//.*", "", src).lower()          # no atomics anywhere in the file
+    device = open(os.path.join(ROOT, "cloth-splatting_amd", "csrc", "csplat_device.h")).read()
+    assert '#include "csplat_device.h"' in src
+    assert "atomic" not in re.sub(r"//.*", "", src + device).lower()          # no atomics anywhere in the file, nor in the helpers it calls
     Bs, Ns, Hs = ({s[i] for s in R.INTEGRATE_SIZES} for i in range(3))
     assert {1, 2, 65} <= Bs and {1, 255, 256, 257, 1000} <= Ns and Hs == {1, 2, 3}
     # each value of one axis with the extremes of the two others

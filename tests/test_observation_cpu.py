@@ -343,7 +343,9 @@ def test_header_exports_and_bindings():
         assert word.lower() in block.lower(), word
     assert native.ABI_VERSION == 9 and native.lib.csplat_abi_version() == 9
     src = open(os.path.join(ROOT, "cloth-splatting_amd", "csrc", "csplat_observation.hip")).read()
+    device = open(os.path.join(ROOT, "cloth-splatting_amd", "csrc", "csplat_device.h")).read()
     code = re.sub(r"//.*", "", src)
+    assert '#include "csplat_device.h"' in code and "atomic" not in re.sub(r"//.*", "", device).lower()      # all the code the file runs
     assert "atomic" not in code.lower() and "#pragma clang fp contract(off)" in code and "__fdiv_rn(__fsub_rn(" in code
     assert ob.CELL_BITS == R.CELL_BITS == int(re.search(r"OB_CELL_BITS = (\d+)", src).group(1)) == 21
 

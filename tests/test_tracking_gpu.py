@@ -15,7 +15,7 @@ points uniform in x, y in [-2.4, 2.4], z in [2, 4], every 11th behind the camera
 pixels and a patch below min_depth; quaternions N(0, 1)^4, not normalised; many ground-truth tracks share a tracked point.
 
 Shapes.  One thread per (frame, point) or per ground-truth track, a 256-thread workgroup of 64-lane waves, no grid stride: N = 1, 63, 64,
-65, 255, 256, 257, 1000, 4099; F = 1, 2, 17; images 1x1, 5x1, 1x5, 37x23, 128x96; G = 1, 63, 64, 65, 257, 1000; T = 1, 2, 30; N = 1, 5, 1000
+65, 255, 256, 257, 1000, 4099; F = 1, 2, 17; images 1x1, 5x1, 1x5, 37x23, 128x96; G = 1, 63, 64, 65, 255, 256, 257, 1000; T = 1, 2, 30; N = 1, 5, 1000
 for the MTE.
 
 What the table showed on an MI355X when this file was written (largest e32 / bar / kernel error of a group; smallest bar / error):
@@ -208,7 +208,7 @@ def mte_check(c, group):
         assert torch.equal(got[0].cpu(), c.traj[:, c.assoc])
 
 
-GS, TS, MTE_NS = [1, 63, 64, 65, 257, 1000], [1, 2, 30], [1, 5, 1000]
+GS, TS, MTE_NS = [1, 63, 64, 65, 255, 256, 257, 1000], [1, 2, 30], [1, 5, 1000]      # (255, 256, 257: k_track_mean's 256 threads)
 MTE_CASES = [(G, 2, 5) for G in GS] + [(257, T, 1000) for T in TS] + [(65, 30, 1), (1000, 30, 1000), (64, 1, 5)]
 
 

@@ -417,6 +417,8 @@ def test_header_exports_and_bindings():
     code = re.sub(r"//.*", "", src)
     assert "atomic" not in code.lower() and "#pragma clang fp contract(off)" in code and "__fmul_rn(__fsub_rn(" in code and "k_traj_features" in code
     csrc = os.path.join(ROOT, "cloth-splatting_amd", "csrc")
+    device = re.sub(r"//.*", "", open(os.path.join(csrc, "csplat_device.h")).read())       # the helpers the smoothing kernel calls
+    assert "atomic" not in device.lower()
     knn = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.startswith("csplat_knn"))   # the knn sources
     smooth = re.sub(r"//.*", "", knn[knn.index("void k_traj_smooth("):knn.index('extern "C" int csplat_traj_smooth(')])
     assert "KBest<CAP>" in smooth and "knn_scan_slabs(" in smooth and "atomic" not in smooth.lower()
@@ -426,6 +428,47 @@ def test_header_exports_and_bindings():
     for fn in ("knn_scan_slabs", "knn_d2", "knn_box_d2"):                                      # (a definition starts its line with __device__)
         assert len(re.findall(r"^__device__[^\n;]*\b" + fn + r"\(", knn, flags=re.M)) == 1, fn
     assert du.FLT_MAX == R.FLT_MAX and du.GRIPPER_OFFSET == (0.0, -0.03, 0.02)
+
+
+def test_the_device_helpers_are_defined_once_and_used_not_copied():
+    """csplat_device.h holds the wave and block reductions, the pixel projection and the finite test: one definition of each in csrc/
+    (the rasterizer's files, which do not include it and keep their own reductions, aside), and no butterfly written out again in a file
+    that includes it"""
+    csrc = os.path.join(ROOT, "cloth-splatting_amd", "csrc")
+    text = {f: re.sub(r"//.*", "", open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc))
+            if f.endswith((".hip", ".h")) and not f.startswith(("csplat_raster", "csplat_k8_views_body"))}
+    everything = "\n".join(text.values())
+    overloads = {"block_put": 2, "block_sum": 2}                    # (the end of block_put's recursion; block_sum for one plain row of slots)
+    for fn in ("finite_f32", "wave_reduce_each", "wave_reduce", "wave_sum", "wave_min", "wave_max", "wave_sum_each", "block_put", "block_stash",
+               "block_join", "block_sum", "project_pixel", "relu_keep_nan"):      # (a definition starts its line with `template <...>` or __device__)
+        where = [f for f, t in text.items() for _ in re.findall(r"^(?:template <[^\n]*> )?__device__[^\n;(]*\b" + fn + r"\(", t, flags=re.M)]
+        assert where == (["csplat_common.h"] if fn == "relu_keep_nan" else ["csplat_device.h"] * overloads.get(fn, 1)), (fn, where)
+    for once in ("struct PixelProj", "typedef float f32x16", "struct OpSum", "struct OpMin", "struct OpMax"):
+        assert everything.count(once) == 1 and once in text["csplat_device.h"], once
+    # a (value, index) pair does not fit the helpers: the farthest point of k_fps (csplat_knn.hip), the apex and the nearest point of the
+    # triangulation (csplat_delaunay.hip).  Kept for speed, each with a comment that says so: the minimum and maximum in step of
+    # block_minmax6_store (csplat_knn.hip), the block sum and the G-lane sums of the regularisers (csplat_knn_regs.hip)
+    allowed = {"csplat_device.h": [r"v = op\(v, __shfl_xor\(v, o, 64\)\)"],
+               "csplat_knn.hip": [r"const float ov = __shfl_xor\(bv, o, 64\);", r"const int oi = __shfl_xor\(bi, o, 64\);"] * 2 +
+                                 [r"lo = fminf\(lo, __shfl_xor\(lo, o, 64\)\); hi = fmaxf\(hi, __shfl_xor\(hi, o, 64\)\);"],
+               "csplat_knn_regs.hip": [r"v \+= __shfl_xor\(v, o, 64\);", r"am\[a\] \+= __shfl_xor\(am\[a\], o, 64\);",
+                                       r"aq\[a\] \+= __shfl_xor\(aq\[a\], o, 64\);"],
+               "csplat_delaunay.hip": [r"const int other = __shfl_xor\(best, off, CSPLAT_WAVE\);"] * 2}
+    in_scope = ("csplat_device.h", "csplat_sim.hip", "csplat_gnn.hip", "csplat_plan.hip", "csplat_observation.hip", "csplat_knn.hip",
+                "csplat_knn_regs.hip", "csplat_image.hip", "csplat_tracking.hip", "csplat_flow_loss.hip", "csplat_mesh.hip", "csplat_delaunay.hip",
+                "csplat_edge_mlp.hip", "csplat_gemm.hip")
+    for f in in_scope:
+        rest = text[f]
+        for pat in allowed.get(f, []):
+            assert re.search(pat, rest), (f, pat)
+            rest = re.sub(pat, "", rest, count=1)
+        assert "__shfl_xor(" not in rest, f
+        assert f in ("csplat_device.h", "csplat_knn_regs.hip") or '#include "csplat_device.h"' in rest, f
+    for f, t in text.items():                                       # (the raw text: a comment says why a site stayed)
+        raw = open(os.path.join(csrc, f)).read()
+        kept = len(re.findall(r"its own loops?[,:]? not \w+(?:<G>)? of csplat_device\.h|its own loop: minimum and maximum in step", raw))
+        assert kept == {"csplat_knn.hip": 1, "csplat_knn_regs.hip": 2}.get(f, 0), (f, kept)
+    assert "fp contract" not in text["csplat_device.h"] and "half_sum(" not in text["csplat_gnn.hip"]
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():
