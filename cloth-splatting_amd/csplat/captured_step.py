@@ -132,10 +132,7 @@ class CapturedStep:
             counts = [1, 1, 1, 1] + [3] * T
             n = len(srcs)
             keep = [t if t.dtype in (torch.float32, torch.int32) else t.float() for t in srcs]
-            pp = (C.c_void_p * n)(*[t.data_ptr() for t in keep])
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_gather_words(_n.stream_handle(dev), n, C.cast(pp, C.c_void_p), C.cast((C.c_int * n)(*kinds), C.c_void_p),
-                                                    C.cast((C.c_int * n)(*counts), C.c_void_p), _n.ptr(st["packed"])), "csplat_gather_words")
+            _n.launch("csplat_gather_words", dev, n, _n.ptr_table(keep), (C.c_int * n)(*kinds), (C.c_int * n)(*counts), _n.ptr(st["packed"]))
             # two copy nodes: the line, then the word the host spins on -- when the second has landed the first has
             st["host"].copy_(st["packed"], non_blocking=True)
             st["host_seq"].copy_(st["packed"][0:1], non_blocking=True)

@@ -21,12 +21,8 @@ def _cloth_regs_for(ctx, D, edge_index, rest_len, lams, csr, defer):
 
     def launch():
         with _n.on_device(dev):
-            key = ("regs", dev, skey, T, V, E)
-            scratch = _IMG_SCRATCH.get(key)          # zeroed once per (device, stream, sizes): the kernel leaves its ticket at zero
-            if scratch is None:
-                if len(_IMG_SCRATCH) >= 64:
-                    _n.evict_scratch(_IMG_SCRATCH)
-                scratch = _IMG_SCRATCH[key] = torch.zeros(_n.lib.csplat_cloth_regs_scratch_bytes(T, V, E), dtype=torch.uint8, device=dev)
+            # zeroed once per (device, stream, sizes): the kernel leaves its ticket at zero
+            scratch = _IMG_SCRATCH.buffer(dev, ("regs", T, V, E), lambda: _n.lib.csplat_cloth_regs_scratch_bytes(T, V, E), stream=skey)
             _n.check(_n.lib.csplat_cloth_regs(stream, T, V, E, _n.ptr(D), _n.ptr(ei), _n.ptr(rl), *[float(v) for v in lams], _n.ptr(loss),
                                               _n.ptr(grad), _n.ptr(scratch), *([None] * 4 if csr is None else [_n.ptr(c) for c in csr])),
                      "csplat_cloth_regs")

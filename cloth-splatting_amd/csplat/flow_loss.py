@@ -1,8 +1,6 @@
 """Optical-flow supervision of the Gaussians' motion between the frames of a step (csplat_flow_loss_fwd / _bwd, include/csplat.h): the
 FlowLoss node, the `where`-based torch composition of the same formulas, and flow_losses(), which validates the arguments and chooses
 between them.  Re-exported by csplat.train, whose train_step adds the term when opt.lambda_flow is > 0."""
-import ctypes as C
-
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -10,26 +8,8 @@ from . import native as _n
 
 
 MAX_FRAMES = 16          # csplat_flow_loss.hip: FL_FRAMES
-_FLOW_SCRATCH = {}
-_n.TICKET_CACHES.append(_FLOW_SCRATCH)
-
-
-def _flow_scratch(dev, T, P):
-    """workgroup partials of csplat_flow_loss_fwd: one buffer per (device, stream, frames, Gaussians)"""
-    key = (dev, _n.scratch_stream(dev), T, P)
-    buf = _FLOW_SCRATCH.get(key)
-    if buf is None:
-        if len(_FLOW_SCRATCH) >= 64:
-            _n.evict_scratch(_FLOW_SCRATCH)
-        buf = _FLOW_SCRATCH[key] = torch.zeros(int(_n.lib.csplat_flow_loss_scratch_bytes(T, P)), dtype=torch.uint8, device=dev)
-    return buf
-
-
-def _ptr_table(tensors):
-    """host array of device pointers; a None entry is NULL, no list is NULL"""
-    if tensors is None:
-        return None
-    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+# workgroup partials of csplat_flow_loss_fwd: one buffer per (device, stream, frames, Gaussians)
+_FLOW_SCRATCH = _n.ScratchCache(cap=64)
 
 
 class FlowLoss(torch.autograd.Function):
@@ -57,8 +37,8 @@ class FlowLoss(torch.autograd.Function):
         count = torch.empty(1, dtype=torch.int32, device=dev)
         unit = torch.empty(T, P, 3, dtype=torch.float32, device=dev) if need else None
         addc = None if add is None else add.reshape(1).float()
-        scratch = _flow_scratch(dev, T, P)
-        _n.launch("csplat_flow_loss_fwd", dev, T, P, W, H, _ptr_table(X), _ptr_table(full), _ptr_table(F), _ptr_table(vis), _ptr_table(M),
+        scratch = _FLOW_SCRATCH.buffer(dev, (T, P), lambda: _n.lib.csplat_flow_loss_scratch_bytes(T, P))
+        _n.launch("csplat_flow_loss_fwd", dev, T, P, W, H, _n.ptr_table(X), _n.ptr_table(full), _n.ptr_table(F), _n.ptr_table(vis), _n.ptr_table(M),
                   float(cap), float(lam), float(weight), _n.ptr(addc), float(add_weight), _n.ptr(unit), _n.ptr(scratch), _n.ptr(out),
                   _n.ptr(count))
         ctx.save_for_backward(unit)

@@ -35,10 +35,8 @@ class MeshTransform(torch.autograd.Function):
         P = int(vid.shape[0])
         xyz = torch.empty((T, P, 3) if batched else (P, 3), dtype=torch.float32, device=vertices.device)
         quat = torch.empty((T, P, 4) if batched else (P, 4), dtype=torch.float32, device=vertices.device)
-        with _n.on_device(vertices.device):
-            _n.check(_n.lib.csplat_mesh_transform_fwd_views(_n.stream_handle(vertices.device), T, P, V, _n.ptr(vid),
-                                                            _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation), _n.ptr(rest),
-                                                            _n.ptr(xyz), _n.ptr(quat)), "csplat_mesh_transform_fwd_views")
+        _n.launch("csplat_mesh_transform_fwd_views", vertices.device, T, P, V, _n.ptr(vid), _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation),
+                  _n.ptr(rest), _n.ptr(xyz), _n.ptr(quat))
         ctx.save_for_backward(vertices, bary, rotation, vid, rest, rowptr, corners)
         ctx.dims = (T, P, V)
         return xyz, quat
@@ -54,12 +52,9 @@ class MeshTransform(torch.autograd.Function):
         scratch = None if rowptr is None else torch.empty(max(corner_scratch_floats(T, P), 1), dtype=torch.float32, device=vertices.device)
         g_xyz = None if g_xyz is None else g_xyz.contiguous().float()
         g_quat = None if g_quat is None else g_quat.contiguous().float()
-        with _n.on_device(vertices.device):
-            _n.check(_n.lib.csplat_mesh_transform_bwd_views(_n.stream_handle(vertices.device), T, P, V, _n.ptr(vid),
-                                                            _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation), _n.ptr(rest),
-                                                            _n.ptr(g_xyz), _n.ptr(g_quat), _n.ptr(d_v), _n.ptr(d_b), _n.ptr(d_r),
-                                                            _n.ptr(rowptr), _n.ptr(corners), _n.ptr(scratch)),
-                     "csplat_mesh_transform_bwd_views")
+        _n.launch("csplat_mesh_transform_bwd_views", vertices.device, T, P, V, _n.ptr(vid), _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation),
+                  _n.ptr(rest), _n.ptr(g_xyz), _n.ptr(g_quat), _n.ptr(d_v), _n.ptr(d_b), _n.ptr(d_r), _n.ptr(rowptr), _n.ptr(corners),
+                  _n.ptr(scratch))
         return d_v, d_b, d_r, None, None, None, None
 
 
@@ -95,10 +90,8 @@ class MeshTransformViews(torch.autograd.Function):
         T, V, P = int(vertices.shape[0]), int(vertices.shape[1]), int(vid.shape[0])
         xyz = torch.empty(T, P, 3, dtype=torch.float32, device=vertices.device)
         quat = torch.empty(T, P, 4, dtype=torch.float32, device=vertices.device)
-        with _n.on_device(vertices.device):
-            _n.check(_n.lib.csplat_mesh_transform_fwd_views(_n.stream_handle(vertices.device), T, P, V, _n.ptr(vid),
-                                                            _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation), _n.ptr(rest),
-                                                            _n.ptr(xyz), _n.ptr(quat)), "csplat_mesh_transform_fwd_views")
+        _n.launch("csplat_mesh_transform_fwd_views", vertices.device, T, P, V, _n.ptr(vid), _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation),
+                  _n.ptr(rest), _n.ptr(xyz), _n.ptr(quat))
         ctx.save_for_backward(vertices, bary, rotation, vid, rest, rowptr, corners)
         ctx.dims = (T, P, V)
         ctx.set_materialize_grads(False)
@@ -137,9 +130,8 @@ def _act_fwd(op_raw, sc_raw, f_dc, f_rest):
     P = op_raw.shape[0]
     opacity, scales = torch.empty_like(op_raw), torch.empty_like(sc_raw)
     shs = torch.empty(P, 16, 3, dtype=torch.float32, device=op_raw.device)
-    with _n.on_device(op_raw.device):
-        _n.check(_n.lib.csplat_gauss_act_fwd(_n.stream_handle(op_raw.device), P, _n.ptr(op_raw), _n.ptr(sc_raw), _n.ptr(f_dc),
-                                             _n.ptr(f_rest), _n.ptr(opacity), _n.ptr(scales), _n.ptr(shs)), "csplat_gauss_act_fwd")
+    _n.launch("csplat_gauss_act_fwd", op_raw.device, P, _n.ptr(op_raw), _n.ptr(sc_raw), _n.ptr(f_dc), _n.ptr(f_rest), _n.ptr(opacity),
+              _n.ptr(scales), _n.ptr(shs))
     return opacity, scales, shs
 
 
@@ -150,10 +142,8 @@ def _act_bwd(opacity, scales, g_op, g_sc, g_shs, sinks=(None, None, None, None))
     d_op, d_sc = _n.grad_out(sinks[0], opacity.shape, dev), _n.grad_out(sinks[1], scales.shape, dev)
     d_dc = _n.grad_out(sinks[2], (P, 1, 3), dev)
     d_rest = _n.grad_out(sinks[3], (P, 15, 3), dev)
-    with _n.on_device(dev):
-        _n.check(_n.lib.csplat_gauss_act_bwd(_n.stream_handle(dev), P, _n.ptr(opacity), _n.ptr(scales), _n.ptr(g_op), _n.ptr(g_sc),
-                                             _n.ptr(g_shs), _n.ptr(d_op), _n.ptr(d_sc), _n.ptr(d_dc), _n.ptr(d_rest)),
-                 "csplat_gauss_act_bwd")
+    _n.launch("csplat_gauss_act_bwd", dev, P, _n.ptr(opacity), _n.ptr(scales), _n.ptr(g_op), _n.ptr(g_sc), _n.ptr(g_shs), _n.ptr(d_op),
+              _n.ptr(d_sc), _n.ptr(d_dc), _n.ptr(d_rest))
     return d_op, d_sc, d_dc, d_rest
 
 
@@ -187,10 +177,8 @@ class GaussianStepInputs(torch.autograd.Function):
         T, V, P = int(vertices.shape[0]), int(vertices.shape[1]), int(vid.shape[0])
         xyz = torch.empty(T, P, 3, dtype=torch.float32, device=vertices.device)
         quat = torch.empty(T, P, 4, dtype=torch.float32, device=vertices.device)
-        with _n.on_device(vertices.device):
-            _n.check(_n.lib.csplat_mesh_transform_fwd_views(_n.stream_handle(vertices.device), T, P, V, _n.ptr(vid),
-                                                            _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation), _n.ptr(rest),
-                                                            _n.ptr(xyz), _n.ptr(quat)), "csplat_mesh_transform_fwd_views")
+        _n.launch("csplat_mesh_transform_fwd_views", vertices.device, T, P, V, _n.ptr(vid), _n.ptr(vertices), _n.ptr(bary), _n.ptr(rotation),
+                  _n.ptr(rest), _n.ptr(xyz), _n.ptr(quat))
         opacity, scales, shs = _act_fwd(op_raw, sc_raw, f_dc, f_rest)
         ctx.save_for_backward(vertices, bary, rotation, vid, rest, rowptr, corners, opacity, scales)
         ctx.dims = (T, P, V)
@@ -405,10 +393,8 @@ class MeshGaussians(DensifyMixin):
         key = (fi._version, mp._version, int(fi.shape[0]))
         if r is None or r[0] != key or r[5] is not fi or r[6] is not mp:
             vid = self._vertex_ids().contiguous()
-            rest = torch.empty(max(int(_n.lib.csplat_mesh_rest_bytes(vid.shape[0])), 256), dtype=torch.uint8, device=vid.device)
-            with _n.on_device(vid.device):
-                _n.check(_n.lib.csplat_mesh_rest(_n.stream_handle(vid.device), int(vid.shape[0]), _n.ptr(vid),
-                                                 _n.ptr(self.mesh.pos.contiguous().float()), _n.ptr(rest)), "csplat_mesh_rest")
+            rest = _n.temp(vid.device, _n.lib.csplat_mesh_rest_bytes(vid.shape[0]))
+            _n.launch("csplat_mesh_rest", vid.device, int(vid.shape[0]), _n.ptr(vid), _n.ptr(self.mesh.pos.contiguous().float()), _n.ptr(rest))
             # vertex <- (Gaussian, corner) incidence, grouped by vertex in ascending pair order: the backward gathers the
             # vertex gradients through it instead of scattering them with atomics (static until the next densification)
             flat = vid.reshape(-1).contiguous()

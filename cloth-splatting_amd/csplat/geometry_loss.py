@@ -1,31 +1,14 @@
 """Depth and silhouette supervision of a step's views (csplat_geom_loss_fwd / _bwd, include/csplat.h): the GeometryLoss node, the
 float64 composition of the same formulas, and geometry_losses(), which validates the views and chooses between them.  Re-exported by
 csplat.train, whose train_step adds the term when opt.lambda_depth / opt.lambda_silhouette are > 0."""
-import ctypes as C
-
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import native as _n
 
 
-_GEOM_SCRATCH = {}
-_n.TICKET_CACHES.append(_GEOM_SCRATCH)
-
-
-def _geom_scratch(dev, V, hw):
-    """workgroup partials of csplat_geom_loss_fwd: one buffer per (device, stream, views, pixels)"""
-    key = (dev, _n.scratch_stream(dev), V, hw)
-    buf = _GEOM_SCRATCH.get(key)
-    if buf is None:
-        if len(_GEOM_SCRATCH) >= 64:
-            _n.evict_scratch(_GEOM_SCRATCH)
-        buf = _GEOM_SCRATCH[key] = torch.zeros(int(_n.lib.csplat_geom_loss_scratch_bytes(V, hw)), dtype=torch.uint8, device=dev)
-    return buf
-
-
-def _ptr_table(tensors):
-    return None if not tensors else (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+# workgroup partials of csplat_geom_loss_fwd: one buffer per (device, stream, views, pixels)
+_GEOM_SCRATCH = _n.ScratchCache(cap=64)
 
 
 class GeometryLoss(torch.autograd.Function):
@@ -50,8 +33,8 @@ class GeometryLoss(torch.autograd.Function):
         out = torch.empty(3, dtype=torch.float32, device=dev)
         sign = torch.empty(V * hw, dtype=torch.uint8, device=dev) if need else None
         addc = None if add is None else add.reshape(1).float()
-        scratch = _geom_scratch(dev, V, hw)
-        _n.launch("csplat_geom_loss_fwd", dev, V, hw, _ptr_table(D if Z else []), _ptr_table(A), _ptr_table(Z), _ptr_table(S), _ptr_table(M),
+        scratch = _GEOM_SCRATCH.buffer(dev, (V, hw), lambda: _n.lib.csplat_geom_loss_scratch_bytes(V, hw))
+        _n.launch("csplat_geom_loss_fwd", dev, V, hw, _n.ptr_table(D if Z else []), _n.ptr_table(A), _n.ptr_table(Z), _n.ptr_table(S), _n.ptr_table(M),
                   float(lam_d), float(lam_s), float(weight), _n.ptr(addc), float(add_weight), _n.ptr(sign), _n.ptr(scratch), _n.ptr(out))
         ctx.save_for_backward(sign, *Z, *M)
         ctx.dims = (V, hw, float(lam_d) if Z else 0.0, float(lam_s) if S else 0.0, float(weight), float(add_weight), len(Z), len(M),
@@ -77,7 +60,7 @@ class GeometryLoss(torch.autograd.Function):
             dev = sign.device
             gD = torch.empty(V, hw, dtype=torch.float32, device=dev) if want_d else None
             gA = torch.empty(V, hw, dtype=torch.float32, device=dev) if want_a else None
-            _n.launch("csplat_geom_loss_bwd", dev, V, hw, _n.ptr(sign), _ptr_table(Z), _ptr_table(M), lam_d, lam_s, weight, _n.ptr(g),
+            _n.launch("csplat_geom_loss_bwd", dev, V, hw, _n.ptr(sign), _n.ptr_table(Z), _n.ptr_table(M), lam_d, lam_s, weight, _n.ptr(g),
                       _n.ptr(gD), _n.ptr(gA))
         grads = []
         for k, buf in enumerate((gD, gA)):      # every view's gradient is a slice of the one buffer the launch wrote

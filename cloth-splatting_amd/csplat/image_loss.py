@@ -50,19 +50,10 @@ def _taps(window_size=11, sigma=1.5):
     return _TAPS[window_size]
 
 
-_L1_SCRATCH = {}
-_n.TICKET_CACHES.append(_L1_SCRATCH)
-
-
-def _l1_scratch(device):
-    """workgroup partial sums of csplat_l1 for the CURRENT stream of `device` (launches on one stream cannot overlap): one buffer per
-    stream instead of an allocation per loss.  (Rounds 1-4 kept a ticket counter here too; since round 5 a second one-workgroup launch sums
-    the partials -- the ticket's device-scope release cost ~10 us of L2 write-back per call, csrc/csplat_image.hip.)"""
-    key = (str(device), _n.scratch_stream(device))
-    buf = _L1_SCRATCH.get(key)
-    if buf is None:
-        buf = _L1_SCRATCH[key] = torch.zeros(int(_n.lib.csplat_l1_scratch_bytes()) // 4, dtype=torch.int32, device=device)
-    return buf
+# workgroup partial sums of csplat_l1 for the stream the work runs on (launches on one stream cannot overlap): one buffer per stream
+# instead of an allocation per loss.  (Rounds 1-4 kept a ticket counter here too; since round 5 a second one-workgroup launch sums the
+# partials -- the ticket's device-scope release cost ~10 us of L2 write-back per call, csrc/csplat_image.hip.)
+_L1_SCRATCH = _n.ScratchCache()
 
 
 class FusedL1(torch.autograd.Function):
@@ -77,7 +68,7 @@ class FusedL1(torch.autograd.Function):
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         a, b = a.contiguous(), b.contiguous()
         mask = None if mask is None else mask.contiguous()
-        scratch = _l1_scratch(a.device)
+        scratch = _L1_SCRATCH.buffer(a.device, (), _n.lib.csplat_l1_scratch_bytes)
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         if mask is not None:
             B, Cc, hw, mc = _mask_layout(a, mask)
@@ -196,20 +187,8 @@ class FusedSSIM(torch.autograd.Function):
         return dx, None
 
 
-_IMG_SCRATCH = {}
-_n.TICKET_CACHES.append(_IMG_SCRATCH)
-
-
-def _image_loss_scratch(dev, shape):
-    """workgroup partials of csplat_image_loss_fwd: one buffer per (device, stream, shape)"""
-    B, Cc, H, W = shape
-    key = (dev, _n.scratch_stream(dev), B, Cc, H, W)
-    buf = _IMG_SCRATCH.get(key)
-    if buf is None:
-        if len(_IMG_SCRATCH) >= 64:
-            _n.evict_scratch(_IMG_SCRATCH)
-        buf = _IMG_SCRATCH[key] = torch.zeros(int(_n.lib.csplat_image_loss_scratch_bytes(B, Cc, H, W)), dtype=torch.uint8, device=dev)
-    return buf
+# workgroup partials of csplat_image_loss_fwd, one buffer per (device, stream, shape); csplat.cloth_regs keeps its own here, under a "regs" tag
+_IMG_SCRATCH = _n.ScratchCache(cap=64)
 
 
 class FusedImageLoss(torch.autograd.Function):
@@ -235,7 +214,7 @@ class FusedImageLoss(torch.autograd.Function):
         p = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=dev) if need else None
         sign = torch.empty(x.shape, dtype=torch.int8, device=dev) if need else None
         addc = None if add is None else add.reshape(1).float()
-        scratch = _image_loss_scratch(dev, (B, Cc, H, W))
+        scratch = _IMG_SCRATCH.buffer(dev, (B, Cc, H, W), lambda: _n.lib.csplat_image_loss_scratch_bytes(B, Cc, H, W))
         _n.launch("csplat_image_loss_fwd", dev, B, Cc, H, W, _taps(), _n.ptr(x), _n.ptr(y), _n.ptr(mask), mc, float(lam), float(img_weight),
                   _n.ptr(addc), float(add_weight), float(psnr_scale), *([_n.ptr(p[k]) for k in range(3)] if need else [None] * 3),
                   _n.ptr(sign), _n.ptr(scratch), _n.ptr(out))
@@ -311,7 +290,7 @@ def psnr(img1, img2):
         a, b = img1.contiguous(), img2.contiguous()
         B = int(a.shape[0])
         out = torch.empty(B, 1, dtype=torch.float32, device=a.device)
-        scratch = torch.empty(_n.lib.csplat_psnr_scratch_bytes(B), dtype=torch.uint8, device=a.device)
+        scratch = _n.temp(a.device, _n.lib.csplat_psnr_scratch_bytes(B))
         _n.launch("csplat_psnr", a.device, B, a.numel() // B, _n.ptr(a), _n.ptr(b), _n.ptr(scratch), _n.ptr(out))
         return out
     _n.composed_fallback("train.psnr", "dtype" if img1.shape == img2.shape and img1.numel() else "shape", img1)

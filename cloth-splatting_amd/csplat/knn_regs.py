@@ -41,10 +41,9 @@ class NeighbourGraph:
             d0, w = torch.empty_like(d2), torch.empty_like(d2)
         off = torch.empty(N + 1, dtype=torch.int32, device=dev)
         ent = torch.empty(N * K, dtype=torch.int32, device=dev)
-        with _n.on_device(dev):
-            temp = torch.empty(int(_n.lib.csplat_knn_regs_graph_temp_bytes(N, K)), dtype=torch.uint8, device=dev)
-            _n.check(_n.lib.csplat_knn_regs_graph(_n.stream_handle(dev), N, K, _n.ptr(idx32), _n.ptr(d2), float(lambda_w), _n.ptr(d0),
-                                                  _n.ptr(w), _n.ptr(off), _n.ptr(ent), _n.ptr(temp)), "csplat_knn_regs_graph")
+        temp = _n.temp(dev, _n.lib.csplat_knn_regs_graph_temp_bytes(N, K))
+        _n.launch("csplat_knn_regs_graph", dev, N, K, _n.ptr(idx32), _n.ptr(d2), float(lambda_w), _n.ptr(d0), _n.ptr(w), _n.ptr(off), _n.ptr(ent),
+                  _n.ptr(temp))
         return d0, w, off, ent
 
     @classmethod
@@ -97,11 +96,9 @@ class _FusedRegs(torch.autograd.Function):
         dev = M.device
         T, N, K = int(M.shape[0]), graph.N, graph.K
         out = torch.empty(4, dtype=torch.float32, device=dev)
-        with _n.on_device(dev):
-            scratch = torch.empty(int(_n.lib.csplat_knn_regs_fwd_scratch_bytes()), dtype=torch.uint8, device=dev)
-            _n.check(_n.lib.csplat_knn_regs_fwd(_n.stream_handle(dev), T, N, K, _n.ptr(M), _n.ptr(Q), _n.ptr(graph.idx32), _n.ptr(graph.d0),
-                                                _n.ptr(graph.w), lam_i, lam_s, lam_r, int(iso_abs), _n.ptr(out), _n.ptr(scratch)),
-                     "csplat_knn_regs_fwd")
+        scratch = _n.temp(dev, _n.lib.csplat_knn_regs_fwd_scratch_bytes())
+        _n.launch("csplat_knn_regs_fwd", dev, T, N, K, _n.ptr(M), _n.ptr(Q), _n.ptr(graph.idx32), _n.ptr(graph.d0), _n.ptr(graph.w), lam_i, lam_s,
+                  lam_r, int(iso_abs), _n.ptr(out), _n.ptr(scratch))
         ctx.save_for_backward(M, Q)
         ctx.graph, ctx.lams, ctx.iso_abs = graph, (lam_i, lam_s, lam_r), int(iso_abs)
         ctx.set_materialize_grads(False)
@@ -121,11 +118,9 @@ class _FusedRegs(torch.autograd.Function):
         g = g.reshape(1).float().contiguous()
         dM = torch.empty_like(M) if want_m else None
         dQ = torch.empty_like(Q) if (want_q and Q is not None) else None
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_knn_regs_bwd(_n.stream_handle(dev), T, graph.N, graph.K, _n.ptr(M), _n.ptr(Q), _n.ptr(graph.idx32),
-                                                _n.ptr(graph.d0), _n.ptr(graph.w), _n.ptr(graph.rev_offsets), _n.ptr(graph.rev_entries),
-                                                ctx.lams[0], ctx.lams[1], ctx.lams[2], ctx.iso_abs, _n.ptr(g), _n.ptr(dM), _n.ptr(dQ)),
-                     "csplat_knn_regs_bwd")
+        _n.launch("csplat_knn_regs_bwd", dev, T, graph.N, graph.K, _n.ptr(M), _n.ptr(Q), _n.ptr(graph.idx32), _n.ptr(graph.d0), _n.ptr(graph.w),
+                  _n.ptr(graph.rev_offsets), _n.ptr(graph.rev_entries), ctx.lams[0], ctx.lams[1], ctx.lams[2], ctx.iso_abs, _n.ptr(g), _n.ptr(dM),
+                  _n.ptr(dQ))
         return dM, dQ, None, None, None, None, None
 
 

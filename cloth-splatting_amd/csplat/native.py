@@ -255,7 +255,8 @@ def why_not_f32c(*tensors):
 # take the wrong "last workgroup" branch and return wrong sums silently -- so any error drops every cached buffer: the next call
 # allocates and zeroes a fresh one.  (csplat_l1, the image, geometry and flow losses register their per-stream partial-sum buffers here
 # too, for the eviction: since round 5 a second launch sums their partials and they leave no ticket.  Of the image kernels only
-# csplat_psnr has one, which it clears itself in every call.)
+# csplat_psnr has one, which it clears itself in every call.)  The product's caches are ScratchCache objects (below), which register
+# themselves; a plain dict appended here is emptied just the same.
 TICKET_CACHES = []
 # Recorded hipGraphs (csplat.train.CapturedStep, bench.py's GraphedSteps) hold RAW POINTERS into these buffers: whenever a cache is
 # emptied the freed memory may be handed to another tensor while the graphs stay replayable.  Every eviction therefore bumps
@@ -300,6 +301,20 @@ def ptr(t):
     return t.data_ptr()
 
 
+def ptr_table(tensors):
+    """host array of the tensors' device pointers, for a `const T *const *` argument (declared c_void_p: it passes without a cast).
+    None or an empty list -> NULL; a None entry -> a NULL entry."""
+    if not tensors:
+        return None
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def temp(device, nbytes):
+    """uninitialised byte buffer sized by any `*_bytes` query (temp, scratch, workspace, packed weight image), never smaller than 256
+    bytes: a temp or scratch query may say 0, and the floor means nothing for the larger ones"""
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -323,6 +338,32 @@ def scratch_stream(device=None):
     idx = torch.cuda.current_device() if idx is None else idx
     alias = REPLAY_STREAM.get(idx)
     return alias if alias is not None else stream_handle(idx)
+
+
+class ScratchCache(dict):
+    """{(device index, stream the work runs on, *sizes): zeroed byte buffer}, registered in TICKET_CACHES.  `cap`: the number of buffers
+    at which the next miss empties the cache first (None = no limit) -- through evict_scratch, so recordings learn of it."""
+
+    def __init__(self, cap=None):
+        super().__init__()
+        self.cap = cap
+        TICKET_CACHES.append(self)
+
+    def buffer(self, device, sizes, nbytes, stream=None):
+        """the buffer of (`device`, `stream`, `sizes`); on a miss `nbytes()` bytes, zeroed on the device's current stream.  `stream`
+        defaults to scratch_stream(device); a launch queued for later passes the key it took when it was queued."""
+        if isinstance(device, str):
+            device = torch.device(device)
+        idx = device.index if isinstance(device, torch.device) else device
+        if idx is None:
+            idx = torch.cuda.current_device()
+        key = (idx, scratch_stream(idx) if stream is None else stream) + tuple(sizes)
+        buf = self.get(key)
+        if buf is None:
+            if self.cap is not None and len(self) >= self.cap:
+                evict_scratch(self)
+            buf = self[key] = torch.zeros(int(nbytes()), dtype=torch.uint8, device=torch.device("cuda", idx))
+        return buf
 
 
 # ---- gradient sinks (csplat.dist.FlatGrads, SURVEY 5.8): where the LAST kernel that forms a parameter's gradient should write it.  A
@@ -435,7 +476,7 @@ class ChunkAllocator:
 
     def _alloc(self, ctx, chunk, nbytes):
         try:
-            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
+            buf = temp(self.device, nbytes)
             self.views[int(ctx or 0)][int(chunk)] = buf
             return buf.data_ptr()
         except Exception:  # never let an exception cross the C boundary
@@ -451,7 +492,7 @@ def group_by_key(keys, n_keys):
     E, dev = int(keys.shape[0]), keys.device
     rowptr = torch.empty(n_keys + 1, dtype=torch.int32, device=dev)
     perm = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-    tmp = torch.empty(max(int(lib.csplat_gnn_csr_temp_bytes(n_keys, E)), 256), dtype=torch.uint8, device=dev)
+    tmp = temp(dev, lib.csplat_gnn_csr_temp_bytes(n_keys, E))
     launch("csplat_gnn_build_csr", dev, n_keys, E, ptr(keys), ptr(rowptr), ptr(perm), ptr(tmp))
     return rowptr, perm[:E]
 

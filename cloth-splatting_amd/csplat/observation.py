@@ -182,11 +182,9 @@ def unproject_depth(depth, *, intrinsics=None, cam_to_world=None, cameras=None, 
             points = torch.empty(cap, 3, dtype=torch.float32, device=dev)
             source = torch.empty(cap, dtype=torch.int32, device=dev)
             count = torch.empty(1, dtype=torch.int32, device=dev)
-            temp = torch.empty(max(int(_n.lib.csplat_obs_unproject_temp_bytes(V, H, W)), 256), dtype=torch.uint8, device=dev)
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_obs_unproject(_n.stream_handle(dev), V, H, W, _n.ptr(D), _n.ptr(Mk), _n.ptr(K4), _n.ptr(C2W), stride, far,
-                                                     0 if kind == "z" else 1, cap, _n.ptr(points), _n.ptr(source), _n.ptr(count), _n.ptr(temp)),
-                         "csplat_obs_unproject")
+            temp = _n.temp(dev, _n.lib.csplat_obs_unproject_temp_bytes(V, H, W))
+            _n.launch("csplat_obs_unproject", dev, V, H, W, _n.ptr(D), _n.ptr(Mk), _n.ptr(K4), _n.ptr(C2W), stride, far, 0 if kind == "z" else 1,
+                      cap, _n.ptr(points), _n.ptr(source), _n.ptr(count), _n.ptr(temp))
             M = int(count.item())          # the call's one blocking read
             src = source[:M].to(torch.int64)
             return Cloud(points[:M], src, torch.div(src, H * W, rounding_mode="floor"))
@@ -257,10 +255,9 @@ def voxel_downsample(points, voxel_size, *, origin=None):
             count = torch.empty(M, dtype=torch.int32, device=dev)
             inverse = torch.empty(M, dtype=torch.int32, device=dev)
             counters = torch.empty(2, dtype=torch.int32, device=dev)
-            temp = torch.empty(max(int(_n.lib.csplat_obs_voxel_temp_bytes(M)), 256), dtype=torch.uint8, device=dev)
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_obs_voxel(_n.stream_handle(dev), M, _n.ptr(P), size, _n.ptr(O), _n.ptr(centroid), _n.ptr(count),
-                                                 _n.ptr(inverse), counters[0:].data_ptr(), counters[1:].data_ptr(), _n.ptr(temp)), "csplat_obs_voxel")
+            temp = _n.temp(dev, _n.lib.csplat_obs_voxel_temp_bytes(M))
+            _n.launch("csplat_obs_voxel", dev, M, _n.ptr(P), size, _n.ptr(O), _n.ptr(centroid), _n.ptr(count), _n.ptr(inverse),
+                      counters[0:].data_ptr(), counters[1:].data_ptr(), _n.ptr(temp))
             K, outside = counters.tolist()          # the call's one blocking read
             vox = Voxels(centroid[:K].clone(), count[:K].clone(), inverse.to(torch.int64))
         else:
@@ -314,8 +311,7 @@ def observable_nodes(cloud, nodes, *, k=2, max_dist=None):
             dev = X.device
             d2, idx = simple_knn._knn_query_i32(C, X, k)
             flags = torch.empty(N, dtype=torch.uint8, device=dev)
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_obs_mark(_n.stream_handle(dev), Q, k, N, _n.ptr(idx), _n.ptr(d2), cap, _n.ptr(flags)), "csplat_obs_mark")
+            _n.launch("csplat_obs_mark", dev, Q, k, N, _n.ptr(idx), _n.ptr(d2), cap, _n.ptr(flags))
             return flags.view(torch.bool)
         _n.composed_fallback("observation.observable_nodes", why, X)
     return _observable_composed(C.to(X.dtype), X, k, cap)

@@ -119,19 +119,16 @@ class GroupedAdam(torch.optim.Adam):
         if len(items) != len(cap["items"]):
             raise RuntimeError("GroupedAdam.step_captured: a tensor with optimizer state has no gradient in the captured step")
         n = len(items)
-        ptrs = [(C.c_void_p * n)(*[t.data_ptr() for t in ts]) for ts in ([it[0] for it in items], [it[0].grad for it in items],
-                                                                          [it[1]["exp_avg"] for it in items], [it[1]["exp_avg_sq"] for it in items])]
+        ptrs = [_n.ptr_table(ts) for ts in ([it[0] for it in items], [it[0].grad for it in items],
+                                            [it[1]["exp_avg"] for it in items], [it[1]["exp_avg_sq"] for it in items])]
         for it in items:
             g = it[0].grad
             if not (g.is_contiguous() and g.dtype == torch.float32 and it[0].is_contiguous() and it[0].dtype == torch.float32):
                 raise RuntimeError("GroupedAdam.step_captured: fp32 contiguous parameters and gradients only")
         numel = (C.c_int64 * n)(*[it[0].numel() for it in items])
         dev = items[0][0].device
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_adam_step_dev(_n.stream_handle(dev), n, C.cast(ptrs[0], C.c_void_p), C.cast(ptrs[1], C.c_void_p),
-                                                 C.cast(ptrs[2], C.c_void_p), C.cast(ptrs[3], C.c_void_p), C.cast(numel, C.c_void_p),
-                                                 _n.ptr(cap["lr"]), items[0][2], items[0][3], items[0][4], _n.ptr(cap["state"]),
-                                                 _n.ptr(valid)), "csplat_adam_step_dev")
+        _n.launch("csplat_adam_step_dev", dev, n, *ptrs, numel, _n.ptr(cap["lr"]), items[0][2], items[0][3], items[0][4], _n.ptr(cap["state"]),
+                  _n.ptr(valid))
 
     def captured_advance_host(self):
         """after a replay whose valid word was 1: the host-side step counters follow the device's"""
@@ -190,13 +187,10 @@ class GroupedAdam(torch.optim.Adam):
                 by_step.setdefault(count_of[id(it[5]["step"])], []).append(it)
             for step, items in by_step.items():
                 n = len(items)
-                ptrs = [(C.c_void_p * n)(*[it[k].data_ptr() for it in items]) for k in range(4)]
+                ptrs = [_n.ptr_table([it[k] for it in items]) for k in range(4)]
                 numel = (C.c_int64 * n)(*[it[0].numel() for it in items])
                 lrs = (C.c_double * n)(*[it[4] for it in items])
-                with _n.on_device(dev):
-                    _n.check(_n.lib.csplat_adam_step(_n.stream_handle(dev), n, C.cast(ptrs[0], C.c_void_p), C.cast(ptrs[1], C.c_void_p),
-                                                     C.cast(ptrs[2], C.c_void_p), C.cast(ptrs[3], C.c_void_p), C.cast(numel, C.c_void_p),
-                                                     C.cast(lrs, C.c_void_p), beta1, beta2, eps, step), "csplat_adam_step")
+                _n.launch("csplat_adam_step", dev, n, *ptrs, numel, lrs, beta1, beta2, eps, step)
         return None
 
 

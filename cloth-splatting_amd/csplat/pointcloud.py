@@ -24,9 +24,7 @@ class ChamferDirection(torch.autograd.Function):
         d2, idx = simple_knn._knn_query_i32(qa, pb, 1)
         d2, idx = d2.view(-1), idx.view(-1)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_chamfer_fwd(_n.stream_handle(dev), int(qa.shape[0]), _n.ptr(d2), float(cap), _n.ptr(loss)),
-                     "csplat_chamfer_fwd")
+        _n.launch("csplat_chamfer_fwd", dev, int(qa.shape[0]), _n.ptr(d2), float(cap), _n.ptr(loss))
         ctx.save_for_backward(qa, pb, d2, idx)
         ctx.cap = float(cap)
         ctx.set_materialize_grads(False)
@@ -42,10 +40,9 @@ class ChamferDirection(torch.autograd.Function):
         g = g.reshape(1).float().contiguous()
         ga = torch.empty(Q, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         gb = torch.empty(N, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        with _n.on_device(dev):
-            temp = torch.empty(int(_n.lib.csplat_chamfer_bwd_temp_bytes(Q, N)), dtype=torch.uint8, device=dev) if gb is not None else None
-            _n.check(_n.lib.csplat_chamfer_bwd(_n.stream_handle(dev), Q, N, _n.ptr(qa), _n.ptr(pb), _n.ptr(d2), _n.ptr(idx), ctx.cap,
-                                               _n.ptr(g), _n.ptr(ga), _n.ptr(gb), _n.ptr(temp)), "csplat_chamfer_bwd")
+        temp = _n.temp(dev, _n.lib.csplat_chamfer_bwd_temp_bytes(Q, N)) if gb is not None else None
+        _n.launch("csplat_chamfer_bwd", dev, Q, N, _n.ptr(qa), _n.ptr(pb), _n.ptr(d2), _n.ptr(idx), ctx.cap, _n.ptr(g), _n.ptr(ga), _n.ptr(gb),
+                  _n.ptr(temp))
         return ga, gb, None
 
 

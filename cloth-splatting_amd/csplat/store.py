@@ -112,10 +112,8 @@ class GaussianStore:
             m8 = mask.to(torch.uint8).contiguous()
             out = torch.empty(n, dtype=torch.int32, device=mask.device)
             cnt = torch.zeros(1, dtype=torch.int32, device=mask.device)
-            tmp = torch.empty(int(_n.lib.csplat_mask_to_map_temp_bytes(n)), dtype=torch.uint8, device=mask.device)
-            with _n.on_device(mask.device):
-                _n.check(_n.lib.csplat_mask_to_map(_n.stream_handle(mask.device), n, _n.ptr(m8), int(base), _n.ptr(out), _n.ptr(cnt),
-                                                   _n.ptr(tmp)), "csplat_mask_to_map")
+            tmp = _n.temp(mask.device, _n.lib.csplat_mask_to_map_temp_bytes(n))
+            _n.launch("csplat_mask_to_map", mask.device, n, _n.ptr(m8), int(base), _n.ptr(out), _n.ptr(cnt), _n.ptr(tmp))
             return out, int(cnt.item())
         ranks = torch.cumsum(mask.to(torch.int64), 0) - 1
         out = torch.where(mask, ranks + base, torch.full_like(ranks, -1)).to(torch.int32)
@@ -132,12 +130,9 @@ class GaussianStore:
             for c0 in range(0, len(pairs), 32):
                 chunk = pairs[c0:c0 + 32]
                 n = len(chunk)
-                srcs = (C.c_void_p * n)(*[None if k is None else k.data_ptr() for k in keep[c0:c0 + 32]])
-                dsts = (C.c_void_p * n)(*[d.data_ptr() for _, d in chunk])
+                srcs, dsts = _n.ptr_table(keep[c0:c0 + 32]), _n.ptr_table([d for _, d in chunk])
                 rb = (C.c_int64 * n)(*[d[0].numel() * d.element_size() for _, d in chunk])
-                with _n.on_device(dev):
-                    _n.check(_n.lib.csplat_rows_scatter(_n.stream_handle(dev), n, C.cast(srcs, C.c_void_p), C.cast(dsts, C.c_void_p),
-                                                        C.cast(rb, C.c_void_p), int(n_rows), _n.ptr(row_map)), "csplat_rows_scatter")
+                _n.launch("csplat_rows_scatter", dev, n, srcs, dsts, rb, int(n_rows), _n.ptr(row_map))
             return
         valid = row_map >= 0
         to = row_map[valid].long()

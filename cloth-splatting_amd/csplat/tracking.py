@@ -156,10 +156,8 @@ def track_visibility(points, full_proj, cam_center, depth, size, *, pixels=None,
             pix_out = torch.empty(F, N, 2, dtype=torch.float32, device=dev)
             flags = torch.empty(2, F, N, dtype=torch.uint8, device=dev)
             counts = torch.empty(F, 2, dtype=torch.int32, device=dev)
-            with _n.on_device(dev):
-                _n.check(_n.lib.csplat_track_visibility(_n.stream_handle(dev), F, N, W, H, _n.ptr(X), _n.ptr(pix), _n.ptr(full), _n.ptr(cam),
-                                                        _n.ptr(D), thr, lo, far, _n.ptr(pix_out), flags[0].data_ptr(), flags[1].data_ptr(),
-                                                        _n.ptr(counts)), "csplat_track_visibility")
+            _n.launch("csplat_track_visibility", dev, F, N, W, H, _n.ptr(X), _n.ptr(pix), _n.ptr(full), _n.ptr(cam), _n.ptr(D), thr, lo, far,
+                      _n.ptr(pix_out), flags[0].data_ptr(), flags[1].data_ptr(), _n.ptr(counts))
             out = (pix_out, flags[0].view(torch.bool), flags[1].view(torch.bool), counts)
             return Visibility(*(t[0] for t in out)) if single else Visibility(*out)
         _n.composed_fallback("tracking.track_visibility", why, X)
@@ -237,9 +235,8 @@ def _mte_kernel(gt, traj, rot, assoc):
     aligned = torch.empty(T, G, 3, dtype=torch.float32, device=dev)
     err = torch.empty(T, G, dtype=torch.float32, device=dev)
     mte = torch.empty(G + 1, dtype=torch.float32, device=dev)          # (the mean behind the per-track values: one allocation)
-    with _n.on_device(dev):
-        _n.check(_n.lib.csplat_track_mte(_n.stream_handle(dev), T, N, G, _n.ptr(traj), _n.ptr(rot), _n.ptr(gt), _n.ptr(a32), _n.ptr(aligned),
-                                         _n.ptr(err), mte.data_ptr(), mte[G:].data_ptr()), "csplat_track_mte")
+    _n.launch("csplat_track_mte", dev, T, N, G, _n.ptr(traj), _n.ptr(rot), _n.ptr(gt), _n.ptr(a32), _n.ptr(aligned), _n.ptr(err), mte.data_ptr(),
+              mte[G:].data_ptr())
     return aligned, err, mte[:G], mte[G]
 
 

@@ -9,8 +9,6 @@ This module is the way in: image_loss.py, geometry_loss.py, flow_loss.py, cloth_
 its stages stay here because tests replace `render_views`, `render`, `geometry_losses` and `cd` as globals of THIS module."""
 from types import SimpleNamespace
 
-import ctypes as C
-
 import torch
 
 from gaussian_renderer import render, render_views
@@ -94,10 +92,7 @@ def step_stats(grads, radii_list, P, dev, dtype=torch.float32, out_vsg=None):
                           out_vsg.numel() == 3 * P) else torch.empty(P, 3, dtype=torch.float32, device=dev)
         radii = torch.empty(P, dtype=torch.int32, device=dev)
         vis = torch.empty(P, dtype=torch.bool, device=dev)
-        gp = (C.c_void_p * V)(*[None if g is None else g.data_ptr() for g in grads])
-        rp = (C.c_void_p * V)(*[r.data_ptr() for r in radii_list])
-        with _n.on_device(dev):
-            _n.check(_n.lib.csplat_step_stats(_n.stream_handle(dev), P, V, gp, rp, _n.ptr(vsg), _n.ptr(radii), _n.ptr(vis)), "csplat_step_stats")
+        _n.launch("csplat_step_stats", dev, P, V, _n.ptr_table(grads), _n.ptr_table(radii_list), _n.ptr(vsg), _n.ptr(radii), _n.ptr(vis))
         return vsg.to(dtype), radii, vis
     if radii_list[0].is_cuda:
         _n.composed_fallback("train.step_stats", "shape" if V > 16 else "dtype", radii_list[0])

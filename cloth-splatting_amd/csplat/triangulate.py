@@ -36,6 +36,7 @@ def checked_threshold(norm_threshold, what):
 
 def temp_bytes(n):
     size = C.c_size_t(0)
+    # (a size query that can refuse its argument, takes no stream: check(), not native.launch)
     _n.check(_n.lib.csplat_delaunay_temp_bytes(int(n), C.byref(size)), "csplat_delaunay_temp_bytes")
     return int(size.value)
 
@@ -64,7 +65,7 @@ def delaunay(points2d, norm_threshold=None):
         faces = torch.empty(max(2 * N, 1), 3, dtype=torch.int32, device=dev)
         edges = torch.empty(max(3 * N, 1), 2, dtype=torch.int32, device=dev)
         counters = torch.empty(5, dtype=torch.int64, device=dev)
-        temp = torch.empty(max(temp_bytes(N), 256), dtype=torch.uint8, device=dev)
+        temp = _n.temp(dev, temp_bytes(N))
         _n.launch("csplat_delaunay", dev, N, _n.ptr(pts), 0 if thr is None else 1, 0.0 if thr is None else thr, _n.ptr(faces), _n.ptr(edges),
                   _n.ptr(counters), _n.ptr(temp))
         return _result(faces, edges, counters)

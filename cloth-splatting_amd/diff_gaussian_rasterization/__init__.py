@@ -500,6 +500,8 @@ class _View:
         dev, rs = self.dev, self.rs
         self.outputs()
         self.alloc, tk = _n.ChunkAllocator(dev), C.c_int(-1)
+        # (in this module: csplat_forward_finish takes a ticket and the entries on csplat_view tables the stream they join LAST -- not
+        # native.launch's stream-first form, so they, and csplat_forward_begin beside them, stay on check())
         with _n.on_device(dev):
             rc = _n.lib.csplat_forward_begin(
                 _n.stream_handle(dev), self.P, int(rs.sh_degree), self.M, _n.ptr(self.bg), self.W, self.H,
@@ -540,7 +542,7 @@ class _View:
         cam = cam_need is not None and any(cam_need)
         sized = _n.lib.csplat_backward_camera_scratch_bytes if cam else _n.lib.csplat_backward_depth_scratch_bytes
         nbytes = sized(P, self.num_rendered, self.W, self.H) if cam or grad_depth is not None else _n.lib.csplat_backward_scratch_bytes(P, self.num_rendered)
-        scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        scratch = _n.temp(dev, nbytes)
         w = _n.CsplatView()
         self.fill(w, _n.stream_handle(dev), (t["means3D"], t["sh"], t["colors_precomp"], None, t["scales"], t["rotations"], t["cov3Ds_precomp"],
                                             t["color"], t["radii"]))
@@ -596,20 +598,17 @@ _side_streams = {}
 # K8 clears every record it consumes (csplat.h: CSPLAT_SCRATCH_ZEROED), so the next step finds them zero again -- no clearing launch and
 # no 25.6 MB of zero fill per step.  Launches on one stream cannot overlap, so two backward passes that share a slot are ordered.  A failed
 # entry point may leave records behind: the cache is a ticket cache (csplat.native.check drops it, recordings are invalidated).
-_ACC_SCRATCH = {}
-_n.TICKET_CACHES.append(_ACC_SCRATCH)
+_ACC_SCRATCH = _n.ScratchCache(cap=32)
 
 
 def _acc_scratch(dev, P, slot):
     """(tensor, True) = the persistent zeroed records of `slot`; (None, False) in the bit-reproducible mode (its scratch is laid out per call)"""
     if int(_n.lib.csplat_debug_flags_query()) & _n.DEBUG_BIT_REPRODUCIBLE:
         return None, False
-    key = (dev.index, _n.scratch_stream(dev), int(P), int(slot))
-    buf = _ACC_SCRATCH.get(key)
+    # the hit, once per view and backward pass, stays written out: 0.56 us a call on the host this way, 0.72 us through buffer() alone
+    buf = _ACC_SCRATCH.get((dev.index, _n.scratch_stream(dev), int(P), int(slot)))
     if buf is None:
-        if len(_ACC_SCRATCH) >= 32:
-            _n.evict_scratch(_ACC_SCRATCH)
-        buf = _ACC_SCRATCH[key] = torch.zeros(max(int(_n.lib.csplat_backward_scratch_bytes(int(P), 0)), 256), dtype=torch.uint8, device=dev)
+        buf = _ACC_SCRATCH.buffer(dev, (int(P), int(slot)), lambda: max(_n.lib.csplat_backward_scratch_bytes(int(P), 0), 256))
     return buf, True
 # how the batched forward's second phase went, per call (bench.py's `speculation` field, tests): "hit" = launched on the previous call's
 # capacities before the counts were read and the counts fitted; "miss" = they did not fit and the phase was repeated with exact sizes;
@@ -678,6 +677,7 @@ class DeferredK8:
     def rows(self, slice_, nslices):
         P = self.entries[0][3]
         lo, hi = C.c_int64(0), C.c_int64(0)
+        # (host arithmetic, takes no stream: check(), not native.launch)
         _n.check(_n.lib.csplat_backward_slice_rows(int(P), int(slice_), int(nslices), C.byref(lo), C.byref(hi)), "csplat_backward_slice_rows")
         return int(lo.value), int(hi.value)
 
@@ -774,7 +774,7 @@ class _Plan:
         for a, i in enumerate(self.active):
             v, w = views[i], self.sub[a]
             gd = _f32c_grad(gdep[i], v.dev)
-            buf = torch.empty(max(int(scratch_bytes(v.P, v.layout_rendered, v.W, v.H)), 256), dtype=torch.uint8, device=v.dev)
+            buf = _n.temp(v.dev, scratch_bytes(v.P, v.layout_rendered, v.W, v.H))
             w.dL_ddepth, w.scratch, w.accmask = _n.ptr(gd), buf.data_ptr(), w.accmask & ~SCRATCH_ZEROED
             self.keep += [gd, buf]
 
@@ -900,8 +900,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         outs, keep = (_n.CsplatVisibility * len(views))(), []
         for o, v in zip(outs, views):
             if v.vis is not None:
-                keep.append(torch.empty(max(int(_n.lib.csplat_visibility_scratch_bytes(v.P, max(v.layout_rendered, v.num_rendered, 0), v.W, v.H)), 256),
-                                        dtype=torch.uint8, device=dev))
+                keep.append(_n.temp(dev, _n.lib.csplat_visibility_scratch_bytes(v.P, max(v.layout_rendered, v.num_rendered, 0), v.W, v.H)))
                 o.weight_max, o.weight_sum, o.pixel_count, o.top_id = (_n.ptr(t) for t in v.vis)
                 o.scratch = keep[-1].data_ptr()
         with _n.on_device(dev):

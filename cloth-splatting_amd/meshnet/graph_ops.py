@@ -27,7 +27,7 @@ class GraphCSR:
         self.N, self.E = int(num_nodes), int(edge_index.shape[1])
         dev = edge_index.device
         self.rowptr, self.perm = {}, {}
-        tmp = torch.empty(max(int(_n.lib.csplat_gnn_csr_temp_bytes(self.N, self.E)), 256), dtype=torch.uint8, device=dev)
+        tmp = _n.temp(dev, _n.lib.csplat_gnn_csr_temp_bytes(self.N, self.E))
         for name, row in (("src", 0), ("dst", 1)):
             rp = torch.empty(self.N + 1, dtype=torch.int32, device=dev)
             pm = torch.empty(max(self.E, 1), dtype=torch.int32, device=dev)      # (never an empty tensor: its pointer would be NULL)
@@ -180,8 +180,7 @@ class SegmentSum(torch.autograd.Function):
         return gather_rows(g, ctx.csr.ei[1]), None
 
 
-_SIMH_SCRATCH = {}
-_n.TICKET_CACHES.append(_SIMH_SCRATCH)
+_SIMH_SCRATCH = _n.ScratchCache()        # csplat_sim_hidden_bwd's, zeroed once per stream: the kernel leaves its ticket word at zero
 
 
 # ---- the simulator's residual MLP: one forward / backward pair per kernel pair; RowsDot, SimHidden, SimResidual and
@@ -204,11 +203,7 @@ def _sim_hidden_bwd(e, W2, h1, h2, g, sinks=(None, None, None, None)):
     dW1 = _n.grad_out(sinks[0], (256, K0), dev)
     dW2 = _n.grad_out(sinks[2], (256, 256), dev)
     db = [_n.grad_out(sinks[1], (256,), dev), _n.grad_out(sinks[3], (256,), dev)]
-    key = (str(dev), _n.scratch_stream(dev))
-    scratch = _SIMH_SCRATCH.get(key)        # zeroed once per stream: the kernel leaves its ticket word at zero
-    if scratch is None:
-        with _n.on_device(dev):       # (the zero fill runs on dev's current stream)
-            scratch = _SIMH_SCRATCH[key] = torch.zeros(int(_n.lib.csplat_sim_hidden_scratch_bytes(8)) // 4, dtype=torch.int32, device=dev)
+    scratch = _SIMH_SCRATCH.buffer(dev, (), lambda: _n.lib.csplat_sim_hidden_scratch_bytes(8))
     _n.launch("csplat_sim_hidden_bwd", dev, T, K0, _n.ptr(e), _n.ptr(W2), _n.ptr(h1), _n.ptr(h2), _n.ptr(g), _n.ptr(dW1), _n.ptr(db[0]),
               _n.ptr(dW2), _n.ptr(db[1]), _n.ptr(scratch))
     return dW1, db[0], dW2, db[1]
@@ -229,7 +224,7 @@ def _rows_dot_bwd(W, h, g, sinks=(None, None)):
     g, W, h = _f32(g), _f32a(W), _f32a(h)
     T, K, R = int(h.shape[0]), int(h.shape[1]), int(W.shape[0])
     dW, db, dh = _n.grad_out(sinks[0], W.shape, g.device), _n.grad_out(sinks[1], (R,), g.device), torch.empty_like(h)
-    scratch = torch.empty(_n.lib.csplat_rows_dot_scratch_bytes(T), dtype=torch.uint8, device=g.device)
+    scratch = _n.temp(g.device, _n.lib.csplat_rows_dot_scratch_bytes(T))
     _n.launch("csplat_rows_dot_bwd", g.device, T, R, K, _n.ptr(W), _n.ptr(h), _n.ptr(g.reshape(T, R)), _n.ptr(dW), _n.ptr(db), _n.ptr(dh),
               _n.ptr(scratch))
     return dW, db, dh
@@ -461,7 +456,7 @@ def edge_mlp3_pack(w0, w1, w2):
     """the three 128 x 128 weights of an edge MLP as the register image csplat_gnn_edge_mlp3 loads (the 16-bit pieces of every wave's 32
     output rows as MFMA A operands, the contraction index of layers 2 and 3 permuted to the order the previous layer leaves its
     activations in): pack once per weight version and per edge_mlp3_mode"""
-    img = torch.empty(int(_n.lib.csplat_gnn_edge_mlp3_image_bytes()), dtype=torch.uint8, device=w0.device)
+    img = _n.temp(w0.device, _n.lib.csplat_gnn_edge_mlp3_image_bytes())
     ws = []
     for w in (w0, w1, w2):
         w = w.detach()
@@ -547,7 +542,7 @@ def mlp3_rows(x, image, b0, b1, b2, layer_norm, x_absmax=None):
 def node_update_pack(w_agg, w_x, w2, w3, w_i_next=None, w_j_next=None):
     """the node update's weights (+ the next layer's x_i / x_j blocks) as the register image csplat_gnn_node_update_packed streams: three bf16
     pieces per matrix as MFMA A operands (csplat_gnn_node_update_pack); pack once per weight version"""
-    img = torch.empty(int(_n.lib.csplat_gnn_node_update_image_bytes()), dtype=torch.uint8, device=w_agg.device)
+    img = _n.temp(w_agg.device, _n.lib.csplat_gnn_node_update_image_bytes())
     c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
     ws = [c(t) for t in (w_agg, w_x, w2, w3, w_i_next, w_j_next)]
     for t in ws[:4]:
@@ -559,7 +554,7 @@ def node_update_pack(w_agg, w_x, w2, w3, w_i_next=None, w_j_next=None):
 def rows_chain_pack(mode, w_first, w_second):
     """the register image of csplat_gnn_rows_chain (mode 0: the pair (Wa, Wb); mode 1: the two layers (W0, W1)); pack once per weight version,
     under the edge_mlp3_mode it will be used with"""
-    img = torch.empty(int(_n.lib.csplat_gnn_node_update_image_bytes()), dtype=torch.uint8, device=w_first.device)
+    img = _n.temp(w_first.device, _n.lib.csplat_gnn_node_update_image_bytes())
     a, b = w_first.detach().contiguous(), w_second.detach().contiguous()
     assert tuple(a.shape) == (128, 128) and tuple(b.shape) == (128, 128) and a.dtype == torch.float32 and a.is_cuda
     _n.launch("csplat_gnn_rows_chain_pack", a.device, int(mode), _n.ptr(a), _n.ptr(b), _n.ptr(img))
@@ -672,7 +667,7 @@ def dw128(g, x, bias=False, x_relu=False):
     M = g.shape[0]
     dW = torch.empty(128, 128, dtype=torch.float32, device=g.device)
     db = torch.empty(128, dtype=torch.float32, device=g.device) if bias else None
-    ws = torch.empty(max(int(_n.lib.csplat_dw128_workspace_bytes(M)), 256), dtype=torch.uint8, device=g.device)
+    ws = _n.temp(g.device, _n.lib.csplat_dw128_workspace_bytes(M))
     _n.launch("csplat_dw128_bias", g.device, M, _n.ptr(g), _n.ptr(x), int(x_relu), _n.ptr(dW), _n.ptr(db), _n.ptr(ws))
     return (dW, db) if bias else dW
 

@@ -10,12 +10,11 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     pts = points.detach().to(torch.float32).contiguous()
     P = int(pts.shape[0])
     out = torch.empty(P, dtype=torch.float32, device=pts.device)
-    with _n.on_device(pts.device):
-        if P >= BOXED_FROM:   # Morton order + box pruning (what the upstream extension does); same bits, O(P) candidates
-            temp = torch.empty(int(_n.lib.csplat_dist2_temp_bytes(P)), dtype=torch.uint8, device=pts.device)
-            _n.check(_n.lib.csplat_dist2_ws(_n.stream_handle(pts.device), P, _n.ptr(pts), _n.ptr(out), _n.ptr(temp)), "csplat_dist2_ws")
-        else:
-            _n.check(_n.lib.csplat_dist2(_n.stream_handle(pts.device), P, _n.ptr(pts), _n.ptr(out)), "csplat_dist2")
+    if P >= BOXED_FROM:   # Morton order + box pruning (what the upstream extension does); same bits, O(P) candidates
+        temp = _n.temp(pts.device, _n.lib.csplat_dist2_temp_bytes(P))
+        _n.launch("csplat_dist2_ws", pts.device, P, _n.ptr(pts), _n.ptr(out), _n.ptr(temp))
+    else:
+        _n.launch("csplat_dist2", pts.device, P, _n.ptr(pts), _n.ptr(out))
     return out
 
 

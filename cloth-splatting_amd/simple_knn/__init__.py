@@ -28,12 +28,11 @@ def knn(points: torch.Tensor, k: int):
     P, dev = int(pts.shape[0]), pts.device
     d2 = torch.empty(P, k, dtype=torch.float32, device=dev)
     idx = torch.empty(P, k, dtype=torch.int32, device=dev)
-    with _n.on_device(dev):
-        if P >= BOXED_FROM:   # Morton order + box pruning; the same bits and indices
-            temp = torch.empty(int(_n.lib.csplat_knn_temp_bytes(P, k)), dtype=torch.uint8, device=dev)
-            _n.check(_n.lib.csplat_knn_ws(_n.stream_handle(dev), P, k, _n.ptr(pts), _n.ptr(d2), _n.ptr(idx), _n.ptr(temp)), "csplat_knn_ws")
-        else:
-            _n.check(_n.lib.csplat_knn(_n.stream_handle(dev), P, k, _n.ptr(pts), _n.ptr(d2), _n.ptr(idx)), "csplat_knn")
+    if P >= BOXED_FROM:   # Morton order + box pruning; the same bits and indices
+        temp = _n.temp(dev, _n.lib.csplat_knn_temp_bytes(P, k))
+        _n.launch("csplat_knn_ws", dev, P, k, _n.ptr(pts), _n.ptr(d2), _n.ptr(idx), _n.ptr(temp))
+    else:
+        _n.launch("csplat_knn", dev, P, k, _n.ptr(pts), _n.ptr(d2), _n.ptr(idx))
     return d2, idx.to(torch.int64)
 
 
@@ -52,8 +51,7 @@ def fps(points: torch.Tensor, num_samples: int, start: int):
     dev = pts.device
     out = torch.empty(S, dtype=torch.int32, device=dev)
     min_d2 = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
-    with _n.on_device(dev):
-        _n.check(_n.lib.csplat_fps(_n.stream_handle(dev), N, S, _n.ptr(pts), int(start) if S else 0, _n.ptr(min_d2), _n.ptr(out)), "csplat_fps")
+    _n.launch("csplat_fps", dev, N, S, _n.ptr(pts), int(start) if S else 0, _n.ptr(min_d2), _n.ptr(out))
     return out.to(torch.int64)
 
 
@@ -82,14 +80,11 @@ def _knn_query_i32(qry, pts, k, boxed=None):
     idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
     if boxed is None:
         boxed = N >= QUERY_BOXED_FROM
-    with _n.on_device(dev):
-        if boxed:   # Morton order + box pruning; the same bits and indices
-            temp = torch.empty(int(_n.lib.csplat_knn_query_temp_bytes(Q, N, k)), dtype=torch.uint8, device=dev)
-            _n.check(_n.lib.csplat_knn_query_ws(_n.stream_handle(dev), Q, N, k, _n.ptr(qry), _n.ptr(pts), _n.ptr(d2), _n.ptr(idx),
-                                                _n.ptr(temp)), "csplat_knn_query_ws")
-        else:
-            _n.check(_n.lib.csplat_knn_query(_n.stream_handle(dev), Q, N, k, _n.ptr(qry), _n.ptr(pts), _n.ptr(d2), _n.ptr(idx)),
-                     "csplat_knn_query")
+    if boxed:   # Morton order + box pruning; the same bits and indices
+        temp = _n.temp(dev, _n.lib.csplat_knn_query_temp_bytes(Q, N, k))
+        _n.launch("csplat_knn_query_ws", dev, Q, N, k, _n.ptr(qry), _n.ptr(pts), _n.ptr(d2), _n.ptr(idx), _n.ptr(temp))
+    else:
+        _n.launch("csplat_knn_query", dev, Q, N, k, _n.ptr(qry), _n.ptr(pts), _n.ptr(d2), _n.ptr(idx))
     return d2, idx
 
 

@@ -422,6 +422,131 @@ def test_cabi_exports_every_declared_symbol():
     assert o3[0] == 0 and o3[1] >= 2500 * 8 and o3[2] - o3[1] >= 640000 * 4
 
 
+def _header_abi(path):
+    """include/csplat.h read with regular expressions -> ({name: (result, [argument types])}, {struct: [(field, type)]}); a C type is
+    its text without `const` and the parameter's name, e.g. "int64_t", "float*", "void**" """
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
+    text = text.replace('extern "C" {', " ")
+
+    def ctype(decl):          # "const float *means3D" -> ("float*", "means3D"); an unnamed parameter has no name to strip
+        decl = re.sub(r"\bconst\b", " ", decl).strip()
+        m = re.fullmatch(r"((?:un)?signed(?:\s+(?:char|short|int|long))?|\w+)\s*((?:\*\s*)*)(\w*)\s*((?:\[\s*\d*\s*\])?)", decl)
+        assert m, f"unreadable declaration {decl!r}"
+        base, stars, name, arr = m.groups()
+        return " ".join(base.split()) + "*" * (stars.count("*") + bool(arr)), name
+    structs = {}
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        fields = structs[m.group(1)] = []
+        for decl in filter(str.strip, m.group(2).split(";")):          # "int P, D, M" / "const float *view, *proj": one base type, several names
+            first, *more = decl.split(",")
+            base = re.sub(r"\*", " ", ctype(first)[0])
+            fields += [ctype(d)[::-1] for d in [first] + [base + " " + d for d in more]]
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{.*?\}\s*\1\s*;", " ", text, flags=re.S)
+    text, n = re.subn(r"typedef\s+void\s*\*\s*\(\s*\*\s*csplat_alloc_fn\s*\)\s*\([^)]*\)\s*;", " ", text)
+    assert n == 1
+    text = re.sub(r"\benum\s*\{[^}]*\}\s*;", " ", text)
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):
+            continue
+        m = re.fullmatch(r"(.*?)\b(csplat_\w+)\s*\((.*)\)", stmt)
+        assert m, f"not a prototype: {stmt!r}"
+        res, name, args = m.groups()
+        assert name not in protos, name
+        args = [] if args.strip() in ("", "void") else [ctype(a)[0] for a in args.split(",")]
+        protos[name] = (ctype(res + " _")[0], args)
+    return protos, structs
+
+
+def _abi_mismatches(protos, exports, records, native):
+    """every place where a ctypes table differs from the header, as text; a C type this reader does not know IS a mismatch"""
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "unsigned": C.c_uint, "unsigned int": C.c_uint, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+               "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double, "csplat_alloc_fn": native.ALLOC_FN}
+    pointees = dict(scalars, **{"csplat_view": native.CsplatView, "csplat_visibility": native.CsplatVisibility,
+                                "uint8_t": C.c_uint8, "uint64_t": C.c_uint64, "char": C.c_char, "signed char": C.c_int8, "unsigned char": C.c_uint8})
+    del pointees["csplat_alloc_fn"]
+
+    def fits(ct, have, result=False):
+        if ct in scalars:
+            return have is scalars[ct]
+        if result:
+            return ct == "char*" and have is C.c_char_p
+        if ct.endswith("**"):          # a table of pointers
+            return fits(ct[:-1], C.c_void_p) and have in (C.c_void_p, C.POINTER(C.c_void_p))
+        if ct.endswith("*") and (ct[:-1] == "void" or ct[:-1] in pointees):
+            return have is C.c_void_p or (ct[:-1] in pointees and have is C.POINTER(pointees[ct[:-1]]))
+        return False          # unknown to this reader: never skipped
+    bad = [f"{n}: declared in only one of the two" for n in sorted(set(protos) ^ set(exports))]
+    for name in sorted(set(protos) & set(exports)):
+        (res, args), (have_res, have_args) = protos[name], exports[name]
+        if not fits(res, have_res, result=True):
+            bad.append(f"{name}: result {res} is {have_res}")
+        if len(args) != len(have_args):
+            bad.append(f"{name}: {len(args)} arguments, the table has {len(have_args)}")
+        bad += [f"{name}: argument {k} {a} is {h}" for k, (a, h) in enumerate(zip(args, have_args)) if not fits(a, h)]
+    for cname, (fields, have) in records.items():
+        if [f for f, _ in fields] != [f for f, _ in have]:
+            bad.append(f"{cname}: fields {[f for f, _ in fields]} are {[f for f, _ in have]}")
+        bad += [f"{cname}.{f}: {t} is {h}" for (f, t), (_, h) in zip(fields, have) if not fits(t, h)]
+    return bad
+
+
+def test_cabi_table_matches_the_header_type_for_type():
+    """native.EXPORTS against every prototype of include/csplat.h -- result and arguments, type for type (a pointer as c_void_p or a
+    POINTER of its element, csplat_alloc_fn as ALLOC_FN) -- and CsplatView / CsplatVisibility against the two structs: names, order and
+    types.  The reader must have seen exactly the names of the table, so a prototype it misses fails too; a type it does not know fails.
+    The comparison itself is shown to fail on a copy of the table with ONE c_int widened to c_int64."""
+    from csplat import native
+    protos, structs = _header_abi(os.path.join(util.ROOT, "include", "csplat.h"))
+    assert set(protos) == set(native.EXPORTS) and len(protos) == len(native.EXPORTS) >= 158
+    assert sorted(structs) == ["csplat_view", "csplat_visibility"] and len(structs["csplat_view"]) == 56
+    records = {"csplat_view": (structs["csplat_view"], native.CsplatView._fields_),
+               "csplat_visibility": (structs["csplat_visibility"], native.CsplatVisibility._fields_)}
+    assert _abi_mismatches(protos, native.EXPORTS, records, native) == []
+    res, args = native.EXPORTS["csplat_knn"]
+    assert args[2] is C.c_int
+    wrong = dict(native.EXPORTS, csplat_knn=(res, args[:2] + [C.c_int64] + args[3:]))
+    assert _abi_mismatches(protos, wrong, records, native) == [f"csplat_knn: argument 2 int is {C.c_int64}"]
+    res, args = native.EXPORTS["csplat_adam_step"]
+    wrong = dict(native.EXPORTS, csplat_adam_step=(res, [C.c_float if t is C.c_double else t for t in args]))
+    assert len(_abi_mismatches(protos, wrong, records, native)) == 3                      # (beta1, beta2, eps)
+    moved = [native.CsplatView._fields_[1], native.CsplatView._fields_[0]] + native.CsplatView._fields_[2:]
+    assert _abi_mismatches(protos, native.EXPORTS, dict(records, csplat_view=(structs["csplat_view"], moved)), native)
+
+
+def test_the_binding_idioms_have_one_home_in_native():
+    """over the .py files of cloth-splatting_amd/: scratch caches register in native.py only (native.ScratchCache does it), no private
+    pointer-table helper, no byte buffer sized by a `*_bytes(` query allocated by hand (native.temp, ScratchCache.buffer), and the
+    written-out `_n.check(_n.lib.X(...))` only where native.launch does not fit"""
+    pkg = os.path.join(util.ROOT, "cloth-splatting_amd")
+    text = {}
+    for d, _dirs, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                text[os.path.relpath(os.path.join(d, f), pkg)] = open(os.path.join(d, f)).read()
+    assert len(text) > 40 and os.path.join("csplat", "native.py") in text
+    nat = os.path.join("csplat", "native.py")
+    assert [f for f, t in text.items() if "TICKET_CACHES.append" in t] == [nat]
+    assert [f for f, t in text.items() if "def _ptr_table" in t] == []
+    on_check = {os.path.join("diff_gaussian_rasterization", "__init__.py"): 1,      # csplat_backward_slice_rows: host arithmetic, no stream
+                os.path.join("csplat", "triangulate.py"): 1,                        # csplat_delaunay_temp_bytes: a size query, no stream
+                os.path.join("csplat", "cloth_regs.py"): 1}                         # _cloth_regs_for: queued, its stream was fixed earlier
+    assert {f: t.count("_n.check(_n.lib.") for f, t in text.items() if "_n.check(_n.lib." in t} == on_check
+    by_hand = []
+    for f, t in text.items():
+        for m in re.finditer(r"torch\.(?:empty|zeros)\(", t):
+            depth, k = 1, m.end()
+            while depth:                      # the argument text, to the matching parenthesis
+                depth += {"(": 1, ")": -1}.get(t[k], 0)
+                k += 1
+            if "_bytes(" in t[m.end():k]:
+                by_hand.append(f)
+    assert set(by_hand) <= {nat}, by_hand
+
+
 def test_densify_prune_and_adam_surgery_replay_the_reference():
     """csplat/densify.py against the reference's own MultiGaussianMesh run (tests/golden/densify.npz, generated by
     make_golden.gen_densify on CPU tensors): three Adam steps, two rounds of statistics, densify (clone + split, same

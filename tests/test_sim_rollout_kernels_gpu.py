@@ -261,6 +261,62 @@ def test_native_launch_takes_the_failure_path_of_check_and_the_next_launch_succe
     assert same_bits(y2, y)
 
 
+def test_scratch_cache_keys_on_device_index_and_run_stream_and_evicts_through_the_epoch():
+    """csplat.native.ScratchCache, a private one with cap=2 and 256-byte buffers: a miss asks the size function once and returns zeros; a
+    hit returns the identical tensor and asks nothing; other sizes are another buffer; the third distinct key empties the cache and moves
+    SCRATCH_EPOCH by exactly one; `cuda` and `cuda:0`-style devices share a buffer; with REPLAY_STREAM set the key carries that handle,
+    not the current stream's; an explicit stream key wins over both; a failing entry (csplat_rows_dot_fwd refusing an operand off a
+    16-byte boundary: it returns on the host, nothing is launched) empties it."""
+    from csplat import native as n
+    idx = torch.cuda.current_device()
+    dev = torch.device("cuda", idx)
+    asked = []
+
+    def size():
+        asked.append(1)
+        return 256
+    cache = n.ScratchCache(cap=2)
+    assert cache.cap == 2 and any(c is cache for c in n.TICKET_CACHES)
+    had_alias = idx in n.REPLAY_STREAM
+    alias = n.REPLAY_STREAM.get(idx)
+    n.REPLAY_STREAM.pop(idx, None)
+    try:
+        cur = n.stream_handle(idx)
+        a = cache.buffer(dev, (3, 5), size)
+        assert len(asked) == 1 and a.dtype == torch.uint8 and a.numel() == 256 and a.device == dev and not bool(a.any())
+        assert list(cache) == [(idx, cur, 3, 5)]
+        assert cache.buffer(dev, (3, 5), size) is a and len(asked) == 1                      # a hit: no size query
+        assert cache.buffer(torch.device("cuda"), (3, 5), size) is a and cache.buffer(None, (3, 5), size) is a and len(asked) == 1
+        b = cache.buffer(dev, (3, 6), size)
+        assert b is not a and b.data_ptr() != a.data_ptr() and len(asked) == 2 and len(cache) == 2
+        epoch = n.SCRATCH_EPOCH[0]
+        c = cache.buffer(dev, (4, 6), size)                                                  # the third key: at the cap, so the cache is emptied first
+        assert n.SCRATCH_EPOCH[0] == epoch + 1 and list(cache) == [(idx, cur, 4, 6)] and cache[(idx, cur, 4, 6)] is c and len(asked) == 3
+        made_up = cur + 0x1000 if cur else 0x1000                                            # (never dereferenced: it is only a key)
+        n.REPLAY_STREAM[idx] = made_up
+        d = cache.buffer(dev, (4, 6), size)
+        assert d is not c and (idx, made_up, 4, 6) in cache and cache[(idx, made_up, 4, 6)] is d and len(cache) == 2
+        assert cache.buffer(dev, (4, 6), size, stream=cur) is c                              # an explicit stream key wins over the alias ...
+        n.REPLAY_STREAM.pop(idx)
+        assert cache.buffer(dev, (4, 6), size, stream=made_up) is d and len(asked) == 4      # ... and over the current stream
+        # a failing entry empties it
+        h8, W, b_, _add, _dy = R.rows_dot_case(771)
+        hc, Wc, bc = cuda(h8[:3]), cuda(W), cuda(b_)
+        moved = torch.zeros(hc.numel() + 1, device="cuda")[1:].view(hc.shape)
+        assert moved.data_ptr() % 16 == 4
+        epoch = n.SCRATCH_EPOCH[0]
+        with pytest.raises(n.CsplatError, match="csplat_rows_dot_fwd"):
+            n.launch("csplat_rows_dot_fwd", dev, 3, 771, 256, P(Wc), P(bc), P(moved), P(filled(3, 771)), None)
+        assert not cache and n.SCRATCH_EPOCH[0] == epoch + 1
+        e = cache.buffer(dev, (4, 6), size)
+        assert len(asked) == 5 and not bool(e.any())
+    finally:
+        n.REPLAY_STREAM.pop(idx, None)
+        if had_alias:
+            n.REPLAY_STREAM[idx] = alias
+        n.TICKET_CACHES[:] = [x for x in n.TICKET_CACHES if x is not cache]
+
+
 # ================================================================================================ sim_hidden
 def _sim_fwd(T, K0, e, W1, b1, W2, b2):
     h1, h2 = filled(T, 256), filled(T, 256)
