@@ -28,7 +28,8 @@
 // pos = column of e0.  Layers 2, 3: the producing wave j' writes its lane's 16 accumulator registers of row n contiguously, pos = 32j'
 // + 16h' + r <-> feature 32j' + 8(r >> 2) + 4h' + (r & 3); the permutation is applied to the packed weights (er_src_col).
 //
-// Two arithmetic modes (csplat_gnn_edge_mlp3_mode):
+// Two arithmetic modes (csplat_gnn_edge_mlp3_mode; Piece<F16> holds their piece arithmetic for this kernel, both packers and PieceChain<F16>,
+// which the node update k_node_update_b3 and the rows chain k_rows_chain further down are written on):
 //   0  two fp16 pieces per operand (x = h1 + h2 to 2^-22 |x|), three products per step (h1 h1 + h1 h2 + h2 h1): 24 MFMAs per tile-layer.
 //      fp16 has 5 exponent bits, so the values are kept where they are representable: the launch's max |e0| (csplat_absmax, once per
 //      rollout step: e0 is the same for all layers) gives the power of two cs that brings the edge rows to max in [8, 16), and ALL the
@@ -57,6 +58,7 @@
 #include "csplat_device.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #ifndef EM_SKIP
 #define EM_SKIP 0      /* timing experiments (tools/edge_mlp3_skip_ab.sh): side tasks left out of the phases -- results wrong */
@@ -78,9 +80,39 @@ constexpr int ER_GSTRIDE = 132;                           // floats per G row (5
 constexpr size_t ER_G_BYTES = (size_t)64 * ER_GSTRIDE * 4;        // 33,792
 constexpr size_t ER_S_BYTES = (size_t)2 * 32 * 4 * 8;     // LayerNorm partials [slot][row 32][wave 4] (sum, M2)
 constexpr size_t ER_T_BYTES = (size_t)4 * EM_N * 4;       // b1, b2, gamma, beta
-template <bool F16> struct ErCfg {
+
+// The 16-bit piece arithmetic of one mode (header): x = p[0] + p[1] (+ p[2]), each piece what its format holds of the remainder the pieces
+// before it left.  All three piece kernels and both packers take their pieces from here.
+template <bool F16> struct Piece {
     static constexpr int NP = F16 ? 2 : 3;                // pieces per operand
     static constexpr int NPROD = F16 ? 3 : 6;             // products per k-step
+    static constexpr float SC = F16 ? 0.0625f : 1.f, ISC = F16 ? 16.f : 1.f;      // PieceChain's fixed scale and its inverse (the edge kernel has its own)
+    // two values -> one dword of 16-bit pieces (round to nearest even), and the two pieces back as floats
+    static __device__ __forceinline__ unsigned pk(float lo, float hi) {
+        if (F16) { h16x2 v; v[0] = (_Float16)lo; v[1] = (_Float16)hi; return __builtin_bit_cast(unsigned, v); }
+        bf16x2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
+        return __builtin_bit_cast(unsigned, v);
+    }
+    static __device__ __forceinline__ float lo_f(unsigned q) {
+        if (F16) return (float)__builtin_bit_cast(h16x2, q)[0];
+        return __uint_as_float(q << 16);
+    }
+    static __device__ __forceinline__ float hi_f(unsigned q) {
+        if (F16) return (float)__builtin_bit_cast(h16x2, q)[1];
+        return __uint_as_float(q & 0xffff0000u);
+    }
+    // one value -> its NP pieces, one at a time (the packers' form)
+    static __device__ __forceinline__ void split(float x, el16 (&p)[3]) {
+#pragma unroll
+        for (int q = 0; q < NP; q++) {
+            if (F16) { const _Float16 v = (_Float16)x; p[q] = __builtin_bit_cast(el16, v); x -= (float)v; }
+            else { const __bf16 v = (__bf16)x; p[q] = __builtin_bit_cast(el16, v); x -= (float)v; }
+        }
+    }
+};
+
+template <bool F16> struct ErCfg {
+    static constexpr int NP = Piece<F16>::NP, NPROD = Piece<F16>::NPROD;
     static constexpr int NS = 8 * NPROD;                  // MFMAs (and gaps) per phase
     static constexpr int NW = 3 * NP * 8;                 // A operands per wave
     static constexpr int XT = NP * ER_TILE_P;             // elements of one tile buffer
@@ -97,6 +129,22 @@ __host__ __device__ inline int er_src_col(int layer, int pos) {
     return 32 * j + 8 * (r >> 2) + 4 * h + (r & 3);
 }
 
+// What both packers do for a lane: the 8 contraction elements (positions 64h + 8st .. + 7, through er_src_col of `layer`) of one output
+// feature's weight row (W + row_off), cut into pieces -> the NP 16-byte MFMA A operands op[0 .. NP - 1]
+template <bool F16>
+__device__ __forceinline__ void pack_operands(const float *__restrict__ W, size_t row_off, int layer, int h, int st, i32x4 (&op)[3]) {
+    el16 p[3][8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        el16 e[3];
+        Piece<F16>::split(W[row_off + er_src_col(layer, 64 * h + 8 * st + i)], e);
+#pragma unroll
+        for (int q = 0; q < Piece<F16>::NP; q++) p[q][i] = e[q];
+    }
+#pragma unroll
+    for (int q = 0; q < Piece<F16>::NP; q++) op[q] = *reinterpret_cast<const i32x4 *>(p[q]);
+}
+
 template <bool F16>
 __global__ __launch_bounds__(64) void k_edge_mlp3r_pack(const float *__restrict__ W0, int ld0, const float *__restrict__ W1, int ld1,
                                                         const float *__restrict__ W2, int ld2, i32x4 *__restrict__ img) {
@@ -106,19 +154,10 @@ __global__ __launch_bounds__(64) void k_edge_mlp3r_pack(const float *__restrict_
     const int lane = threadIdx.x, m = lane & 31, h = lane >> 5;
     const float *W = l == 0 ? W0 : (l == 1 ? W1 : W2);
     const int ld = l == 0 ? ld0 : (l == 1 ? ld1 : ld2);
-    el16 p[3][8];
+    i32x4 op[3];
+    pack_operands<F16>(W, (size_t)(32 * j + m) * ld, l, h, st, op);
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-        float x = W[(size_t)(32 * j + m) * ld + er_src_col(l, 64 * h + 8 * st + i)];
-#pragma unroll
-        for (int q = 0; q < NP; q++) {
-            if (F16) { const _Float16 v = (_Float16)x; p[q][i] = __builtin_bit_cast(el16, v); x -= (float)v; }
-            else { const __bf16 v = (__bf16)x; p[q][i] = __builtin_bit_cast(el16, v); x -= (float)v; }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NP; q++)
-        img[((size_t)j * ErCfg<F16>::NW + (l * NP + q) * 8 + st) * 64 + lane] = *reinterpret_cast<const i32x4 *>(p[q]);
+    for (int q = 0; q < NP; q++) img[((size_t)j * ErCfg<F16>::NW + (l * NP + q) * 8 + st) * 64 + lane] = op[q];
 }
 
 // Every ReLU here is relu_keep_nan (csplat_common.h: `x < 0.f ? 0.f : x`, a NaN passes).  A value that left fp16's range turns into NaN one layer later (pieces Inf and -Inf),
@@ -221,20 +260,8 @@ __global__ __launch_bounds__(256) void k_edge_mlp3r(int64_t M, const float *__re
             else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(Wv[id & 7]), "v"(b));
         }
     };
-    // two values -> one dword of 16-bit pieces (round to nearest even), and the two pieces back as floats
-    auto pk = [&](float lo, float hi) __attribute__((always_inline)) -> unsigned {
-        if (F16) { h16x2 v; v[0] = (_Float16)lo; v[1] = (_Float16)hi; return __builtin_bit_cast(unsigned, v); }
-        bf16x2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-        return __builtin_bit_cast(unsigned, v);
-    };
-    auto lo_f = [&](unsigned q) __attribute__((always_inline)) -> float {
-        if (F16) return (float)__builtin_bit_cast(h16x2, q)[0];
-        return __uint_as_float(q << 16);
-    };
-    auto hi_f = [&](unsigned q) __attribute__((always_inline)) -> float {
-        if (F16) return (float)__builtin_bit_cast(h16x2, q)[1];
-        return __uint_as_float(q & 0xffff0000u);
-    };
+    constexpr auto pk = Piece<F16>::pk;
+    constexpr auto lo_f = Piece<F16>::lo_f, hi_f = Piece<F16>::hi_f;
 
     // =================== side work, cut into operations of 1-4 instructions that ride in the gaps between MFMAs.  One wave per SIMD: a gap
     // hides ~5 single-issue instructions, the sixth costs its full price -- so every task is a numbered list of small operations and
@@ -657,11 +684,11 @@ __global__ __launch_bounds__(256) void k_edge_mlp3r(int64_t M, const float *__re
 //   h = relu(agg Wa^T + x Wx^T + b0);  h = relu(h W2^T + b2);  x' = LayerNorm(h W3^T + b3) + x;  xa' = x' Wi^T;  xb' = x' Wj^T
 // (/root/reference/meshnet/graph_network.py:203-222).  Rounds 2-5 ran it on the exact-fp32 MFMA with the weights transposed through LDS
 // by scalar writes (k_node_update, csplat_gemm.hip: 44 us at N = 1e4, 0.66 of the 3.0 ms rollout step).  Here: 16-bit pieces as in the edge
-// kernel (F16: two fp16 pieces, three products, a fixed 2^-4 scale; else three bf16 pieces, six products), weights PRE-PACKED as MFMA A
+// kernel (Piece<F16>: two fp16 pieces, three products, a fixed 2^-4 scale; else three bf16 pieces, six products), weights PRE-PACKED as MFMA A
 // operands (csplat_gnn_node_update_pack: [matrix 6][wave 4][piece 3][step 8][lane] x 16 bytes) and streamed from L2 into registers half
 // a product ahead; one 32-row tile per 4-wave workgroup, wave j = output features 32j .. 32j + 31, activations between the layers as
-// piece tiles in LDS.  ~160 registers and 80 KB of LDS: two workgroups per CU, which is what fills the gaps (the layers of a tile are
-// a dependent chain).  (Two tiles per workgroup sharing each weight operand -- half the 576 KB of packed weights per row through the L1 --
+// piece tiles in LDS (PieceChain<F16> below, which k_rows_chain runs on as well).  ~160 registers and 80 KB of LDS: two workgroups per CU,
+// which is what fills the gaps (the layers of a tile are a dependent chain).  (Two tiles per workgroup sharing each weight operand -- half the 576 KB of packed weights per row through the L1 --
 // measured SLOWER, 36.9 against 30.3 us: the chain of six products per tile, not the weight traffic, is what a workgroup waits for.)
 constexpr int NB_MATS = 6;                                         // Wa, Wx, W2, W3, Wi', Wj'
 constexpr size_t NB_IMAGE_BYTES = (size_t)NB_MATS * 4 * 3 * 8 * 64 * 16;      // 589,824
@@ -678,77 +705,50 @@ __global__ __launch_bounds__(64) void k_node_pack(const float *__restrict__ W0, 
     const float *W = mat == 0 ? W0 : mat == 1 ? W1 : mat == 2 ? W2 : mat == 3 ? W3 : mat == 4 ? W4 : W5;
     if (!W) return;
     const int lane = threadIdx.x, m = lane & 31, h = lane >> 5;
-    constexpr int NP = F16 ? 2 : 3;
-    el16 p[3][8];
+    constexpr int NP = Piece<F16>::NP;
+    i32x4 op[3];
+    pack_operands<F16>(W, (size_t)(32 * j + m) * EM_N, mat < 2 ? 0 : 1, h, st, op);
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-        float x = W[(size_t)(32 * j + m) * EM_N + er_src_col(mat < 2 ? 0 : 1, 64 * h + 8 * st + i)];
-#pragma unroll
-        for (int q = 0; q < NP; q++) {
-            if (F16) { const _Float16 v = (_Float16)x; p[q][i] = __builtin_bit_cast(el16, v); x -= (float)v; }
-            else { const __bf16 v = (__bf16)x; p[q][i] = __builtin_bit_cast(el16, v); x -= (float)v; }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NP; q++) img[((size_t)((mat * 4 + j) * NP + q) * 8 + st) * 64 + lane] = *reinterpret_cast<const i32x4 *>(p[q]);
+    for (int q = 0; q < NP; q++) img[((size_t)((mat * 4 + j) * NP + q) * 8 + st) * 64 + lane] = op[q];
 }
 
-template <bool F16>
-__global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const float *__restrict__ agg, const float *__restrict__ x,
-                                                           const i32x4 *__restrict__ img, const float *__restrict__ b0,
-                                                           const float *__restrict__ b2, const float *__restrict__ b3,
-                                                           const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
-                                                           int has_next, float *__restrict__ x_new, float *__restrict__ xa,
-                                                           float *__restrict__ xb, const int *__restrict__ piece_ptr) {
-    extern __shared__ char s_mem[];
-    el16 *const sB = reinterpret_cast<el16 *>(s_mem);                                         // three tiles of three pieces
-    float2 *const sS = reinterpret_cast<float2 *>(s_mem + (size_t)3 * NB_XT * 2);             // [32][wave 4] (sum, M2)
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = lane & 31, h = lane >> 5;
-    const int64_t row0 = (int64_t)blockIdx.x * 32;
-    // F16: two fp16 pieces per operand, three products per step -- half the MFMAs of the layers' dependent chain.  fp16's range is kept by
-    // running everything multiplied by SC = 2^-4 (exact: ReLU is homogeneous, LayerNorm takes SC^2 eps, the next layer's products are
-    // multiplied back): aggregates and latents up to ~1e6 in magnitude fit, and an element below 2 of the original units keeps an absolute
-    // error of 5e-7 -- node latents and aggregates of LayerNorm'd messages are O(1 .. 100).
-    constexpr int NP = F16 ? 2 : 3, NPROD = F16 ? 3 : 6;
-    constexpr float SC = F16 ? 0.0625f : 1.f, ISC = F16 ? 16.f : 1.f;
-    auto pk = [&](float lo, float hi) __attribute__((always_inline)) -> unsigned {
-        if (F16) { h16x2 v; v[0] = (_Float16)lo; v[1] = (_Float16)hi; return __builtin_bit_cast(unsigned, v); }
-        bf16x2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-        return __builtin_bit_cast(unsigned, v);
-    };
-    auto lo_f = [&](unsigned q) __attribute__((always_inline)) -> float {
-        if (F16) return (float)__builtin_bit_cast(h16x2, q)[0];
-        return __uint_as_float(q << 16);
-    };
-    auto hi_f = [&](unsigned q) __attribute__((always_inline)) -> float {
-        if (F16) return (float)__builtin_bit_cast(h16x2, q)[1];
-        return __uint_as_float(q & 0xffff0000u);
-    };
-    eps *= SC * SC;
+// PieceChain -- what a wave of k_node_update_b3 and k_rows_chain (below) works with: one 32-row tile per 4-wave workgroup, a chain of
+// 128-wide products on it.  Lane (n, h) of wave w holds, in an accumulator, features 32w + 8(r >> 2) + 4h + (r & 3) of row n.
+// F16: two fp16 pieces per operand, three products per step -- half the MFMAs of the layers' dependent chain.  fp16's range is kept by
+// running everything multiplied by SC = 2^-4 (exact: ReLU is homogeneous, LayerNorm takes SC^2 eps, the next layer's products are
+// multiplied back): aggregates and latents up to ~1e6 in magnitude fit, and an element below 2 of the original units keeps an absolute
+// error of 5e-7 -- node latents and aggregates of LayerNorm'd messages are O(1 .. 100).
+template <bool F16> struct PieceChain {
+    typedef Piece<F16> P;
+    static constexpr int NP = P::NP, NPROD = P::NPROD;
+    static constexpr float SC = P::SC;
+    const int lane, w, n, h;
+    const int64_t N, row0, grow;      // (grow: the row this lane holds in an accumulator)
+    const i32x4 *const img;
+    i32x4 wq[2][4 * NP];      // weights: the 24 A operands of a product in two halves (steps 0-3, 4-7), each requested half a product ahead
 
-    // weights: the 24 A operands of a product in two halves (steps 0-3, 4-7), each requested half a product ahead
-    i32x4 wq[2][4 * NP];
-    auto fetch = [&](int mat, int half) __attribute__((always_inline)) {
+    __device__ __forceinline__ PieceChain(int64_t N_, const i32x4 *__restrict__ img_)
+        : lane(threadIdx.x & 63), w(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)), n(lane & 31), h(lane >> 5), N(N_),
+          row0((int64_t)blockIdx.x * 32), grow(row0 + n), img(img_) {
+        fetch(0, 0);
+        fetch(0, 1);
+    }
+    __device__ __forceinline__ void fetch(int mat, int half) {
         const i32x4 *src = img + ((size_t)(mat * 4 + w) * NP * 8) * 64 + lane;
 #pragma unroll
         for (int p = 0; p < NP; p++)
 #pragma unroll
             for (int s4 = 0; s4 < 4; s4++) wq[half][p * 4 + s4] = src[(size_t)(p * 8 + 4 * half + s4) * 64];
-    };
-    fetch(0, 0);
-    fetch(0, 1);
-    // ---- the tile's rows of agg and x, whole rows per instruction (half-wave per row), cut into pieces -> tiles 0 and 1
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        const float *src = a == 0 ? agg : x;
+    }
+    // the tile's rows of src, whole rows per instruction (half-wave per row), cut into pieces -> tile Bt
+    __device__ __forceinline__ void cut_rows(const float *__restrict__ src, el16 *Bt, const int *__restrict__ piece_ptr = nullptr) {
         float4 v[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             int64_t row = row0 + 8 * w + 2 * k + h;
             row = row < N ? row : N - 1;
-            if (a == 0 && piece_ptr) {
-                // the aggregate arrives as the edge launch's "pieces" (csplat_gnn_edge_mlp3): node `row` owns pieces piece_ptr[row] ..
+            if (piece_ptr) {
+                // the rows arrive as the edge launch's "pieces" (csplat_gnn_edge_mlp3): node `row` owns pieces piece_ptr[row] ..
                 // piece_ptr[row + 1] - 1, summed here in that order -- what csplat_gnn_segment_sum over the pieces would have written
                 const int p0 = piece_ptr[row], p1 = piece_ptr[row + 1];
                 float4 acc4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -761,28 +761,18 @@ __global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const floa
         }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            el16 *dst = sB + (size_t)a * NB_XT + (size_t)(8 * w + 2 * k + h) * EM_STRIDE + 4 * n;
+            el16 *dst = Bt + (size_t)(8 * w + 2 * k + h) * EM_STRIDE + 4 * n;
             float e[4] = {v[k].x * SC, v[k].y * SC, v[k].z * SC, v[k].w * SC};
 #pragma unroll
             for (int p = 0; p < NP; p++) {
-                const unsigned q0 = pk(e[0], e[1]), q1 = pk(e[2], e[3]);
+                const unsigned q0 = P::pk(e[0], e[1]), q1 = P::pk(e[2], e[3]);
                 *reinterpret_cast<uint2 *>(dst + (size_t)p * ER_TILE_P) = make_uint2(q0, q1);
-                e[0] -= lo_f(q0); e[1] -= hi_f(q0); e[2] -= lo_f(q1); e[3] -= hi_f(q1);
+                e[0] -= P::lo_f(q0); e[1] -= P::hi_f(q0); e[2] -= P::lo_f(q1); e[3] -= P::hi_f(q1);
             }
         }
     }
-    // the residual's x in the accumulators' layout (register r <-> feature 32w + 8(r >> 2) + 4h + (r & 3) of row n)
-    float4 xres[4];
-    {
-        int64_t row = row0 + n;
-        row = row < N ? row : N - 1;
-#pragma unroll
-        for (int q = 0; q < 4; q++) xres[q] = *reinterpret_cast<const float4 *>(x + row * EM_N + 32 * w + 8 * q + 4 * h);
-    }
-    __syncthreads();
-
     // one product: acc += W_mat (registers) x tile (pieces in LDS); the next weights are requested as the halves free up
-    auto product = [&](const el16 *Bt, f32x16 &acc, int next_mat) __attribute__((always_inline)) {
+    __device__ __forceinline__ void product(const el16 *Bt, f32x16 &acc, int next_mat) {
         constexpr int WP[6] = {0, F16 ? 1 : 2, F16 ? 0 : 1, 0, 1, 0}, XP[6] = {F16 ? 1 : 2, 0, F16 ? 0 : 1, 1, 0, 0};
         const el16 *row = Bt + (size_t)n * EM_STRIDE + 64 * h;
         i32x4 bc[NP], bn[NP];
@@ -806,16 +796,16 @@ __global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const floa
             for (int p = 0; p < NP; p++) bc[p] = bn[p];
         }
         if (next_mat >= 0) fetch(next_mat, 1);
-    };
-    auto start_from = [&](const float *b, f32x16 &acc) __attribute__((always_inline)) {
+    }
+    __device__ __forceinline__ void start_from(const float *__restrict__ b, f32x16 &acc) const {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const float4 t = b ? *reinterpret_cast<const float4 *>(b + 32 * w + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
             acc[4 * q] = t.x * SC; acc[4 * q + 1] = t.y * SC; acc[4 * q + 2] = t.z * SC; acc[4 * q + 3] = t.w * SC;
         }
-    };
+    }
     // 16 values of row n -> the next product's pieces, positions 32w + 16h .. + 15
-    auto to_pieces = [&](const float (&v)[16], el16 *Bt, float scale) __attribute__((always_inline)) {
+    __device__ __forceinline__ void to_pieces(const float (&v)[16], el16 *Bt, float scale) const {
         float e[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) e[r] = F16 ? v[r] * scale : v[r];
@@ -824,40 +814,75 @@ __global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const floa
         for (int p = 0; p < NP; p++) {
             unsigned q[8];
 #pragma unroll
-            for (int j = 0; j < 8; j++) { q[j] = pk(e[2 * j], e[2 * j + 1]); e[2 * j] -= lo_f(q[j]); e[2 * j + 1] -= hi_f(q[j]); }
+            for (int j = 0; j < 8; j++) { q[j] = P::pk(e[2 * j], e[2 * j + 1]); e[2 * j] -= P::lo_f(q[j]); e[2 * j + 1] -= P::hi_f(q[j]); }
             *reinterpret_cast<uint4 *>(dst + (size_t)p * ER_TILE_P) = make_uint4(q[0], q[1], q[2], q[3]);
             *reinterpret_cast<uint4 *>(dst + (size_t)p * ER_TILE_P + 8) = make_uint4(q[4], q[5], q[6], q[7]);
         }
-    };
-    const int64_t grow = row0 + n;
-    auto store_rows = [&](const float (&v)[16], float *dst) __attribute__((always_inline)) {
+    }
+    __device__ __forceinline__ void store_rows(const float (&v)[16], float *__restrict__ dst) const {
         if (grow < N) {
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 *reinterpret_cast<float4 *>(dst + grow * EM_N + 32 * w + 8 * q + 4 * h) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
         }
-    };
-    el16 *const B0 = sB, *const B1 = sB + NB_XT, *const B2 = sB + 2 * NB_XT;
+    }
+    // a bare product dst = tile W^T in the original units, from the weights in the registers
+    __device__ __forceinline__ void plain_product(const el16 *Bt, int next_mat, float *__restrict__ dst) {
+        f32x16 acc;
+        float v[16];
+        start_from(nullptr, acc);
+        product(Bt, acc, next_mat);
+#pragma unroll
+        for (int r = 0; r < 16; r++) v[r] = acc[r] * P::ISC;
+        store_rows(v, dst);
+    }
+};
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const float *__restrict__ agg, const float *__restrict__ x,
+                                                           const i32x4 *__restrict__ img, const float *__restrict__ b0,
+                                                           const float *__restrict__ b2, const float *__restrict__ b3,
+                                                           const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
+                                                           int has_next, float *__restrict__ x_new, float *__restrict__ xa,
+                                                           float *__restrict__ xb, const int *__restrict__ piece_ptr) {
+    extern __shared__ char s_mem[];
+    el16 *const B0 = reinterpret_cast<el16 *>(s_mem), *const B1 = B0 + NB_XT, *const B2 = B0 + 2 * NB_XT;      // three tiles of three pieces
+    float2 *const sS = reinterpret_cast<float2 *>(s_mem + (size_t)3 * NB_XT * 2);             // [32][wave 4] (sum, M2)
+    constexpr float SC = Piece<F16>::SC;
+    eps *= SC * SC;
+    PieceChain<F16> c(N, img);
+    const int w = c.w, n = c.n, h = c.h;
+    c.cut_rows(agg, B0, piece_ptr);
+    c.cut_rows(x, B1);
+    // the residual's x in the accumulators' layout (register r <-> feature 32w + 8(r >> 2) + 4h + (r & 3) of row n)
+    float4 xres[4];
+    {
+        int64_t row = c.row0 + n;
+        row = row < N ? row : N - 1;
+#pragma unroll
+        for (int q = 0; q < 4; q++) xres[q] = *reinterpret_cast<const float4 *>(x + row * EM_N + 32 * w + 8 * q + 4 * h);
+    }
+    __syncthreads();
     f32x16 acc;
     float v[16];
     // ---- layer 1 (K = 256: agg and x)
-    start_from(b0, acc);
-    product(B0, acc, 1);
-    product(B1, acc, 2);
+    c.start_from(b0, acc);
+    c.product(B0, acc, 1);
+    c.product(B1, acc, 2);
 #pragma unroll
     for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]);
-    to_pieces(v, B2, 1.f);
+    c.to_pieces(v, B2, 1.f);
     __syncthreads();
     // ---- layer 2
-    start_from(b2, acc);
-    product(B2, acc, 3);
+    c.start_from(b2, acc);
+    c.product(B2, acc, 3);
 #pragma unroll
     for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]);
-    to_pieces(v, B0, 1.f);
+    c.to_pieces(v, B0, 1.f);
     __syncthreads();
     // ---- layer 3, LayerNorm (the four waves' partials combined by the parallel-variance formula), residual
-    start_from(b3, acc);
-    product(B0, acc, has_next ? 4 : -1);
+    c.start_from(b3, acc);
+    c.product(B0, acc, has_next ? 4 : -1);
     {
         float s = 0.f;
 #pragma unroll
@@ -885,24 +910,16 @@ __global__ __launch_bounds__(256, 2) void k_node_update_b3(int64_t N, const floa
             v[4 * q + 2] = (acc[4 * q + 2] - mean) * rstd * ga.z + be.z + xres[q].z; v[4 * q + 3] = (acc[4 * q + 3] - mean) * rstd * ga.w + be.w + xres[q].w;
         }
     }
-    store_rows(v, x_new);
+    c.store_rows(v, x_new);
     if (!has_next) return;
     // ---- the next layer's node-level products of the updated latents
-    to_pieces(v, B1, SC);
+    c.to_pieces(v, B1, SC);
     __syncthreads();
-    start_from(nullptr, acc);
-    product(B1, acc, 5);
-#pragma unroll
-    for (int r = 0; r < 16; r++) v[r] = acc[r] * ISC;
-    store_rows(v, xa);
-    start_from(nullptr, acc);
-    product(B1, acc, -1);
-#pragma unroll
-    for (int r = 0; r < 16; r++) v[r] = acc[r] * ISC;
-    store_rows(v, xb);
+    c.plain_product(B1, 5, xa);
+    c.plain_product(B1, -1, xb);
 }
 
-// A CHAIN of 128-wide Linears on node rows with the node update's machinery (pre-packed 16-bit-piece weights streamed into registers half a
+// A CHAIN of 128-wide Linears on node rows, PieceChain<F16> again (pre-packed 16-bit-piece weights streamed into registers half a
 // product ahead, one 32-row tile per workgroup), round 6 -- what the rollout step still ran as four launches of the exact-fp32
 // k_linear128_rows32 (16 us each at N = 10^4: latency-sized):
 //   MODE 0: out_a = x Wa^T, out_b = x Wb^T                 (the first processor layer's x_i / x_j products, graph_network.py:178-199)
@@ -913,151 +930,30 @@ template <bool F16, int MODE>
 __global__ __launch_bounds__(256, 2) void k_rows_chain(int64_t N, const float *__restrict__ x, const i32x4 *__restrict__ img,
                                                        const float *__restrict__ b0, const float *__restrict__ b1,
                                                        float *__restrict__ out_a, float *__restrict__ out_b) {
-
     extern __shared__ char s_mem[];
-    el16 *const sB = reinterpret_cast<el16 *>(s_mem);                                         // three tiles of three pieces
-    float2 *const sS = reinterpret_cast<float2 *>(s_mem + (size_t)3 * NB_XT * 2);             // [32][wave 4] (sum, M2)
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = lane & 31, h = lane >> 5;
-    const int64_t row0 = (int64_t)blockIdx.x * 32;
-    // F16: two fp16 pieces per operand, three products per step -- half the MFMAs of the layers' dependent chain.  fp16's range is kept by
-    // running everything multiplied by SC = 2^-4 (exact: ReLU is homogeneous, LayerNorm takes SC^2 eps, the next layer's products are
-    // multiplied back): aggregates and latents up to ~1e6 in magnitude fit, and an element below 2 of the original units keeps an absolute
-    // error of 5e-7 -- node latents and aggregates of LayerNorm'd messages are O(1 .. 100).
-    constexpr int NP = F16 ? 2 : 3, NPROD = F16 ? 3 : 6;
-    constexpr float SC = F16 ? 0.0625f : 1.f, ISC = F16 ? 16.f : 1.f;
-    auto pk = [&](float lo, float hi) __attribute__((always_inline)) -> unsigned {
-        if (F16) { h16x2 v; v[0] = (_Float16)lo; v[1] = (_Float16)hi; return __builtin_bit_cast(unsigned, v); }
-        bf16x2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-        return __builtin_bit_cast(unsigned, v);
-    };
-    auto lo_f = [&](unsigned q) __attribute__((always_inline)) -> float {
-        if (F16) return (float)__builtin_bit_cast(h16x2, q)[0];
-        return __uint_as_float(q << 16);
-    };
-    auto hi_f = [&](unsigned q) __attribute__((always_inline)) -> float {
-        if (F16) return (float)__builtin_bit_cast(h16x2, q)[1];
-        return __uint_as_float(q & 0xffff0000u);
-    };
-
-    // weights: the 24 A operands of a product in two halves (steps 0-3, 4-7), each requested half a product ahead
-    i32x4 wq[2][4 * NP];
-    auto fetch = [&](int mat, int half) __attribute__((always_inline)) {
-        const i32x4 *src = img + ((size_t)(mat * 4 + w) * NP * 8) * 64 + lane;
-#pragma unroll
-        for (int p = 0; p < NP; p++)
-#pragma unroll
-            for (int s4 = 0; s4 < 4; s4++) wq[half][p * 4 + s4] = src[(size_t)(p * 8 + 4 * half + s4) * 64];
-    };
-    fetch(0, 0);
-    fetch(0, 1);
-    // ---- the tile's rows of x, whole rows per instruction (half-wave per row), cut into pieces -> tile 0
-    {
-        float4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            int64_t row = row0 + 8 * w + 2 * k + h;
-            row = row < N ? row : N - 1;
-            v[k] = *reinterpret_cast<const float4 *>(x + row * EM_N + 4 * n);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            el16 *dst = sB + (size_t)(8 * w + 2 * k + h) * EM_STRIDE + 4 * n;
-            float e[4] = {v[k].x * SC, v[k].y * SC, v[k].z * SC, v[k].w * SC};
-#pragma unroll
-            for (int p = 0; p < NP; p++) {
-                const unsigned q0 = pk(e[0], e[1]), q1 = pk(e[2], e[3]);
-                *reinterpret_cast<uint2 *>(dst + (size_t)p * ER_TILE_P) = make_uint2(q0, q1);
-                e[0] -= lo_f(q0); e[1] -= hi_f(q0); e[2] -= lo_f(q1); e[3] -= hi_f(q1);
-            }
-        }
-    }
+    el16 *const B0 = reinterpret_cast<el16 *>(s_mem), *const B1 = B0 + NB_XT;                 // tiles of three pieces (the node update's layout)
+    constexpr float ISC = Piece<F16>::ISC;
+    PieceChain<F16> c(N, img);
+    c.cut_rows(x, B0);
     __syncthreads();
-
-    // one product: acc += W_mat (registers) x tile (pieces in LDS); the next weights are requested as the halves free up
-    auto product = [&](const el16 *Bt, f32x16 &acc, int next_mat) __attribute__((always_inline)) {
-        constexpr int WP[6] = {0, F16 ? 1 : 2, F16 ? 0 : 1, 0, 1, 0}, XP[6] = {F16 ? 1 : 2, 0, F16 ? 0 : 1, 1, 0, 0};
-        const el16 *row = Bt + (size_t)n * EM_STRIDE + 64 * h;
-        i32x4 bc[NP], bn[NP];
-#pragma unroll
-        for (int p = 0; p < NP; p++) bc[p] = *reinterpret_cast<const i32x4 *>(row + p * ER_TILE_P);
-#pragma unroll
-        for (int st = 0; st < 8; st++) {
-            if (st < 7) {
-#pragma unroll
-                for (int p = 0; p < NP; p++) bn[p] = *reinterpret_cast<const i32x4 *>(row + p * ER_TILE_P + 8 * (st + 1));
-            }
-#pragma unroll
-            for (int i = 0; i < NPROD; i++) {
-                if (F16) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, wq[st >> 2][WP[i] * 4 + (st & 3)]),
-                                                                      __builtin_bit_cast(f16x8v, bc[XP[i]]), acc, 0, 0, 0);
-                else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8v, wq[st >> 2][WP[i] * 4 + (st & 3)]),
-                                                                   __builtin_bit_cast(bf16x8v, bc[XP[i]]), acc, 0, 0, 0);
-            }
-            if (st == 3 && next_mat >= 0) fetch(next_mat, 0);
-#pragma unroll
-            for (int p = 0; p < NP; p++) bc[p] = bn[p];
-        }
-        if (next_mat >= 0) fetch(next_mat, 1);
-    };
-    auto start_from = [&](const float *b, f32x16 &acc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float4 t = b ? *reinterpret_cast<const float4 *>(b + 32 * w + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
-            acc[4 * q] = t.x * SC; acc[4 * q + 1] = t.y * SC; acc[4 * q + 2] = t.z * SC; acc[4 * q + 3] = t.w * SC;
-        }
-    };
-    // 16 values of row n -> the next product's pieces, positions 32w + 16h .. + 15
-    auto to_pieces = [&](const float (&v)[16], el16 *Bt, float scale) __attribute__((always_inline)) {
-        float e[16];
-#pragma unroll
-        for (int r = 0; r < 16; r++) e[r] = F16 ? v[r] * scale : v[r];
-        el16 *dst = Bt + (size_t)n * EM_STRIDE + 32 * w + 16 * h;
-#pragma unroll
-        for (int p = 0; p < NP; p++) {
-            unsigned q[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) { q[j] = pk(e[2 * j], e[2 * j + 1]); e[2 * j] -= lo_f(q[j]); e[2 * j + 1] -= hi_f(q[j]); }
-            *reinterpret_cast<uint4 *>(dst + (size_t)p * ER_TILE_P) = make_uint4(q[0], q[1], q[2], q[3]);
-            *reinterpret_cast<uint4 *>(dst + (size_t)p * ER_TILE_P + 8) = make_uint4(q[4], q[5], q[6], q[7]);
-        }
-    };
-    const int64_t grow = row0 + n;
-    auto store_rows = [&](const float (&v)[16], float *dst) __attribute__((always_inline)) {
-        if (grow < N) {
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                *reinterpret_cast<float4 *>(dst + grow * EM_N + 32 * w + 8 * q + 4 * h) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        }
-    };
-    el16 *const B0 = sB, *const B1 = sB + NB_XT, *const B2 = sB + 2 * NB_XT;
     f32x16 acc;
     float v[16];
     if (MODE == 0) {
-        start_from(nullptr, acc);
-        product(B0, acc, 1);
-#pragma unroll
-        for (int r = 0; r < 16; r++) v[r] = acc[r] * ISC;
-        store_rows(v, out_a);
-        start_from(nullptr, acc);
-        product(B0, acc, -1);
-#pragma unroll
-        for (int r = 0; r < 16; r++) v[r] = acc[r] * ISC;
-        store_rows(v, out_b);
+        c.plain_product(B0, 1, out_a);
+        c.plain_product(B0, -1, out_b);
     } else {
-        start_from(b0, acc);
-        product(B0, acc, 2);
+        c.start_from(b0, acc);
+        c.product(B0, acc, 2);
 #pragma unroll
         for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]);
-        to_pieces(v, B1, 1.f);
+        c.to_pieces(v, B1, 1.f);
         __syncthreads();
-        start_from(b1, acc);
-        product(B1, acc, -1);
+        c.start_from(b1, acc);
+        c.product(B1, acc, -1);
 #pragma unroll
         for (int r = 0; r < 16; r++) v[r] = relu_keep_nan(acc[r]) * ISC;
-        store_rows(v, out_a);
+        c.store_rows(v, out_a);
     }
-    (void)B2; (void)sS;
 }
 
 }  // namespace
@@ -1071,19 +967,66 @@ extern "C" int csplat_gnn_edge_mlp3_mode(int mode) {
     return was;
 }
 
+// ---- what the entry points below share
+template <int I> using int_c = std::integral_constant<int, I>;
+// the one mode dispatch: f(std::bool_constant<F16>) under the current piece mode, so that a launch's argument list is written once
+template <class F> static int by_mode(F &&f) { return g_em_mode == 0 ? f(std::true_type{}) : f(std::false_type{}); }
+// `bytes` of dynamic LDS for KERNEL: the runtime is asked once per kernel, a refusal is the caller's error `what`
+template <auto KERNEL> static int need_lds(size_t bytes, const char *what) {
+    static const bool ok = [bytes] {
+        const bool granted = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+        (void)hipGetLastError();
+        return granted;
+    }();
+    CSPLAT_REQUIRE(ok, what);
+    return 0;
+}
+template <class... T> static bool aligned16(const T *...p) { return ((... | (uintptr_t)p) & 15u) == 0; }
+
+// k_edge_mlp3r<F16, MODE> over M rows of in_cols floats, for csplat_gnn_edge_mlp3 and csplat_gnn_mlp3_rows.  The kernel addresses its rows
+// through 32-bit buffer offsets (rows past the end dropped by the hardware's bounds check): 2^22 rows = 2 GiB of [.,128] floats per launch,
+// longer inputs go out in chunks.  This owns the chunk size, the grid rule and the per-chunk offsets of every per-row operand.
+// CSPLAT_EM_CHUNK_ROWS (a test-only hook: a smaller chunk, a multiple of 64, so that tests reach the loop) holds for BOTH entries since the
+// two loops became this one; csplat_gnn_mlp3_rows did not read it before.
+template <bool F16, int MODE>
+static int em_launch_chunks(hipStream_t s, const char *lds_refused, int64_t M, const float *e0, int in_cols, float alpha, const float *e0_absmax,
+                            const float *xa, const int64_t *ia, const float *xb, const int64_t *ib, const void *image, const float *b0,
+                            const float *b1, const float *b2, const float *gamma, const float *beta, float eps, float *out,
+                            const int32_t *group_piece0, float *pieces) {
+    if (const int e = need_lds<k_edge_mlp3r<F16, MODE>>(ErCfg<F16>::LDS_BYTES, lds_refused)) return e;
+    ProfScope ps(PROF_GNN, s);
+    static const int64_t CHUNK = [] {
+        const char *e = getenv("CSPLAT_EM_CHUNK_ROWS");
+        const int64_t v = e ? atoll(e) : 0;
+        return (v >= 64 && v % 64 == 0 && v <= ((int64_t)1 << 22)) ? v : (int64_t)1 << 22;
+    }();
+    for (int64_t r0 = 0; r0 < M; r0 += CHUNK) {
+        const int64_t rows = M - r0 < CHUNK ? M - r0 : CHUNK;
+        const int64_t nst = (rows + 63) / 64;
+        const int grid = (int)(nst < 256 ? nst : 256);      // persistent: one 4-wave workgroup per CU, two 32-row tiles in flight each
+        unsigned long long *stamps = csplat_stamp_buffer((size_t)256 * 64);
+        k_edge_mlp3r<F16, MODE><<<grid, 256, ErCfg<F16>::LDS_BYTES, s>>>(
+            rows, e0 + r0 * in_cols, alpha, e0_absmax, xa, ia ? ia + r0 : nullptr, xb, ib ? ib + r0 : nullptr, (const i32x4 *)image, b0, b1, b2,
+            gamma, beta, eps, out ? out + r0 * EM_N : nullptr, group_piece0 ? group_piece0 + r0 / 8 : nullptr, pieces, MODE == 2 ? in_cols : 0, stamps);
+        LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 extern "C" size_t csplat_gnn_edge_mlp3_image_bytes(void) { return ErCfg<false>::IMAGE_BYTES; }      // (the larger of the two)
 
 extern "C" int csplat_gnn_edge_mlp3_pack(void *stream, const float *W0, int ld0, const float *W1, int ld1, const float *W2, int ld2, void *image) {
     CSPLAT_REQUIRE(W0 && W1 && W2 && image && ld0 >= EM_N && ld1 >= EM_N && ld2 >= EM_N, "csplat_gnn_edge_mlp3_pack: bad arguments");
-    CSPLAT_REQUIRE(((uintptr_t)image & 15u) == 0, "csplat_gnn_edge_mlp3_pack: the image must be 16-byte aligned");
-    if (g_em_mode == 0) k_edge_mlp3r_pack<true><<<4 * 3 * 8, 64, 0, (hipStream_t)stream>>>(W0, ld0, W1, ld1, W2, ld2, (i32x4 *)image);
-    else k_edge_mlp3r_pack<false><<<4 * 3 * 8, 64, 0, (hipStream_t)stream>>>(W0, ld0, W1, ld1, W2, ld2, (i32x4 *)image);
-    LAUNCH_CHECK();
-    return 0;
+    CSPLAT_REQUIRE(aligned16(image), "csplat_gnn_edge_mlp3_pack: the image must be 16-byte aligned");
+    return by_mode([&](auto f16) {
+        k_edge_mlp3r_pack<decltype(f16)::value><<<4 * 3 * 8, 64, 0, (hipStream_t)stream>>>(W0, ld0, W1, ld1, W2, ld2, (i32x4 *)image);
+        LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 extern "C" int csplat_absmax(void *stream, int64_t n, const float *x, float *out) {
-    CSPLAT_REQUIRE(n >= 0 && out && (n == 0 || x) && (n & 3) == 0 && ((uintptr_t)x & 15u) == 0, "csplat_absmax: n must be a multiple of 4, x 16-byte aligned");
+    CSPLAT_REQUIRE(n >= 0 && out && (n == 0 || x) && (n & 3) == 0 && aligned16(x), "csplat_absmax: n must be a multiple of 4, x 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(out, 0, sizeof(float), s));
     if (n == 0) return 0;
@@ -1102,62 +1045,46 @@ extern "C" int csplat_gnn_edge_mlp3(void *stream, int64_t E, const float *e0, fl
                    "csplat_gnn_edge_mlp3: bad arguments");
     CSPLAT_REQUIRE(!agg || (group_piece0 && g_em_mode == 0), "csplat_gnn_edge_mlp3: the fused aggregation needs group_piece0 and mode 0");
     if (E == 0) return 0;
-    const uintptr_t al = (uintptr_t)e0 | (uintptr_t)xa | (uintptr_t)xb | (uintptr_t)image | (uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)b2 |
-                         (uintptr_t)ln_gamma | (uintptr_t)ln_beta | (uintptr_t)out | (uintptr_t)pieces;
-    CSPLAT_REQUIRE((al & 15u) == 0, "csplat_gnn_edge_mlp3: operands must be 16-byte aligned");
+    CSPLAT_REQUIRE(aligned16(e0, xa, xb, image, b0, b1, b2, ln_gamma, ln_beta, out, pieces), "csplat_gnn_edge_mlp3: operands must be 16-byte aligned");
     CSPLAT_REQUIRE(out != e0 && pieces != e0, "csplat_gnn_edge_mlp3: out must not alias e0 (rows are read ahead of the rows being written)");
     int ex = 0;
     const float m = frexpf(alpha, &ex);
     CSPLAT_REQUIRE(alpha > 0.f && m == 0.5f, "csplat_gnn_edge_mlp3: alpha must be a power of two (the edge scale 2^l)");
-    hipStream_t s = (hipStream_t)stream;
-    static int s_ok = -1;
-    if (s_ok < 0) {
-        s_ok = hipFuncSetAttribute((const void *)k_edge_mlp3r<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ErCfg<true>::LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_edge_mlp3r<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ErCfg<true>::LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_edge_mlp3r<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ErCfg<true>::LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_edge_mlp3r<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ErCfg<false>::LDS_BYTES) == hipSuccess;
-        (void)hipGetLastError();
-    }
-    CSPLAT_REQUIRE(s_ok, "csplat_gnn_edge_mlp3: 141 KB of dynamic LDS refused by the runtime");
-    ProfScope ps(PROF_GNN, s);
-    // the kernel addresses its rows through 32-bit buffer offsets (rows past the end dropped by the hardware's bounds check): 2^22 rows =
-    // 2 GiB of [.,128] floats per launch
-    static const int64_t CHUNK = [] {      // (CSPLAT_EM_CHUNK_ROWS: a smaller chunk, a multiple of 64, so that tests reach the loop)
-        const char *e = getenv("CSPLAT_EM_CHUNK_ROWS");
-        const int64_t v = e ? atoll(e) : 0;
-        return (v >= 64 && v % 64 == 0 && v <= ((int64_t)1 << 22)) ? v : (int64_t)1 << 22;
-    }();
-    for (int64_t r0 = 0; r0 < E; r0 += CHUNK) {
-        const int64_t rows = E - r0 < CHUNK ? E - r0 : CHUNK;
-        const int64_t nst = (rows + 63) / 64;
-        const int grid = (int)(nst < 256 ? nst : 256);      // persistent: one 4-wave workgroup per CU, two 32-row tiles in flight each
-        unsigned long long *stamps = csplat_stamp_buffer((size_t)256 * 64);
-        float *o = out ? out + r0 * EM_N : nullptr;
-        const int *gp = group_piece0 ? group_piece0 + r0 / 8 : nullptr;
-        if (agg)
-            k_edge_mlp3r<true, 1><<<grid, 256, ErCfg<true>::LDS_BYTES, s>>>(rows, e0 + r0 * EM_N, alpha, e0_absmax, xa, index_a + r0, xb, index_b + r0,
-                                                                                (const i32x4 *)image, b0, b1, b2, ln_gamma, ln_beta, ln_eps, o, gp, pieces, 0, stamps);
-        else if (g_em_mode == 0)
-            k_edge_mlp3r<true, 0><<<grid, 256, ErCfg<true>::LDS_BYTES, s>>>(rows, e0 + r0 * EM_N, alpha, e0_absmax, xa, index_a + r0, xb, index_b + r0,
-                                                                                 (const i32x4 *)image, b0, b1, b2, ln_gamma, ln_beta, ln_eps, o, gp, pieces, 0, stamps);
-        else
-            k_edge_mlp3r<false, 0><<<grid, 256, ErCfg<false>::LDS_BYTES, s>>>(rows, e0 + r0 * EM_N, alpha, e0_absmax, xa, index_a + r0, xb, index_b + r0,
-                                                                                   (const i32x4 *)image, b0, b1, b2, ln_gamma, ln_beta, ln_eps, o, gp, pieces, 0, stamps);
-        LAUNCH_CHECK();
-    }
-    return 0;
+    auto run = [&](auto f16, auto mode) {      // MODE 1 (agg): messages summed per destination, pieces out; 0: message rows out
+        return em_launch_chunks<decltype(f16)::value, decltype(mode)::value>(
+            (hipStream_t)stream, "csplat_gnn_edge_mlp3: 141 KB of dynamic LDS refused by the runtime", E, e0, EM_N, alpha, e0_absmax, xa, index_a, xb,
+            index_b, image, b0, b1, b2, ln_gamma, ln_beta, ln_eps, out, group_piece0, pieces);
+    };
+    if (agg) return run(std::true_type{}, int_c<1>{});
+    return by_mode([&](auto f16) { return run(f16, int_c<0>{}); });
 }
 
 extern "C" size_t csplat_gnn_node_update_image_bytes(void) { return NB_IMAGE_BYTES; }
 
+// one launch of a PieceChain kernel over N rows (a 32-row tile per workgroup), KERNEL(N, args...)
+template <auto KERNEL, class... A> static int chain_launch(void *stream, const char *lds_refused, int64_t N, A... args) {
+    if (const int e = need_lds<KERNEL>(NB_LDS_BYTES, lds_refused)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_GNN, s);
+    KERNEL<<<(unsigned)((N + 31) / 32), 256, NB_LDS_BYTES, s>>>(N, args...);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// k_node_pack under the current mode (absent matrices: nullptr, their slots are left as they are)
+static int node_pack(void *stream, const float *W0, const float *W1, const float *W2, const float *W3, const float *W4, const float *W5, void *image) {
+    return by_mode([&](auto f16) {
+        k_node_pack<decltype(f16)::value><<<NB_MATS * 4 * 8, 64, 0, (hipStream_t)stream>>>(W0, W1, W2, W3, W4, W5, (i32x4 *)image);
+        LAUNCH_CHECK();
+        return 0;
+    });
+}
+
 extern "C" int csplat_gnn_node_update_pack(void *stream, const float *Wa, const float *Wx, const float *W2, const float *W3, const float *Wi_next,
                                            const float *Wj_next, void *image) {
     CSPLAT_REQUIRE(Wa && Wx && W2 && W3 && image && (Wi_next == nullptr) == (Wj_next == nullptr), "csplat_gnn_node_update_pack: bad arguments");
-    CSPLAT_REQUIRE(((uintptr_t)image & 15u) == 0, "csplat_gnn_node_update_pack: the image must be 16-byte aligned");
-    if (g_em_mode == 0) k_node_pack<true><<<NB_MATS * 4 * 8, 64, 0, (hipStream_t)stream>>>(Wa, Wx, W2, W3, Wi_next, Wj_next, (i32x4 *)image);
-    else k_node_pack<false><<<NB_MATS * 4 * 8, 64, 0, (hipStream_t)stream>>>(Wa, Wx, W2, W3, Wi_next, Wj_next, (i32x4 *)image);
-    LAUNCH_CHECK();
-    return 0;
+    CSPLAT_REQUIRE(aligned16(image), "csplat_gnn_node_update_pack: the image must be 16-byte aligned");
+    return node_pack(stream, Wa, Wx, W2, W3, Wi_next, Wj_next, image);
 }
 
 extern "C" int csplat_gnn_node_update_packed(void *stream, int64_t N, const float *agg, const float *x, const void *image, const float *b0,
@@ -1166,27 +1093,13 @@ extern "C" int csplat_gnn_node_update_packed(void *stream, int64_t N, const floa
     CSPLAT_REQUIRE(N >= 0 && (N == 0 || (agg && x && image && b0 && b2 && b3 && ln_gamma && ln_beta && x_new)), "csplat_gnn_node_update_packed: bad arguments");
     CSPLAT_REQUIRE(!has_next || (xa_next && xb_next), "csplat_gnn_node_update_packed: next-layer outputs missing");
     CSPLAT_REQUIRE(x_new != x && x_new != agg, "csplat_gnn_node_update_packed: x_new must not alias an input (the residual reads x)");
-    const uintptr_t al = (uintptr_t)agg | (uintptr_t)x | (uintptr_t)image | (uintptr_t)b0 | (uintptr_t)b2 | (uintptr_t)b3 | (uintptr_t)ln_gamma |
-                         (uintptr_t)ln_beta | (uintptr_t)x_new | (uintptr_t)xa_next | (uintptr_t)xb_next;
-    CSPLAT_REQUIRE((al & 15u) == 0, "csplat_gnn_node_update_packed: operands must be 16-byte aligned");
+    CSPLAT_REQUIRE(aligned16(agg, x, image, b0, b2, b3, ln_gamma, ln_beta, x_new, xa_next, xb_next), "csplat_gnn_node_update_packed: operands must be 16-byte aligned");
     if (N == 0) return 0;
-    static int s_ok = -1;
-    if (s_ok < 0) {
-        s_ok = hipFuncSetAttribute((const void *)k_node_update_b3<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NB_LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_node_update_b3<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NB_LDS_BYTES) == hipSuccess;
-        (void)hipGetLastError();
-    }
-    CSPLAT_REQUIRE(s_ok, "csplat_gnn_node_update_packed: 78 KB of dynamic LDS refused by the runtime");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(PROF_GNN, s);
-    if (g_em_mode == 0)
-        k_node_update_b3<true><<<(unsigned)((N + 31) / 32), 256, NB_LDS_BYTES, s>>>(N, agg, x, (const i32x4 *)image, b0, b2, b3, ln_gamma, ln_beta, ln_eps,
-                                                                          has_next ? 1 : 0, x_new, xa_next, xb_next, piece_ptr);
-    else
-        k_node_update_b3<false><<<(unsigned)((N + 31) / 32), 256, NB_LDS_BYTES, s>>>(N, agg, x, (const i32x4 *)image, b0, b2, b3, ln_gamma, ln_beta, ln_eps,
-                                                                          has_next ? 1 : 0, x_new, xa_next, xb_next, piece_ptr);
-    LAUNCH_CHECK();
-    return 0;
+    return by_mode([&](auto f16) {
+        return chain_launch<k_node_update_b3<decltype(f16)::value>>(stream, "csplat_gnn_node_update_packed: 78 KB of dynamic LDS refused by the runtime", N, agg, x,
+                                                                    (const i32x4 *)image, b0, b2, b3, ln_gamma, ln_beta, ln_eps, has_next ? 1 : 0, x_new,
+                                                                    xa_next, xb_next, piece_ptr);
+    });
 }
 
 // MODE 2 of the same kernel as a stand-alone operator: out[m] = LayerNorm( W2 relu( W1 relu( W0 x[m] + b0 ) + b1 ) + b2 ) for NARROW input rows
@@ -1198,68 +1111,27 @@ extern "C" int csplat_gnn_mlp3_rows(void *stream, int64_t M, const float *x, int
                    "csplat_gnn_mlp3_rows: bad arguments (K a multiple of 4, 4 .. 128)");
     CSPLAT_REQUIRE(g_em_mode == 0, "csplat_gnn_mlp3_rows: mode 0 (fp16 pieces) only");
     if (M == 0) return 0;
-    const uintptr_t al = (uintptr_t)x | (uintptr_t)image | (uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)ln_gamma | (uintptr_t)ln_beta | (uintptr_t)out;
-    CSPLAT_REQUIRE((al & 15u) == 0, "csplat_gnn_mlp3_rows: operands must be 16-byte aligned");
-    static int s_ok = -1;
-    if (s_ok < 0) {
-        s_ok = hipFuncSetAttribute((const void *)k_edge_mlp3r<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ErCfg<true>::LDS_BYTES) == hipSuccess;
-        (void)hipGetLastError();
-    }
-    CSPLAT_REQUIRE(s_ok, "csplat_gnn_mlp3_rows: 141 KB of dynamic LDS refused by the runtime");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(PROF_GNN, s);
-    // (32-bit buffer offsets inside the kernel: 2^22 rows of 128 floats per launch, as csplat_gnn_edge_mlp3 -- longer inputs go out in chunks)
-    const int64_t CHUNK = (int64_t)1 << 22;
-    for (int64_t r0 = 0; r0 < M; r0 += CHUNK) {
-        const int64_t rows = M - r0 < CHUNK ? M - r0 : CHUNK;
-        const int64_t nst = (rows + 63) / 64;
-        k_edge_mlp3r<true, 2><<<(int)(nst < 256 ? nst : 256), 256, ErCfg<true>::LDS_BYTES, s>>>(rows, x + r0 * K, 1.0f, x_absmax, nullptr, nullptr, nullptr, nullptr,
-                                                                                               (const i32x4 *)image, b0, b1, b2, ln_gamma, ln_beta, ln_eps,
-                                                                                               out + r0 * EM_N, nullptr, nullptr, K,
-                                                                                               csplat_stamp_buffer((size_t)256 * 64));
-        LAUNCH_CHECK();
-    }
-    return 0;
+    CSPLAT_REQUIRE(aligned16(x, image, b0, b1, b2, ln_gamma, ln_beta, out), "csplat_gnn_mlp3_rows: operands must be 16-byte aligned");
+    return em_launch_chunks<true, 2>((hipStream_t)stream, "csplat_gnn_mlp3_rows: 141 KB of dynamic LDS refused by the runtime", M, x, K, 1.0f, x_absmax,
+                                     nullptr, nullptr, nullptr, nullptr, image, b0, b1, b2, ln_gamma, ln_beta, ln_eps, out, nullptr, nullptr);
 }
 
 // ---- csplat_gnn_rows_chain: k_rows_chain (above).  mode 0: out_a = x Wa^T, out_b = x Wb^T; mode 1: out_a = relu(W1 relu(W0 x + b0) + b1).
 // The image (csplat_gnn_node_update_image_bytes bytes) is packed under the current csplat_gnn_edge_mlp3_mode and must be used under it.
 extern "C" int csplat_gnn_rows_chain_pack(void *stream, int mode, const float *Wfirst, const float *Wsecond, void *image) {
-    CSPLAT_REQUIRE((mode == 0 || mode == 1) && Wfirst && Wsecond && image && ((uintptr_t)image & 15u) == 0, "csplat_gnn_rows_chain_pack: bad arguments");
-    const float *W1 = mode == 0 ? Wsecond : nullptr, *W2 = mode == 1 ? Wsecond : nullptr;
-    if (g_em_mode == 0) k_node_pack<true><<<NB_MATS * 4 * 8, 64, 0, (hipStream_t)stream>>>(Wfirst, W1, W2, nullptr, nullptr, nullptr, (i32x4 *)image);
-    else k_node_pack<false><<<NB_MATS * 4 * 8, 64, 0, (hipStream_t)stream>>>(Wfirst, W1, W2, nullptr, nullptr, nullptr, (i32x4 *)image);
-    LAUNCH_CHECK();
-    return 0;
+    CSPLAT_REQUIRE((mode == 0 || mode == 1) && Wfirst && Wsecond && image && aligned16(image), "csplat_gnn_rows_chain_pack: bad arguments");
+    return node_pack(stream, Wfirst, mode == 0 ? Wsecond : nullptr, mode == 1 ? Wsecond : nullptr, nullptr, nullptr, nullptr, image);
 }
 extern "C" int csplat_gnn_rows_chain(void *stream, int64_t N, int mode, const float *x, const void *image, const float *b0, const float *b1,
                                      float *out_a, float *out_b) {
     CSPLAT_REQUIRE(N >= 0 && (mode == 0 || mode == 1) && (N == 0 || (x && image && out_a)) && (mode == 1 || out_b || N == 0),
                    "csplat_gnn_rows_chain: bad arguments");
     CSPLAT_REQUIRE(out_a != x && out_b != x, "csplat_gnn_rows_chain: the outputs must not alias x");
-    const uintptr_t al = (uintptr_t)x | (uintptr_t)image | (uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)out_a | (uintptr_t)out_b;
-    CSPLAT_REQUIRE((al & 15u) == 0, "csplat_gnn_rows_chain: operands must be 16-byte aligned");
+    CSPLAT_REQUIRE(aligned16(x, image, b0, b1, out_a, out_b), "csplat_gnn_rows_chain: operands must be 16-byte aligned");
     if (N == 0) return 0;
-    static int s_ok = -1;
-    if (s_ok < 0) {
-        s_ok = hipFuncSetAttribute((const void *)k_rows_chain<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NB_LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_rows_chain<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NB_LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_rows_chain<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NB_LDS_BYTES) == hipSuccess;
-        s_ok &= hipFuncSetAttribute((const void *)k_rows_chain<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NB_LDS_BYTES) == hipSuccess;
-        (void)hipGetLastError();
-    }
-    CSPLAT_REQUIRE(s_ok, "csplat_gnn_rows_chain: 78 KB of dynamic LDS refused by the runtime");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(PROF_GNN, s);
-    const unsigned grid = (unsigned)((N + 31) / 32);
-    const i32x4 *im = (const i32x4 *)image;
-    if (g_em_mode == 0) {
-        if (mode == 0) k_rows_chain<true, 0><<<grid, 256, NB_LDS_BYTES, s>>>(N, x, im, b0, b1, out_a, out_b);
-        else k_rows_chain<true, 1><<<grid, 256, NB_LDS_BYTES, s>>>(N, x, im, b0, b1, out_a, out_b);
-    } else {
-        if (mode == 0) k_rows_chain<false, 0><<<grid, 256, NB_LDS_BYTES, s>>>(N, x, im, b0, b1, out_a, out_b);
-        else k_rows_chain<false, 1><<<grid, 256, NB_LDS_BYTES, s>>>(N, x, im, b0, b1, out_a, out_b);
-    }
-    LAUNCH_CHECK();
-    return 0;
+    auto run = [&](auto f16, auto md) {
+        return chain_launch<k_rows_chain<decltype(f16)::value, decltype(md)::value>>(stream, "csplat_gnn_rows_chain: 78 KB of dynamic LDS refused by the runtime", N, x,
+                                                                                    (const i32x4 *)image, b0, b1, out_a, out_b);
+    };
+    return by_mode([&](auto f16) { return mode == 0 ? run(f16, int_c<0>{}) : run(f16, int_c<1>{}); });
 }

@@ -33,6 +33,39 @@ __device__ __forceinline__ float l128_half_sum(float v) {
 }
 constexpr int GK = 128, GN = 128, WT_STRIDE = 129;   // W^T rows padded: conflict-free transposed staging
 
+// LayerNorm statistics of a 32-row x 128 tile that four waves hold in the MFMA C/D layout (wave w = columns 32w .. 32w + 31, lane r32 =
+// column, register r <-> tile row (r & 3) + 8 (r >> 2) + 4h): per register the mean and 1 / sqrt(biased variance + eps) of its row.
+// Two passes (sum, then squares about the mean), each a half-wave sum per wave joined across the waves through s_part[pass][row][wave].
+// Holds TWO workgroup barriers: every wave of the workgroup calls it, and what the waves did before it is complete behind the first.
+// The results go to each(r, mean, rstd) register by register, so that the caller's use of a row's rstd follows its LDS read directly
+// (all 16 handed back as an array cost k_linear128_rows32<true> 32 registers and a wave of occupancy).
+template <class Each>
+__device__ __forceinline__ void l128_tile_ln_stats(const float (&v)[16], float (*s_part)[32][4], int w, int h, int r32, float eps, Each &&each) {
+    float mean[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        float sum = v[r];
+        sum = l128_half_sum(sum);
+        if (r32 == 0) s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sum;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const float *p = s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h];
+        mean[r] = ((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN);
+        const float d = v[r] - mean[r];
+        float sq = d * d;
+        sq = l128_half_sum(sq);
+        if (r32 == 0) s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sq;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const float *p = s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h];
+        each(r, mean[r], rsqrtf(((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN) + eps));
+    }
+}
+
 // Epilogue options (all fused into the accumulator registers, no extra HBM pass):
 //   alpha     : out = alpha * (A @ W^T) + bias                (the 2^l edge-feature scale of graph_network.py:222)
 //   GATHER    : + ga[ia[row]][col] + gb[ib[row]][col]          (the x_i / x_j column blocks of the split first Linear)
@@ -434,32 +467,11 @@ __global__ __launch_bounds__(256) void k_linear128_rows32(int64_t M, const float
         if (relu) v[r] = relu_keep_nan(v[r]);
     }
     if (LN) {
-        float mean[16];
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            float sum = v[r];
-            sum = l128_half_sum(sum);
-            if (r32 == 0) s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sum;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const float *p = s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h];
-            mean[r] = ((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN);
-            const float d = v[r] - mean[r];
-            float sq = d * d;
-            sq = l128_half_sum(sq);
-            if (r32 == 0) s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sq;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const float *p = s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h];
-            const float rstd = rsqrtf(((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN) + eps);
+        l128_tile_ln_stats(v, s_part, w, h, r32, eps, [&](int r, float mean, float rstd) __attribute__((always_inline)) {
             const int64_t srow = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (ln_stats && w == 0 && r32 == 0 && srow < M) ln_stats[srow] = make_float2(mean[r], rstd);
-            v[r] = (v[r] - mean[r]) * rstd * gcol + becol;
-        }
+            if (ln_stats && w == 0 && r32 == 0 && srow < M) ln_stats[srow] = make_float2(mean, rstd);
+            v[r] = (v[r] - mean) * rstd * gcol + becol;
+        });
     }
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -582,41 +594,23 @@ __global__ __launch_bounds__(256) void k_node_update(int64_t N, const float *__r
     // ---- layer 2 + LayerNorm + residual
     load_act(X);
     acc = mma(W3, Wi, X, zero());
-    float v[16], mean[16];
+    float v[16];
     {
         const float bv = b3[col];
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            v[r] = acc[r] + bv;
-            float sum = v[r];
-            sum = l128_half_sum(sum);
-            if (r32 == 0) s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sum;
-        }
+        for (int r = 0; r < 16; r++) v[r] = acc[r] + bv;
     }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const float *p = s_part[0][(r & 3) + 8 * (r >> 2) + 4 * h];
-        mean[r] = ((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN);
-        const float d = v[r] - mean[r];
-        float sq = d * d;
-        sq = l128_half_sum(sq);
-        if (r32 == 0) s_part[1][(r & 3) + 8 * (r >> 2) + 4 * h][w] = sq;
-    }
-    __syncthreads();                          // (also: every wave is done reading s_act)
     {
         const float gcol = gamma[col], becol = beta[col];
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
+        // (the barriers inside also: every wave is done reading s_act)
+        l128_tile_ln_stats(v, s_part, w, h, r32, eps, [&](int r, float mean, float rstd) __attribute__((always_inline)) {
             const int trow = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float *p = s_part[1][trow];
-            const float rstd = rsqrtf(((p[0] + p[1]) + (p[2] + p[3])) * (1.f / GN) + eps);
             const int64_t orow = tile * 32 + trow;
             const int64_t crow = orow < N ? orow : N - 1;
-            const float o = (v[r] - mean[r]) * rstd * gcol + becol + x[crow * GN + col];
+            const float o = (v[r] - mean) * rstd * gcol + becol + x[crow * GN + col];
             if (orow < N) x_new[orow * GN + col] = o;
             s_act[trow][col] = o;
-        }
+        });
     }
     if (Wi == nullptr) return;                // (uniform)
     __syncthreads();

@@ -64,13 +64,18 @@ def test_constants_of_the_hip_file_are_the_ones_the_reference_assumes(src):
     assert int(_one(src, r"constexpr int ER_TILE_P = (\d+) \* EM_STRIDE;")) == R.TILE
     assert int(_one(src, r"nst = \(rows \+ 63\) / (\d+);")) == R.STEP_ROWS == 2 * R.TILE
     assert {int(v) for v in re.findall(r"nst < (\d+) \? nst : (\d+)", src)[0]} == {R.GRID_CAP}
-    assert len(re.findall(r"nst < 256 \? nst : 256", src)) == 2          # (the edge entry and the narrow-row entry)
+    # one chunked launcher, em_launch_chunks, for the edge entry and the narrow-row entry: one grid rule, one chunk size, and both reach it
+    assert len(re.findall(r"nst < 256 \? nst : 256", src)) == 1 and len(re.findall(r"\bCHUNK = ", src)) == 1
+    assert len(re.findall(r"return em_launch_chunks<", src)) == 2 and "return em_launch_chunks<true, 2>(" in src
     assert R.NO_LOOP_ROWS == 16384
-    assert [int(_one(src, r"\? v : \(int64_t\)1 << (\d+);")), int(_one(src, r"const int64_t CHUNK = \(int64_t\)1 << (\d+);"))] == [22, 22]
+    assert int(_one(src, r"\? v : \(int64_t\)1 << (\d+);")) == 22 and int(_one(src, r"v <= \(\(int64_t\)1 << (\d+)\)")) == 22
     assert 1 << 22 == R.CHUNK_ROWS
     assert _one(src, r"static constexpr int NP = F16 \? (\d) : (\d);") == (str(R.NP["f16"]), str(R.NP["bf16"]))
     assert _one(src, r"static constexpr int NPROD = F16 \? (\d) : (\d);") == (str(R.NPROD["f16"]), str(R.NPROD["bf16"]))
-    assert _one(src, r"constexpr int NP = F16 \? (\d) : (\d), NPROD = F16 \? (\d) : (\d);") == ("2", "3", "3", "6")      # (the node kernels)
+    # those two lines are Piece<F16>'s, the only place that says them: the edge kernel's ErCfg and the node kernels' PieceChain take them from it
+    assert len(re.findall(r"NP = F16 \?", src)) == 1 and len(re.findall(r"NPROD = F16 \?", src)) == 1
+    assert "static constexpr int NP = Piece<F16>::NP, NPROD = Piece<F16>::NPROD;" in src      # (ErCfg)
+    assert "typedef Piece<F16> P;\n    static constexpr int NP = P::NP, NPROD = P::NPROD;" in src      # (PieceChain)
     for kind in ("f16", "bf16"):       # NPROD = the number of (i, j) with i + j <= NP - 1
         n = R.NP[kind]
         assert sum(1 for i in range(n) for j in range(n) if i + j <= n - 1) == R.NPROD[kind]
