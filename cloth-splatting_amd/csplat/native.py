@@ -122,6 +122,9 @@ EXPORTS = {
     "csplat_obs_voxel_temp_bytes": (_sz, [_i64]),
     "csplat_obs_voxel": (_i, [_vp, _i64, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csplat_obs_mark": (_i, [_vp, _i64, _i, _i, _vp, _vp, _f, _vp]),
+    "csplat_zb_mesh": (_i, [_vp, _i, _i64, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "csplat_zb_points": (_i, [_vp, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz]),
+    "csplat_zb_mark": (_i, [_vp, _i, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "csplat_traj_smooth": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "csplat_traj_features": (_i, [_vp, _i, _i, _i64, _vp, _vp, _f, _vp, _vp, _vp]),
     "csplat_delaunay_temp_bytes": (_i, [_i, C.POINTER(_sz)]),

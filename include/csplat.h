@@ -28,6 +28,9 @@
  *   csplat_obs_unproject, csplat_obs_voxel, csplat_obs_mark
  *       the host-side observation code: get_world_coords (manipulation/envs/camera_utils.py:106-133, manipulation/deform_mesh.py:168-195)
  *       and get_observable_particle_index (camera_utils.py:136-162); the voxel grid thins the cloud before node sampling.
+ *   csplat_zb_mesh, csplat_zb_points, csplat_zb_mark
+ *       what a depth camera sees of the mesh: the Blender renders of manipulation/fold_rendering/ and the pixel loop
+ *       build_depth_from_pointcloud (manipulation/envs/camera_utils.py:7-41), as an exact z-buffer on the device.
  *   csplat_gnn_*
  *       the torch_geometric MessagePassing gather / scatter-add inside InteractionNetwork.propagate,
  *       meshnet/graph_network.py:173-174 (gather x_i, x_j: PyG __lift__), :197 (concat), :136 (aggr='add').
@@ -836,6 +839,61 @@ size_t csplat_obs_voxel_temp_bytes(int64_t M);
 int csplat_obs_voxel(void *stream, int64_t M, const float *points, float voxel, const float *origin /* device, or NULL */, float *centroid,
                      int32_t *count, int32_t *inverse, int32_t *n_voxels, int32_t *n_outside, void *temp);
 int csplat_obs_mark(void *stream, int64_t Q, int K, int N, const int32_t *idx, const float *d2, float max_sq_dist, uint8_t *flags);
+
+/* Mesh z-buffer, the arrow mesh -> image (csplat_zbuffer.hip): what a depth camera would see of a triangle mesh -- depth, silhouette and
+ * face-id images of V views -- and of a point cloud as one-pixel primitives.  The reference answers this on the host: Blender renders
+ * (manipulation/fold_rendering/), the Python double loop build_depth_from_pointcloud (manipulation/envs/camera_utils.py:7-41) and the guess
+ * of get_observable_particle_index.  An observation: no gradients.  Every output is a pure function of the inputs: coverage is exact integer
+ * arithmetic, the only atomic is a 64-bit unsigned integer minimum (independent of the order of arrival), NO float atomics: every output
+ * is bit-reproducible run to run.  Float arithmetic without contraction, every operation one float32 rounding, `/` and sqrt correctly rounded.
+ * Every entry validates its arguments before any launch (a bad one returns non-zero and csplat_last_error() names the entry): sizes out of
+ * range, NULL operands, operands that are not 4-byte aligned (screen and temp: 16), an output or `temp` that shares a byte with another
+ * operand.  Sizes: 0 <= V <= 65535, H, W >= 0, V * H * W < 2^31, 0 <= N, M, F < 2^31, V * N < 2^31; V * H * W == 0 writes nothing and F == 0
+ * gives images that are all holes.  NO CLIPPING: a face with a corner behind `near` is dropped whole (the cloth is in front of the camera).
+ *
+ * Cameras as csplat_obs_unproject takes them, mirrored: intrinsics [V][4] = (fx, fy, cx, cy) in pixel units, pixel centres at the
+ * integers; world_to_cam [V][3][4] row-major, column-vector form (p_cam = R p_world + t, t the fourth column).  vertices [N][3]
+ * (per_view 0: one mesh for all views) or [V][N][3] (per_view 1); faces [F][3] int32.  near finite and >= 0.
+ *   Stage P, per (view, vertex): p_cam[r] = R[r][0] X + R[r][1] Y + R[r][2] Z + t[r], summed left to right;  px = (fx * x) / z + cx,
+ *   py = (fy * y) / z + cy, iz = 1 / z.  The vertex is VALID when x, y, z, px, py and iz are finite, z > near, |px| <= 16384 and
+ *   |py| <= 16384.  Snapped coordinates sx = rint(256 px), sy = rint(256 py) as int32, round-half-even.  screen [V][N][4] int32 =
+ *   (sx, sy, float bits of iz, valid); all four are 0 for an invalid vertex.
+ *   Stage D, per (view, face), in exact int64 arithmetic on the snapped corners 0, 1, 2: A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0).
+ *   A face with an invalid corner, a corner index outside [0, N) or A == 0 is dropped.  A < 0: corners 1 and 2 change places (the cloth is
+ *   two-sided).  For pixel (X, Y), P = (256 X, 256 Y), and for each directed edge a -> b of 0 -> 1, 1 -> 2, 2 -> 0 with dx = xb - xa,
+ *   dy = yb - ya:  E = dx (Py - ya) - dy (Px - xa).  The pixel is COVERED iff for all three edges E > 0, or E == 0 and (dy < 0, or
+ *   dy == 0 and dx > 0): the top-left rule, every pixel of a watertight mesh has one owner per layer.  E12, E20, E01 are the weights of
+ *   the (exchanged) corners 0, 1, 2 and sum to A.
+ *   Depth: b_i = (float)E_i / (float)A for the face's OWN corners i = 0, 1, 2 (the exchange undone), q = b0 iz0 + b1 iz1 + b2 iz2 summed
+ *   left to right, z = 1 / q: interpolating 1 / z is perspective-correct.  The nearest face wins; on equal float32 z the lower face index:
+ *   the per-pixel state is one uint64 key (float bits of z) << 32 | face, all-ones = background, initialised by the call itself on every
+ *   call, and the draw is atomicMin on it.
+ *   Outputs per view: depth [V][H][W] = z (kind 0) or z * sqrt(u u + w w + 1), u = (X - cx) / fx, w = (Y - cy) / fy (kind 1: the
+ *   distance along the pixel's ray, the inverse of csplat_obs_unproject's kind 1), 0 where no face covers the pixel (the hole convention
+ *   of csplat_obs_unproject); silhouette [V][H][W] 0 or 1; face_id [V][H][W] int32, -1 on the background; bary [V][3][H][W] or NULL: the
+ *   perspective-correct weights (b_i iz_i) / q in the face's corner order, 0 on the background; screen or NULL (then it lives in temp).
+ * Launches: k_zb_project, k_zb_clear (16-byte stores), k_zb_draw -- one workgroup of four waves per (view, face), the waves stride over
+ * the 8 x 8-pixel blocks of the bounding box clipped to the image, 64 lanes = one block, a block wholly outside one edge is skipped -- and
+ * k_zb_resolve per pixel, which reads the key's z and recomputes the winner's weights with the same operations; plain stores.
+ * temp: temp_bytes >= align256(8 V H W) + align256(16 V n) bytes of device memory (n = N or M, align256 rounds up to a multiple of 256;
+ * csplat.zbuffer.temp_bytes computes it -- the library exports no size query and refuses a smaller temp_bytes), no initial state.
+ *
+ * csplat_zb_points: points [M][3] or [V][M][3] as one-pixel primitives (build_depth_from_pointcloud): the same stage P and validity; the
+ * pixel is (rint(px), rint(py)), round-half-even, and a point outside the image is dropped; the same key with z = p_cam.z and the point
+ * index in the low word, so the nearest point wins and a tie goes to the lower index; the same resolve writes depth [V][H][W] and
+ * point_id [V][H][W] (int32, -1: none).
+ *
+ * csplat_zb_mark: face_id [V][H][W], faces [F][3] -> face_visible [V][F] and node_visible [V][N] (uint8): 1 iff some pixel of the view
+ * holds the face, respectively a face with that corner, else 0.  The entry zeroes the flags on the stream, then every writer stores the
+ * same byte: plain stores.  Ids outside [0, F) (the -1 of the background) and corners outside [0, N) mark nothing; V * F < 2^31.
+ * Added exports: CSPLAT_ABI_VERSION is unchanged. */
+int csplat_zb_mesh(void *stream, int V, int64_t N, int64_t F, int H, int W, const float *vertices, int per_view, const int32_t *faces,
+                   const float *intrinsics, const float *world_to_cam, float near, int kind, float *depth, float *silhouette, int32_t *face_id,
+                   float *bary /* or NULL */, int32_t *screen /* or NULL */, void *temp, size_t temp_bytes);
+int csplat_zb_points(void *stream, int V, int64_t M, int H, int W, const float *points, int per_view, const float *intrinsics,
+                     const float *world_to_cam, float near, int kind, float *depth, int32_t *point_id, void *temp, size_t temp_bytes);
+int csplat_zb_mark(void *stream, int V, int64_t N, int64_t F, int H, int W, const int32_t *face_id, const int32_t *faces, uint8_t *face_visible,
+                   uint8_t *node_visible);
 
 /* Trajectory preprocessing, the step between the sensing end and the planner (csplat_traj_smooth in csplat_knn.hip, csplat_traj_features in
  * csplat_trajectory.hip): what turns a tracked cloud [T][N][3] into the smoothed positions, velocities and per-frame edge features the GNN and
